@@ -16,6 +16,11 @@ Other BASELINE configs (parity cases; each prints one JSON line of the same shap
                ranks with the frame reassembled on rank 0 (the only place a collective is on the data path)
   --config 5   frame format, BlockLinked 64 KiB blocks: one dependency chain (a stress, not a throughput path)
 
+A plain run sets up, warms up, times the steps, checks the round trip on the device and prints the line; `--full` adds
+everything else the line used to carry: the CPU baselines, the oracle's checks, other configurations and batch sizes under
+`other_configs`, and roofline.traffic measured in the run.  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64, under 64 MB); the inputs are a function of the arguments, so two builds can be compared.
+
 Encoder: `--compress-mode fast` (default) is the throughput encoder (its own parse: a valid LZ4 block that lz4_flex's
 decoder returns to the input -- north_star's compress contract; ratio reported), `exact` reproduces lz4_flex's bytes.
 The decoder is bit-exact in either case.  Multi-GPU: blocks are independent, so ranks own disjoint block ranges (weak
@@ -113,12 +118,20 @@ def main():
     ap.add_argument("--only", choices=["both", "compress", "decompress"], default="both",
                     help="profiling aid: run only one kernel in the timed steps (value then covers that kernel only)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="the default line measures roofline.traffic of the dominant kernel in this run (two rocprofv3 --pmc passes of a "
-                         "short compress-only child run, ~30 s); this switches that off (the figure then comes from profiles/traffic.json)")
+                    help="with --full, the default line measures roofline.traffic of the dominant kernel in this run (two rocprofv3 --pmc passes "
+                         "of a short compress-only child run, ~30 s); this switches that off (the figure then comes from profiles/traffic.json)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default line (config 2, one GPU) also runs configs 3, 4 and 5 for a few steps behind its timed loop and "
-                         "carries their figures under `other_configs`; this switches that off")
+                    help="with --full, the default line (config 2, one GPU) also runs configs 3, 4 and 5 for a few steps behind its timed loop "
+                         "and carries their figures under `other_configs`; this switches that off")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: CPU baselines, oracle checks, other configs and sizes, live HBM traffic. "
+                         "Without it a run sets up, warms up, times the steps, checks the round trip on the device and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, < 64 MB: "
+                         "per-block lengths, statuses and byte digests in full, the bytes of a fixed, seeded sample of blocks)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         relaunch_ranks(args.gpus)                  # does not return
 
@@ -161,10 +174,10 @@ def main():
         out = run_sharded_frame(args, env)
     else:
         out = run_linked_frame(args, env)
-    # The driver only runs the default line: the other BASELINE configs ride on it (one GPU, behind the headline's timed loop and its
-    # verification; a few steps each, the same code as `--config K`), so that their figures are driver-observed too
-    if (args.config == 2 and world == 1 and args.only == "both" and not args.blocks and not args.no_cpu_baseline and not args.no_other_configs
-            and not args.no_verify and not args.decompress_variant):
+    # With --full the other BASELINE configs ride on the default line (one GPU, behind the headline's timed loop and its
+    # verification; a few steps each, the same code as `--config K`)
+    if (args.full and args.config == 2 and world == 1 and args.only == "both" and not args.blocks and not args.no_cpu_baseline
+            and not args.no_other_configs and not args.no_verify and not args.decompress_variant):
         out["other_configs"] = other_configs(args, env)
         if not args.no_live_traffic:
             live_traffic(out, args)
@@ -239,7 +252,7 @@ def other_configs(args, env):
     res = {}
     for k, fn in ((3, run_blocks), (4, run_sharded_frame), (5, run_linked_frame)):
         a2 = copy.copy(args)
-        a2.config, a2.steps, a2.warmup, a2.blocks = k, 5, 2, 0
+        a2.config, a2.steps, a2.warmup, a2.blocks, a2.dump_outputs = k, 5, 2, 0, None
         t0 = time.perf_counter()
         try:
             env["torch"].cuda.empty_cache()
@@ -260,7 +273,7 @@ def other_configs(args, env):
     res["medium_batches"] = {}
     for cfg, nb in ((2, 4096), (2, 8192), (3, 4096)):
         a2 = copy.copy(args)
-        a2.config, a2.steps, a2.warmup, a2.blocks, a2.no_cpu_baseline = cfg, 5, 2, nb, True
+        a2.config, a2.steps, a2.warmup, a2.blocks, a2.no_cpu_baseline, a2.dump_outputs = cfg, 5, 2, nb, True, None
         key = "%s_%d_blocks" % ("json" if cfg == 2 else "text", nb)
         try:
             env["torch"].cuda.empty_cache()
@@ -350,6 +363,90 @@ def timed(args, env, step):
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
     return elapsed
+
+
+# --------------------------------------------------------------------------------------- --dump-outputs
+# What the last timed step computed, for comparing two builds output for output: per block (or per 64 KiB chunk of a frame) its
+# length, status and a position-weighted byte sum, for every block; the bytes themselves for a fixed, seeded sample of blocks.
+DUMP_LIMIT = 64 * 10**6      # bytes over all files
+DUMP_SAMPLE = 64             # blocks / chunks whose bytes are written whole
+DUMP_SEED = 12345
+
+
+def sample_rows(n):
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+
+
+def weighted_sums(rows, lens):
+    """per row r: sum over i < lens[r] of (i + 1) * rows[r, i] -- exact in float64 for rows of up to 72 128 bytes (< 2**53)"""
+    import torch
+    w = torch.arange(1, rows.shape[1] + 1, dtype=torch.int64, device=rows.device)
+    out = []
+    for r0 in range(0, rows.shape[0], 256):
+        x = rows[r0:r0 + 256].to(torch.int64) * w
+        x.masked_fill_(w > lens[r0:r0 + 256, None].to(torch.int64), 0)
+        out.append(x.sum(1))
+    return torch.cat(out).to(torch.float64).cpu().numpy()
+
+
+def block_outputs(only, n, stride, comp, comp_len, c_status, back, back_len, d_status):
+    """configs 2 / 3: the compressed blocks (at `stride`) with their lengths and statuses, the decompressed blocks likewise"""
+    import numpy as np
+    import torch
+    idx = sample_rows(n)
+    t_idx = torch.from_numpy(idx).to(comp.device)
+    out = {"sample_blocks": idx.astype(np.float64)}
+    if only in ("both", "compress"):
+        clen = comp_len.clamp(0, stride)
+        rows = comp[:n * stride].view(n, stride)
+        h_len, h_rows = clen[t_idx].cpu().numpy(), rows[t_idx].cpu().numpy()
+        out["compressed_len"] = comp_len.cpu().numpy().astype(np.float64)
+        out["compress_status"] = c_status.cpu().numpy().astype(np.float64)
+        out["compressed_digest"] = weighted_sums(rows, clen)
+        out["compressed_sample"] = np.concatenate([h_rows[j, :h_len[j]] for j in range(len(idx))]).astype(np.float32)
+    if only in ("both", "decompress"):
+        rows = back[:n * BLOCK].view(n, BLOCK)
+        out["decompressed_len"] = back_len.cpu().numpy().astype(np.float64)
+        out["decompress_status"] = d_status.cpu().numpy().astype(np.float64)
+        out["decompressed_digest"] = weighted_sums(rows, back_len.clamp(0, BLOCK))
+        out["decompressed_sample"] = rows[t_idx].cpu().numpy().astype(np.float32)
+    return out
+
+
+def byte_outputs(name, buf):
+    """a byte buffer (uint8 tensor or bytes) cut into 64 KiB chunks: its length, every chunk's digest, the bytes of the sampled
+    chunks (past the end: -1)"""
+    import numpy as np
+    import torch
+    if isinstance(buf, (bytes, bytearray)):
+        buf = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8).copy())
+    size = int(buf.numel())
+    nch = max(1, -(-size // BLOCK))
+    if size != nch * BLOCK:
+        padded = torch.zeros(nch * BLOCK, dtype=torch.uint8, device=buf.device)
+        padded[:size] = buf
+        buf = padded
+    rows = buf.contiguous().view(nch, BLOCK)
+    lens = torch.full((nch,), BLOCK, dtype=torch.int64, device=buf.device)
+    lens[-1] = size - (nch - 1) * BLOCK
+    idx = sample_rows(nch)
+    sample = rows[torch.from_numpy(idx).to(buf.device)].cpu().numpy().astype(np.float32)
+    h_lens = lens.cpu().numpy()
+    for j, r in enumerate(idx):
+        sample[j, h_lens[r]:] = -1
+    return {name + "_len": np.array([size], dtype=np.float64), name + "_digest": weighted_sums(rows, lens),
+            name + "_sample_chunks": idx.astype(np.float64), name + "_sample": sample}
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes, more than %d" % (total, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # --------------------------------------------------------------------------------------- configs 2 and 3: block batches
@@ -473,7 +570,9 @@ def run_blocks(args, env):
         "kernels": kernels,
         "verified": "NOT VERIFIED (--no-verify)" if args.no_verify else "round trip bit-exact on device; all per-block status 0",
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs and rank == 0:      # before the --full legs below: they reuse comp / back
+        write_outputs(args.dump_outputs, block_outputs(args.only, n, stride, comp, comp_len, c_status, back, back_len, d_status))
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             stash = {}
             out["cpu_baseline"] = cpu_baseline(src, comp, comp_off, comp_len, n, args.compress_mode, stash)
@@ -536,8 +635,12 @@ def run_sharded_frame(args, env):
         exp = workloads.log_stream(lo * bs, (hi - lo) * bs, device=dev)
         assert torch.equal(state["out"], exp), "sharded frame round trip mismatch"
     total = per_rank * world
+    if args.dump_outputs and rank == 0:
+        outs = byte_outputs("decompressed", state["out"])
+        outs.update(byte_outputs("frame", state["frame"]))
+        write_outputs(args.dump_outputs, outs)
     oracle_checked = None
-    if rank == 0 and not args.no_verify and total <= (2 << 30):
+    if args.full and rank == 0 and not args.no_verify and total <= (2 << 30):
         # the gathered frame through the REFERENCE's frame decoder (oracle restatement), once, after the timed loop
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_api as O
@@ -555,7 +658,7 @@ def run_sharded_frame(args, env):
     # by 64 KiB ("compress_sliding_window" 0: round 3's bytes, every byte indexed once) and by 32 KiB (1: round 4's default, every byte
     # indexed twice) are timed beside it, outside the reported value.
     windows_64k = windows_32k = None
-    if world == 1 and not args.no_verify and args.compress_mode != "exact":
+    if args.full and world == 1 and not args.no_verify and args.compress_mode != "exact":
         from lz4_flex_amd import _lib as L
         lib = L.load()
         default = lib.lz4flex_get_tuning(None, b"compress_sliding_window")
@@ -598,7 +701,7 @@ def run_sharded_frame(args, env):
         "verified": "NOT VERIFIED" if args.no_verify else "every rank's decoded block range equals the stream bytes it owns" +
                     ("; " + oracle_checked if oracle_checked else ""),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline_buffer(local[:64 * bs], bs)
         except Exception as e:
@@ -627,9 +730,14 @@ def run_linked_frame(args, env):
         state["back"] = F.decompress_frame(fr, len(data))[0]
 
     elapsed = timed(args, env, step)
+    if args.dump_outputs and rank == 0:
+        outs = byte_outputs("decompressed", state["back"])
+        outs.update(byte_outputs("frame", state["frame"]))
+        write_outputs(args.dump_outputs, outs)
     oracle_checked = None
     if not args.no_verify:
         assert state["back"] == data
+    if args.full and not args.no_verify:
         # the reference's FrameDecoder (oracle restatement) over the frame the GPU wrote, once, after the timed loop
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_api as O
@@ -643,7 +751,7 @@ def run_linked_frame(args, env):
     # own).  The same data also goes through the reference-exact chain encoder (lz4_flex's bytes) and back, outside the timed loop:
     # that is what the reference's own byte stream costs on this design.
     dep = None
-    if rank == 0 and not exact and not args.no_verify:
+    if args.full and rank == 0 and not exact and not args.no_verify:
         try:
             block.set_compress_mode("exact")
             t0 = time.perf_counter(); fr_x = F.compress_frame(data, fi); torch.cuda.synchronize(); t1 = time.perf_counter()
@@ -659,13 +767,13 @@ def run_linked_frame(args, env):
         finally:
             block.set_compress_mode(args.compress_mode)
     many = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             many = many_linked_streams(args, env, plain)
         except Exception as e:
             many = {"error": repr(e)}
-    base = {"note": "--no-cpu-baseline"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    base = {"note": "--no-cpu-baseline" if args.full else "--full not given"}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             base = cpu_baseline_linked(data)
         except Exception as e:
@@ -686,7 +794,7 @@ def run_linked_frame(args, env):
                    "blocks": n, "compress_mode": args.compress_mode},
         "ratio": round(len(state["frame"]) / len(data), 5),
         "roofline": dict(roof(alg, elapsed / args.steps), kernel=("lz4_compress_chain_kernel" if exact else "lz4_compress_wave_kernel") + " + lz4_decompress_pcd_kernel (chained batch)"),
-        "verified": "NOT VERIFIED" if args.no_verify else "frame round trip bit-exact; " + oracle_checked,
+        "verified": "NOT VERIFIED" if args.no_verify else "frame round trip bit-exact" + ("; " + oracle_checked if oracle_checked else ""),
         "dependency_carrying_frame": dep,
         "many_streams": many,
         "cpu_baseline": base,

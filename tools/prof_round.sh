@@ -11,8 +11,8 @@ mkdir -p $OUT
 for c in $CONFIGS; do
   extra=""
   [ "$c" = "5" ] && extra="--steps 3 --warmup 1"
-  timeout 300 python bench.py --config $c > $OUT/bench_line_config$c.json 2> $OUT/bench_config$c.err      # (the bench line: default steps)
-  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_config$c -o t -- python bench.py --config $c --no-cpu-baseline $extra > $OUT/trace_config$c.log 2>&1
+  timeout 300 python bench.py --config $c --full > $OUT/bench_line_config$c.json 2> $OUT/bench_config$c.err      # (the bench line: default steps)
+  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_config$c -o t -- python bench.py --config $c --no-cpu-baseline --full $extra > $OUT/trace_config$c.log 2>&1
   if [ "$c" = "2" ]; then
     for only in compress decompress; do
       for set in FETCH_SIZE WRITE_SIZE; do
@@ -21,7 +21,7 @@ for c in $CONFIGS; do
     done
   else
     for set in FETCH_SIZE WRITE_SIZE; do
-      timeout 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pmc_config${c}_both_$set -o p -- python bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pmc_config${c}_both_$set.log 2>&1
+      timeout 150 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $OUT/pmc_config${c}_both_$set -o p -- python bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline --full > $OUT/pmc_config${c}_both_$set.log 2>&1
     done
   fi
 done
