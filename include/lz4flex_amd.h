@@ -217,7 +217,11 @@ int lz4flex_decompress_batch(lz4flex_ctx *ctx, const void *in_base, const uint64
 /* Optional per-block extras for decoding: an external dictionary (block::decompress_into_with_dict,
  * src/block/decompress.rs:462-468) and/or an initial sink position: the output region
  * [out_off, out_off+out_pos) already holds earlier bytes that matches may reference (the prefix mode
- * of Linked frames, src/frame/decompress.rs:293-306); out_len counts only the new bytes. */
+ * of Linked frames, src/frame/decompress.rs:293-306); out_len counts only the new bytes.  out_pos[i] <= out_cap[i] is required
+ * (out_cap counts from out_off, prefix included; out_pos == out_cap is legal and leaves room for an empty block only): a block
+ * with out_pos[i] > out_cap[i] gets status LZ4FLEX_E_INVALID_ARG, out_len 0 and detail 0, and nothing is written (the reference
+ * panics there, src/sink.rs:103-107); in a CHAINED batch it ends its chain as a decode error does.  The OutputTooSmall detail
+ * counts from out_off too, prefix included (src/block/decompress.rs:349-355,402-407): {expected, actual = out_cap}. */
 typedef struct lz4flex_decompress_ext {
     const void *dict_base;     /* nullable */
     const uint64_t *dict_off;
@@ -269,7 +273,8 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uin
  *   a piece cutter and the replay decoder's copy engine inside one workgroup (lz4_decompress_fused.hip: level with 4 on JSON, ahead on
  *   text, behind on incompressible data and runs; -DLZ4FLEX_TOOLS builds only since round 6), 9 = plan / replay
  *   (lz4_decompress_plan.hip + lz4_decompress_replay.hip; -DLZ4FLEX_TOOLS builds only since round 5: slower than 0 on every shape
- *   measured), 1 = decoder whose window lives in HBM/L2 (always used for dictionary / prefix blocks); "decompress_blocks_per_wg" (variant 4: 0 = 64, the default at every batch size; 8/16/32: the older narrow geometries, tests); "decompress_lanes"
+ *   measured), 1 = decoder whose window lives in HBM/L2 (always used for dictionary blocks; prefix blocks without a dictionary go to 7, or
+ *   to 13 when 13 is pinned or picked and the batch is not chained); "decompress_blocks_per_wg" (variant 4: 0 = 64, the default at every batch size; 8/16/32: the older narrow geometries, tests); "decompress_lanes"
  *   (16; 8/32/64 in -DLZ4FLEX_ALL_VARIANTS builds, variant 1); exact encoder: "compress_lanes" (8/16 lanes of a wavefront per
  *   block), "compress_variant" (1 = group encoder + emitter wavefront; 3 = group encoder alone, -DLZ4FLEX_ALL_VARIANTS builds);
  *   "decompress_second_pass" (tests: 0 leaves the blocks that variants 7 ... 13 hand to the reference-order kernel marked with

@@ -100,6 +100,9 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
                                                 uint32_t out_pos, uint32_t cap, const uint8_t* __restrict__ dict,
                                                 uint32_t dict_len, uint32_t g, uint32_t* produced,
                                                 uint64_t* det_expected) {
+    // a sink position behind the sink's end: SliceSink::new panics (src/sink.rs:103-107) before anything is decoded.  The descriptors
+    // may live in device memory, so this is the only place it can be checked; unchecked, `cap - op` below would wrap
+    if (out_pos > cap) return LZ4FLEX_DEV_E_INVALID_ARG;
     if (ilen == 0u) return LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE;   // decompress.rs:207-209
     if (!USE_DICT) dict_len = 0u;
     uint32_t ip = 0u, op = out_pos;

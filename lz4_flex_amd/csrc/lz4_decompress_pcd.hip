@@ -30,7 +30,7 @@
 //
 // It diagnoses nothing: any irregularity (every DecompressError of src/block/mod.rs:82-98, a sink too small, an offset behind
 // the output, a tile that does not settle) marks the block, and lz4_decompress_blocks_kernel decodes it again in the
-// reference's check order and names the error (as behind lz4_decompress_wave.hip).  The host model of this algorithm is
+// reference's check order and names the error (as behind lz4_decompress_seq.hip).  The host model of this algorithm is
 // tests/sim/pcd_model.cpp (same walker: lz4_pcd_common.h; tests/test_pcd_model.py).  Every wait in here is bounded.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -658,6 +658,7 @@ __global__ void __launch_bounds__(G::T) lz4_decompress_pcd_kernel(DecompressArgs
     uint32_t OP = OP0;         // output position: everything before it is written back
     uint32_t hist = 0u;        // window bytes [0, hist) hold output [OP - hist, OP)
     bool ended = false, bad = a.debug_giveup == b + 1u;      // (tests: a block that gives up without an error of its own)
+    if (OP0 > X.cap) bad = true;                              // a sink position behind the sink's end: the reference-order kernel refuses it
     if (bad) ended = true;
     __syncthreads();
     PCD_PROF_DECL

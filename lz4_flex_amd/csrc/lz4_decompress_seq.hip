@@ -138,7 +138,7 @@ __device__ __forceinline__ uint32_t lds_rd4u(uint32_t a) {
     return __builtin_amdgcn_alignbyte(d1, d0, a & 3u);
 }
 
-// n (1..16) bytes of v to LDS, exactly (lz4_decompress_wave.hip write_exact16)
+// n (1..16) bytes of v to LDS, exactly (the write_exact16 of the wave decoder this kernel replaced)
 __device__ __forceinline__ void write_exact16(uint32_t dst, const u32x4& v, uint32_t n) {
     if (n >= 16u) { lds_wr16(dst, v); return; }
     const bool n8 = (n & 8u) != 0u, n4 = (n & 4u) != 0u, n2 = (n & 2u) != 0u;

@@ -9,6 +9,7 @@
 #define LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE 3
 #define LZ4FLEX_DEV_E_OFFSET_ZERO 4
 #define LZ4FLEX_DEV_E_OFFSET_OUT_OF_BOUNDS 5
+#define LZ4FLEX_DEV_E_INVALID_ARG 64        // a sink position behind the sink's end (out_pos > out_cap): the reference panics there
 
 struct lz4flex_ctx;
 

@@ -5,7 +5,7 @@
 // The decoder this belongs to handles FEW, LARGE blocks (and small batches): one workgroup per block.  Reference semantics:
 // src/block/decompress.rs:201-449.  It diagnoses nothing: a block with ANY irregularity (every DecompressError, a sink that
 // is too small, a chain that does not converge) is left marked for the reference-order kernel (lz4_decompress.hip), which
-// decodes it again and names the exact error -- as lz4_decompress_wave.hip does.
+// decodes it again and names the exact error -- as behind the sequence decoder (lz4_decompress_seq.hip).
 #pragma once
 #include <stdint.h>
 

@@ -43,6 +43,9 @@ def lib():
         o.lz4o_decompress_into_with_dict.restype = C.c_int64
         o.lz4o_decompress_into_with_dict.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p,
                                                      C.c_size_t, C.POINTER(ErrDetail)]
+        o.lz4o__decompress_internal.restype = C.c_int64
+        o.lz4o__decompress_internal.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, C.c_char_p,
+                                                C.c_size_t, C.POINTER(ErrDetail)]
         o.lz4o_does_token_fit.restype = C.c_int
         o.lz4o_does_token_fit.argtypes = [C.c_uint8]
         o.lz4o_count_same_bytes.restype = C.c_size_t
@@ -117,6 +120,24 @@ def decompress(data, cap, dict_data=None, prefill=None):
     if n < 0:
         return ERR_NAMES[-n], (int(d.expected), int(d.actual))
     return "ok", out.raw[:n]
+
+
+def decompress_prefix(data, prefix, cap, dict_data=None):
+    """the reference's decompress_internal with a sink that already holds `prefix` (src/block/decompress.rs:201-449 with
+    SliceSink::new(output, pos), src/sink.rs:103-107: Linked frames, lz4flex_decompress_batch_ex's out_pos).  `cap` counts from the
+    sink's start, prefix included, as the C ABI's out_cap does.  Returns ('ok', the new bytes) or (ErrName, (expected, actual)), the
+    OutputTooSmall detail absolute like cap."""
+    data, prefix = bytes(data), bytes(prefix)
+    if cap < len(prefix):
+        raise ValueError("cap %d < prefix %d: the reference panics (SliceSink::new)" % (cap, len(prefix)))
+    out = C.create_string_buffer(max(cap, 1))
+    C.memmove(out, prefix, len(prefix))
+    d = ErrDetail()
+    dd = b"" if dict_data is None else bytes(dict_data)
+    n = lib().lz4o__decompress_internal(data, len(data), out, len(prefix), cap, 0 if dict_data is None else 1, dd, len(dd), C.byref(d))
+    if n < 0:
+        return ERR_NAMES[-n], (int(d.expected), int(d.actual))
+    return "ok", out.raw[len(prefix):len(prefix) + n]
 
 
 def frame_info(content_size=None, block_size=0, block_mode=0, block_checksums=False, content_checksum=False):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import oracle_api as O
+from lz4_writer import Writer
 
 pytestmark = pytest.mark.gpu
 REDO = 0x7F000001
@@ -44,45 +45,6 @@ def _batch(block, ctx, comps, caps, slack=64, misalign=0):
     out = np.full(int(out_off[-1]) + caps[-1] + slack, 0xA5, dtype=np.uint8)
     ol, st, det = block.decompress_batch(inb, in_off, in_len, out, out_off, caps, ctx=ctx)
     return out, out_off, ol, st, det
-
-
-class Writer:
-    """an LZ4 block, sequence by sequence (src/block/compress.rs:463-487 is the layout), with the plain text the format's byte-wise
-    semantics give (decompress_safe.rs:93-247)"""
-
-    def __init__(self, seed=1):
-        self.comp, self.out, self.rnd = bytearray(), bytearray(), random.Random(seed)
-
-    def _len(self, v):
-        while v >= 255:
-            self.comp.append(255)
-            v -= 255
-        self.comp.append(v)
-
-    def seq(self, lit, off, ml):
-        lits = bytes(self.rnd.getrandbits(8) for _ in range(lit)) if isinstance(lit, int) else bytes(lit)
-        self.comp.append((min(len(lits), 15) << 4) | min(ml - 4, 15))
-        if len(lits) >= 15:
-            self._len(len(lits) - 15)
-        self.comp += lits
-        self.out += lits
-        assert 1 <= off <= len(self.out) and off <= 65535 and ml >= 4, (off, len(self.out), ml)
-        self.comp += bytes((off & 0xFF, off >> 8))
-        if ml - 4 >= 15:
-            self._len(ml - 19)
-        start = len(self.out) - off
-        for k in range(ml):
-            self.out.append(self.out[start + k])
-        return self
-
-    def end(self, lit=5):
-        lits = bytes(self.rnd.getrandbits(8) for _ in range(lit))
-        self.comp.append(min(lit, 15) << 4)
-        if lit >= 15:
-            self._len(lit - 15)
-        self.comp += lits
-        self.out += lits
-        return bytes(self.comp), bytes(self.out)
 
 
 def _blocks():
