@@ -245,7 +245,7 @@ __device__ __forceinline__ void index_chunk(const lds_u8* lp, lds_u16* tab, g_u8
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]), "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]) :: "memory");
 #pragma unroll
         for (uint32_t u = 0; u < 8u; ++u) {
-            const uint32_t x = __builtin_amdgcn_alignbyte((uint32_t)(xr[u] >> 32), (uint32_t)xr[u], lane & 3u);
+            const uint32_t x = __builtin_amdgcn_alignbyte((uint32_t)(xr[u] >> 32), (uint32_t)xr[u], lane);   // (shift: bits 1:0 of lane)
             h[u] = (x * 2654435761u) >> (32u - HBITS);
         }
 #pragma unroll
@@ -469,9 +469,11 @@ struct EncState {
 };
 
 // Lane-parallel encoding of the chosen sequences (lane k < npend: psq = match end << 16 | distance, psp = match start; the
-// literals of sequence 0 start at st.last_end) into the segment's body.  A sequence with >= 15 literals or a match of
-// >= 274 bytes needs length bytes beyond the lane-parallel form: such "hard" sequences are written one at a time by the whole
-// wavefront, each at the place the prefix sum gave it.  Runs once per ~4 supersteps, two call sites.
+// literals of sequence 0 start at st.last_end) into the segment's body.  The lane-parallel form takes at most one length byte on
+// either side: fewer than 270 literals (LIT_LANE) and a match of fewer than 274 bytes.  Anything longer is "hard" and written one
+// at a time by the whole wavefront (emit_generic), each at the place the prefix sum gave it.  Until round 6 every sequence with
+// >= 15 literals was hard: ~1 % of JSON's sequences, but each one a call with its spills around it.  Runs once per ~4 supersteps,
+// two call sites.
 #ifndef LZ4W_EXP_CALL_ENC       // inlined (round 6): JSON 3.44 -> 3.37 ms, text 4.67 -> 4.49 -- a call cost 16 scratch operations for callee-saved registers and six readfirstlanes
 __device__ __forceinline__
 #else
@@ -511,12 +513,14 @@ EncState encode_seqs(uint32_t psq, uint32_t psp, uint32_t npend_, uint8_t* body_
         const uint32_t se = psq >> 16, off = psq & 0xFFFFu, sp = psp;
         const uint32_t pe = dpp_wave_shr1(se, last_end);
         const uint32_t lit = sp - pe, len = se - sp, mlc = len - 4u;
-        const uint64_t hardm = __builtin_amdgcn_ballot_w64(issel & ((lit >= 15u) | (mlc >= 270u)));
+        constexpr uint32_t LIT_LANE = 15u + 255u;                       // literals with one length byte: 15 .. 269
+        const uint64_t hardm = __builtin_amdgcn_ballot_w64(issel & ((lit >= LIT_LANE) | (mlc >= 270u)));
         const bool first = (has == 0u) & (lane == 0u);                  // the segment's first sequence: its token comes later
         const uint32_t ext = mlc >= 15u ? 1u : 0u;
-        uint32_t size = issel ? ((first ? 2u : 3u + lit) + ext) : 0u;
-        if (hardm != 0ull) {                                            // the length bytes of the hard ones
-            const uint32_t more = (first ? 0u : len_ext_bytes(lit)) + len_ext_bytes(mlc) - ext;
+        const uint32_t lext = ((lit >= 15u) & !first) ? 1u : 0u;         // the literal length byte of a lane-parallel sequence
+        uint32_t size = issel ? ((first ? 2u : 3u + lit) + ext + lext) : 0u;
+        if (hardm != 0ull) {                                            // the further length bytes of the hard ones
+            const uint32_t more = (first ? 0u : len_ext_bytes(lit)) + len_ext_bytes(mlc) - ext - lext;
             size += __builtin_amdgcn_inverse_ballot_w64(hardm) ? more : 0u;
         }
         const uint32_t incl = wave_incl_add(size);
@@ -527,9 +531,19 @@ EncState encode_seqs(uint32_t psq, uint32_t psp, uint32_t npend_, uint8_t* body_
         if (__builtin_amdgcn_inverse_ballot_w64(ordm)) {
             uint32_t o = o0;
             if (!first) {
-                st_u8(body, o, (lit << 4) | (mlc < 15u ? mlc : 15u));
-                copy_lit_small(body, o + 1u, lds + L_WIN + pe, lit);
-                o += 1u + lit;
+                st_u8(body, o, ((lit < 15u ? lit : 15u) << 4) | (mlc < 15u ? mlc : 15u));
+                o += 1u;
+                if (lext) { st_u8(body, o, lit - 15u); o += 1u; }
+                uint32_t n = lit;
+                const lds_u8* src = lds + L_WIN + pe;
+                while (n >= 16u) {                                      // (lanes with >= 16 literals: a few per call, if any)
+                    u32x4 v;
+                    __builtin_memcpy(&v, (const void*)src, 16);
+                    __builtin_memcpy((void*)(body + o), &v, 16);
+                    src += 16; o += 16u; n -= 16u;
+                }
+                copy_lit_small(body, o, src, n);
+                o += n;
             }
             st_u16(body, o, off);
             if (ext) st_u8(body, o + 2u, mlc - 15u);
@@ -564,6 +578,9 @@ template <uint32_t V> struct UConst { static constexpr uint32_t value = V; };
 // measured, one more scalar instruction per superstep costs 13 cycles, one more vector instruction 6.  Hence the
 // compile-time superstep size (no masks for "step u is part of this superstep"), the hand-written walk, v_mbcnt's
 // accumulator operand, LDS addressed from 0 (the kernel checks), ...
+// tools/wave_phase_mix.py counts the listing per phase (profiles/r07_encoder_phase_budget.txt; static, every path once): heads 77
+// vector / 62 scalar, compaction + lengths 240 / 113, scan 24 / 11, walk 8 / 54, merge 65 / 44, encode_seqs + latch 172 / 67; the
+// indexer 7.6 vector + 3.1 LDS per 64-position step.  Dynamically a JSON superstep is ~350 vector instructions.
 __device__ __attribute__((noinline)) void match_segment(const uint8_t* __restrict__ cand_t_, uint8_t* body_, uint32_t w_, uint32_t lane,
                               uint32_t s0_, uint32_t s1_, uint32_t mfl_end_, uint32_t mend_, unsigned long long* prof_) {
     const uint32_t w = uni(w_), s0 = uni(s0_), s1 = uni(s1_), mfl_end = uni(mfl_end_), mend = uni(mend_);
@@ -590,13 +607,15 @@ __device__ __attribute__((noinline)) void match_segment(const uint8_t* __restric
     auto mbcnt = [&](uint64_t m, uint32_t base) -> uint32_t {      // bits of m below the lane + base
         return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, base));
     };
+    // v_alignbyte_b32 shifts by bits 1:0 of its third operand and ignores the rest; hipcc does not know that and spends a v_and on
+    // "pos & 3" (one per call), so the position goes in whole
     auto ld4 = [&](uint32_t pos) -> uint32_t {                     // 4 bytes at any position from two aligned dwords
         const lds_u32* ap = (const lds_u32*)(win + (pos & ~3u));
-        return __builtin_amdgcn_alignbyte(ap[1], ap[0], pos & 3u);
+        return __builtin_amdgcn_alignbyte(ap[1], ap[0], pos);
     };
     auto ld16a = [&](uint32_t pos) -> u32x4 {                      // 16 bytes at any position from five aligned dwords
         const lds_u32* ap = (const lds_u32*)(win + (pos & ~3u));
-        const uint32_t w0 = ap[0], w1 = ap[1], w2 = ap[2], w3 = ap[3], w4 = ap[4], sh = pos & 3u;
+        const uint32_t w0 = ap[0], w1 = ap[1], w2 = ap[2], w3 = ap[3], w4 = ap[4], sh = pos;   // (bits 1:0 of sh)
         u32x4 v;
         v.x = __builtin_amdgcn_alignbyte(w1, w0, sh); v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
         v.z = __builtin_amdgcn_alignbyte(w3, w2, sh); v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
@@ -678,12 +697,12 @@ __device__ __attribute__((noinline)) void match_segment(const uint8_t* __restric
         }
         // all 4-byte reads are issued before the first compare (one LDS round trip); lanes without a candidate read
         // something harmless.  Own side: dwords at b + 64 u + (lane & ~3), one address for all the steps.
-        const uint32_t lane3 = lane & 3u;                        // (recomputed per superstep: registers that live across the call of encode_seqs are scarce)
+        // (b is a multiple of 64: the shift is bits 1:0 of the lane, and the lane goes in whole -- see ld4)
         const lds_u32* own = (const lds_u32*)(win + (b + (lane & ~3u)));
         uint32_t a0 = 0u, a1 = 0u, a2 = 0u, a3 = 0u, g0 = 1u, g1 = 1u, g2 = 1u, g3 = 1u;
-        a0 = __builtin_amdgcn_alignbyte(own[1], own[0], lane3);
-        if (NS > 1u) a1 = __builtin_amdgcn_alignbyte(own[17], own[16], lane3);
-        if (NS > 2u) { a2 = __builtin_amdgcn_alignbyte(own[33], own[32], lane3); a3 = __builtin_amdgcn_alignbyte(own[49], own[48], lane3); }
+        a0 = __builtin_amdgcn_alignbyte(own[1], own[0], lane);
+        if (NS > 1u) a1 = __builtin_amdgcn_alignbyte(own[17], own[16], lane);
+        if (NS > 2u) { a2 = __builtin_amdgcn_alignbyte(own[33], own[32], lane); a3 = __builtin_amdgcn_alignbyte(own[49], own[48], lane); }
         g0 = ld4(p0 - t0);
         if (NS > 1u) g1 = ld4(p1 - t1);
         if (NS > 2u) { g2 = ld4(p2 - t2); g3 = ld4(p3 - t3); }
