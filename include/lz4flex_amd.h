@@ -75,9 +75,10 @@ const char *lz4flex_version(void);
 /* hash of the sources (csrc/ + include/ + compiler flags) this binary was built from; lz4_flex_amd/build.py
  * recomputes it from the tree, so a stale library is detectable */
 const char *lz4flex_build_id(void);
-/* The round of this header: 6.  Changes a caller built against an earlier header has to know: round 5 appended chain_prev / n_chains to
+/* The round of this header: 7.  Changes a caller built against an earlier header has to know: round 5 appended chain_prev / n_chains to
  * lz4flex_decompress_ext (read only for LZ4FLEX_MEM_DEVICE | LZ4FLEX_MEM_CHAINED batches; a struct of the four older members is fine for
- * every other call); round 6 removed "decompress_variant" 5 / 6 (the wave decoder; 13 took its place) and moved 12 to tools builds. */
+ * every other call); round 6 removed "decompress_variant" 5 / 6 (the wave decoder; 13 took its place) and moved 12 to tools builds;
+ * round 7 added lz4flex_decompressed_size_batch and the setting "size_scan_serial". */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -213,6 +214,22 @@ int lz4flex_decompress_batch(lz4flex_ctx *ctx, const void *in_base, const uint64
                              uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                              uint32_t *out_len, int32_t *status, uint64_t *detail, int mem_kind,
                              void *hip_stream);
+
+/* The decompressed sizes of n raw blocks (no size prefix, no frame): what block::decompress_into (src/block/decompress.rs:201-449)
+ * would return for block i = in_base[in_off[i] .. + in_len[i]) with a sink too large for OutputTooSmall and history[i] bytes in front
+ * of the block's output (the ext_dict_len of decompress_into_with_dict, or the out_pos of lz4flex_decompress_batch_ex's prefix form:
+ * it only decides the OffsetOutOfBounds check, :399-401; history NULL = 0).  out_size[i] = the NEW bytes the block produces, prefix not
+ * counted (u64: a block expands up to 255 x), status[i] = 0 or the first error in the reference's check order (LITERAL_OUT_OF_BOUNDS,
+ * EXPECTED_ANOTHER_BYTE -- the empty block too, :207-209 -- OFFSET_ZERO, OFFSET_OUT_OF_BOUNDS); out_size[i] = 0 when status[i] != 0.
+ * Nothing is decoded and nothing but out_size / status is written.  A block with status 0 and size S decodes with out_cap = S (and the
+ * same history) on every decoder configuration, to out_len S.  So a caller that holds raw blocks without their sizes runs this, an
+ * exclusive prefix sum of out_size for the out_off, and one lz4flex_decompress_batch with out_cap = out_size -- all of it on the device.
+ * mem_kind: LZ4FLEX_MEM_HOST (staged through the context, synchronous) or LZ4FLEX_MEM_DEVICE (every pointer device memory, asynchronous
+ * on hip_stream); LZ4FLEX_MEM_BIG_BLOCKS may be ORed in (a hint, results do not depend on it).  n == 0 returns 0.  Returns 0 or -code.
+ * Setting "size_scan_serial" (tests): 1 = every block is measured by the serial pass alone (lz4_size_scan.hip), 0 (default). */
+int lz4flex_decompressed_size_batch(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                    uint32_t n, const uint32_t *history, uint64_t *out_size, int32_t *status, int mem_kind,
+                                    void *hip_stream);
 
 /* Optional per-block extras for decoding: an external dictionary (block::decompress_into_with_dict,
  * src/block/decompress.rs:462-468) and/or an initial sink position: the output region

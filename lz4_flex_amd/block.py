@@ -300,3 +300,70 @@ def decompress_batch(in_buf, in_off, in_len, out_buf, out_off, out_cap, ctx=None
     if rc:
         raise DeviceError("lz4flex_decompress_batch failed (%d): %s" % (rc, L.last_error()))
     return out_len, status, detail
+
+
+def decompressed_size_batch(in_buf, in_off, in_len, history=None, ctx=None):
+    """lz4flex_decompressed_size_batch over host buffers: for raw blocks without their sizes, (size[u64], status[i32]) -- the bytes
+    decompress_into would produce with an unbounded sink and history[i] (None: 0) bytes in front of the block, or its error code (size
+    0).  Nothing is decoded."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = np.ascontiguousarray(np.frombuffer(memoryview(in_buf), dtype=np.uint8)) if not isinstance(in_buf, np.ndarray) else in_buf
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    hi, hip = (None, None) if history is None else _np(history, np.uint32)
+    size = np.zeros(n, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.int32)
+    rc = lib.lz4flex_decompressed_size_batch(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, hip,
+                                             C.c_void_p(size.ctypes.data), C.c_void_p(status.ctypes.data), L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
+    return size, status
+
+
+def decompress_blocks_device(src, in_off, in_len, stream=None):
+    """Raw blocks in device memory, sizes unknown: src is a uint8 torch tensor on the GPU, in_off / in_len integer tensors (block i is
+    src[in_off[i] : in_off[i] + in_len[i]]).  The size pass, an exclusive prefix sum for the output offsets, ONE host synchronisation (the
+    total, to allocate exactly that), one lz4flex_decompress_batch with out_cap = the sizes.  Returns (out, out_off, out_len, status) as
+    device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and an empty slot.
+    A block of more than 4 GiB - 1 decompressed bytes (the decoders' u32 out_cap) raises ValueError."""
+    import torch
+    lib = L.load()
+    dev = src.device
+    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n:
+        raise ValueError("in_off and in_len differ in length")
+    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
+    d_len = in_len.to(device=dev, dtype=torch.int32).contiguous()
+    size = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), size, torch.empty(0, dtype=torch.int32, device=dev), status
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    sp = C.c_void_p(stream)
+    rc = lib.lz4flex_decompressed_size_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                             None, C.c_void_p(size.data_ptr()), C.c_void_p(status.data_ptr()), L.MEM_DEVICE, sp)
+    if rc:
+        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
+    incl = torch.cumsum(size, 0)
+    out_off = incl - size
+    total, biggest = (int(v) for v in torch.stack([incl[-1], size.max()]).cpu())     # the one synchronisation
+    if biggest > 0xFFFFFFFF:
+        raise ValueError("a block decompresses to %d bytes: more than the decoders' u32 out_cap" % biggest)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    cap = size.to(torch.int32)       # (the bit pattern of a u32 <= 0xFFFFFFFF)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    st2 = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib.lz4flex_decompress_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
+                                      C.c_void_p(out_len.data_ptr()), C.c_void_p(st2.data_ptr()), None,
+                                      L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if biggest > 131072 else 0), sp)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch failed (%d): %s" % (rc, L.last_error()))
+    # a block the size pass rejected keeps its status; the decoder's is the one of every other block (0 by the size pass's contract)
+    status = torch.where(status != 0, status, st2)
+    out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
+    return out[:total], out_off, out_len, status

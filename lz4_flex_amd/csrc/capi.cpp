@@ -88,6 +88,7 @@ struct lz4flex_ctx {
     void* many_ws[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t many_cap[4] = {0, 0, 0, 0};
     int fail_next_batch = 0;      // tests: the next N batch calls on this context fail before they launch anything (what an allocation failure looks like to the caller)
+    int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
 };
 
 static constexpr uint32_t PCD_MAX_BLOCKS = DISPATCH_PCD_256;     // up to here the default dispatch takes the workgroup decoder
@@ -489,6 +490,11 @@ int lz4flex_set_tuning(lz4flex_ctx* c, const char* key, int value) {
         c->comp_lanes = value;
         return 0;
     }
+    if (!strcmp(key, "size_scan_serial")) {
+        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
+        c->size_serial = value;
+        return 0;
+    }
     // Test hooks (fault injection; unsupported, see the header): only in a process that opted in with LZ4FLEX_TEST_HOOKS=1 (tests/conftest.py
     // does) -- the frame layer and every scalar call of a process share the default context, a hook set there by anybody else would make
     // unrelated users fail or take the slow redo path
@@ -547,10 +553,11 @@ int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     if (!strcmp(key, "decompress_blocks_per_wg")) return c->dec_blocks_per_wg;
     if (!strcmp(key, "decompress_level_chains")) return c->dec_level_chains;
     if (!strcmp(key, "decompress_lanes")) return c->dec_lanes;
+    if (!strcmp(key, "size_scan_serial")) return c->size_serial;
     return -LZ4FLEX_E_INVALID_ARG;
 }
 
-int lz4flex_abi_version(void) { return 6; }
+int lz4flex_abi_version(void) { return 7; }
 
 size_t lz4flex_get_maximum_output_size(size_t input_len) {
     return 16 + 4 + (size_t)((uint64_t)input_len * 110 / 100);
@@ -971,6 +978,60 @@ int lz4flex_decompress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64
                              uint32_t* out_len, int32_t* status, uint64_t* detail, int mem_kind, void* hip_stream) {
     return lz4flex_decompress_batch_ex(ctx, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status,
                                        detail, nullptr, mem_kind, hip_stream);
+}
+
+// The sizes of raw blocks (lz4_size_scan.hip).  HOST: the input span and the descriptors go up in one staging layout, the results come
+// back to page-locked memory, one synchronisation.  DEVICE: two launches on the caller's stream, nothing else.
+int lz4flex_decompressed_size_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                    const uint32_t* history, uint64_t* out_size, int32_t* status, int mem_kind, void* hip_stream) {
+    int rc;
+    if (!ctx && (rc = default_ctx(&ctx))) return rc;
+    if ((mem_kind & ~LZ4FLEX_MEM_BIG_BLOCKS) != LZ4FLEX_MEM_HOST && (mem_kind & ~LZ4FLEX_MEM_BIG_BLOCKS) != LZ4FLEX_MEM_DEVICE)
+        return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!in_off || !in_len || !out_size || !status) return -LZ4FLEX_E_INVALID_ARG;
+    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
+    if ((mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE) {
+        const hipError_t le = launch_size_scan((const uint8_t*)in_base, in_off, in_len, history, n, out_size, status, ctx->size_serial,
+                                               (hipStream_t)hip_stream);
+        return le != hipSuccess ? hip_fail(le, "size scan launch") : 0;
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    HIP_TRY(hipSetDevice(ctx->device));
+    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
+    const Span sp = span_of(in_off, in_len, n);
+    const size_t in_bytes = (size_t)(sp.hi - sp.lo);
+    // [in_off in_len history | out_size status], the same layout in pinned memory and behind the input in the arena
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
+    const size_t at_in_off = take(8ull * n), at_in_len = take(4ull * n), at_hist = take(history ? 4ull * n : 0);
+    const size_t up_bytes = o;
+    const size_t at_size = take(8ull * n), at_status = take(4ull * n);
+    const size_t desc_bytes = o;
+    if ((rc = ensure_pin(ctx, desc_bytes))) return rc;
+    const size_t a_desc = align_up(in_bytes + 64, 256);
+    if ((rc = ensure_arena(ctx, a_desc + desc_bytes + 256))) return rc;
+    uint8_t* hp = ctx->h_pin;
+    for (uint32_t i = 0; i < n; i++) {
+        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
+        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
+        if (history) ((uint32_t*)(hp + at_hist))[i] = history[i];
+    }
+    uint8_t* d = ctx->d_arena;
+    uint8_t* dd = d + a_desc;
+    hipStream_t s = ctx->stream;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(d, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
+    const hipError_t le = launch_size_scan(d, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len),
+                                           history ? (const uint32_t*)(dd + at_hist) : nullptr, n, (uint64_t*)(dd + at_size),
+                                           (int32_t*)(dd + at_status), ctx->size_serial, s);
+    if (le != hipSuccess) return hip_fail(le, "size scan launch");
+    HIP_TRY(hipMemcpyAsync(hp + at_size, dd + at_size, desc_bytes - at_size, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out_size, hp + at_size, 8ull * n);
+    memcpy(status, hp + at_status, 4ull * n);
+    return 0;
 }
 
 // ---- scalar, lz4_flex-shaped --------------------------------------------------------------

@@ -164,6 +164,14 @@ hipError_t launch_frame_sums_check(const uint8_t* base, const uint64_t* pay_off,
 hipError_t launch_copy_batch(const uint8_t* src_base, const uint64_t* src_off, const uint32_t* len, uint8_t* dst_base, const uint64_t* dst_off,
                              uint32_t n, hipStream_t s);
 
+// lz4_size_scan.hip (lz4flex_decompressed_size_batch): per block the bytes decompress_into would produce with an unbounded sink and
+// history[i] (nullable: 0) bytes in front of the block, or its DecompressError; nothing but out_size / status is written.  A wavefront per
+// block walks the token chain and sums the lengths; the blocks it leaves marked SIZE_SCAN_REDO are measured again in the reference's
+// check order, a lane per block, behind it.  serial_only: that second pass for every block (tests).
+constexpr int32_t SIZE_SCAN_REDO = 0x7F000003;
+hipError_t launch_size_scan(const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* history, uint32_t n,
+                            uint64_t* out_size, int32_t* status, int serial_only, hipStream_t s);
+
 
 // capi.cpp, for frame_many.cpp: *ctx = the calling thread's default context if null; the context's device / own stream / compress_mode;
 // grow-only device scratch in 4 slots (valid until the next ctx_scratch of the same slot; the caller runs to completion before it returns)
