@@ -111,7 +111,20 @@ static size_t put_len(uint8_t *out, size_t o, uint32_t r) {   /* compress.rs:237
     return o;
 }
 
-typedef struct { uint32_t lit_start, lit_len, off, mlen; } lz4w_seq;
+/* one sequence of the parse; the fields behind mlen are the trace (lz4w_trace): where the kernel writes the sequence.  win, wj: its
+ * window and segment; first: its segment's first sequence (place_segment writes its token and literals: pend of them carried in from
+ * in front of the segment, the rest its own); lane, call: its lane in, and the number of, its segment's encode_seqs call (after
+ * merge_batch); run: the one sequence of a run window.  The final literals have mlen == 0, win = the last window, wj = nseg. */
+typedef struct { uint32_t lit_start, lit_len, off, mlen; uint32_t win, wj, first, pend, lane, call, run; } lz4w_seq;
+/* a segment of the trace: [s0, s1) of the block (n counts the history), in window win whose first byte is wbase; run: a run window's */
+typedef struct { uint32_t win, wj, wbase, s0, s1, run; } lz4w_seg;
+static lz4w_seg *g_segs;     /* (lz4w_trace: the segment table; NULL for lz4w_compress) */
+static size_t g_nsegs, g_segcap;
+static void note_seg(uint32_t win, uint32_t wj, uint32_t wbase, uint32_t s0, uint32_t s1, uint32_t run) {
+    if (!g_segs || g_nsegs >= g_segcap) return;
+    lz4w_seg *g = &g_segs[g_nsegs++];
+    g->win = win; g->wj = wj; g->wbase = wbase; g->s0 = s0; g->s1 = s1; g->run = run;
+}
 
 /* is p a head of segment [s0, s1) given the running best match `carry` (window-relative end << 16 | distance)? */
 static int is_head(const uint8_t *in, uint32_t n, const uint16_t *d, const lz4w_params *P, uint32_t wbase, uint32_t s0, uint32_t s1,
@@ -134,6 +147,20 @@ static size_t merge_batch(lz4w_seq *seqs, size_t from, size_t cnt, size_t ns) {
         seqs[o++] = seqs[i];
     }
     return o;
+}
+
+/* one encode_seqs call: merge_batch, then its sequences get their lanes and the call its number (the segment's count of calls so far) */
+static size_t enc_call(lz4w_seq *seqs, size_t from, size_t cnt, size_t ns, uint32_t *calls) {
+    const size_t o = merge_batch(seqs, from, cnt, ns);
+    const size_t kept = cnt - (ns - o);
+    for (size_t i = 0; i < kept; i++) { seqs[from + i].lane = (uint32_t)i; seqs[from + i].call = *calls; }
+    if (kept) ++*calls;
+    return o;
+}
+
+static void new_seq(lz4w_seq *s, uint32_t lit_start, uint32_t lit_len, uint32_t off, uint32_t mlen, uint32_t win, uint32_t wj) {
+    s->lit_start = lit_start; s->lit_len = lit_len; s->off = off; s->mlen = mlen;
+    s->win = win; s->wj = wj; s->first = 0; s->pend = 0; s->lane = 0; s->call = 0; s->run = 0;
 }
 
 /* parse of one block; returns the number of sequences (the last one has mlen == 0: final literals).
@@ -163,7 +190,9 @@ size_t lz4w_parse(const uint8_t *in, uint32_t n, const uint16_t *d, const lz4w_p
             int run = wl >= RUN_MIN && wbase + ms < act_abs && me >= ms + 4;
             for (uint32_t p = wbase + 1; run && p < wend; p++) run = in[p] == in[wbase];
             if (run) {
-                seqs[ns].lit_start = anchor; seqs[ns].lit_len = wbase + ms - anchor; seqs[ns].off = 1; seqs[ns].mlen = me - ms;
+                new_seq(&seqs[ns], anchor, wbase + ms - anchor, 1, me - ms, sj / P->nseg, 0);
+                seqs[ns].first = 1; seqs[ns].pend = newfrom - anchor; seqs[ns].run = 1;
+                note_seg(sj / P->nseg, 0, wbase, newfrom, wend, 1);
                 ns++;
                 anchor = wbase + me;
                 sj += P->nseg - 1;
@@ -197,6 +226,9 @@ size_t lz4w_parse(const uint8_t *in, uint32_t n, const uint16_t *d, const lz4w_p
         if (s0 > n) s0 = n;
         if (s1 > n) s1 = n;
         if (s0 == s1) continue;
+        note_seg(sj / P->nseg, wj, wbase, s0, s1, 0);
+        const size_t seg_from = ns;
+        uint32_t calls = 0;
         uint32_t mend = (n >= 5) ? ((s1 < n - 5) ? s1 : n - 5) : 0;         /* matches end here at the latest */
         if (mend > wbase + 65535u) mend = wbase + 65535u;                    /* ends are 16-bit window-relative numbers */
         size_t batch_from = ns, npend = 0;   /* the sequences waiting in the kernel's lanes for a full wavefront (encode_seqs takes <= 64 at a time) */
@@ -258,7 +290,7 @@ size_t lz4w_parse(const uint8_t *in, uint32_t n, const uint16_t *d, const lz4w_p
                 if (!can) { cursor++; continue; }
                 if (i + 1 < cnt && (best[i + 1] >> 16) > e + 1) { cursor++; continue; }
                 const uint32_t len = e - rel;
-                seqs[ns].lit_start = anchor; seqs[ns].lit_len = p - anchor; seqs[ns].off = best[i] & 0xFFFF; seqs[ns].mlen = len;
+                new_seq(&seqs[ns], anchor, p - anchor, best[i] & 0xFFFF, len, sj / P->nseg, wj);
                 ns++;
                 cursor = anchor = p + len;
             }
@@ -266,21 +298,21 @@ size_t lz4w_parse(const uint8_t *in, uint32_t n, const uint16_t *d, const lz4w_p
             b = e1;
             const size_t nsel = ns - (batch_from + npend);
             if (npend + nsel > 64) {                     /* no room in the lanes: the waiting ones are encoded, the new ones wait */
-                ns = merge_batch(seqs, batch_from, npend, ns);
+                ns = enc_call(seqs, batch_from, npend, ns, &calls);
                 batch_from = ns - nsel; npend = nsel;
             } else npend += nsel;
         }
-        ns = merge_batch(seqs, batch_from, npend, ns);   /* the segment's end: the rest is encoded */
+        ns = enc_call(seqs, batch_from, npend, ns, &calls);   /* the segment's end: the rest is encoded */
+        if (ns > seg_from) { seqs[seg_from].first = 1; seqs[seg_from].pend = s0 - seqs[seg_from].lit_start; }
     }
-    seqs[ns].lit_start = anchor; seqs[ns].lit_len = n - anchor; seqs[ns].off = 0; seqs[ns].mlen = 0;
+    new_seq(&seqs[ns], anchor, n - anchor, 0, 0, nwin - 1, P->nseg);
     ns++;
     return ns;
 }
 
-/* whole encoder: returns the compressed size (out must hold get_maximum_output_size(n)) */
-size_t lz4w_compress(const uint8_t *in, uint32_t n, uint8_t *out, const lz4w_params *P, uint32_t *n_seq) {
+/* the parse of a whole block into seqs (room for n / 4 + 2); returns the number of sequences */
+static size_t parse_block(const uint8_t *in, uint32_t n, const lz4w_params *P, lz4w_seq *seqs) {
     uint16_t *d = (uint16_t *)calloc((size_t)n + WAVE, 2);
-    lz4w_seq *seqs = (lz4w_seq *)malloc(sizeof(lz4w_seq) * ((size_t)n / 4 + 2));
     g_slide = P->hist != 0 ? HIST : (P->slide == 2 ? 49152u : (P->slide == 1 ? HIST : 0u));
     g_subq = 0;
     if (P->sub >= 2 && P->sub <= 4 && P->hist == 0 && n <= WINDOW) {
@@ -289,6 +321,14 @@ size_t lz4w_compress(const uint8_t *in, uint32_t n, uint8_t *out, const lz4w_par
     }
     if (n) lz4w_index(in, n, d, P->hist);
     const size_t ns = n ? lz4w_parse(in, n, d, P, seqs) : 0;
+    free(d);
+    return ns;
+}
+
+/* whole encoder: returns the compressed size (out must hold get_maximum_output_size(n)) */
+size_t lz4w_compress(const uint8_t *in, uint32_t n, uint8_t *out, const lz4w_params *P, uint32_t *n_seq) {
+    lz4w_seq *seqs = (lz4w_seq *)malloc(sizeof(lz4w_seq) * ((size_t)n / 4 + 2));
+    const size_t ns = parse_block(in, n, P, seqs);
     size_t o = 0;
     if (n == 0) { out[o++] = 0; }
     for (size_t i = 0; i < ns; i++) {
@@ -305,6 +345,16 @@ size_t lz4w_compress(const uint8_t *in, uint32_t n, uint8_t *out, const lz4w_par
         if (ml >= 15) o = put_len(out, o, ml - 15);
     }
     if (n_seq) *n_seq = (uint32_t)ns;
-    free(d); free(seqs);
+    free(seqs);
     return o;
+}
+
+/* TEST INFRASTRUCTURE for the tests: the sequences lz4w_compress writes (seqs: room for n / 4 + 2; the same parse, with the trace
+ * fields) and the non-empty segments of the block (segs: room for seg_cap); returns the number of sequences, *n_segs the segments' */
+size_t lz4w_trace(const uint8_t *in, uint32_t n, const lz4w_params *P, lz4w_seq *seqs, lz4w_seg *segs, size_t seg_cap, size_t *n_segs) {
+    g_segs = segs; g_segcap = seg_cap; g_nsegs = 0;
+    const size_t ns = parse_block(in, n, P, seqs);
+    *n_segs = g_nsegs;
+    g_segs = NULL; g_segcap = 0; g_nsegs = 0;
+    return ns;
 }
