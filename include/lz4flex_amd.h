@@ -61,7 +61,8 @@ typedef struct lz4flex_err_detail {
 } lz4flex_err_detail;
 
 /* ---- context ------------------------------------------------------------------------------ */
-/* Owns the device workspace (the throughput encoder's 164 MiB of candidate slots and segment bodies, allocated HERE so
+/* Owns the device workspace (the throughput encoder's 164 MiB of candidate slots and segment bodies and 32 MiB of staging slots
+ * for dictionary items, allocated HERE so
  * that no compress call allocates; the staging arena and descriptor arrays of MEM_HOST calls) and a HIP stream.
  * One context per thread; distinct contexts are independent (reference: no global state, all fns reentrant).  MEM_DEVICE
  * compress batches of ONE context share its encoder workspace: the library orders them on the device (a batch enqueued on
@@ -75,10 +76,11 @@ const char *lz4flex_version(void);
 /* hash of the sources (csrc/ + include/ + compiler flags) this binary was built from; lz4_flex_amd/build.py
  * recomputes it from the tree, so a stale library is detectable */
 const char *lz4flex_build_id(void);
-/* The round of this header: 7.  Changes a caller built against an earlier header has to know: round 5 appended chain_prev / n_chains to
+/* The round of this header: 8.  Changes a caller built against an earlier header has to know: round 5 appended chain_prev / n_chains to
  * lz4flex_decompress_ext (read only for LZ4FLEX_MEM_DEVICE | LZ4FLEX_MEM_CHAINED batches; a struct of the four older members is fine for
  * every other call); round 6 removed "decompress_variant" 5 / 6 (the wave decoder; 13 took its place) and moved 12 to tools builds;
- * round 7 added lz4flex_decompressed_size_batch and the setting "size_scan_serial". */
+ * round 7 added lz4flex_decompressed_size_batch and the setting "size_scan_serial"; round 8 added lz4flex_compress_batch_ex
+ * (per-block dictionaries for compressing, both compress modes) -- the context's device workspace grew by 64 KiB per encoder workgroup. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -185,6 +187,40 @@ int lz4flex_compress_batch(lz4flex_ctx *ctx, const void *in_base, const uint64_t
                            const uint32_t *out_cap, uint32_t *out_len, int32_t *status, int mem_kind,
                            void *hip_stream);
 
+/* Compress n independent blocks, each against an external dictionary of its own: block::compress_into_with_dict
+ * (src/block/compress.rs:554-616) as a batch.  Block i reads in_base[in_off[i] .. + in_len[i]], its dictionary is
+ * dict_base[dict_off[i] .. + dict_len[i]] (dict_len[i] == 0: none); dictionaries may overlap each other and the inputs.
+ * Everything not said here is as for lz4flex_compress_batch (the OUTPUT_TOO_SMALL rule; MEM_HOST: staged -- the dictionary
+ * spans travel with the batch -- and synchronous; MEM_DEVICE: every pointer, the ext arrays included, is device memory, the call
+ * is asynchronous on hip_stream and allocates nothing).
+ *   No dictionaries: ext == NULL, ext->dict_base == NULL, or every dict_len[i] == 0 behaves as lz4flex_compress_batch and gives
+ *     the same bytes; a block with dict_len[i] == 0 in a mixed batch gets the bytes lz4flex_compress_batch gives it in a batch of
+ *     the same size.
+ *   compress_mode exact: block i gets exactly the bytes of lz4flex_compress_into_with_dict(block, dict) -- the table kind from the
+ *     UNtruncated dict_len + in_len < 65 535 (compress.rs:559), init_dict over the dictionary's last 64 KiB, every third position
+ *     (:571-583); dictionaries of 1 - 3 bytes count (only the _prepend_size_ helpers ignore them, :626-628).  One-block chains
+ *     of the reference-exact chain encoder (lz4flex_compress_chains), their records built on the device.
+ *   compress_mode fast (the default): block i is encoded by the throughput encoder as the item [last h bytes of the dictionary |
+ *     block], h = min(dict_len[i], 32 768): the LZ4FLEX_BLOCK_HISTORY mechanism with the history read from the dictionary; no
+ *     sub-windows.  The bytes depend only on the block, the dictionary's last h bytes and "compress_sliding_window" -- never on
+ *     the batch or the device -- and they decode with decompress_into_with_dict(block, dict) or any dictionary that ends in the
+ *     same h bytes.  Measured on an MI355X (profiles/r08_dict_compress.txt; one 32 KiB
+ *     dictionary, device-resident batches): 16 384 x 64 KiB JSON tiles 5.5 ms (3.0 without a dictionary, 67 ms in exact mode),
+ *     ratio 0.200 (0.230; exact 0.163); 65 536 x 4 KiB log records 5.8 ms (6.2 without, 58 in exact mode), ratio 0.298 (0.391;
+ *     exact 0.315) -- fast mode is the faster one for both shapes, even though a 4 KiB record indexes 32 KiB of dictionary.
+ *   Refused: a block with a dictionary and flags[i] != 0 (frame tables, LZ4FLEX_BLOCK_HISTORY and a dictionary do not combine)
+ *     gets status LZ4FLEX_E_INVALID_ARG, out_len 0, and nothing is written; the other blocks of the batch are unaffected.
+ * Returns 0 or -code for call-level failures (-LZ4FLEX_E_INVALID_ARG: dict_base set and dict_off / dict_len NULL). */
+typedef struct lz4flex_compress_ext {
+    const void *dict_base;      /* same memory kind as the batch; NULL = no dictionaries */
+    const uint64_t *dict_off;
+    const uint32_t *dict_len;   /* 0 = this block has no dictionary */
+} lz4flex_compress_ext;
+int lz4flex_compress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                              const uint32_t *flags, uint32_t n, void *out_base, const uint64_t *out_off,
+                              const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
+                              const lz4flex_compress_ext *ext, int mem_kind, void *hip_stream);
+
 /* Chains of DEPENDENT blocks: the full compress_internal signature (src/block/compress.rs:289-325) -- a
  * prefix before in_pos, an external dictionary, a stream offset and ONE hash table that persists across
  * the blocks of a chain (Linked frames, src/frame/compress.rs:280-299,327-356; compress_into_with_dict,
@@ -260,8 +296,9 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uin
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own
  *   parse -- any LZ4 decoder returns the input; ratio within a percent of the reference's, usually better), 1 = the
- *   reference's exact bytes (src/block/compress.rs:318-489 restated; about 3x slower).  Blocks with a dictionary / prefix
- *   always use the exact encoder.  A Linked frame (src/frame/compress.rs:261-371) written in mode 0 holds blocks whose matches
+ *   reference's exact bytes (src/block/compress.rs:318-489 restated; about 3x slower).  The scalar calls with a dictionary
+ *   (lz4flex_compress_into_with_dict and its _prepend_size_ form) always use the exact encoder; lz4flex_compress_batch_ex follows
+ *   this setting.  A Linked frame (src/frame/compress.rs:261-371) written in mode 0 holds blocks whose matches
  *   reach up to 64 KiB back into the blocks before them (LZ4FLEX_BLOCK_HISTORY below: 32 KiB of the stream in front of every
  *   block are its history) -- a dependency-carrying Linked frame that any decoder returns to the input, with a ratio below the
  *   reference's and still one launch per batch of blocks; in mode 1 it holds the reference's bytes (one dependency chain,

@@ -367,3 +367,106 @@ def decompress_blocks_device(src, in_off, in_len, stream=None):
     status = torch.where(status != 0, status, st2)
     out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
     return out[:total], out_off, out_len, status
+
+
+def _host_u8(b):
+    return np.ascontiguousarray(np.frombuffer(memoryview(b), dtype=np.uint8)) if not isinstance(b, np.ndarray) else b
+
+
+def compress_batch_with_dict(in_buf, in_off, in_len, dict_buf, dict_off, dict_len, out_buf, out_off, out_cap, flags=None, ctx=None):
+    """lz4flex_compress_batch_ex over host buffers: block i = in_buf[in_off[i] : + in_len[i]] compressed against the dictionary
+    dict_buf[dict_off[i] : + dict_len[i]] (dict_len[i] == 0: none) into out_buf[out_off[i] : + out_cap[i]] -- block::compress_into_with_dict
+    as a batch.  compress_mode exact gives the reference's bytes; fast (the default) the throughput encoder's, which use the dictionary's
+    last 32 KiB.  Returns (out_len[u32], status[i32])."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    dict_buf = _host_u8(dict_buf)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    do, dop = _np(dict_off, np.uint64)
+    dl, dlp = _np(dict_len, np.uint32)
+    oo, oop = _np(out_off, np.uint64)
+    oc, ocp = _np(out_cap, np.uint32)
+    fl, flp = (None, None) if flags is None else _np(flags, np.uint32)
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    # (an empty dictionary buffer still needs an address: NULL would mean "no dictionaries" for the whole batch)
+    keep = dict_buf if dict_buf.size else np.zeros(1, dtype=np.uint8)
+    ext = L.CompressExt(keep.ctypes.data, dop.value, dlp.value)
+    rc = lib.lz4flex_compress_batch_ex(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, flp, n,
+                                       C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
+                                       C.c_void_p(status.ctypes.data), C.byref(ext), L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_ex failed (%d): %s" % (rc, L.last_error()))
+    return out_len, status
+
+
+def decompress_batch_with_dict(in_buf, in_off, in_len, dict_buf, dict_off, dict_len, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_decompress_batch_ex with per-block dictionaries over host buffers (block::decompress_into_with_dict as a batch):
+    returns (out_len[u32], status[i32], detail[n,2] u64)."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    dict_buf = _host_u8(dict_buf)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    do, dop = _np(dict_off, np.uint64)
+    dl, dlp = _np(dict_len, np.uint32)
+    oo, oop = _np(out_off, np.uint64)
+    oc, ocp = _np(out_cap, np.uint32)
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    detail = np.zeros((n, 2), dtype=np.uint64)
+    keep = dict_buf if dict_buf.size else np.zeros(1, dtype=np.uint8)
+    ext = L.DecompressExt(keep.ctypes.data, dop.value, dlp.value, None, None, 0)
+    rc = lib.lz4flex_decompress_batch_ex(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
+                                         C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
+                                         C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), C.byref(ext), L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_ex failed (%d): %s" % (rc, L.last_error()))
+    return out_len, status, detail
+
+
+def compress_blocks_with_dict_device(src, in_off, in_len, dicts, dict_off, dict_len, stream=None):
+    """Blocks and dictionaries in device memory: src and dicts are uint8 torch tensors on the GPU, block i is src[in_off[i] : + in_len[i]]
+    and its dictionary dicts[dict_off[i] : + dict_len[i]] (0: none).  One lz4flex_compress_batch_ex (MEM_DEVICE, asynchronous on `stream`,
+    default the current one) into output slots of get_maximum_output_size(in_len[i]) bytes.  Returns (out, out_off, out_len, status) as
+    device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
+    import torch
+    lib = L.load()
+    dev = src.device
+    for t, name in ((src, "src"), (dicts, "dicts")):
+        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
+    if dev.type != "cuda":
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n or int(dict_off.numel()) != n or int(dict_len.numel()) != n:
+        raise ValueError("in_off, in_len, dict_off and dict_len differ in length")
+    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
+    d_len = in_len.to(device=dev, dtype=torch.int64)
+    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
+    out_off = torch.cumsum(cap64, 0) - cap64
+    total = int(cap64.sum()) if n else 0
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    in_len32 = d_len.to(torch.int32)
+    cap = cap64.to(torch.int32)
+    k_off = dict_off.to(device=dev, dtype=torch.int64).contiguous()
+    k_len = dict_len.to(device=dev, dtype=torch.int32).contiguous()
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0], out_off, out_len, status
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    dict_ptr = dicts.data_ptr() if dicts.numel() else out.data_ptr()     # (not NULL: NULL would mean "no dictionaries")
+    ext = L.CompressExt(dict_ptr, k_off.data_ptr(), k_len.data_ptr())
+    big = L.MEM_BIG_BLOCKS if int(d_len.max()) > 65536 else 0
+    rc = lib.lz4flex_compress_batch_ex(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(in_len32.data_ptr()),
+                                       None, n, C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
+                                       C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()), C.byref(ext),
+                                       L.MEM_DEVICE | big, C.c_void_p(stream))
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_ex failed (%d): %s" % (rc, L.last_error()))
+    return out[:total], out_off, out_len, status

@@ -227,10 +227,46 @@ static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a
 // Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
 // of <= 64 KiB and the host cannot see the device-resident lengths, so a block that breaks the promise is flagged on the
 // device (its bytes would be a valid block, but not lz4_flex's) instead of passing silently.
-__global__ void lz4flex_flag_long_blocks_kernel(const uint32_t* in_len, uint32_t n, uint32_t* out_len, int32_t* status) {
+__global__ void lz4flex_flag_long_blocks_kernel(const uint32_t* in_len, uint32_t n, uint32_t* out_len, int32_t* status, const uint32_t* dict_len) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n && in_len[b] > 65536u) { status[b] = LZ4FLEX_E_INVALID_ARG; out_len[b] = 0u; }
+    if (b < n && in_len[b] > 65536u && (dict_len == nullptr || dict_len[b] == 0u)) { status[b] = LZ4FLEX_E_INVALID_ARG; out_len[b] = 0u; }
 }
+
+// lz4flex_compress_batch_ex, reference-exact mode: block i's one-block chain for the chain kernel -- the record
+// lz4flex_compress_into_with_dict builds on the host (compress.rs:554-583: the table kind from the UNtruncated dictionary length, the
+// dictionary's last 64 KiB, input_stream_offset = their length), built here because a DEVICE batch's lengths are device memory.
+// count[i] = 1 for a block with a dictionary, 0 (not encoded by the chain kernel) for the others and for refused ones: a dictionary
+// with flags, or an input the u32 stream positions cannot hold (status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written).
+__global__ void lz4flex_dict_chain_records_kernel(const uint64_t* in_off, const uint32_t* in_len, const uint32_t* flags,
+                                                  const uint64_t* dict_off, const uint32_t* dict_len, uint32_t n,
+                                                  lz4flex_chain_block* rec, uint32_t* count, uint32_t* out_len, int32_t* status) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const uint32_t dl = dict_len[b], len = in_len[b];
+    uint32_t cnt = 0u;
+    if (dl != 0u) {
+        if ((flags != nullptr && flags[b] != 0u) || len > 0x7FFFFFFFu) {
+            status[b] = LZ4FLEX_E_INVALID_ARG;
+            out_len[b] = 0u;
+        } else {
+            const uint32_t tl = dl > 65536u ? 65536u : dl;
+            lz4flex_chain_block r;
+            r.in_off = in_off[b];
+            r.dict_off = dict_off[b] + (dl - tl);
+            r.in_len = len;
+            r.in_pos = 0u;
+            r.dict_len = tl;
+            r.so = tl;
+            r.repos = 0u;
+            r.flags = ((uint64_t)dl + len < 65535u ? 1u : 0u) | 2u;
+            rec[b] = r;
+            cnt = 1u;
+        }
+    }
+    count[b] = cnt;
+}
+
+static inline size_t align_up_(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // the encoders for independent blocks: throughput mode (own parse, any block length) or the reference-exact one
 static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, bool big, hipStream_t s) {
@@ -251,10 +287,36 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, bool big, 
             c->wave_used = true;
         }
     } else {
+        // (blocks with a dictionary are left alone by both launches below and encoded by the chain kernel behind them)
         le = launch_compress(a, c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant), s);
         if (le == hipSuccess && !big && a.n) {
-            hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a.in_len, a.n, a.out_len, a.status);
+            hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a.in_len, a.n, a.out_len, a.status,
+                               a.dict_len);
             le = hipGetLastError();
+        }
+        if (le == hipSuccess && a.dict_len && a.n) {
+            // one-block chains, their records in the (otherwise idle) throughput encoder's workspace: no allocation, ordered across
+            // streams like the encoder's own launches; batches larger than the workspace holds records for run in pieces
+            if (!c->wave_ws || !c->wave_done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
+            if (c->wave_used && s != c->wave_last) HIP_TRY(hipStreamWaitEvent(s, c->wave_done, 0));
+            const size_t per = sizeof(lz4flex_chain_block) + 4u;
+            const uint32_t piece = (uint32_t)std::min<size_t>(compress_wave_workspace_bytes(c->wave_wgs) / per - 64u, 0x40000000u);
+            lz4flex_chain_block* rec = (lz4flex_chain_block*)c->wave_ws;
+            uint32_t* cnt = (uint32_t*)((uint8_t*)c->wave_ws + align_up_(sizeof(lz4flex_chain_block) * (size_t)piece, 256));
+            for (uint32_t b0 = 0; b0 < a.n && le == hipSuccess; b0 += piece) {
+                const uint32_t m = std::min<uint32_t>(piece, a.n - b0);
+                hipLaunchKernelGGL(lz4flex_dict_chain_records_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, a.in_off + b0, a.in_len + b0,
+                                   a.flags ? a.flags + b0 : nullptr, a.dict_off + b0, a.dict_len + b0, m, rec, cnt, a.out_len + b0, a.status + b0);
+                le = hipGetLastError();
+                if (le == hipSuccess)
+                    le = launch_compress_chain(a.in_base, rec, nullptr, cnt, m, a.out_base, a.out_off + b0, a.out_cap + b0, a.out_len + b0,
+                                               a.status + b0, nullptr, s, a.dict_base);
+            }
+            if (le == hipSuccess) {
+                HIP_TRY(hipEventRecord(c->wave_done, s));
+                c->wave_last = s;
+                c->wave_used = true;
+            }
         }
     }
     if (le != hipSuccess) return hip_fail(le, "kernel launch");
@@ -344,7 +406,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     (void)hipGetDevice(&prev);
     e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    // the throughput encoder's workspace (two 80 KiB workgroups per CU, 164 MiB on an MI355X) and its ordering event: here, not
+    // the throughput encoder's workspace (two 80 KiB workgroups per CU, 196 MiB on an MI355X with the dictionary staging slots) and its ordering event: here, not
     // inside the first compress call -- a hipMalloc in an "asynchronous" entry point is a device synchronisation and breaks
     // stream capture
     if (e == hipSuccess) {
@@ -557,7 +619,7 @@ int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     return -LZ4FLEX_E_INVALID_ARG;
 }
 
-int lz4flex_abi_version(void) { return 7; }
+int lz4flex_abi_version(void) { return 8; }
 
 size_t lz4flex_get_maximum_output_size(size_t input_len) {
     return 16 + 4 + (size_t)((uint64_t)input_len * 110 / 100);
@@ -705,6 +767,14 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
     const bool has_dict = ext && ext->dict_base && ext->dict_off && ext->dict_len;
     const bool has_pos = ext && ext->out_pos;
     if (has_dict) hb.dict_span = span_of(ext->dict_off, ext->dict_len, n);
+    if (has_dict && compress) {
+        // (compress: the dictionary offsets of blocks without one are not looked at -- they need not lie anywhere near the others)
+        Span ds;
+        for (uint32_t i = 0; i < n; i++)
+            if (ext->dict_len[i]) { ds.lo = std::min<uint64_t>(ds.lo, ext->dict_off[i]); ds.hi = std::max<uint64_t>(ds.hi, ext->dict_off[i] + ext->dict_len[i]); }
+        if (ds.lo > ds.hi) { ds.lo = 0; ds.hi = 0; }
+        hb.dict_span = ds;
+    }
     const size_t in_bytes = (size_t)(hb.in_span.hi - hb.in_span.lo);
     const size_t out_bytes = (size_t)(hb.out_span.hi - hb.out_span.lo);
     const size_t dict_bytes = has_dict ? (size_t)(hb.dict_span.hi - hb.dict_span.lo) : 0;
@@ -730,7 +800,7 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
         ((uint32_t*)(hp + at_out_cap))[i] = out_cap[i];
         if (flags) ((uint32_t*)(hp + at_flags))[i] = flags[i];
         if (has_dict) {
-            ((uint64_t*)(hp + at_dict_off))[i] = ext->dict_off[i] - hb.dict_span.lo;
+            ((uint64_t*)(hp + at_dict_off))[i] = (compress && !ext->dict_len[i]) ? 0u : ext->dict_off[i] - hb.dict_span.lo;
             ((uint32_t*)(hp + at_dict_len))[i] = ext->dict_len[i];
         }
         if (has_pos) ((uint32_t*)(hp + at_out_pos))[i] = ext->out_pos[i];
@@ -756,6 +826,11 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
         a.flags = flags ? (const uint32_t*)(dd + at_flags) : nullptr;
         a.out_base = d + a_out; a.out_off = (const uint64_t*)(dd + at_out_off); a.out_cap = (const uint32_t*)(dd + at_out_cap);
         a.out_len = (uint32_t*)(dd + at_out_len); a.status = (int32_t*)(dd + at_status); a.n = n;
+        if (has_dict) {
+            a.dict_base = d + a_dict;
+            a.dict_off = (const uint64_t*)(dd + at_dict_off);
+            a.dict_len = (const uint32_t*)(dd + at_dict_len);
+        }
         bool big = false;
         for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 65536u;
         if ((rc = launch_compress_any(c, a, big, s))) return rc;
@@ -872,6 +947,7 @@ static int run_device_batch(lz4flex_ctx* c, bool compress, const void* in_base, 
         a.in_base = (const uint8_t*)in_base; a.in_off = in_off; a.in_len = in_len; a.flags = flags;
         a.out_base = (uint8_t*)out_base; a.out_off = out_off; a.out_cap = out_cap; a.out_len = out_len;
         a.status = status; a.n = n;
+        if (ext && ext->dict_base) { a.dict_base = (const uint8_t*)ext->dict_base; a.dict_off = ext->dict_off; a.dict_len = ext->dict_len; }
         const int rc = launch_compress_any(c, a, big_hint != 0, s);
         if (rc) return rc;
         le = hipSuccess;
@@ -946,6 +1022,29 @@ int lz4flex_compress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t
         return run_device_batch(ctx, true, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status,
                                 nullptr, nullptr, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
     return -LZ4FLEX_E_INVALID_ARG;
+}
+
+int lz4flex_compress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
+                              const uint32_t* flags, uint32_t n, void* out_base, const uint64_t* out_off,
+                              const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
+                              const lz4flex_compress_ext* ext, int mem_kind, void* hip_stream) {
+    if (!ext || !ext->dict_base)
+        return lz4flex_compress_batch(ctx, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status, mem_kind, hip_stream);
+    // (the arguments are checked before a context is looked for: a wrong call says so on any machine)
+    if (!ext->dict_off || !ext->dict_len) return -LZ4FLEX_E_INVALID_ARG;
+    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
+    const bool device = (mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE && (mem_kind & ~(0xFF | LZ4FLEX_MEM_BIG_BLOCKS)) == 0;
+    if (mem_kind != LZ4FLEX_MEM_HOST && !device) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if (!ctx && (rc = default_ctx(&ctx))) return rc;
+    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
+    lz4flex_decompress_ext_ e{};
+    e.dict_base = ext->dict_base; e.dict_off = ext->dict_off; e.dict_len = ext->dict_len;
+    if (mem_kind == LZ4FLEX_MEM_HOST)
+        return run_host_batch(ctx, true, (const uint8_t*)in_base, in_off, in_len, flags, n, (uint8_t*)out_base, out_off,
+                              out_cap, out_len, status, nullptr, &e);
+    return run_device_batch(ctx, true, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status,
+                            nullptr, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
 }
 
 int lz4flex_decompress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,

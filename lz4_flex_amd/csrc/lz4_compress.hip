@@ -757,11 +757,12 @@ __device__ __forceinline__ int32_t encode_general(const uint8_t* __restrict__ in
 
 // One group per chain; the chain's blocks are encoded in order with one persistent u32 table in LDS.
 // tbl_state (nullable, 4096 u32 per chain): loaded before the first block unless it is cleared, saved at the end.
+// chain_first nullable: chain c is block c alone (chain_count[c] 0 or 1); dict_base: dict_off indexes it (in_base when it is null)
 __global__ void __launch_bounds__(64) lz4_compress_chain_kernel(const uint8_t* in_base, const ChainBlock* blocks,
                                                                const uint32_t* chain_first, const uint32_t* chain_count,
                                                                uint32_t n_chains, uint8_t* out_base, const uint64_t* out_off,
                                                                const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                                               uint32_t* tbl_state) {
+                                                               uint32_t* tbl_state, const uint8_t* dict_base) {
     constexpr int G = 8;
     __shared__ __attribute__((aligned(16))) uint32_t tables[64 / G][4096];
     const uint32_t lane = threadIdx.x;
@@ -771,13 +772,13 @@ __global__ void __launch_bounds__(64) lz4_compress_chain_kernel(const uint8_t* i
     const uint32_t c = blockIdx.x * (64 / G) + lane / G;
     if (c >= n_chains) return;
     uint32_t* tbl = &tables[lane / G][0];
-    const uint32_t first = chain_first[c], count = chain_count[c];
+    const uint32_t first = chain_first ? chain_first[c] : c, count = chain_count[c];
     if (tbl_state) for (uint32_t k = grp.g; k < 4096u; k += G) tbl[k] = tbl_state[(size_t)c * 4096u + k];
     else for (uint32_t k = grp.g; k < 4096u; k += G) tbl[k] = 0u;
     for (uint32_t j = 0; j < count; ++j) {
         const ChainBlock b = blocks[first + j];
         const uint8_t* in = in_base + b.in_off;
-        const uint8_t* dict = in_base + b.dict_off;
+        const uint8_t* dict = (dict_base ? dict_base : in_base) + b.dict_off;
         const bool use_h4 = (b.flags & 1u) != 0u;
         if (b.flags & 2u) {
             for (uint32_t k = grp.g; k < 4096u; k += G) tbl[k] = 0u;
@@ -802,12 +803,12 @@ __global__ void __launch_bounds__(64) lz4_compress_chain_kernel(const uint8_t* i
 hipError_t launch_compress_chain(const uint8_t* in_base, const void* blocks, const uint32_t* chain_first,
                                  const uint32_t* chain_count, uint32_t n_chains, uint8_t* out_base,
                                  const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                 uint32_t* tbl_state, hipStream_t s) {
+                                 uint32_t* tbl_state, hipStream_t s, const uint8_t* dict_base) {
     if (n_chains == 0u) return hipSuccess;
     const uint32_t grid = (n_chains + 7u) / 8u;
     hipLaunchKernelGGL(lz4_compress_chain_kernel, dim3(grid), dim3(64), 0, s, in_base,
                        reinterpret_cast<const ChainBlock*>(blocks), chain_first, chain_count, n_chains, out_base, out_off,
-                       out_cap, out_len, status, tbl_state);
+                       out_cap, out_len, status, tbl_state, dict_base);
     return hipGetLastError();
 }
 
@@ -838,6 +839,8 @@ __global__ void __launch_bounds__(MODE == 0 ? 64 : 128) lz4_compress_blocks_kern
     grp.shift = (lane / G) * G;
     const uint32_t j = lane / G;                                                            // block slot of this lane group
     const uint32_t b = blockIdx.x * BPW + j;
+    // a block with a dictionary (lz4flex_compress_batch_ex) is the chain kernel's: here it is treated as a slot behind the batch's end
+    const bool dict_blk = a.dict_len != nullptr && j < BPW && b < a.n && a.dict_len[b] != 0u;
     if (EQ) {
         // sequence queues (+ input rings, MODE 4) behind the tables; the second wave is the emitter
         if (threadIdx.x < BPW) {
@@ -847,7 +850,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 64 : 128) lz4_compress_blocks_kern
         }
         __syncthreads();
         if (threadIdx.x >= 64u) {
-            const bool live = j < BPW && b < a.n;
+            const bool live = j < BPW && b < a.n && !dict_blk;
             emitter_wave<G, RG>(a, b, live, EmitQ{(lds_u8*)(rings + (size_t)(live ? j : 0u) * EQB)}, grp);
             return;
         }
@@ -880,7 +883,7 @@ __global__ void __launch_bounds__(MODE == 0 ? 64 : 128) lz4_compress_blocks_kern
         }
     }
     if (j >= BPW) return;
-    if (b >= a.n) {
+    if (b >= a.n || dict_blk) {
         if (MODE == 2 && grp.g == 0u) progress[j] = 0xFFFFFFFFu;
         return;
     }

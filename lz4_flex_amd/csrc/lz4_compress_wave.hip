@@ -78,8 +78,9 @@ __host__ __device__ constexpr uint32_t seg_longest() {
 constexpr uint32_t SEG = seg_longest();   // longest segment
 constexpr uint32_t HIST = WINDOW / 2u;      // history in front of a block (see Item)
 // Start of segment j (0 .. WORKERS) of a window whose first `skip` positions are history.  Without history in front of the block
-// the segments are the fixed ones, clipped (only an anchored last window has skip != 0); with it (skip >= HIST in every window)
-// the eight segments share the parsed part in the same proportions -- clipped, half of the workers would have nothing to do.
+// the segments are the fixed ones, clipped (only an anchored last window has skip != 0); with it (skip = h in an item's first window,
+// h in [1, HIST]: HIST for LZ4FLEX_BLOCK_HISTORY, any length for a dictionary's tail; skip >= HIST in every later window) the eight
+// segments share the parsed part in the same proportions -- clipped, half of the workers would have nothing to do.
 // Starts other than `skip` itself are multiples of 512.
 // send: 0 = the fixed segments; else the eight segments share [skip, send) in the fixed ones' proportions (WINDOW with history or sliding
 // windows; the end of a SUB-WINDOW, see Item::sub)
@@ -130,6 +131,10 @@ constexpr uint32_t SLOT_BYTES = 2u * WINDOW;                // cand[] of one win
 constexpr uint32_t BODY_STRIDE = (SEG + SEG / 128u + 255u) / 256u * 256u + 256u;   // a segment's encoded bytes never exceed SEG + SEG/255 + 16
 constexpr uint32_t WS_BYTES = 2u * SLOT_BYTES + WORKERS * BODY_STRIDE;
 static_assert(WS_BYTES % 256u == 0u, "workspace slots stay 256 B aligned");
+// per workgroup, behind everything else in the workspace: the staging slot of a dictionary item's window (stage_window) -- the window
+// and the 64 bytes of slack load_window reads behind it
+constexpr uint32_t STAGE_BYTES = WINDOW + 256u;
+constexpr uint32_t STAGE_READ = WINDOW + 64u;
 
 struct SegMeta {          // LDS, one per worker, valid between the two barriers of a window
     uint32_t has;         // the segment holds at least one match
@@ -300,6 +305,43 @@ __device__ __attribute__((noinline)) uint32_t run_scan(const uint8_t* __restrict
     }
     if (lane < wl - n16) acc |= (uint32_t)gwin[n16 + lane] ^ (splat & 255u);
     return __builtin_amdgcn_ballot_w64(acc != 0u) == 0ull ? 1u : 0u;
+}
+
+// DICTIONARY ITEMS (lz4flex_compress_batch_ex): the item [last h bytes of the dictionary | block] lies in two places.  Before the
+// indexer streams a window of such an item it copies the window's bytes [base, base + n) into the workgroup's staging slot -- item
+// positions p < h from dsrc[p] (the dictionary's tail), the others from bsrc[p] (the block) -- so that index_window (its counted
+// inline-assembly loads) and load_window read one contiguous buffer as they do for every other item.  Plain loads, 4 x 16 B per
+// lane in flight; the one 16-byte piece that straddles p = h and the last partial one are gathered byte by byte.  Items without a
+// dictionary never come here.
+__device__ __attribute__((noinline)) void stage_window(const uint8_t* dsrc_, const uint8_t* bsrc_, uint32_t base_, uint32_t n_, uint32_t h_,
+                                                       uint8_t* dst_, uint32_t lane) {
+    const g_u8* __restrict__ dsrc = uni_gptr<const g_u8>(dsrc_);
+    const g_u8* __restrict__ bsrc = uni_gptr<const g_u8>(bsrc_);
+    g_u8* __restrict__ dst = uni_gptr<g_u8>(dst_);
+    const uint32_t base = uni(base_), n = uni(n_), h = uni(h_);
+    for (uint32_t i0 = 0; i0 < n; i0 += 4096u) {                      // (uniform trip count, the lane's share inside)
+        u32x4 v[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t o = i0 + 1024u * j + 16u * lane, p = base + o;
+            v[j] = u32x4{0u, 0u, 0u, 0u};
+            if (o + 16u <= n && p + 16u <= h) __builtin_memcpy(&v[j], (const void*)(dsrc + p), 16);
+            else if (o + 16u <= n && p >= h) __builtin_memcpy(&v[j], (const void*)(bsrc + p), 16);
+            else if (o < n) {
+                uint32_t wd[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (uint32_t k = 0; k < 16u; ++k)
+                    if (o + k < n) wd[k >> 2] |= (uint32_t)(p + k < h ? dsrc[p + k] : bsrc[p + k]) << (8u * (k & 3u));
+                v[j] = u32x4{wd[0], wd[1], wd[2], wd[3]};
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t o = i0 + 1024u * j + 16u * lane;
+            if (o < n) __builtin_memcpy((void*)(dst + o), &v[j], 16);   // (the slot has room for the zero padding of the last piece)
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");           // the stores have landed before this wavefront reads them back
 }
 
 // returns 1 when the window is a run window (see above; only asked when run_ok_: the caller has checked the lengths), else 0
@@ -1228,9 +1270,14 @@ __device__ __attribute__((noinline)) void load_window(const uint8_t* __restrict_
 // eight segments share the parsed quarter, and the items of a block are drawn by different workgroups like the windows of a long
 // block (the carry ring).  Price: item k indexes and loads k + 1 quarters (2.5 x the indexing for sub = 4: free on an idle chip), the
 // segments are shorter (ratio + 0.1 ... 0.3 %), and the bytes depend on `sub` (the scalar model takes it as a parameter).
+// DICTIONARIES (CompressArgs::dict_*, lz4flex_compress_batch_ex): the same as history, with h = min(dict_len, HIST) bytes that come
+// from the END of the block's dictionary (any h in [1, HIST]; the item is [dictionary tail | block], in_off = the block's in_off - h
+// so that item position p >= h is in_base[in_off + p]) -- windows advance by HIST, no sub-windows.  The windows the indexer and the
+// workers read go through the workgroup's staging slot (stage_window); place_segment reads literals only, never history.
 struct Item {
     uint32_t blk, win, nwin, len, skip, hist, slide;     // slide: 0, or the bytes the windows advance by (HIST with history in front of the block; CompressArgs::slide for a long block)
     uint32_t sub;                                        // 0, or the parsed bytes per sub-window (WINDOW / CompressArgs::sub, rounded up to 512) of a block cut into sub-windows
+    uint32_t dct;                                        // 1: the first `hist` bytes are the tail of the block's dictionary (stage_window)
     uint64_t in_off;
 };
 // window geometry: window t.win covers [win_base, win_base + win_len) of the item and parses [win_from, that end)
@@ -1256,11 +1303,19 @@ __device__ __forceinline__ uint32_t win_len(const Item& t) {
 __device__ __forceinline__ uint32_t win_send(const Item& t) { return t.sub != 0u ? win_len(t) : (t.slide != 0u ? WINDOW : 0u); }
 __device__ __forceinline__ void item_load(const CompressArgs& a, Item& it) {
     // first window of block it.blk (or invalid)
-    it.win = 0u; it.nwin = 0u; it.len = 0u; it.skip = 0u; it.hist = 0u; it.slide = 0u; it.sub = 0u; it.in_off = 0ull;
+    it.win = 0u; it.nwin = 0u; it.len = 0u; it.skip = 0u; it.hist = 0u; it.slide = 0u; it.sub = 0u; it.dct = 0u; it.in_off = 0ull;
     if (it.blk >= a.n) return;
     const uint32_t len = a.in_len[it.blk];
     const uint32_t cap = a.out_cap[it.blk];
-    const uint32_t h = (a.flags != nullptr && (a.flags[it.blk] >> 8) >= HIST && len != 0u && len <= 0xFFFFFFFFu - HIST) ? HIST : 0u;
+    uint32_t h = (a.flags != nullptr && (a.flags[it.blk] >> 8) >= HIST && len != 0u && len <= 0xFFFFFFFFu - HIST) ? HIST : 0u;
+    const uint32_t dl = a.dict_len != nullptr ? a.dict_len[it.blk] : 0u;
+    if (dl != 0u) {
+        // a dictionary: its last h bytes are the item's history.  With frame flags or history bits as well, or an item longer than
+        // 4 GiB, the block is refused (status LZ4FLEX_E_INVALID_ARG, nothing written)
+        h = dl < HIST ? dl : HIST;
+        if ((a.flags != nullptr && a.flags[it.blk] != 0u) || len > 0xFFFFFFFFu - h) { it.skip = 2u; it.nwin = 1u; return; }
+        it.dct = 1u;
+    }
     it.hist = h;
     it.len = len + h;
     it.in_off = a.in_off[it.blk] - h;
@@ -1277,6 +1332,16 @@ __device__ __forceinline__ void item_load(const CompressArgs& a, Item& it) {
     }
     const uint64_t need = 20ull + (uint64_t)len * 110ull / 100ull;   // get_maximum_output_size, compress.rs:588-590
     if ((uint64_t)cap < need) { it.skip = 1u; it.nwin = 1u; }
+}
+// where the indexer and the workers read window t.win of item t: the item itself, or (a dictionary item) the staging slot
+__device__ __forceinline__ const uint8_t* win_src(const CompressArgs& a, const Item& t, const uint8_t* stg) {
+    return t.dct ? stg : a.in_base + t.in_off + (size_t)win_base(t);
+}
+// the readable bytes from the window's first one on (index_window's / load_window's rd_n): a staged window holds STAGE_READ of them,
+// which is every byte either function looks at (<= the window + 16 bytes; load_window's 64 bytes of slack)
+__device__ __forceinline__ uint32_t win_rd(const Item& t) {
+    const uint32_t r = t.len - win_base(t);
+    return t.dct && r > STAGE_READ ? STAGE_READ : r;
 }
 // Two ways of dealing work to the persistent workgroups.  Block mode: workgroup g owns blocks g, g + G, ... and walks
 // their windows in order (the carry between windows stays in LDS).  Window mode (fewer blocks than workgroups -- few, large
@@ -1354,6 +1419,7 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
     uint8_t* my_ws = ws + (size_t)blockIdx.x * WS_BYTES;
     uint8_t* slots = my_ws;                                        // two cand[] slots
     uint8_t* bodies = my_ws + 2u * SLOT_BYTES;
+    uint8_t* stg = a.stage + (size_t)blockIdx.x * STAGE_BYTES;       // dictionary items: the window being indexed (stage_window)
 
     const bool wmode = carry != nullptr;                          // windows (not blocks) are dealt to the workgroups
     lds_u32* giq = (lds_u32*)(lds + L_META) + 5u * WORKERS + 4u;   // window mode: item indices drawn by thread 0
@@ -1382,20 +1448,27 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
     uint32_t k = 0u;
 
     lds_u32* run_flag = (lds_u32*)(lds + L_META) + 5u * WORKERS + 11u;   // [slot]: the window whose cand[] slot this would be is a run window
-    auto do_index = [&](const Item& t, uint32_t slot) {
+    auto do_stage = [&](const Item& t) {
+        const uint32_t base = win_base(t);
+        const uint32_t nrd = win_rd(t);
+        const uint8_t* tail = a.dict_base + a.dict_off[t.blk] + (a.dict_len[t.blk] - t.hist);    // the dictionary's last h bytes
+        stage_window(tail, a.in_base + t.in_off, base, nrd, t.hist, stg, lane);
+    };
+    auto do_index = [&](const Item& t, uint32_t slot, bool stage) {
         if (t.skip) { if (lane == 0u) run_flag[slot] = 0u; return; }
+        if (t.dct && stage) do_stage(t);
         const uint32_t base = win_base(t), wl = win_len(t);
         const uint32_t act_abs = t.len >= 12u ? t.len - 11u : 0u;            // positions p < act_abs start 4 readable bytes and may match
         const uint32_t act_n = act_abs > base ? (act_abs - base < wl ? act_abs - base : wl) : 0u;
         // a run window's one match (see index_window): from the first parsed position that has a byte in front of it in the window to
         // the window's last match end; asked for only where that is a match the block format allows
         const RunGeom rg = run_geom(t);
-        const uint32_t run = index_window(a.in_base + t.in_off + base, wl, act_n, t.len - base, slots + (size_t)slot * SLOT_BYTES, lds, lane, rg.ok);
+        const uint32_t run = index_window(win_src(a, t, stg), wl, act_n, win_rd(t), slots + (size_t)slot * SLOT_BYTES, lds, lane, rg.ok);
         if (lane == 0u) run_flag[slot] = run;
     };
     auto do_load = [&](const Item& t) {
         if (t.skip) return;
-        load_window(a.in_base + t.in_off + (size_t)win_base(t), win_len(t), t.len - win_base(t), lds, threadIdx.x);
+        load_window(win_src(a, t, stg), win_len(t), win_rd(t), lds, threadIdx.x);
     };
 
     // (sums are kept in registers and added to prof[] once, when the workgroup is done: an atomic per tick made the
@@ -1410,8 +1483,13 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
             t_prev = t;
         }
     };
-    // prologue: cand[] of the first window, the first window into LDS
-    if (w == WORKERS) { do_index(it, 0u); tick(0u); }
+    // prologue: cand[] of the first window, the first window into LDS (a dictionary item's first window is staged before either
+    // reads it; later windows are staged by the indexer while the workers match the window before -- they have loaded it by then)
+    if (it.dct && !it.skip) {
+        if (w == WORKERS) do_stage(it);
+        __syncthreads();
+    }
+    if (w == WORKERS) { do_index(it, 0u, false); tick(0u); }
     else { do_load(it); tick(5u); }
     __syncthreads();
     tick(w == WORKERS ? 1u : 6u);
@@ -1433,7 +1511,7 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
         const uint32_t wl = win_len(it);
         const bool last_win = it.win + 1u == it.nwin;
         if (w == WORKERS) {
-            if (ix.blk < a.n) do_index(ix, (k + 1u) & 1u);
+            if (ix.blk < a.n) do_index(ix, (k + 1u) & 1u, true);
         } else if (!it.skip) {
             const uint32_t base = win_base(it), skip = win_skip(it);
             uint32_t s0 = seg_start(w, skip, win_send(it));
@@ -1474,7 +1552,7 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
         }
         if (w != WORKERS) {
             if (it.skip) {
-                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = (a.dict_len != nullptr && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
             } else {
                 place_segment(lds, a.in_base + it.in_off, it.len, it.win, last_win, wl, win_base(it), win_skip(it), win_send(it), bodies + (size_t)w * BODY_STRIDE,
                               a.out_base + a.out_off[it.blk], k & 1u, w, lane, a.out_len + it.blk, a.status + it.blk,
@@ -1503,22 +1581,37 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
     }
 }
 
+// Batches without dictionaries run kernels whose arguments say so at compile time: every dictionary branch folds away and the
+// code is the encoder's as it was before dictionaries existed (same registers, same speed); batches with them run the _dict_ kernels.
+__device__ __forceinline__ CompressArgs no_dicts(CompressArgs a) {
+    a.dict_base = nullptr; a.dict_off = nullptr; a.dict_len = nullptr;
+    return a;
+}
 __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_kernel(const CompressArgs a, uint8_t* __restrict__ ws,
                                                                     uint32_t* __restrict__ carry, unsigned long long* __restrict__ prof, uint32_t carry_spins) {
-    wave_body(a, ws, carry, prof, 0, carry_spins);
+    wave_body(no_dicts(a), ws, carry, prof, 0, carry_spins);
 }
 // the launch behind a window-mode launch (a kernel of its own so that profiles tell the two apart): block mode, only blocks
 // left with status `redo`
 __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_redo_kernel(const CompressArgs a, uint8_t* __restrict__ ws,
                                                                                                                      int32_t redo) {
+    wave_body(no_dicts(a), ws, nullptr, nullptr, redo, CARRY_SPINS);
+}
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_dict_kernel(const CompressArgs a, uint8_t* __restrict__ ws,
+                                                                    uint32_t* __restrict__ carry, unsigned long long* __restrict__ prof, uint32_t carry_spins) {
+    wave_body(a, ws, carry, prof, 0, carry_spins);
+}
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_dict_redo_kernel(const CompressArgs a, uint8_t* __restrict__ ws,
+                                                                                                                          int32_t redo) {
     wave_body(a, ws, nullptr, nullptr, redo, CARRY_SPINS);
 }
 
 }  // namespace wave
 
 // cand[] slots and segment bodies per workgroup, then the window-carry ring and window counter per block for batches of fewer
-// blocks than workgroups
-size_t compress_wave_workspace_bytes(int n_workgroups) { return (size_t)n_workgroups * (wave::WS_BYTES + wave::CARRY_DWORDS * 4u + 4u); }
+// blocks than workgroups, then a staging slot per workgroup for the windows of dictionary items
+static size_t wave_stage_at(int n_workgroups) { return ((size_t)n_workgroups * (wave::WS_BYTES + wave::CARRY_DWORDS * 4u + 4u) + 255u) & ~(size_t)255u; }
+size_t compress_wave_workspace_bytes(int n_workgroups) { return wave_stage_at(n_workgroups) + (size_t)n_workgroups * wave::STAGE_BYTES; }
 
 hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s, unsigned long long* prof, bool carry_wait) {
     if (a.n == 0u) return hipSuccess;
@@ -1528,12 +1621,12 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
     (void)hipGetDevice(&dev);
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(have & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wave::lz4_compress_wave_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wave::lz4_compress_wave_redo_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave::LDS_BYTES);
-        if (e != hipSuccess) return e;
+        for (const void* k : {reinterpret_cast<const void*>(wave::lz4_compress_wave_kernel), reinterpret_cast<const void*>(wave::lz4_compress_wave_redo_kernel),
+                              reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_kernel),
+                              reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_redo_kernel)}) {
+            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave::LDS_BYTES);
+            if (e != hipSuccess) return e;
+        }
         have |= bit;
     }
     // fewer blocks than workgroups: windows, not blocks, are dealt out (see item_seek); the carry slots and the item counter
@@ -1544,8 +1637,11 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
         const hipError_t e = hipMemsetAsync(carry, 0, (size_t)a.n * (wave::CARRY_DWORDS * 4u + 4u), s);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(wave::lz4_compress_wave_kernel, dim3((uint32_t)n_workgroups), dim3(wave::THREADS), wave::LDS_BYTES, s, a,
-                       (uint8_t*)workspace, carry, prof, carry_wait ? wave::CARRY_SPINS : 1u);
+    CompressArgs as = a;
+    as.stage = (uint8_t*)workspace + wave_stage_at(n_workgroups);
+    const bool dicts = as.dict_base != nullptr && as.dict_off != nullptr && as.dict_len != nullptr;
+    hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_kernel : wave::lz4_compress_wave_kernel, dim3((uint32_t)n_workgroups), dim3(wave::THREADS),
+                       wave::LDS_BYTES, s, as, (uint8_t*)workspace, carry, prof, carry_wait ? wave::CARRY_SPINS : 1u);
     const hipError_t first = hipGetLastError();      // (reading it clears it: a failed first launch must not be reported as success)
     if (first != hipSuccess) return first;
 #ifndef LZ4W_EXP_NO_REDO     // (tools: shows what the second launch is for)
@@ -1554,7 +1650,8 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
         // debugger) left its block with status 66.  Those blocks are encoded again by their own workgroup, window after window,
         // with the carry in LDS: the same bytes, no waiting, and no valid input turns into an error.  Nothing to do: ~10 us.
         const uint32_t g = a.n < (uint32_t)n_workgroups ? a.n : (uint32_t)n_workgroups;
-        hipLaunchKernelGGL(wave::lz4_compress_wave_redo_kernel, dim3(g), dim3(wave::THREADS), wave::LDS_BYTES, s, a, (uint8_t*)workspace, 66);
+        hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_redo_kernel : wave::lz4_compress_wave_redo_kernel, dim3(g), dim3(wave::THREADS),
+                           wave::LDS_BYTES, s, as, (uint8_t*)workspace, 66);
     }
 #endif
     return hipGetLastError();

@@ -77,6 +77,13 @@ struct CompressArgs {
     uint32_t n;
     uint32_t slide;            // throughput encoder: 0, or the bytes the windows of a block longer than 64 KiB advance by (32 768 or 49 152; lz4_compress_wave.hip Item)
     uint32_t sub;              // throughput encoder: 2 / 4 = blocks of at most 64 KiB are cut into that many sub-windows (small batches: lz4_compress_wave.hip Item::sub); else one window
+    // nullable (all three or none): per-block external dictionaries (lz4flex_compress_batch_ex); dict_len[i] == 0 = block i has none.
+    // Throughput encoder: the dictionary's last min(dict_len, 32 KiB) bytes are the block's history (lz4_compress_wave.hip Item);
+    // reference-exact encoder: lz4_compress_blocks_kernel leaves blocks with a dictionary alone (the chain kernel encodes them)
+    const uint8_t* dict_base;
+    const uint64_t* dict_off;
+    const uint32_t* dict_len;
+    uint8_t* stage;            // throughput encoder: the workgroups' staging slots (set by launch_compress_wave)
 };
 
 // plan / replay decoder (lz4_decompress_plan.hip, lz4_decompress_replay.hip; record format: lz4_plan_common.h)
@@ -130,11 +137,13 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
                                 bool carry_wait = true);               // tests: false = a window that has to wait for its predecessor gives up at once
 
 // chains of dependent blocks (dictionary / Linked frames); `blocks` is an array of the 40-byte ChainBlock
-// records laid out as {u64 in_off, u64 dict_off, u32 in_len, in_pos, dict_len, so, repos, flags}
+// records laid out as {u64 in_off, u64 dict_off, u32 in_len, in_pos, dict_len, so, repos, flags}.
+// chain_first nullable: chain c starts at block c (one-block chains; chain_count[c] 0 = block c is not encoded, nothing written).
+// dict_base nullable: dict_off indexes in_base
 hipError_t launch_compress_chain(const uint8_t* in_base, const void* blocks, const uint32_t* chain_first,
                                  const uint32_t* chain_count, uint32_t n_chains, uint8_t* out_base,
                                  const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                                 uint32_t* tbl_state, hipStream_t s);
+                                 uint32_t* tbl_state, hipStream_t s, const uint8_t* dict_base = nullptr);
 
 hipError_t launch_xxh32_batch(const uint8_t* base, const uint64_t* off, const uint32_t* len, uint32_t n, uint32_t seed,
                               uint32_t* out, hipStream_t s);
