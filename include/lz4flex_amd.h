@@ -80,7 +80,9 @@ const char *lz4flex_build_id(void);
  * lz4flex_decompress_ext (read only for LZ4FLEX_MEM_DEVICE | LZ4FLEX_MEM_CHAINED batches; a struct of the four older members is fine for
  * every other call); round 6 removed "decompress_variant" 5 / 6 (the wave decoder; 13 took its place) and moved 12 to tools builds;
  * round 7 added lz4flex_decompressed_size_batch and the setting "size_scan_serial"; round 8 added lz4flex_compress_batch_ex
- * (per-block dictionaries for compressing, both compress modes) -- the context's device workspace grew by 64 KiB per encoder workgroup. */
+ * (per-block dictionaries for compressing, both compress modes) -- the context's device workspace grew by 64 KiB per encoder workgroup.
+ * Later additions that change nothing for an existing call keep the number: lz4flex_compress_batch_shared_dict and the setting
+ * "compress_shared_dict" came after round 8 (the workspace grew by 41 KiB per context) -- a caller detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -221,6 +223,35 @@ int lz4flex_compress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uint6
                               const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
                               const lz4flex_compress_ext *ext, int mem_kind, void *hip_stream);
 
+/* Compress n independent blocks against ONE dictionary: the many-small-records use of lz4flex_compress_batch_ex, with the work
+ * that depends on the dictionary alone done once per call instead of once per block.  `dict` (dict_len bytes, a HOST value in both
+ * memory kinds) lies in the same memory kind as the batch.  There are no flags: dictionaries and flags do not combine.
+ * Everything not said here is as for lz4flex_compress_batch_ex (the OUTPUT_TOO_SMALL rule, LZ4FLEX_MEM_BIG_BLOCKS; MEM_HOST: staged and
+ * synchronous; MEM_DEVICE: asynchronous on hip_stream, allocates nothing).
+ *   The bytes: block i gets exactly what lz4flex_compress_batch_ex gives it with dict_off[i] = 0, dict_len[i] = dict_len for every
+ *     i, in both compress modes and under every "compress_sliding_window".  dict == NULL or dict_len == 0: lz4flex_compress_batch
+ *     without flags.
+ *   compress_mode fast: an item is [last h bytes of the dictionary | block], h = min(dict_len, 32 768), and what the encoder's
+ *     indexer does to its first hs positions -- hs = the largest multiple of 1 024 with hs + 3 <= h -- is the same for every item.  A
+ *     small kernel in front of the encoder does it once (the digest: the hash table after those positions, whether they are one
+ *     byte repeated, the tail itself; it lives in the context's workspace); the first window of every item whose positions below
+ *     hs may all start a match (block length >= hs + 11 - h) loads that table instead of clearing it, indexes from hs on, and stages
+ *     only the block behind the tail its workgroup's staging slot already holds.  Every other item (a dictionary shorter than
+ *     1 027 bytes, a block of a few bytes, the later windows of a block longer than 32 KiB) takes the per-block path in the same kernel.
+ *     Setting "compress_shared_dict" (default 1): 0 = no item starts from the digest (the per-block path for all of them: A/B
+ *     measurements, tests).  Measured on an MI355X (profiles/r09_shared_dict.txt; one 32 KiB dictionary, device-resident batches,
+ *     this entry against lz4flex_compress_batch_ex alternating in one session): 65 536 x 4 KiB log records 5.47 ms against 5.67 ms
+ *     (1.04 x), 16 384 x 64 KiB JSON tiles 5.01 ms against 5.52 ms (1.10 x).  The indexer's work per 4 KiB record falls 3.5 x, but it
+ *     runs beside the workers, and a record's window waits for the one worker that parses 3 of its 4 KiB (the segment geometry is
+ *     part of the bytes).
+ *   compress_mode exact: the one-block chains of lz4flex_compress_batch_ex with the one dictionary.
+ * Returns 0 or -code for call-level failures (-LZ4FLEX_E_INVALID_ARG: a missing array, dict == NULL with dict_len != 0, a mem_kind
+ * other than HOST / DEVICE (| BIG_BLOCKS)); n == 0 returns 0. */
+int lz4flex_compress_batch_shared_dict(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                       uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
+                                       uint32_t *out_len, int32_t *status, const void *dict, uint32_t dict_len,
+                                       int mem_kind, void *hip_stream);
+
 /* Chains of DEPENDENT blocks: the full compress_internal signature (src/block/compress.rs:289-325) -- a
  * prefix before in_pos, an external dictionary, a stream offset and ONE hash table that persists across
  * the blocks of a chain (Linked frames, src/frame/compress.rs:280-299,327-356; compress_into_with_dict,
@@ -340,7 +371,7 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uin
  *   the same bytes: a time-sliced GPU costs time, never an error); "decompress_level_chains" (default 1024; lz4flex_frame_decompress_many:
  *   a call that holds at least this many Linked streams decodes block k of every stream in ONE launch -- a plain batch whose prefixes
  *   the launches before it have written -- instead of a workgroup per block that polls its predecessor: thousands of short streams,
- *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1).
+ *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
  * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1. */
 int lz4flex_set_tuning(lz4flex_ctx *ctx, const char *key, int value);

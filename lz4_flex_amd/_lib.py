@@ -70,6 +70,7 @@ SIGNATURES = {
     "lz4flex_decompress_size_prepended": (_I64, [_VP, _SZ, _VP, _SZ, C.POINTER(ErrDetail)]),
     "lz4flex_compress_batch": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_compress_batch_ex": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, C.POINTER(CompressExt), _I32, _VP]),
+    "lz4flex_compress_batch_shared_dict": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _I32, _VP]),
     "lz4flex_compress_chains": (_I32, [_VP, _VP, C.POINTER(ChainBlock), _U32, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP,
                                         _I32, _VP]),
     "lz4flex_decompress_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),

@@ -470,3 +470,68 @@ def compress_blocks_with_dict_device(src, in_off, in_len, dicts, dict_off, dict_
     if rc:
         raise DeviceError("lz4flex_compress_batch_ex failed (%d): %s" % (rc, L.last_error()))
     return out[:total], out_off, out_len, status
+
+
+def compress_batch_with_shared_dict(in_buf, in_off, in_len, dictionary, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_compress_batch_shared_dict over host buffers: every block in_buf[in_off[i] : + in_len[i]] is compressed against the ONE
+    `dictionary` (bytes-like or a uint8 array) into out_buf[out_off[i] : + out_cap[i]] -- the bytes of compress_batch_with_dict with
+    that dictionary for every block, with the work that depends on the dictionary alone done once per call.  Returns (out_len[u32],
+    status[i32])."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    d = _host_u8(dictionary)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    oo, oop = _np(out_off, np.uint64)
+    oc, ocp = _np(out_cap, np.uint32)
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    rc = lib.lz4flex_compress_batch_shared_dict(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
+                                                C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
+                                                C.c_void_p(status.ctypes.data), C.c_void_p(d.ctypes.data if d.size else 0), int(d.size),
+                                                L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
+    return out_len, status
+
+
+def compress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, stream=None):
+    """Blocks and ONE dictionary in device memory: src and dictionary are uint8 torch tensors on the GPU, block i is
+    src[in_off[i] : + in_len[i]].  One lz4flex_compress_batch_shared_dict (MEM_DEVICE, asynchronous on `stream`, default the current
+    one) into output slots of get_maximum_output_size(in_len[i]) bytes.  Returns (out, out_off, out_len, status) as device tensors:
+    block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
+    import torch
+    lib = L.load()
+    dev = src.device
+    for t, name in ((src, "src"), (dictionary, "dictionary")):
+        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
+    if dev.type != "cuda":
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n:
+        raise ValueError("in_off and in_len differ in length")
+    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
+    d_len = in_len.to(device=dev, dtype=torch.int64)
+    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
+    out_off = torch.cumsum(cap64, 0) - cap64
+    total = int(cap64.sum()) if n else 0
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    in_len32 = d_len.to(torch.int32)
+    cap = cap64.to(torch.int32)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0], out_off, out_len, status
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    big = L.MEM_BIG_BLOCKS if int(d_len.max()) > 65536 else 0
+    rc = lib.lz4flex_compress_batch_shared_dict(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(in_len32.data_ptr()),
+                                                n, C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
+                                                C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()),
+                                                C.c_void_p(dictionary.data_ptr() if dictionary.numel() else 0), int(dictionary.numel()),
+                                                L.MEM_DEVICE | big, C.c_void_p(stream))
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
+    return out[:total], out_off, out_len, status

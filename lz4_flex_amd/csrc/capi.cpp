@@ -88,6 +88,8 @@ struct lz4flex_ctx {
     void* many_ws[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t many_cap[4] = {0, 0, 0, 0};
     int fail_next_batch = 0;      // tests: the next N batch calls on this context fail before they launch anything (what an allocation failure looks like to the caller)
+    int comp_shared = 1;          // "compress_shared_dict": 1 = lz4flex_compress_batch_shared_dict starts its items from the dictionary's digest; 0 = every item takes the per-block path (A/B measurements, tests)
+    bool shared_counted = false;  // the last shared-dictionary call ran the throughput encoder: its digest counter is what "debug_shared_dict_items" reads
     int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
 };
 
@@ -266,11 +268,21 @@ __global__ void lz4flex_dict_chain_records_kernel(const uint64_t* in_off, const 
     count[b] = cnt;
 }
 
+// lz4flex_compress_batch_shared_dict, reference-exact mode: the per-block dictionary arrays the chain records are built from -- every
+// block has the one dictionary (offset 0 of dict_base, `len` bytes)
+__global__ void lz4flex_fill_shared_dict_kernel(uint64_t* dict_off, uint32_t* dict_len, uint32_t n, uint32_t len) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n) { dict_off[b] = 0ull; dict_len[b] = len; }
+}
+
 static inline size_t align_up_(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // the encoders for independent blocks: throughput mode (own parse, any block length) or the reference-exact one
-static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, bool big, hipStream_t s) {
+// shared (nullable): ONE dictionary for every block (lz4flex_compress_batch_shared_dict; a has no dictionaries and no flags then)
+static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big, hipStream_t s, const SharedDictArgs* shared = nullptr) {
     hipError_t le;
+    CompressArgs a = a_;
+    if (shared) c->shared_counted = c->comp_mode == 0;
     if (c->comp_mode == 0) {
         if (!c->wave_ws || !c->wave_done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
         if (c->wave_used && s != c->wave_last) HIP_TRY(hipStreamWaitEvent(s, c->wave_done, 0));
@@ -280,7 +292,7 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, bool big, 
         // without a block cut their blocks of <= 64 KiB into 2 / 3 / 4 items each
         aw.sub = c->comp_det ? 1u : c->comp_sub != 0 ? (uint32_t)c->comp_sub
                                   : (a.n * 4u <= (uint32_t)c->wave_wgs ? 4u : (a.n * 3u <= (uint32_t)c->wave_wgs ? 3u : (a.n * 2u <= (uint32_t)c->wave_wgs ? 2u : 1u)));
-        le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0);
+        le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0, shared);
         if (le == hipSuccess) {
             HIP_TRY(hipEventRecord(c->wave_done, s));
             c->wave_last = s;
@@ -288,25 +300,36 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, bool big, 
         }
     } else {
         // (blocks with a dictionary are left alone by both launches below and encoded by the chain kernel behind them)
-        le = launch_compress(a, c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant), s);
-        if (le == hipSuccess && !big && a.n) {
+        // (a shared dictionary: every block has it, the chain kernel encodes them all)
+        le = shared ? hipSuccess : launch_compress(a, c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant), s);
+        if (le == hipSuccess && !big && a.n && !shared) {
             hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a.in_len, a.n, a.out_len, a.status,
                                a.dict_len);
             le = hipGetLastError();
         }
-        if (le == hipSuccess && a.dict_len && a.n) {
+        if (le == hipSuccess && (a.dict_len || shared) && a.n) {
             // one-block chains, their records in the (otherwise idle) throughput encoder's workspace: no allocation, ordered across
             // streams like the encoder's own launches; batches larger than the workspace holds records for run in pieces
             if (!c->wave_ws || !c->wave_done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
             if (c->wave_used && s != c->wave_last) HIP_TRY(hipStreamWaitEvent(s, c->wave_done, 0));
-            const size_t per = sizeof(lz4flex_chain_block) + 4u;
+            const size_t per = sizeof(lz4flex_chain_block) + 4u + (shared ? 12u : 0u);
             const uint32_t piece = (uint32_t)std::min<size_t>(compress_wave_workspace_bytes(c->wave_wgs) / per - 64u, 0x40000000u);
             lz4flex_chain_block* rec = (lz4flex_chain_block*)c->wave_ws;
             uint32_t* cnt = (uint32_t*)((uint8_t*)c->wave_ws + align_up_(sizeof(lz4flex_chain_block) * (size_t)piece, 256));
+            if (shared) {
+                // the one dictionary as per-block arrays of one piece (every piece reads the same ones), behind the records in the workspace
+                uint64_t* soff = (uint64_t*)((uint8_t*)cnt + align_up_(4u * (size_t)piece, 256));
+                uint32_t* slen = (uint32_t*)((uint8_t*)soff + align_up_(8u * (size_t)piece, 256));
+                const uint32_t m = std::min<uint32_t>(piece, a.n);
+                hipLaunchKernelGGL(lz4flex_fill_shared_dict_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, soff, slen, m, shared->len);
+                le = hipGetLastError();
+                a.dict_base = shared->dict; a.dict_off = soff; a.dict_len = slen;
+            }
             for (uint32_t b0 = 0; b0 < a.n && le == hipSuccess; b0 += piece) {
                 const uint32_t m = std::min<uint32_t>(piece, a.n - b0);
+                const uint32_t d0 = shared ? 0u : b0;
                 hipLaunchKernelGGL(lz4flex_dict_chain_records_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, a.in_off + b0, a.in_len + b0,
-                                   a.flags ? a.flags + b0 : nullptr, a.dict_off + b0, a.dict_len + b0, m, rec, cnt, a.out_len + b0, a.status + b0);
+                                   a.flags ? a.flags + b0 : nullptr, a.dict_off + d0, a.dict_len + d0, m, rec, cnt, a.out_len + b0, a.status + b0);
                 le = hipGetLastError();
                 if (le == hipSuccess)
                     le = launch_compress_chain(a.in_base, rec, nullptr, cnt, m, a.out_base, a.out_off + b0, a.out_cap + b0, a.out_len + b0,
@@ -557,6 +580,11 @@ int lz4flex_set_tuning(lz4flex_ctx* c, const char* key, int value) {
         c->size_serial = value;
         return 0;
     }
+    if (!strcmp(key, "compress_shared_dict")) {
+        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
+        c->comp_shared = value;
+        return 0;
+    }
     // Test hooks (fault injection; unsupported, see the header): only in a process that opted in with LZ4FLEX_TEST_HOOKS=1 (tests/conftest.py
     // does) -- the frame layer and every scalar call of a process share the default context, a hook set there by anybody else would make
     // unrelated users fail or take the slow redo path
@@ -579,6 +607,10 @@ int lz4flex_set_tuning(lz4flex_ctx* c, const char* key, int value) {
 
 int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     if (!key) return -LZ4FLEX_E_INVALID_ARG;
+    if (!strncmp(key, "debug_", 6)) {                            // test hooks: see lz4flex_set_tuning (refused before a context is looked for)
+        const char* e = getenv("LZ4FLEX_TEST_HOOKS");
+        if (!e || strcmp(e, "1") != 0) return -LZ4FLEX_E_INVALID_ARG;
+    }
     // the batch sizes at which the default decoder dispatch changes kernel or geometry (lz4_device.h), in ascending order; the
     // list ends where the key is refused.  tests/test_gpu_block.py builds its size matrix from it.
     if (!strncmp(key, "dispatch_threshold_", 19)) {
@@ -616,6 +648,21 @@ int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     if (!strcmp(key, "decompress_level_chains")) return c->dec_level_chains;
     if (!strcmp(key, "decompress_lanes")) return c->dec_lanes;
     if (!strcmp(key, "size_scan_serial")) return c->size_serial;
+    if (!strcmp(key, "compress_shared_dict")) return c->comp_shared;
+    if (!strcmp(key, "debug_shared_dict_items")) {
+        // the items of the last lz4flex_compress_batch_shared_dict call on this context whose first window started from the digest
+        // (0: none yet, the reference-exact mode, "compress_shared_dict" 0); waits for the device
+        if (!c->shared_counted || !c->wave_ws) return 0;
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        HIP_TRY(hipSetDevice(c->device));
+        uint32_t v = 0;
+        hipError_t e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(&v, compress_wave_shared_counter(c->wave_ws, c->wave_wgs), 4, hipMemcpyDeviceToHost);
+        (void)hipSetDevice(prev);
+        if (e != hipSuccess) return hip_fail(e, "debug_shared_dict_items");
+        return (int)std::min<uint32_t>(v, 0x7FFFFFFFu);
+    }
     return -LZ4FLEX_E_INVALID_ARG;
 }
 
@@ -662,6 +709,8 @@ struct lz4flex_decompress_ext_ {
     const uint32_t* out_pos;
     const uint32_t* chain_prev;
     uint32_t n_chains;
+    const void* shared_dict;      // compress only: ONE dictionary of shared_len bytes for every block (no dict_base then)
+    uint32_t shared_len;
 };
 
 // A host batch of a few small blocks (the scalar calls above all: compress_into / decompress_into are 1-block batches): ONE transfer up
@@ -777,7 +826,8 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
     }
     const size_t in_bytes = (size_t)(hb.in_span.hi - hb.in_span.lo);
     const size_t out_bytes = (size_t)(hb.out_span.hi - hb.out_span.lo);
-    const size_t dict_bytes = has_dict ? (size_t)(hb.dict_span.hi - hb.dict_span.lo) : 0;
+    const bool has_shared = compress && ext && ext->shared_dict && ext->shared_len;
+    const size_t dict_bytes = has_shared ? (size_t)ext->shared_len : has_dict ? (size_t)(hb.dict_span.hi - hb.dict_span.lo) : 0;
     // descriptor block (pinned host mirror and device copy share one layout)
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
@@ -809,7 +859,7 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
     hipStream_t s = c->stream;
     if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, in_base + hb.in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
     if (dict_bytes)
-        HIP_TRY(hipMemcpyAsync(d + a_dict, (const uint8_t*)ext->dict_base + hb.dict_span.lo, dict_bytes,
+        HIP_TRY(hipMemcpyAsync(d + a_dict, has_shared ? (const uint8_t*)ext->shared_dict : (const uint8_t*)ext->dict_base + hb.dict_span.lo, dict_bytes,
                                hipMemcpyHostToDevice, s));
     if (has_pos && out_bytes) {
         // prefix mode: the sink already holds bytes [0, out_pos) that matches may reference; in a chained batch only what lies
@@ -833,7 +883,9 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
         }
         bool big = false;
         for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 65536u;
-        if ((rc = launch_compress_any(c, a, big, s))) return rc;
+        SharedDictArgs sh{};
+        sh.dict = d + a_dict; sh.len = has_shared ? ext->shared_len : 0u; sh.use = (uint32_t)c->comp_shared;
+        if ((rc = launch_compress_any(c, a, big, s, has_shared ? &sh : nullptr))) return rc;
         le = hipSuccess;
     } else {
         DecompressArgs a{};
@@ -948,7 +1000,10 @@ static int run_device_batch(lz4flex_ctx* c, bool compress, const void* in_base, 
         a.out_base = (uint8_t*)out_base; a.out_off = out_off; a.out_cap = out_cap; a.out_len = out_len;
         a.status = status; a.n = n;
         if (ext && ext->dict_base) { a.dict_base = (const uint8_t*)ext->dict_base; a.dict_off = ext->dict_off; a.dict_len = ext->dict_len; }
-        const int rc = launch_compress_any(c, a, big_hint != 0, s);
+        SharedDictArgs sh{};
+        const bool has_shared = ext && ext->shared_dict && ext->shared_len;
+        if (has_shared) { sh.dict = (const uint8_t*)ext->shared_dict; sh.len = ext->shared_len; sh.use = (uint32_t)c->comp_shared; }
+        const int rc = launch_compress_any(c, a, big_hint != 0, s, has_shared ? &sh : nullptr);
         if (rc) return rc;
         le = hipSuccess;
     } else {
@@ -1044,6 +1099,32 @@ int lz4flex_compress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint6
         return run_host_batch(ctx, true, (const uint8_t*)in_base, in_off, in_len, flags, n, (uint8_t*)out_base, out_off,
                               out_cap, out_len, status, nullptr, &e);
     return run_device_batch(ctx, true, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status,
+                            nullptr, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
+}
+
+int lz4flex_compress_batch_shared_dict(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
+                                       uint32_t n, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
+                                       uint32_t* out_len, int32_t* status, const void* dict, uint32_t dict_len,
+                                       int mem_kind, void* hip_stream) {
+    // (the arguments are checked before a context is looked for: a wrong call says so on any machine)
+    if (!dict && dict_len) return -LZ4FLEX_E_INVALID_ARG;
+    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
+    const bool device = (mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE && (mem_kind & ~(0xFF | LZ4FLEX_MEM_BIG_BLOCKS)) == 0;
+    if (mem_kind != LZ4FLEX_MEM_HOST && !device) return -LZ4FLEX_E_INVALID_ARG;
+    // "debug_shared_dict_items" speaks of THIS call from here on: one that forwards or has nothing to do counts nothing
+    if (lz4flex_ctx* c0 = ctx ? ctx : g_default_ctx) c0->shared_counted = false;
+    if (n == 0) return 0;
+    if (!dict || !dict_len)
+        return lz4flex_compress_batch(ctx, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len, status, mem_kind, hip_stream);
+    int rc;
+    if (!ctx && (rc = default_ctx(&ctx))) return rc;
+    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
+    lz4flex_decompress_ext_ e{};
+    e.shared_dict = dict; e.shared_len = dict_len;
+    if (mem_kind == LZ4FLEX_MEM_HOST)
+        return run_host_batch(ctx, true, (const uint8_t*)in_base, in_off, in_len, nullptr, n, (uint8_t*)out_base, out_off,
+                              out_cap, out_len, status, nullptr, &e);
+    return run_device_batch(ctx, true, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len, status,
                             nullptr, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
 }
 

@@ -286,6 +286,9 @@ __device__ __forceinline__ void index_chunk(const lds_u8* lp, lds_u16* tab, g_u8
 // when that is one byte repeated.  The scalar model has the same rule (tests/sim/wave_encoder_model.c, run_window).
 constexpr uint32_t RUN_MIN = 8192u;
 // are bytes [from, wl) of the window all equal to the bytes of `splat` (one byte, four times)?  plain loads, whole wavefront
+// (SHARED: a second copy for index_window<true>.  The ordinary path's only call passes from = CHUNK and the compiler builds that constant
+// in -- a second caller of the same function would change the code of every kernel that has no shared dictionary)
+template <bool SHARED>
 __device__ __attribute__((noinline)) uint32_t run_scan(const uint8_t* __restrict__ gwin_, uint32_t from_, uint32_t wl_, uint32_t splat_, uint32_t lane) {
     const g_u8* __restrict__ gwin = uni_gptr<const g_u8>(gwin_);
     const uint32_t from = uni(from_), wl = uni(wl_), splat = uni(splat_);
@@ -344,14 +347,55 @@ __device__ __attribute__((noinline)) void stage_window(const uint8_t* dsrc_, con
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");           // the stores have landed before this wavefront reads them back
 }
 
-// returns 1 when the window is a run window (see above; only asked when run_ok_: the caller has checked the lengths), else 0
+// THE DIGEST OF A SHARED DICTIONARY (lz4flex_compress_batch_shared_dict): every item of such a batch is [the same h bytes | block], so
+// what the indexer does to positions [0, hs) of an item's first window -- hs = the largest multiple of CHUNK whose positions all hash
+// dictionary bytes only (hs + 3 <= h) -- is the same for every item.  lz4_shared_digest_kernel does it once per call, with index_chunk
+// itself, and leaves in the context's workspace: the table as it stands after [0, hs), whether [0, hs) is one byte repeated (run windows),
+// the tail itself (16-byte aligned, the source the staging slots are filled from) and a counter of the items that started from it.
+constexpr uint32_t DG_TAB = 0u;                          // 4096 x u16
+constexpr uint32_t DG_HDR = DG_TAB + (2u << HBITS);      // words: [0] [0, hs) is one byte repeated, [1] that byte four times, [2] items started from the digest
+constexpr uint32_t DG_TAIL = DG_HDR + 256u;              // the dictionary's last h bytes, zeros behind them
+constexpr uint32_t DIGEST_BYTES = DG_TAIL + HIST + 256u;
+static_assert(DIGEST_BYTES % 256u == 0u && DIGEST_BYTES < 65536u, "the digest stays small and aligned");
+__host__ __device__ constexpr uint32_t digest_hs(uint32_t h) { return h >= CHUNK + 3u ? (h - 3u) / CHUNK * CHUNK : 0u; }
+
+// returns 1 when the window is a run window (see above; only asked when run_ok_: the caller has checked the lengths), else 0.
+// SHARED (the first window of an item of a shared-dictionary batch, every position below hs active): the table comes from the digest
+// instead of being cleared, the chunks start at hs / CHUNK, and cand[] below hs is not written (the workers parse from h on).
+// (the ordinary instance takes an empty DigestRef: no argument, the function every other kernel calls is what it was)
+template <bool SHARED> struct DigestRef {};
+template <> struct DigestRef<true> { const uint8_t* digest; uint32_t hs; };
+__device__ __forceinline__ uint32_t digest_c0(const DigestRef<false>&) { return 0u; }
+__device__ __forceinline__ uint32_t digest_c0(const DigestRef<true>& d) { return uni(d.hs) / CHUNK; }
+__device__ __forceinline__ const g_u8* digest_ptr(const DigestRef<false>&) { return nullptr; }
+__device__ __forceinline__ const g_u8* digest_ptr(const DigestRef<true>& d) { return uni_gptr<const g_u8>(d.digest); }
+template <bool SHARED>
 __device__ __attribute__((noinline)) uint32_t index_window(const uint8_t* __restrict__ gwin_, uint32_t wl_, uint32_t act_n_, uint32_t rd_n_,
-                             uint8_t* __restrict__ slot_t_, lds_u8* lds, uint32_t lane, uint32_t run_ok_) {
+                             uint8_t* __restrict__ slot_t_, lds_u8* lds, uint32_t lane, uint32_t run_ok_, DigestRef<SHARED> dref) {
     const g_u8* __restrict__ gwin = uni_gptr<const g_u8>(gwin_);
     g_u8* __restrict__ slot_t = uni_gptr<g_u8>(slot_t_);
     const uint32_t wl = uni(wl_), act_n = uni(act_n_), rd_n = uni(rd_n_), run_ok = uni(run_ok_);
     lds_u16* tab = (lds_u16*)(lds + L_TAB);
-    {
+    const uint32_t c0 = digest_c0(dref);               // the first chunk that is indexed here
+    if (SHARED) {
+        const g_u8* __restrict__ dg = digest_ptr(dref);
+#ifndef LZ4W_NO_RUN_WINDOWS
+        if (run_ok) {
+            // [0, hs) one byte repeated (the digest knows) and the rest of the window that byte too: the first-KiB test and the scan
+            // behind it of the ordinary path, with the part the digest has looked at left out
+            const g_u32* hd = reinterpret_cast<const g_u32*>(dg + DG_HDR);
+            const uint32_t same = uni(hd[0]), splat = uni(hd[1]);
+            if (same != 0u && run_scan<true>(gwin_, c0 * CHUNK, wl, splat, lane)) return 1u;
+        }
+#endif
+        // 8 KiB, 8 x 16 B per lane, all in flight at once; they have landed (the compiler waits for them: plain loads) before the first
+        // chunk is asked for, so the hand-counted waits below count what they always counted
+        u32x4 tv[8];
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) tv[j] = *reinterpret_cast<const g_u32x4*>(dg + DG_TAB + 1024u * j + 16u * lane);
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; ++j) __builtin_memcpy((void*)(lds + L_TAB + 1024u * j + 16u * lane), &tv[j], 16);
+    } else {
         lds_u32* t4 = (lds_u32*)(lds + L_TAB);
         for (uint32_t i = lane; i < (2u << HBITS) / 4u; i += 64u) t4[i] = 0u;
     }
@@ -363,13 +407,13 @@ __device__ __attribute__((noinline)) uint32_t index_window(const uint8_t* __rest
     n_main = n_main < nchunks ? n_main : nchunks;
     g_u8* cand_lane = slot_t + 8u * lane;
     const uint32_t lane4 = lane & ~3u;
-    if (n_main != 0u) {
+    if (n_main > c0) {                                   // (c0 <= n_main: the caller has checked that positions [0, hs) are all active)
         const uint32_t last = n_main - 1u;
         ChunkRegs q[IDX_DEPTH];
 #pragma unroll
-        for (uint32_t j = 0; j < IDX_DEPTH; ++j) chunk_issue(q[j], gwin, j < last ? j : last, lane);   // past the end: the last chunk again
+        for (uint32_t j = 0; j < IDX_DEPTH; ++j) chunk_issue(q[j], gwin, c0 + j < last ? c0 + j : last, lane);   // past the end: the last chunk again
 #ifndef LZ4W_NO_RUN_WINDOWS
-        if (run_ok) {
+        if (!SHARED && run_ok) {
             // the first KiB (six younger loads: q[0] has landed): one byte repeated?  Then -- rare -- everything that is in flight
             // lands before the compiler may touch it, and the rest of the window is looked at
             chunk_wait<6>(q[0]);
@@ -377,7 +421,7 @@ __device__ __attribute__((noinline)) uint32_t index_window(const uint8_t* __rest
             const uint32_t dif = (q[0].main.x ^ splat) | (q[0].main.y ^ splat) | (q[0].main.z ^ splat) | (q[0].main.w ^ splat);
             if (__builtin_amdgcn_ballot_w64((dif != 0u) | (splat != uni(splat))) == 0ull) {
                 chunk_wait<0>(q[0]); chunk_wait<0>(q[1]); chunk_wait<0>(q[2]); chunk_wait<0>(q[3]);
-                if (run_scan(gwin_, CHUNK, wl, uni(splat), lane)) return 1u;
+                if (run_scan<false>(gwin_, CHUNK, wl, uni(splat), lane)) return 1u;
             }
         }
 #endif
@@ -394,13 +438,13 @@ __device__ __attribute__((noinline)) uint32_t index_window(const uint8_t* __rest
             index_chunk<true>(sl + lane4, tab, cand_lane, (CC), act_n, lane);                       \
         }
         static_assert(IDX_DEPTH == 4u, "the wait counts below are for four chunks in flight");
-        uint32_t c = 0u;
-        if (n_main >= IDX_DEPTH) {                       // first round: fewer stores are in flight yet
-            LZ4W_ONE_CHUNK(6, 0u, 0)
-            LZ4W_ONE_CHUNK(10, 1u, 1)
-            LZ4W_ONE_CHUNK(14, 2u, 2)
-            LZ4W_ONE_CHUNK(18, 3u, 3)
-            c = IDX_DEPTH;
+        uint32_t c = c0;
+        if (n_main - c0 >= IDX_DEPTH) {                  // first round: fewer stores are in flight yet
+            LZ4W_ONE_CHUNK(6, c0, 0)
+            LZ4W_ONE_CHUNK(10, c0 + 1u, 1)
+            LZ4W_ONE_CHUNK(14, c0 + 2u, 2)
+            LZ4W_ONE_CHUNK(18, c0 + 3u, 3)
+            c = c0 + IDX_DEPTH;
         }
         for (; c + IDX_DEPTH <= n_main; c += IDX_DEPTH) {   // steady state: 3 x 2 loads + 4 x 4 stores are younger
             LZ4W_ONE_CHUNK(22, c, 0)
@@ -438,6 +482,64 @@ __device__ __attribute__((noinline)) uint32_t index_window(const uint8_t* __rest
         index_chunk<false>(sl + lane4, tab, cand_lane, c, act_n, lane);
     }
     return 0u;
+}
+
+// 16 bytes at item position o of the tail (h bytes), zeros behind its end
+__device__ __forceinline__ u32x4 tail16(const g_u8* __restrict__ tail, uint32_t o, uint32_t h) {
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (o + 16u <= h) __builtin_memcpy(&v, (const void*)(tail + o), 16);      // (any alignment)
+    else if (o < h) {
+        uint32_t wd[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k)
+            if (o + k < h) wd[k >> 2] |= (uint32_t)tail[o + k] << (8u * (k & 3u));
+        v = u32x4{wd[0], wd[1], wd[2], wd[3]};
+    }
+    return v;
+}
+// The digest of one dictionary (see above): ONE wavefront, once per lz4flex_compress_batch_shared_dict call, in front of the encoder
+// on the same stream.  The chunks go through an LDS slot exactly like the tail chunks of index_window and are indexed by
+// index_chunk<true> -- the indexer's own rule, not a copy of it; the cand[] entries it writes for them go to `cand_scratch` (the first
+// workgroup's first cand[] slot: the encoder has not started yet and overwrites it).  LDS: the table, then one chunk slot.
+__global__ void __launch_bounds__(64) lz4_shared_digest_kernel(const uint8_t* __restrict__ dict, uint32_t dict_len, uint8_t* __restrict__ digest,
+                                                               uint8_t* __restrict__ cand_scratch) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
+    lds_u8* lds = (lds_u8*)dyn_lds;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t h = dict_len < HIST ? dict_len : HIST, hs = digest_hs(h);
+    const g_u8* __restrict__ tail = (const g_u8*)dict + (dict_len - h);
+    g_u8* __restrict__ dg = (g_u8*)digest;
+    for (uint32_t o = 16u * lane; o < HIST + 256u; o += 1024u) {
+        const u32x4 v = tail16(tail, o, h);
+        __builtin_memcpy((void*)(dg + DG_TAIL + o), &v, 16);
+    }
+    const uint32_t splat = h != 0u ? (uint32_t)tail[0] * 0x01010101u : 0u;
+    uint32_t acc = 0u;
+    for (uint32_t o = 16u * lane; o < hs; o += 1024u) {                 // (hs is a multiple of 1024: every lane, every round)
+        const u32x4 v = tail16(tail, o, h);
+        acc |= (v.x ^ splat) | (v.y ^ splat) | (v.z ^ splat) | (v.w ^ splat);
+    }
+    const uint32_t same = (hs != 0u && __builtin_amdgcn_ballot_w64(acc != 0u) == 0ull) ? 1u : 0u;
+    lds_u16* tab = (lds_u16*)lds;
+    lds_u8* sl = lds + (2u << HBITS);
+    for (uint32_t i = lane; i < (2u << HBITS) / 4u; i += 64u) ((lds_u32*)lds)[i] = 0u;
+    for (uint32_t c = 0; c < hs / CHUNK; ++c) {
+        for (uint32_t i = lane; i < (CHUNK + 16u) / 16u; i += 64u) {
+            const u32x4 v = tail16(tail, c * CHUNK + 16u * i, h);
+            __builtin_memcpy((void*)(sl + 16u * i), &v, 16);
+        }
+        index_chunk<true>(sl + (lane & ~3u), tab, (g_u8*)cand_scratch + 8u * lane, c, hs, lane);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; ++j) {
+        u32x4 v;
+        __builtin_memcpy(&v, (const void*)(lds + 1024u * j + 16u * lane), 16);
+        __builtin_memcpy((void*)(dg + DG_TAB + 1024u * j + 16u * lane), &v, 16);
+    }
+    if (lane == 0u) {
+        g_u32* hd = reinterpret_cast<g_u32*>(dg + DG_HDR);
+        hd[0] = same; hd[1] = splat; hd[2] = 0u;
+    }
 }
 
 // ---- worker ---------------------------------------------------------------------------------------------------
@@ -1274,6 +1376,17 @@ __device__ __attribute__((noinline)) void load_window(const uint8_t* __restrict_
 // from the END of the block's dictionary (any h in [1, HIST]; the item is [dictionary tail | block], in_off = the block's in_off - h
 // so that item position p >= h is in_base[in_off + p]) -- windows advance by HIST, no sub-windows.  The windows the indexer and the
 // workers read go through the workgroup's staging slot (stage_window); place_segment reads literals only, never history.
+// What the _shared_ kernels work on: the batch and the one dictionary of lz4flex_compress_batch_shared_dict.  Everything from item_load to
+// wave_body is a template on the argument type: with CompressArgs itself (every other kernel) the shared-dictionary code is not even
+// compiled (if constexpr), so those kernels are what they were.
+struct WaveArgs : CompressArgs {
+    const uint8_t* shared_dict;   // nullable: ONE dictionary of shared_len bytes for every block
+    uint32_t shared_len;
+    uint32_t shared_hs;           // digest_hs(h), or 0: no item starts from the digest (every one takes the per-block path)
+    uint32_t shared_keep;         // 1: a workgroup that goes from first window to first window keeps the staged tail
+    uint8_t* digest;
+};
+template <class A> constexpr bool IS_SHARED = __is_same(A, WaveArgs);
 struct Item {
     uint32_t blk, win, nwin, len, skip, hist, slide;     // slide: 0, or the bytes the windows advance by (HIST with history in front of the block; CompressArgs::slide for a long block)
     uint32_t sub;                                        // 0, or the parsed bytes per sub-window (WINDOW / CompressArgs::sub, rounded up to 512) of a block cut into sub-windows
@@ -1301,14 +1414,16 @@ __device__ __forceinline__ uint32_t win_len(const Item& t) {
 }
 // what the window's eight segments share (seg_start's `send`)
 __device__ __forceinline__ uint32_t win_send(const Item& t) { return t.sub != 0u ? win_len(t) : (t.slide != 0u ? WINDOW : 0u); }
-__device__ __forceinline__ void item_load(const CompressArgs& a, Item& it) {
+template <class A>
+__device__ __forceinline__ void item_load(const A& a, Item& it) {
     // first window of block it.blk (or invalid)
     it.win = 0u; it.nwin = 0u; it.len = 0u; it.skip = 0u; it.hist = 0u; it.slide = 0u; it.sub = 0u; it.dct = 0u; it.in_off = 0ull;
     if (it.blk >= a.n) return;
     const uint32_t len = a.in_len[it.blk];
     const uint32_t cap = a.out_cap[it.blk];
     uint32_t h = (a.flags != nullptr && (a.flags[it.blk] >> 8) >= HIST && len != 0u && len <= 0xFFFFFFFFu - HIST) ? HIST : 0u;
-    const uint32_t dl = a.dict_len != nullptr ? a.dict_len[it.blk] : 0u;
+    uint32_t dl = a.dict_len != nullptr ? a.dict_len[it.blk] : 0u;
+    if constexpr (IS_SHARED<A>) dl = a.shared_len;                   // (a shared dictionary: every block has it)
     if (dl != 0u) {
         // a dictionary: its last h bytes are the item's history.  With frame flags or history bits as well, or an item longer than
         // 4 GiB, the block is refused (status LZ4FLEX_E_INVALID_ARG, nothing written)
@@ -1334,7 +1449,8 @@ __device__ __forceinline__ void item_load(const CompressArgs& a, Item& it) {
     if ((uint64_t)cap < need) { it.skip = 1u; it.nwin = 1u; }
 }
 // where the indexer and the workers read window t.win of item t: the item itself, or (a dictionary item) the staging slot
-__device__ __forceinline__ const uint8_t* win_src(const CompressArgs& a, const Item& t, const uint8_t* stg) {
+template <class A>
+__device__ __forceinline__ const uint8_t* win_src(const A& a, const Item& t, const uint8_t* stg) {
     return t.dct ? stg : a.in_base + t.in_off + (size_t)win_base(t);
 }
 // the readable bytes from the window's first one on (index_window's / load_window's rd_n): a staged window holds STAGE_READ of them,
@@ -1351,18 +1467,21 @@ __device__ __forceinline__ uint32_t win_rd(const Item& t) {
 // when its block has no windows left it moves on to the next block that has.
 // redo != 0 (the second launch behind a window-mode launch): only blocks whose status is `redo` -- a window of theirs gave up
 // waiting for its predecessor's carry (a time-sliced or preempted GPU) -- are encoded, again, in block mode, where nothing waits
-__device__ __forceinline__ void item_seek(const CompressArgs& a, Item& it, int32_t redo) {
+template <class A>
+__device__ __forceinline__ void item_seek(const A& a, Item& it, int32_t redo) {
     if (redo != 0)
         while (it.blk < a.n && a.status[it.blk] != redo) it.blk += gridDim.x;
     item_load(a, it);
 }
-__device__ __forceinline__ void item_next_block(const CompressArgs& a, Item& it, int32_t redo) {
+template <class A>
+__device__ __forceinline__ void item_next_block(const A& a, Item& it, int32_t redo) {
     if (it.win + 1u < it.nwin) { it.win += 1u; return; }
     it.blk += gridDim.x;
     item_seek(a, it, redo);
 }
 // window mode, one thread: the next window for this workgroup, starting the search at block b0 -> {block, window} (block == n: none)
-__device__ __forceinline__ void item_draw(const CompressArgs& a, uint32_t* wctr, uint32_t b0, uint32_t& ob, uint32_t& ow) {
+template <class A>
+__device__ __forceinline__ void item_draw(const A& a, uint32_t* wctr, uint32_t b0, uint32_t& ob, uint32_t& ow) {
     const uint32_t n = a.n;
     uint32_t b = b0;
     // (its own block, then a few behind it: every block has workgroups that start at it and stay until it is done, so giving up
@@ -1401,7 +1520,8 @@ __device__ __forceinline__ RunGeom run_geom(const Item& t) {
 // prof (nullable, tools only): cycle sums per role, [0] indexer busy, [1] indexer at barriers, [2] workers matching,
 // [3] workers at the barrier behind matching, [4] placing, [5] loading the next window, [6] at the barrier behind loading,
 // [7] windows
-__device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __restrict__ ws, uint32_t* __restrict__ carry,
+template <class A>
+__device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, uint32_t* __restrict__ carry,
                                           unsigned long long* __restrict__ prof, const int32_t redo, const uint32_t carry_spins) {
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
     lds_u8* lds = (lds_u8*)dyn_lds;
@@ -1448,11 +1568,23 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
     uint32_t k = 0u;
 
     lds_u32* run_flag = (lds_u32*)(lds + L_META) + 5u * WORKERS + 11u;   // [slot]: the window whose cand[] slot this would be is a run window
+    // shared-dictionary batches, the indexer wavefront (the only one that stages): bytes [0, h) of the staging slot hold the dictionary's
+    // tail -- the first window of the previous item left them there and nothing has overwritten them since (a later window of a long
+    // item does); the first window of the next item then stages the block part only
+    [[maybe_unused]] uint32_t tail_kept = 0u;
     auto do_stage = [&](const Item& t) {
         const uint32_t base = win_base(t);
         const uint32_t nrd = win_rd(t);
+        if constexpr (IS_SHARED<A>) {
+            // (from the 16-byte boundary below h on: stage_window gathers the piece that straddles h byte by byte; win 0: base == 0)
+            const uint32_t from = (t.win == 0u && tail_kept != 0u) ? (t.hist & ~15u) : 0u;
+            stage_window(a.digest + DG_TAIL, a.in_base + t.in_off, base + from, nrd - from, t.hist, stg + from, lane);
+            tail_kept = (t.win == 0u && a.shared_keep != 0u) ? 1u : 0u;
+            return;
+        } else {
         const uint8_t* tail = a.dict_base + a.dict_off[t.blk] + (a.dict_len[t.blk] - t.hist);    // the dictionary's last h bytes
         stage_window(tail, a.in_base + t.in_off, base, nrd, t.hist, stg, lane);
+        }
     };
     auto do_index = [&](const Item& t, uint32_t slot, bool stage) {
         if (t.skip) { if (lane == 0u) run_flag[slot] = 0u; return; }
@@ -1463,7 +1595,18 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
         // a run window's one match (see index_window): from the first parsed position that has a byte in front of it in the window to
         // the window's last match end; asked for only where that is a match the block format allows
         const RunGeom rg = run_geom(t);
-        const uint32_t run = index_window(win_src(a, t, stg), wl, act_n, win_rd(t), slots + (size_t)slot * SLOT_BYTES, lds, lane, rg.ok);
+        if constexpr (IS_SHARED<A>) {
+            if (t.win == 0u && a.shared_hs != 0u && act_n >= a.shared_hs) {
+                // the item's positions [0, hs) are the digest's: the table from there, chunks from hs / CHUNK on
+                const uint32_t run = index_window<true>(win_src(a, t, stg), wl, act_n, win_rd(t), slots + (size_t)slot * SLOT_BYTES, lds, lane, rg.ok,
+                                                        DigestRef<true>{a.digest, a.shared_hs});
+                if (redo == 0 && lane == 0u)      // (tests: the items that started from the digest; a block encoded again by the redo launch is not counted twice)
+                    __hip_atomic_fetch_add((uint32_t*)(a.digest + DG_HDR) + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0u) run_flag[slot] = run;
+                return;
+            }
+        }
+        const uint32_t run = index_window<false>(win_src(a, t, stg), wl, act_n, win_rd(t), slots + (size_t)slot * SLOT_BYTES, lds, lane, rg.ok, DigestRef<false>{});
         if (lane == 0u) run_flag[slot] = run;
     };
     auto do_load = [&](const Item& t) {
@@ -1552,7 +1695,7 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
         }
         if (w != WORKERS) {
             if (it.skip) {
-                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = (a.dict_len != nullptr && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = ((IS_SHARED<A> || a.dict_len != nullptr) && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
             } else {
                 place_segment(lds, a.in_base + it.in_off, it.len, it.win, last_win, wl, win_base(it), win_skip(it), win_send(it), bodies + (size_t)w * BODY_STRIDE,
                               a.out_base + a.out_off[it.blk], k & 1u, w, lane, a.out_len + it.blk, a.status + it.blk,
@@ -1583,9 +1726,18 @@ __device__ __forceinline__ void wave_body(const CompressArgs& a, uint8_t* __rest
 
 // Batches without dictionaries run kernels whose arguments say so at compile time: every dictionary branch folds away and the
 // code is the encoder's as it was before dictionaries existed (same registers, same speed); batches with them run the _dict_ kernels.
+// The _shared_ kernels (lz4flex_compress_batch_shared_dict) are the only instances of wave_body<WaveArgs>; they hold no per-block
+// dictionaries and no flags.
 __device__ __forceinline__ CompressArgs no_dicts(CompressArgs a) {
     a.dict_base = nullptr; a.dict_off = nullptr; a.dict_len = nullptr;
     return a;
+}
+__device__ __forceinline__ WaveArgs only_shared(const CompressArgs& a, const SharedDictArgs& sh) {
+    WaveArgs r;
+    static_cast<CompressArgs&>(r) = no_dicts(a);
+    r.flags = nullptr;
+    r.shared_dict = sh.dict; r.shared_len = sh.len; r.shared_hs = sh.hs; r.shared_keep = sh.keep; r.digest = sh.digest;
+    return r;
 }
 __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_kernel(const CompressArgs a, uint8_t* __restrict__ ws,
                                                                     uint32_t* __restrict__ carry, unsigned long long* __restrict__ prof, uint32_t carry_spins) {
@@ -1605,15 +1757,29 @@ __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6,
                                                                                                                           int32_t redo) {
     wave_body(a, ws, nullptr, nullptr, redo, CARRY_SPINS);
 }
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_shared_kernel(const CompressArgs a, const SharedDictArgs sh,
+                                                                    uint8_t* __restrict__ ws, uint32_t* __restrict__ carry, unsigned long long* __restrict__ prof, uint32_t carry_spins) {
+    wave_body(only_shared(a, sh), ws, carry, prof, 0, carry_spins);
+}
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_shared_redo_kernel(const CompressArgs a, const SharedDictArgs sh,
+                                                                                                                            uint8_t* __restrict__ ws, int32_t redo) {
+    wave_body(only_shared(a, sh), ws, nullptr, nullptr, redo, CARRY_SPINS);
+}
 
 }  // namespace wave
 
 // cand[] slots and segment bodies per workgroup, then the window-carry ring and window counter per block for batches of fewer
 // blocks than workgroups, then a staging slot per workgroup for the windows of dictionary items
 static size_t wave_stage_at(int n_workgroups) { return ((size_t)n_workgroups * (wave::WS_BYTES + wave::CARRY_DWORDS * 4u + 4u) + 255u) & ~(size_t)255u; }
-size_t compress_wave_workspace_bytes(int n_workgroups) { return wave_stage_at(n_workgroups) + (size_t)n_workgroups * wave::STAGE_BYTES; }
+// ... and behind those ONE digest of a shared dictionary (lz4_shared_digest_kernel): the batches of a context are ordered on the device
+static size_t wave_digest_at(int n_workgroups) { return wave_stage_at(n_workgroups) + (size_t)n_workgroups * wave::STAGE_BYTES; }
+size_t compress_wave_workspace_bytes(int n_workgroups) { return wave_digest_at(n_workgroups) + wave::DIGEST_BYTES; }
+const uint32_t* compress_wave_shared_counter(const void* workspace, int n_workgroups) {
+    return (const uint32_t*)((const uint8_t*)workspace + wave_digest_at(n_workgroups) + wave::DG_HDR) + 2;
+}
 
-hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s, unsigned long long* prof, bool carry_wait) {
+hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s, unsigned long long* prof, bool carry_wait,
+                                const SharedDictArgs* shared_dict) {
     if (a.n == 0u) return hipSuccess;
     if (!workspace || n_workgroups <= 0) return hipErrorInvalidValue;
     static unsigned long long have = 0ull;
@@ -1623,7 +1789,9 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
     if (!(have & bit)) {
         for (const void* k : {reinterpret_cast<const void*>(wave::lz4_compress_wave_kernel), reinterpret_cast<const void*>(wave::lz4_compress_wave_redo_kernel),
                               reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_redo_kernel)}) {
+                              reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_redo_kernel),
+                              reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_kernel),
+                              reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_redo_kernel)}) {
             const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave::LDS_BYTES);
             if (e != hipSuccess) return e;
         }
@@ -1640,8 +1808,34 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
     CompressArgs as = a;
     as.stage = (uint8_t*)workspace + wave_stage_at(n_workgroups);
     const bool dicts = as.dict_base != nullptr && as.dict_off != nullptr && as.dict_len != nullptr;
-    hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_kernel : wave::lz4_compress_wave_kernel, dim3((uint32_t)n_workgroups), dim3(wave::THREADS),
-                       wave::LDS_BYTES, s, as, (uint8_t*)workspace, carry, prof, carry_wait ? wave::CARRY_SPINS : 1u);
+    const bool shared = shared_dict != nullptr && shared_dict->dict != nullptr && shared_dict->len != 0u;
+    const uint32_t spins = carry_wait ? wave::CARRY_SPINS : 1u;
+    SharedDictArgs sh{};
+    if (shared) {
+        // the digest of the shared dictionary, once, in front of the encoder (its scratch: the first workgroup's first cand[] slot)
+        sh = *shared_dict;
+        sh.digest = (uint8_t*)workspace + wave_digest_at(n_workgroups);
+        const uint32_t h = sh.len < wave::HIST ? sh.len : wave::HIST;
+        sh.hs = sh.use != 0u ? wave::digest_hs(h) : 0u;
+        sh.keep = sh.use;
+        // tools builds: one step alone (profiles/r09_shared_dict.txt).  The table and the shifted start only exist together: a restored
+        // table in front of chunk 0 would find every position of [0, hs) as its own candidate.
+#ifdef LZ4W_EXP_SHARED_NO_DIGEST     // the resident staged tail alone: cleared table, chunks from 0
+        sh.hs = 0u;
+#endif
+#ifdef LZ4W_EXP_SHARED_NO_KEEP       // the table and the shifted start alone: every item staged in full
+        sh.keep = 0u;
+#endif
+        hipLaunchKernelGGL(wave::lz4_shared_digest_kernel, dim3(1), dim3(64), (2u << wave::HBITS) + wave::CHUNK_SLOT, s, sh.dict, sh.len, sh.digest,
+                           (uint8_t*)workspace);
+        const hipError_t de = hipGetLastError();
+        if (de != hipSuccess) return de;
+        hipLaunchKernelGGL(wave::lz4_compress_wave_shared_kernel, dim3((uint32_t)n_workgroups), dim3(wave::THREADS), wave::LDS_BYTES, s, as, sh,
+                           (uint8_t*)workspace, carry, prof, spins);
+    } else {
+        hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_kernel : wave::lz4_compress_wave_kernel, dim3((uint32_t)n_workgroups), dim3(wave::THREADS),
+                           wave::LDS_BYTES, s, as, (uint8_t*)workspace, carry, prof, spins);
+    }
     const hipError_t first = hipGetLastError();      // (reading it clears it: a failed first launch must not be reported as success)
     if (first != hipSuccess) return first;
 #ifndef LZ4W_EXP_NO_REDO     // (tools: shows what the second launch is for)
@@ -1650,8 +1844,11 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
         // debugger) left its block with status 66.  Those blocks are encoded again by their own workgroup, window after window,
         // with the carry in LDS: the same bytes, no waiting, and no valid input turns into an error.  Nothing to do: ~10 us.
         const uint32_t g = a.n < (uint32_t)n_workgroups ? a.n : (uint32_t)n_workgroups;
-        hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_redo_kernel : wave::lz4_compress_wave_redo_kernel, dim3(g), dim3(wave::THREADS),
-                           wave::LDS_BYTES, s, as, (uint8_t*)workspace, 66);
+        if (shared)
+            hipLaunchKernelGGL(wave::lz4_compress_wave_shared_redo_kernel, dim3(g), dim3(wave::THREADS), wave::LDS_BYTES, s, as, sh, (uint8_t*)workspace, 66);
+        else
+            hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_redo_kernel : wave::lz4_compress_wave_redo_kernel, dim3(g), dim3(wave::THREADS),
+                               wave::LDS_BYTES, s, as, (uint8_t*)workspace, 66);
     }
 #endif
     return hipGetLastError();

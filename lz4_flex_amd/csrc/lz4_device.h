@@ -85,6 +85,17 @@ struct CompressArgs {
     const uint32_t* dict_len;
     uint8_t* stage;            // throughput encoder: the workgroups' staging slots (set by launch_compress_wave)
 };
+// lz4flex_compress_batch_shared_dict: ONE dictionary of `len` bytes (device memory) for every block of the batch; the batch itself has
+// no per-block dictionaries and no flags.  Throughput encoder: what the indexer does to the dictionary's tail is done once per call
+// (lz4_compress_wave.hip, the digest); use 0 = every item takes the per-block path instead.  hs / keep / digest are set by launch_compress_wave.
+struct SharedDictArgs {
+    const uint8_t* dict;
+    uint32_t len;
+    uint32_t use;
+    uint32_t hs;
+    uint32_t keep;
+    uint8_t* digest;
+};
 
 // plan / replay decoder (lz4_decompress_plan.hip, lz4_decompress_replay.hip; record format: lz4_plan_common.h)
 namespace plan { struct BlockPlan; }
@@ -132,9 +143,12 @@ hipError_t launch_compress(const CompressArgs& a, int variant, hipStream_t s);
 // throughput ("wave") encoder, lz4_compress_wave.hip: persistent workgroups, `workspace` holds
 // compress_wave_workspace_bytes(n_workgroups) bytes (cand[] slots + segment bodies, L2 / Infinity Cache resident)
 size_t compress_wave_workspace_bytes(int n_workgroups);
+// where the last shared-dictionary launch on `workspace` counts the items whose first window started from the digest (device memory)
+const uint32_t* compress_wave_shared_counter(const void* workspace, int n_workgroups);
 hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s,
                                 unsigned long long* prof = nullptr,    // prof: 8 cycle counters (tools), nullable
-                                bool carry_wait = true);               // tests: false = a window that has to wait for its predecessor gives up at once
+                                bool carry_wait = true,                // tests: false = a window that has to wait for its predecessor gives up at once
+                                const SharedDictArgs* shared_dict = nullptr);   // nullable: the batch's one dictionary (the _shared_ kernels)
 
 // chains of dependent blocks (dictionary / Linked frames); `blocks` is an array of the 40-byte ChainBlock
 // records laid out as {u64 in_off, u64 dict_off, u32 in_len, in_pos, dict_len, so, repos, flags}.
