@@ -82,7 +82,8 @@ const char *lz4flex_build_id(void);
  * round 7 added lz4flex_decompressed_size_batch and the setting "size_scan_serial"; round 8 added lz4flex_compress_batch_ex
  * (per-block dictionaries for compressing, both compress modes) -- the context's device workspace grew by 64 KiB per encoder workgroup.
  * Later additions that change nothing for an existing call keep the number: lz4flex_compress_batch_shared_dict and the setting
- * "compress_shared_dict" came after round 8 (the workspace grew by 41 KiB per context) -- a caller detects them by the symbol. */
+ * "compress_shared_dict" came after round 8 (the workspace grew by 41 KiB per context), then lz4flex_decompress_batch_shared_dict and
+ * the setting "decompress_shared_dict" (no workspace) -- a caller detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -324,6 +325,31 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uin
                                 uint32_t *out_len, int32_t *status, uint64_t *detail,
                                 const lz4flex_decompress_ext *ext, int mem_kind, void *hip_stream);
 
+/* Decompress n independent blocks against ONE dictionary: the mirror of lz4flex_compress_batch_shared_dict.  `dict` (dict_len bytes, a
+ * HOST value in both memory kinds) lies in the same memory kind as the batch.  mem_kind: LZ4FLEX_MEM_HOST (staged, the dictionary once
+ * per call; synchronous) or LZ4FLEX_MEM_DEVICE (asynchronous on hip_stream, allocates nothing); LZ4FLEX_MEM_BIG_BLOCKS may be ORed in
+ * (results do not depend on it); LZ4FLEX_MEM_CHAINED is refused.
+ *   The results: block i gets exactly what lz4flex_decompress_batch_ex gives it with dict_base = dict, dict_off[i] = 0, dict_len[i] =
+ *     dict_len and no out_pos -- bytes, out_len, status (every DecompressError in the reference's check order; OffsetOutOfBounds is
+ *     offset > produced + dict_len, src/block/decompress.rs:399-401) and detail (OutputTooSmall {expected, actual = out_cap}, counted from
+ *     out_off).  Nothing is written behind out_len bytes of a sink, nothing in front of out_off, never into the dictionary.  dict == NULL
+ *     or dict_len == 0: lz4flex_decompress_batch.
+ *   The kernel: lz4flex_decompress_batch_ex decodes dictionary blocks sixteen lanes per block, a block's sequences one after the other
+ *     (lz4_decompress.hip).  This entry runs the sequence decoder (lz4_decompress_seq.hip: a wavefront per block, a lane per sequence) in
+ *     its dictionary form at every n: the dictionary's last min(dict_len, 65 536) bytes are a virtual prefix in front of every block's
+ *     output, read from the one buffer and never stored to; a match that starts in the dictionary and ends in the block is decoded there.
+ *     Blocks it cannot decode (errors, sinks too small) are decoded again in the reference's order with the dictionary.
+ *     Setting "decompress_shared_dict" (default 1): 0 = every block in the reference's order, sixteen lanes per block (the per-block
+ *     path's decode_block; A/B measurements, tests); "decompress_variant" 1 pinned has the same effect.
+ *     Not timed yet: tools/shared_dict_decode_bench.py times this entry against lz4flex_decompress_batch_ex with per-block arrays and
+ *     against the same records without a dictionary (profiles/r10_shared_dict_decode.txt holds the register figures and awaits the table).
+ * Returns 0 or -code for call-level failures (-LZ4FLEX_E_INVALID_ARG: a missing array, dict == NULL with dict_len != 0, a mem_kind
+ * other than HOST / DEVICE (| BIG_BLOCKS)); n == 0 returns 0. */
+int lz4flex_decompress_batch_shared_dict(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                         uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
+                                         uint32_t *out_len, int32_t *status, uint64_t *detail /* nullable */,
+                                         const void *dict, uint32_t dict_len, int mem_kind, void *hip_stream);
+
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own
  *   parse -- any LZ4 decoder returns the input; ratio within a percent of the reference's, usually better), 1 = the
@@ -371,7 +397,8 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx *ctx, const void *in_base, const uin
  *   the same bytes: a time-sliced GPU costs time, never an error); "decompress_level_chains" (default 1024; lz4flex_frame_decompress_many:
  *   a call that holds at least this many Linked streams decodes block k of every stream in ONE launch -- a plain batch whose prefixes
  *   the launches before it have written -- instead of a workgroup per block that polls its predecessor: thousands of short streams,
- *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict).
+ *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict);
+ *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
  * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1. */
 int lz4flex_set_tuning(lz4flex_ctx *ctx, const char *key, int value);

@@ -74,6 +74,7 @@ SIGNATURES = {
     "lz4flex_compress_chains": (_I32, [_VP, _VP, C.POINTER(ChainBlock), _U32, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP,
                                         _I32, _VP]),
     "lz4flex_decompress_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
+    "lz4flex_decompress_batch_shared_dict": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _I32, _VP]),
     "lz4flex_decompress_batch_ex": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP,
                                             C.POINTER(DecompressExt), _I32, _VP]),
     "lz4flex_decompressed_size_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _I32, _VP]),

@@ -535,3 +535,82 @@ def compress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, str
     if rc:
         raise DeviceError("lz4flex_compress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
     return out[:total], out_off, out_len, status
+
+
+def decompress_batch_with_shared_dict(in_buf, in_off, in_len, dictionary, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_decompress_batch_shared_dict over host buffers: every block in_buf[in_off[i] : + in_len[i]] is decoded against the ONE
+    `dictionary` (bytes-like or a uint8 array) into out_buf[out_off[i] : + out_cap[i]] -- the results of decompress_batch_with_dict with
+    that dictionary for every block.  Returns (out_len[u32], status[i32], detail[n,2] u64)."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    d = _host_u8(dictionary)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    oo, oop = _np(out_off, np.uint64)
+    oc, ocp = _np(out_cap, np.uint32)
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    detail = np.zeros((n, 2), dtype=np.uint64)
+    rc = lib.lz4flex_decompress_batch_shared_dict(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
+                                                  C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
+                                                  C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data),
+                                                  C.c_void_p(d.ctypes.data if d.size else 0), int(d.size), L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
+    return out_len, status, detail
+
+
+def decompress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, stream=None):
+    """Raw blocks and their ONE dictionary in device memory, sizes unknown: the counterpart of decompress_blocks_device and the inverse
+    of compress_blocks_with_shared_dict_device.  The size pass with the dictionary's length as every block's history, an exclusive prefix
+    sum for the output offsets, ONE host synchronisation (the total, to allocate exactly that), one
+    lz4flex_decompress_batch_shared_dict with out_cap = the sizes.  Returns (out, out_off, out_len, status) as device tensors: block i's
+    bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and an empty slot."""
+    import torch
+    lib = L.load()
+    dev = src.device
+    for t, name in ((src, "src"), (dictionary, "dictionary")):
+        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
+    if dev.type != "cuda":
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n:
+        raise ValueError("in_off and in_len differ in length")
+    dlen = int(dictionary.numel())
+    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
+    d_len = in_len.to(device=dev, dtype=torch.int32).contiguous()
+    size = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), size, torch.empty(0, dtype=torch.int32, device=dev), status
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    sp = C.c_void_p(stream)
+    hist = torch.full((n,), dlen, dtype=torch.int64, device=dev).to(torch.int32)     # (the bit pattern of a u32)
+    rc = lib.lz4flex_decompressed_size_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                             C.c_void_p(hist.data_ptr()), C.c_void_p(size.data_ptr()), C.c_void_p(status.data_ptr()),
+                                             L.MEM_DEVICE, sp)
+    if rc:
+        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
+    incl = torch.cumsum(size, 0)
+    out_off = incl - size
+    total, biggest = (int(v) for v in torch.stack([incl[-1], size.max()]).cpu())     # the one synchronisation
+    if biggest > 0xFFFFFFFF:
+        raise ValueError("a block decompresses to %d bytes: more than the decoders' u32 out_cap" % biggest)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    cap = size.to(torch.int32)       # (the bit pattern of a u32 <= 0xFFFFFFFF)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    st2 = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib.lz4flex_decompress_batch_shared_dict(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
+                                                  C.c_void_p(out_len.data_ptr()), C.c_void_p(st2.data_ptr()), None,
+                                                  C.c_void_p(dictionary.data_ptr() if dlen else 0), dlen,
+                                                  L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if biggest > 131072 else 0), sp)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
+    # a block the size pass rejected keeps its status; the decoder's is the one of every other block (0 by the size pass's contract)
+    status = torch.where(status != 0, status, st2)
+    out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
+    return out[:total], out_off, out_len, status

@@ -90,6 +90,7 @@ struct lz4flex_ctx {
     int fail_next_batch = 0;      // tests: the next N batch calls on this context fail before they launch anything (what an allocation failure looks like to the caller)
     int comp_shared = 1;          // "compress_shared_dict": 1 = lz4flex_compress_batch_shared_dict starts its items from the dictionary's digest; 0 = every item takes the per-block path (A/B measurements, tests)
     bool shared_counted = false;  // the last shared-dictionary call ran the throughput encoder: its digest counter is what "debug_shared_dict_items" reads
+    int dec_shared = 1;           // "decompress_shared_dict": 1 = lz4flex_decompress_batch_shared_dict runs the sequence decoder's dictionary form; 0 = every block through decode_block<16, true>, the per-block path (A/B measurements, tests)
     int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
 };
 
@@ -224,6 +225,20 @@ static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a
     }
 #endif
     return launch_decompress_split(a, s, c->dec_blocks_per_wg);
+}
+
+// lz4flex_decompress_batch_shared_dict: every block of `a` (no per-block dictionaries, no prefix) against the ONE dictionary.  A wavefront
+// per block and a lane per sequence at every n (never worse than sixteen serial lanes per block); the blocks it marks are decoded again
+// in the reference's order with the dictionary.  "decompress_shared_dict" 0 / "decompress_variant" 1: that order for every block.
+static hipError_t launch_decompress_shared(lz4flex_ctx* c, const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
+    if (!c->dec_shared || c->dec_variant == 1) return launch_decompress_shared_dict(a, dict, dict_len, s);
+    constexpr int32_t REDO = 0x7F000001;
+    const hipError_t e = launch_decompress_seq_dict(a, dict, dict_len, REDO, s);
+    if (e != hipSuccess) return e;
+    if (!c->dec_second_pass) return hipSuccess;
+    DecompressArgs r = a;
+    r.only_status = REDO;
+    return launch_decompress_shared_dict(r, dict, dict_len, s);
 }
 
 // Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
@@ -585,6 +600,11 @@ int lz4flex_set_tuning(lz4flex_ctx* c, const char* key, int value) {
         c->comp_shared = value;
         return 0;
     }
+    if (!strcmp(key, "decompress_shared_dict")) {
+        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
+        c->dec_shared = value;
+        return 0;
+    }
     // Test hooks (fault injection; unsupported, see the header): only in a process that opted in with LZ4FLEX_TEST_HOOKS=1 (tests/conftest.py
     // does) -- the frame layer and every scalar call of a process share the default context, a hook set there by anybody else would make
     // unrelated users fail or take the slow redo path
@@ -649,6 +669,7 @@ int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     if (!strcmp(key, "decompress_lanes")) return c->dec_lanes;
     if (!strcmp(key, "size_scan_serial")) return c->size_serial;
     if (!strcmp(key, "compress_shared_dict")) return c->comp_shared;
+    if (!strcmp(key, "decompress_shared_dict")) return c->dec_shared;
     if (!strcmp(key, "debug_shared_dict_items")) {
         // the items of the last lz4flex_compress_batch_shared_dict call on this context whose first window started from the digest
         // (0: none yet, the reference-exact mode, "compress_shared_dict" 0); waits for the device
@@ -709,7 +730,7 @@ struct lz4flex_decompress_ext_ {
     const uint32_t* out_pos;
     const uint32_t* chain_prev;
     uint32_t n_chains;
-    const void* shared_dict;      // compress only: ONE dictionary of shared_len bytes for every block (no dict_base then)
+    const void* shared_dict;      // the *_shared_dict calls: ONE dictionary of shared_len bytes for every block (no dict_base then)
     uint32_t shared_len;
 };
 
@@ -826,7 +847,7 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
     }
     const size_t in_bytes = (size_t)(hb.in_span.hi - hb.in_span.lo);
     const size_t out_bytes = (size_t)(hb.out_span.hi - hb.out_span.lo);
-    const bool has_shared = compress && ext && ext->shared_dict && ext->shared_len;
+    const bool has_shared = ext && ext->shared_dict && ext->shared_len;
     const size_t dict_bytes = has_shared ? (size_t)ext->shared_len : has_dict ? (size_t)(hb.dict_span.hi - hb.dict_span.lo) : 0;
     // descriptor block (pinned host mirror and device copy share one layout)
     size_t o = 0;
@@ -904,7 +925,8 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
             a.chain_done = c->chain_ws;
             a.debug_giveup = (uint32_t)c->chain_giveup;
         }
-        le = ((c->dec_variant != 1 || chained) && !has_dict) ? launch_decompress_fast(c, a, s, big) : launch_decompress(a, c->dec_lanes, s);
+        if (has_shared) le = launch_decompress_shared(c, a, d + a_dict, ext->shared_len, s);
+        else le = ((c->dec_variant != 1 || chained) && !has_dict) ? launch_decompress_fast(c, a, s, big) : launch_decompress(a, c->dec_lanes, s);
         if (chained) (void)chain_ws_end(c, s);               // (also behind a failed launch: whatever was enqueued is ordered)
     }
     if (le != hipSuccess) return hip_fail(le, "kernel launch");
@@ -1022,7 +1044,8 @@ static int run_device_batch(lz4flex_ctx* c, bool compress, const void* in_base, 
             a.n_chains = ext->n_chains;
             a.debug_giveup = (uint32_t)c->chain_giveup;
         }
-        le = ((c->dec_variant != 1 || chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, big_hint != 0) : launch_decompress(a, c->dec_lanes, s);
+        if (ext && ext->shared_dict && ext->shared_len) le = launch_decompress_shared(c, a, (const uint8_t*)ext->shared_dict, ext->shared_len, s);
+        else le = ((c->dec_variant != 1 || chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, big_hint != 0) : launch_decompress(a, c->dec_lanes, s);
         if (chained && n) (void)chain_ws_end(c, s);
     }
     if (le != hipSuccess) return hip_fail(le, "kernel launch");
@@ -1151,6 +1174,30 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uin
         return run_device_batch(ctx, false, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len,
                                 status, detail, ext ? &e : nullptr, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0, chained);
     return -LZ4FLEX_E_INVALID_ARG;
+}
+
+int lz4flex_decompress_batch_shared_dict(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
+                                         uint32_t n, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
+                                         uint32_t* out_len, int32_t* status, uint64_t* detail, const void* dict, uint32_t dict_len,
+                                         int mem_kind, void* hip_stream) {
+    // (the arguments are checked before a context is looked for: a wrong call says so on any machine)
+    if (!dict && dict_len) return -LZ4FLEX_E_INVALID_ARG;
+    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
+    const int kind = mem_kind & ~LZ4FLEX_MEM_BIG_BLOCKS;
+    if (kind != LZ4FLEX_MEM_HOST && kind != LZ4FLEX_MEM_DEVICE) return -LZ4FLEX_E_INVALID_ARG;     // (LZ4FLEX_MEM_CHAINED among them)
+    if (n == 0) return 0;
+    if (!dict || !dict_len)
+        return lz4flex_decompress_batch(ctx, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, detail, mem_kind, hip_stream);
+    int rc;
+    if (!ctx && (rc = default_ctx(&ctx))) return rc;
+    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
+    lz4flex_decompress_ext_ e{};
+    e.shared_dict = dict; e.shared_len = dict_len;
+    if (kind == LZ4FLEX_MEM_HOST)
+        return run_host_batch(ctx, false, (const uint8_t*)in_base, in_off, in_len, nullptr, n, (uint8_t*)out_base, out_off,
+                              out_cap, out_len, status, detail, &e);
+    return run_device_batch(ctx, false, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len, status,
+                            detail, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
 }
 
 int lz4flex_decompress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,

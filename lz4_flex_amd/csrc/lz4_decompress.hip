@@ -233,6 +233,37 @@ __global__ void __launch_bounds__(256) lz4_decompress_blocks_kernel(DecompressAr
     }
 }
 
+// lz4flex_decompress_batch_shared_dict: decode_block<16, true> with ONE dictionary for every block -- no per-block dictionary arrays, no
+// workspace, any n.  only_status != 0: the second pass behind the sequence decoder's dictionary form (the blocks it marked, in the
+// reference's check order, WITH the dictionary); 0: every block ("decompress_shared_dict" 0, "decompress_variant" 1).
+__global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(DecompressArgs a, const uint8_t* dict, uint32_t dict_len) {
+    constexpr int G = 16;
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t b = tid / G;
+    const uint32_t g = tid % G;
+    if (b >= a.n) return;
+    if (a.only_status != 0 && a.status[b] != a.only_status) return;
+    const uint32_t cap = a.out_cap[b];
+    uint32_t produced = 0u;
+    uint64_t expected = 0u;
+    const int32_t st = decode_block<G, true>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g, &produced, &expected);
+    if (g == 0u) {
+        a.status[b] = st;
+        a.out_len[b] = st == 0 ? produced : 0u;
+        if (a.detail) {
+            a.detail[2u * b] = st == LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL ? expected : 0u;
+            a.detail[2u * b + 1u] = st == LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL ? (uint64_t)cap : 0u;
+        }
+    }
+}
+
+hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (dict == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, dict, dict_len);
+    return hipGetLastError();
+}
+
 // Second pass behind a CHAINED batch (Linked frames: block i's prefix is what blocks 0..i-1 of the batch write).  The marked blocks
 // of such a batch cannot be decoded side by side -- block k + 1 would read block k's last 64 KiB while block k is being written
 // again (status 0, wrong bytes) -- so ONE wavefront decodes them one after the other, in chain order.  Slow, and only

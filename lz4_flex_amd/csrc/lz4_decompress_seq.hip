@@ -217,7 +217,13 @@ __device__ __forceinline__ void walk_part(const g_u8* g, uint32_t t0, uint32_t i
     else { s.marks = m2; s.from = entry; s.exit = exit_; }
 }
 
-template <class G>
+// DICT (lz4flex_decompress_batch_shared_dict): ONE external dictionary for every block of the batch, decoded as prefix mode decodes a
+// prefix -- but the prefix lives in another buffer.  Positions are VIRTUAL: with dl = min(dict_len, 65 536) (an offset is at most
+// 65 535) and PV = dl rounded up to 16, positions [PV - dl, PV) are the dictionary's last dl bytes, PV + k is byte k of the block's
+// output, positions below LO = PV - dl do not exist.  `out` and `dv` are both biased by -PV: a position p >= PV is out[p] (every
+// store: F starts at PV, a multiple of 16, so write_back's units lie where they lie without a dictionary and none begins in front of
+// the sink), a position in [LO, PV) is dv[p] (loads only).  A 16-byte load that straddles PV is put together byte by byte.
+template <class G, bool DICT = false>
 struct Dec {
     const g_u8* in;
     g_u8* out;
@@ -225,6 +231,25 @@ struct Dec {
     uint32_t OP;         // bytes produced
     uint32_t W0;         // the window holds [W0, OP), W0 a multiple of 16
     uint32_t F;          // bytes written back, a multiple of 16 (W0 <= F)
+    const g_u8* dv;      // DICT: the dictionary's end - PV
+    uint32_t PV, LO;     // DICT: the output's first position; the oldest position there is
+
+    __device__ __forceinline__ uint32_t lo() const { return DICT ? LO : 0u; }
+    // DICT: where the byte of position p (>= LO; written back if >= PV) lies, and the byte (0 in front of LO)
+    __device__ __forceinline__ const g_u8* vp(uint32_t p) const { return (p < PV ? dv : (const g_u8*)out) + p; }
+    __device__ __forceinline__ uint32_t vbyte(uint32_t p) const { return p >= LO ? (uint32_t)*vp(p) : 0u; }
+    // DICT: the 16 bytes at position p, of which those in front of `lim` exist
+    __device__ __forceinline__ u32x4 vload16(uint32_t p, uint32_t lim) const {
+        u32x4 v;
+        if (p >= LO && p + 16u <= lim && (p >= PV || p + 16u <= PV)) __builtin_memcpy(&v, (const void*)vp(p), 16);
+        else {
+            uint32_t wv[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (uint32_t k = 0u; k < 16u; ++k) if (p + k < lim) wv[k >> 2] |= vbyte(p + k) << (8u * (k & 3u));
+            v = u32x4{wv[0], wv[1], wv[2], wv[3]};
+        }
+        return v;
+    }
 
     // window -> output, whole 16-byte units of [F, op)
     __device__ __forceinline__ void write_back(uint32_t op) {
@@ -276,7 +301,8 @@ struct Dec {
             const uint32_t i = i0 + 16u * lane;
             if (i < n) {
                 u32x4 v = {0u, 0u, 0u, 0u};
-                if (W0 + i + 16u <= OP) __builtin_memcpy(&v, (const void*)(out + W0 + i), 16);
+                if constexpr (DICT) v = vload16(W0 + i, OP);
+                else if (W0 + i + 16u <= OP) __builtin_memcpy(&v, (const void*)(out + W0 + i), 16);
                 else {
                     uint32_t wv[4] = {0u, 0u, 0u, 0u};
                     for (uint32_t k = 0u; k < 16u; ++k) if (W0 + i + k < OP) wv[k >> 2] |= (uint32_t)out[W0 + i + k] << (8u * (k & 3u));
@@ -302,6 +328,19 @@ struct Dec {
             SQ_JOIN();
         }
     }
+    // DICT: the same from position sp (a match's source: in the dictionary, in the output, or across both)
+    __device__ __forceinline__ void pos_copy(uint32_t sp, uint32_t n) {
+        for (uint32_t i0 = 0u; i0 < n; i0 += 1024u) {
+            const uint32_t i = i0 + 16u * lane;
+            if (i + 16u <= n) {
+                const u32x4 v = vload16(sp + i, sp + n);
+                __builtin_memcpy((void*)(out + OP + i), &v, 16);
+            } else if (i < n) {
+                for (uint32_t k = i; k < n; ++k) out[OP + k] = (uint8_t)vbyte(sp + k);
+            }
+            SQ_JOIN();
+        }
+    }
     __device__ __forceinline__ uint32_t mod_small(uint32_t i, uint32_t m, float rcp) {      // i mod m, i < 2^22, rcp = 1 / m
         const uint32_t q = (uint32_t)((float)i * rcp);
         uint32_t r = i - q * m;                                    // q is off by at most one either way
@@ -320,13 +359,15 @@ struct Dec {
     __device__ void big_match(uint32_t offset, uint32_t n) {
         flush_all();
         if (offset >= 1024u) {
-            mem_copy(out + OP - offset, n);
+            if constexpr (DICT) pos_copy(OP - offset, n);
+            else mem_copy(out + OP - offset, n);
         } else {
             const float rcp = 1.0f / (float)offset;
             const uint32_t el = offset + 1040u;
             for (uint32_t k0 = 0u; k0 < el; k0 += 64u) {
                 const uint32_t k = k0 + lane;
-                if (k < el) *L8(LDS_WIN + k) = out[OP - offset + mod_small(k, offset, rcp)];
+                if constexpr (DICT) { if (k < el) *L8(LDS_WIN + k) = (uint8_t)vbyte(OP - offset + mod_small(k, offset, rcp)); }
+                else if (k < el) *L8(LDS_WIN + k) = out[OP - offset + mod_small(k, offset, rcp)];
                 SQ_JOIN();
             }
             uint32_t ph = 0u;                                      // i0 mod offset
@@ -385,7 +426,7 @@ struct Dec {
                         si = r;
                     }
                     const uint32_t ps = src + si;
-                    const uint8_t byte = ps >= W0 ? *L8(LDS_WIN + ps - W0) : out[ps];
+                    const uint8_t byte = ps >= W0 ? *L8(LDS_WIN + ps - W0) : (DICT ? *vp(ps) : out[ps]);
                     *L8(LDS_WIN + d - W0 + i) = byte;
                 }
                 SQ_JOIN();
@@ -428,7 +469,7 @@ struct Dec {
                 if (b != 255u) break;
             }
         }
-        if (offset > OP || ml > cap - OP || OP + ml > POS_LIMIT) return false;
+        if (offset > OP - lo() || ml > cap - OP || OP + ml > POS_LIMIT) return false;
         coop_match(offset, ml);
         if (ip >= ilen) return false;              // a match is always followed by another token (decompress.rs:439-443)
         return true;
@@ -446,8 +487,8 @@ struct Chunk {
 
 // Set-up of the chunk that starts at sequence sidx with `op` bytes in front of it -- of which the last `pending` are still being
 // produced by the chunk before (room for both is made here: a slide never moves a placed chunk).  false: the block is irregular.
-template <class G>
-__device__ __forceinline__ bool setup_chunk(Dec<G>& D, uint32_t t0, uint32_t n_tile, uint32_t sidx, uint32_t op, uint32_t pending, Chunk& C) {
+template <class G, bool DICT>
+__device__ __forceinline__ bool setup_chunk(Dec<G, DICT>& D, uint32_t t0, uint32_t n_tile, uint32_t sidx, uint32_t op, uint32_t pending, Chunk& C) {
     const uint32_t lane = D.lane;
     const uint32_t ilr = D.ilen - t0;                          // the block's end, relative to t0
     const uint32_t tb = LDS_TILE + TPAD;
@@ -496,14 +537,16 @@ __device__ __forceinline__ bool setup_chunk(Dec<G>& D, uint32_t t0, uint32_t n_t
     const uint32_t src = dm - off;
     uint64_t am = low_mask(nact);
     const uint64_t hasm = ~lastm;
-    if ((ballot(off > dm) & hasm & am) != 0ull) return false;  // OffsetOutOfBounds (:286-289, :398-402)
+    if ((ballot(off > dm - D.lo()) & hasm & am) != 0ull) return false;  // OffsetOutOfBounds (:286-289, :398-402)
     // a source in front of the window comes from the written-back output: all of it has to be there, and short enough for a lane.
     // "The window" is what the NEXT chunk's set-up will have left of it when this chunk is copied: a slide keeps KEEP bytes in front
     // of the chunk that is pending then -- this one
     const uint32_t near_lo = op > G::KEEP && op - G::KEEP > D.W0 ? op - G::KEEP : D.W0;
     const uint64_t farm = ballot(src < near_lo) & hasm;
     {
-        const uint64_t fbig = farm & am & (ballot(src + ml > D.F) | ballot(ml > FARMAX));
+        uint64_t fbig = farm & am & (ballot(src + ml > D.F) | ballot(ml > FARMAX));
+        // DICT: a far source whose 16-byte loads could cross from the dictionary into the output is exact_seq's (byte loads)
+        if constexpr (DICT) fbig |= farm & am & ballot(src < D.PV && src + FARMAX > D.PV);
         if (fbig != 0ull) { nact = ctz64(fbig); am = low_mask(nact); T = nact != 0u ? rdlane(incl, nact - 1u) : 0u; }
     }
     C.lit = lit; C.ml = ml; C.dst = dst; C.src = src; C.lsr = lsr;
@@ -516,10 +559,11 @@ __device__ __forceinline__ bool setup_chunk(Dec<G>& D, uint32_t t0, uint32_t n_t
     // ---- far sources: requested now, used a chunk later --------------------------------------------------------------------------
     C.f0 = u32x4{0u, 0u, 0u, 0u}; C.f1 = C.f0; C.f2 = C.f0; C.f3 = C.f0;
     if (lanes(C.far)) {
-        __builtin_memcpy(&C.f0, (const void*)(D.out + src), 16);
-        if (ml > 16u) __builtin_memcpy(&C.f1, (const void*)(D.out + src + ml - 16u), 16);
-        if (ml > 32u) __builtin_memcpy(&C.f2, (const void*)(D.out + src + 16u), 16);
-        if (ml > 48u) __builtin_memcpy(&C.f3, (const void*)(D.out + src + 32u), 16);
+        const g_u8* fs = DICT ? D.vp(src) : D.out + src;       // (DICT: [src, src + FARMAX) lies on one side of PV)
+        __builtin_memcpy(&C.f0, (const void*)fs, 16);
+        if (ml > 16u) __builtin_memcpy(&C.f1, (const void*)(fs + ml - 16u), 16);
+        if (ml > 32u) __builtin_memcpy(&C.f2, (const void*)(fs + 16u), 16);
+        if (ml > 48u) __builtin_memcpy(&C.f3, (const void*)(fs + 32u), 16);
     }
     SQ_JOIN();
     return true;
@@ -574,8 +618,8 @@ __device__ __forceinline__ void lane_copy(const CopyPlan& P, uint64_t m) {
 }
 
 // The copies of a placed chunk (decompress.rs:276-280, 314-325, 357-361, 410-437).
-template <class G>
-__device__ __forceinline__ void exec_chunk(Dec<G>& D, const Chunk& C SQ_PROF_ARG) {
+template <class G, bool DICT>
+__device__ __forceinline__ void exec_chunk(Dec<G, DICT>& D, const Chunk& C SQ_PROF_ARG) {
     const uint32_t wb = LDS_WIN - D.W0;                        // window address of output position 0
     const uint32_t wl = wb + C.dst, wm = wl + C.lit;
     // ---- literals: 16 bytes per access, exact length ---------------------------------------------------------------------------
@@ -627,11 +671,11 @@ __device__ __forceinline__ void exec_chunk(Dec<G>& D, const Chunk& C SQ_PROF_ARG
 
 // The chunks of one tile: sequences [0, n_tile) of the token list.  Two chunks are in flight: the next one is set up (token decode,
 // placement, checks, room in the window, requests for far sources) before the current one is copied.  false: the block is irregular.
-template <class G>
-__device__ __forceinline__ bool run_chunks(Dec<G>& D, uint32_t t0, uint32_t n_tile, bool& done SQ_PROF_ARG) {
+template <class G, bool DICT>
+__device__ __forceinline__ bool run_chunks(Dec<G, DICT>& D, uint32_t t0, uint32_t n_tile, bool& done SQ_PROF_ARG) {
     uint32_t sidx = 0u;
     Chunk C;
-    if (!setup_chunk<G>(D, t0, n_tile, 0u, D.OP, 0u, C)) return false;
+    if (!setup_chunk<G, DICT>(D, t0, n_tile, 0u, D.OP, 0u, C)) return false;
     SQ_TICK(4)
     for (;;) {
         if (C.nact == 0u) {                                    // the sequence alone, by the whole wavefront
@@ -640,7 +684,7 @@ __device__ __forceinline__ bool run_chunks(Dec<G>& D, uint32_t t0, uint32_t n_ti
             SQ_TICK(9) SQ_COUNT(19, 1)
             if (done) return sidx == n_tile;
             if (sidx >= n_tile) return true;
-            if (!setup_chunk<G>(D, t0, n_tile, sidx, D.OP, 0u, C)) return false;
+            if (!setup_chunk<G, DICT>(D, t0, n_tile, sidx, D.OP, 0u, C)) return false;
             SQ_TICK(4)
             continue;
         }
@@ -650,10 +694,10 @@ __device__ __forceinline__ bool run_chunks(Dec<G>& D, uint32_t t0, uint32_t n_ti
         N.nact = 0u; N.T = 0u; N.tp0 = 0u; N.last = false; N.act = 0ull; N.haslit = 0ull; N.near = 0ull; N.far = 0ull;
         N.lit = 0u; N.ml = 0u; N.dst = 0u; N.src = 0u; N.lsr = 0u;
         N.f0 = u32x4{0u, 0u, 0u, 0u}; N.f1 = N.f0; N.f2 = N.f0; N.f3 = N.f0;
-        if (have_next) { if (!setup_chunk<G>(D, t0, n_tile, nsidx, nop, C.T, N)) return false; }
+        if (have_next) { if (!setup_chunk<G, DICT>(D, t0, n_tile, nsidx, nop, C.T, N)) return false; }
         SQ_TICK(4)
 #ifndef LZ4S_EXP_NOEXEC         // timing experiments only (wrong bytes): chunks are placed, nothing is copied
-        exec_chunk<G>(D, C SQ_PROF_PASS);
+        exec_chunk<G, DICT>(D, C SQ_PROF_PASS);
 #endif
         D.OP = nop;
         sidx = nsidx;
@@ -668,26 +712,41 @@ __device__ __forceinline__ bool run_chunks(Dec<G>& D, uint32_t t0, uint32_t n_ti
 #else
 #define LZ4S_WAVES_ATTR
 #endif
-template <class G>
-__global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code) {
+// DICT: every block of the batch has the ONE dictionary dict[0, dict_len) (device memory, dict_len != 0), and none has a prefix
+template <class G, bool DICT>
+__global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code, const uint8_t* dict, uint32_t dict_len) {
     extern __shared__ __attribute__((aligned(16))) uint8_t seq_lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= a.n) return;
     // (every LDS access below goes by byte address from 0: the dynamic segment is the kernel's only LDS)
     if ((uint32_t)(uintptr_t)(lds_u8*)seq_lds != 0u) { if (lane == 0u) { a.status[b] = redo_code; a.out_len[b] = 0u; } return; }
-    Dec<G> D;
+    Dec<G, DICT> D;
     D.in = (const g_u8*)(a.in_base + a.in_off[b]);
     D.out = (g_u8*)(a.out_base + a.out_off[b]);
     D.ilen = a.in_len[b];
     D.cap = a.out_cap[b];
     D.lane = lane;
     D.OP = 0u; D.W0 = 0u; D.F = 0u;
+    D.dv = nullptr; D.PV = 0u; D.LO = 0u;
     // PREFIX mode (out_pos, round 6; decompress_into_with_prefix-like: a Linked frame's block, src/frame/decompress.rs:195-222,280-305): the
     // sink already holds [0, PFX) of the stream, matches may reach into it, and the block's bytes follow at PFX -- for this decoder a source in
     // front of its window is a read of written-back output anyway; the prefix is the same read.  The window starts as the last KEEP bytes
     // of the prefix.  (Not for CHAINED batches: the bytes must be in memory when the launch starts -- a level of chains per launch.)
-    const uint32_t PFX = a.out_pos != nullptr ? uni(a.out_pos[b]) : 0u;
+    uint32_t PFX = 0u;
+    if constexpr (DICT) {
+        // the dictionary as a VIRTUAL prefix (see Dec): nothing is ever stored at a position below PV -- not into the dictionary every
+        // block shares, not in front of out_off -- and the capacity counts from PV (a sink so large that `cap + PV` would pass
+        // POS_LIMIT is cut there: a block that needs more is the reference-order kernel's)
+        const uint32_t dl = dict_len < 65536u ? dict_len : 65536u;
+        PFX = (dl + 15u) & ~15u;
+        D.PV = PFX; D.LO = PFX - dl;
+        D.dv = (const g_u8*)((uintptr_t)dict + dict_len - PFX);
+        D.out = (g_u8*)((uintptr_t)(a.out_base + a.out_off[b]) - PFX);
+        D.cap = (D.cap < POS_LIMIT - PFX ? D.cap : POS_LIMIT - PFX) + PFX;
+    } else {
+        PFX = a.out_pos != nullptr ? uni(a.out_pos[b]) : 0u;
+    }
     const uint32_t ilen = D.ilen;
     bool ok = ilen != 0u && ilen <= POS_LIMIT && PFX <= POS_LIMIT / 2u && D.cap >= PFX, done = false;     // (an empty block: decompress.rs:207-209, the reference-order kernel reports it)
     if (PFX != 0u && ok) { D.OP = PFX; D.reload_window(); }
@@ -810,7 +869,7 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
         entry = t0 + tile_exit;
         continue;
 #endif
-        if (!run_chunks<G>(D, t0, n_tile, tdone SQ_PROF_PASS)) { ok = false; break; }
+        if (!run_chunks<G, DICT>(D, t0, n_tile, tdone SQ_PROF_PASS)) { ok = false; break; }
         if (tdone) { done = true; break; }
         if (tile_exit >= ilr) { ok = false; break; }        // the chain ran out without a last sequence
         entry = t0 + tile_exit;
@@ -836,14 +895,25 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
 
 }  // namespace sq
 
-// Blocks without dictionary (a prefix in the sink is fine, round 6).  Irregular blocks get status `redo_code`; the caller runs launch_decompress with
+// Blocks without dictionary (a prefix in the sink is fine, round 6; one dictionary for the whole batch: launch_decompress_seq_dict).  Irregular blocks get status `redo_code`; the caller runs launch_decompress with
 // only_status = redo_code behind this launch.
 hipError_t launch_decompress_seq(const DecompressArgs& a, int32_t redo_code, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     if (a.dict_base != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;       // (a prefix -- out_pos -- is fine: see the kernel)
     typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
     static_assert(G::LDS <= 65536u, "the default limit of dynamic LDS: no function attribute to set per device");
-    hipLaunchKernelGGL(sq::lz4_decompress_seq_kernel<G>, dim3(a.n), dim3(64), G::LDS, s, a, redo_code);
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, false>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, (const uint8_t*)nullptr, 0u);
+    return hipGetLastError();
+}
+
+// Every block against the ONE dictionary dict[0, dict_len) (lz4flex_decompress_batch_shared_dict): the dictionary form of the kernel, no
+// per-block dictionary arrays, no prefix, no chain.  Irregular blocks get status `redo_code`; the caller runs
+// launch_decompress_shared_dict with only_status = redo_code behind this launch.
+hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (dict == nullptr || dict_len == 0u || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, true>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, dict, dict_len);
     return hipGetLastError();
 }
 

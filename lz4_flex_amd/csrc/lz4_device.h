@@ -132,6 +132,11 @@ hipError_t launch_decompress_chain_redo(const DecompressArgs& a, hipStream_t s);
 // 64 sequences at a time are placed by a prefix sum and copied by their lanes; irregular blocks are left with status redo_code for a
 // second pass of launch_decompress (only_status = redo_code), which decodes them in the reference's check order
 hipError_t launch_decompress_seq(const DecompressArgs& a, int32_t redo_code, hipStream_t s);
+// the same with ONE dictionary dict[0, dict_len) (device memory, dict_len != 0) for every block of the batch: the kernel's dictionary
+// form (no per-block dictionary arrays, no prefix, no chain); the second pass is launch_decompress_shared_dict with only_status = redo_code
+hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s);
+// lz4_decompress.hip's decode_block<16, true> with that one dictionary: a.only_status 0 = every block, else the marked ones
+hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s);
 hipError_t launch_decompress_split(const DecompressArgs& a, hipStream_t s, int blocks_per_wg = 0);   // parser / copier wavefronts, no dict/prefix
 // parser -> emitter -> quad wavefronts (lz4_decompress_fused.hip: the split decoder's parser, the replay decoder's copy engine, no dict/prefix);
 // blocks of 512 KiB or more are left with status redo_code for a second pass of launch_decompress.  -DLZ4FLEX_TOOLS builds only (round 6)
