@@ -400,7 +400,10 @@ int lz4flex_decompress_batch_shared_dict(lz4flex_ctx *ctx, const void *in_base, 
  *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict);
  *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
- * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1. */
+ * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.
+ * The key is looked at before a context is: an unknown key and a refused "debug_" key answer -LZ4FLEX_E_INVALID_ARG on any machine,
+ * a known key with ctx NULL needs the default context and with it a device (-LZ4FLEX_E_NO_DEVICE without one).  The same for
+ * lz4flex_get_tuning. */
 int lz4flex_set_tuning(lz4flex_ctx *ctx, const char *key, int value);
 /* the current value of a setting (>= 0), or -LZ4FLEX_E_INVALID_ARG for an unknown key.  Two read-only lists need no device and no
  * context: "dispatch_threshold_<i>" (the batch sizes at which the default decoder dispatch changes kernel or geometry, ascending) and

@@ -1,7 +1,18 @@
-// capi.cpp -- host side of the C ABI declared in include/lz4flex_amd.h: context / device
-// workspace management, the batched entry points (host- or device-resident buffers) and the
-// lz4_flex-shaped scalar calls, which are 1-block batches through the same HIP kernels.
-// There is no CPU codec in this library: every call that produces bytes launches a kernel.
+// capi.cpp -- host side of the C ABI declared in include/lz4flex_amd.h.  There is no CPU codec in this library: every call that
+// produces bytes launches a kernel.  How a batched call travels through this file:
+//   entry point      checks its arguments in ITS order (batch_arrays_ok, classify_mem, begin_batch / injected_failure), describes the
+//                    batch as a BatchCall (batch_of: the arrays every batch has; the rest by field name) and hands it to run_batch;
+//   run_host_batch   MEM_HOST: mirrors the caller's layout in the context's device arena, rebases the BatchCall onto it, launches,
+//                    copies the results back (run_host_small: the one-transfer-each-way form for a few small blocks, which the
+//                    lz4_flex-shaped scalar calls -- 1-block batches -- take);
+//   run_device_batch MEM_DEVICE: the caller's BatchCall as it is, on the caller's stream;
+//   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode (the
+//                    SharedDictArgs set-up, launch_compress_any) and launch_decode (the chain bracket and the choice between the
+//                    shared-dictionary, the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
+//                    shape, launch_redo is the second pass behind every first-pass decoder).
+// The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
+// DeviceGuard, Layout, GrowBuf) are in lz4_ctx.h; the integer settings are one table (SETTINGS) that lz4flex_set_tuning and
+// lz4flex_get_tuning walk.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +24,7 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "lz4_ctx.h"
 #include "lz4_device.h"
 #include "lz4_plan_common.h"
 
@@ -32,84 +44,52 @@ static int hip_fail(hipError_t e, const char* what) {
         if (_e != hipSuccess) return hip_fail(_e, #expr); \
     } while (0)
 
+// NULL context: the calling thread's default one (the scalar calls, the frame layer)
+static thread_local lz4flex_ctx* g_default_ctx = nullptr;
+static int default_ctx(lz4flex_ctx** out) {
+    if (!g_default_ctx) {
+        int rc = lz4flex_ctx_create(&g_default_ctx, -1);
+        if (rc) return rc;
+    }
+    *out = g_default_ctx;
+    return 0;
+}
+
 // compress_variant -> launch_compress mode bits: 1 = encode_block + emitter wave (default), 3 = encode_block alone
 static inline int comp_mode_bits(int v) { return v == 1 ? 0x600 : 0; }
-
-struct lz4flex_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint8_t* d_arena = nullptr;   // device staging for MEM_HOST calls
-    size_t arena_cap = 0;
-    uint8_t* h_pin = nullptr;     // pinned host staging for descriptor / result arrays
-    size_t pin_cap = 0;
-    uint8_t* h_pay = nullptr;     // pinned host staging for compacted results of MEM_HOST compress batches
-    size_t pay_cap = 0;
-    int dec_lanes = 16;           // lanes per block, decode
-    int comp_lanes = 8;           // lanes per block, encode
-    int comp_mode = 0;            // 0 = throughput ("wave") encoder, own parse (default); 1 = reference-exact encoder (lz4_flex's bytes)
-    int comp_variant = 1;         // reference-exact encoder: 1 = group encoder + emitter wave (default), 3 = group encoder alone
-    uint8_t* pcd_ws = nullptr;    // workgroup decoder, small batches: a parser and a copier workgroup per block hand token lists over through this (lz4_device.h pair_ws); one per context, ordered across streams like wave_ws
-    hipEvent_t pcd_done = nullptr;
-    hipStream_t pcd_last = nullptr;
-    bool pcd_used = false;
-    int dec_pcd_pair = 1;         // 1: two workgroups per block for batches of few large blocks; 0: never, 2: whenever the batch is small enough (tests, measurements)
-    uint32_t* chain_ws = nullptr; // chained decode batches (Linked frames): one "done" word per block, CHAIN_WS_BLOCKS of them; one per context, ordered across streams like wave_ws
-    hipEvent_t chain_evt = nullptr;
-    hipStream_t chain_last = nullptr;
-    bool chain_used = false;
-    void* wave_ws = nullptr;      // wave encoder workspace: wave_wgs persistent workgroups; allocated by lz4flex_ctx_create
-    unsigned long long* wave_prof = nullptr;   // tools: per-role cycle counters of the wave encoder (lz4flex_debug_wave_prof)
-    int wave_wgs = 0;
-    // The workspace is ONE per context, and MEM_DEVICE batches are enqueued on the caller's stream: two batches on different
-    // streams could overlap on the GPU and race on it.  Every wave launch records wave_done; a launch on another stream than
-    // the previous one first makes its stream wait for it (same stream: already ordered).
-    hipEvent_t wave_done = nullptr;
-    hipStream_t wave_last = nullptr;
-    bool wave_used = false;
-    int dec_blocks_per_wg = 0;    // split decoder: blocks per workgroup (8/16/32/64), 0 = 64
-    int comp_det = 0;             // "compress_deterministic": 1 = a block's bytes depend on the block and the settings alone (no sub-windows by batch size)
-    int dec_level_chains = 1024;  // "decompress_level_chains": from this many Linked streams in one *_many call on, block k of every stream is one plain launch (frame_many.cpp); 0 = never
-    int comp_sub = 0;             // throughput encoder, "compress_subwindows": 0 = by batch size, 1 = never, 2 / 4 = always that many sub-windows per block of <= 64 KiB
-    int dec_variant = 0;          // 0 = by batch size, 1 = window in HBM/L2 (lz4_decompress.hip), 4 = parser / copier split (lz4_decompress_split.hip), 7 = a workgroup per block (lz4_decompress_pcd.hip; 8: its test geometry; 10 / 11: 256 / 512 lanes), 13 = a wavefront per block, a lane per sequence (lz4_decompress_seq.hip); tools builds: 9 = plan / replay, 12 = parser / emitter / quads
-    int comp_sliding = 2;         // throughput encoder: the windows of a block longer than 64 KiB advance by 48 KiB (2: every window start has 16 KiB of history) or 32 KiB (1: round 4's bytes); 0 = by 64 KiB (round 3's bytes, fastest)
-    int comp_carry_wait = 1;      // tests: 0 = a window of the throughput encoder that has to wait for its predecessor's carry gives up at once (the block then takes the second launch)
-    int dec_second_pass = 1;      // tests: 0 leaves the blocks a first-pass decoder marked (status 0x7F000001) instead of decoding them again
-    // plan / replay decoder (lz4_decompress_plan.hip, lz4_decompress_replay.hip): the copy plans of a batch, plan_slot_words() words per
-    // block + a 32-byte header each.  Grows with the largest batch seen (a hipMalloc -- a device synchronisation -- in the first such
-    // call and whenever a larger batch arrives; never shrinks); one per context, ordered across streams like wave_ws.
-    uint8_t* plan_ws = nullptr;
-    size_t plan_cap = 0;
-    hipEvent_t plan_done = nullptr;
-    hipStream_t plan_last = nullptr;
-    bool plan_used = false;
-    int chain_giveup = 0;         // tests: block chain_giveup - 1 of the next chained decode batches gives up without an error (the ordered second pass decodes it and everything behind it)
-    // many frames at once (frame_many.cpp): device scratch of the calls that run to completion before they return (compressed staging,
-    // descriptor arrays, staged host buffers).  Grow-only, a hipMalloc when a larger job arrives; freed with the context.
-    void* many_ws[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t many_cap[4] = {0, 0, 0, 0};
-    int fail_next_batch = 0;      // tests: the next N batch calls on this context fail before they launch anything (what an allocation failure looks like to the caller)
-    int comp_shared = 1;          // "compress_shared_dict": 1 = lz4flex_compress_batch_shared_dict starts its items from the dictionary's digest; 0 = every item takes the per-block path (A/B measurements, tests)
-    bool shared_counted = false;  // the last shared-dictionary call ran the throughput encoder: its digest counter is what "debug_shared_dict_items" reads
-    int dec_shared = 1;           // "decompress_shared_dict": 1 = lz4flex_decompress_batch_shared_dict runs the sequence decoder's dictionary form; 0 = every block through decode_block<16, true>, the per-block path (A/B measurements, tests)
-    int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
-};
 
 static constexpr uint32_t PCD_MAX_BLOCKS = DISPATCH_PCD_256;     // up to here the default dispatch takes the workgroup decoder
 static constexpr uint32_t CHAIN_WS_BLOCKS = 65536u;      // blocks per chained decode batch (LZ4FLEX_MEM_CHAINED)
 
 // the decoders for blocks without dictionary / prefix
 // The "done" words of a chained batch are the context's: two chained batches on different streams would clear and poll the same
-// flags -- a launch on another stream than the previous one waits for it first, every launch records the event (ADVICE r3 for the
-// device path, r4 for the host path: ONE helper for both)
+// flags (ADVICE r3 for the device path, r4 for the host path: ONE helper for both).  The event is recorded behind the memset too: a
+// call that fails between here and chain_ws_end still leaves ordered work of this stream on the words.
 static hipError_t chain_ws_begin(lz4flex_ctx* c, uint32_t n, hipStream_t s) {
-    if (c->chain_used && s != c->chain_last) { const hipError_t w = hipStreamWaitEvent(s, c->chain_evt, 0); if (w != hipSuccess) return w; }
-    // (marked used BEFORE the kernels: a call that fails between here and its record still leaves work of this stream on the words)
-    c->chain_last = s; c->chain_used = true;
+    const hipError_t w = c->chain.acquire(s);
+    if (w != hipSuccess) return w;
     const hipError_t m = hipMemsetAsync(c->chain_ws, 0, 4ull * n, s);
     if (m != hipSuccess) return m;
-    return hipEventRecord(c->chain_evt, s);
+    return c->chain.release(s);
 }
-static hipError_t chain_ws_end(lz4flex_ctx* c, hipStream_t s) { return hipEventRecord(c->chain_evt, s); }
+static hipError_t chain_ws_end(lz4flex_ctx* c, hipStream_t s) { return c->chain.release(s); }
+
+// The second pass behind a first-pass decoder: the blocks it left marked DECODE_REDO (errors, sinks too small, shapes it does not
+// take) are decoded again in the reference's order of checks.  "decompress_second_pass" 0 (tests) leaves them marked.
+enum class Redo {
+    Blocks,       // launch_decompress: side by side
+    Chain,        // launch_decompress_chain_redo: a chained batch's marked blocks depend on each other -- in chain order
+    SharedDict,   // launch_decompress_shared_dict: with the batch's one dictionary
+};
+static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, Redo how = Redo::Blocks, const uint8_t* dict = nullptr,
+                              uint32_t dict_len = 0) {
+    if (!c->dec_second_pass) return hipSuccess;
+    DecompressArgs r = a;
+    r.only_status = DECODE_REDO;
+    if (how == Redo::Chain) return launch_decompress_chain_redo(r, s);
+    if (how == Redo::SharedDict) return launch_decompress_shared_dict(r, dict, dict_len, s);
+    return launch_decompress(r, c->dec_lanes, s);
+}
 
 static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a_, hipStream_t s, bool big_blocks = false) {
     DecompressArgs a = a_;
@@ -141,87 +121,68 @@ static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a
         // plan / replay: every block is turned into a copy plan (one wavefront per block, everything that is parallel), then the
         // plans are replayed (four lanes per block, the serial rest); blocks without a plan (errors, sinks too small, oversized) go
         // to the reference-order kernel
-        constexpr int32_t REDO = 0x7F000001;
         const size_t slot = plan_slot_words();
         const size_t need = (size_t)a.n * (slot * 4u + 32u) + 256u;
         if (need > c->plan_cap) {
-            if (c->plan_used) { const hipError_t w = hipEventSynchronize(c->plan_done); if (w != hipSuccess) return w; }
+            if (c->plan.used) { const hipError_t w = hipEventSynchronize(c->plan.done); if (w != hipSuccess) return w; }
             if (c->plan_ws) (void)hipFree(c->plan_ws);
             c->plan_ws = nullptr; c->plan_cap = 0;
             const hipError_t m = hipMalloc((void**)&c->plan_ws, need);
             if (m != hipSuccess) return m;
             c->plan_cap = need;
         }
-        if (c->plan_used && s != c->plan_last) { const hipError_t w = hipStreamWaitEvent(s, c->plan_done, 0); if (w != hipSuccess) return w; }
+        hipError_t e = c->plan.acquire(s);
+        if (e != hipSuccess) return e;
         PlanArgs pa;
         pa.in_base = a.in_base; pa.in_off = a.in_off; pa.in_len = a.in_len; pa.out_off = a.out_off; pa.out_cap = a.out_cap;
         pa.plans = (plan::BlockPlan*)c->plan_ws;
-        pa.words = (uint32_t*)(c->plan_ws + (((size_t)a.n * 32u + 255u) & ~(size_t)255u));
-        pa.out_len = a.out_len; pa.status = a.status; pa.n = a.n; pa.slot_words = (uint32_t)slot; pa.redo_code = REDO;
-        hipError_t e = launch_plan(pa, s);
+        pa.words = (uint32_t*)(c->plan_ws + align_up((size_t)a.n * 32u, 256));
+        pa.out_len = a.out_len; pa.status = a.status; pa.n = a.n; pa.slot_words = (uint32_t)slot; pa.redo_code = DECODE_REDO;
+        e = launch_plan(pa, s);
         if (e != hipSuccess) return e;
         ReplayArgs ra;
         ra.in_base = a.in_base; ra.out_base = a.out_base; ra.plans = pa.plans; ra.words = pa.words; ra.n = a.n; ra.max_turns = (uint32_t)(slot / plan::TURN_WORDS) + 2u;
         e = launch_replay(ra, s);
         if (e != hipSuccess) return e;
-        e = hipEventRecord(c->plan_done, s);
+        e = c->plan.release(s);
         if (e != hipSuccess) return e;
-        c->plan_last = s; c->plan_used = true;
         if (a.detail) { const hipError_t z = hipMemsetAsync(a.detail, 0, 16ull * a.n, s); if (z != hipSuccess) return z; }
-        if (!c->dec_second_pass) return hipSuccess;
-        DecompressArgs r = a;
-        r.only_status = REDO;
-        return launch_decompress(r, c->dec_lanes, s);
+        return launch_redo(c, a, s);
     }
 #endif
     if (v == 7 || v == 8 || v == 10 || v == 11) {
         // one block per workgroup; blocks it marks (errors, sinks too small) are decoded again in the reference's order
-        constexpr int32_t REDO = 0x7F000001;
         bool pair = false;
         if (v >= 7 && v <= 8 && (c->dec_pcd_pair == 2 || (c->dec_pcd_pair == 1 && big_blocks)) && c->pcd_ws && a.n <= PCD_PAIR_MAX_BLOCKS) {
             // few LARGE blocks: a parser and a copier workgroup each (half the CUs would idle otherwise; a block of one tile has
             // nothing to overlap and would only pay the hand-over: 64 KiB JSON blocks 0.144 -> 0.156 ms).  2 = always (tests).  The hand-over workspace is the
             // context's: launches on different streams are ordered by an event, as the encoder's are
-            if (c->pcd_used && s != c->pcd_last) { const hipError_t w = hipStreamWaitEvent(s, c->pcd_done, 0); if (w != hipSuccess) return w; }
+            const hipError_t w = c->pcd.acquire(s);
+            if (w != hipSuccess) return w;
             const hipError_t m = hipMemsetAsync(c->pcd_ws, 0, 64ull * a.n, s);
             if (m != hipSuccess) return m;
             a.pair_ws = c->pcd_ws;
             pair = true;
         }
-        hipError_t e = launch_decompress_pcd(a, REDO, s, pcd_geo);
+        hipError_t e = launch_decompress_pcd(a, DECODE_REDO, s, pcd_geo);
         if (e != hipSuccess) return e;
         if (pair) {
-            e = hipEventRecord(c->pcd_done, s);
+            e = c->pcd.release(s);
             if (e != hipSuccess) return e;
-            c->pcd_last = s; c->pcd_used = true;
             a.pair_ws = nullptr;
         }
-        if (!c->dec_second_pass) return hipSuccess;
-        DecompressArgs r = a;
-        r.only_status = REDO;
-        // a chained batch's marked blocks depend on each other: in chain order, not side by side
-        return r.chain_done ? launch_decompress_chain_redo(r, s) : launch_decompress(r, c->dec_lanes, s);
+        return launch_redo(c, a, s, a.chain_done ? Redo::Chain : Redo::Blocks);
     }
     if (v == 13) {
         // a wavefront per block, a lane per sequence (lz4_decompress_seq.hip); irregular blocks go to the reference-order kernel
-        constexpr int32_t REDO = 0x7F000001;
-        const hipError_t e = launch_decompress_seq(a, REDO, s);
-        if (e != hipSuccess) return e;
-        if (!c->dec_second_pass) return hipSuccess;
-        DecompressArgs r = a;
-        r.only_status = REDO;
-        return launch_decompress(r, c->dec_lanes, s);
+        const hipError_t e = launch_decompress_seq(a, DECODE_REDO, s);
+        return e != hipSuccess ? e : launch_redo(c, a, s);
     }
 #ifdef LZ4FLEX_TOOLS
     if (v == 12) {
         // parser -> emitter -> quads (lz4_decompress_fused.hip); oversized blocks go to the reference-order kernel
-        constexpr int32_t REDO = 0x7F000001;
-        const hipError_t e = launch_decompress_fused(a, REDO, s);
-        if (e != hipSuccess) return e;
-        if (!c->dec_second_pass) return hipSuccess;
-        DecompressArgs r = a;
-        r.only_status = REDO;
-        return launch_decompress(r, c->dec_lanes, s);
+        const hipError_t e = launch_decompress_fused(a, DECODE_REDO, s);
+        return e != hipSuccess ? e : launch_redo(c, a, s);
     }
 #endif
     return launch_decompress_split(a, s, c->dec_blocks_per_wg);
@@ -232,13 +193,8 @@ static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a
 // in the reference's order with the dictionary.  "decompress_shared_dict" 0 / "decompress_variant" 1: that order for every block.
 static hipError_t launch_decompress_shared(lz4flex_ctx* c, const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
     if (!c->dec_shared || c->dec_variant == 1) return launch_decompress_shared_dict(a, dict, dict_len, s);
-    constexpr int32_t REDO = 0x7F000001;
-    const hipError_t e = launch_decompress_seq_dict(a, dict, dict_len, REDO, s);
-    if (e != hipSuccess) return e;
-    if (!c->dec_second_pass) return hipSuccess;
-    DecompressArgs r = a;
-    r.only_status = REDO;
-    return launch_decompress_shared_dict(r, dict, dict_len, s);
+    const hipError_t e = launch_decompress_seq_dict(a, dict, dict_len, DECODE_REDO, s);
+    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::SharedDict, dict, dict_len);
 }
 
 // Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
@@ -289,18 +245,41 @@ __global__ void lz4flex_fill_shared_dict_kernel(uint64_t* dict_off, uint32_t* di
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < n) { dict_off[b] = 0ull; dict_len[b] = len; }
 }
+// MEM_HOST batches whose results are sparse in the output span (compress: ~15 KB used of every 72 KB stride):
+// pack the produced bytes densely on the device so that ONE transfer brings them to the host.
+__global__ void __launch_bounds__(256) lz4flex_pack_results_kernel(const uint8_t* src, const uint64_t* src_off, const uint32_t* len,
+                                                                   const int32_t* status, const uint64_t* dst_off, uint8_t* dst,
+                                                                   uint32_t n) {
+    const uint32_t b = blockIdx.x;
+    if (b >= n || status[b] != 0) return;
+    const uint8_t* s = src + src_off[b];
+    uint8_t* d = dst + dst_off[b];
+    const uint32_t m = len[b];
+    for (uint32_t i = threadIdx.x; i < m; i += 256u) d[i] = s[i];
+}
 
-static inline size_t align_up_(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// staging memory that has to hold `need` bytes; a failed allocation is this thread's last error like every other HIP failure
+static int ensure_buf(GrowBuf& b, size_t need) {
+    const hipError_t e = b.ensure(need);
+    return e == hipSuccess ? 0 : hip_fail(e, b.pinned ? "hipHostMalloc (staging)" : "hipMalloc (staging)");
+}
+
+// the throughput encoder's workspace (it also holds the reference-exact mode's dictionary chain records): ordered across streams
+static int wave_ws_acquire(lz4flex_ctx* c, hipStream_t s) {
+    if (!c->wave_ws || !c->wave.done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
+    HIP_TRY(c->wave.acquire(s));
+    return 0;
+}
 
 // the encoders for independent blocks: throughput mode (own parse, any block length) or the reference-exact one
 // shared (nullable): ONE dictionary for every block (lz4flex_compress_batch_shared_dict; a has no dictionaries and no flags then)
 static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big, hipStream_t s, const SharedDictArgs* shared = nullptr) {
     hipError_t le;
+    int rc;
     CompressArgs a = a_;
     if (shared) c->shared_counted = c->comp_mode == 0;
     if (c->comp_mode == 0) {
-        if (!c->wave_ws || !c->wave_done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
-        if (c->wave_used && s != c->wave_last) HIP_TRY(hipStreamWaitEvent(s, c->wave_done, 0));
+        if ((rc = wave_ws_acquire(c, s))) return rc;
         CompressArgs aw = a;
         aw.slide = c->comp_sliding == 2 ? 49152u : (c->comp_sliding == 1 ? 32768u : 0u);
         // sub-windows (lz4_compress_wave.hip Item::sub): batches that leave at least half / three quarters of the persistent workgroups
@@ -308,11 +287,7 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
         aw.sub = c->comp_det ? 1u : c->comp_sub != 0 ? (uint32_t)c->comp_sub
                                   : (a.n * 4u <= (uint32_t)c->wave_wgs ? 4u : (a.n * 3u <= (uint32_t)c->wave_wgs ? 3u : (a.n * 2u <= (uint32_t)c->wave_wgs ? 2u : 1u)));
         le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0, shared);
-        if (le == hipSuccess) {
-            HIP_TRY(hipEventRecord(c->wave_done, s));
-            c->wave_last = s;
-            c->wave_used = true;
-        }
+        if (le == hipSuccess) HIP_TRY(c->wave.release(s));
     } else {
         // (blocks with a dictionary are left alone by both launches below and encoded by the chain kernel behind them)
         // (a shared dictionary: every block has it, the chain kernel encodes them all)
@@ -325,16 +300,15 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
         if (le == hipSuccess && (a.dict_len || shared) && a.n) {
             // one-block chains, their records in the (otherwise idle) throughput encoder's workspace: no allocation, ordered across
             // streams like the encoder's own launches; batches larger than the workspace holds records for run in pieces
-            if (!c->wave_ws || !c->wave_done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
-            if (c->wave_used && s != c->wave_last) HIP_TRY(hipStreamWaitEvent(s, c->wave_done, 0));
+            if ((rc = wave_ws_acquire(c, s))) return rc;
             const size_t per = sizeof(lz4flex_chain_block) + 4u + (shared ? 12u : 0u);
             const uint32_t piece = (uint32_t)std::min<size_t>(compress_wave_workspace_bytes(c->wave_wgs) / per - 64u, 0x40000000u);
             lz4flex_chain_block* rec = (lz4flex_chain_block*)c->wave_ws;
-            uint32_t* cnt = (uint32_t*)((uint8_t*)c->wave_ws + align_up_(sizeof(lz4flex_chain_block) * (size_t)piece, 256));
+            uint32_t* cnt = (uint32_t*)((uint8_t*)c->wave_ws + align_up(sizeof(lz4flex_chain_block) * (size_t)piece, 256));
             if (shared) {
                 // the one dictionary as per-block arrays of one piece (every piece reads the same ones), behind the records in the workspace
-                uint64_t* soff = (uint64_t*)((uint8_t*)cnt + align_up_(4u * (size_t)piece, 256));
-                uint32_t* slen = (uint32_t*)((uint8_t*)soff + align_up_(8u * (size_t)piece, 256));
+                uint64_t* soff = (uint64_t*)((uint8_t*)cnt + align_up(4u * (size_t)piece, 256));
+                uint32_t* slen = (uint32_t*)((uint8_t*)soff + align_up(8u * (size_t)piece, 256));
                 const uint32_t m = std::min<uint32_t>(piece, a.n);
                 hipLaunchKernelGGL(lz4flex_fill_shared_dict_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, soff, slen, m, shared->len);
                 le = hipGetLastError();
@@ -350,57 +324,88 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
                     le = launch_compress_chain(a.in_base, rec, nullptr, cnt, m, a.out_base, a.out_off + b0, a.out_cap + b0, a.out_len + b0,
                                                a.status + b0, nullptr, s, a.dict_base);
             }
-            if (le == hipSuccess) {
-                HIP_TRY(hipEventRecord(c->wave_done, s));
-                c->wave_last = s;
-                c->wave_used = true;
-            }
+            if (le == hipSuccess) HIP_TRY(c->wave.release(s));
         }
     }
     if (le != hipSuccess) return hip_fail(le, "kernel launch");
     return 0;
 }
 
-static int ensure_arena(lz4flex_ctx* c, size_t need) {
-    if (need <= c->arena_cap) return 0;
-    if (c->d_arena) { (void)hipFree(c->d_arena); c->d_arena = nullptr; c->arena_cap = 0; }
-    size_t cap = std::max<size_t>(need + need / 4, 1u << 20);
-    HIP_TRY(hipMalloc((void**)&c->d_arena, cap));
-    c->arena_cap = cap;
-    return 0;
-}
-static int ensure_pin(lz4flex_ctx* c, size_t need) {
-    if (need <= c->pin_cap) return 0;
-    if (c->h_pin) { (void)hipHostFree(c->h_pin); c->h_pin = nullptr; c->pin_cap = 0; }
-    size_t cap = std::max<size_t>(need + need / 4, 1u << 16);
-    HIP_TRY(hipHostMalloc((void**)&c->h_pin, cap, hipHostMallocDefault));
-    c->pin_cap = cap;
-    return 0;
+// ------------------------------------------------------------------------------------------
+// One batch, as every batched entry point and every scalar call describes it.  The pointers are the caller's (host memory for
+// run_host_batch, device memory for run_device_batch and launch_batch); what a call does not use stays null / 0.
+struct BatchCall {
+    bool compress = false;
+    const uint8_t* in_base = nullptr;
+    const uint64_t* in_off = nullptr;
+    const uint32_t* in_len = nullptr;
+    const uint32_t* flags = nullptr;        // compress, nullable
+    uint32_t n = 0;
+    uint8_t* out_base = nullptr;
+    const uint64_t* out_off = nullptr;
+    const uint32_t* out_cap = nullptr;
+    uint32_t* out_len = nullptr;
+    int32_t* status = nullptr;
+    uint64_t* detail = nullptr;             // decompress, nullable
+    const uint8_t* dict_base = nullptr;     // per-block dictionaries (the *_ex calls): all three or none
+    const uint64_t* dict_off = nullptr;
+    const uint32_t* dict_len = nullptr;
+    const uint8_t* shared_dict = nullptr;   // the *_shared_dict calls: ONE dictionary of shared_len bytes for every block (no dict_base then)
+    uint32_t shared_len = 0;
+    const uint32_t* out_pos = nullptr;      // decompress: prefix mode
+    const uint32_t* chain_prev = nullptr;   // chained DEVICE batches: several chains side by side
+    uint32_t n_chains = 0;
+    bool has_ext = false;                   // the caller handed an extension struct over, whatever it holds: such a host batch takes the general path
+    bool chained = false;                   // LZ4FLEX_MEM_CHAINED
+    bool big = false;                       // LZ4FLEX_MEM_BIG_BLOCKS, or -- host batches -- what the lengths say
+    hipStream_t stream = nullptr;           // DEVICE batches: the caller's (NULL = HIP's null stream); host batches: the context's
+};
+
+// the arrays every batch has, in the order the public entry points take them
+static BatchCall batch_of(bool compress, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* out_base,
+                          const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status, void* hip_stream = nullptr) {
+    BatchCall b;
+    b.compress = compress;
+    b.in_base = (const uint8_t*)in_base; b.in_off = in_off; b.in_len = in_len; b.n = n;
+    b.out_base = (uint8_t*)out_base; b.out_off = out_off; b.out_cap = out_cap; b.out_len = out_len; b.status = status;
+    b.stream = (hipStream_t)hip_stream;
+    return b;
 }
 
-static int ensure_pay(lz4flex_ctx* c, size_t need) {
-    if (need <= c->pay_cap) return 0;
-    if (c->h_pay) { (void)hipHostFree(c->h_pay); c->h_pay = nullptr; c->pay_cap = 0; }
-    size_t cap = std::max<size_t>(need + need / 4, 1u << 20);
-    HIP_TRY(hipHostMalloc((void**)&c->h_pay, cap, hipHostMallocDefault));
-    c->pay_cap = cap;
-    return 0;
+static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
+    CompressArgs a{};
+    a.in_base = b.in_base; a.in_off = b.in_off; a.in_len = b.in_len; a.flags = b.flags;
+    a.out_base = b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.out_len = b.out_len; a.status = b.status; a.n = b.n;
+    if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
+    SharedDictArgs sh{};
+    sh.dict = b.shared_dict; sh.len = b.shared_len; sh.use = (uint32_t)c->comp_shared;
+    return launch_compress_any(c, a, b.big, b.stream, b.shared_dict && b.shared_len ? &sh : nullptr);
 }
 
-// MEM_HOST batches whose results are sparse in the output span (compress: ~15 KB used of every 72 KB stride):
-// pack the produced bytes densely on the device so that ONE transfer brings them to the host.
-__global__ void __launch_bounds__(256) lz4flex_pack_results_kernel(const uint8_t* src, const uint64_t* src_off, const uint32_t* len,
-                                                                   const int32_t* status, const uint64_t* dst_off, uint8_t* dst,
-                                                                   uint32_t n) {
-    const uint32_t b = blockIdx.x;
-    if (b >= n || status[b] != 0) return;
-    const uint8_t* s = src + src_off[b];
-    uint8_t* d = dst + dst_off[b];
-    const uint32_t m = len[b];
-    for (uint32_t i = threadIdx.x; i < m; i += 256u) d[i] = s[i];
+static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
+    hipStream_t s = b.stream;
+    DecompressArgs a{};
+    a.in_base = b.in_base; a.in_off = b.in_off; a.in_len = b.in_len;
+    a.out_base = b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.out_pos = b.out_pos;
+    a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len;
+    a.out_len = b.out_len; a.status = b.status; a.detail = b.detail; a.n = b.n;
+    const bool chain = b.chained && b.n;
+    if (chain) {
+        HIP_TRY(chain_ws_begin(c, b.n, s));
+        a.chain_done = c->chain_ws;
+        a.chain_prev = b.chain_prev;
+        a.n_chains = b.n_chains;
+        a.debug_giveup = (uint32_t)c->chain_giveup;
+    }
+    hipError_t le;
+    if (b.shared_dict && b.shared_len) le = launch_decompress_shared(c, a, b.shared_dict, b.shared_len, s);
+    // "decompress_variant" 1 and blocks with dictionaries: the reference-order kernel (a chain has no such form)
+    else le = ((c->dec_variant != 1 || b.chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, b.big) : launch_decompress(a, c->dec_lanes, s);
+    if (chain) (void)chain_ws_end(c, s);                     // (also behind a failed launch: whatever was enqueued is ordered)
+    return le != hipSuccess ? hip_fail(le, "kernel launch") : 0;
 }
 
-static int default_ctx(lz4flex_ctx** out);
+static int launch_batch(lz4flex_ctx* c, const BatchCall& b) { return b.compress ? launch_encode(c, b) : launch_decode(c, b); }
 
 extern "C" {
 
@@ -440,28 +445,28 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     if (const char* e = getenv("LZ4FLEX_COMPRESS_VARIANT")) { const int v = atoi(e); if (v == 1 || v == 3) c->comp_variant = v; }
 #endif
     if (const char* e = getenv("LZ4FLEX_DECOMPRESS_VARIANT")) { const int v = atoi(e); if (v == 0 || v == 1 || (v >= 4 && v <= 12 && v != 9)) c->dec_variant = v; }
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    // the throughput encoder's workspace (two 80 KiB workgroups per CU, 196 MiB on an MI355X with the dictionary staging slots) and its ordering event: here, not
-    // inside the first compress call -- a hipMalloc in an "asynchronous" entry point is a device synchronisation and breaks
-    // stream capture
-    if (e == hipSuccess) {
-        int cus = 0;
-        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    {
+        DeviceGuard guard(device);
+        e = guard.err;
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+        // the throughput encoder's workspace (two 80 KiB workgroups per CU, 196 MiB on an MI355X with the dictionary staging slots) and its ordering event: here, not
+        // inside the first compress call -- a hipMalloc in an "asynchronous" entry point is a device synchronisation and breaks
+        // stream capture
         if (e == hipSuccess) {
-            c->wave_wgs = 2 * cus;
-            e = hipMalloc(&c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs));
+            int cus = 0;
+            e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+            if (e == hipSuccess) {
+                c->wave_wgs = 2 * cus;
+                e = hipMalloc(&c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs));
+            }
         }
+        if (e == hipSuccess) e = c->wave.create();
+        if (e == hipSuccess) e = hipMalloc((void**)&c->chain_ws, 4u * CHAIN_WS_BLOCKS);
+        if (e == hipSuccess) e = c->chain.create();
+        if (e == hipSuccess) e = c->plan.create();
+        if (e == hipSuccess) e = c->pcd.create();
+        if (e == hipSuccess) e = hipMalloc((void**)&c->pcd_ws, decompress_pcd_pair_ws_bytes());
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->wave_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->chain_ws, 4u * CHAIN_WS_BLOCKS);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->chain_evt, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->plan_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->pcd_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->pcd_ws, decompress_pcd_pair_ws_bytes());
-    (void)hipSetDevice(prev);
     if (e != hipSuccess) {
         const int rc = hip_fail(e, "ctx_create");
         lz4flex_ctx_destroy(c);
@@ -473,19 +478,19 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
 
 void lz4flex_ctx_destroy(lz4flex_ctx* c) {
     if (!c) return;
-    if (c->d_arena) (void)hipFree(c->d_arena);
+    c->arena.free();
     if (c->wave_ws) (void)hipFree(c->wave_ws);
-    if (c->wave_done) (void)hipEventDestroy(c->wave_done);
+    c->wave.destroy();
     if (c->chain_ws) (void)hipFree(c->chain_ws);
-    if (c->chain_evt) (void)hipEventDestroy(c->chain_evt);
+    c->chain.destroy();
     if (c->plan_ws) (void)hipFree(c->plan_ws);
-    if (c->plan_done) (void)hipEventDestroy(c->plan_done);
+    c->plan.destroy();
     if (c->pcd_ws) (void)hipFree(c->pcd_ws);
-    if (c->pcd_done) (void)hipEventDestroy(c->pcd_done);
+    c->pcd.destroy();
     if (c->wave_prof) (void)hipFree(c->wave_prof);
     for (void* p : c->many_ws) if (p) (void)hipFree(p);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_pay) (void)hipHostFree(c->h_pay);
+    c->pin.free();
+    c->pay.free();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -510,134 +515,119 @@ int lz4flex_debug_wave_prof(lz4flex_ctx* c, int enable, unsigned long long* vals
 }
 #endif
 
+}  // extern "C"
+
+// ---- the integer settings: key, field, the values it takes.  lz4flex_set_tuning and lz4flex_get_tuning walk this one table.
+namespace {
+
+struct Setting {
+    const char* key;
+    int lz4flex_ctx::* field;
+    bool (*takes)(int value);
+    bool set_only;
+};
+bool is_flag(int v) { return v == 0 || v == 1; }
+bool is_count(int v) { return v >= 0; }
+bool up_to_2(int v) { return v >= 0 && v <= 2; }
+bool read_only(int) { return false; }
+
+const Setting SETTINGS[] = {
+    {"decompress_lanes", &lz4flex_ctx::dec_lanes, [](int v) {
+#ifdef LZ4FLEX_ALL_VARIANTS
+         return v == 8 || v == 16 || v == 32 || v == 64;
+#else
+         return v == 16;                                        // the other widths exist in variant builds only (-DLZ4FLEX_ALL_VARIANTS)
+#endif
+     }, false},
+    {"compress_mode", &lz4flex_ctx::comp_mode, is_flag, false},
+    {"compress_subwindows", &lz4flex_ctx::comp_sub, [](int v) { return v >= 0 && v <= 4; }, false},
+    {"compress_deterministic", &lz4flex_ctx::comp_det, is_flag, false},
+    {"decompress_level_chains", &lz4flex_ctx::dec_level_chains, is_count, false},
+    {"decompress_blocks_per_wg", &lz4flex_ctx::dec_blocks_per_wg, [](int v) { return v == 0 || v == 8 || v == 16 || v == 32 || v == 64; }, false},
+    {"decompress_variant", &lz4flex_ctx::dec_variant, [](int v) {
+         if (v != 0 && v != 1 && (v < 4 || v > 13)) return false;
+         if (v == 5 || v == 6) return false;                    // the wave decoder and its two-wavefront form: replaced by 13 in round 6
+#ifndef LZ4FLEX_TOOLS
+         if (v == 9 || v == 12) return false;                   // plan / replay, parser / emitter / quads: tools builds only
+#endif
+         return true;
+     }, false},
+    {"decompress_second_pass", &lz4flex_ctx::dec_second_pass, is_flag, false},
+    {"decompress_pcd_pair", &lz4flex_ctx::dec_pcd_pair, up_to_2, false},
+    {"compress_carry_wait", &lz4flex_ctx::comp_carry_wait, is_flag, false},
+    {"compress_sliding_window", &lz4flex_ctx::comp_sliding, up_to_2, false},
+    {"compress_variant", &lz4flex_ctx::comp_variant, [](int v) {
+#ifdef LZ4FLEX_ALL_VARIANTS
+         return v == 1 || v == 3;
+#else
+         return v == 1;                                         // 3 (no emitter wavefront) exists in variant builds only
+#endif
+     }, false},
+    {"compress_lanes", &lz4flex_ctx::comp_lanes, [](int v) { return v == 8 || v == 16; }, false},
+    {"size_scan_serial", &lz4flex_ctx::size_serial, is_flag, false},
+    {"compress_shared_dict", &lz4flex_ctx::comp_shared, is_flag, false},
+    {"decompress_shared_dict", &lz4flex_ctx::dec_shared, is_flag, false},
+    // (what "compress_subwindows" 0 decides by: n * 4 <= this -> 4, n * 3 <= this -> 3, n * 2 <= this -> 2)
+    {"compress_workgroups", &lz4flex_ctx::wave_wgs, read_only, false},
+    {"debug_chain_giveup", &lz4flex_ctx::chain_giveup, is_count, true},
+    {"debug_fail_next_batch", &lz4flex_ctx::fail_next_batch, is_count, true},      // tests/test_gpu_sharded_native.py: one rank's call-level failure
+};
+const Setting* find_setting(const char* key) {
+    for (const Setting& s : SETTINGS) if (!strcmp(key, s.key)) return &s;
+    return nullptr;
+}
+
+// Test hooks (every "debug_" key; fault injection, unsupported, see the header): only in a process that opted in with LZ4FLEX_TEST_HOOKS=1
+// (tests/conftest.py does) -- the frame layer and every scalar call of a process share the default context, a hook set there by anybody
+// else would make unrelated users fail or take the slow redo path.  Refused before a context is looked for.
+bool key_allowed(const char* key) {
+    if (strncmp(key, "debug_", 6) != 0) return true;
+    const char* e = getenv("LZ4FLEX_TEST_HOOKS");
+    return e && !strcmp(e, "1");
+}
+
+// "<prefix><i>": entry i of a list that ends where the key is refused
+int list_entry(const char* index, const int* t, int n) {
+    const int i = atoi(index);
+    if (i < 0 || i >= n || index[0] < '0' || index[0] > '9') return -LZ4FLEX_E_INVALID_ARG;
+    return t[i];
+}
+
+// "debug_shared_dict_items": the items of the last lz4flex_compress_batch_shared_dict call on this context whose first window started
+// from the digest (0: none yet, the reference-exact mode, "compress_shared_dict" 0); waits for the device
+int shared_dict_items(lz4flex_ctx* c) {
+    if (!c->shared_counted || !c->wave_ws) return 0;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    uint32_t v = 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&v, compress_wave_shared_counter(c->wave_ws, c->wave_wgs), 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "debug_shared_dict_items");
+    return (int)std::min<uint32_t>(v, 0x7FFFFFFFu);
+}
+
+}  // namespace
+
+extern "C" {
+
 int lz4flex_set_tuning(lz4flex_ctx* c, const char* key, int value) {
     if (!key) return -LZ4FLEX_E_INVALID_ARG;
+    const Setting* st = find_setting(key);
+    if (!st || !key_allowed(key)) return -LZ4FLEX_E_INVALID_ARG;
     if (!c) { const int rc = default_ctx(&c); if (rc) return rc; }   // NULL: this thread's default context (the scalar calls)
-    if (!strcmp(key, "decompress_lanes")) {
-#ifdef LZ4FLEX_ALL_VARIANTS
-        if (value != 8 && value != 16 && value != 32 && value != 64) return -LZ4FLEX_E_INVALID_ARG;
-#else
-        if (value != 16) return -LZ4FLEX_E_INVALID_ARG;          // the other widths exist in variant builds only (-DLZ4FLEX_ALL_VARIANTS)
-#endif
-        c->dec_lanes = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_mode")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_mode = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_subwindows")) {
-        if (value < 0 || value > 4) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_sub = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_deterministic")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_det = value;
-        return 0;
-    }
-    if (!strcmp(key, "decompress_level_chains")) {
-        if (value < 0) return -LZ4FLEX_E_INVALID_ARG;
-        c->dec_level_chains = value;
-        return 0;
-    }
-    if (!strcmp(key, "decompress_blocks_per_wg")) {
-        if (value != 0 && value != 8 && value != 16 && value != 32 && value != 64) return -LZ4FLEX_E_INVALID_ARG;
-        c->dec_blocks_per_wg = value;
-        return 0;
-    }
-    if (!strcmp(key, "decompress_variant")) {
-        if (value != 0 && value != 1 && (value < 4 || value > 13)) return -LZ4FLEX_E_INVALID_ARG;
-        if (value == 5 || value == 6) return -LZ4FLEX_E_INVALID_ARG;      // the wave decoder and its two-wavefront form: replaced by 13 in round 6
-#ifndef LZ4FLEX_TOOLS
-        if (value == 9 || value == 12) return -LZ4FLEX_E_INVALID_ARG;     // plan / replay, parser / emitter / quads: tools builds only
-#endif
-        c->dec_variant = value;
-        return 0;
-    }
-    if (!strcmp(key, "decompress_second_pass")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->dec_second_pass = value;
-        return 0;
-    }
-    if (!strcmp(key, "decompress_pcd_pair")) {
-        if (value < 0 || value > 2) return -LZ4FLEX_E_INVALID_ARG;
-        c->dec_pcd_pair = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_carry_wait")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_carry_wait = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_sliding_window")) {
-        if (value < 0 || value > 2) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_sliding = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_variant")) {
-#ifdef LZ4FLEX_ALL_VARIANTS
-        if (value != 1 && value != 3) return -LZ4FLEX_E_INVALID_ARG;
-#else
-        if (value != 1) return -LZ4FLEX_E_INVALID_ARG;           // 3 (no emitter wavefront) exists in variant builds only
-#endif
-        c->comp_variant = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_lanes")) {
-        if (value != 8 && value != 16) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_lanes = value;
-        return 0;
-    }
-    if (!strcmp(key, "size_scan_serial")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->size_serial = value;
-        return 0;
-    }
-    if (!strcmp(key, "compress_shared_dict")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->comp_shared = value;
-        return 0;
-    }
-    if (!strcmp(key, "decompress_shared_dict")) {
-        if (value != 0 && value != 1) return -LZ4FLEX_E_INVALID_ARG;
-        c->dec_shared = value;
-        return 0;
-    }
-    // Test hooks (fault injection; unsupported, see the header): only in a process that opted in with LZ4FLEX_TEST_HOOKS=1 (tests/conftest.py
-    // does) -- the frame layer and every scalar call of a process share the default context, a hook set there by anybody else would make
-    // unrelated users fail or take the slow redo path
-    if (!strncmp(key, "debug_", 6)) {
-        const char* e = getenv("LZ4FLEX_TEST_HOOKS");
-        if (!e || strcmp(e, "1") != 0) return -LZ4FLEX_E_INVALID_ARG;
-    }
-    if (!strcmp(key, "debug_chain_giveup")) {
-        if (value < 0) return -LZ4FLEX_E_INVALID_ARG;
-        c->chain_giveup = value;
-        return 0;
-    }
-    if (!strcmp(key, "debug_fail_next_batch")) {                 // tests/test_gpu_sharded_native.py: one rank's call-level failure
-        if (value < 0) return -LZ4FLEX_E_INVALID_ARG;
-        c->fail_next_batch = value;
-        return 0;
-    }
-    return -LZ4FLEX_E_INVALID_ARG;
+    if (!st->takes(value)) return -LZ4FLEX_E_INVALID_ARG;
+    c->*(st->field) = value;
+    return 0;
 }
 
 int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     if (!key) return -LZ4FLEX_E_INVALID_ARG;
-    if (!strncmp(key, "debug_", 6)) {                            // test hooks: see lz4flex_set_tuning (refused before a context is looked for)
-        const char* e = getenv("LZ4FLEX_TEST_HOOKS");
-        if (!e || strcmp(e, "1") != 0) return -LZ4FLEX_E_INVALID_ARG;
-    }
     // the batch sizes at which the default decoder dispatch changes kernel or geometry (lz4_device.h), in ascending order; the
     // list ends where the key is refused.  tests/test_gpu_block.py builds its size matrix from it.
     if (!strncmp(key, "dispatch_threshold_", 19)) {
-        const uint32_t t[] = {PCD_PAIR_MAX_BLOCKS, DISPATCH_PCD_1024, DISPATCH_PCD_512, DISPATCH_PCD_256, DISPATCH_SEQ_MAX, DISPATCH_SPLIT_FULL};
-        const int i = atoi(key + 19);
-        if (i < 0 || i >= (int)(sizeof t / sizeof t[0]) || (key[19] < '0' || key[19] > '9')) return -LZ4FLEX_E_INVALID_ARG;
-        return (int)t[i];
+        const int t[] = {(int)PCD_PAIR_MAX_BLOCKS, (int)DISPATCH_PCD_1024, (int)DISPATCH_PCD_512, (int)DISPATCH_PCD_256, (int)DISPATCH_SEQ_MAX,
+                         (int)DISPATCH_SPLIT_FULL};
+        return list_entry(key + 19, t, (int)(sizeof t / sizeof t[0]));
     }
     // every decoder configuration this build can be pinned to, as variant * 1000 + parameter ("decompress_lanes" for variant 1,
     // "decompress_blocks_per_wg" for variant 4, else 0); the list ends where the key is refused.  ONE list: tests/test_gpu_block.py's
@@ -648,43 +638,14 @@ int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
                          9000, 12000,
 #endif
         };
-        const int i = atoi(key + 15);
-        if (i < 0 || i >= (int)(sizeof t / sizeof t[0]) || (key[15] < '0' || key[15] > '9')) return -LZ4FLEX_E_INVALID_ARG;
-        return t[i];
+        return list_entry(key + 15, t, (int)(sizeof t / sizeof t[0]));
     }
+    const bool items = !strcmp(key, "debug_shared_dict_items");
+    const Setting* st = items ? nullptr : find_setting(key);
+    if ((!items && !st) || !key_allowed(key)) return -LZ4FLEX_E_INVALID_ARG;
     if (!c) { const int rc = default_ctx(&c); if (rc) return rc; }
-    if (!strcmp(key, "compress_mode")) return c->comp_mode;
-    if (!strcmp(key, "compress_variant")) return c->comp_variant;
-    if (!strcmp(key, "compress_carry_wait")) return c->comp_carry_wait;
-    if (!strcmp(key, "compress_sliding_window")) return c->comp_sliding;
-    if (!strcmp(key, "compress_subwindows")) return c->comp_sub;
-    if (!strcmp(key, "compress_deterministic")) return c->comp_det;
-    if (!strcmp(key, "compress_workgroups")) return c->wave_wgs;         // (what "compress_subwindows" 0 decides by: n * 4 <= this -> 4, n * 3 <= this -> 3, n * 2 <= this -> 2)
-    if (!strcmp(key, "decompress_pcd_pair")) return c->dec_pcd_pair;
-    if (!strcmp(key, "compress_lanes")) return c->comp_lanes;
-    if (!strcmp(key, "decompress_variant")) return c->dec_variant;
-    if (!strcmp(key, "decompress_second_pass")) return c->dec_second_pass;
-    if (!strcmp(key, "decompress_blocks_per_wg")) return c->dec_blocks_per_wg;
-    if (!strcmp(key, "decompress_level_chains")) return c->dec_level_chains;
-    if (!strcmp(key, "decompress_lanes")) return c->dec_lanes;
-    if (!strcmp(key, "size_scan_serial")) return c->size_serial;
-    if (!strcmp(key, "compress_shared_dict")) return c->comp_shared;
-    if (!strcmp(key, "decompress_shared_dict")) return c->dec_shared;
-    if (!strcmp(key, "debug_shared_dict_items")) {
-        // the items of the last lz4flex_compress_batch_shared_dict call on this context whose first window started from the digest
-        // (0: none yet, the reference-exact mode, "compress_shared_dict" 0); waits for the device
-        if (!c->shared_counted || !c->wave_ws) return 0;
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        HIP_TRY(hipSetDevice(c->device));
-        uint32_t v = 0;
-        hipError_t e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(&v, compress_wave_shared_counter(c->wave_ws, c->wave_wgs), 4, hipMemcpyDeviceToHost);
-        (void)hipSetDevice(prev);
-        if (e != hipSuccess) return hip_fail(e, "debug_shared_dict_items");
-        return (int)std::min<uint32_t>(v, 0x7FFFFFFFu);
-    }
-    return -LZ4FLEX_E_INVALID_ARG;
+    if (items) return shared_dict_items(c);
+    return st->set_only ? -LZ4FLEX_E_INVALID_ARG : c->*(st->field);
 }
 
 int lz4flex_abi_version(void) { return 8; }
@@ -699,237 +660,176 @@ size_t lz4flex_get_maximum_output_size(size_t input_len) {
 // host-resident batches: mirror the caller's layout in the device arena, run, copy back
 namespace {
 
-struct Span { uint64_t lo = ~0ull, hi = 0; };
-static Span span_of(const uint64_t* off, const uint32_t* len, uint32_t n) {
-    Span s;
-    for (uint32_t i = 0; i < n; i++) {
-        s.lo = std::min<uint64_t>(s.lo, off[i]);
-        s.hi = std::max<uint64_t>(s.hi, off[i] + len[i]);
-    }
-    if (n == 0 || s.lo > s.hi) { s.lo = 0; s.hi = 0; }
-    return s;
-}
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct HostBatch {
-    // device views
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_dict = nullptr;
-    uint64_t *d_in_off = nullptr, *d_out_off = nullptr, *d_dict_off = nullptr, *d_detail = nullptr;
-    uint32_t *d_in_len = nullptr, *d_out_cap = nullptr, *d_out_len = nullptr, *d_flags = nullptr, *d_dict_len = nullptr,
-             *d_out_pos = nullptr;
-    int32_t* d_status = nullptr;
-    Span in_span, out_span, dict_span;
+// the bytes [lo, hi) that (offset, length) pairs cover; nothing added (or lengths that wrap): empty at 0
+struct Span {
+    uint64_t lo = ~0ull, hi = 0;
+    void add(uint64_t off, uint64_t len) { lo = std::min<uint64_t>(lo, off); hi = std::max<uint64_t>(hi, off + len); }
+    Span closed() const { return lo > hi ? Span{0, 0} : *this; }
+    size_t bytes() const { return (size_t)(hi - lo); }
 };
+Span span_of(const uint64_t* off, const uint32_t* len, uint32_t n) {
+    Span s;
+    for (uint32_t i = 0; i < n; i++) s.add(off[i], len[i]);
+    return s.closed();
+}
+
+// host arrays are visible: a batch with a block beyond 64 KiB (compress) / 128 KiB compressed (decompress) is one of "large" blocks
+bool host_big(const BatchCall& b) {
+    const uint32_t limit = b.compress ? 65536u : 131072u;
+    bool big = false;
+    for (uint32_t i = 0; i < b.n; i++) big |= b.in_len[i] > limit;
+    return big;
+}
 
 }  // namespace
-
-struct lz4flex_decompress_ext_ {
-    const void* dict_base;
-    const uint64_t* dict_off;
-    const uint32_t* dict_len;
-    const uint32_t* out_pos;
-    const uint32_t* chain_prev;
-    uint32_t n_chains;
-    const void* shared_dict;      // the *_shared_dict calls: ONE dictionary of shared_len bytes for every block (no dict_base then)
-    uint32_t shared_len;
-};
 
 // A host batch of a few small blocks (the scalar calls above all: compress_into / decompress_into are 1-block batches): ONE transfer up
 // (descriptors + input, from page-locked staging), the kernels, ONE transfer down (results + output), one synchronisation -- the
 // general path below costs two transfers each way from pageable memory and two synchronisations (0.16 / 0.38 ms per 64 KiB block in
-// round 3).  Same semantics: a block that failed leaves the caller's bytes alone.
+// round 3).  Same semantics: a block that failed leaves the caller's bytes alone.  For batches without dictionaries, prefixes or a
+// chain only: run_host_batch sees to that.
 static constexpr uint32_t SMALL_BATCH_BLOCKS = 8u;
 static constexpr size_t SMALL_BATCH_BYTES = 4u << 20;
-static int run_host_small(lz4flex_ctx* c, bool compress, const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len,
-                          const uint32_t* flags, uint32_t n, uint8_t* out_base, const uint64_t* out_off, const uint32_t* out_cap,
-                          uint32_t* out_len, int32_t* status, uint64_t* detail) {
+static int run_host_small(lz4flex_ctx* c, const BatchCall& b) {
+    const uint32_t n = b.n;
+    auto in_slot = [&](uint32_t i) { return align_up(b.in_len[i] + 16, 64); };
+    auto out_slot = [&](uint32_t i) { return align_up((size_t)b.out_cap[i] + 16, 64); };
     size_t in_bytes = 0, out_bytes = 0;
-    for (uint32_t i = 0; i < n; i++) { in_bytes += align_up(in_len[i] + 16, 64); out_bytes += align_up((size_t)out_cap[i] + 16, 64); }
+    for (uint32_t i = 0; i < n; i++) { in_bytes += in_slot(i); out_bytes += out_slot(i); }
     // [up: in_off out_off in_len out_cap flags | input blocks]  [down: out_len status detail | output slots]
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 64); return at; };
-    const size_t at_in_off = take(8ull * n), at_out_off = take(8ull * n), at_in_len = take(4ull * n), at_out_cap = take(4ull * n),
-                 at_flags = take(4ull * n), at_in = take(in_bytes);
-    const size_t up_bytes = o;
-    const size_t at_out_len = take(4ull * n), at_status = take(4ull * n), at_detail = take(16ull * n), at_out = take(out_bytes);
-    const size_t total = o;
+    Layout l{64};
+    const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_in_len = l.take(4ull * n), at_out_cap = l.take(4ull * n),
+                 at_flags = l.take(4ull * n), at_in = l.take(in_bytes);
+    const size_t up_bytes = l.end;
+    const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n), at_out = l.take(out_bytes);
+    const size_t total = l.end;
     int rc;
-    if ((rc = ensure_pin(c, total))) return rc;
-    if ((rc = ensure_arena(c, total + 256))) return rc;
-    uint8_t* hp = c->h_pin;
-    uint8_t* d = c->d_arena;
+    if ((rc = ensure_buf(c->pin, total))) return rc;
+    if ((rc = ensure_buf(c->arena, total + 256))) return rc;
+    uint8_t* hp = c->pin.p;
+    uint8_t* d = c->arena.p;
     size_t ia = 0, oa = 0;
     for (uint32_t i = 0; i < n; i++) {
         ((uint64_t*)(hp + at_in_off))[i] = ia;
         ((uint64_t*)(hp + at_out_off))[i] = oa;
-        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
-        ((uint32_t*)(hp + at_out_cap))[i] = out_cap[i];
-        ((uint32_t*)(hp + at_flags))[i] = flags ? flags[i] : 0u;
-        if (in_len[i]) memcpy(hp + at_in + ia, in_base + in_off[i], in_len[i]);
-        ia += align_up(in_len[i] + 16, 64);
-        oa += align_up((size_t)out_cap[i] + 16, 64);
+        ((uint32_t*)(hp + at_in_len))[i] = b.in_len[i];
+        ((uint32_t*)(hp + at_out_cap))[i] = b.out_cap[i];
+        ((uint32_t*)(hp + at_flags))[i] = b.flags ? b.flags[i] : 0u;
+        if (b.in_len[i]) memcpy(hp + at_in + ia, b.in_base + b.in_off[i], b.in_len[i]);
+        ia += in_slot(i);
+        oa += out_slot(i);
     }
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(d, hp, up_bytes, hipMemcpyHostToDevice, s));
-    if (compress) {
-        CompressArgs a{};
-        a.in_base = d + at_in; a.in_off = (const uint64_t*)(d + at_in_off); a.in_len = (const uint32_t*)(d + at_in_len);
-        a.flags = flags ? (const uint32_t*)(d + at_flags) : nullptr;
-        a.out_base = d + at_out; a.out_off = (const uint64_t*)(d + at_out_off); a.out_cap = (const uint32_t*)(d + at_out_cap);
-        a.out_len = (uint32_t*)(d + at_out_len); a.status = (int32_t*)(d + at_status); a.n = n;
-        bool big = false;
-        for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 65536u;
-        if ((rc = launch_compress_any(c, a, big, s))) return rc;
-    } else {
-        DecompressArgs a{};
-        a.in_base = d + at_in; a.in_off = (const uint64_t*)(d + at_in_off); a.in_len = (const uint32_t*)(d + at_in_len);
-        a.out_base = d + at_out; a.out_off = (const uint64_t*)(d + at_out_off); a.out_cap = (const uint32_t*)(d + at_out_cap);
-        a.out_len = (uint32_t*)(d + at_out_len); a.status = (int32_t*)(d + at_status); a.detail = (uint64_t*)(d + at_detail); a.n = n;
-        bool big = false;
-        for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 131072u;
-        const hipError_t le = c->dec_variant != 1 ? launch_decompress_fast(c, a, s, big) : launch_decompress(a, c->dec_lanes, s);
-        if (le != hipSuccess) return hip_fail(le, "kernel launch");
-    }
+    // the batch as it lies in the arena
+    BatchCall dv = batch_of(b.compress, d + at_in, (const uint64_t*)(d + at_in_off), (const uint32_t*)(d + at_in_len), n, d + at_out,
+                            (const uint64_t*)(d + at_out_off), (const uint32_t*)(d + at_out_cap), (uint32_t*)(d + at_out_len),
+                            (int32_t*)(d + at_status), s);
+    dv.big = host_big(b);
+    dv.flags = b.flags ? (const uint32_t*)(d + at_flags) : nullptr;
+    dv.detail = (uint64_t*)(d + at_detail);
+    if ((rc = launch_batch(c, dv))) return rc;
     HIP_TRY(hipMemcpyAsync(hp + at_out_len, d + at_out_len, total - at_out_len, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t* r_det = (const uint64_t*)(hp + at_detail);
     oa = 0;
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t len = ((const uint32_t*)(hp + at_out_len))[i];
         const int32_t st = ((const int32_t*)(hp + at_status))[i];
-        out_len[i] = len;
-        status[i] = st;
-        if (detail) { detail[2 * i] = compress ? 0 : ((const uint64_t*)(hp + at_detail))[2 * i]; detail[2 * i + 1] = compress ? 0 : ((const uint64_t*)(hp + at_detail))[2 * i + 1]; }
-        if (st == 0 && len) memcpy(out_base + out_off[i], hp + at_out + oa, len);
-        oa += align_up((size_t)out_cap[i] + 16, 64);
+        b.out_len[i] = len;
+        b.status[i] = st;
+        if (b.detail) { b.detail[2 * i] = b.compress ? 0 : r_det[2 * i]; b.detail[2 * i + 1] = b.compress ? 0 : r_det[2 * i + 1]; }
+        if (st == 0 && len) memcpy(b.out_base + b.out_off[i], hp + at_out + oa, len);
+        oa += out_slot(i);
     }
     return 0;
 }
 
-static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base, const uint64_t* in_off,
-                          const uint32_t* in_len, const uint32_t* flags, uint32_t n, uint8_t* out_base,
-                          const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                          uint64_t* detail, const lz4flex_decompress_ext_* ext, bool chained = false) {
+static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
+    const uint32_t n = b.n;
     if (n == 0) return 0;
-    if (chained && (n > CHAIN_WS_BLOCKS || !ext || !ext->out_pos || ext->dict_base)) return -LZ4FLEX_E_INVALID_ARG;
-    if (ext && ext->chain_prev) return -LZ4FLEX_E_INVALID_ARG;      // several chains in one batch: DEVICE batches only (a host batch stages ONE output region)
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    HIP_TRY(hipSetDevice(c->device));
-    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
+    if (b.chained && (n > CHAIN_WS_BLOCKS || !b.out_pos || b.dict_base)) return -LZ4FLEX_E_INVALID_ARG;
+    if (b.chain_prev) return -LZ4FLEX_E_INVALID_ARG;                // several chains in one batch: DEVICE batches only (a host batch stages ONE output region)
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
     // LZ4FLEX_BLOCK_HISTORY: the bytes in front of a block travel with it
     uint64_t hist_lo = ~0ull;
-    if (compress && flags)
+    if (b.compress && b.flags)
         for (uint32_t i = 0; i < n; i++) {
-            const uint64_t h = flags[i] >> 8;
-            if (h > in_off[i]) return -LZ4FLEX_E_INVALID_ARG;
-            if (h) hist_lo = std::min<uint64_t>(hist_lo, in_off[i] - h);
+            const uint64_t h = b.flags[i] >> 8;
+            if (h > b.in_off[i]) return -LZ4FLEX_E_INVALID_ARG;
+            if (h) hist_lo = std::min<uint64_t>(hist_lo, b.in_off[i] - h);
         }
-    if (n <= SMALL_BATCH_BLOCKS && !ext && !chained && hist_lo == ~0ull) {
+    const bool has_dict = b.dict_base && b.dict_off && b.dict_len;
+    const bool has_pos = b.out_pos != nullptr;
+    const bool has_shared = b.shared_dict && b.shared_len;
+    if (n <= SMALL_BATCH_BLOCKS && !b.has_ext && !b.chained && hist_lo == ~0ull) {
         size_t bytes = 0;
-        for (uint32_t i = 0; i < n; i++) bytes += (size_t)in_len[i] + out_cap[i];
-        if (bytes <= SMALL_BATCH_BYTES) return run_host_small(c, compress, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status, detail);
+        for (uint32_t i = 0; i < n; i++) bytes += (size_t)b.in_len[i] + b.out_cap[i];
+        if (bytes <= SMALL_BATCH_BYTES) return run_host_small(c, b);
     }
 
-    HostBatch hb;
-    hb.in_span = span_of(in_off, in_len, n);
-    if (hist_lo < hb.in_span.lo) hb.in_span.lo = hist_lo;
-    hb.out_span = span_of(out_off, out_cap, n);
-    const bool has_dict = ext && ext->dict_base && ext->dict_off && ext->dict_len;
-    const bool has_pos = ext && ext->out_pos;
-    if (has_dict) hb.dict_span = span_of(ext->dict_off, ext->dict_len, n);
-    if (has_dict && compress) {
+    Span in_span = span_of(b.in_off, b.in_len, n), dict_span;
+    if (hist_lo < in_span.lo) in_span.lo = hist_lo;
+    const Span out_span = span_of(b.out_off, b.out_cap, n);
+    if (has_dict) {
         // (compress: the dictionary offsets of blocks without one are not looked at -- they need not lie anywhere near the others)
-        Span ds;
         for (uint32_t i = 0; i < n; i++)
-            if (ext->dict_len[i]) { ds.lo = std::min<uint64_t>(ds.lo, ext->dict_off[i]); ds.hi = std::max<uint64_t>(ds.hi, ext->dict_off[i] + ext->dict_len[i]); }
-        if (ds.lo > ds.hi) { ds.lo = 0; ds.hi = 0; }
-        hb.dict_span = ds;
+            if (!b.compress || b.dict_len[i]) dict_span.add(b.dict_off[i], b.dict_len[i]);
+        dict_span = dict_span.closed();
     }
-    const size_t in_bytes = (size_t)(hb.in_span.hi - hb.in_span.lo);
-    const size_t out_bytes = (size_t)(hb.out_span.hi - hb.out_span.lo);
-    const bool has_shared = ext && ext->shared_dict && ext->shared_len;
-    const size_t dict_bytes = has_shared ? (size_t)ext->shared_len : has_dict ? (size_t)(hb.dict_span.hi - hb.dict_span.lo) : 0;
+    const size_t in_bytes = in_span.bytes(), out_bytes = out_span.bytes();
+    const size_t dict_bytes = has_shared ? (size_t)b.shared_len : has_dict ? dict_span.bytes() : 0;
     // descriptor block (pinned host mirror and device copy share one layout)
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
-    const size_t at_in_off = take(8ull * n), at_out_off = take(8ull * n), at_dict_off = take(has_dict ? 8ull * n : 0),
-                 at_in_len = take(4ull * n), at_out_cap = take(4ull * n), at_flags = take(flags ? 4ull * n : 0),
-                 at_dict_len = take(has_dict ? 4ull * n : 0), at_out_pos = take(has_pos ? 4ull * n : 0);
-    const size_t desc_in_bytes = o;
-    const size_t at_out_len = take(4ull * n), at_status = take(4ull * n), at_detail = take(16ull * n);
-    const size_t desc_bytes = o;
+    Layout l{16};
+    const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_dict_off = l.take(has_dict ? 8ull * n : 0),
+                 at_in_len = l.take(4ull * n), at_out_cap = l.take(4ull * n), at_flags = l.take(b.flags ? 4ull * n : 0),
+                 at_dict_len = l.take(has_dict ? 4ull * n : 0), at_out_pos = l.take(has_pos ? 4ull * n : 0);
+    const size_t desc_in_bytes = l.end;
+    const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n);
+    const size_t desc_bytes = l.end;
     int rc;
-    if ((rc = ensure_pin(c, desc_bytes))) return rc;
+    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
     const size_t a_in = 0, a_out = align_up(in_bytes + 64, 256), a_dict = a_out + align_up(out_bytes + 64, 256),
                  a_desc = a_dict + align_up(dict_bytes + 64, 256);
-    if ((rc = ensure_arena(c, a_desc + desc_bytes + 256))) return rc;
-    uint8_t* hp = c->h_pin;
+    if ((rc = ensure_buf(c->arena, a_desc + desc_bytes + 256))) return rc;
+    uint8_t* hp = c->pin.p;
     for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - hb.in_span.lo;
-        ((uint64_t*)(hp + at_out_off))[i] = out_off[i] - hb.out_span.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
-        ((uint32_t*)(hp + at_out_cap))[i] = out_cap[i];
-        if (flags) ((uint32_t*)(hp + at_flags))[i] = flags[i];
+        ((uint64_t*)(hp + at_in_off))[i] = b.in_off[i] - in_span.lo;
+        ((uint64_t*)(hp + at_out_off))[i] = b.out_off[i] - out_span.lo;
+        ((uint32_t*)(hp + at_in_len))[i] = b.in_len[i];
+        ((uint32_t*)(hp + at_out_cap))[i] = b.out_cap[i];
+        if (b.flags) ((uint32_t*)(hp + at_flags))[i] = b.flags[i];
         if (has_dict) {
-            ((uint64_t*)(hp + at_dict_off))[i] = (compress && !ext->dict_len[i]) ? 0u : ext->dict_off[i] - hb.dict_span.lo;
-            ((uint32_t*)(hp + at_dict_len))[i] = ext->dict_len[i];
+            ((uint64_t*)(hp + at_dict_off))[i] = (b.compress && !b.dict_len[i]) ? 0u : b.dict_off[i] - dict_span.lo;
+            ((uint32_t*)(hp + at_dict_len))[i] = b.dict_len[i];
         }
-        if (has_pos) ((uint32_t*)(hp + at_out_pos))[i] = ext->out_pos[i];
+        if (has_pos) ((uint32_t*)(hp + at_out_pos))[i] = b.out_pos[i];
     }
-    uint8_t* d = c->d_arena;
+    uint8_t* d = c->arena.p;
     hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, in_base + hb.in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, b.in_base + in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
     if (dict_bytes)
-        HIP_TRY(hipMemcpyAsync(d + a_dict, has_shared ? (const uint8_t*)ext->shared_dict : (const uint8_t*)ext->dict_base + hb.dict_span.lo, dict_bytes,
-                               hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d + a_dict, has_shared ? b.shared_dict : b.dict_base + dict_span.lo, dict_bytes, hipMemcpyHostToDevice, s));
     if (has_pos && out_bytes) {
         // prefix mode: the sink already holds bytes [0, out_pos) that matches may reference; in a chained batch only what lies
         // before the FIRST block's position exists yet (the rest is what the batch produces)
-        const size_t up = chained ? std::min<size_t>(out_bytes, (size_t)(out_off[0] - hb.out_span.lo) + ext->out_pos[0]) : out_bytes;
-        if (up) HIP_TRY(hipMemcpyAsync(d + a_out, out_base + hb.out_span.lo, up, hipMemcpyHostToDevice, s));
+        const size_t up = b.chained ? std::min<size_t>(out_bytes, (size_t)(b.out_off[0] - out_span.lo) + b.out_pos[0]) : out_bytes;
+        if (up) HIP_TRY(hipMemcpyAsync(d + a_out, b.out_base + out_span.lo, up, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(hipMemcpyAsync(d + a_desc, hp, desc_in_bytes, hipMemcpyHostToDevice, s));
     uint8_t* dd = d + a_desc;
-    hipError_t le;
-    if (compress) {
-        CompressArgs a{};
-        a.in_base = d + a_in; a.in_off = (const uint64_t*)(dd + at_in_off); a.in_len = (const uint32_t*)(dd + at_in_len);
-        a.flags = flags ? (const uint32_t*)(dd + at_flags) : nullptr;
-        a.out_base = d + a_out; a.out_off = (const uint64_t*)(dd + at_out_off); a.out_cap = (const uint32_t*)(dd + at_out_cap);
-        a.out_len = (uint32_t*)(dd + at_out_len); a.status = (int32_t*)(dd + at_status); a.n = n;
-        if (has_dict) {
-            a.dict_base = d + a_dict;
-            a.dict_off = (const uint64_t*)(dd + at_dict_off);
-            a.dict_len = (const uint32_t*)(dd + at_dict_len);
-        }
-        bool big = false;
-        for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 65536u;
-        SharedDictArgs sh{};
-        sh.dict = d + a_dict; sh.len = has_shared ? ext->shared_len : 0u; sh.use = (uint32_t)c->comp_shared;
-        if ((rc = launch_compress_any(c, a, big, s, has_shared ? &sh : nullptr))) return rc;
-        le = hipSuccess;
-    } else {
-        DecompressArgs a{};
-        a.in_base = d + a_in; a.in_off = (const uint64_t*)(dd + at_in_off); a.in_len = (const uint32_t*)(dd + at_in_len);
-        a.out_base = d + a_out; a.out_off = (const uint64_t*)(dd + at_out_off); a.out_cap = (const uint32_t*)(dd + at_out_cap);
-        a.out_pos = has_pos ? (const uint32_t*)(dd + at_out_pos) : nullptr;
-        a.dict_base = has_dict ? d + a_dict : nullptr;
-        a.dict_off = has_dict ? (const uint64_t*)(dd + at_dict_off) : nullptr;
-        a.dict_len = has_dict ? (const uint32_t*)(dd + at_dict_len) : nullptr;
-        a.out_len = (uint32_t*)(dd + at_out_len); a.status = (int32_t*)(dd + at_status);
-        a.detail = (uint64_t*)(dd + at_detail); a.n = n;
-        bool big = false;                                    // host arrays are visible: blocks beyond 128 KiB compressed are "large"
-        for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 131072u;
-        if (chained) {
-            HIP_TRY(chain_ws_begin(c, n, s));
-            a.chain_done = c->chain_ws;
-            a.debug_giveup = (uint32_t)c->chain_giveup;
-        }
-        if (has_shared) le = launch_decompress_shared(c, a, d + a_dict, ext->shared_len, s);
-        else le = ((c->dec_variant != 1 || chained) && !has_dict) ? launch_decompress_fast(c, a, s, big) : launch_decompress(a, c->dec_lanes, s);
-        if (chained) (void)chain_ws_end(c, s);               // (also behind a failed launch: whatever was enqueued is ordered)
-    }
-    if (le != hipSuccess) return hip_fail(le, "kernel launch");
+    // the batch as it lies in the arena
+    BatchCall dv = batch_of(b.compress, d + a_in, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, d + a_out,
+                            (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap), (uint32_t*)(dd + at_out_len),
+                            (int32_t*)(dd + at_status), s);
+    dv.chained = b.chained; dv.big = host_big(b);
+    dv.flags = b.flags ? (const uint32_t*)(dd + at_flags) : nullptr;
+    dv.detail = (uint64_t*)(dd + at_detail);
+    if (has_dict) { dv.dict_base = d + a_dict; dv.dict_off = (const uint64_t*)(dd + at_dict_off); dv.dict_len = (const uint32_t*)(dd + at_dict_len); }
+    if (has_shared) { dv.shared_dict = d + a_dict; dv.shared_len = b.shared_len; }
+    if (has_pos) dv.out_pos = (const uint32_t*)(dd + at_out_pos);
+    if ((rc = launch_batch(c, dv))) return rc;
     HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint32_t* r_len = (const uint32_t*)(hp + at_out_len);
@@ -937,9 +837,9 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
     const uint64_t* r_det = (const uint64_t*)(hp + at_detail);
     uint64_t produced = 0;
     for (uint32_t i = 0; i < n; i++) {
-        out_len[i] = r_len[i];
-        status[i] = r_st[i];
-        if (detail) { detail[2 * i] = compress ? 0 : r_det[2 * i]; detail[2 * i + 1] = compress ? 0 : r_det[2 * i + 1]; }
+        b.out_len[i] = r_len[i];
+        b.status[i] = r_st[i];
+        if (b.detail) { b.detail[2 * i] = b.compress ? 0 : r_det[2 * i]; b.detail[2 * i + 1] = b.compress ? 0 : r_det[2 * i + 1]; }
         if (r_st[i] == 0) produced += r_len[i];
     }
     // copy results back: dense outputs in one transfer, sparse ones block by block
@@ -952,15 +852,15 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
         bool all_ok = true;
         uint64_t cap_sum = 0, short_tail = 0;
         for (uint32_t i = 0; i < n; i++) {
-            cap_sum += out_cap[i];
+            cap_sum += b.out_cap[i];
             if (r_st[i] != 0) { all_ok = false; break; }
-            if (r_len[i] == out_cap[i]) continue;
-            if (out_off[i] + out_cap[i] == hb.out_span.hi && short_tail == 0 && r_len[i] < out_cap[i]) short_tail = out_cap[i] - r_len[i];
+            if (r_len[i] == b.out_cap[i]) continue;
+            if (b.out_off[i] + b.out_cap[i] == out_span.hi && short_tail == 0 && r_len[i] < b.out_cap[i]) short_tail = b.out_cap[i] - r_len[i];
             else { all_ok = false; break; }
         }
         all_ok = all_ok && cap_sum == (uint64_t)out_bytes;
         if (all_ok) {
-            if (out_bytes > short_tail) HIP_TRY(hipMemcpyAsync(out_base + hb.out_span.lo, d + a_out, out_bytes - (size_t)short_tail, hipMemcpyDeviceToHost, s));
+            if (out_bytes > short_tail) HIP_TRY(hipMemcpyAsync(b.out_base + out_span.lo, d + a_out, out_bytes - (size_t)short_tail, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             return 0;
         }
@@ -968,7 +868,7 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
     // sparse results, many blocks: pack them on the device into the (now free) input region, one transfer to pinned
     // memory, scatter on the host.  A per-block hipMemcpy to pageable memory costs ~10 us each.
     if (!has_pos && n >= 16u && produced != 0 && produced <= (uint64_t)align_up(in_bytes + 64, 256) &&
-        ensure_pay(c, (size_t)produced) == 0) {
+        ensure_buf(c->pay, (size_t)produced) == 0) {
         uint64_t* h_dense = (uint64_t*)(hp + at_detail);          // reuse the detail slot (16 B per block >= 8 B)
         uint64_t at = 0;
         for (uint32_t i = 0; i < n; i++) { h_dense[i] = at; if (r_st[i] == 0) at += r_len[i]; }
@@ -979,95 +879,44 @@ static int run_host_batch(lz4flex_ctx* c, bool compress, const uint8_t* in_base,
                            (const int32_t*)(dd + at_status), d_dense, d + a_in, n);
         const hipError_t pe = hipGetLastError();              // (reading it clears it: read once)
         if (pe != hipSuccess) return hip_fail(pe, "pack kernel launch");
-        HIP_TRY(hipMemcpyAsync(c->h_pay, d + a_in, (size_t)produced, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->pay.p, d + a_in, (size_t)produced, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         at = 0;
         for (uint32_t i = 0; i < n; i++) {
             if (r_st[i] != 0 || r_len[i] == 0) continue;
-            memcpy(out_base + out_off[i], c->h_pay + at, r_len[i]);
+            memcpy(b.out_base + b.out_off[i], c->pay.p + at, r_len[i]);
             at += r_len[i];
         }
         return 0;
     }
-    if (chained) {
+    if (b.chained) {
         // one region, the blocks back to back behind the first one's position: one transfer up to the end of the last good block
-        uint64_t lo = out_off[0] + ext->out_pos[0], hi = lo;
+        uint64_t lo = b.out_off[0] + b.out_pos[0], hi = lo;
         for (uint32_t i = 0; i < n; i++)
-            if (r_st[i] == 0) hi = std::max<uint64_t>(hi, out_off[i] + ext->out_pos[i] + r_len[i]);
-        if (hi > lo) HIP_TRY(hipMemcpyAsync(out_base + lo, d + a_out + (lo - hb.out_span.lo), (size_t)(hi - lo), hipMemcpyDeviceToHost, s));
+            if (r_st[i] == 0) hi = std::max<uint64_t>(hi, b.out_off[i] + b.out_pos[i] + r_len[i]);
+        if (hi > lo) HIP_TRY(hipMemcpyAsync(b.out_base + lo, d + a_out + (lo - out_span.lo), (size_t)(hi - lo), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return 0;
     }
     for (uint32_t i = 0; i < n; i++) {
         if (r_st[i] != 0 || r_len[i] == 0) continue;
-        const uint32_t pos = has_pos ? ext->out_pos[i] : 0u;
-        HIP_TRY(hipMemcpyAsync(out_base + out_off[i] + pos, d + a_out + (out_off[i] - hb.out_span.lo) + pos, r_len[i],
+        const uint32_t pos = has_pos ? b.out_pos[i] : 0u;
+        HIP_TRY(hipMemcpyAsync(b.out_base + b.out_off[i] + pos, d + a_out + (b.out_off[i] - out_span.lo) + pos, r_len[i],
                                hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }
 
-static int run_device_batch(lz4flex_ctx* c, bool compress, const void* in_base, const uint64_t* in_off,
-                            const uint32_t* in_len, const uint32_t* flags, uint32_t n, void* out_base,
-                            const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
-                            uint64_t* detail, const lz4flex_decompress_ext_* ext, void* hip_stream, int big_hint, bool chained = false) {
-    if (chained && (compress || n > CHAIN_WS_BLOCKS || !ext || !ext->out_pos || ext->dict_base)) return -LZ4FLEX_E_INVALID_ARG;
-    if (!chained && ext && ext->chain_prev) return -LZ4FLEX_E_INVALID_ARG;
-    hipStream_t s = (hipStream_t)hip_stream;   // DEVICE batches run on the caller's stream (NULL = HIP's null stream)
-    hipError_t le;
-    if (compress) {
-        CompressArgs a{};
-        a.in_base = (const uint8_t*)in_base; a.in_off = in_off; a.in_len = in_len; a.flags = flags;
-        a.out_base = (uint8_t*)out_base; a.out_off = out_off; a.out_cap = out_cap; a.out_len = out_len;
-        a.status = status; a.n = n;
-        if (ext && ext->dict_base) { a.dict_base = (const uint8_t*)ext->dict_base; a.dict_off = ext->dict_off; a.dict_len = ext->dict_len; }
-        SharedDictArgs sh{};
-        const bool has_shared = ext && ext->shared_dict && ext->shared_len;
-        if (has_shared) { sh.dict = (const uint8_t*)ext->shared_dict; sh.len = ext->shared_len; sh.use = (uint32_t)c->comp_shared; }
-        const int rc = launch_compress_any(c, a, big_hint != 0, s, has_shared ? &sh : nullptr);
-        if (rc) return rc;
-        le = hipSuccess;
-    } else {
-        DecompressArgs a{};
-        a.in_base = (const uint8_t*)in_base; a.in_off = in_off; a.in_len = in_len;
-        a.out_base = (uint8_t*)out_base; a.out_off = out_off; a.out_cap = out_cap;
-        a.out_pos = ext ? ext->out_pos : nullptr;
-        a.dict_base = ext ? (const uint8_t*)ext->dict_base : nullptr;
-        a.dict_off = ext ? ext->dict_off : nullptr;
-        a.dict_len = ext ? ext->dict_len : nullptr;
-        a.out_len = out_len; a.status = status; a.detail = detail; a.n = n;
-        if (chained && n) {
-            HIP_TRY(chain_ws_begin(c, n, s));
-            a.chain_done = c->chain_ws;
-            a.chain_prev = ext->chain_prev;
-            a.n_chains = ext->n_chains;
-            a.debug_giveup = (uint32_t)c->chain_giveup;
-        }
-        if (ext && ext->shared_dict && ext->shared_len) le = launch_decompress_shared(c, a, (const uint8_t*)ext->shared_dict, ext->shared_len, s);
-        else le = ((c->dec_variant != 1 || chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, big_hint != 0) : launch_decompress(a, c->dec_lanes, s);
-        if (chained && n) (void)chain_ws_end(c, s);
-    }
-    if (le != hipSuccess) return hip_fail(le, "kernel launch");
-    return 0;
+// DEVICE batches run on the caller's stream, on the caller's arrays
+static int run_device_batch(lz4flex_ctx* c, const BatchCall& b) {
+    if (b.chained ? (b.compress || b.n > CHAIN_WS_BLOCKS || !b.out_pos || b.dict_base) : b.chain_prev != nullptr) return -LZ4FLEX_E_INVALID_ARG;
+    return launch_batch(c, b);
 }
 
-static thread_local lz4flex_ctx* g_default_ctx = nullptr;
-static int default_ctx(lz4flex_ctx** out) {
-    if (!g_default_ctx) {
-        int rc = lz4flex_ctx_create(&g_default_ctx, -1);
-        if (rc) return rc;
-    }
-    *out = g_default_ctx;
-    return 0;
-}
-
-// frame_many.cpp's view of a context (lz4_device.h): the context or the calling thread's default one; its device; grow-only scratch
+// frame_many.cpp's view of a context (lz4_ctx.h): the context or the calling thread's default one; grow-only scratch
 namespace lz4flex_dev {
 int ctx_resolve(lz4flex_ctx** ctx) { return *ctx ? 0 : default_ctx(ctx); }
-int ctx_device(lz4flex_ctx* c) { return c->device; }
-hipStream_t ctx_stream(lz4flex_ctx* c) { return c->stream; }
-int ctx_comp_mode(lz4flex_ctx* c) { return c->comp_mode; }
 int ctx_scratch(lz4flex_ctx* c, int slot, size_t bytes, void** out) {
     if (slot < 0 || slot >= 4) return -LZ4FLEX_E_INVALID_ARG;
     if (bytes > c->many_cap[slot]) {
@@ -1083,6 +932,47 @@ int ctx_scratch(lz4flex_ctx* c, int slot, size_t bytes, void** out) {
 }
 }  // namespace lz4flex_dev
 
+// ---- what the batched entry points share.  Each keeps ITS order of checks and ITS accepted mem_kind values: both are observable.
+namespace {
+
+bool batch_arrays_ok(const BatchCall& b) {
+    return !b.n || (b.in_off && b.in_len && b.out_off && b.out_cap && b.out_len && b.status);
+}
+
+// "debug_fail_next_batch" (tests)
+int injected_failure(lz4flex_ctx* c) {
+    if (c->fail_next_batch <= 0) return 0;
+    c->fail_next_batch--;
+    g_last_error = "debug_fail_next_batch";
+    return -LZ4FLEX_E_HIP;
+}
+// the entry points that check their arguments first (a wrong call says so on any machine): then the context, then the hook
+int begin_batch(lz4flex_ctx** ctx) {
+    const int rc = ctx_resolve(ctx);
+    return rc ? rc : injected_failure(*ctx);
+}
+
+// mem_kind: the low byte says where the buffers are, the bits above it are flags.  An entry point accepts HOST with the flags of
+// host_flags at most and DEVICE with those of device_flags at most.
+enum class Mem { Host, Device, Invalid };
+struct MemKind { Mem where; bool big, chained; };
+constexpr int ANY_FLAGS = ~0xFF;
+MemKind classify_mem(int mem_kind, int host_flags, int device_flags) {
+    const int where = mem_kind & 0xFF, flags = mem_kind & ~0xFF;
+    MemKind k{Mem::Invalid, (flags & LZ4FLEX_MEM_BIG_BLOCKS) != 0, (flags & LZ4FLEX_MEM_CHAINED) != 0};
+    if (where == LZ4FLEX_MEM_HOST && !(flags & ~host_flags)) k.where = Mem::Host;
+    if (where == LZ4FLEX_MEM_DEVICE && !(flags & ~device_flags)) k.where = Mem::Device;
+    return k;
+}
+
+int run_batch(lz4flex_ctx* c, BatchCall& b, const MemKind& k) {
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    b.big = k.big;
+    return k.where == Mem::Host ? run_host_batch(c, b) : run_device_batch(c, b);
+}
+
+}  // namespace
+
 extern "C" {
 
 int lz4flex_compress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
@@ -1090,16 +980,12 @@ int lz4flex_compress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t
                            const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int mem_kind,
                            void* hip_stream) {
     int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
-    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
-    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
-    if (mem_kind == LZ4FLEX_MEM_HOST)
-        return run_host_batch(ctx, true, (const uint8_t*)in_base, in_off, in_len, flags, n, (uint8_t*)out_base, out_off,
-                              out_cap, out_len, status, nullptr, nullptr);
-    if ((mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE)
-        return run_device_batch(ctx, true, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status,
-                                nullptr, nullptr, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
-    return -LZ4FLEX_E_INVALID_ARG;
+    if ((rc = ctx_resolve(&ctx))) return rc;
+    BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.flags = flags;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    if ((rc = injected_failure(ctx))) return rc;
+    return run_batch(ctx, b, classify_mem(mem_kind, 0, ANY_FLAGS));      // (of the flags, DEVICE batches read BIG_BLOCKS alone)
 }
 
 int lz4flex_compress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
@@ -1108,47 +994,34 @@ int lz4flex_compress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint6
                               const lz4flex_compress_ext* ext, int mem_kind, void* hip_stream) {
     if (!ext || !ext->dict_base)
         return lz4flex_compress_batch(ctx, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status, mem_kind, hip_stream);
-    // (the arguments are checked before a context is looked for: a wrong call says so on any machine)
     if (!ext->dict_off || !ext->dict_len) return -LZ4FLEX_E_INVALID_ARG;
-    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
-    const bool device = (mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE && (mem_kind & ~(0xFF | LZ4FLEX_MEM_BIG_BLOCKS)) == 0;
-    if (mem_kind != LZ4FLEX_MEM_HOST && !device) return -LZ4FLEX_E_INVALID_ARG;
-    int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
-    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
-    lz4flex_decompress_ext_ e{};
-    e.dict_base = ext->dict_base; e.dict_off = ext->dict_off; e.dict_len = ext->dict_len;
-    if (mem_kind == LZ4FLEX_MEM_HOST)
-        return run_host_batch(ctx, true, (const uint8_t*)in_base, in_off, in_len, flags, n, (uint8_t*)out_base, out_off,
-                              out_cap, out_len, status, nullptr, &e);
-    return run_device_batch(ctx, true, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status,
-                            nullptr, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
+    BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.flags = flags;
+    b.has_ext = true; b.dict_base = (const uint8_t*)ext->dict_base; b.dict_off = ext->dict_off; b.dict_len = ext->dict_len;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, 0, LZ4FLEX_MEM_BIG_BLOCKS);
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    const int rc = begin_batch(&ctx);
+    return rc ? rc : run_batch(ctx, b, k);
 }
 
 int lz4flex_compress_batch_shared_dict(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
                                        uint32_t n, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
                                        uint32_t* out_len, int32_t* status, const void* dict, uint32_t dict_len,
                                        int mem_kind, void* hip_stream) {
-    // (the arguments are checked before a context is looked for: a wrong call says so on any machine)
     if (!dict && dict_len) return -LZ4FLEX_E_INVALID_ARG;
-    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
-    const bool device = (mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE && (mem_kind & ~(0xFF | LZ4FLEX_MEM_BIG_BLOCKS)) == 0;
-    if (mem_kind != LZ4FLEX_MEM_HOST && !device) return -LZ4FLEX_E_INVALID_ARG;
+    BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.has_ext = true; b.shared_dict = (const uint8_t*)dict; b.shared_len = dict_len;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, 0, LZ4FLEX_MEM_BIG_BLOCKS);
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
     // "debug_shared_dict_items" speaks of THIS call from here on: one that forwards or has nothing to do counts nothing
     if (lz4flex_ctx* c0 = ctx ? ctx : g_default_ctx) c0->shared_counted = false;
     if (n == 0) return 0;
     if (!dict || !dict_len)
         return lz4flex_compress_batch(ctx, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len, status, mem_kind, hip_stream);
-    int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
-    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
-    lz4flex_decompress_ext_ e{};
-    e.shared_dict = dict; e.shared_len = dict_len;
-    if (mem_kind == LZ4FLEX_MEM_HOST)
-        return run_host_batch(ctx, true, (const uint8_t*)in_base, in_off, in_len, nullptr, n, (uint8_t*)out_base, out_off,
-                              out_cap, out_len, status, nullptr, &e);
-    return run_device_batch(ctx, true, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len, status,
-                            nullptr, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
+    const int rc = begin_batch(&ctx);
+    return rc ? rc : run_batch(ctx, b, k);
 }
 
 int lz4flex_decompress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
@@ -1156,48 +1029,38 @@ int lz4flex_decompress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uin
                                 uint32_t* out_len, int32_t* status, uint64_t* detail,
                                 const lz4flex_decompress_ext* ext, int mem_kind, void* hip_stream) {
     int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
-    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
-    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
-    lz4flex_decompress_ext_ e{};
-    const bool chained = (mem_kind & LZ4FLEX_MEM_CHAINED) != 0;
+    if ((rc = ctx_resolve(&ctx))) return rc;
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.detail = detail;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    if ((rc = injected_failure(ctx))) return rc;
+    const MemKind k = classify_mem(mem_kind, ANY_FLAGS, ANY_FLAGS);
+    b.chained = k.chained;
     if (ext) {
-        e.dict_base = ext->dict_base; e.dict_off = ext->dict_off; e.dict_len = ext->dict_len; e.out_pos = ext->out_pos;
+        b.has_ext = true;
+        b.dict_base = (const uint8_t*)ext->dict_base; b.dict_off = ext->dict_off; b.dict_len = ext->dict_len; b.out_pos = ext->out_pos;
         // chain_prev / n_chains (round 5) lie behind the four members every earlier caller knows: they are only looked at in the one
         // batch shape that uses them -- a caller built against the round-4 header hands over a 32-byte struct (lz4flex_abi_version)
-        if (chained && (mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE) { e.chain_prev = ext->chain_prev; e.n_chains = ext->n_chains; }
+        if (k.chained && k.where == Mem::Device) { b.chain_prev = ext->chain_prev; b.n_chains = ext->n_chains; }
     }
-    if ((mem_kind & 0xFF) == LZ4FLEX_MEM_HOST)
-        return run_host_batch(ctx, false, (const uint8_t*)in_base, in_off, in_len, nullptr, n, (uint8_t*)out_base, out_off,
-                              out_cap, out_len, status, detail, ext ? &e : nullptr, chained);
-    if ((mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE)
-        return run_device_batch(ctx, false, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len,
-                                status, detail, ext ? &e : nullptr, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0, chained);
-    return -LZ4FLEX_E_INVALID_ARG;
+    return run_batch(ctx, b, k);
 }
 
 int lz4flex_decompress_batch_shared_dict(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
                                          uint32_t n, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
                                          uint32_t* out_len, int32_t* status, uint64_t* detail, const void* dict, uint32_t dict_len,
                                          int mem_kind, void* hip_stream) {
-    // (the arguments are checked before a context is looked for: a wrong call says so on any machine)
     if (!dict && dict_len) return -LZ4FLEX_E_INVALID_ARG;
-    if (n && (!in_off || !in_len || !out_off || !out_cap || !out_len || !status)) return -LZ4FLEX_E_INVALID_ARG;
-    const int kind = mem_kind & ~LZ4FLEX_MEM_BIG_BLOCKS;
-    if (kind != LZ4FLEX_MEM_HOST && kind != LZ4FLEX_MEM_DEVICE) return -LZ4FLEX_E_INVALID_ARG;     // (LZ4FLEX_MEM_CHAINED among them)
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.detail = detail; b.has_ext = true; b.shared_dict = (const uint8_t*)dict; b.shared_len = dict_len;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
     if (n == 0) return 0;
     if (!dict || !dict_len)
         return lz4flex_decompress_batch(ctx, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, detail, mem_kind, hip_stream);
-    int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
-    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
-    lz4flex_decompress_ext_ e{};
-    e.shared_dict = dict; e.shared_len = dict_len;
-    if (kind == LZ4FLEX_MEM_HOST)
-        return run_host_batch(ctx, false, (const uint8_t*)in_base, in_off, in_len, nullptr, n, (uint8_t*)out_base, out_off,
-                              out_cap, out_len, status, detail, &e);
-    return run_device_batch(ctx, false, in_base, in_off, in_len, nullptr, n, out_base, out_off, out_cap, out_len, status,
-                            detail, &e, hip_stream, (mem_kind & LZ4FLEX_MEM_BIG_BLOCKS) != 0);
+    const int rc = begin_batch(&ctx);
+    return rc ? rc : run_batch(ctx, b, k);
 }
 
 int lz4flex_decompress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
@@ -1212,40 +1075,37 @@ int lz4flex_decompress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64
 int lz4flex_decompressed_size_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
                                     const uint32_t* history, uint64_t* out_size, int32_t* status, int mem_kind, void* hip_stream) {
     int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
-    if ((mem_kind & ~LZ4FLEX_MEM_BIG_BLOCKS) != LZ4FLEX_MEM_HOST && (mem_kind & ~LZ4FLEX_MEM_BIG_BLOCKS) != LZ4FLEX_MEM_DEVICE)
-        return -LZ4FLEX_E_INVALID_ARG;
+    if ((rc = ctx_resolve(&ctx))) return rc;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
     if (n == 0) return 0;
     if (!in_off || !in_len || !out_size || !status) return -LZ4FLEX_E_INVALID_ARG;
-    if (ctx->fail_next_batch > 0) { ctx->fail_next_batch--; g_last_error = "debug_fail_next_batch"; return -LZ4FLEX_E_HIP; }
-    if ((mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE) {
+    if ((rc = injected_failure(ctx))) return rc;
+    if (k.where == Mem::Device) {
         const hipError_t le = launch_size_scan((const uint8_t*)in_base, in_off, in_len, history, n, out_size, status, ctx->size_serial,
                                                (hipStream_t)hip_stream);
         return le != hipSuccess ? hip_fail(le, "size scan launch") : 0;
     }
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    HIP_TRY(hipSetDevice(ctx->device));
-    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
+    DeviceGuard guard(ctx->device);
+    HIP_TRY(guard.err);
     const Span sp = span_of(in_off, in_len, n);
-    const size_t in_bytes = (size_t)(sp.hi - sp.lo);
+    const size_t in_bytes = sp.bytes();
     // [in_off in_len history | out_size status], the same layout in pinned memory and behind the input in the arena
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
-    const size_t at_in_off = take(8ull * n), at_in_len = take(4ull * n), at_hist = take(history ? 4ull * n : 0);
-    const size_t up_bytes = o;
-    const size_t at_size = take(8ull * n), at_status = take(4ull * n);
-    const size_t desc_bytes = o;
-    if ((rc = ensure_pin(ctx, desc_bytes))) return rc;
+    Layout l{16};
+    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n), at_hist = l.take(history ? 4ull * n : 0);
+    const size_t up_bytes = l.end;
+    const size_t at_size = l.take(8ull * n), at_status = l.take(4ull * n);
+    const size_t desc_bytes = l.end;
+    if ((rc = ensure_buf(ctx->pin, desc_bytes))) return rc;
     const size_t a_desc = align_up(in_bytes + 64, 256);
-    if ((rc = ensure_arena(ctx, a_desc + desc_bytes + 256))) return rc;
-    uint8_t* hp = ctx->h_pin;
+    if ((rc = ensure_buf(ctx->arena, a_desc + desc_bytes + 256))) return rc;
+    uint8_t* hp = ctx->pin.p;
     for (uint32_t i = 0; i < n; i++) {
         ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
         ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
         if (history) ((uint32_t*)(hp + at_hist))[i] = history[i];
     }
-    uint8_t* d = ctx->d_arena;
+    uint8_t* d = ctx->arena.p;
     uint8_t* dd = d + a_desc;
     hipStream_t s = ctx->stream;
     if (in_bytes) HIP_TRY(hipMemcpyAsync(d, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
@@ -1261,7 +1121,10 @@ int lz4flex_decompressed_size_batch(lz4flex_ctx* ctx, const void* in_base, const
     return 0;
 }
 
-// ---- scalar, lz4_flex-shaped --------------------------------------------------------------
+// ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------
+static const uint64_t OFF0 = 0;
+static const uint8_t EMPTY = 0;
+
 int64_t lz4flex_compress_into(const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap) {
     if (in_len > 0xFFFFFFFFull) return -LZ4FLEX_E_INVALID_ARG;
     // compress.rs:338-340: OutputTooSmall is decided up front, before anything is written
@@ -1269,12 +1132,11 @@ int64_t lz4flex_compress_into(const uint8_t* in, size_t in_len, uint8_t* out, si
     lz4flex_ctx* c;
     int rc = default_ctx(&c);
     if (rc) return rc;
-    const uint64_t off0 = 0;
     const uint32_t len = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull);
     uint32_t olen = 0;
     int32_t st = 0;
-    static const uint8_t empty = 0;
-    rc = run_host_batch(c, true, in ? in : &empty, &off0, &len, nullptr, 1, out, &off0, &cap, &olen, &st, nullptr, nullptr);
+    const BatchCall b = batch_of(true, in ? in : &EMPTY, &OFF0, &len, 1, out, &OFF0, &cap, &olen, &st);
+    rc = run_host_batch(c, b);
     if (rc) return rc;
     if (st) return -(int64_t)st;
     return (int64_t)olen;
@@ -1286,62 +1148,56 @@ int lz4flex_compress_chains(lz4flex_ctx* ctx, const void* in_base, const lz4flex
                             uint32_t* tbl_state, int mem_kind, void* hip_stream) {
     static_assert(sizeof(lz4flex_chain_block) == 40, "ChainBlock layout");
     int rc;
-    if (!ctx && (rc = default_ctx(&ctx))) return rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;
     if (n_chains == 0 || n_blocks == 0) return 0;
     if (!blocks || !chain_first || !chain_count || !out_off || !out_cap || !out_len || !status) return -LZ4FLEX_E_INVALID_ARG;
-    if ((mem_kind & 0xFF) == LZ4FLEX_MEM_DEVICE) {
+    const MemKind k = classify_mem(mem_kind, 0, ANY_FLAGS);
+    if (k.where == Mem::Device) {
         hipError_t le = launch_compress_chain((const uint8_t*)in_base, blocks, chain_first, chain_count, n_chains,
                                               (uint8_t*)out_base, out_off, out_cap, out_len, status, tbl_state,
                                               (hipStream_t)hip_stream);
         return le == hipSuccess ? 0 : hip_fail(le, "chain kernel launch");
     }
-    if (mem_kind != LZ4FLEX_MEM_HOST) return -LZ4FLEX_E_INVALID_ARG;
-    for (uint32_t k = 0; k < n_chains; k++)                     // host arrays can be checked: a chain stays inside `blocks`
-        if (chain_first[k] > n_blocks || chain_count[k] > n_blocks - chain_first[k]) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where != Mem::Host) return -LZ4FLEX_E_INVALID_ARG;
+    for (uint32_t i = 0; i < n_chains; i++)                     // host arrays can be checked: a chain stays inside `blocks`
+        if (chain_first[i] > n_blocks || chain_count[i] > n_blocks - chain_first[i]) return -LZ4FLEX_E_INVALID_ARG;
     lz4flex_ctx* c = ctx;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    HIP_TRY(hipSetDevice(c->device));
-    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev};
-    // spans of the caller's buffers
-    uint64_t ilo = ~0ull, ihi = 0;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    // spans of the caller's buffers (a block's dictionary lies in the input buffer too)
+    Span is;
     for (uint32_t i = 0; i < n_blocks; i++) {
-        ilo = std::min<uint64_t>(ilo, blocks[i].in_off);
-        ihi = std::max<uint64_t>(ihi, blocks[i].in_off + blocks[i].in_len);
-        if (blocks[i].dict_len) {
-            ilo = std::min<uint64_t>(ilo, blocks[i].dict_off);
-            ihi = std::max<uint64_t>(ihi, blocks[i].dict_off + blocks[i].dict_len);
-        }
+        is.add(blocks[i].in_off, blocks[i].in_len);
+        if (blocks[i].dict_len) is.add(blocks[i].dict_off, blocks[i].dict_len);
     }
-    if (ilo > ihi) { ilo = 0; ihi = 0; }
-    Span os = span_of(out_off, out_cap, n_blocks);
-    const size_t in_bytes = (size_t)(ihi - ilo), out_bytes = (size_t)(os.hi - os.lo);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 16); return at; };
-    const size_t at_blocks = take(sizeof(lz4flex_chain_block) * (size_t)n_blocks), at_first = take(4ull * n_chains),
-                 at_count = take(4ull * n_chains), at_out_off = take(8ull * n_blocks), at_out_cap = take(4ull * n_blocks);
-    const size_t desc_in = o;
-    const size_t at_out_len = take(4ull * n_blocks), at_status = take(4ull * n_blocks);
-    const size_t desc_bytes = o;
+    is = is.closed();
+    const Span os = span_of(out_off, out_cap, n_blocks);
+    const size_t in_bytes = is.bytes(), out_bytes = os.bytes();
+    Layout l{16};
+    const size_t at_blocks = l.take(sizeof(lz4flex_chain_block) * (size_t)n_blocks), at_first = l.take(4ull * n_chains),
+                 at_count = l.take(4ull * n_chains), at_out_off = l.take(8ull * n_blocks), at_out_cap = l.take(4ull * n_blocks);
+    const size_t desc_in = l.end;
+    const size_t at_out_len = l.take(4ull * n_blocks), at_status = l.take(4ull * n_blocks);
+    const size_t desc_bytes = l.end;
     const size_t tbl_bytes = tbl_state ? 16384ull * n_chains : 0;
-    if ((rc = ensure_pin(c, desc_bytes))) return rc;
+    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
     const size_t a_in = 0, a_out = align_up(in_bytes + 64, 256), a_desc = a_out + align_up(out_bytes + 64, 256),
                  a_tbl = a_desc + align_up(desc_bytes + 64, 256);
-    if ((rc = ensure_arena(c, a_tbl + tbl_bytes + 256))) return rc;
-    uint8_t* hp = c->h_pin;
+    if ((rc = ensure_buf(c->arena, a_tbl + tbl_bytes + 256))) return rc;
+    uint8_t* hp = c->pin.p;
     lz4flex_chain_block* hb = (lz4flex_chain_block*)(hp + at_blocks);
     for (uint32_t i = 0; i < n_blocks; i++) {
         hb[i] = blocks[i];
-        hb[i].in_off -= ilo;
-        hb[i].dict_off = blocks[i].dict_len ? blocks[i].dict_off - ilo : 0;
+        hb[i].in_off -= is.lo;
+        hb[i].dict_off = blocks[i].dict_len ? blocks[i].dict_off - is.lo : 0;
         ((uint64_t*)(hp + at_out_off))[i] = out_off[i] - os.lo;
         ((uint32_t*)(hp + at_out_cap))[i] = out_cap[i];
     }
     memcpy(hp + at_first, chain_first, 4ull * n_chains);
     memcpy(hp + at_count, chain_count, 4ull * n_chains);
-    uint8_t* d = c->d_arena;
+    uint8_t* d = c->arena.p;
     hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, (const uint8_t*)in_base + ilo, in_bytes, hipMemcpyHostToDevice, s));
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, (const uint8_t*)in_base + is.lo, in_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + a_desc, hp, desc_in, hipMemcpyHostToDevice, s));
     if (tbl_state) HIP_TRY(hipMemcpyAsync(d + a_tbl, tbl_state, tbl_bytes, hipMemcpyHostToDevice, s));
     uint8_t* dd = d + a_desc;
@@ -1380,11 +1236,10 @@ int64_t lz4flex_compress_into_with_dict(const uint8_t* in, size_t in_len, uint8_
     b.in_off = dict_len; b.dict_off = 0; b.in_len = (uint32_t)in_len; b.in_pos = 0; b.dict_len = (uint32_t)dict_len;
     b.so = (uint32_t)dict_len; b.repos = 0; b.flags = (h4 ? 1u : 0u) | 2u;
     const uint32_t first = 0, count = 1;
-    const uint64_t off0 = 0;
     const uint32_t cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull);
     uint32_t olen = 0;
     int32_t st = 0;
-    int rc = lz4flex_compress_chains(nullptr, buf.data(), &b, 1, &first, &count, 1, out, &off0, &cap, &olen, &st, nullptr,
+    int rc = lz4flex_compress_chains(nullptr, buf.data(), &b, 1, &first, &count, 1, out, &OFF0, &cap, &olen, &st, nullptr,
                                      LZ4FLEX_MEM_HOST, nullptr);
     if (rc) return rc;
     if (st) return -(int64_t)st;
@@ -1408,17 +1263,15 @@ static int64_t decompress_common(const uint8_t* in, size_t in_len, uint8_t* out,
     lz4flex_ctx* c;
     int rc = default_ctx(&c);
     if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
-    const uint64_t off0 = 0;
     const uint32_t len = (uint32_t)in_len, cap = (uint32_t)out_cap, dlen = (uint32_t)dict_len;
     uint32_t olen = 0;
     int32_t st = 0;
     uint64_t det[2] = {0, 0};
-    static const uint8_t empty = 0;
-    lz4flex_decompress_ext_ e{};
-    e.dict_base = dict ? dict : &empty; e.dict_off = &off0; e.dict_len = &dlen; e.out_pos = nullptr;
     static uint8_t sink_dummy = 0;
-    rc = run_host_batch(c, false, in ? in : &empty, &off0, &len, nullptr, 1, out ? out : &sink_dummy, &off0, &cap, &olen,
-                        &st, det, use_dict ? &e : nullptr);
+    BatchCall b = batch_of(false, in ? in : &EMPTY, &OFF0, &len, 1, out ? out : &sink_dummy, &OFF0, &cap, &olen, &st);
+    b.detail = det;
+    if (use_dict) { b.has_ext = true; b.dict_base = dict ? dict : &EMPTY; b.dict_off = &OFF0; b.dict_len = &dlen; }
+    rc = run_host_batch(c, b);
     if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
     if (st) {
         if (detail) { detail->expected = det[0]; detail->actual = det[1]; }
@@ -1503,15 +1356,15 @@ int64_t lz4flex_compress_into_with_table(const uint8_t* in, size_t in_len, uint8
     if (rc) return rc;
     t->ctx->comp_mode = dc->comp_mode;                         // the thread's encoder choice (throughput / reference-exact)
     t->ctx->comp_variant = dc->comp_variant;
-    const uint64_t off0 = 0;
     const uint32_t len = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull);
     // Large: HashTable4K, cleared, stream offset 0 == the frame encoder's first block (LZ4FLEX_BLOCK_FRAME_FIRST);
     // Small: what compress_into picks for inputs below 65 535 bytes
     const uint32_t flags = t->large ? LZ4FLEX_BLOCK_FRAME_FIRST : LZ4FLEX_BLOCK_DEFAULT;
     uint32_t olen = 0;
     int32_t st = 0;
-    static const uint8_t empty = 0;
-    rc = run_host_batch(t->ctx, true, in ? in : &empty, &off0, &len, &flags, 1, out, &off0, &cap, &olen, &st, nullptr, nullptr);
+    BatchCall b = batch_of(true, in ? in : &EMPTY, &OFF0, &len, 1, out, &OFF0, &cap, &olen, &st);
+    b.flags = &flags;
+    rc = run_host_batch(t->ctx, b);
     if (rc) return rc;
     if (st) return -(int64_t)st;
     return (int64_t)olen;

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "lz4_ctx.h"
 #include "lz4_device.h"
 
 namespace {
@@ -84,12 +85,6 @@ struct Desc {
     }
 };
 
-struct DeviceGuard {
-    int prev = 0;
-    explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); (void)hipSetDevice(dev); }
-    ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
 // ---- the streams the batch path leaves out: FrameEncoder / FrameDecoder over flat buffers, one stream at a time
 int compress_one(const uint8_t* d_in, uint64_t len, const lz4flex_frame_info* info, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
                  int32_t* status, hipStream_t s) {
@@ -121,7 +116,7 @@ int decompress_one(const uint8_t* d_in, uint64_t len, uint8_t* d_out, uint64_t c
 int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n,
                          const lz4flex_frame_info* info, uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
                          int32_t* status, hipStream_t s) {
-    const bool linked = info->block_mode == 1, exact = ctx_comp_mode(c) == 1;
+    const bool linked = info->block_mode == 1, exact = c->comp_mode == 1;
     const bool bsum = info->block_checksums != 0, csum = info->content_checksum != 0;
     // ---- which streams go through the batch, and their blocks
     std::vector<uint32_t> fast;                        // stream indices
@@ -484,11 +479,11 @@ int lz4flex_frame_compress_many(lz4flex_ctx* ctx, const void* in_base, const uin
     try {
     if (mem_kind != LZ4FLEX_MEM_HOST && mem_kind != LZ4FLEX_MEM_DEVICE) return -LZ4FLEX_E_INVALID_ARG;
     // (the DEVICE path too: the call's scratch is allocated on -- and cached with -- the context's device, whatever the thread's current one is)
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (mem_kind == LZ4FLEX_MEM_DEVICE)
         return compress_many_device(ctx, (const uint8_t*)in_base, in_off, in_len, n, info, (uint8_t*)out_base, out_off, out_cap, out_len, status,
                                     (hipStream_t)hip_stream);
-    hipStream_t s = ctx_stream(ctx);
+    hipStream_t s = ctx->stream;
     std::vector<uint64_t> s_in, s_out, cap(n);
     for (uint32_t i = 0; i < n; i++) cap[i] = std::min<uint64_t>(out_cap[i], lz4flex_frame_compress_bound((size_t)in_len[i], info));
     const uint64_t in_bytes = staged(in_len, n, s_in), out_bytes = staged(cap.data(), n, s_out);
@@ -514,11 +509,11 @@ int lz4flex_frame_decompress_many(lz4flex_ctx* ctx, const void* in_base, const u
     TRY_RC(ctx_resolve(&ctx));
     try {
     if (mem_kind != LZ4FLEX_MEM_HOST && mem_kind != LZ4FLEX_MEM_DEVICE) return -LZ4FLEX_E_INVALID_ARG;
-    DeviceGuard guard(ctx_device(ctx));
+    DeviceGuard guard(ctx->device);
     if (mem_kind == LZ4FLEX_MEM_DEVICE)
         return decompress_many_device(ctx, (const uint8_t*)in_base, in_off, in_len, n, (uint8_t*)out_base, out_off, out_cap, out_len, status, detail,
                                       (hipStream_t)hip_stream);
-    hipStream_t s = ctx_stream(ctx);
+    hipStream_t s = ctx->stream;
     std::vector<uint64_t> s_in, s_out;
     const uint64_t in_bytes = staged(in_len, n, s_in), out_bytes = staged(out_cap, n, s_out);
     void *d_in = nullptr, *d_out = nullptr;

@@ -1,0 +1,118 @@
+// lz4_ctx.h -- the host layer's private state: struct lz4flex_ctx (opaque in include/lz4flex_amd.h) and the few helpers every host file
+// that works on a context needs (capi.cpp, frame_many.cpp).  Host only, not installed, no kernel includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+namespace lz4flex_dev {
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// arrays laid out one behind the other, each start aligned: the layout a pinned host mirror and its device copy share
+struct Layout {
+    size_t align;
+    size_t end = 0;               // the bytes taken so far (aligned)
+    size_t take(size_t bytes) { const size_t at = end; end = align_up(end + bytes, align); return at; }
+};
+
+// the calling thread's device for the lifetime of the guard: the context's one (err: what selecting it answered)
+struct DeviceGuard {
+    int prev = 0;
+    hipError_t err;
+    explicit DeviceGuard(int dev) { (void)hipGetDevice(&prev); err = hipSetDevice(dev); }
+    ~DeviceGuard() { (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// grow-only staging memory, device or page-locked host: a larger request frees and allocates (a quarter on top, at least min_cap)
+struct GrowBuf {
+    bool pinned;
+    size_t min_cap;
+    uint8_t* p = nullptr;
+    size_t cap = 0;
+    void free() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+    hipError_t ensure(size_t need) {
+        if (need <= cap) return hipSuccess;
+        free();
+        const size_t want = std::max<size_t>(need + need / 4, min_cap);
+        const hipError_t e = pinned ? hipHostMalloc((void**)&p, want, hipHostMallocDefault) : hipMalloc((void**)&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+};
+
+// A workspace that is ONE per context while MEM_DEVICE batches are enqueued on the caller's stream: two batches on different streams
+// could overlap on the GPU and race on it.  acquire() before the first thing enqueued that touches it: a launch on another stream than
+// the previous one first makes its stream wait for that one's event (same stream: already ordered).  release() behind the last one.
+// The workspace counts as used from acquire() on: a call that fails between the two still leaves work of its stream on it.
+struct OrderedWs {
+    hipEvent_t done = nullptr;
+    hipStream_t last = nullptr;
+    bool used = false;
+    hipError_t create() { return hipEventCreateWithFlags(&done, hipEventDisableTiming); }
+    void destroy() { if (done) (void)hipEventDestroy(done); done = nullptr; }
+    hipError_t acquire(hipStream_t s) {
+        if (used && s != last) { const hipError_t w = hipStreamWaitEvent(s, done, 0); if (w != hipSuccess) return w; }
+        last = s; used = true;
+        return hipSuccess;
+    }
+    hipError_t release(hipStream_t s) { last = s; return hipEventRecord(done, s); }
+};
+
+}  // namespace lz4flex_dev
+
+struct lz4flex_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    lz4flex_dev::GrowBuf arena{false, 1u << 20};   // device staging for MEM_HOST calls
+    lz4flex_dev::GrowBuf pin{true, 1u << 16};      // pinned host staging for descriptor / result arrays
+    lz4flex_dev::GrowBuf pay{true, 1u << 20};      // pinned host staging for compacted results of MEM_HOST compress batches
+    int dec_lanes = 16;           // lanes per block, decode
+    int comp_lanes = 8;           // lanes per block, encode
+    int comp_mode = 0;            // 0 = throughput ("wave") encoder, own parse (default); 1 = reference-exact encoder (lz4_flex's bytes)
+    int comp_variant = 1;         // reference-exact encoder: 1 = group encoder + emitter wave (default), 3 = group encoder alone
+    uint8_t* pcd_ws = nullptr;    // workgroup decoder, small batches: a parser and a copier workgroup per block hand token lists over through this (lz4_device.h pair_ws)
+    lz4flex_dev::OrderedWs pcd;
+    int dec_pcd_pair = 1;         // 1: two workgroups per block for batches of few large blocks; 0: never, 2: whenever the batch is small enough (tests, measurements)
+    uint32_t* chain_ws = nullptr; // chained decode batches (Linked frames): one "done" word per block, CHAIN_WS_BLOCKS of them
+    lz4flex_dev::OrderedWs chain;
+    void* wave_ws = nullptr;      // wave encoder workspace: wave_wgs persistent workgroups; allocated by lz4flex_ctx_create
+    lz4flex_dev::OrderedWs wave;
+    unsigned long long* wave_prof = nullptr;   // tools: per-role cycle counters of the wave encoder (lz4flex_debug_wave_prof)
+    int wave_wgs = 0;
+    int dec_blocks_per_wg = 0;    // split decoder: blocks per workgroup (8/16/32/64), 0 = 64
+    int comp_det = 0;             // "compress_deterministic": 1 = a block's bytes depend on the block and the settings alone (no sub-windows by batch size)
+    int dec_level_chains = 1024;  // "decompress_level_chains": from this many Linked streams in one *_many call on, block k of every stream is one plain launch (frame_many.cpp); 0 = never
+    int comp_sub = 0;             // throughput encoder, "compress_subwindows": 0 = by batch size, 1 = never, 2 / 4 = always that many sub-windows per block of <= 64 KiB
+    int dec_variant = 0;          // 0 = by batch size, 1 = window in HBM/L2 (lz4_decompress.hip), 4 = parser / copier split (lz4_decompress_split.hip), 7 = a workgroup per block (lz4_decompress_pcd.hip; 8: its test geometry; 10 / 11: 256 / 512 lanes), 13 = a wavefront per block, a lane per sequence (lz4_decompress_seq.hip); tools builds: 9 = plan / replay, 12 = parser / emitter / quads
+    int comp_sliding = 2;         // throughput encoder: the windows of a block longer than 64 KiB advance by 48 KiB (2: every window start has 16 KiB of history) or 32 KiB (1: round 4's bytes); 0 = by 64 KiB (round 3's bytes, fastest)
+    int comp_carry_wait = 1;      // tests: 0 = a window of the throughput encoder that has to wait for its predecessor's carry gives up at once (the block then takes the second launch)
+    int dec_second_pass = 1;      // tests: 0 leaves the blocks a first-pass decoder marked (status DECODE_REDO) instead of decoding them again
+    // plan / replay decoder (lz4_decompress_plan.hip, lz4_decompress_replay.hip): the copy plans of a batch, plan_slot_words() words per
+    // block + a 32-byte header each.  Grows with the largest batch seen (a hipMalloc -- a device synchronisation -- in the first such
+    // call and whenever a larger batch arrives; never shrinks).
+    uint8_t* plan_ws = nullptr;
+    size_t plan_cap = 0;
+    lz4flex_dev::OrderedWs plan;
+    int chain_giveup = 0;         // tests: block chain_giveup - 1 of the next chained decode batches gives up without an error (the ordered second pass decodes it and everything behind it)
+    // many frames at once (frame_many.cpp): device scratch of the calls that run to completion before they return (compressed staging,
+    // descriptor arrays, staged host buffers).  Grow-only, a hipMalloc when a larger job arrives; freed with the context.
+    void* many_ws[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t many_cap[4] = {0, 0, 0, 0};
+    int fail_next_batch = 0;      // tests: the next N batch calls on this context fail before they launch anything (what an allocation failure looks like to the caller)
+    int comp_shared = 1;          // "compress_shared_dict": 1 = lz4flex_compress_batch_shared_dict starts its items from the dictionary's digest; 0 = every item takes the per-block path (A/B measurements, tests)
+    bool shared_counted = false;  // the last shared-dictionary call ran the throughput encoder: its digest counter is what "debug_shared_dict_items" reads
+    int dec_shared = 1;           // "decompress_shared_dict": 1 = lz4flex_decompress_batch_shared_dict runs the sequence decoder's dictionary form; 0 = every block through decode_block<16, true>, the per-block path (A/B measurements, tests)
+    int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
+};
+
+namespace lz4flex_dev {
+// capi.cpp, for frame_many.cpp: *ctx = the calling thread's default context if null; grow-only device scratch in 4 slots (valid until
+// the next ctx_scratch of the same slot; the caller runs to completion before it returns)
+int ctx_resolve(lz4flex_ctx** ctx);
+int ctx_scratch(lz4flex_ctx* c, int slot, size_t bytes, void** out);
+}  // namespace lz4flex_dev

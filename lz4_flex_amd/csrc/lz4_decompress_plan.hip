@@ -472,7 +472,7 @@ extern "C" int lz4flex_debug_plan(const void* in_base, const void* in_off, const
     a.in_base = (const uint8_t*)in_base; a.in_off = (const uint64_t*)in_off; a.in_len = (const uint32_t*)in_len;
     a.out_off = (const uint64_t*)out_off; a.out_cap = (const uint32_t*)out_cap;
     a.plans = (lz4flex_dev::plan::BlockPlan*)plans; a.words = (uint32_t*)words; a.out_len = (uint32_t*)out_len; a.status = (int32_t*)status;
-    a.n = n; a.slot_words = (uint32_t)lz4flex_dev::plan_slot_words(); a.redo_code = 0x7F000001;
+    a.n = n; a.slot_words = (uint32_t)lz4flex_dev::plan_slot_words(); a.redo_code = lz4flex_dev::DECODE_REDO;
     return (int)lz4flex_dev::launch_plan(a, (hipStream_t)stream);
 }
 extern "C" unsigned lz4flex_debug_plan_slot_words() { return (unsigned)lz4flex_dev::plan_slot_words(); }

@@ -1,5 +1,5 @@
 // lz4_device.h -- kernel argument blocks and launch entry points shared by the HIP kernels
-// and the host C ABI (capi.cpp).  Device-side status codes mirror include/lz4flex_amd.h.
+// and the host C ABI (capi.cpp; its context and host-only helpers: lz4_ctx.h).  Device-side status codes mirror include/lz4flex_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,8 +10,6 @@
 #define LZ4FLEX_DEV_E_OFFSET_ZERO 4
 #define LZ4FLEX_DEV_E_OFFSET_OUT_OF_BOUNDS 5
 #define LZ4FLEX_DEV_E_INVALID_ARG 64        // a sink position behind the sink's end (out_pos > out_cap): the reference panics there
-
-struct lz4flex_ctx;
 
 namespace lz4flex_dev {
 
@@ -199,14 +197,8 @@ hipError_t launch_copy_batch(const uint8_t* src_base, const uint64_t* src_off, c
 constexpr int32_t SIZE_SCAN_REDO = 0x7F000003;
 hipError_t launch_size_scan(const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* history, uint32_t n,
                             uint64_t* out_size, int32_t* status, int serial_only, hipStream_t s);
-
-
-// capi.cpp, for frame_many.cpp: *ctx = the calling thread's default context if null; the context's device / own stream / compress_mode;
-// grow-only device scratch in 4 slots (valid until the next ctx_scratch of the same slot; the caller runs to completion before it returns)
-int ctx_resolve(struct ::lz4flex_ctx** ctx);
-int ctx_device(struct ::lz4flex_ctx* c);
-hipStream_t ctx_stream(struct ::lz4flex_ctx* c);
-int ctx_comp_mode(struct ::lz4flex_ctx* c);
-int ctx_scratch(struct ::lz4flex_ctx* c, int slot, size_t bytes, void** out);
+// DECODE_REDO: the status a first-pass decoder (sequence, workgroup, plan, fused) leaves on a block it does not decode: the host then runs a reference-order
+// kernel with only_status = DECODE_REDO over the batch (capi.cpp launch_redo)
+constexpr int32_t DECODE_REDO = 0x7F000001;
 
 }  // namespace lz4flex_dev

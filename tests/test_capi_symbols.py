@@ -147,3 +147,94 @@ def test_many_frames_entry_points_check_their_arguments_without_a_device():
         from lz4_flex_amd import block
         with pytest.raises(block.DeviceError):
             frame.compress_frames([b"no gpu, no codec"])
+
+
+def _one_block_args():
+    """a valid 1-block host batch (one literal) as ctypes arrays: in, in_off, in_len, out, out_off, out_cap, out_len, status"""
+    import ctypes as C
+    return (C.create_string_buffer(bytes([0x10, 0x61]), 16), (C.c_uint64 * 1)(0), (C.c_uint32 * 1)(2), C.create_string_buffer(64),
+            (C.c_uint64 * 1)(0), (C.c_uint32 * 1)(64), (C.c_uint32 * 1)(0), (C.c_int32 * 1)(0))
+
+
+def test_batched_entry_points_keep_their_order_of_checks_and_mem_kinds(lib_path):
+    """lz4flex_compress_batch / lz4flex_decompress_batch look for a context before they look at the arrays; the dictionary path of
+    lz4flex_compress_batch_ex and both *_shared_dict entries check their arguments first and accept fewer mem_kind values (the table in
+    capi.cpp's classify_mem calls).  Callers see both."""
+    import ctypes as C
+    from lz4_flex_amd import _lib
+    lib = _lib.load()
+    INV, NODEV = -_lib.E_INVALID_ARG, -_lib.E_NO_DEVICE
+    have = lib.lz4flex_device_count() > 0
+    src, in_off, in_len, out, out_off, cap, out_len, st = _one_block_args()
+    dic = C.create_string_buffer(b"dictionary", 16)
+    dlen = (C.c_uint32 * 1)(10)
+    ext = _lib.CompressExt(C.cast(dic, C.c_void_p), C.cast(in_off, C.c_void_p), C.cast(dlen, C.c_void_p))
+
+    def compress(mem, off=in_off):
+        return lib.lz4flex_compress_batch(None, src, off, in_len, None, 1, out, out_off, cap, out_len, st, mem, None)
+
+    def decompress(mem, off=in_off):
+        return lib.lz4flex_decompress_batch(None, src, off, in_len, 1, out, out_off, cap, out_len, st, None, mem, None)
+
+    def compress_ex(mem, off=in_off):
+        return lib.lz4flex_compress_batch_ex(None, src, off, in_len, None, 1, out, out_off, cap, out_len, st, C.byref(ext), mem, None)
+
+    def compress_shared(mem, off=in_off):
+        return lib.lz4flex_compress_batch_shared_dict(None, src, off, in_len, 1, out, out_off, cap, out_len, st, dic, 10, mem, None)
+
+    def decompress_shared(mem, off=in_off):
+        return lib.lz4flex_decompress_batch_shared_dict(None, src, off, in_len, 1, out, out_off, cap, out_len, st, None, dic, 10, mem, None)
+
+    if not have:
+        assert compress(_lib.MEM_HOST, None) == NODEV and decompress(_lib.MEM_HOST, None) == NODEV
+        assert compress(7) == NODEV and decompress(7) == NODEV
+    for entry in (compress_ex, compress_shared, decompress_shared):
+        assert entry(_lib.MEM_HOST, None) == INV, entry.__name__
+        for mem in (7, _lib.MEM_DEVICE | _lib.MEM_CHAINED, 0x1001):
+            assert entry(mem) == INV, (entry.__name__, hex(mem))
+    assert compress_ex(_lib.MEM_HOST | _lib.MEM_BIG_BLOCKS) == INV and compress_shared(_lib.MEM_HOST | _lib.MEM_BIG_BLOCKS) == INV
+    # accepted: the call goes on to its context (and, with a device, decodes the block)
+    st[0], out_len[0] = -1, 99
+    assert decompress_shared(_lib.MEM_HOST | _lib.MEM_BIG_BLOCKS) == (0 if have else NODEV)
+    if have:
+        assert (st[0], out_len[0], out.raw[:1]) == (0, 1, b"a")
+    else:
+        assert (st[0], out_len[0]) == (-1, 99)
+    assert compress_ex(_lib.MEM_HOST) == (0 if have else NODEV) and compress_shared(_lib.MEM_HOST) == (0 if have else NODEV)
+
+
+SETTINGS = ["decompress_lanes", "compress_mode", "compress_subwindows", "compress_deterministic", "decompress_level_chains",
+            "decompress_blocks_per_wg", "decompress_variant", "decompress_second_pass", "decompress_pcd_pair", "compress_carry_wait",
+            "compress_sliding_window", "compress_variant", "compress_lanes", "size_scan_serial", "compress_shared_dict",
+            "decompress_shared_dict"]
+HOOKS = ["debug_chain_giveup", "debug_fail_next_batch"]            # set only
+READ_ONLY = ["compress_workgroups", "debug_shared_dict_items"]     # (dispatch_threshold_<i>, decoder_config_<i>: the two tests above)
+
+
+def test_every_settings_key_without_a_context(lib_path):
+    """lz4flex_set_tuning / lz4flex_get_tuning with a NULL context: an unknown key is refused as such on any machine, a known one goes
+    on to the default context -- which needs a device; the test hooks do not exist in a process that has not asked for them"""
+    import sys
+    from lz4_flex_amd import _lib
+    lib = _lib.load()
+    INV, NODEV = -_lib.E_INVALID_ARG, -_lib.E_NO_DEVICE
+    assert os.environ.get("LZ4FLEX_TEST_HOOKS") == "1"
+    for key in ("no_such_key", "", "debug_no_such_hook", "compress_mode_", "Compress_mode"):
+        assert lib.lz4flex_set_tuning(None, key.encode(), 0) == INV, key
+        assert lib.lz4flex_get_tuning(None, key.encode()) == INV, key
+    assert lib.lz4flex_set_tuning(None, None, 0) == INV and lib.lz4flex_get_tuning(None, None) == INV
+    assert lib.lz4flex_set_tuning(None, b"debug_shared_dict_items", 0) == INV
+    if lib.lz4flex_device_count() == 0:
+        for key in SETTINGS + HOOKS + READ_ONLY:
+            assert lib.lz4flex_get_tuning(None, key.encode()) == NODEV, key
+        for key in SETTINGS + HOOKS + READ_ONLY[:1]:
+            assert lib.lz4flex_set_tuning(None, key.encode(), 1) == NODEV, key
+    # without LZ4FLEX_TEST_HOOKS=1 every "debug_" key is refused before a context is looked for
+    env = {k: v for k, v in os.environ.items() if k != "LZ4FLEX_TEST_HOOKS"}
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from lz4_flex_amd import _lib\n"
+            "lib = _lib.load()\n"
+            "for k in %r:\n"
+            "    assert lib.lz4flex_set_tuning(None, k.encode(), 0) == -_lib.E_INVALID_ARG, k\n"
+            "    assert lib.lz4flex_get_tuning(None, k.encode()) == -_lib.E_INVALID_ARG, k\n" % (ROOT, HOOKS + ["debug_shared_dict_items"]))
+    subprocess.check_call([sys.executable, "-c", code], env=env)
