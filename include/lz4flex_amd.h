@@ -83,7 +83,9 @@ const char *lz4flex_build_id(void);
  * (per-block dictionaries for compressing, both compress modes) -- the context's device workspace grew by 64 KiB per encoder workgroup.
  * Later additions that change nothing for an existing call keep the number: lz4flex_compress_batch_shared_dict and the setting
  * "compress_shared_dict" came after round 8 (the workspace grew by 41 KiB per context), then lz4flex_decompress_batch_shared_dict and
- * the setting "decompress_shared_dict" (no workspace) -- a caller detects them by the symbol. */
+ * the setting "decompress_shared_dict" (no workspace), then the packed entries lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed
+ * with lz4flex_packed_work_size, lz4flex_compress_packed_scratch_bound and the read-only setting "packed_scan_tile" (no workspace in the
+ * context: the caller brings it) -- a caller detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -299,6 +301,72 @@ int lz4flex_decompressed_size_batch(lz4flex_ctx *ctx, const void *in_base, const
                                     uint32_t n, const uint32_t *history, uint64_t *out_size, int32_t *status, int mem_kind,
                                     void *hip_stream);
 
+/* ---- packed batches: ONE output buffer, the offsets computed on the device -------------------------------------------------
+ * The batched entries above take the output layout from the caller (out_off[], out_cap[]).  A caller that holds n size-prepended
+ * blocks (block::compress_prepend_size's output), or raw blocks, cannot know that layout before the sizes are known; a caller that
+ * compresses wants the produced bytes back to back with an offset table, not one worst-case slot per block.  The two entries below
+ * take ONE buffer of total_cap bytes and write the layout themselves: out_off[0 .. n] = the exclusive prefix sums of the slot sizes,
+ * each rounded up to `align` (a power of two from 1 to 256; 1 = dense), out_off[n] = the bytes the batch needs.
+ *   The fit rule: block i fits iff out_off[i] + size[i] <= total_cap.  A block that does not fit gets status LZ4FLEX_E_OUTPUT_TOO_SMALL,
+ *     out_len 0, capacity 0 and (decode) detail {expected = out_off[i] + size[i], actual = total_cap}; nothing of it is written.  It is
+ *     applied to every block, also to one whose size is 0 or unknown.  out_off[] is the pure scan in every case: out_off[n] is the
+ *     capacity the batch needs even when it exceeds total_cap, so a caller can enlarge the buffer and call again.
+ *   total_cap and align are HOST values.  mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, `work` holds
+ *     lz4flex_packed_work_size(n) bytes (8-byte aligned), the call is asynchronous on hip_stream, allocates nothing, copies nothing to
+ *     the host and never synchronises -- or LZ4FLEX_MEM_HOST -- staged through the context and synchronous; `work` and `scratch` are
+ *     ignored.  LZ4FLEX_MEM_BIG_BLOCKS may be ORed in; LZ4FLEX_MEM_CHAINED is refused.  No dictionaries.
+ *   The arguments are checked before a context or a device is looked at: -LZ4FLEX_E_INVALID_ARG for an unknown size_mode, an align that
+ *     is not a power of two from 1 to 256, a mem_kind other than HOST / DEVICE (| BIG_BLOCKS), and -- n != 0 -- a missing array,
+ *     sizes == NULL in GIVEN mode, work == NULL (compress: or scratch == NULL) in a DEVICE call.  n == 0 returns 0.
+ *   The kernels (lz4_packed.hip): the sizes, an exclusive scan in three phases (every workgroup sums a tile of "packed_scan_tile" sizes
+ *     -- a read-only setting --, one workgroup scans the tile sums, every workgroup scans its tile; integer sums in a fixed order), and
+ *     on the compress side a gather, one workgroup per block, 16 bytes per lane where source and destination allow.
+ *   Not timed: tools/packed_bench.py times both entries against the plain batch calls and against block.decompress_blocks_device
+ *     (profiles/r11_packed.txt awaits the table). */
+#define LZ4FLEX_SIZES_PREPENDED 0   /* block::decompress_size_prepended, src/block/decompress.rs:493-499 */
+#define LZ4FLEX_SIZES_GIVEN     1   /* block::decompress(input, min_uncompressed_size), :508-517 */
+#define LZ4FLEX_SIZES_SCAN      2   /* raw blocks, sizes by lz4flex_decompressed_size_batch */
+
+/* bytes of `work` a MEM_DEVICE call of either packed entry needs for n blocks */
+size_t lz4flex_packed_work_size(uint32_t n);
+/* bytes of `scratch` that hold the slots of lz4flex_compress_batch_packed for ANY n blocks of total_in_bytes bytes together: at least
+ * the sum of get_maximum_output_size(in_len[i]) + (prepend_size ? 4 : 0) */
+uint64_t lz4flex_compress_packed_scratch_bound(uint64_t total_in_bytes, uint32_t n, int prepend_size);
+
+/* Decompress n independent blocks into one buffer, slot after slot.  The slot size of block i:
+ *   LZ4FLEX_SIZES_PREPENDED: the LE u32 in front of the block (in_base[in_off[i] .. + 4), any alignment); the block proper is the
+ *     in_len[i] - 4 bytes behind it.  in_len[i] < 4: size 0 and status LZ4FLEX_E_EXPECTED_ANOTHER_BYTE (block::uncompressed_size,
+ *     src/block/mod.rs:151-157).  out_len may be smaller than the prefix (the reference truncates its Vec); the slot keeps the prefix's
+ *     size.  A hostile prefix does not fit and gets OUTPUT_TOO_SMALL -- the reference would allocate it.
+ *   LZ4FLEX_SIZES_GIVEN: sizes[i], the min_uncompressed_size of block::decompress.
+ *   LZ4FLEX_SIZES_SCAN: what lz4flex_decompressed_size_batch measures (history 0).  A block the size pass rejects keeps that status
+ *     and gets an empty slot; a block of more than 4 GiB - 1 bytes gets size 0 and status LZ4FLEX_E_UNSUPPORTED.
+ * Written: out_off (n + 1), out_cap (n: the slot sizes, 0 for a block without room), out_len, status, detail (nullable, 2 n: every
+ * entry is written, {0, 0} for a block whose status is not OUTPUT_TOO_SMALL).
+ * A block that fits gets exactly what lz4flex_decompress_batch gives it with out_off[i] and out_cap[i] = its slot size: bytes, out_len,
+ * every DecompressError variant, and the OutputTooSmall detail counted from the slot.  Nothing is written outside
+ * [out_off[i], out_off[i] + out_len[i]) of fitting blocks, and nothing beyond total_cap. */
+int lz4flex_decompress_batch_packed(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                    uint32_t n, int size_mode, const uint32_t *sizes /* GIVEN only */, void *out_base,
+                                    uint64_t total_cap, uint32_t align, uint64_t *out_off /* n + 1, written */,
+                                    uint32_t *out_cap /* n, written: the slot sizes */, uint32_t *out_len, int32_t *status,
+                                    uint64_t *detail /* nullable */, void *work, int mem_kind, void *hip_stream);
+
+/* Compress n independent blocks into one packed stream.  The encoder writes block i into a slot of get_maximum_output_size(in_len[i])
+ * (+ 4 with prepend_size) bytes of `scratch`, slot behind slot; the produced lengths are scanned into out_off and the payloads copied
+ * to out_base + out_off[i].  The payload of block i is, byte for byte, what lz4flex_compress_batch (flags NULL) gives the same batch
+ * under the same settings.  prepend_size != 0: the payload follows the LE u32 in_len[i] and out_len[i] counts the 4 -- under
+ * compress_mode exact the reference's compress_prepend_size output (src/block/compress.rs:673-675), what LZ4FLEX_SIZES_PREPENDED reads.
+ * A block the encoder refuses keeps its status and takes no room in the stream (out_len 0).
+ * scratch_cap: MEM_HOST (the lengths are visible) -LZ4FLEX_E_INVALID_ARG when it is below the sum of the slots; MEM_DEVICE: the fit rule
+ * on the scratch slots -- a block whose slot ends behind scratch_cap gets OUTPUT_TOO_SMALL, the others are unaffected.
+ * lz4flex_compress_packed_scratch_bound gives a capacity that always holds.
+ * Written: out_off (n + 1), out_len, status. */
+int lz4flex_compress_batch_packed(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                  uint32_t n, int prepend_size, void *scratch, uint64_t scratch_cap, void *out_base,
+                                  uint64_t total_cap, uint32_t align, uint64_t *out_off /* n + 1, written */, uint32_t *out_len,
+                                  int32_t *status, void *work, int mem_kind, void *hip_stream);
+
 /* Optional per-block extras for decoding: an external dictionary (block::decompress_into_with_dict,
  * src/block/decompress.rs:462-468) and/or an initial sink position: the output region
  * [out_off, out_off+out_pos) already holds earlier bytes that matches may reference (the prefix mode
@@ -398,7 +466,8 @@ int lz4flex_decompress_batch_shared_dict(lz4flex_ctx *ctx, const void *in_base, 
  *   a call that holds at least this many Linked streams decodes block k of every stream in ONE launch -- a plain batch whose prefixes
  *   the launches before it have written -- instead of a workgroup per block that polls its predecessor: thousands of short streams,
  *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict);
- *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict).
+ *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict);
+ *   "packed_scan_tile" (read-only: the sizes one workgroup of the packed entries' offset scan takes, see the packed batches).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
  * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.
  * The key is looked at before a context is: an unknown key and a refused "debug_" key answer -LZ4FLEX_E_INVALID_ARG on any machine,

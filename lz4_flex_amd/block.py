@@ -614,3 +614,140 @@ def decompress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, s
     status = torch.where(status != 0, status, st2)
     out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
     return out[:total], out_off, out_len, status
+
+
+# ---- packed batches: one output buffer, the offsets computed on the device (lz4flex_*_batch_packed) ------------------------
+SIZE_MODES = {"prepended": L.SIZES_PREPENDED, "given": L.SIZES_GIVEN, "scan": L.SIZES_SCAN}
+
+
+def decompress_batch_packed(in_buf, in_off, in_len, out_buf, size_mode="prepended", sizes=None, align=1, total_cap=None, big_blocks=False,
+                            ctx=None):
+    """lz4flex_decompress_batch_packed over host buffers: block i = in_buf[in_off[i] : + in_len[i]] is decoded into out_buf, slot behind
+    slot.  size_mode "prepended": the blocks carry block::compress_prepend_size's LE u32 (block::decompress_size_prepended as a batch);
+    "given": sizes[i] is block i's capacity (block::decompress); "scan": raw blocks, measured on the device.  total_cap (default: all of
+    out_buf) bounds what is written; a block whose slot ends behind it gets OutputTooSmall.  Returns (out_off[u64, n + 1], out_cap[u32],
+    out_len[u32], status[i32], detail[n, 2] u64): block i's bytes are out_buf[out_off[i] : out_off[i] + out_len[i]], out_off[n] is the
+    capacity the batch needs."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    sz, szp = (None, None) if sizes is None else _np(sizes, np.uint32)
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    out_cap = np.zeros(n, dtype=np.uint32)
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    detail = np.zeros((n, 2), dtype=np.uint64)
+    cap = int(out_buf.size) if total_cap is None else int(total_cap)
+    rc = lib.lz4flex_decompress_batch_packed(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, SIZE_MODES[size_mode], szp,
+                                             C.c_void_p(out_buf.ctypes.data if out_buf.size else 0), cap, int(align),
+                                             C.c_void_p(out_off.ctypes.data), C.c_void_p(out_cap.ctypes.data), C.c_void_p(out_len.ctypes.data),
+                                             C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), None,
+                                             L.MEM_HOST | (L.MEM_BIG_BLOCKS if big_blocks else 0), None)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_packed failed (%d): %s" % (rc, L.last_error()))
+    return out_off, out_cap, out_len, status, detail
+
+
+def compress_batch_packed(in_buf, in_off, in_len, out_buf, prepend_size=True, align=1, total_cap=None, ctx=None):
+    """lz4flex_compress_batch_packed over host buffers: the blocks in_buf[in_off[i] : + in_len[i]] compressed back to back into out_buf
+    (prepend_size: each behind its LE u32 length, block::compress_prepend_size).  Returns (out_off[u64, n + 1], out_len[u32],
+    status[i32]): block i's bytes are out_buf[out_off[i] : out_off[i] + out_len[i]], out_off[n] is the capacity the stream needs."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    cap = int(out_buf.size) if total_cap is None else int(total_cap)
+    slots = int(lib.lz4flex_compress_packed_scratch_bound(int(il.sum(dtype=np.uint64)), n, 1 if prepend_size else 0))
+    rc = lib.lz4flex_compress_batch_packed(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, 1 if prepend_size else 0,
+                                           None, slots, C.c_void_p(out_buf.ctypes.data if out_buf.size else 0), cap, int(align),
+                                           C.c_void_p(out_off.ctypes.data), C.c_void_p(out_len.ctypes.data), C.c_void_p(status.ctypes.data),
+                                           None, L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_packed failed (%d): %s" % (rc, L.last_error()))
+    return out_off, out_len, status
+
+
+def _packed_device_args(src, in_off, in_len):
+    import torch
+    dev = src.device
+    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n:
+        raise ValueError("in_off and in_len differ in length")
+    return dev, n, in_off.to(device=dev, dtype=torch.int64).contiguous(), in_len.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def decompress_blocks_packed_device(src, in_off, in_len, capacity, size_mode="prepended", sizes=None, align=1, big_blocks=False, stream=None,
+                                    ctx=None):
+    """Blocks in device memory, decoded into ONE buffer of `capacity` bytes whose layout is computed on the device: src is a uint8 torch
+    tensor on the GPU, block i is src[in_off[i] : in_off[i] + in_len[i]] (size_mode as for decompress_batch_packed; "given": sizes is an
+    integer tensor).  One lz4flex_decompress_batch_packed (MEM_DEVICE, asynchronous on `stream`, default the current one): no host
+    synchronisation, nothing copied to the host.  Returns (out, out_off, out_len, status) as device tensors: out has `capacity` bytes,
+    out_off n + 1 entries (the last one: the capacity the batch needs), block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]; a
+    block whose slot ends behind `capacity` has status E_OUTPUT_TOO_SMALL and nothing of it is written."""
+    import torch
+    lib = L.load()
+    dev, n, d_off, d_len = _packed_device_args(src, in_off, in_len)
+    capacity = int(capacity)
+    out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    out_cap = torch.empty(n, dtype=torch.int32, device=dev)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:capacity], out_off, out_len, status
+    d_sizes = None if sizes is None else sizes.to(device=dev, dtype=torch.int64).to(torch.int32).contiguous()
+    work = torch.empty(int(lib.lz4flex_packed_work_size(n)), dtype=torch.uint8, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.lz4flex_decompress_batch_packed(ctx, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                             SIZE_MODES[size_mode], None if d_sizes is None else C.c_void_p(d_sizes.data_ptr()),
+                                             C.c_void_p(out.data_ptr()), capacity, int(align), C.c_void_p(out_off.data_ptr()),
+                                             C.c_void_p(out_cap.data_ptr()), C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()),
+                                             None, C.c_void_p(work.data_ptr()), L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if big_blocks else 0),
+                                             C.c_void_p(stream))
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_packed failed (%d): %s" % (rc, L.last_error()))
+    return out[:capacity], out_off, out_len, status
+
+
+def compress_blocks_packed_device(src, in_off, in_len, capacity, prepend_size=True, align=1, big_blocks=False, scratch_cap=None, stream=None,
+                                  ctx=None):
+    """Blocks in device memory, compressed back to back into ONE buffer of `capacity` bytes: src is a uint8 torch tensor on the GPU, block
+    i is src[in_off[i] : in_off[i] + in_len[i]]; prepend_size: every block behind its LE u32 length (block::compress_prepend_size).  One
+    lz4flex_compress_batch_packed (MEM_DEVICE, asynchronous on `stream`, default the current one): no host synchronisation.  The scratch
+    slots are sized for blocks that together have no more bytes than src (scratch_cap: another capacity; blocks whose slots end behind
+    it get E_OUTPUT_TOO_SMALL).  big_blocks: the batch may hold blocks of more than 64 KiB (compress_mode exact needs to know).  Returns
+    (out, out_off, out_len, status) as device tensors: out has `capacity` bytes, out_off n + 1 entries (the last one: the capacity the
+    stream needs), block i's bytes are out[out_off[i] : out_off[i] + out_len[i]] -- what decompress_blocks_packed_device reads."""
+    import torch
+    lib = L.load()
+    dev, n, d_off, d_len = _packed_device_args(src, in_off, in_len)
+    capacity = int(capacity)
+    out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:capacity], out_off, out_len, status
+    if scratch_cap is None:
+        scratch_cap = int(lib.lz4flex_compress_packed_scratch_bound(int(src.numel()), n, 1 if prepend_size else 0))
+    scratch = torch.empty(max(int(scratch_cap), 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(lib.lz4flex_packed_work_size(n)), dtype=torch.uint8, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = lib.lz4flex_compress_batch_packed(ctx, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                           1 if prepend_size else 0, C.c_void_p(scratch.data_ptr()), int(scratch_cap),
+                                           C.c_void_p(out.data_ptr()), capacity, int(align), C.c_void_p(out_off.data_ptr()),
+                                           C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(work.data_ptr()),
+                                           L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if big_blocks else 0), C.c_void_p(stream))
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_packed failed (%d): %s" % (rc, L.last_error()))
+    return out[:capacity], out_off, out_len, status

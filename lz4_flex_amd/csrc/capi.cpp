@@ -436,6 +436,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     lz4flex_ctx* c = new (std::nothrow) lz4flex_ctx();
     if (!c) return -LZ4FLEX_E_NOMEM;
     c->device = device;
+    c->packed_tile = (int)PACKED_SCAN_TILE;
     if (const char* e = getenv("LZ4FLEX_COMPRESS_MODE")) c->comp_mode = (!strcmp(e, "exact") || !strcmp(e, "1")) ? 1 : 0;
     if (const char* e = getenv("LZ4FLEX_SLIDING_WINDOW")) {      // "0", "1" or "2", nothing else ("off" used to read as 0 silently: ADVICE r4)
         if (!strcmp(e, "0") || !strcmp(e, "1") || !strcmp(e, "2")) c->comp_sliding = e[0] - '0';
@@ -567,6 +568,8 @@ const Setting SETTINGS[] = {
     {"size_scan_serial", &lz4flex_ctx::size_serial, is_flag, false},
     {"compress_shared_dict", &lz4flex_ctx::comp_shared, is_flag, false},
     {"decompress_shared_dict", &lz4flex_ctx::dec_shared, is_flag, false},
+    // (the sizes one workgroup of the packed entries' offset scan takes: lz4_device.h PACKED_SCAN_TILE; the tests cut their batches around it)
+    {"packed_scan_tile", &lz4flex_ctx::packed_tile, read_only, false},
     // (what "compress_subwindows" 0 decides by: n * 4 <= this -> 4, n * 3 <= this -> 3, n * 2 <= this -> 2)
     {"compress_workgroups", &lz4flex_ctx::wave_wgs, read_only, false},
     {"debug_chain_giveup", &lz4flex_ctx::chain_giveup, is_count, true},
@@ -1119,6 +1122,229 @@ int lz4flex_decompressed_size_batch(lz4flex_ctx* ctx, const void* in_base, const
     memcpy(out_size, hp + at_size, 8ull * n);
     memcpy(status, hp + at_status, 4ull * n);
     return 0;
+}
+
+// ---- packed batches: ONE output buffer, the layout computed on the device (lz4_packed.hip) -----------------------------------
+}  // extern "C"
+
+namespace {
+
+bool packed_align_ok(uint32_t a) { return a >= 1u && a <= 256u && (a & (a - 1u)) == 0u; }
+
+// everything the public decode entry takes, as device pointers
+struct PackedDecode {
+    const uint8_t* in_base; const uint64_t* in_off; const uint32_t* in_len; uint32_t n; int size_mode; const uint32_t* sizes;
+    uint8_t* out_base; uint64_t total_cap; uint32_t align; uint64_t* out_off; uint32_t* out_cap; uint32_t* out_len; int32_t* status;
+    uint64_t* detail; void* work; bool big; hipStream_t stream;
+};
+// the slot sizes, out_off[0 .. n], out_cap and the blocks without size or room (PackedWork::pre): three small launches (SCAN: behind
+// the size pass)
+int packed_decode_layout(lz4flex_ctx* c, const PackedDecode& d) {
+    const PackedWork w = packed_work(d.work, d.n);
+    hipError_t e = hipSuccess;
+    if (d.size_mode == LZ4FLEX_SIZES_SCAN) e = launch_size_scan(d.in_base, d.in_off, d.in_len, nullptr, d.n, w.size, w.pre, c->size_serial, d.stream);
+    if (e == hipSuccess) e = launch_packed_sizes(d.size_mode, d.in_base, d.in_off, d.in_len, d.sizes, nullptr, d.n, 0u, w.size, w.aux_off, w.aux_len, w.pre, d.stream);
+    if (e == hipSuccess) e = launch_packed_scan(w.size, d.n, d.align, d.total_cap, 0u, w.tiles, d.out_off, w.place, d.out_cap, w.pre, d.stream);
+    return e != hipSuccess ? hip_fail(e, "packed layout launch") : 0;
+}
+// the decoder on the slots (a block without size or room has capacity 0: nothing of it is written), then those blocks' own status
+int packed_decode_run(lz4flex_ctx* c, const PackedDecode& d) {
+    const PackedWork w = packed_work(d.work, d.n);
+    const bool prepended = d.size_mode == LZ4FLEX_SIZES_PREPENDED;
+    BatchCall b = batch_of(false, d.in_base, prepended ? w.aux_off : d.in_off, prepended ? w.aux_len : d.in_len, d.n, d.out_base, w.place,
+                           d.out_cap, d.out_len, d.status, d.stream);
+    b.detail = d.detail; b.big = d.big;
+    const int rc = run_device_batch(c, b);
+    if (rc) return rc;
+    const hipError_t e = launch_packed_finish(w.pre, w.size, d.out_off, d.n, d.total_cap, d.out_len, d.status, d.detail, d.stream);
+    return e != hipSuccess ? hip_fail(e, "packed finish launch") : 0;
+}
+
+struct PackedCompress {
+    const uint8_t* in_base; const uint64_t* in_off; const uint32_t* in_len; uint32_t n; uint32_t prefix; uint8_t* scratch; uint64_t scratch_cap;
+    uint8_t* out_base; uint64_t total_cap; uint32_t align; uint64_t* out_off; uint32_t* out_len; int32_t* status; void* work; bool big;
+    hipStream_t stream;
+};
+// scratch slots of get_maximum_output_size (+ prefix) bytes back to back, the encoder into them, the produced lengths scanned into
+// out_off, the gather.  A slot beyond scratch_cap has capacity 0: the encoder answers OUTPUT_TOO_SMALL for that block.
+int packed_compress_run(lz4flex_ctx* c, const PackedCompress& d) {
+    const PackedWork w = packed_work(d.work, d.n);
+    hipStream_t s = d.stream;
+    hipError_t e = launch_packed_sizes(PACKED_SIZES_SLOTS, d.in_base, d.in_off, d.in_len, nullptr, nullptr, d.n, d.prefix, w.size, nullptr, nullptr, w.pre, s);
+    if (e == hipSuccess) e = launch_packed_scan(w.size, d.n, 1u, d.scratch_cap, d.prefix, w.tiles, w.aux_off, w.place, w.aux_len, w.pre, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d.out_len, 0, 4ull * d.n, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d.status, 0, 4ull * d.n, s);
+    if (e != hipSuccess) return hip_fail(e, "packed layout launch");
+    BatchCall b = batch_of(true, d.in_base, d.in_off, d.in_len, d.n, d.scratch, w.place, w.aux_len, d.out_len, d.status, s);
+    b.big = d.big;
+    const int rc = run_device_batch(c, b);
+    if (rc) return rc;
+    e = launch_packed_sizes(PACKED_SIZES_PRODUCED, nullptr, nullptr, nullptr, d.out_len, d.status, d.n, d.prefix, w.size, nullptr, nullptr, nullptr, s);
+    if (e == hipSuccess) e = launch_packed_scan(w.size, d.n, d.align, d.total_cap, 0u, w.tiles, d.out_off, nullptr, nullptr, nullptr, s);
+    if (e == hipSuccess) e = launch_packed_gather(d.scratch, w.place, w.size, d.out_off, d.in_len, d.n, d.prefix, d.total_cap, d.out_base, d.out_len, d.status, s);
+    return e != hipSuccess ? hip_fail(e, "packed gather launch") : 0;
+}
+
+// MEM_HOST: the produced bytes [0, used) of the device buffer come down in one transfer; every good block's bytes go to their place in
+// the caller's buffer (the gaps between blocks and everything behind them stay the caller's)
+int packed_scatter_to_host(lz4flex_ctx* c, const uint8_t* d_out, uint64_t used, uint8_t* out_base, const uint64_t* off, const uint32_t* len,
+                           const int32_t* st, uint32_t n) {
+    if (!used) return 0;
+    int rc;
+    if ((rc = ensure_buf(c->pay, (size_t)used))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->pay.p, d_out, (size_t)used, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; i++)
+        if (st[i] == 0 && len[i] && off[i] + len[i] <= used) memcpy(out_base + off[i], c->pay.p + off[i], len[i]);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lz4flex_packed_work_size(uint32_t n) { return packed_work_bytes(n); }
+
+uint64_t lz4flex_compress_packed_scratch_bound(uint64_t total_in_bytes, uint32_t n, int prepend_size) {
+    // sum of floor(len_i * 110 / 100) <= floor(total * 110 / 100)
+    return total_in_bytes / 100u * 110u + (total_in_bytes % 100u) * 110u / 100u + (uint64_t)n * (20u + (prepend_size ? 4u : 0u));
+}
+
+int lz4flex_decompress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                    int size_mode, const uint32_t* sizes, void* out_base, uint64_t total_cap, uint32_t align,
+                                    uint64_t* out_off, uint32_t* out_cap, uint32_t* out_len, int32_t* status, uint64_t* detail, void* work,
+                                    int mem_kind, void* hip_stream) {
+    if (size_mode != LZ4FLEX_SIZES_PREPENDED && size_mode != LZ4FLEX_SIZES_GIVEN && size_mode != LZ4FLEX_SIZES_SCAN) return -LZ4FLEX_E_INVALID_ARG;
+    if (!packed_align_ok(align)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!in_off || !in_len || !out_off || !out_cap || !out_len || !status) return -LZ4FLEX_E_INVALID_ARG;
+    if (size_mode == LZ4FLEX_SIZES_GIVEN && !sizes) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && !work) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = begin_batch(&ctx))) return rc;
+    PackedDecode d{(const uint8_t*)in_base, in_off, in_len, n, size_mode, sizes, (uint8_t*)out_base, total_cap, align, out_off, out_cap,
+                   out_len, status, detail, work, k.big, (hipStream_t)hip_stream};
+    if (k.where == Mem::Device) return (rc = packed_decode_layout(ctx, d)) ? rc : packed_decode_run(ctx, d);
+
+    // MEM_HOST: [input span | descriptors up, results down | work] in the arena; the output buffer is sized once the layout is known
+    lz4flex_ctx* c = ctx;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    const Span sp = span_of(in_off, in_len, n);
+    const size_t in_bytes = sp.bytes();
+    const bool given = size_mode == LZ4FLEX_SIZES_GIVEN;
+    Layout l{16};
+    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n), at_sizes = l.take(given ? 4ull * n : 0);
+    const size_t up_bytes = l.end;
+    const size_t at_out_off = l.take(8ull * n + 8), at_out_cap = l.take(4ull * n), at_out_len = l.take(4ull * n), at_status = l.take(4ull * n),
+                 at_detail = l.take(16ull * n);
+    const size_t desc_bytes = l.end;
+    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
+    const size_t a_desc = align_up(in_bytes + 64, 256), a_work = a_desc + align_up(desc_bytes, 256);
+    if ((rc = ensure_buf(c->arena, a_work + packed_work_bytes(n) + 256))) return rc;
+    uint8_t* hp = c->pin.p;
+    for (uint32_t i = 0; i < n; i++) {
+        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
+        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
+        if (given) ((uint32_t*)(hp + at_sizes))[i] = sizes[i];
+    }
+    uint8_t* dv = c->arena.p;
+    uint8_t* dd = dv + a_desc;
+    hipStream_t s = c->stream;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(dv, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
+    d.in_base = dv; d.in_off = (const uint64_t*)(dd + at_in_off); d.in_len = (const uint32_t*)(dd + at_in_len);
+    d.sizes = given ? (const uint32_t*)(dd + at_sizes) : nullptr;
+    d.out_off = (uint64_t*)(dd + at_out_off); d.out_cap = (uint32_t*)(dd + at_out_cap); d.out_len = (uint32_t*)(dd + at_out_len);
+    d.status = (int32_t*)(dd + at_status); d.detail = (uint64_t*)(dd + at_detail); d.work = dv + a_work; d.stream = s;
+    d.big = k.big || [&] { bool big = false; for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 131072u; return big; }();
+    if ((rc = packed_decode_layout(c, d))) return rc;
+    uint64_t need = 0;
+    HIP_TRY(hipMemcpyAsync(&need, d.out_off + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t used = std::min<uint64_t>(need, total_cap);
+    void* d_out = nullptr;
+    if ((rc = ctx_scratch(c, 0, (size_t)used + 256, &d_out))) return rc;
+    d.out_base = (uint8_t*)d_out;
+    if ((rc = packed_decode_run(c, d))) return rc;
+    HIP_TRY(hipMemcpyAsync(hp + at_out_off, dd + at_out_off, desc_bytes - at_out_off, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out_off, hp + at_out_off, 8ull * n + 8);
+    memcpy(out_cap, hp + at_out_cap, 4ull * n);
+    memcpy(out_len, hp + at_out_len, 4ull * n);
+    memcpy(status, hp + at_status, 4ull * n);
+    if (detail) memcpy(detail, hp + at_detail, 16ull * n);
+    return packed_scatter_to_host(c, (const uint8_t*)d_out, used, (uint8_t*)out_base, out_off, out_len, status, n);
+}
+
+int lz4flex_compress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                  int prepend_size, void* scratch, uint64_t scratch_cap, void* out_base, uint64_t total_cap, uint32_t align,
+                                  uint64_t* out_off, uint32_t* out_len, int32_t* status, void* work, int mem_kind, void* hip_stream) {
+    if (!packed_align_ok(align)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!in_off || !in_len || !out_off || !out_len || !status) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && (!work || !scratch)) return -LZ4FLEX_E_INVALID_ARG;
+    const uint32_t prefix = prepend_size ? 4u : 0u;
+    uint64_t slots = 0, packed_bound = 0;
+    bool big = k.big;
+    if (k.where == Mem::Host) {                       // the lengths are visible: the scratch a DEVICE call of this batch would need
+        for (uint32_t i = 0; i < n; i++) {
+            const uint64_t slot = lz4flex_get_maximum_output_size(in_len[i]) + prefix;
+            slots += slot;
+            packed_bound += (slot + align - 1u) & ~(uint64_t)(align - 1u);
+            big |= in_len[i] > 65536u;
+        }
+        if (scratch_cap < slots) return -LZ4FLEX_E_INVALID_ARG;
+    }
+    int rc;
+    if ((rc = begin_batch(&ctx))) return rc;
+    PackedCompress d{(const uint8_t*)in_base, in_off, in_len, n, prefix, (uint8_t*)scratch, scratch_cap, (uint8_t*)out_base, total_cap, align,
+                     out_off, out_len, status, work, big, (hipStream_t)hip_stream};
+    if (k.where == Mem::Device) return packed_compress_run(ctx, d);
+
+    // MEM_HOST: [input span | descriptors up, results down | work] in the arena, the scratch slots and the packed stream in the context's scratch
+    lz4flex_ctx* c = ctx;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    const Span sp = span_of(in_off, in_len, n);
+    const size_t in_bytes = sp.bytes();
+    Layout l{16};
+    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n);
+    const size_t up_bytes = l.end;
+    const size_t at_out_off = l.take(8ull * n + 8), at_out_len = l.take(4ull * n), at_status = l.take(4ull * n);
+    const size_t desc_bytes = l.end;
+    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
+    const size_t a_desc = align_up(in_bytes + 64, 256), a_work = a_desc + align_up(desc_bytes, 256);
+    if ((rc = ensure_buf(c->arena, a_work + packed_work_bytes(n) + 256))) return rc;
+    const uint64_t out_bytes = std::min<uint64_t>(packed_bound, total_cap);
+    void *d_scratch = nullptr, *d_out = nullptr;
+    if ((rc = ctx_scratch(c, 0, (size_t)slots + 256, &d_scratch))) return rc;
+    if ((rc = ctx_scratch(c, 1, (size_t)out_bytes + 256, &d_out))) return rc;
+    uint8_t* hp = c->pin.p;
+    for (uint32_t i = 0; i < n; i++) {
+        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
+        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
+    }
+    uint8_t* dv = c->arena.p;
+    uint8_t* dd = dv + a_desc;
+    hipStream_t s = c->stream;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(dv, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
+    d.in_base = dv; d.in_off = (const uint64_t*)(dd + at_in_off); d.in_len = (const uint32_t*)(dd + at_in_len);
+    d.scratch = (uint8_t*)d_scratch; d.scratch_cap = slots; d.out_base = (uint8_t*)d_out;
+    d.out_off = (uint64_t*)(dd + at_out_off); d.out_len = (uint32_t*)(dd + at_out_len); d.status = (int32_t*)(dd + at_status);
+    d.work = dv + a_work; d.stream = s;
+    if ((rc = packed_compress_run(c, d))) return rc;
+    HIP_TRY(hipMemcpyAsync(hp + at_out_off, dd + at_out_off, desc_bytes - at_out_off, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(out_off, hp + at_out_off, 8ull * n + 8);
+    memcpy(out_len, hp + at_out_len, 4ull * n);
+    memcpy(status, hp + at_status, 4ull * n);
+    return packed_scatter_to_host(c, (const uint8_t*)d_out, std::min<uint64_t>(out_off[n], out_bytes), (uint8_t*)out_base, out_off, out_len, status, n);
 }
 
 // ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------

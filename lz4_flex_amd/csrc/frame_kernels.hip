@@ -13,11 +13,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lz4_copy_range.h"
 #include "lz4_device.h"
 
 namespace lz4flex_dev {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // one workgroup of 1024 threads: per[i] = 4 + min(comp_len, in_len stored raw) (+ 4), seg_off = exclusive sum, seg_off[n] = total
 __global__ void __launch_bounds__(1024) frame_sizes_scan_kernel(const uint32_t* __restrict__ in_len, const uint32_t* __restrict__ comp_len,
@@ -46,33 +45,6 @@ __global__ void __launch_bounds__(1024) frame_sizes_scan_kernel(const uint32_t* 
         o += 4ull + (c >= u ? u : c) + tail;
     }
     if (t == 1023u) seg_off[n] = part[1023];
-}
-
-__device__ __forceinline__ void copy_range(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t n, uint32_t t, uint32_t nt) {
-    if ((((uintptr_t)dst | (uintptr_t)src) & 15u) == 0u) {
-        const uint64_t nv = n / 16u;
-        for (uint64_t i = t; i < nv; i += nt) reinterpret_cast<u32x4*>(dst)[i] = reinterpret_cast<const u32x4*>(src)[i];
-        for (uint64_t i = nv * 16u + t; i < n; i += nt) dst[i] = src[i];
-    } else if (((uintptr_t)dst & 15u) == ((uintptr_t)src & 15u)) {
-        const uint64_t head = (16u - ((uintptr_t)dst & 15u)) & 15u;
-        const uint64_t h = head < n ? head : n;
-        for (uint64_t i = t; i < h; i += nt) dst[i] = src[i];
-        const uint64_t nv = (n - h) / 16u;
-        for (uint64_t i = t; i < nv; i += nt) reinterpret_cast<u32x4*>(dst + h)[i] = reinterpret_cast<const u32x4*>(src + h)[i];
-        for (uint64_t i = h + nv * 16u + t; i < n; i += nt) dst[i] = src[i];
-    } else {
-        // different phase: aligned 16-byte stores, unaligned loads (global memory takes any alignment)
-        const uint64_t head = (16u - ((uintptr_t)dst & 15u)) & 15u;
-        const uint64_t h = head < n ? head : n;
-        for (uint64_t i = t; i < h; i += nt) dst[i] = src[i];
-        const uint64_t nv = (n - h) / 16u;
-        for (uint64_t i = t; i < nv; i += nt) {
-            u32x4 v;
-            __builtin_memcpy(&v, src + h + 16u * i, 16);
-            reinterpret_cast<u32x4*>(dst + h)[i] = v;
-        }
-        for (uint64_t i = h + nv * 16u + t; i < n; i += nt) dst[i] = src[i];
-    }
 }
 
 // block b: [u32 header][payload]; the checksum slot behind it is filled by frame_checksum_kernel

@@ -9,6 +9,7 @@
 #define LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE 3
 #define LZ4FLEX_DEV_E_OFFSET_ZERO 4
 #define LZ4FLEX_DEV_E_OFFSET_OUT_OF_BOUNDS 5
+#define LZ4FLEX_DEV_E_UNSUPPORTED 68        // lz4_packed.hip: a raw block that decompresses to more than the decoders' u32 out_cap holds
 #define LZ4FLEX_DEV_E_INVALID_ARG 64        // a sink position behind the sink's end (out_pos > out_cap): the reference panics there
 
 namespace lz4flex_dev {
@@ -197,6 +198,43 @@ hipError_t launch_copy_batch(const uint8_t* src_base, const uint64_t* src_off, c
 constexpr int32_t SIZE_SCAN_REDO = 0x7F000003;
 hipError_t launch_size_scan(const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* history, uint32_t n,
                             uint64_t* out_size, int32_t* status, int serial_only, hipStream_t s);
+// lz4_packed.hip (lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed): the output layout of a batch, computed on the device.
+constexpr uint32_t PACKED_SCAN_TILE = 1024u;         // the sizes one workgroup scans ("packed_scan_tile")
+enum : int {
+    PACKED_SIZES_PREPENDED = 0,   // the LE u32 in front of every block; sh_off / sh_len receive the block behind it (in_len < 4: EXPECTED_ANOTHER_BYTE)
+    PACKED_SIZES_GIVEN = 1,       // given[i]
+    PACKED_SIZES_SCAN = 2,        // size / pre hold launch_size_scan's out_size / status (in place: failed blocks 0, more than 4 GiB - 1: UNSUPPORTED)
+    PACKED_SIZES_SLOTS = 3,       // compress, scratch slots: get_maximum_output_size(in_len[i]) + extra
+    PACKED_SIZES_PRODUCED = 4,    // compress, packed stream: given[i] (the encoder's out_len) + extra where given_st[i] == 0, else 0; pre is not written
+};
+// the arrays a packed call keeps in the caller's `work` (packed_work_bytes(n) bytes, any 8-byte aligned address)
+struct PackedWork {
+    uint64_t* size;       // n: slot sizes
+    uint64_t* place;      // n: where the codec writes block i (0 for a block without room)
+    uint64_t* aux_off;    // n + 1: PREPENDED: the blocks behind their prefixes; compress: the scratch slots' offsets
+    uint64_t* tiles;      // the scan's tile sums
+    uint32_t* aux_len;    // n: PREPENDED: the lengths behind the prefixes; compress: the scratch slots' capacities
+    int32_t* pre;         // n: 0, or the status a block has before / instead of the codec's
+};
+size_t packed_work_bytes(uint32_t n);
+PackedWork packed_work(void* work, uint32_t n);
+hipError_t launch_packed_sizes(int mode, const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* given,
+                               const int32_t* given_st, uint32_t n, uint32_t extra, uint64_t* size, uint64_t* sh_off, uint32_t* sh_len,
+                               int32_t* pre, hipStream_t s);
+// off[0 .. n] = exclusive sums of the sizes, each rounded up to align (a power of two), off[n] the total.  Fit rule: block i fits iff
+// off[i] + size[i] <= total_cap.  Nullable: place[i] = off[i] + shift (0 without room), cap[i] = size[i] - shift (0 without room),
+// pre[i] = OUTPUT_TOO_SMALL without room (untouched otherwise).  tiles: n / PACKED_SCAN_TILE + 2 words of scratch
+hipError_t launch_packed_scan(const uint64_t* size, uint32_t n, uint32_t align, uint64_t total_cap, uint32_t shift, uint64_t* tiles,
+                              uint64_t* off, uint64_t* place, uint32_t* cap, int32_t* pre, hipStream_t s);
+// decode: blocks with pre[i] != 0 get that status, out_len 0 and detail {off[i] + size[i], total_cap} (no room) or {0, 0}; the
+// other blocks keep the decoder's detail if their status is OUTPUT_TOO_SMALL and get {0, 0} otherwise
+hipError_t launch_packed_finish(const int32_t* pre, const uint64_t* size, const uint64_t* off, uint32_t n, uint64_t total_cap,
+                                uint32_t* out_len, int32_t* status, uint64_t* detail, hipStream_t s);
+// compress: block i with status 0 and room: [LE u32 in_len[i] (prefix = 4)] scratch[src_off[i] .. + size[i] - prefix) -> out + off[i],
+// out_len[i] = size[i]; without room: status OUTPUT_TOO_SMALL; every block that is not copied: out_len 0
+hipError_t launch_packed_gather(const uint8_t* scratch, const uint64_t* src_off, const uint64_t* size, const uint64_t* off,
+                                const uint32_t* in_len, uint32_t n, uint32_t prefix, uint64_t total_cap, uint8_t* out, uint32_t* out_len,
+                                int32_t* status, hipStream_t s);
 // DECODE_REDO: the status a first-pass decoder (sequence, workgroup, plan, fused) leaves on a block it does not decode: the host then runs a reference-order
 // kernel with only_status = DECODE_REDO over the batch (capi.cpp launch_redo)
 constexpr int32_t DECODE_REDO = 0x7F000001;
