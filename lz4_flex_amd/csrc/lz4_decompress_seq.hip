@@ -8,14 +8,10 @@
 // Round 6.  Every other batch decoder in this tree walks a block's token chain with ONE lane and copies its pieces with one
 // group of four lanes: the kernel's time is one block's chain (3 380 sequences x ~630 dependent wave-instructions).
 // Here nothing is done a sequence at a time:
-//   * WALK (the reference's `ip` chain, decompress.rs:244-332, positions only).  The compressed stream is consumed in tiles of
-//     3 840 bytes staged in LDS; a tile is cut into 64 parts of 60 bytes (15 dwords: lane k reading part k hits its own bank) and
-//     lane k walks part k's chain from an ASSUMED entry, two LDS round trips per hop at most (token + first length byte; the match
-//     length byte of a 15-nibble), marking token positions in a 64-bit register mask.  A chain started at a wrong byte falls into
-//     step with the true chain after a few sequences; the exits are followed from the tile's true entry (every part leaving into
-//     the next one: a DPP move; else pointer jumping with ds_bpermute), parts whose entry was wrong walk again until they meet
-//     their first walk's marks (the parallel-chain parse of lz4_decompress_pcd.hip / lz4_decompress_plan.hip, masks only).
-//     The set bits of the live parts, compacted into a u16 list in LDS, are the tile's sequences in order.
+//   * WALK (lz4_seq_walk.h, shared with the size scan lz4_size_scan.hip): the compressed stream is consumed in tiles of 3 840 bytes
+//     staged in LDS, 64 lanes walk the 64 parts of a tile from assumed entries, the true chain is settled from the tile's entry, and
+//     the set bits of the live parts, compacted into a u16 list in LDS, are the tile's sequences in order.  The tile loop below calls
+//     its stages (stage_tile, first_walks, settle_chain, write_token_list); setup_chunk reads a sequence with decode_token.
 //   * CHUNKS of 64 consecutive sequences, lane = sequence: token, lengths and offset from two aligned dword-pair reads of the
 //     tile (decompress.rs:249-258, 284, 373-391), a DPP prefix sum of literal + match lengths places all 64 in the output at
 //     once, every reference check that needs the position (offset <= position :286-289 / :398-402, capacity :346-356) is one
@@ -34,46 +30,25 @@
 #include <stdint.h>
 
 #include "lz4_device.h"
-#include "lz4_pcd_common.h"
+#include "lz4_seq_walk.h"
 
 namespace lz4flex_dev {
 namespace sq {
 
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace sw;      // the walk, its geometry and the lane / LDS helpers
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-using pcd::X_END;
-using pcd::X_ERR;
 
-#ifndef LZ4S_PB
-#define LZ4S_PB 60
-#endif
 #ifndef LZ4S_R
 #define LZ4S_R 3584
 #endif
 #ifndef LZ4S_KEEP
 #define LZ4S_KEEP 1280
 #endif
-constexpr uint32_t PB = LZ4S_PB;             // bytes per part (an odd number of dwords: lane k reading part k hits its own bank)
-constexpr uint32_t NPART = 64u;              // parts per tile = lanes
-constexpr uint32_t PT = PB * NPART;          // 3 840 compressed bytes per tile
-constexpr uint32_t TPAD = 16u;               // bytes in front of the tile (a lane reads the 16 bytes that END with its literals)
-constexpr uint32_t TMARGIN = 224u;           // bytes behind the tile staged with it
-constexpr uint32_t TILE_LDS = TPAD + PT + TMARGIN;
-constexpr uint32_t POSCAP = PT / 3u;         // sequences per tile: a sequence with a match is at least 3 bytes
-constexpr uint32_t POS_LDS = (2u * POSCAP + 15u) & ~15u;
 constexpr uint32_t LITMAX = 64u;             // literal run a lane copies itself
 constexpr uint32_t FARMAX = 64u;             // match from the written-back output a lane copies itself
-constexpr uint32_t POS_LIMIT = 0xFFFF0000u;   // positions in either stream stay below this: `pos + a KiB` never wraps (a block beyond it is the reference-order kernel's)
 constexpr uint32_t BIGRUN = 1024u;           // literal runs / matches from here on go memory to memory (exact_seq)
-constexpr uint32_t WALK_LITMAX = 200u;       // literal run a hop steps over without the generic walker (its end stays inside the staged bytes)
-// LDS: [token list | tile | window | scratch 16]  (the tile is not first: a lane may read up to 16 bytes in front of it)
-constexpr uint32_t LDS_POS = 0u, LDS_TILE = LDS_POS + POS_LDS, LDS_WIN = LDS_TILE + TILE_LDS;
-static_assert(TILE_LDS % 16u == 0u && PT % 16u == 0u && POS_LDS % 16u == 0u && PB % 4u == 0u && (PB / 4u) % 2u == 1u && PB <= 64u, "geometry");
-static_assert(PT - 1u + 4u + 15u + WALK_LITMAX + 4u < PT + TMARGIN, "a hop's length byte lies inside the staged bytes");
+// LDS: [token list | tile | window | scratch 16]
+constexpr uint32_t LDS_WIN = LDS_TILE + TILE_LDS;
 static_assert(PT + 1u + LITMAX + 16u <= PT + TMARGIN && PT + 1u + LITMAX + 8u <= PT + TMARGIN, "a lane's literals and offset lie inside the staged bytes");
 
 template <uint32_t R_, uint32_t KEEP_>
@@ -100,43 +75,9 @@ struct Prof { uint64_t c[32]; uint64_t t; };
 #define SQ_COUNT(i, n)
 #endif
 
-// Behind a region only some lanes execute: an (empty) instruction of its own.  Without it the compiler lets the region end in the
-// block where uniform paths (an early return, a loop's exit) meet as well, and then takes every value merged there -- the
-// function's result, the loop's state -- for divergent: masks and counters move to vector registers, uniform branches become
-// exec-mask loops (the first build of this file ran its whole main loop that way).
-#define SQ_JOIN() asm volatile("; join")
-#define LZ4S_DPP(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rmask), 0xf, false))
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    v += LZ4S_DPP(v, 0x111, 0xf);     // row_shr:1
-    v += LZ4S_DPP(v, 0x112, 0xf);     // row_shr:2
-    v += LZ4S_DPP(v, 0x114, 0xf);     // row_shr:4
-    v += LZ4S_DPP(v, 0x118, 0xf);     // row_shr:8
-    v += LZ4S_DPP(v, 0x142, 0xa);     // row_bcast:15 -> rows 1, 3
-    v += LZ4S_DPP(v, 0x143, 0xc);     // row_bcast:31 -> rows 2, 3
-    return v;
-}
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
-__device__ __forceinline__ bool lanes(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }      // this lane's bit of a wave-uniform mask
-__device__ __forceinline__ uint32_t ctz64(uint64_t x) { return (uint32_t)__builtin_ctzll(x); }
-__device__ __forceinline__ uint64_t low_mask(uint32_t n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }
-__device__ __forceinline__ uint32_t bperm(uint32_t lane_src, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(lane_src * 4u), (int)v); }
-
-// LDS by byte address (the dynamic segment starts at 0)
-__device__ __forceinline__ lds_u8* L8(uint32_t a) { return (lds_u8*)(uintptr_t)a; }
 __device__ __forceinline__ u32x4 lds_rd16(uint32_t a) { u32x4 v; __builtin_memcpy(&v, (const void*)L8(a), 16); return v; }
-__device__ __forceinline__ void lds_wr16(uint32_t a, const u32x4& v) { __builtin_memcpy((void*)L8(a), &v, 16); }
 __device__ __forceinline__ void lds_wr8(uint32_t a, uint32_t lo, uint32_t hi) { const u32x2 v = {lo, hi}; __builtin_memcpy((void*)L8(a), &v, 8); }
-__device__ __forceinline__ void lds_wr4(uint32_t a, uint32_t v) { __builtin_memcpy((void*)L8(a), &v, 4); }
-__device__ __forceinline__ void lds_wr2(uint32_t a, uint32_t v) { const uint16_t t = (uint16_t)v; __builtin_memcpy((void*)L8(a), &t, 2); }
 __device__ __forceinline__ void lds_wr1(uint32_t a, uint32_t v) { *L8(a) = (uint8_t)v; }
-// the four bytes at LDS address a (any alignment) out of two aligned dwords
-__device__ __forceinline__ uint32_t lds_rd4u(uint32_t a) {
-    const lds_u32* q = (const lds_u32*)(uintptr_t)(a & ~3u);
-    const uint32_t d0 = q[0], d1 = q[1];
-    return __builtin_amdgcn_alignbyte(d1, d0, a & 3u);
-}
 
 // n (1..16) bytes of v to LDS, exactly (the write_exact16 of the wave decoder this kernel replaced)
 __device__ __forceinline__ void write_exact16(uint32_t dst, const u32x4& v, uint32_t n) {
@@ -148,73 +89,6 @@ __device__ __forceinline__ void write_exact16(uint32_t dst, const u32x4& v, uint
     if (n4) lds_wr4(dst + (n & 8u), w4);
     if (n2) lds_wr2(dst + (n & 12u), wq);
     if (n & 1u) lds_wr1(dst + (n & 14u), wq >> (n2 ? 16 : 0));
-}
-
-// the compressed bytes for the generic sequence walker (lz4_pcd_common.h parse_seq): the staged tile from LDS, else memory
-struct Reader {
-    const g_u8* g;
-    uint32_t t0;
-    __device__ __forceinline__ uint32_t operator()(uint32_t pos) const {
-        const uint32_t r = pos - t0;
-        return r < PT + TMARGIN ? (uint32_t)*L8(LDS_TILE + TPAD + r) : (uint32_t)g[pos];
-    }
-    __device__ __forceinline__ uint32_t u32(uint32_t pos) const { return (*this)(pos) | ((*this)(pos + 1u) << 8) | ((*this)(pos + 2u) << 16) | ((*this)(pos + 3u) << 24); }
-};
-// where the sequence at position p ends (the next token; ilen: the block ends there), exactly, byte by byte -- the walk's rare path, kept
-// out of its loop.  X_ERR: this chain cannot be a real one.
-__device__ __noinline__ uint32_t slow_next(const g_u8* g, uint32_t t0, uint32_t ilen, uint32_t p) {
-    Reader rd;
-    rd.g = g; rd.t0 = t0;
-    pcd::Seq q;
-    const uint32_t nx = pcd::parse_seq<Reader, false>(rd, ilen, p, q);
-    return nx == X_END ? ilen : nx;
-}
-
-struct Part {           // positions relative to the tile's first byte t0
-    uint64_t marks;      // token positions of the standing walk, relative to the part's first byte
-    uint32_t from;       // where the standing walk began (X_ERR: none)
-    uint32_t exit;       // where its chain leaves the part: a position >= the part's end (>= ilen - t0: the block ends or fails there), or X_ERR
-};
-
-// One walk of a part from r (decompress.rs:244-258, 366-391: positions only).  FIRST: every position is marked.  Else: until the walk
-// lands on a position the standing walk marked (its marks stand from there, and its exit) or leaves the part.  A hop is two LDS
-// round trips at most: token + first length byte, and the match length byte of a 15-nibble.
-template <bool FIRST>
-__device__ __forceinline__ void walk_part(const g_u8* g, uint32_t t0, uint32_t ilen, uint32_t r, uint32_t p0, uint32_t pend, Part& s) {
-    const uint32_t entry = r;
-    const uint32_t tb = LDS_TILE + TPAD;
-    uint64_t m2 = 0ull;
-    uint32_t exit_ = X_ERR;
-    bool merged = false;
-    for (;;) {
-        bool slow = false;
-        uint64_t bit = 0ull;
-        for (;;) {
-            if (r >= pend) { exit_ = r; break; }
-            bit = 1ull << (r - p0);
-            if (!FIRST && (s.marks & bit) != 0ull) { merged = true; break; }
-            const uint32_t w = lds_rd4u(tb + r);
-            const uint32_t L = (w >> 4) & 15u, M = w & 15u, e1 = (w >> 8) & 0xFFu;
-            const bool l15 = L == 15u;
-            uint32_t nx = r + (l15 ? 15u + e1 + 4u : L + 3u);
-            slow = l15 && e1 > WALK_LITMAX - 15u;
-            if (M == 15u && !slow) {
-                const uint32_t e2 = *L8(tb + nx);
-                nx += 1u;
-                slow = e2 == 255u;
-            }
-            if (slow) break;
-            m2 |= bit;
-            r = nx;
-        }
-        if (!slow) break;
-        const uint32_t nx = slow_next(g, t0, ilen, t0 + r);     // (r < pend: a position of the block)
-        if (nx == X_ERR) break;
-        m2 |= bit;
-        r = nx - t0;
-    }
-    if (merged) { s.marks = m2 | (s.marks & ~((1ull << (r - p0)) - 1ull)); s.from = entry; }
-    else { s.marks = m2; s.from = entry; s.exit = exit_; }
 }
 
 // DICT (lz4flex_decompress_batch_shared_dict): ONE external dictionary for every block of the batch, decoded as prefix mode decodes a
@@ -260,7 +134,7 @@ struct Dec {
                 const u32x4 v = lds_rd16(LDS_WIN + (q - W0));
                 __builtin_memcpy((void*)(out + q), &v, 16);
             }
-            SQ_JOIN();
+            SW_JOIN();
         }
         F = lim;
     }
@@ -276,23 +150,21 @@ struct Dec {
                 const u32x4 v = lds_rd16(LDS_WIN + S + i);
                 lds_wr16(LDS_WIN + i, v);
             }
-            SQ_JOIN();
+            SW_JOIN();
         }
         W0 = nw;
     }
-    __device__ __forceinline__ void finish() {
-        write_back(OP);
-        if (F + lane < OP) out[F + lane] = *L8(LDS_WIN + F + lane - W0);
-        SQ_JOIN();
-        F = OP;
-    }
-    // ---- runs of BIGRUN bytes or more go memory to memory, 16 bytes per lane, and the window is read back behind them ----------------
     // everything produced so far, the last odd bytes too
     __device__ __forceinline__ void flush_all() {
         write_back(OP);
         if (F + lane < OP) out[F + lane] = *L8(LDS_WIN + F + lane - W0);
-        SQ_JOIN();
+        SW_JOIN();
     }
+    __device__ __forceinline__ void finish() {
+        flush_all();
+        F = OP;
+    }
+    // ---- runs of BIGRUN bytes or more go memory to memory, 16 bytes per lane, and the window is read back behind them ----------------
     // the window = the last KEEP bytes of the output, from memory (this wavefront's own stores: one CU, one L1 -- coherent in program order)
     __device__ __forceinline__ void reload_window() {
         W0 = OP > G::KEEP ? (OP - G::KEEP) & ~15u : 0u;
@@ -310,7 +182,7 @@ struct Dec {
                 }
                 lds_wr16(LDS_WIN + i, v);
             }
-            SQ_JOIN();
+            SW_JOIN();
         }
         F = OP & ~15u;
     }
@@ -325,7 +197,7 @@ struct Dec {
             } else if (i < n) {
                 for (uint32_t k = i; k < n; ++k) out[OP + k] = from[k];
             }
-            SQ_JOIN();
+            SW_JOIN();
         }
     }
     // DICT: the same from position sp (a match's source: in the dictionary, in the output, or across both)
@@ -338,7 +210,7 @@ struct Dec {
             } else if (i < n) {
                 for (uint32_t k = i; k < n; ++k) out[OP + k] = (uint8_t)vbyte(sp + k);
             }
-            SQ_JOIN();
+            SW_JOIN();
         }
     }
     __device__ __forceinline__ uint32_t mod_small(uint32_t i, uint32_t m, float rcp) {      // i mod m, i < 2^22, rcp = 1 / m
@@ -368,7 +240,7 @@ struct Dec {
                 const uint32_t k = k0 + lane;
                 if constexpr (DICT) { if (k < el) *L8(LDS_WIN + k) = (uint8_t)vbyte(OP - offset + mod_small(k, offset, rcp)); }
                 else if (k < el) *L8(LDS_WIN + k) = out[OP - offset + mod_small(k, offset, rcp)];
-                SQ_JOIN();
+                SW_JOIN();
             }
             uint32_t ph = 0u;                                      // i0 mod offset
             const uint32_t adv = mod_small(1024u, offset, rcp);
@@ -382,7 +254,7 @@ struct Dec {
                         for (uint32_t k = 0u; i + k < n; ++k) out[OP + i + k] = (uint8_t)(wv[k >> 2] >> (8u * (k & 3u)));
                     }
                 }
-                SQ_JOIN();
+                SW_JOIN();
                 ph += adv;
                 ph = ph >= offset ? ph - offset : ph;
             }
@@ -399,7 +271,7 @@ struct Dec {
             for (uint32_t i0 = 0u; i0 < m; i0 += 64u) {
                 const uint32_t i = i0 + lane;
                 if (i < m) *L8(LDS_WIN + OP - W0 + i) = in[src + c + i];
-                SQ_JOIN();
+                SW_JOIN();
             }
             OP += m;
         }
@@ -429,7 +301,7 @@ struct Dec {
                     const uint8_t byte = ps >= W0 ? *L8(LDS_WIN + ps - W0) : (DICT ? *vp(ps) : out[ps]);
                     *L8(LDS_WIN + d - W0 + i) = byte;
                 }
-                SQ_JOIN();
+                SW_JOIN();
             }
             OP += m;
         }
@@ -491,24 +363,12 @@ template <class G, bool DICT>
 __device__ __forceinline__ bool setup_chunk(Dec<G, DICT>& D, uint32_t t0, uint32_t n_tile, uint32_t sidx, uint32_t op, uint32_t pending, Chunk& C) {
     const uint32_t lane = D.lane;
     const uint32_t ilr = D.ilen - t0;                          // the block's end, relative to t0
-    const uint32_t tb = LDS_TILE + TPAD;
     const uint32_t nrem = n_tile - sidx;
-    const uint32_t idx = sidx + (lane < nrem ? lane : nrem - 1u);
-    const uint32_t tpr = (uint32_t)*(const lds_u16*)(uintptr_t)(LDS_POS + 2u * idx);
-    // ---- token, lengths, offset (decompress.rs:249-258, 284, 373-391) ----------------------------------------------------
-    const uint32_t w = lds_rd4u(tb + tpr);
-    const uint32_t L = (w >> 4) & 15u, M = w & 15u, e1 = (w >> 8) & 0xFFu;
-    const bool l15 = L == 15u;
-    const uint32_t lit = l15 ? 15u + e1 : L;
-    const uint32_t lsr = tpr + (l15 ? 2u : 1u);
-    const uint64_t biglit = ballot(lit > LITMAX);              // (covers a length byte of 255) not a lane's work: exact_seq
-    const uint32_t lend = lit > LITMAX ? 0u : lsr + lit;
-    const uint32_t w1 = lds_rd4u(tb + lend);
-    const uint32_t off = w1 & 0xFFFFu, e2 = (w1 >> 16) & 0xFFu;
-    const bool m15 = M == 15u;
-    const uint32_t mlx = 4u + M + (m15 ? e2 : 0u);
-    const uint32_t nxt = lend + (m15 ? 3u : 2u);               // the next token
-    const uint64_t lastm = ballot(lend >= ilr);                // the block's last sequence: literals only (:366-368) -- or an error
+    // ---- token, lengths, offset; a literal run of more than LITMAX bytes is not a lane's work: exact_seq --------------------------
+    const Token t = decode_token<LITMAX>(sidx + (lane < nrem ? lane : nrem - 1u), ilr);
+    const uint32_t tpr = t.tpr, lit = t.lit, lsr = t.lsr, lend = t.lend, off = t.off, e2 = t.e2, mlx = t.mlx, nxt = t.nxt;
+    const bool m15 = t.m15;
+    const uint64_t biglit = t.biglit, lastm = t.lastm;
     const uint64_t errm = ballot(lend > ilr) |                                                           // :346-348
                           (~lastm & (ballot(lend + 2u > ilr) | ballot(nxt >= ilr) | ballot(off == 0u))); // :373-375, :439-443, :168-173
     const uint64_t bigm = biglit | (~lastm & (ballot(m15 && e2 == 255u) | ballot(off < mlx)));           // more length bytes; a match that reads its own output
@@ -565,7 +425,7 @@ __device__ __forceinline__ bool setup_chunk(Dec<G, DICT>& D, uint32_t t0, uint32
         if (ml > 32u) __builtin_memcpy(&C.f2, (const void*)(fs + 16u), 16);
         if (ml > 48u) __builtin_memcpy(&C.f3, (const void*)(fs + 32u), 16);
     }
-    SQ_JOIN();
+    SW_JOIN();
     return true;
 }
 
@@ -608,11 +468,11 @@ __device__ __forceinline__ void lane_copy(const CopyPlan& P, uint64_t m) {
         if (lanes(m & P.c2)) { lds_wr2(P.d, r1.x); lds_wr2(P.d2 + 14u, r1.x >> (8u * (P.n - 2u))); }                          // n = 2, 3
         if (lanes(m & P.c1)) lds_wr1(P.d, r1.x);
     }
-    SQ_JOIN();
+    SW_JOIN();
     uint64_t more = m & P.gt32;
     for (uint32_t p = 16u; more != 0ull; p += 16u) {
         if (lanes(more)) { const u32x4 r = lds_rd16(P.s + p); lds_wr16(P.d + p, r); }
-        SQ_JOIN();
+        SW_JOIN();
         more &= ballot(p + 32u < P.n);                        // the next piece, at p + 16, begins in front of the last one's start: p + 16 < n - 16
     }
 }
@@ -636,7 +496,7 @@ __device__ __forceinline__ void exec_chunk(Dec<G, DICT>& D, const Chunk& C SQ_PR
                 lds_wr16(wm + C.ml - 16u, C.f1);
             }
         }
-        SQ_JOIN();
+        SW_JOIN();
     }
     SQ_TICK(7) SQ_COUNT(17, 1) SQ_COUNT(20, C.nact) SQ_COUNT(23, __builtin_popcountll(C.far)) SQ_COUNT(24, __builtin_popcountll(C.near))
     // ---- matches inside the window, in rounds: ready = every sequence that starts before the source's end is done ----------------
@@ -764,105 +624,21 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
         if (uni((ok && !done) ? 1u : 0u) == 0u) break;
         const uint32_t t0 = entry & ~15u;
         SQ_TICK(15)
-        // ---- stage the tile: [t0, t0 + PT + TMARGIN), zeros behind the block --------------------------------------------------------
-        for (uint32_t o0 = 0u; o0 < PT + TMARGIN; o0 += 1024u) {
-            const uint32_t o = o0 + 16u * lane;
-            if (o < PT + TMARGIN) {
-                u32x4 v = {0u, 0u, 0u, 0u};
-                const uint32_t g = t0 + o;
-                if (g + 16u <= ilen) __builtin_memcpy(&v, (const void*)(D.in + g), 16);
-                else if (g < ilen) {
-                    uint32_t wv[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                    for (uint32_t k = 0u; k < 16u; ++k) if (g + k < ilen) wv[k >> 2] |= (uint32_t)D.in[g + k] << (8u * (k & 3u));
-                    v = u32x4{wv[0], wv[1], wv[2], wv[3]};
-                }
-                lds_wr16(LDS_TILE + TPAD + o, v);
-            }
-            SQ_JOIN();
-        }
+        stage_tile(D.in, ilen, t0, lane);
         SQ_TICK(0) SQ_COUNT(16, 1)
-        // ---- 1. first walks: lane 0 from the tile's entry, the others from their part's first byte (positions relative to t0) --------
         const uint32_t ilr = ilen - t0;
-        const uint32_t p0 = PB * lane;
-        const uint32_t pend = p0 + PB < ilr ? p0 + PB : ilr;
         const uint32_t entry_r = entry - t0;
         Part s;
-        s.marks = 0ull; s.from = X_ERR; s.exit = X_ERR;
-        if (p0 < ilr) walk_part<true>(D.in, t0, ilen, lane == 0u ? entry_r : p0, p0, pend, s);
-        SQ_JOIN();
+        first_walks(D.in, ilen, t0, lane, entry_r, s);
         SQ_TICK(1)
-        // ---- 2. / 3. which parts does the true chain visit, and where does it enter them?  (lz4_decompress_plan.hip) ----------------
-        uint32_t my_entry = X_ERR;
-        uint64_t path = 1ull;
-        bool settled = false;
-        const uint32_t nparts = ilr < PT ? (ilr + PB - 1u) / PB : NPART;       // parts that hold bytes of the block
-        for (uint32_t round = 0u; round < NPART + 2u; ++round) {
-            const bool inside = s.exit != X_ERR && s.exit < PT && s.exit < ilr;
-            const uint32_t nxt = inside ? s.exit / PB : 64u;
-            // the usual tile: every part's chain leaves into the NEXT part (no sequence is longer than a part) -- the path is all parts and
-            // a part's entry is its left neighbour's exit, one DPP move; else the general form, pointer jumping over the exits
-            const uint64_t chain_ok = ballot(nxt == lane + 1u || (lane + 1u >= nparts && nxt == 64u)) | ~low_mask(nparts);
-            if (chain_ok == ~0ull) {
-                path = low_mask(nparts);
-                const uint32_t left = (uint32_t)__builtin_amdgcn_update_dpp((int)X_ERR, (int)s.exit, 0x138, 0xf, 0xf, false);   // wave_shr:1
-                my_entry = lane == 0u ? entry_r : (lane < nparts ? left : X_ERR);
-            } else {
-                uint64_t reach = 1ull << lane;
-                uint32_t jump = nxt;
-#pragma unroll
-                for (uint32_t i = 0u; i < 6u; ++i) {
-                    const uint32_t sl = jump < 64u ? jump : lane;
-                    const uint32_t rlo = bperm(sl, (uint32_t)reach), rhi = bperm(sl, (uint32_t)(reach >> 32)), j2 = bperm(sl, jump);
-                    if (jump < 64u) { reach |= ((uint64_t)rhi << 32) | rlo; jump = j2; }
-                }
-                path = ((uint64_t)rdlane((uint32_t)(reach >> 32), 0u) << 32) | rdlane((uint32_t)reach, 0u);
-                const uint64_t before = path & ((1ull << lane) - 1ull);
-                const uint32_t pred = before != 0ull ? 63u - (uint32_t)__builtin_clzll(before) : lane;
-                const uint32_t pulled = bperm(pred, s.exit);
-                my_entry = lane == 0u ? entry_r : (lanes(path) && before != 0ull ? pulled : X_ERR);
-            }
-            SQ_JOIN();
-            path = ((uint64_t)uni((uint32_t)(path >> 32)) << 32) | uni((uint32_t)path);
-            // an entry the standing walk passed through needs no walk: its marks stand from there
-            if (my_entry != X_ERR && s.from != my_entry && my_entry - p0 < 64u && ((s.marks >> (my_entry - p0)) & 1ull) != 0ull) {
-                s.marks &= ~((1ull << (my_entry - p0)) - 1ull);
-                s.from = my_entry;
-            }
-            SQ_JOIN();
-            const uint64_t needm = ballot(my_entry != X_ERR && s.from != my_entry);
-            if (needm == 0ull) { settled = true; break; }
-            if (lanes(needm)) walk_part<false>(D.in, t0, ilen, my_entry, p0, pend, s);
-            SQ_JOIN();
-            SQ_COUNT(21, 1)
-        }
-        // (the compiler folds the loop's uniform exit into the divergent re-walk branch and then takes everything behind it for
-        // divergent: say what is uniform)
-        settled = uni(settled ? 1u : 0u) != 0u;
-        path = ((uint64_t)uni((uint32_t)(path >> 32)) << 32) | uni((uint32_t)path);
-        // the last part on the path says where the chain leaves the tile
-        const uint32_t tile_exit = settled ? rdlane(s.exit, 63u - (uint32_t)__builtin_clzll(path)) : X_ERR;
-        SQ_TICK(2)
+        uint32_t my_entry, rounds;
+        const uint32_t tile_exit = settle_chain(D.in, ilen, t0, lane, entry_r, s, my_entry, rounds);
+        SQ_TICK(2) SQ_COUNT(21, rounds)
         if (tile_exit == X_ERR) { ok = false; break; }
-        // ---- 4. the token list ---------------------------------------------------------------------------------------------------------
-        uint64_t m = my_entry != X_ERR ? s.marks : 0ull;
-        const uint32_t cnt = (uint32_t)__builtin_popcountll(m);
-        const uint32_t cincl = wave_incl_add(cnt);
-        const uint32_t n_tile = rdlane(cincl, 63u);
+        const uint32_t n_tile = write_token_list(lane, my_entry, s);
         if (n_tile > POSCAP || n_tile == 0u) { ok = false; break; }
-        {
-            uint32_t at = LDS_POS + 2u * (cincl - cnt);
-            while (ballot(m != 0ull) != 0ull) {
-                if (m != 0ull) {
-                    lds_wr2(at, p0 + ctz64(m));
-                    at += 2u;
-                    m &= m - 1ull;
-                }
-                SQ_JOIN();
-            }
-        }
         SQ_TICK(3)
-        // ---- 5. the chunks ----------------------------------------------------------------------------------------------------------------
+        // ---- the chunks -------------------------------------------------------------------------------------------------------------------
         bool tdone = false;
 #ifdef LZ4S_EXP_NOCHUNKS       // timing experiments only (no output): the walks and the token list alone
         if (tile_exit >= ilr) { done = true; break; }

@@ -11,6 +11,7 @@ import pytest
 import corpus
 import ext_cases
 import oracle_api as O
+import seq_blocks
 import size_model as S
 
 pytestmark = pytest.mark.gpu
@@ -166,6 +167,26 @@ def test_shapes(lib, ctx):
         for serial in (0, 1):
             size, st = scan(lib, ctx, blocks, mode=mode, serial=serial)
             expect(size, st, [oracle_size(c) for c in blocks])
+
+
+@pytest.fixture(scope="module")
+def walk_blocks():
+    """the sequence decoder's own list: ((block, expected), ...) for every block whole, then for every block cut by 3 bytes"""
+    named = seq_blocks.blocks()
+    whole = [(c, (0, len(p))) for _name, c, p in named]
+    cut = [(c[:-3], S.size(c[:-3])) for _name, c, _p in named]
+    return [name for name, _c, _p in named], whole, cut
+
+
+@pytest.mark.parametrize("serial", [0, 1])
+def test_blocks_on_the_walks_boundaries(lib, ctx, walk_blocks, serial):
+    """the size scan shares the decoder's tile walk (lz4_seq_walk.h): the blocks test_gpu_seq.py writes onto the walk's boundaries -- 6 000
+    three-byte sequences, tile boundaries shifted by 0 .. 63, literal runs that jump over tiles, of 3 839 / 3 840 / 3 841 bytes, literals
+    only -- give status 0 and len(plain); cut by 3 bytes, what size_model says.  One DEVICE batch per pass."""
+    names, whole, cut = walk_blocks
+    assert len(names) >= 150 and "6 000 three-byte sequences" in names and "literals only 0" in names
+    size, st = scan(lib, ctx, [c for c, _w in whole + cut], mode="device", serial=serial)
+    expect(size, st, [w for _c, w in whole + cut])
 
 
 def test_large_blocks(lib, ctx):
