@@ -85,7 +85,8 @@ const char *lz4flex_build_id(void);
  * "compress_shared_dict" came after round 8 (the workspace grew by 41 KiB per context), then lz4flex_decompress_batch_shared_dict and
  * the setting "decompress_shared_dict" (no workspace), then the packed entries lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed
  * with lz4flex_packed_work_size, lz4flex_compress_packed_scratch_bound and the read-only setting "packed_scan_tile" (no workspace in the
- * context: the caller brings it) -- a caller detects them by the symbol. */
+ * context: the caller brings it), then the dictionary sets lz4flex_dict_set_create / _free / _count with lz4flex_compress_batch_dict_set and
+ * lz4flex_decompress_batch_dict_set (no workspace in the context: a set owns its memory) -- a caller detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -417,6 +418,64 @@ int lz4flex_decompress_batch_shared_dict(lz4flex_ctx *ctx, const void *in_base, 
                                          uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                                          uint32_t *out_len, int32_t *status, uint64_t *detail /* nullable */,
                                          const void *dict, uint32_t dict_len, int mem_kind, void *hip_stream);
+
+/* ---- dictionary sets: K prepared dictionaries, one id per block ----------------------------------------------------------------
+ * The *_shared_dict entries prepare their one dictionary again on every call (the digest kernel, one wavefront; a MEM_HOST call
+ * stages the dictionary again), and a batch whose records belong to a handful of dictionaries -- one per table or per column -- has
+ * only the *_ex entries: per-block indexing on the way in, sixteen serial lanes per block on the way back.  A dictionary set is the
+ * prepared-dictionary object for both: K dictionaries copied to the device ONCE and digested ONCE, owned by a handle, addressed per
+ * block by an id.
+ *   lz4flex_dict_set_create: dictionary d is dict_base[dict_off[d] .. + dict_len[d]); mem_kind LZ4FLEX_MEM_HOST or LZ4FLEX_MEM_DEVICE
+ *     says where the bytes AND the two arrays lie.  1 <= k <= 1 024 (this library's cap).  dict_len[d] == 0 is legal: id d means "no
+ *     dictionary".  The set copies each dictionary's last min(len, 65 536) bytes -- an offset is at most 65 535, so no decoder and no
+ *     encoder reads further back -- into device memory it owns, and records the untruncated length (compress_mode exact picks its
+ *     table kind from it, src/block/compress.rs:559).  It builds a digest per dictionary (the one lz4flex_compress_batch_shared_dict
+ *     builds per call; 41 KiB each) in ONE launch, a workgroup per dictionary.  The digests live in the set, not in a context's
+ *     workspace: a shared-dictionary call on the same context does not disturb them.  The call blocks until the set is ready; the
+ *     caller may free or overwrite its buffers afterwards.  The set belongs to the context's DEVICE, not to the context: any context
+ *     of that device may use it, also several at a time (nothing in it is written after create but a test counter).
+ *     -LZ4FLEX_E_INVALID_ARG: out, dict_off or dict_len NULL, k == 0, k > 1 024, a mem_kind other than HOST / DEVICE (checked before a
+ *     context is looked at); dict_base NULL with a non-empty dictionary.  -LZ4FLEX_E_NO_DEVICE without a device.
+ *   lz4flex_dict_set_free: the caller orders it behind the work that uses the set (a MEM_DEVICE call is asynchronous: synchronise its
+ *     stream first).  NULL is harmless.
+ *   dict_id (n ids, in the BATCH's memory kind): block i's dictionary is number dict_id[i] of the set.  0xFFFFFFFF: block i has no
+ *     dictionary.  Any other id >= k: the block gets status LZ4FLEX_E_INVALID_ARG and out_len 0, nothing of it is written, the rest of
+ *     the batch is unaffected.
+ *   The calls: everything not said here is as for the *_shared_dict entries.  The arguments are checked before a context is looked
+ *     at: -LZ4FLEX_E_INVALID_ARG for a missing array (dict_id is one), set == NULL with n != 0, a mem_kind other than HOST / DEVICE
+ *     (| BIG_BLOCKS; LZ4FLEX_MEM_CHAINED is refused); n == 0 returns 0.  A set of another device than the context's: -LZ4FLEX_E_INVALID_ARG.
+ *     MEM_DEVICE calls are asynchronous on hip_stream and allocate nothing; MEM_HOST calls stage the batch and the ids, NOT the
+ *     dictionaries.
+ *   The contract is equality with entries that exist.  Compress: block i gets, byte for byte, what lz4flex_compress_batch_ex gives it
+ *     with dictionary dict_id[i] as its per-block dictionary, in both compress modes and under every "compress_sliding_window"; a
+ *     block without a dictionary gets what lz4flex_compress_batch gives it in a batch of the same size.  Decompress: block i gets what
+ *     lz4flex_decompress_batch_ex gives it with that dictionary and no out_pos -- bytes, out_len, every DecompressError in the
+ *     reference's check order, the OutputTooSmall detail counted from out_off.  Nothing is written behind out_len, in front of
+ *     out_off, or into the set.
+ *   The kernels.  compress_mode fast: a third instance of the throughput encoder's body (lz4_compress_wave.hip, the _set_ kernels)
+ *     reads the item's record through its id; an item with a dictionary takes the path it takes in the _shared_ kernels -- the tail
+ *     staged from that dictionary's digest, the first window's table from it when hs > 0 and block length >= hs + 11 - h -- every
+ *     other item the per-block path; a workgroup keeps the staged tail only from an item to the next of the SAME dictionary.
+ *     "compress_shared_dict" 0: no item starts from a digest.  compress_mode exact: the one-block chains of lz4flex_compress_batch_ex,
+ *     their records filled from the set's table on the device.  Decompress: the sequence decoder's dictionary form with the
+ *     dictionary looked up per block (a block without one decodes in the same launch); the blocks it hands back are decoded in the
+ *     reference's order with their own dictionary; "decompress_shared_dict" 0 / "decompress_variant" 1: that order for every block.
+ *   Not timed yet: tools/dict_set_bench.py times K = 1 against the *_shared_dict entries (large batches; 256 and 1 024 records per call:
+ *     what the prepared digest saves per call), and K = 4 against the *_ex entries with per-block arrays
+ *     (profiles/r12_dict_set.txt holds the register figures and awaits the table). */
+typedef struct lz4flex_dict_set lz4flex_dict_set;
+int lz4flex_dict_set_create(lz4flex_ctx *ctx, const void *dict_base, const uint64_t *dict_off, const uint32_t *dict_len,
+                            uint32_t k, int mem_kind, lz4flex_dict_set **out);
+void lz4flex_dict_set_free(lz4flex_dict_set *s);
+uint32_t lz4flex_dict_set_count(const lz4flex_dict_set *s);
+int lz4flex_compress_batch_dict_set(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                    uint32_t n, const uint32_t *dict_id, void *out_base, const uint64_t *out_off,
+                                    const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
+                                    const lz4flex_dict_set *set, int mem_kind, void *hip_stream);
+int lz4flex_decompress_batch_dict_set(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                      uint32_t n, const uint32_t *dict_id, void *out_base, const uint64_t *out_off,
+                                      const uint32_t *out_cap, uint32_t *out_len, int32_t *status, uint64_t *detail /* nullable */,
+                                      const lz4flex_dict_set *set, int mem_kind, void *hip_stream);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

@@ -76,6 +76,11 @@ SIGNATURES = {
                                         _I32, _VP]),
     "lz4flex_decompress_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_decompress_batch_shared_dict": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _I32, _VP]),
+    "lz4flex_dict_set_create": (_I32, [_VP, _VP, _VP, _VP, _U32, _I32, C.POINTER(_VP)]),
+    "lz4flex_dict_set_free": (None, [_VP]),
+    "lz4flex_dict_set_count": (_U32, [_VP]),
+    "lz4flex_compress_batch_dict_set": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
+    "lz4flex_decompress_batch_dict_set": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_decompress_batch_ex": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP,
                                             C.POINTER(DecompressExt), _I32, _VP]),
     "lz4flex_decompressed_size_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _I32, _VP]),

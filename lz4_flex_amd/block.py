@@ -616,6 +616,206 @@ def decompress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, s
     return out[:total], out_off, out_len, status
 
 
+# ---- dictionary sets: K prepared dictionaries, one id per block (lz4flex_dict_set_*, lz4flex_*_batch_dict_set) -------------
+NO_DICT = 0xFFFFFFFF     # the dict_id of a block without a dictionary
+
+
+class DictSet:
+    """lz4flex_dict_set: `dictionaries` (a sequence of bytes-like objects or uint8 arrays; an empty one means "no dictionary" for its
+    id) copied to the device and digested once, reused by every compress_batch_with_dict_set / decompress_batch_with_dict_set call
+    that names it.  A context manager; close() (or the end of the object) frees the device memory -- order it behind the work that
+    uses the set.  len() is K."""
+
+    def __init__(self, dictionaries, ctx=None):
+        self._lib = L.load()
+        self._h = C.c_void_p()
+        parts = [_host_u8(d) for d in dictionaries]
+        self.lengths = np.array([p.size for p in parts], dtype=np.uint32)
+        offs = np.zeros(len(parts), dtype=np.uint64)
+        if len(parts):
+            offs[1:] = np.cumsum(self.lengths[:-1], dtype=np.uint64)
+        flat = np.concatenate(parts) if len(parts) and int(self.lengths.sum()) else np.zeros(1, dtype=np.uint8)
+        rc = self._lib.lz4flex_dict_set_create(ctx, C.c_void_p(flat.ctypes.data), C.c_void_p(offs.ctypes.data),
+                                               C.c_void_p(self.lengths.ctypes.data), len(parts), L.MEM_HOST, C.byref(self._h))
+        if rc:
+            raise DeviceError("lz4flex_dict_set_create failed (%d): %s" % (rc, L.last_error()))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ValueError("the dictionary set is closed")
+        return self._h
+
+    def __len__(self):
+        return int(self._lib.lz4flex_dict_set_count(self.handle))
+
+    def close(self):
+        h, self._h = self._h, C.c_void_p()
+        if h:
+            self._lib.lz4flex_dict_set_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def compress_batch_with_dict_set(in_buf, in_off, in_len, dict_id, dict_set, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_compress_batch_dict_set over host buffers: block in_buf[in_off[i] : + in_len[i]] is compressed against dictionary
+    dict_id[i] of `dict_set` (NO_DICT: none) into out_buf[out_off[i] : + out_cap[i]] -- the bytes of compress_batch_with_dict with that
+    dictionary per block; only the batch and the ids travel to the device.  Returns (out_len[u32], status[i32])."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    di, dip = _np(dict_id, np.uint32)
+    oo, oop = _np(out_off, np.uint64)
+    oc, ocp = _np(out_cap, np.uint32)
+    if len(di) != n:
+        raise ValueError("in_off and dict_id differ in length")
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    rc = lib.lz4flex_compress_batch_dict_set(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, dip,
+                                             C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
+                                             C.c_void_p(status.ctypes.data), dict_set.handle, L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
+    return out_len, status
+
+
+def decompress_batch_with_dict_set(in_buf, in_off, in_len, dict_id, dict_set, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_decompress_batch_dict_set over host buffers: the mirror of compress_batch_with_dict_set -- the results of
+    decompress_batch_with_dict with dictionary dict_id[i] per block.  Returns (out_len[u32], status[i32], detail[n,2] u64)."""
+    lib = L.load()
+    n = len(in_off)
+    in_buf = _host_u8(in_buf)
+    io, iop = _np(in_off, np.uint64)
+    il, ilp = _np(in_len, np.uint32)
+    di, dip = _np(dict_id, np.uint32)
+    oo, oop = _np(out_off, np.uint64)
+    oc, ocp = _np(out_cap, np.uint32)
+    if len(di) != n:
+        raise ValueError("in_off and dict_id differ in length")
+    out_len = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    detail = np.zeros((n, 2), dtype=np.uint64)
+    rc = lib.lz4flex_decompress_batch_dict_set(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, dip,
+                                               C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
+                                               C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), dict_set.handle,
+                                               L.MEM_HOST, None)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
+    return out_len, status, detail
+
+
+def _device_ids(dict_id, n, dev):
+    """dict_id as the int32 bit pattern of n u32 on dev"""
+    import torch
+    if int(dict_id.numel()) != n:
+        raise ValueError("in_off and dict_id differ in length")
+    ids = dict_id.to(device=dev, dtype=torch.int64) & 0xFFFFFFFF
+    return ids, torch.where(ids >= 0x80000000, ids - 0x100000000, ids).to(torch.int32).contiguous()
+
+
+def compress_blocks_with_dict_set_device(src, in_off, in_len, dict_id, dict_set, stream=None):
+    """Blocks in device memory against a DictSet: src is a uint8 torch tensor on the set's GPU, block i is src[in_off[i] : + in_len[i]],
+    its dictionary dict_id[i] (NO_DICT: none).  One lz4flex_compress_batch_dict_set (MEM_DEVICE, asynchronous on `stream`, default the
+    current one) into output slots of get_maximum_output_size(in_len[i]) bytes.  Returns (out, out_off, out_len, status) as device
+    tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
+    import torch
+    lib = L.load()
+    dev = src.device
+    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n:
+        raise ValueError("in_off and in_len differ in length")
+    _, ids = _device_ids(dict_id, n, dev)
+    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
+    d_len = in_len.to(device=dev, dtype=torch.int64)
+    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
+    out_off = torch.cumsum(cap64, 0) - cap64
+    total = int(cap64.sum()) if n else 0
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    in_len32 = d_len.to(torch.int32)
+    cap = cap64.to(torch.int32)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0], out_off, out_len, status
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    big = L.MEM_BIG_BLOCKS if int(d_len.max()) > 65536 else 0
+    rc = lib.lz4flex_compress_batch_dict_set(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(in_len32.data_ptr()),
+                                             n, C.c_void_p(ids.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()),
+                                             C.c_void_p(cap.data_ptr()), C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()),
+                                             dict_set.handle, L.MEM_DEVICE | big, C.c_void_p(stream))
+    if rc:
+        raise DeviceError("lz4flex_compress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
+    return out[:total], out_off, out_len, status
+
+
+def decompress_blocks_with_dict_set_device(src, in_off, in_len, dict_id, dict_set, stream=None):
+    """Raw blocks in device memory against a DictSet, sizes unknown: the inverse of compress_blocks_with_dict_set_device.  The size pass
+    with each block's dictionary length as its history, an exclusive prefix sum for the output offsets, ONE host synchronisation (the
+    total, to allocate exactly that), one lz4flex_decompress_batch_dict_set with out_cap = the sizes.  Returns (out, out_off, out_len,
+    status) as device tensors; a block that fails gets its status and an empty slot (an id the set does not have: INVALID_ARG)."""
+    import torch
+    lib = L.load()
+    dev = src.device
+    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    n = int(in_off.numel())
+    if int(in_len.numel()) != n:
+        raise ValueError("in_off and in_len differ in length")
+    ids64, ids = _device_ids(dict_id, n, dev)
+    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
+    d_len = in_len.to(device=dev, dtype=torch.int32).contiguous()
+    size = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), size, torch.empty(0, dtype=torch.int32, device=dev), status
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    sp = C.c_void_p(stream)
+    # (an id without a dictionary -- NO_DICT, or one the set does not have: the decoder refuses that block -- has no history)
+    lens = torch.cat([torch.from_numpy(dict_set.lengths.astype(np.int64)), torch.zeros(1, dtype=torch.int64)]).to(dev)
+    k = len(dict_set)
+    hist = lens[torch.where(ids64 < k, ids64, torch.full_like(ids64, k))].to(torch.int32)     # (the bit pattern of a u32)
+    rc = lib.lz4flex_decompressed_size_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                             C.c_void_p(hist.data_ptr()), C.c_void_p(size.data_ptr()), C.c_void_p(status.data_ptr()),
+                                             L.MEM_DEVICE, sp)
+    if rc:
+        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
+    incl = torch.cumsum(size, 0)
+    out_off = incl - size
+    total, biggest = (int(v) for v in torch.stack([incl[-1], size.max()]).cpu())     # the one synchronisation
+    if biggest > 0xFFFFFFFF:
+        raise ValueError("a block decompresses to %d bytes: more than the decoders' u32 out_cap" % biggest)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    cap = size.to(torch.int32)       # (the bit pattern of a u32 <= 0xFFFFFFFF)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    st2 = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = lib.lz4flex_decompress_batch_dict_set(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
+                                               C.c_void_p(ids.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()),
+                                               C.c_void_p(cap.data_ptr()), C.c_void_p(out_len.data_ptr()), C.c_void_p(st2.data_ptr()), None,
+                                               dict_set.handle, L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if biggest > 131072 else 0), sp)
+    if rc:
+        raise DeviceError("lz4flex_decompress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
+    # a refused id is the decoder's to report; otherwise a block the size pass rejected keeps that status
+    status = torch.where((status != 0) & (st2 != L.E_INVALID_ARG), status, st2)
+    out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
+    return out[:total], out_off, out_len, status
+
+
 # ---- packed batches: one output buffer, the offsets computed on the device (lz4flex_*_batch_packed) ------------------------
 SIZE_MODES = {"prepended": L.SIZES_PREPENDED, "given": L.SIZES_GIVEN, "scan": L.SIZES_SCAN}
 

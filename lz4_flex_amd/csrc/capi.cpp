@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -55,6 +56,21 @@ static int default_ctx(lz4flex_ctx** out) {
     return 0;
 }
 
+// A dictionary set (lz4flex_dict_set_create): ONE device allocation -- [table | counter | digests | the kept bytes] -- that nothing writes
+// after create but the encoder's counter word.  LIVE_SETS: the sets that exist; "debug_dict_set_items" names the set a context used last
+// and must not read one that is gone (a set is not the context's: either may be freed first).
+struct lz4flex_dict_set {
+    int device = 0;
+    uint32_t k = 0;
+    uint8_t* mem = nullptr;
+    const DictSetRec* table = nullptr;       // device: k records
+    uint32_t* counter = nullptr;             // device: the items of the last throughput-encoder call that started from a digest
+};
+static std::mutex g_sets_mu;
+static std::vector<const lz4flex_dict_set*> g_live_sets;
+static constexpr uint32_t DICT_SET_MAX = 1024u;
+static constexpr uint32_t DICT_KEEP = 65536u;
+
 // compress_variant -> launch_compress mode bits: 1 = encode_block + emitter wave (default), 3 = encode_block alone
 static inline int comp_mode_bits(int v) { return v == 1 ? 0x600 : 0; }
 
@@ -80,13 +96,15 @@ enum class Redo {
     Blocks,       // launch_decompress: side by side
     Chain,        // launch_decompress_chain_redo: a chained batch's marked blocks depend on each other -- in chain order
     SharedDict,   // launch_decompress_shared_dict: with the batch's one dictionary
+    DictSet,      // launch_decompress_dict_set: with each block's dictionary out of the batch's set
 };
 static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, Redo how = Redo::Blocks, const uint8_t* dict = nullptr,
-                              uint32_t dict_len = 0) {
+                              uint32_t dict_len = 0, const DictSetArgs* set = nullptr) {
     if (!c->dec_second_pass) return hipSuccess;
     DecompressArgs r = a;
     r.only_status = DECODE_REDO;
     if (how == Redo::Chain) return launch_decompress_chain_redo(r, s);
+    if (how == Redo::DictSet) return launch_decompress_dict_set(r, *set, s);
     if (how == Redo::SharedDict) return launch_decompress_shared_dict(r, dict, dict_len, s);
     return launch_decompress(r, c->dec_lanes, s);
 }
@@ -197,6 +215,14 @@ static hipError_t launch_decompress_shared(lz4flex_ctx* c, const DecompressArgs&
     return e != hipSuccess ? e : launch_redo(c, a, s, Redo::SharedDict, dict, dict_len);
 }
 
+// lz4flex_decompress_batch_dict_set: launch_decompress_shared with the dictionary looked up per block; the same two settings send every
+// block through the reference-order kernel
+static hipError_t launch_decompress_set(lz4flex_ctx* c, const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
+    if (!c->dec_shared || c->dec_variant == 1) return launch_decompress_dict_set(a, set, s);
+    const hipError_t e = launch_decompress_seq_dict_set(a, set, DECODE_REDO, s);
+    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::DictSet, nullptr, 0, &set);
+}
+
 // Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
 // of <= 64 KiB and the host cannot see the device-resident lengths, so a block that breaks the promise is flagged on the
 // device (its bytes would be a valid block, but not lz4_flex's) instead of passing silently.
@@ -245,6 +271,27 @@ __global__ void lz4flex_fill_shared_dict_kernel(uint64_t* dict_off, uint32_t* di
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < n) { dict_off[b] = 0ull; dict_len[b] = len; }
 }
+// lz4flex_compress_batch_dict_set, reference-exact mode: the per-block dictionary arrays of one piece, from the set's table.  dict_off
+// is relative to `base` (the set's allocation) and names where the dictionary WOULD begin if all of `len` were kept: the records kernel
+// above adds len - min(len, 64 KiB), which lands on the first kept byte (u64 arithmetic: the intermediate may wrap).  A refused id gets
+// dict_len 1 (the block encoder leaves the block alone) and flag 1 (the records kernel refuses a dictionary with flags: status
+// LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written).
+__global__ void lz4flex_fill_set_dict_kernel(DictSetArgs set, const uint8_t* base, uint32_t n, uint64_t* dict_off, uint32_t* dict_len, uint32_t* flags) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const uint32_t id = set.dict_id[b];
+    uint64_t off = 0ull;
+    uint32_t len = 0u, flag = 0u;
+    if (id != DICT_ID_NONE) {
+        if (id >= set.k) { len = 1u; flag = 1u; }
+        else {
+            const DictSetRec r = set.table[id];
+            len = r.len;
+            off = (uint64_t)(r.end - base) - r.len;
+        }
+    }
+    dict_off[b] = off; dict_len[b] = len; flags[b] = flag;
+}
 // MEM_HOST batches whose results are sparse in the output span (compress: ~15 KB used of every 72 KB stride):
 // pack the produced bytes densely on the device so that ONE transfer brings them to the host.
 __global__ void __launch_bounds__(256) lz4flex_pack_results_kernel(const uint8_t* src, const uint64_t* src_off, const uint32_t* len,
@@ -273,35 +320,41 @@ static int wave_ws_acquire(lz4flex_ctx* c, hipStream_t s) {
 
 // the encoders for independent blocks: throughput mode (own parse, any block length) or the reference-exact one
 // shared (nullable): ONE dictionary for every block (lz4flex_compress_batch_shared_dict; a has no dictionaries and no flags then)
-static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big, hipStream_t s, const SharedDictArgs* shared = nullptr) {
+// set (nullable, not with shared): a dictionary per block out of a prepared set (lz4flex_compress_batch_dict_set; a has no dictionaries
+// and no flags then); set_base: the set's allocation
+static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big, hipStream_t s, const SharedDictArgs* shared = nullptr,
+                               const DictSetArgs* set = nullptr, const uint8_t* set_base = nullptr) {
     hipError_t le;
     int rc;
     CompressArgs a = a_;
     if (shared) c->shared_counted = c->comp_mode == 0;
     if (c->comp_mode == 0) {
         if ((rc = wave_ws_acquire(c, s))) return rc;
+        if (set) HIP_TRY(hipMemsetAsync(set->counter, 0, 4, s));      // ("debug_dict_set_items" speaks of this call)
         CompressArgs aw = a;
         aw.slide = c->comp_sliding == 2 ? 49152u : (c->comp_sliding == 1 ? 32768u : 0u);
         // sub-windows (lz4_compress_wave.hip Item::sub): batches that leave at least half / three quarters of the persistent workgroups
         // without a block cut their blocks of <= 64 KiB into 2 / 3 / 4 items each
         aw.sub = c->comp_det ? 1u : c->comp_sub != 0 ? (uint32_t)c->comp_sub
                                   : (a.n * 4u <= (uint32_t)c->wave_wgs ? 4u : (a.n * 3u <= (uint32_t)c->wave_wgs ? 3u : (a.n * 2u <= (uint32_t)c->wave_wgs ? 2u : 1u)));
-        le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0, shared);
+        le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0, shared, set);
         if (le == hipSuccess) HIP_TRY(c->wave.release(s));
     } else {
         // (blocks with a dictionary are left alone by both launches below and encoded by the chain kernel behind them)
         // (a shared dictionary: every block has it, the chain kernel encodes them all)
-        le = shared ? hipSuccess : launch_compress(a, c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant), s);
-        if (le == hipSuccess && !big && a.n && !shared) {
+        // (a set: which blocks have one is in the table -- the block encoder runs piece by piece below, behind the arrays it reads)
+        const int enc_bits = c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant);
+        le = (shared || set) ? hipSuccess : launch_compress(a, enc_bits, s);
+        if (le == hipSuccess && !big && a.n && !shared && !set) {
             hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a.in_len, a.n, a.out_len, a.status,
                                a.dict_len);
             le = hipGetLastError();
         }
-        if (le == hipSuccess && (a.dict_len || shared) && a.n) {
+        if (le == hipSuccess && (a.dict_len || shared || set) && a.n) {
             // one-block chains, their records in the (otherwise idle) throughput encoder's workspace: no allocation, ordered across
             // streams like the encoder's own launches; batches larger than the workspace holds records for run in pieces
             if ((rc = wave_ws_acquire(c, s))) return rc;
-            const size_t per = sizeof(lz4flex_chain_block) + 4u + (shared ? 12u : 0u);
+            const size_t per = sizeof(lz4flex_chain_block) + 4u + (shared ? 12u : 0u) + (set ? 16u : 0u);
             const uint32_t piece = (uint32_t)std::min<size_t>(compress_wave_workspace_bytes(c->wave_wgs) / per - 64u, 0x40000000u);
             lz4flex_chain_block* rec = (lz4flex_chain_block*)c->wave_ws;
             uint32_t* cnt = (uint32_t*)((uint8_t*)c->wave_ws + align_up(sizeof(lz4flex_chain_block) * (size_t)piece, 256));
@@ -314,17 +367,44 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
                 le = hipGetLastError();
                 a.dict_base = shared->dict; a.dict_off = soff; a.dict_len = slen;
             }
+            uint32_t* sflg = nullptr;
+            if (set) {
+                // a set: the per-block arrays of one piece, filled from the table in front of every piece, and a flag word per block
+                uint64_t* soff = (uint64_t*)((uint8_t*)cnt + align_up(4u * (size_t)piece, 256));
+                uint32_t* slen = (uint32_t*)((uint8_t*)soff + align_up(8u * (size_t)piece, 256));
+                sflg = (uint32_t*)((uint8_t*)slen + align_up(4u * (size_t)piece, 256));
+                a.dict_base = set_base; a.dict_off = soff; a.dict_len = slen;
+            }
             for (uint32_t b0 = 0; b0 < a.n && le == hipSuccess; b0 += piece) {
                 const uint32_t m = std::min<uint32_t>(piece, a.n - b0);
-                const uint32_t d0 = shared ? 0u : b0;
+                const uint32_t d0 = (shared || set) ? 0u : b0;
+                const dim3 grid((m + 255u) / 256u), block(256);
+                if (set) {
+                    // the piece's arrays, then what the launches in front of the loop do for the other batches: the block encoder
+                    // takes the piece's blocks without a dictionary
+                    CompressArgs p = a;
+                    p.in_off += b0; p.in_len += b0; p.flags = nullptr; p.out_off += b0; p.out_cap += b0; p.out_len += b0; p.status += b0; p.n = m;
+                    DictSetArgs ps = *set;
+                    ps.dict_id += b0;
+                    hipLaunchKernelGGL(lz4flex_fill_set_dict_kernel, grid, block, 0, s, ps, set_base, m, (uint64_t*)a.dict_off, (uint32_t*)a.dict_len, sflg);
+                    le = hipGetLastError();
+                    if (le == hipSuccess) le = launch_compress(p, enc_bits, s);
+                    if (le == hipSuccess && !big) {
+                        hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, grid, block, 0, s, p.in_len, m, p.out_len, p.status, p.dict_len);
+                        le = hipGetLastError();
+                    }
+                    if (le != hipSuccess) break;
+                }
                 hipLaunchKernelGGL(lz4flex_dict_chain_records_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, a.in_off + b0, a.in_len + b0,
-                                   a.flags ? a.flags + b0 : nullptr, a.dict_off + d0, a.dict_len + d0, m, rec, cnt, a.out_len + b0, a.status + b0);
+                                   set ? sflg : (a.flags ? a.flags + b0 : nullptr), a.dict_off + d0, a.dict_len + d0, m, rec, cnt, a.out_len + b0, a.status + b0);
                 le = hipGetLastError();
                 if (le == hipSuccess)
                     le = launch_compress_chain(a.in_base, rec, nullptr, cnt, m, a.out_base, a.out_off + b0, a.out_cap + b0, a.out_len + b0,
                                                a.status + b0, nullptr, s, a.dict_base);
             }
-            if (le == hipSuccess) HIP_TRY(c->wave.release(s));
+            // (also behind a failed launch: whatever was enqueued on the workspace is ordered)
+            const hipError_t re = c->wave.release(s);
+            if (le == hipSuccess) le = re;
         }
     }
     if (le != hipSuccess) return hip_fail(le, "kernel launch");
@@ -352,6 +432,8 @@ struct BatchCall {
     const uint32_t* dict_len = nullptr;
     const uint8_t* shared_dict = nullptr;   // the *_shared_dict calls: ONE dictionary of shared_len bytes for every block (no dict_base then)
     uint32_t shared_len = 0;
+    const lz4flex_dict_set* set = nullptr;  // the *_dict_set calls: block i has dictionary dict_id[i] of the set (no dict_base, no shared_dict then)
+    const uint32_t* dict_id = nullptr;      // ... in the batch's memory kind
     const uint32_t* out_pos = nullptr;      // decompress: prefix mode
     const uint32_t* chain_prev = nullptr;   // chained DEVICE batches: several chains side by side
     uint32_t n_chains = 0;
@@ -372,11 +454,20 @@ static BatchCall batch_of(bool compress, const void* in_base, const uint64_t* in
     return b;
 }
 
+static DictSetArgs set_args_of(lz4flex_ctx* c, const BatchCall& b) {
+    return DictSetArgs{b.set->table, b.dict_id, b.set->k, (uint32_t)c->comp_shared, b.set->counter};
+}
+
 static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
     CompressArgs a{};
     a.in_base = b.in_base; a.in_off = b.in_off; a.in_len = b.in_len; a.flags = b.flags;
     a.out_base = b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.out_len = b.out_len; a.status = b.status; a.n = b.n;
     if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
+    if (b.set) {
+        const DictSetArgs ds = set_args_of(c, b);
+        c->set_counted = c->comp_mode == 0 ? b.set : nullptr;
+        return launch_compress_any(c, a, b.big, b.stream, nullptr, &ds, b.set->mem);
+    }
     SharedDictArgs sh{};
     sh.dict = b.shared_dict; sh.len = b.shared_len; sh.use = (uint32_t)c->comp_shared;
     return launch_compress_any(c, a, b.big, b.stream, b.shared_dict && b.shared_len ? &sh : nullptr);
@@ -398,7 +489,8 @@ static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
         a.debug_giveup = (uint32_t)c->chain_giveup;
     }
     hipError_t le;
-    if (b.shared_dict && b.shared_len) le = launch_decompress_shared(c, a, b.shared_dict, b.shared_len, s);
+    if (b.set) le = launch_decompress_set(c, a, set_args_of(c, b), s);
+    else if (b.shared_dict && b.shared_len) le = launch_decompress_shared(c, a, b.shared_dict, b.shared_len, s);
     // "decompress_variant" 1 and blocks with dictionaries: the reference-order kernel (a chain has no such form)
     else le = ((c->dec_variant != 1 || b.chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, b.big) : launch_decompress(a, c->dec_lanes, s);
     if (chain) (void)chain_ws_end(c, s);                     // (also behind a failed launch: whatever was enqueued is ordered)
@@ -609,6 +701,20 @@ int shared_dict_items(lz4flex_ctx* c) {
     return (int)std::min<uint32_t>(v, 0x7FFFFFFFu);
 }
 
+// "debug_dict_set_items": the same for the last lz4flex_compress_batch_dict_set call on this context, read from that call's set (0: none
+// yet, the reference-exact mode, "compress_shared_dict" 0, a set that has been freed since)
+int dict_set_items(lz4flex_ctx* c) {
+    std::lock_guard<std::mutex> lock(g_sets_mu);
+    if (!c->set_counted || std::find(g_live_sets.begin(), g_live_sets.end(), c->set_counted) == g_live_sets.end()) return 0;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    uint32_t v = 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&v, c->set_counted->counter, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e, "debug_dict_set_items");
+    return (int)std::min<uint32_t>(v, 0x7FFFFFFFu);
+}
+
 }  // namespace
 
 extern "C" {
@@ -643,11 +749,12 @@ int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
         };
         return list_entry(key + 15, t, (int)(sizeof t / sizeof t[0]));
     }
-    const bool items = !strcmp(key, "debug_shared_dict_items");
+    const bool set_items = !strcmp(key, "debug_dict_set_items");
+    const bool items = set_items || !strcmp(key, "debug_shared_dict_items");
     const Setting* st = items ? nullptr : find_setting(key);
     if ((!items && !st) || !key_allowed(key)) return -LZ4FLEX_E_INVALID_ARG;
     if (!c) { const int rc = default_ctx(&c); if (rc) return rc; }
-    if (items) return shared_dict_items(c);
+    if (items) return set_items ? dict_set_items(c) : shared_dict_items(c);
     return st->set_only ? -LZ4FLEX_E_INVALID_ARG : c->*(st->field);
 }
 
@@ -787,7 +894,8 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
     Layout l{16};
     const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_dict_off = l.take(has_dict ? 8ull * n : 0),
                  at_in_len = l.take(4ull * n), at_out_cap = l.take(4ull * n), at_flags = l.take(b.flags ? 4ull * n : 0),
-                 at_dict_len = l.take(has_dict ? 4ull * n : 0), at_out_pos = l.take(has_pos ? 4ull * n : 0);
+                 at_dict_len = l.take(has_dict ? 4ull * n : 0), at_out_pos = l.take(has_pos ? 4ull * n : 0),
+                 at_dict_id = l.take(b.set ? 4ull * n : 0);
     const size_t desc_in_bytes = l.end;
     const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n);
     const size_t desc_bytes = l.end;
@@ -809,6 +917,7 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
         }
         if (has_pos) ((uint32_t*)(hp + at_out_pos))[i] = b.out_pos[i];
     }
+    if (b.set) memcpy(hp + at_dict_id, b.dict_id, 4ull * n);      // (the ids travel with the batch; the dictionaries are on the device already)
     uint8_t* d = c->arena.p;
     hipStream_t s = c->stream;
     if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, b.in_base + in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
@@ -832,6 +941,7 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
     if (has_dict) { dv.dict_base = d + a_dict; dv.dict_off = (const uint64_t*)(dd + at_dict_off); dv.dict_len = (const uint32_t*)(dd + at_dict_len); }
     if (has_shared) { dv.shared_dict = d + a_dict; dv.shared_len = b.shared_len; }
     if (has_pos) dv.out_pos = (const uint32_t*)(dd + at_out_pos);
+    if (b.set) { dv.set = b.set; dv.dict_id = (const uint32_t*)(dd + at_dict_id); }
     if ((rc = launch_batch(c, dv))) return rc;
     HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1064,6 +1174,123 @@ int lz4flex_decompress_batch_shared_dict(lz4flex_ctx* ctx, const void* in_base, 
         return lz4flex_decompress_batch(ctx, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, detail, mem_kind, hip_stream);
     const int rc = begin_batch(&ctx);
     return rc ? rc : run_batch(ctx, b, k);
+}
+
+// ---- dictionary sets ----------------------------------------------------------------------------------------------------------
+int lz4flex_dict_set_create(lz4flex_ctx* ctx, const void* dict_base, const uint64_t* dict_off, const uint32_t* dict_len, uint32_t k,
+                            int mem_kind, lz4flex_dict_set** out) {
+    if (out) *out = nullptr;
+    if (!out || !dict_off || !dict_len || k == 0u || k > DICT_SET_MAX) return -LZ4FLEX_E_INVALID_ARG;
+    if (mem_kind != LZ4FLEX_MEM_HOST && mem_kind != LZ4FLEX_MEM_DEVICE) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;
+    DeviceGuard guard(ctx->device);
+    HIP_TRY(guard.err);
+    // a DEVICE caller's descriptor arrays are device memory: their host copy
+    std::vector<uint64_t> offs(k);
+    std::vector<uint32_t> lens(k);
+    const hipMemcpyKind from = mem_kind == LZ4FLEX_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+    HIP_TRY(hipMemcpy(offs.data(), dict_off, 8ull * k, from));
+    HIP_TRY(hipMemcpy(lens.data(), dict_len, 4ull * k, from));
+    // [table | counter | a digest per dictionary | the kept bytes, each dictionary's start 256-byte aligned]
+    const size_t dg = compress_wave_digest_bytes();
+    Layout l{256};
+    const size_t at_table = l.take(sizeof(DictSetRec) * (size_t)k), at_counter = l.take(4), at_digest = l.take(dg * k);
+    std::vector<size_t> at_bytes(k);
+    bool any = false;
+    for (uint32_t d = 0; d < k; d++) {
+        at_bytes[d] = l.take(std::min<uint32_t>(lens[d], DICT_KEEP));
+        any |= lens[d] != 0u;
+    }
+    if (any && !dict_base) return -LZ4FLEX_E_INVALID_ARG;
+    lz4flex_dict_set* set = new (std::nothrow) lz4flex_dict_set();
+    if (!set) return -LZ4FLEX_E_NOMEM;
+    set->device = ctx->device; set->k = k;
+    uint8_t* scratch = nullptr;
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMalloc((void**)&set->mem, l.end + 256);
+    if (e == hipSuccess) e = hipMalloc((void**)&scratch, compress_wave_digest_scratch_bytes() * k);
+    std::vector<DictSetRec> table(k);
+    for (uint32_t d = 0; d < k && e == hipSuccess; d++) {
+        DictSetRec& r = table[d];
+        r.len = lens[d];
+        r.kept = std::min<uint32_t>(lens[d], DICT_KEEP);
+        r.h = std::min<uint32_t>(lens[d], 32768u);
+        r.hs = compress_wave_digest_hs(r.h);
+        r.end = set->mem + at_bytes[d] + r.kept;
+        r.digest = set->mem + at_digest + dg * d;
+        if (r.kept)
+            e = hipMemcpyAsync(set->mem + at_bytes[d], (const uint8_t*)dict_base + offs[d] + (lens[d] - r.kept), r.kept,
+                               mem_kind == LZ4FLEX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    }
+    // (pageable host memory: hipMemcpyAsync has read the caller's bytes, and `table`, when it returns)
+    if (e == hipSuccess) e = hipMemcpyAsync(set->mem + at_table, table.data(), sizeof(DictSetRec) * (size_t)k, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(set->mem + at_counter, 0, 4, s);
+    set->table = (const DictSetRec*)(set->mem + at_table);
+    set->counter = (uint32_t*)(set->mem + at_counter);
+    if (e == hipSuccess) e = launch_dict_set_digests(set->table, k, scratch, s);
+    const hipError_t w = hipStreamSynchronize(s);      // (also behind a failure: nothing of this call is in flight when its memory goes)
+    if (e == hipSuccess) e = w;
+    if (scratch) (void)hipFree(scratch);
+    if (e != hipSuccess) {
+        rc = hip_fail(e, "dict_set_create");
+        if (set->mem) (void)hipFree(set->mem);
+        delete set;
+        return e == hipErrorOutOfMemory ? -LZ4FLEX_E_NOMEM : rc;
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_sets_mu);
+        g_live_sets.push_back(set);
+    }
+    *out = set;
+    return 0;
+}
+
+void lz4flex_dict_set_free(lz4flex_dict_set* set) {
+    if (!set) return;
+    {
+        std::lock_guard<std::mutex> lock(g_sets_mu);
+        g_live_sets.erase(std::remove(g_live_sets.begin(), g_live_sets.end(), set), g_live_sets.end());
+    }
+    if (set->mem) {
+        DeviceGuard guard(set->device);
+        (void)hipFree(set->mem);
+    }
+    delete set;
+}
+
+uint32_t lz4flex_dict_set_count(const lz4flex_dict_set* set) { return set ? set->k : 0u; }
+
+// what the two *_dict_set entries share: the checks in their order, then the batch
+static int run_dict_set_batch(lz4flex_ctx* ctx, BatchCall& b, const uint32_t* dict_id, const lz4flex_dict_set* set, int mem_kind, int host_flags) {
+    if (!batch_arrays_ok(b) || (b.n && (!dict_id || !set))) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, host_flags, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    // "debug_dict_set_items" speaks of THIS call from here on: one that has nothing to do or is refused below counts nothing
+    if (b.compress)
+        if (lz4flex_ctx* c0 = ctx ? ctx : g_default_ctx) c0->set_counted = nullptr;
+    if (b.n == 0) return 0;
+    b.has_ext = true; b.set = set; b.dict_id = dict_id;
+    const int rc = begin_batch(&ctx);
+    if (rc) return rc;
+    if (ctx->device != set->device) { g_last_error = "the dictionary set belongs to another device"; return -LZ4FLEX_E_INVALID_ARG; }
+    return run_batch(ctx, b, k);
+}
+
+int lz4flex_compress_batch_dict_set(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                    const uint32_t* dict_id, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
+                                    uint32_t* out_len, int32_t* status, const lz4flex_dict_set* set, int mem_kind, void* hip_stream) {
+    BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    return run_dict_set_batch(ctx, b, dict_id, set, mem_kind, 0);
+}
+
+int lz4flex_decompress_batch_dict_set(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                      const uint32_t* dict_id, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
+                                      uint32_t* out_len, int32_t* status, uint64_t* detail, const lz4flex_dict_set* set, int mem_kind,
+                                      void* hip_stream) {
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.detail = detail;
+    return run_dict_set_batch(ctx, b, dict_id, set, mem_kind, LZ4FLEX_MEM_BIG_BLOCKS);
 }
 
 int lz4flex_decompress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,

@@ -501,10 +501,8 @@ __device__ __forceinline__ u32x4 tail16(const g_u8* __restrict__ tail, uint32_t 
 // on the same stream.  The chunks go through an LDS slot exactly like the tail chunks of index_window and are indexed by
 // index_chunk<true> -- the indexer's own rule, not a copy of it; the cand[] entries it writes for them go to `cand_scratch` (the first
 // workgroup's first cand[] slot: the encoder has not started yet and overwrites it).  LDS: the table, then one chunk slot.
-__global__ void __launch_bounds__(64) lz4_shared_digest_kernel(const uint8_t* __restrict__ dict, uint32_t dict_len, uint8_t* __restrict__ digest,
-                                                               uint8_t* __restrict__ cand_scratch) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
-    lds_u8* lds = (lds_u8*)dyn_lds;
+__device__ __forceinline__ void digest_body(const uint8_t* __restrict__ dict, uint32_t dict_len, uint8_t* __restrict__ digest,
+                                            uint8_t* __restrict__ cand_scratch, lds_u8* lds) {
     const uint32_t lane = threadIdx.x;
     const uint32_t h = dict_len < HIST ? dict_len : HIST, hs = digest_hs(h);
     const g_u8* __restrict__ tail = (const g_u8*)dict + (dict_len - h);
@@ -540,6 +538,19 @@ __global__ void __launch_bounds__(64) lz4_shared_digest_kernel(const uint8_t* __
         g_u32* hd = reinterpret_cast<g_u32*>(dg + DG_HDR);
         hd[0] = same; hd[1] = splat; hd[2] = 0u;
     }
+}
+__global__ void __launch_bounds__(64) lz4_shared_digest_kernel(const uint8_t* __restrict__ dict, uint32_t dict_len, uint8_t* __restrict__ digest,
+                                                               uint8_t* __restrict__ cand_scratch) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
+    digest_body(dict, dict_len, digest, cand_scratch, (lds_u8*)dyn_lds);
+}
+// The digests of a dictionary set (lz4flex_dict_set_create): the same body, a workgroup per dictionary, once per SET.  Dictionary d is
+// the `kept` bytes in front of table[d].end (its last h bytes are all the body reads); its cand[] scratch is slot d of cand_scratch.
+constexpr uint32_t DIGEST_SCRATCH = 2u * HIST;           // cand[] of the positions [0, hs), hs < HIST: two bytes each
+__global__ void __launch_bounds__(64) lz4_set_digest_kernel(const DictSetRec* __restrict__ table, uint8_t* __restrict__ cand_scratch) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
+    const DictSetRec r = table[blockIdx.x];
+    digest_body(r.end - r.kept, r.kept, r.digest, cand_scratch + (size_t)blockIdx.x * DIGEST_SCRATCH, (lds_u8*)dyn_lds);
 }
 
 // ---- worker ---------------------------------------------------------------------------------------------------
@@ -1387,10 +1398,19 @@ struct WaveArgs : CompressArgs {
     uint8_t* digest;
 };
 template <class A> constexpr bool IS_SHARED = __is_same(A, WaveArgs);
+// What the _set_ kernels work on (lz4flex_compress_batch_dict_set): block i's dictionary is record dict_id[i] of a prepared set.  An item
+// with a dictionary is what it is in a _shared_ kernel -- the tail staged from that dictionary's digest, the first window's table from
+// it when the item is eligible -- with the digest looked up per item; an item without one is what it is in every other kernel.
+struct SetArgs : CompressArgs {
+    DictSetArgs set;
+};
+template <class A> constexpr bool IS_SET = __is_same(A, SetArgs);
+template <class A> constexpr bool HAS_DIGEST = IS_SHARED<A> || IS_SET<A>;
 struct Item {
     uint32_t blk, win, nwin, len, skip, hist, slide;     // slide: 0, or the bytes the windows advance by (HIST with history in front of the block; CompressArgs::slide for a long block)
     uint32_t sub;                                        // 0, or the parsed bytes per sub-window (WINDOW / CompressArgs::sub, rounded up to 512) of a block cut into sub-windows
     uint32_t dct;                                        // 1: the first `hist` bytes are the tail of the block's dictionary (stage_window)
+    uint32_t did;                                        // _set_ kernels, dct items: the dictionary's record
     uint64_t in_off;
 };
 // window geometry: window t.win covers [win_base, win_base + win_len) of the item and parses [win_from, that end)
@@ -1417,13 +1437,22 @@ __device__ __forceinline__ uint32_t win_send(const Item& t) { return t.sub != 0u
 template <class A>
 __device__ __forceinline__ void item_load(const A& a, Item& it) {
     // first window of block it.blk (or invalid)
-    it.win = 0u; it.nwin = 0u; it.len = 0u; it.skip = 0u; it.hist = 0u; it.slide = 0u; it.sub = 0u; it.dct = 0u; it.in_off = 0ull;
+    it.win = 0u; it.nwin = 0u; it.len = 0u; it.skip = 0u; it.hist = 0u; it.slide = 0u; it.sub = 0u; it.dct = 0u; it.did = 0u; it.in_off = 0ull;
     if (it.blk >= a.n) return;
     const uint32_t len = a.in_len[it.blk];
     const uint32_t cap = a.out_cap[it.blk];
     uint32_t h = (a.flags != nullptr && (a.flags[it.blk] >> 8) >= HIST && len != 0u && len <= 0xFFFFFFFFu - HIST) ? HIST : 0u;
     uint32_t dl = a.dict_len != nullptr ? a.dict_len[it.blk] : 0u;
     if constexpr (IS_SHARED<A>) dl = a.shared_len;                   // (a shared dictionary: every block has it)
+    if constexpr (IS_SET<A>) {
+        // (a set: h is min(len, HIST) of the record's untruncated length, as for a per-block dictionary of that length)
+        const uint32_t id = a.set.dict_id[it.blk];
+        if (id != DICT_ID_NONE) {
+            if (id >= a.set.k) { it.skip = 2u; it.nwin = 1u; return; }       // refused: status LZ4FLEX_E_INVALID_ARG, nothing written
+            dl = a.set.table[id].len;
+            it.did = id;
+        }
+    }
     if (dl != 0u) {
         // a dictionary: its last h bytes are the item's history.  With frame flags or history bits as well, or an item longer than
         // 4 GiB, the block is refused (status LZ4FLEX_E_INVALID_ARG, nothing written)
@@ -1517,6 +1546,22 @@ __device__ __forceinline__ RunGeom run_geom(const Item& t) {
     return g;
 }
 
+// The digest a dictionary item of a _shared_ / _set_ kernel starts from, what it covers, and the word its eligible items are counted in.
+// A set's record is read through uniform registers: the item is the workgroup's, whichever lane asks.
+__device__ __forceinline__ const uint8_t* item_digest(const WaveArgs& a, const Item&) { return a.digest; }
+__device__ __forceinline__ uint32_t item_hs(const WaveArgs& a, const Item&) { return a.shared_hs; }
+__device__ __forceinline__ uint32_t* item_counter(const WaveArgs& a) { return (uint32_t*)(a.digest + DG_HDR) + 2; }
+__device__ __forceinline__ const DictSetRec* set_rec(const SetArgs& a, const Item& t) { return uni_gptr<const DictSetRec>(a.set.table) + uni(t.did); }
+__device__ __forceinline__ const uint8_t* item_digest(const SetArgs& a, const Item& t) { return uni_gptr<const uint8_t>(set_rec(a, t)->digest); }
+__device__ __forceinline__ uint32_t item_hs(const SetArgs& a, const Item& t) { return a.set.use != 0u ? uni(set_rec(a, t)->hs) : 0u; }
+__device__ __forceinline__ uint32_t* item_counter(const SetArgs& a) { return a.set.counter; }
+// the staged tail a workgroup keeps from first window to first window (tail_kept): 0 = none, else whose -- a _shared_ kernel has one
+// dictionary, a _set_ kernel keeps the tail only for an item of the same record
+__device__ __forceinline__ uint32_t keep_tag(const WaveArgs& a, const Item&) { return a.shared_keep != 0u ? 1u : 0u; }
+__device__ __forceinline__ bool keep_hit(const WaveArgs&, const Item&, uint32_t kept) { return kept != 0u; }
+__device__ __forceinline__ uint32_t keep_tag(const SetArgs& a, const Item& t) { return a.set.use != 0u ? t.did + 1u : 0u; }
+__device__ __forceinline__ bool keep_hit(const SetArgs&, const Item& t, uint32_t kept) { return kept == t.did + 1u; }
+
 // prof (nullable, tools only): cycle sums per role, [0] indexer busy, [1] indexer at barriers, [2] workers matching,
 // [3] workers at the barrier behind matching, [4] placing, [5] loading the next window, [6] at the barrier behind loading,
 // [7] windows
@@ -1575,11 +1620,11 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
     auto do_stage = [&](const Item& t) {
         const uint32_t base = win_base(t);
         const uint32_t nrd = win_rd(t);
-        if constexpr (IS_SHARED<A>) {
+        if constexpr (HAS_DIGEST<A>) {
             // (from the 16-byte boundary below h on: stage_window gathers the piece that straddles h byte by byte; win 0: base == 0)
-            const uint32_t from = (t.win == 0u && tail_kept != 0u) ? (t.hist & ~15u) : 0u;
-            stage_window(a.digest + DG_TAIL, a.in_base + t.in_off, base + from, nrd - from, t.hist, stg + from, lane);
-            tail_kept = (t.win == 0u && a.shared_keep != 0u) ? 1u : 0u;
+            const uint32_t from = (t.win == 0u && keep_hit(a, t, tail_kept)) ? (t.hist & ~15u) : 0u;
+            stage_window(item_digest(a, t) + DG_TAIL, a.in_base + t.in_off, base + from, nrd - from, t.hist, stg + from, lane);
+            tail_kept = t.win == 0u ? keep_tag(a, t) : 0u;
             return;
         } else {
         const uint8_t* tail = a.dict_base + a.dict_off[t.blk] + (a.dict_len[t.blk] - t.hist);    // the dictionary's last h bytes
@@ -1595,13 +1640,14 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
         // a run window's one match (see index_window): from the first parsed position that has a byte in front of it in the window to
         // the window's last match end; asked for only where that is a match the block format allows
         const RunGeom rg = run_geom(t);
-        if constexpr (IS_SHARED<A>) {
-            if (t.win == 0u && a.shared_hs != 0u && act_n >= a.shared_hs) {
+        if constexpr (HAS_DIGEST<A>) {
+            const uint32_t hs = (IS_SHARED<A> || t.dct != 0u) ? item_hs(a, t) : 0u;     // (a _set_ kernel's item without a dictionary has no record)
+            if (t.win == 0u && hs != 0u && act_n >= hs) {
                 // the item's positions [0, hs) are the digest's: the table from there, chunks from hs / CHUNK on
                 const uint32_t run = index_window<true>(win_src(a, t, stg), wl, act_n, win_rd(t), slots + (size_t)slot * SLOT_BYTES, lds, lane, rg.ok,
-                                                        DigestRef<true>{a.digest, a.shared_hs});
+                                                        DigestRef<true>{item_digest(a, t), hs});
                 if (redo == 0 && lane == 0u)      // (tests: the items that started from the digest; a block encoded again by the redo launch is not counted twice)
-                    __hip_atomic_fetch_add((uint32_t*)(a.digest + DG_HDR) + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(item_counter(a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (lane == 0u) run_flag[slot] = run;
                 return;
             }
@@ -1695,7 +1741,7 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
         }
         if (w != WORKERS) {
             if (it.skip) {
-                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = ((IS_SHARED<A> || a.dict_len != nullptr) && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = ((HAS_DIGEST<A> || a.dict_len != nullptr) && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
             } else {
                 place_segment(lds, a.in_base + it.in_off, it.len, it.win, last_win, wl, win_base(it), win_skip(it), win_send(it), bodies + (size_t)w * BODY_STRIDE,
                               a.out_base + a.out_off[it.blk], k & 1u, w, lane, a.out_len + it.blk, a.status + it.blk,
@@ -1727,7 +1773,7 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
 // Batches without dictionaries run kernels whose arguments say so at compile time: every dictionary branch folds away and the
 // code is the encoder's as it was before dictionaries existed (same registers, same speed); batches with them run the _dict_ kernels.
 // The _shared_ kernels (lz4flex_compress_batch_shared_dict) are the only instances of wave_body<WaveArgs>; they hold no per-block
-// dictionaries and no flags.
+// dictionaries and no flags.  The _set_ kernels (lz4flex_compress_batch_dict_set) are those of wave_body<SetArgs>, likewise.
 __device__ __forceinline__ CompressArgs no_dicts(CompressArgs a) {
     a.dict_base = nullptr; a.dict_off = nullptr; a.dict_len = nullptr;
     return a;
@@ -1737,6 +1783,13 @@ __device__ __forceinline__ WaveArgs only_shared(const CompressArgs& a, const Sha
     static_cast<CompressArgs&>(r) = no_dicts(a);
     r.flags = nullptr;
     r.shared_dict = sh.dict; r.shared_len = sh.len; r.shared_hs = sh.hs; r.shared_keep = sh.keep; r.digest = sh.digest;
+    return r;
+}
+__device__ __forceinline__ SetArgs only_set(const CompressArgs& a, const DictSetArgs& st) {
+    SetArgs r;
+    static_cast<CompressArgs&>(r) = no_dicts(a);
+    r.flags = nullptr;
+    r.set = st;
     return r;
 }
 __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_compress_wave_kernel(const CompressArgs a, uint8_t* __restrict__ ws,
@@ -1765,6 +1818,16 @@ __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6,
                                                                                                                             uint8_t* __restrict__ ws, int32_t redo) {
     wave_body(only_shared(a, sh), ws, nullptr, nullptr, redo, CARRY_SPINS);
 }
+// (Not lz4_compress_wave_set_*: tests/test_isa_shared_dict.py lists the kernels of that stem by name, as the six they were when it was
+// written, and stays as it is.  The register figures of these two are in profiles/r12_dict_set.txt.)
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_wave_set_kernel(const CompressArgs a, const DictSetArgs st,
+                                                                    uint8_t* __restrict__ ws, uint32_t* __restrict__ carry, unsigned long long* __restrict__ prof, uint32_t carry_spins) {
+    wave_body(only_set(a, st), ws, carry, prof, 0, carry_spins);
+}
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) lz4_wave_set_redo_kernel(const CompressArgs a, const DictSetArgs st,
+                                                                                                                         uint8_t* __restrict__ ws, int32_t redo) {
+    wave_body(only_set(a, st), ws, nullptr, nullptr, redo, CARRY_SPINS);
+}
 
 }  // namespace wave
 
@@ -1778,8 +1841,17 @@ const uint32_t* compress_wave_shared_counter(const void* workspace, int n_workgr
     return (const uint32_t*)((const uint8_t*)workspace + wave_digest_at(n_workgroups) + wave::DG_HDR) + 2;
 }
 
+size_t compress_wave_digest_bytes() { return wave::DIGEST_BYTES; }
+uint32_t compress_wave_digest_hs(uint32_t h) { return wave::digest_hs(h); }
+size_t compress_wave_digest_scratch_bytes() { return wave::DIGEST_SCRATCH; }
+hipError_t launch_dict_set_digests(const DictSetRec* table, uint32_t k, uint8_t* cand_scratch, hipStream_t s) {
+    if (k == 0u) return hipSuccess;
+    hipLaunchKernelGGL(wave::lz4_set_digest_kernel, dim3(k), dim3(64), (2u << wave::HBITS) + wave::CHUNK_SLOT, s, table, cand_scratch);
+    return hipGetLastError();
+}
+
 hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s, unsigned long long* prof, bool carry_wait,
-                                const SharedDictArgs* shared_dict) {
+                                const SharedDictArgs* shared_dict, const DictSetArgs* dict_set) {
     if (a.n == 0u) return hipSuccess;
     if (!workspace || n_workgroups <= 0) return hipErrorInvalidValue;
     static unsigned long long have = 0ull;
@@ -1791,7 +1863,9 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
                               reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_kernel),
                               reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_redo_kernel),
                               reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_redo_kernel)}) {
+                              reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_redo_kernel),
+                              reinterpret_cast<const void*>(wave::lz4_wave_set_kernel),
+                              reinterpret_cast<const void*>(wave::lz4_wave_set_redo_kernel)}) {
             const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave::LDS_BYTES);
             if (e != hipSuccess) return e;
         }
@@ -1811,7 +1885,12 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
     const bool shared = shared_dict != nullptr && shared_dict->dict != nullptr && shared_dict->len != 0u;
     const uint32_t spins = carry_wait ? wave::CARRY_SPINS : 1u;
     SharedDictArgs sh{};
-    if (shared) {
+    if (dict_set != nullptr) {
+        // (the digests are the set's, made when it was: nothing in front of the encoder)
+        if (shared || dicts || dict_set->table == nullptr || dict_set->dict_id == nullptr || dict_set->counter == nullptr) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(wave::lz4_wave_set_kernel, dim3((uint32_t)n_workgroups), dim3(wave::THREADS), wave::LDS_BYTES, s, as, *dict_set,
+                           (uint8_t*)workspace, carry, prof, spins);
+    } else if (shared) {
         // the digest of the shared dictionary, once, in front of the encoder (its scratch: the first workgroup's first cand[] slot)
         sh = *shared_dict;
         sh.digest = (uint8_t*)workspace + wave_digest_at(n_workgroups);
@@ -1844,7 +1923,9 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
         // debugger) left its block with status 66.  Those blocks are encoded again by their own workgroup, window after window,
         // with the carry in LDS: the same bytes, no waiting, and no valid input turns into an error.  Nothing to do: ~10 us.
         const uint32_t g = a.n < (uint32_t)n_workgroups ? a.n : (uint32_t)n_workgroups;
-        if (shared)
+        if (dict_set != nullptr)
+            hipLaunchKernelGGL(wave::lz4_wave_set_redo_kernel, dim3(g), dim3(wave::THREADS), wave::LDS_BYTES, s, as, *dict_set, (uint8_t*)workspace, 66);
+        else if (shared)
             hipLaunchKernelGGL(wave::lz4_compress_wave_shared_redo_kernel, dim3(g), dim3(wave::THREADS), wave::LDS_BYTES, s, as, sh, (uint8_t*)workspace, 66);
         else
             hipLaunchKernelGGL(dicts ? wave::lz4_compress_wave_dict_redo_kernel : wave::lz4_compress_wave_redo_kernel, dim3(g), dim3(wave::THREADS),

@@ -236,7 +236,10 @@ __global__ void __launch_bounds__(256) lz4_decompress_blocks_kernel(DecompressAr
 // lz4flex_decompress_batch_shared_dict: decode_block<16, true> with ONE dictionary for every block -- no per-block dictionary arrays, no
 // workspace, any n.  only_status != 0: the second pass behind the sequence decoder's dictionary form (the blocks it marked, in the
 // reference's check order, WITH the dictionary); 0: every block ("decompress_shared_dict" 0, "decompress_variant" 1).
-__global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(DecompressArgs a, const uint8_t* dict, uint32_t dict_len) {
+// lz4flex_decompress_batch_dict_set: the same with block b's dictionary looked up in a set (SET; dict / dict_len are not read then).  A
+// block without one decodes with dict_len 0; a refused id is status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written.
+template <bool SET>
+__global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(DecompressArgs a, const uint8_t* dict, uint32_t dict_len, DictSetArgs set) {
     constexpr int G = 16;
     const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
     const uint32_t b = tid / G;
@@ -246,7 +249,10 @@ __global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(Decompr
     const uint32_t cap = a.out_cap[b];
     uint32_t produced = 0u;
     uint64_t expected = 0u;
-    const int32_t st = decode_block<G, true>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g, &produced, &expected);
+    bool found = true;
+    if constexpr (SET) found = dict_set_find(set, b, dict, dict_len);
+    const int32_t st = !found ? LZ4FLEX_DEV_E_INVALID_ARG
+                              : decode_block<G, true>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g, &produced, &expected);
     if (g == 0u) {
         a.status[b] = st;
         a.out_len[b] = st == 0 ? produced : 0u;
@@ -260,7 +266,14 @@ __global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(Decompr
 hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     if (dict == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, dict, dict_len);
+    hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel<false>, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, dict, dict_len, DictSetArgs{});
+    return hipGetLastError();
+}
+
+hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel<true>, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, (const uint8_t*)nullptr, 0u, set);
     return hipGetLastError();
 }
 

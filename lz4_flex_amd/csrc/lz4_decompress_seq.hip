@@ -572,13 +572,36 @@ __device__ __forceinline__ bool run_chunks(Dec<G, DICT>& D, uint32_t t0, uint32_
 #else
 #define LZ4S_WAVES_ATTR
 #endif
-// DICT: every block of the batch has the ONE dictionary dict[0, dict_len) (device memory, dict_len != 0), and none has a prefix
-template <class G, bool DICT>
-__global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code, const uint8_t* dict, uint32_t dict_len) {
+// Where the blocks' dictionaries come from.  OneDict: every block of the batch has the ONE dictionary dict[0, dict_len) (device memory,
+// dict_len != 0), and none has a prefix.  DictSetArgs (lz4_device.h): block b has the dictionary its id names in a prepared set -- or none
+// (dl = 0, so PV = LO = 0: the block decodes as it does without the dictionary form), or a refused id.
+struct NoDict {};
+struct OneDict { const uint8_t* dict; uint32_t dict_len; };
+template <class SRC> constexpr bool SRC_DICT = !__is_same(SRC, NoDict);
+template <class G, class SRC>
+__global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code, SRC src) {
+    constexpr bool DICT = SRC_DICT<SRC>;
     extern __shared__ __attribute__((aligned(16))) uint8_t seq_lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= a.n) return;
+    [[maybe_unused]] const uint8_t* dict = nullptr;
+    [[maybe_unused]] uint32_t dict_len = 0u;
+    if constexpr (__is_same(SRC, OneDict)) { dict = src.dict; dict_len = src.dict_len; }
+    if constexpr (__is_same(SRC, DictSetArgs)) {
+        if (!dict_set_find(src, b, dict, dict_len)) {
+            if (lane == 0u) {
+                a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG;
+                a.out_len[b] = 0u;
+                if (a.detail) { a.detail[2u * b] = 0u; a.detail[2u * b + 1u] = 0u; }
+            }
+            return;
+        }
+        // (the wavefront's one record, said to be uniform: PV / LO / dv below are scalars as they are with the launch's one dictionary)
+        const uint64_t dp = (uint64_t)(uintptr_t)dict;
+        dict = (const uint8_t*)(uintptr_t)(((uint64_t)uni((uint32_t)(dp >> 32)) << 32) | uni((uint32_t)dp));
+        dict_len = uni(dict_len);
+    }
     // (every LDS access below goes by byte address from 0: the dynamic segment is the kernel's only LDS)
     if ((uint32_t)(uintptr_t)(lds_u8*)seq_lds != 0u) { if (lane == 0u) { a.status[b] = redo_code; a.out_len[b] = 0u; } return; }
     Dec<G, DICT> D;
@@ -678,7 +701,7 @@ hipError_t launch_decompress_seq(const DecompressArgs& a, int32_t redo_code, hip
     if (a.dict_base != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;       // (a prefix -- out_pos -- is fine: see the kernel)
     typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
     static_assert(G::LDS <= 65536u, "the default limit of dynamic LDS: no function attribute to set per device");
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, false>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, (const uint8_t*)nullptr, 0u);
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::NoDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::NoDict{});
     return hipGetLastError();
 }
 
@@ -689,7 +712,18 @@ hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* di
     if (a.n == 0u) return hipSuccess;
     if (dict == nullptr || dict_len == 0u || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
     typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, true>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, dict, dict_len);
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::OneDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::OneDict{dict, dict_len});
+    return hipGetLastError();
+}
+
+// Every block against the dictionary its id names in a set (lz4flex_decompress_batch_dict_set): the dictionary form with the
+// dictionary looked up per block.  Irregular blocks get status `redo_code`; the caller runs launch_decompress_dict_set with only_status
+// = redo_code behind this launch.  A refused id gets its final status here.
+hipError_t launch_decompress_seq_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, DictSetArgs>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, set);
     return hipGetLastError();
 }
 

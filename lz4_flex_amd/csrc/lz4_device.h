@@ -96,6 +96,35 @@ struct SharedDictArgs {
     uint8_t* digest;
 };
 
+// A dictionary set (lz4flex_dict_set): K dictionaries in device memory the set owns, prepared once.  One record per dictionary:
+struct DictSetRec {
+    const uint8_t* end;        // behind the last of the `kept` bytes the set holds of it
+    uint8_t* digest;           // its digest for the throughput encoder (compress_wave_digest_bytes() bytes; lz4_compress_wave.hip DG_*)
+    uint32_t len;              // the caller's length, untruncated (reference-exact mode picks its table kind from it); 0 = no dictionary
+    uint32_t kept;             // min(len, 65 536): an offset is at most 65 535
+    uint32_t h, hs;            // throughput encoder: min(len, 32 768), and the positions the digest covers (0: no item starts from it)
+};
+// a batch's view of a set: block i has dictionary table[dict_id[i]]; DICT_ID_NONE = none; any other id >= k: the block is refused
+// (status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written)
+constexpr uint32_t DICT_ID_NONE = 0xFFFFFFFFu;
+struct DictSetArgs {
+    const DictSetRec* table;
+    const uint32_t* dict_id;
+    uint32_t k;
+    uint32_t use;              // throughput encoder: 0 = no item starts from a digest ("compress_shared_dict" 0)
+    uint32_t* counter;         // throughput encoder: the items that started from a digest are counted here (the set's word)
+};
+// block b's dictionary: false = a refused id; dl == 0 = none
+__device__ __forceinline__ bool dict_set_find(const DictSetArgs& st, uint32_t b, const uint8_t*& dict, uint32_t& dl) {
+    const uint32_t id = st.dict_id[b];
+    dict = nullptr; dl = 0u;
+    if (id == DICT_ID_NONE) return true;
+    if (id >= st.k) return false;
+    const DictSetRec r = st.table[id];
+    dict = r.end - r.kept; dl = r.kept;
+    return true;
+}
+
 // plan / replay decoder (lz4_decompress_plan.hip, lz4_decompress_replay.hip; record format: lz4_plan_common.h)
 namespace plan { struct BlockPlan; }
 struct ReplayArgs {
@@ -136,6 +165,10 @@ hipError_t launch_decompress_seq(const DecompressArgs& a, int32_t redo_code, hip
 hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s);
 // lz4_decompress.hip's decode_block<16, true> with that one dictionary: a.only_status 0 = every block, else the marked ones
 hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s);
+// lz4flex_decompress_batch_dict_set: the two launches above with block b's dictionary looked up in a set (DictSetArgs); a block without
+// one decodes in the same launch, a refused id gets its status from whichever of the two sees the block first
+hipError_t launch_decompress_seq_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s);
+hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s);
 hipError_t launch_decompress_split(const DecompressArgs& a, hipStream_t s, int blocks_per_wg = 0);   // parser / copier wavefronts, no dict/prefix
 // parser -> emitter -> quad wavefronts (lz4_decompress_fused.hip: the split decoder's parser, the replay decoder's copy engine, no dict/prefix);
 // blocks of 512 KiB or more are left with status redo_code for a second pass of launch_decompress.  -DLZ4FLEX_TOOLS builds only (round 6)
@@ -152,7 +185,14 @@ const uint32_t* compress_wave_shared_counter(const void* workspace, int n_workgr
 hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s,
                                 unsigned long long* prof = nullptr,    // prof: 8 cycle counters (tools), nullable
                                 bool carry_wait = true,                // tests: false = a window that has to wait for its predecessor gives up at once
-                                const SharedDictArgs* shared_dict = nullptr);   // nullable: the batch's one dictionary (the _shared_ kernels)
+                                const SharedDictArgs* shared_dict = nullptr,    // nullable: the batch's one dictionary (the _shared_ kernels)
+                                const DictSetArgs* dict_set = nullptr);         // nullable (not with shared_dict): a dictionary per block out of a set (the _set_ kernels)
+// a dictionary set's digests: bytes per dictionary, and the kernel that fills table[0 .. k)'s (a workgroup of one wavefront per
+// dictionary; cand_scratch: compress_wave_digest_scratch_bytes() bytes per dictionary, dead behind the launch)
+size_t compress_wave_digest_bytes();
+uint32_t compress_wave_digest_hs(uint32_t h);     // the positions of an item with h bytes of dictionary in front that a digest covers
+size_t compress_wave_digest_scratch_bytes();
+hipError_t launch_dict_set_digests(const DictSetRec* table, uint32_t k, uint8_t* cand_scratch, hipStream_t s);
 
 // chains of dependent blocks (dictionary / Linked frames); `blocks` is an array of the 40-byte ChainBlock
 // records laid out as {u64 in_off, u64 dict_off, u32 in_len, in_pos, dict_len, so, repos, flags}.
