@@ -61,6 +61,12 @@ def _raise_decode(code, detail):
     raise DeviceError("lz4flex error %d: %s" % (code, L.last_error()))
 
 
+def _check(rc, name):
+    """the return code of the C entry `name`"""
+    if rc:
+        raise DeviceError("%s failed (%d): %s" % (name, rc, L.last_error()))
+
+
 def _buf(b):
     """bytes-like -> (ctypes pointer, length, keepalive)"""
     if isinstance(b, (bytes, bytearray)):
@@ -74,9 +80,7 @@ def set_compress_mode(mode, ctx=None):
     """Encoder of this thread's default context (or of `ctx`): "fast" = throughput encoder (own parse: a valid LZ4 block
     that lz4_flex decodes to the input; default), "exact" = lz4_flex's own bytes (src/block/compress.rs:318-489)."""
     v = {"fast": 0, "exact": 1}[mode]
-    rc = L.load().lz4flex_set_tuning(ctx, b"compress_mode", v)
-    if rc:
-        raise DeviceError("lz4flex_set_tuning(compress_mode) failed (%d): %s" % (rc, L.last_error()))
+    _check(L.load().lz4flex_set_tuning(ctx, b"compress_mode", v), "lz4flex_set_tuning(compress_mode)")
 
 
 def get_maximum_output_size(input_len):
@@ -257,97 +261,126 @@ def decompress_size_prepended_with_dict(input, ext_dict):
     return bytes(out[:r])
 
 
-# ---- batched entry points (host numpy arrays) -----------------------------------------------------
+# ---- batched entry points -------------------------------------------------------------------------
+# Every batched entry of the C ABI has one shape:
+#     name(ctx, in_base, in_off, in_len, [flags,] n, <what is particular to it>, out_len, status, [detail,] <more of that>, mem_kind, stream)
+# The host forms (numpy arrays in, numpy arrays out) are one _host_call each; the device forms (torch tensors) share _device_args and
+# _device_call, the three that compress into slots of the maximum output size _compress_slots_device, the three that decode blocks of
+# unknown sizes _size_then_decode_device.  A form keeps its docstring, what is particular to it, and its return.
+NO_DICT = 0xFFFFFFFF     # the dict_id of a block without a dictionary (lz4flex_dict_set_*, lz4flex_*_batch_dict_set)
+SIZE_MODES = {"prepended": L.SIZES_PREPENDED, "given": L.SIZES_GIVEN, "scan": L.SIZES_SCAN}     # lz4flex_decompress_batch_packed
+
+
+def _host_u8(b):
+    return b if isinstance(b, np.ndarray) else np.ascontiguousarray(np.frombuffer(memoryview(b), dtype=np.uint8))
+
+
 def _np(a, dt):
-    a = np.ascontiguousarray(a, dtype=dt)
-    return a, C.c_void_p(a.ctypes.data if a.size else 0)
+    return np.ascontiguousarray(a, dtype=dt)
 
 
-def compress_batch(in_buf, in_off, in_len, out_buf, out_off, out_cap, flags=None, ctx=None):
-    """lz4flex_compress_batch over host buffers: returns (out_len[u32], status[i32])."""
-    lib = L.load()
+def _u32(a):
+    return None if a is None else _np(a, np.uint32)
+
+
+def _arg(a):
+    """one argument as ctypes takes it: a numpy array or a torch tensor by its address (NULL when it is empty), a DictSet by its handle,
+    anything else as it is"""
+    if isinstance(a, np.ndarray):
+        return C.c_void_p(a.ctypes.data) if a.size else None
+    if hasattr(a, "data_ptr"):
+        return C.c_void_p(a.data_ptr()) if a.numel() else None
+    return a.handle if isinstance(a, DictSet) else a
+
+
+def _host_call(name, ctx, in_buf, in_off, in_len, out=None, before_n=(), middle=(), tail=(), detail=False, len_dtype=np.uint32,
+               mem_kind=L.MEM_HOST):
+    """The host marshaller:
+        name(ctx, in_base, in_off, in_len, *before_n, n, *middle, [out_base, out_off, out_cap,] out_len, status, [detail,] *tail, mem_kind, NULL)
+    in_buf is bytes-like or a uint8 array, in_off / in_len and `out` = (out_buf, out_off, out_cap) anything numpy converts; before_n,
+    middle and tail hold what is particular to the entry, each as _arg takes it.  Returns the arrays the call wrote: (out_len[len_dtype],
+    status[i32]) and, with `detail`, detail[n, 2] u64."""
     n = len(in_off)
-    in_buf = np.ascontiguousarray(np.frombuffer(memoryview(in_buf), dtype=np.uint8)) if not isinstance(in_buf, np.ndarray) else in_buf
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    fl, flp = (None, None) if flags is None else _np(flags, np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    rc = lib.lz4flex_compress_batch(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, flp, n,
-                                    C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                    C.c_void_p(status.ctypes.data), L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_compress_batch failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status
+    results = [np.zeros(n, dtype=len_dtype), np.zeros(n, dtype=np.int32)] + ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
+    slots = [] if out is None else [out[0], _np(out[1], np.uint64), _np(out[2], np.uint32)]
+    args = [_host_u8(in_buf), _np(in_off, np.uint64), _np(in_len, np.uint32), *before_n, n, *middle, *slots, *results, *tail]
+    _check(getattr(L.load(), name)(ctx, *map(_arg, args), mem_kind, None), name)
+    return tuple(results)
 
 
-def decompress_batch(in_buf, in_off, in_len, out_buf, out_off, out_cap, ctx=None):
-    """lz4flex_decompress_batch over host buffers: returns (out_len[u32], status[i32], detail[n,2] u64)."""
-    lib = L.load()
-    n = len(in_off)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    detail = np.zeros((n, 2), dtype=np.uint64)
-    rc = lib.lz4flex_decompress_batch(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
-                                      C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                      C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status, detail
+def _host_dict_ext(ext_type, dict_buf, dict_off, dict_len):
+    """the ext structure of per-block dictionaries, and the arrays it points into (to keep until the call returns)"""
+    keep = [_host_u8(dict_buf), _np(dict_off, np.uint64), _np(dict_len, np.uint32)]
+    if not keep[0].size:
+        keep[0] = np.zeros(1, dtype=np.uint8)     # (an empty dictionary buffer still needs an address: NULL would mean "no dictionaries")
+    return ext_type(*(a.ctypes.data if a.size else None for a in keep)), keep
 
 
-def decompressed_size_batch(in_buf, in_off, in_len, history=None, ctx=None):
-    """lz4flex_decompressed_size_batch over host buffers: for raw blocks without their sizes, (size[u64], status[i32]) -- the bytes
-    decompress_into would produce with an unbounded sink and history[i] (None: 0) bytes in front of the block, or its error code (size
-    0).  Nothing is decoded."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = np.ascontiguousarray(np.frombuffer(memoryview(in_buf), dtype=np.uint8)) if not isinstance(in_buf, np.ndarray) else in_buf
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    hi, hip = (None, None) if history is None else _np(history, np.uint32)
-    size = np.zeros(n, dtype=np.uint64)
-    status = np.zeros(n, dtype=np.int32)
-    rc = lib.lz4flex_decompressed_size_batch(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, hip,
-                                             C.c_void_p(size.ctypes.data), C.c_void_p(status.ctypes.data), L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
-    return size, status
+def _host_ids(dict_id, n):
+    ids = _np(dict_id, np.uint32)
+    if len(ids) != n:
+        raise ValueError("in_off and dict_id differ in length")
+    return ids
 
 
-def decompress_blocks_device(src, in_off, in_len, stream=None):
-    """Raw blocks in device memory, sizes unknown: src is a uint8 torch tensor on the GPU, in_off / in_len integer tensors (block i is
-    src[in_off[i] : in_off[i] + in_len[i]]).  The size pass, an exclusive prefix sum for the output offsets, ONE host synchronisation (the
-    total, to allocate exactly that), one lz4flex_decompress_batch with out_cap = the sizes.  Returns (out, out_off, out_len, status) as
-    device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and an empty slot.
-    A block of more than 4 GiB - 1 decompressed bytes (the decoders' u32 out_cap) raises ValueError."""
+def _device_args(src, in_off, in_len, stream, wide_len=False, **companions):
+    """The device prologue: src (and every companion, by its parameter's name) is a contiguous uint8 tensor on one GPU, in_off / in_len
+    have one length.  Returns (device, n, in_off as int64, in_len as int32 -- wide_len: int64 --, the stream's pointer; default: the
+    current stream)."""
     import torch
-    lib = L.load()
     dev = src.device
     if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
         raise ValueError("src must be a contiguous uint8 tensor on the GPU")
+    for name, t in companions.items():
+        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
     n = int(in_off.numel())
     if int(in_len.numel()) != n:
         raise ValueError("in_off and in_len differ in length")
-    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
-    d_len = in_len.to(device=dev, dtype=torch.int32).contiguous()
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    return (dev, n, in_off.to(device=dev, dtype=torch.int64).contiguous(),
+            in_len.to(device=dev, dtype=torch.int64 if wide_len else torch.int32).contiguous(), C.c_void_p(stream))
+
+
+def _device_call(name, head, n, rest, big_blocks, stream_ptr, ctx=None):
+    """name(ctx, *head, n, *rest, MEM_DEVICE [| MEM_BIG_BLOCKS], stream), every argument as _arg takes it"""
+    mem_kind = L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if big_blocks else 0)
+    _check(getattr(L.load(), name)(ctx, *map(_arg, head), n, *map(_arg, rest), mem_kind, stream_ptr), name)
+
+
+def _compress_slots_device(name, src, in_off, in_len, stream, before_n=(), after_n=(), tail=(), **companions):
+    """The device compress recipe: one
+        name(NULL, src, in_off, in_len, *before_n, n, *after_n, out, out_off, out_cap, out_len, status, *tail, mem_kind, stream)
+    into slots of get_maximum_output_size(in_len[i]) bytes, asynchronous on `stream`.  Returns (out, out_off, out_len, status)."""
+    import torch
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream, wide_len=True, **companions)
+    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
+    out_off = torch.cumsum(cap64, 0) - cap64
+    total = int(cap64.sum()) if n else 0
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0], out_off, out_len, status
+    _device_call(name, [src, d_off, d_len.to(torch.int32), *before_n], n, [*after_n, out, out_off, cap64.to(torch.int32), out_len, status, *tail],
+                 int(d_len.max()) > 65536, sp)
+    return out[:total], out_off, out_len, status
+
+
+def _size_then_decode_device(name, src, in_off, in_len, stream, history=None, after_n=(), tail=(), decoder_wins=None, **companions):
+    """The device decode recipe for raw blocks of unknown sizes: the size pass (history: an int32 tensor of the bytes in front of each
+    block, or None), an exclusive prefix sum for the output offsets, ONE host synchronisation (the total, to allocate exactly that), one
+        name(NULL, src, in_off, in_len, n, *after_n, out, out_off, out_cap = the sizes, out_len, status, NULL, *tail, mem_kind, stream)
+    A block the size pass rejected keeps that status, unless the decoder's is `decoder_wins`; a block that fails has an empty slot.
+    Returns (out, out_off, out_len, status)."""
+    import torch
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream, **companions)
     size = torch.empty(n, dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     if n == 0:
         return torch.empty(0, dtype=torch.uint8, device=dev), size, torch.empty(0, dtype=torch.int32, device=dev), status
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    sp = C.c_void_p(stream)
-    rc = lib.lz4flex_decompressed_size_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                             None, C.c_void_p(size.data_ptr()), C.c_void_p(status.data_ptr()), L.MEM_DEVICE, sp)
-    if rc:
-        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
+    _device_call("lz4flex_decompressed_size_batch", [src, d_off, d_len], n, [history, size, status], False, sp)
     incl = torch.cumsum(size, 0)
     out_off = incl - size
     total, biggest = (int(v) for v in torch.stack([incl[-1], size.max()]).cpu())     # the one synchronisation
@@ -357,75 +390,58 @@ def decompress_blocks_device(src, in_off, in_len, stream=None):
     cap = size.to(torch.int32)       # (the bit pattern of a u32 <= 0xFFFFFFFF)
     out_len = torch.zeros(n, dtype=torch.int32, device=dev)
     st2 = torch.empty(n, dtype=torch.int32, device=dev)
-    rc = lib.lz4flex_decompress_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                      C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
-                                      C.c_void_p(out_len.data_ptr()), C.c_void_p(st2.data_ptr()), None,
-                                      L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if biggest > 131072 else 0), sp)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch failed (%d): %s" % (rc, L.last_error()))
-    # a block the size pass rejected keeps its status; the decoder's is the one of every other block (0 by the size pass's contract)
-    status = torch.where(status != 0, status, st2)
+    _device_call(name, [src, d_off, d_len], n, [*after_n, out, out_off, cap, out_len, st2, None, *tail], biggest > 131072, sp)
+    # (the decoder's status is the one of every block the size pass accepted: 0 by the size pass's contract)
+    rejected = status != 0 if decoder_wins is None else (status != 0) & (st2 != decoder_wins)
+    status = torch.where(rejected, status, st2)
     out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
     return out[:total], out_off, out_len, status
 
 
-def _host_u8(b):
-    return np.ascontiguousarray(np.frombuffer(memoryview(b), dtype=np.uint8)) if not isinstance(b, np.ndarray) else b
+# ---- plain batches ------------------------------------------------------------------------------------------------------------
+def compress_batch(in_buf, in_off, in_len, out_buf, out_off, out_cap, flags=None, ctx=None):
+    """lz4flex_compress_batch over host buffers: returns (out_len[u32], status[i32])."""
+    return _host_call("lz4flex_compress_batch", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), before_n=[_u32(flags)])
 
 
+def decompress_batch(in_buf, in_off, in_len, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_decompress_batch over host buffers: returns (out_len[u32], status[i32], detail[n,2] u64)."""
+    return _host_call("lz4flex_decompress_batch", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), detail=True)
+
+
+def decompressed_size_batch(in_buf, in_off, in_len, history=None, ctx=None):
+    """lz4flex_decompressed_size_batch over host buffers: for raw blocks without their sizes, (size[u64], status[i32]) -- the bytes
+    decompress_into would produce with an unbounded sink and history[i] (None: 0) bytes in front of the block, or its error code (size
+    0).  Nothing is decoded."""
+    return _host_call("lz4flex_decompressed_size_batch", ctx, in_buf, in_off, in_len, middle=[_u32(history)], len_dtype=np.uint64)
+
+
+def decompress_blocks_device(src, in_off, in_len, stream=None):
+    """Raw blocks in device memory, sizes unknown: src is a uint8 torch tensor on the GPU, in_off / in_len integer tensors (block i is
+    src[in_off[i] : in_off[i] + in_len[i]]).  The size pass, an exclusive prefix sum for the output offsets, ONE host synchronisation (the
+    total, to allocate exactly that), one lz4flex_decompress_batch with out_cap = the sizes.  Returns (out, out_off, out_len, status) as
+    device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and an empty slot.
+    A block of more than 4 GiB - 1 decompressed bytes (the decoders' u32 out_cap) raises ValueError."""
+    return _size_then_decode_device("lz4flex_decompress_batch", src, in_off, in_len, stream)
+
+
+# ---- per-block dictionaries (lz4flex_*_batch_ex) --------------------------------------------------------------------------------
 def compress_batch_with_dict(in_buf, in_off, in_len, dict_buf, dict_off, dict_len, out_buf, out_off, out_cap, flags=None, ctx=None):
     """lz4flex_compress_batch_ex over host buffers: block i = in_buf[in_off[i] : + in_len[i]] compressed against the dictionary
     dict_buf[dict_off[i] : + dict_len[i]] (dict_len[i] == 0: none) into out_buf[out_off[i] : + out_cap[i]] -- block::compress_into_with_dict
     as a batch.  compress_mode exact gives the reference's bytes; fast (the default) the throughput encoder's, which use the dictionary's
     last 32 KiB.  Returns (out_len[u32], status[i32])."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
-    dict_buf = _host_u8(dict_buf)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    do, dop = _np(dict_off, np.uint64)
-    dl, dlp = _np(dict_len, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    fl, flp = (None, None) if flags is None else _np(flags, np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    # (an empty dictionary buffer still needs an address: NULL would mean "no dictionaries" for the whole batch)
-    keep = dict_buf if dict_buf.size else np.zeros(1, dtype=np.uint8)
-    ext = L.CompressExt(keep.ctypes.data, dop.value, dlp.value)
-    rc = lib.lz4flex_compress_batch_ex(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, flp, n,
-                                       C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                       C.c_void_p(status.ctypes.data), C.byref(ext), L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_ex failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status
+    ext, _keep = _host_dict_ext(L.CompressExt, dict_buf, dict_off, dict_len)
+    return _host_call("lz4flex_compress_batch_ex", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), before_n=[_u32(flags)],
+                      tail=[C.byref(ext)])
 
 
 def decompress_batch_with_dict(in_buf, in_off, in_len, dict_buf, dict_off, dict_len, out_buf, out_off, out_cap, ctx=None):
     """lz4flex_decompress_batch_ex with per-block dictionaries over host buffers (block::decompress_into_with_dict as a batch):
     returns (out_len[u32], status[i32], detail[n,2] u64)."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
-    dict_buf = _host_u8(dict_buf)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    do, dop = _np(dict_off, np.uint64)
-    dl, dlp = _np(dict_len, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    detail = np.zeros((n, 2), dtype=np.uint64)
-    keep = dict_buf if dict_buf.size else np.zeros(1, dtype=np.uint8)
-    ext = L.DecompressExt(keep.ctypes.data, dop.value, dlp.value, None, None, 0)
-    rc = lib.lz4flex_decompress_batch_ex(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
-                                         C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                         C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), C.byref(ext), L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_ex failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status, detail
+    ext, _keep = _host_dict_ext(L.DecompressExt, dict_buf, dict_off, dict_len)     # (no out_pos, no chains)
+    return _host_call("lz4flex_decompress_batch_ex", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), tail=[C.byref(ext)],
+                      detail=True)
 
 
 def compress_blocks_with_dict_device(src, in_off, in_len, dicts, dict_off, dict_len, stream=None):
@@ -434,66 +450,24 @@ def compress_blocks_with_dict_device(src, in_off, in_len, dicts, dict_off, dict_
     default the current one) into output slots of get_maximum_output_size(in_len[i]) bytes.  Returns (out, out_off, out_len, status) as
     device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
     import torch
-    lib = L.load()
-    dev = src.device
-    for t, name in ((src, "src"), (dicts, "dicts")):
-        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
-    if dev.type != "cuda":
-        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
     n = int(in_off.numel())
-    if int(in_len.numel()) != n or int(dict_off.numel()) != n or int(dict_len.numel()) != n:
+    if int(dict_off.numel()) != n or int(dict_len.numel()) != n:
         raise ValueError("in_off, in_len, dict_off and dict_len differ in length")
-    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
-    d_len = in_len.to(device=dev, dtype=torch.int64)
-    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
-    out_off = torch.cumsum(cap64, 0) - cap64
-    total = int(cap64.sum()) if n else 0
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    in_len32 = d_len.to(torch.int32)
-    cap = cap64.to(torch.int32)
-    k_off = dict_off.to(device=dev, dtype=torch.int64).contiguous()
-    k_len = dict_len.to(device=dev, dtype=torch.int32).contiguous()
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return out[:0], out_off, out_len, status
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    dict_ptr = dicts.data_ptr() if dicts.numel() else out.data_ptr()     # (not NULL: NULL would mean "no dictionaries")
-    ext = L.CompressExt(dict_ptr, k_off.data_ptr(), k_len.data_ptr())
-    big = L.MEM_BIG_BLOCKS if int(d_len.max()) > 65536 else 0
-    rc = lib.lz4flex_compress_batch_ex(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(in_len32.data_ptr()),
-                                       None, n, C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
-                                       C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()), C.byref(ext),
-                                       L.MEM_DEVICE | big, C.c_void_p(stream))
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_ex failed (%d): %s" % (rc, L.last_error()))
-    return out[:total], out_off, out_len, status
+    k_off = dict_off.to(device=src.device, dtype=torch.int64).contiguous()
+    k_len = dict_len.to(device=src.device, dtype=torch.int32).contiguous()
+    # (dict_base is not NULL, which would mean "no dictionaries": without dictionary bytes every dict_len is 0 and the address is not read)
+    ext = L.CompressExt((dicts if dicts.numel() else k_len).data_ptr(), k_off.data_ptr(), k_len.data_ptr())
+    return _compress_slots_device("lz4flex_compress_batch_ex", src, in_off, in_len, stream, before_n=[None], tail=[C.byref(ext)], dicts=dicts)
 
 
+# ---- one dictionary for the batch (lz4flex_*_batch_shared_dict) ----------------------------------------------------------------
 def compress_batch_with_shared_dict(in_buf, in_off, in_len, dictionary, out_buf, out_off, out_cap, ctx=None):
     """lz4flex_compress_batch_shared_dict over host buffers: every block in_buf[in_off[i] : + in_len[i]] is compressed against the ONE
     `dictionary` (bytes-like or a uint8 array) into out_buf[out_off[i] : + out_cap[i]] -- the bytes of compress_batch_with_dict with
     that dictionary for every block, with the work that depends on the dictionary alone done once per call.  Returns (out_len[u32],
     status[i32])."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
     d = _host_u8(dictionary)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    rc = lib.lz4flex_compress_batch_shared_dict(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
-                                                C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                                C.c_void_p(status.ctypes.data), C.c_void_p(d.ctypes.data if d.size else 0), int(d.size),
-                                                L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status
+    return _host_call("lz4flex_compress_batch_shared_dict", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), tail=[d, int(d.size)])
 
 
 def compress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, stream=None):
@@ -501,64 +475,17 @@ def compress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, str
     src[in_off[i] : + in_len[i]].  One lz4flex_compress_batch_shared_dict (MEM_DEVICE, asynchronous on `stream`, default the current
     one) into output slots of get_maximum_output_size(in_len[i]) bytes.  Returns (out, out_off, out_len, status) as device tensors:
     block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
-    import torch
-    lib = L.load()
-    dev = src.device
-    for t, name in ((src, "src"), (dictionary, "dictionary")):
-        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
-    if dev.type != "cuda":
-        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
-    n = int(in_off.numel())
-    if int(in_len.numel()) != n:
-        raise ValueError("in_off and in_len differ in length")
-    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
-    d_len = in_len.to(device=dev, dtype=torch.int64)
-    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
-    out_off = torch.cumsum(cap64, 0) - cap64
-    total = int(cap64.sum()) if n else 0
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    in_len32 = d_len.to(torch.int32)
-    cap = cap64.to(torch.int32)
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return out[:0], out_off, out_len, status
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    big = L.MEM_BIG_BLOCKS if int(d_len.max()) > 65536 else 0
-    rc = lib.lz4flex_compress_batch_shared_dict(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(in_len32.data_ptr()),
-                                                n, C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
-                                                C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()),
-                                                C.c_void_p(dictionary.data_ptr() if dictionary.numel() else 0), int(dictionary.numel()),
-                                                L.MEM_DEVICE | big, C.c_void_p(stream))
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
-    return out[:total], out_off, out_len, status
+    return _compress_slots_device("lz4flex_compress_batch_shared_dict", src, in_off, in_len, stream,
+                                  tail=[dictionary, int(dictionary.numel())], dictionary=dictionary)
 
 
 def decompress_batch_with_shared_dict(in_buf, in_off, in_len, dictionary, out_buf, out_off, out_cap, ctx=None):
     """lz4flex_decompress_batch_shared_dict over host buffers: every block in_buf[in_off[i] : + in_len[i]] is decoded against the ONE
     `dictionary` (bytes-like or a uint8 array) into out_buf[out_off[i] : + out_cap[i]] -- the results of decompress_batch_with_dict with
     that dictionary for every block.  Returns (out_len[u32], status[i32], detail[n,2] u64)."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
     d = _host_u8(dictionary)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    detail = np.zeros((n, 2), dtype=np.uint64)
-    rc = lib.lz4flex_decompress_batch_shared_dict(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n,
-                                                  C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                                  C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data),
-                                                  C.c_void_p(d.ctypes.data if d.size else 0), int(d.size), L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status, detail
+    return _host_call("lz4flex_decompress_batch_shared_dict", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap),
+                      tail=[d, int(d.size)], detail=True)
 
 
 def decompress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, stream=None):
@@ -568,58 +495,13 @@ def decompress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, s
     lz4flex_decompress_batch_shared_dict with out_cap = the sizes.  Returns (out, out_off, out_len, status) as device tensors: block i's
     bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and an empty slot."""
     import torch
-    lib = L.load()
-    dev = src.device
-    for t, name in ((src, "src"), (dictionary, "dictionary")):
-        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous uint8 tensor on the GPU of src" % name)
-    if dev.type != "cuda":
-        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
-    n = int(in_off.numel())
-    if int(in_len.numel()) != n:
-        raise ValueError("in_off and in_len differ in length")
     dlen = int(dictionary.numel())
-    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
-    d_len = in_len.to(device=dev, dtype=torch.int32).contiguous()
-    size = torch.empty(n, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return torch.empty(0, dtype=torch.uint8, device=dev), size, torch.empty(0, dtype=torch.int32, device=dev), status
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    sp = C.c_void_p(stream)
-    hist = torch.full((n,), dlen, dtype=torch.int64, device=dev).to(torch.int32)     # (the bit pattern of a u32)
-    rc = lib.lz4flex_decompressed_size_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                             C.c_void_p(hist.data_ptr()), C.c_void_p(size.data_ptr()), C.c_void_p(status.data_ptr()),
-                                             L.MEM_DEVICE, sp)
-    if rc:
-        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
-    incl = torch.cumsum(size, 0)
-    out_off = incl - size
-    total, biggest = (int(v) for v in torch.stack([incl[-1], size.max()]).cpu())     # the one synchronisation
-    if biggest > 0xFFFFFFFF:
-        raise ValueError("a block decompresses to %d bytes: more than the decoders' u32 out_cap" % biggest)
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    cap = size.to(torch.int32)       # (the bit pattern of a u32 <= 0xFFFFFFFF)
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    st2 = torch.empty(n, dtype=torch.int32, device=dev)
-    rc = lib.lz4flex_decompress_batch_shared_dict(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()), C.c_void_p(cap.data_ptr()),
-                                                  C.c_void_p(out_len.data_ptr()), C.c_void_p(st2.data_ptr()), None,
-                                                  C.c_void_p(dictionary.data_ptr() if dlen else 0), dlen,
-                                                  L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if biggest > 131072 else 0), sp)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_shared_dict failed (%d): %s" % (rc, L.last_error()))
-    # a block the size pass rejected keeps its status; the decoder's is the one of every other block (0 by the size pass's contract)
-    status = torch.where(status != 0, status, st2)
-    out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
-    return out[:total], out_off, out_len, status
+    hist = torch.full((int(in_off.numel()),), dlen, dtype=torch.int64, device=src.device).to(torch.int32)     # (the bit pattern of a u32)
+    return _size_then_decode_device("lz4flex_decompress_batch_shared_dict", src, in_off, in_len, stream, history=hist,
+                                    tail=[dictionary, dlen], dictionary=dictionary)
 
 
 # ---- dictionary sets: K prepared dictionaries, one id per block (lz4flex_dict_set_*, lz4flex_*_batch_dict_set) -------------
-NO_DICT = 0xFFFFFFFF     # the dict_id of a block without a dictionary
-
-
 class DictSet:
     """lz4flex_dict_set: `dictionaries` (a sequence of bytes-like objects or uint8 arrays; an empty one means "no dictionary" for its
     id) copied to the device and digested once, reused by every compress_batch_with_dict_set / decompress_batch_with_dict_set call
@@ -635,10 +517,8 @@ class DictSet:
         if len(parts):
             offs[1:] = np.cumsum(self.lengths[:-1], dtype=np.uint64)
         flat = np.concatenate(parts) if len(parts) and int(self.lengths.sum()) else np.zeros(1, dtype=np.uint8)
-        rc = self._lib.lz4flex_dict_set_create(ctx, C.c_void_p(flat.ctypes.data), C.c_void_p(offs.ctypes.data),
-                                               C.c_void_p(self.lengths.ctypes.data), len(parts), L.MEM_HOST, C.byref(self._h))
-        if rc:
-            raise DeviceError("lz4flex_dict_set_create failed (%d): %s" % (rc, L.last_error()))
+        _check(self._lib.lz4flex_dict_set_create(ctx, _arg(flat), _arg(offs), _arg(self.lengths), len(parts), L.MEM_HOST, C.byref(self._h)),
+               "lz4flex_dict_set_create")
 
     @property
     def handle(self):
@@ -671,53 +551,19 @@ def compress_batch_with_dict_set(in_buf, in_off, in_len, dict_id, dict_set, out_
     """lz4flex_compress_batch_dict_set over host buffers: block in_buf[in_off[i] : + in_len[i]] is compressed against dictionary
     dict_id[i] of `dict_set` (NO_DICT: none) into out_buf[out_off[i] : + out_cap[i]] -- the bytes of compress_batch_with_dict with that
     dictionary per block; only the batch and the ids travel to the device.  Returns (out_len[u32], status[i32])."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    di, dip = _np(dict_id, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    if len(di) != n:
-        raise ValueError("in_off and dict_id differ in length")
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    rc = lib.lz4flex_compress_batch_dict_set(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, dip,
-                                             C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                             C.c_void_p(status.ctypes.data), dict_set.handle, L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status
+    return _host_call("lz4flex_compress_batch_dict_set", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap),
+                      middle=[_host_ids(dict_id, len(in_off))], tail=[dict_set])
 
 
 def decompress_batch_with_dict_set(in_buf, in_off, in_len, dict_id, dict_set, out_buf, out_off, out_cap, ctx=None):
     """lz4flex_decompress_batch_dict_set over host buffers: the mirror of compress_batch_with_dict_set -- the results of
     decompress_batch_with_dict with dictionary dict_id[i] per block.  Returns (out_len[u32], status[i32], detail[n,2] u64)."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    di, dip = _np(dict_id, np.uint32)
-    oo, oop = _np(out_off, np.uint64)
-    oc, ocp = _np(out_cap, np.uint32)
-    if len(di) != n:
-        raise ValueError("in_off and dict_id differ in length")
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    detail = np.zeros((n, 2), dtype=np.uint64)
-    rc = lib.lz4flex_decompress_batch_dict_set(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, dip,
-                                               C.c_void_p(out_buf.ctypes.data), oop, ocp, C.c_void_p(out_len.ctypes.data),
-                                               C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), dict_set.handle,
-                                               L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
-    return out_len, status, detail
+    return _host_call("lz4flex_decompress_batch_dict_set", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap),
+                      middle=[_host_ids(dict_id, len(in_off))], tail=[dict_set], detail=True)
 
 
 def _device_ids(dict_id, n, dev):
-    """dict_id as the int32 bit pattern of n u32 on dev"""
+    """dict_id as n int64 on dev, and as the int32 bit pattern of n u32"""
     import torch
     if int(dict_id.numel()) != n:
         raise ValueError("in_off and dict_id differ in length")
@@ -730,37 +576,8 @@ def compress_blocks_with_dict_set_device(src, in_off, in_len, dict_id, dict_set,
     its dictionary dict_id[i] (NO_DICT: none).  One lz4flex_compress_batch_dict_set (MEM_DEVICE, asynchronous on `stream`, default the
     current one) into output slots of get_maximum_output_size(in_len[i]) bytes.  Returns (out, out_off, out_len, status) as device
     tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
-    import torch
-    lib = L.load()
-    dev = src.device
-    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
-        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
-    n = int(in_off.numel())
-    if int(in_len.numel()) != n:
-        raise ValueError("in_off and in_len differ in length")
-    _, ids = _device_ids(dict_id, n, dev)
-    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
-    d_len = in_len.to(device=dev, dtype=torch.int64)
-    cap64 = 20 + d_len * 110 // 100                      # get_maximum_output_size, compress.rs:588-590
-    out_off = torch.cumsum(cap64, 0) - cap64
-    total = int(cap64.sum()) if n else 0
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    in_len32 = d_len.to(torch.int32)
-    cap = cap64.to(torch.int32)
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return out[:0], out_off, out_len, status
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    big = L.MEM_BIG_BLOCKS if int(d_len.max()) > 65536 else 0
-    rc = lib.lz4flex_compress_batch_dict_set(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(in_len32.data_ptr()),
-                                             n, C.c_void_p(ids.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()),
-                                             C.c_void_p(cap.data_ptr()), C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()),
-                                             dict_set.handle, L.MEM_DEVICE | big, C.c_void_p(stream))
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
-    return out[:total], out_off, out_len, status
+    _, ids = _device_ids(dict_id, int(in_off.numel()), src.device)
+    return _compress_slots_device("lz4flex_compress_batch_dict_set", src, in_off, in_len, stream, after_n=[ids], tail=[dict_set])
 
 
 def decompress_blocks_with_dict_set_device(src, in_off, in_len, dict_id, dict_set, stream=None):
@@ -769,57 +586,19 @@ def decompress_blocks_with_dict_set_device(src, in_off, in_len, dict_id, dict_se
     total, to allocate exactly that), one lz4flex_decompress_batch_dict_set with out_cap = the sizes.  Returns (out, out_off, out_len,
     status) as device tensors; a block that fails gets its status and an empty slot (an id the set does not have: INVALID_ARG)."""
     import torch
-    lib = L.load()
-    dev = src.device
-    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
-        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
-    n = int(in_off.numel())
-    if int(in_len.numel()) != n:
-        raise ValueError("in_off and in_len differ in length")
+    n, dev, hist = int(in_off.numel()), src.device, None
     ids64, ids = _device_ids(dict_id, n, dev)
-    d_off = in_off.to(device=dev, dtype=torch.int64).contiguous()
-    d_len = in_len.to(device=dev, dtype=torch.int32).contiguous()
-    size = torch.empty(n, dtype=torch.int64, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return torch.empty(0, dtype=torch.uint8, device=dev), size, torch.empty(0, dtype=torch.int32, device=dev), status
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    sp = C.c_void_p(stream)
-    # (an id without a dictionary -- NO_DICT, or one the set does not have: the decoder refuses that block -- has no history)
-    lens = torch.cat([torch.from_numpy(dict_set.lengths.astype(np.int64)), torch.zeros(1, dtype=torch.int64)]).to(dev)
-    k = len(dict_set)
-    hist = lens[torch.where(ids64 < k, ids64, torch.full_like(ids64, k))].to(torch.int32)     # (the bit pattern of a u32)
-    rc = lib.lz4flex_decompressed_size_batch(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                             C.c_void_p(hist.data_ptr()), C.c_void_p(size.data_ptr()), C.c_void_p(status.data_ptr()),
-                                             L.MEM_DEVICE, sp)
-    if rc:
-        raise DeviceError("lz4flex_decompressed_size_batch failed (%d): %s" % (rc, L.last_error()))
-    incl = torch.cumsum(size, 0)
-    out_off = incl - size
-    total, biggest = (int(v) for v in torch.stack([incl[-1], size.max()]).cpu())     # the one synchronisation
-    if biggest > 0xFFFFFFFF:
-        raise ValueError("a block decompresses to %d bytes: more than the decoders' u32 out_cap" % biggest)
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    cap = size.to(torch.int32)       # (the bit pattern of a u32 <= 0xFFFFFFFF)
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    st2 = torch.empty(n, dtype=torch.int32, device=dev)
-    rc = lib.lz4flex_decompress_batch_dict_set(None, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                               C.c_void_p(ids.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(out_off.data_ptr()),
-                                               C.c_void_p(cap.data_ptr()), C.c_void_p(out_len.data_ptr()), C.c_void_p(st2.data_ptr()), None,
-                                               dict_set.handle, L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if biggest > 131072 else 0), sp)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_dict_set failed (%d): %s" % (rc, L.last_error()))
-    # a refused id is the decoder's to report; otherwise a block the size pass rejected keeps that status
-    status = torch.where((status != 0) & (st2 != L.E_INVALID_ARG), status, st2)
-    out_len = torch.where(status != 0, torch.zeros_like(out_len), out_len)
-    return out[:total], out_off, out_len, status
+    if n:
+        # (an id without a dictionary -- NO_DICT, or one the set does not have: the decoder refuses that block -- has no history)
+        lens = torch.cat([torch.from_numpy(dict_set.lengths.astype(np.int64)), torch.zeros(1, dtype=torch.int64)]).to(dev)
+        k = len(dict_set)
+        hist = lens[torch.where(ids64 < k, ids64, torch.full_like(ids64, k))].to(torch.int32)     # (the bit pattern of a u32)
+    # (a refused id is the decoder's to report)
+    return _size_then_decode_device("lz4flex_decompress_batch_dict_set", src, in_off, in_len, stream, history=hist, after_n=[ids],
+                                    tail=[dict_set], decoder_wins=L.E_INVALID_ARG)
 
 
 # ---- packed batches: one output buffer, the offsets computed on the device (lz4flex_*_batch_packed) ------------------------
-SIZE_MODES = {"prepended": L.SIZES_PREPENDED, "given": L.SIZES_GIVEN, "scan": L.SIZES_SCAN}
-
-
 def decompress_batch_packed(in_buf, in_off, in_len, out_buf, size_mode="prepended", sizes=None, align=1, total_cap=None, big_blocks=False,
                             ctx=None):
     """lz4flex_decompress_batch_packed over host buffers: block i = in_buf[in_off[i] : + in_len[i]] is decoded into out_buf, slot behind
@@ -828,60 +607,34 @@ def decompress_batch_packed(in_buf, in_off, in_len, out_buf, size_mode="prepende
     out_buf) bounds what is written; a block whose slot ends behind it gets OutputTooSmall.  Returns (out_off[u64, n + 1], out_cap[u32],
     out_len[u32], status[i32], detail[n, 2] u64): block i's bytes are out_buf[out_off[i] : out_off[i] + out_len[i]], out_off[n] is the
     capacity the batch needs."""
-    lib = L.load()
     n = len(in_off)
-    in_buf = _host_u8(in_buf)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
-    sz, szp = (None, None) if sizes is None else _np(sizes, np.uint32)
-    out_off = np.zeros(n + 1, dtype=np.uint64)
-    out_cap = np.zeros(n, dtype=np.uint32)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
-    detail = np.zeros((n, 2), dtype=np.uint64)
+    out_off, out_cap = np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
     cap = int(out_buf.size) if total_cap is None else int(total_cap)
-    rc = lib.lz4flex_decompress_batch_packed(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, SIZE_MODES[size_mode], szp,
-                                             C.c_void_p(out_buf.ctypes.data if out_buf.size else 0), cap, int(align),
-                                             C.c_void_p(out_off.ctypes.data), C.c_void_p(out_cap.ctypes.data), C.c_void_p(out_len.ctypes.data),
-                                             C.c_void_p(status.ctypes.data), C.c_void_p(detail.ctypes.data), None,
-                                             L.MEM_HOST | (L.MEM_BIG_BLOCKS if big_blocks else 0), None)
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_packed failed (%d): %s" % (rc, L.last_error()))
-    return out_off, out_cap, out_len, status, detail
+    return (out_off, out_cap) + _host_call("lz4flex_decompress_batch_packed", ctx, in_buf, in_off, in_len,
+                                           middle=[SIZE_MODES[size_mode], _u32(sizes), out_buf, cap, int(align), out_off, out_cap], tail=[None],
+                                           detail=True, mem_kind=L.MEM_HOST | (L.MEM_BIG_BLOCKS if big_blocks else 0))
 
 
 def compress_batch_packed(in_buf, in_off, in_len, out_buf, prepend_size=True, align=1, total_cap=None, ctx=None):
     """lz4flex_compress_batch_packed over host buffers: the blocks in_buf[in_off[i] : + in_len[i]] compressed back to back into out_buf
     (prepend_size: each behind its LE u32 length, block::compress_prepend_size).  Returns (out_off[u64, n + 1], out_len[u32],
     status[i32]): block i's bytes are out_buf[out_off[i] : out_off[i] + out_len[i]], out_off[n] is the capacity the stream needs."""
-    lib = L.load()
-    n = len(in_off)
-    in_buf = _host_u8(in_buf)
-    io, iop = _np(in_off, np.uint64)
-    il, ilp = _np(in_len, np.uint32)
+    n, prefix, in_len = len(in_off), 1 if prepend_size else 0, _np(in_len, np.uint32)
     out_off = np.zeros(n + 1, dtype=np.uint64)
-    out_len = np.zeros(n, dtype=np.uint32)
-    status = np.zeros(n, dtype=np.int32)
     cap = int(out_buf.size) if total_cap is None else int(total_cap)
-    slots = int(lib.lz4flex_compress_packed_scratch_bound(int(il.sum(dtype=np.uint64)), n, 1 if prepend_size else 0))
-    rc = lib.lz4flex_compress_batch_packed(ctx, C.c_void_p(in_buf.ctypes.data if in_buf.size else 0), iop, ilp, n, 1 if prepend_size else 0,
-                                           None, slots, C.c_void_p(out_buf.ctypes.data if out_buf.size else 0), cap, int(align),
-                                           C.c_void_p(out_off.ctypes.data), C.c_void_p(out_len.ctypes.data), C.c_void_p(status.ctypes.data),
-                                           None, L.MEM_HOST, None)
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_packed failed (%d): %s" % (rc, L.last_error()))
-    return out_off, out_len, status
+    slots = int(L.load().lz4flex_compress_packed_scratch_bound(int(in_len.sum(dtype=np.uint64)), n, prefix))
+    return (out_off,) + _host_call("lz4flex_compress_batch_packed", ctx, in_buf, in_off, in_len,
+                                   middle=[prefix, None, slots, out_buf, cap, int(align), out_off], tail=[None])
 
 
-def _packed_device_args(src, in_off, in_len):
+def _packed_device_args(src, in_off, in_len, capacity, stream):
+    """what the two packed device forms share: the prologue, and the tensors they return -- out (of max(capacity, 1) bytes), out_off
+    (n + 1), out_len, status"""
     import torch
-    dev = src.device
-    if dev.type != "cuda" or src.dtype != torch.uint8 or not src.is_contiguous():
-        raise ValueError("src must be a contiguous uint8 tensor on the GPU")
-    n = int(in_off.numel())
-    if int(in_len.numel()) != n:
-        raise ValueError("in_off and in_len differ in length")
-    return dev, n, in_off.to(device=dev, dtype=torch.int64).contiguous(), in_len.to(device=dev, dtype=torch.int32).contiguous()
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
+    return dev, n, d_off, d_len, sp, (torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev),
+                                      torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+                                      torch.zeros(n, dtype=torch.int32, device=dev))
 
 
 def decompress_blocks_packed_device(src, in_off, in_len, capacity, size_mode="prepended", sizes=None, align=1, big_blocks=False, stream=None,
@@ -893,28 +646,15 @@ def decompress_blocks_packed_device(src, in_off, in_len, capacity, size_mode="pr
     out_off n + 1 entries (the last one: the capacity the batch needs), block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]; a
     block whose slot ends behind `capacity` has status E_OUTPUT_TOO_SMALL and nothing of it is written."""
     import torch
-    lib = L.load()
-    dev, n, d_off, d_len = _packed_device_args(src, in_off, in_len)
     capacity = int(capacity)
-    out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
-    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    out_cap = torch.empty(n, dtype=torch.int32, device=dev)
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return out[:capacity], out_off, out_len, status
-    d_sizes = None if sizes is None else sizes.to(device=dev, dtype=torch.int64).to(torch.int32).contiguous()
-    work = torch.empty(int(lib.lz4flex_packed_work_size(n)), dtype=torch.uint8, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.lz4flex_decompress_batch_packed(ctx, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                             SIZE_MODES[size_mode], None if d_sizes is None else C.c_void_p(d_sizes.data_ptr()),
-                                             C.c_void_p(out.data_ptr()), capacity, int(align), C.c_void_p(out_off.data_ptr()),
-                                             C.c_void_p(out_cap.data_ptr()), C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()),
-                                             None, C.c_void_p(work.data_ptr()), L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if big_blocks else 0),
-                                             C.c_void_p(stream))
-    if rc:
-        raise DeviceError("lz4flex_decompress_batch_packed failed (%d): %s" % (rc, L.last_error()))
+    dev, n, d_off, d_len, sp, (out, out_off, out_len, status) = _packed_device_args(src, in_off, in_len, capacity, stream)
+    if n:
+        out_cap = torch.empty(n, dtype=torch.int32, device=dev)
+        d_sizes = None if sizes is None else sizes.to(device=dev, dtype=torch.int64).to(torch.int32).contiguous()
+        work = torch.empty(int(L.load().lz4flex_packed_work_size(n)), dtype=torch.uint8, device=dev)
+        _device_call("lz4flex_decompress_batch_packed", [src, d_off, d_len], n,
+                     [SIZE_MODES[size_mode], d_sizes, out, capacity, int(align), out_off, out_cap, out_len, status, None, work],
+                     big_blocks, sp, ctx)
     return out[:capacity], out_off, out_len, status
 
 
@@ -928,26 +668,14 @@ def compress_blocks_packed_device(src, in_off, in_len, capacity, prepend_size=Tr
     (out, out_off, out_len, status) as device tensors: out has `capacity` bytes, out_off n + 1 entries (the last one: the capacity the
     stream needs), block i's bytes are out[out_off[i] : out_off[i] + out_len[i]] -- what decompress_blocks_packed_device reads."""
     import torch
-    lib = L.load()
-    dev, n, d_off, d_len = _packed_device_args(src, in_off, in_len)
-    capacity = int(capacity)
-    out = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
-    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    if n == 0:
-        return out[:capacity], out_off, out_len, status
-    if scratch_cap is None:
-        scratch_cap = int(lib.lz4flex_compress_packed_scratch_bound(int(src.numel()), n, 1 if prepend_size else 0))
-    scratch = torch.empty(max(int(scratch_cap), 1), dtype=torch.uint8, device=dev)
-    work = torch.empty(int(lib.lz4flex_packed_work_size(n)), dtype=torch.uint8, device=dev)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.lz4flex_compress_batch_packed(ctx, C.c_void_p(src.data_ptr()), C.c_void_p(d_off.data_ptr()), C.c_void_p(d_len.data_ptr()), n,
-                                           1 if prepend_size else 0, C.c_void_p(scratch.data_ptr()), int(scratch_cap),
-                                           C.c_void_p(out.data_ptr()), capacity, int(align), C.c_void_p(out_off.data_ptr()),
-                                           C.c_void_p(out_len.data_ptr()), C.c_void_p(status.data_ptr()), C.c_void_p(work.data_ptr()),
-                                           L.MEM_DEVICE | (L.MEM_BIG_BLOCKS if big_blocks else 0), C.c_void_p(stream))
-    if rc:
-        raise DeviceError("lz4flex_compress_batch_packed failed (%d): %s" % (rc, L.last_error()))
+    capacity, prefix = int(capacity), 1 if prepend_size else 0
+    dev, n, d_off, d_len, sp, (out, out_off, out_len, status) = _packed_device_args(src, in_off, in_len, capacity, stream)
+    if n:
+        lib = L.load()
+        if scratch_cap is None:
+            scratch_cap = int(lib.lz4flex_compress_packed_scratch_bound(int(src.numel()), n, prefix))
+        scratch = torch.empty(max(int(scratch_cap), 1), dtype=torch.uint8, device=dev)
+        work = torch.empty(int(lib.lz4flex_packed_work_size(n)), dtype=torch.uint8, device=dev)
+        _device_call("lz4flex_compress_batch_packed", [src, d_off, d_len], n,
+                     [prefix, scratch, int(scratch_cap), out, capacity, int(align), out_off, out_len, status, work], big_blocks, sp, ctx)
     return out[:capacity], out_off, out_len, status
