@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "frame_plan.h"
 #include "host_pin.h"
 #include "xxh32.h"
 
@@ -18,34 +19,20 @@ namespace {
 
 using lz4flex::PinBuf;
 using lz4flex::XxHash32;
+using namespace lz4flex_plan;   // block sizes, BLOCK_UNCOMPRESSED_SIZE_BIT, WINDOW_SIZE, TableOffset, LinkedWindow
 
 // src/frame/header.rs:11-34
 constexpr uint8_t FLG_RESERVED_MASK = 0x02, FLG_VERSION_MASK = 0xC0, FLG_SUPPORTED_VERSION_BITS = 0x40,
                   FLG_INDEPENDENT_BLOCKS = 0x20, FLG_BLOCK_CHECKSUMS = 0x10, FLG_CONTENT_SIZE = 0x08,
                   FLG_CONTENT_CHECKSUM = 0x04, FLG_DICTIONARY_ID = 0x01, BD_BLOCK_SIZE_MASK = 0x70,
                   BD_RESERVED_MASK = 0x8F;
-constexpr uint32_t BLOCK_UNCOMPRESSED_SIZE_BIT = 0x80000000u, LZ4F_MAGIC_NUMBER = 0x184D2204u,
-                   LZ4F_LEGACY_MAGIC_NUMBER = 0x184C2102u;
-constexpr size_t MIN_FRAME_INFO_SIZE = 7, MAX_FRAME_INFO_SIZE = 19, WINDOW_SIZE = 64 * 1024;
+constexpr uint32_t LZ4F_MAGIC_NUMBER = 0x184D2204u, LZ4F_LEGACY_MAGIC_NUMBER = 0x184C2102u;
+constexpr size_t MIN_FRAME_INFO_SIZE = 7, MAX_FRAME_INFO_SIZE = 19;
 
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); }
 void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 void wr64(uint8_t* p, uint64_t v) { wr32(p, (uint32_t)v); wr32(p + 4, (uint32_t)(v >> 32)); }
-
-// BlockSize::get_size, header.rs:68-77
-size_t block_size_bytes(int code) {
-    switch (code) {
-        case 4: return 64u * 1024;
-        case 5: return 256u * 1024;
-        case 6: return 1024u * 1024;
-        case 7: return 4u * 1024 * 1024;
-        case 8: return 8u * 1024 * 1024;
-        default: return 0;
-    }
-}
-// BlockSize::from_buf_length, header.rs:57-67
-int block_size_from_buf_length(size_t n) { return n > 256u * 1024 ? 7 : (n > 64u * 1024 ? 5 : 4); }
 
 }  // namespace
 
@@ -140,22 +127,19 @@ struct lz4flex_frame_encoder {
     size_t batch_bytes = 64u << 20;
     bool batch_auto = true;        // no explicit set_batch_bytes: big blocks get enough blocks per launch to fill the GPU
     uint64_t content_len = 0;
-    uint64_t src_stream_offset = 0;   // mirrors the reference field that decides the table state (N3)
+    TableOffset tbl;               // Independent frame: mirrors the reference field that decides the table state (N3)
     XxHash32 content_hasher{0};
     bool is_frame_open = false, data_to_frame_written = false;
     bool final_write = false;       // lz4flex_frame_compress: the write in progress is the stream's last (finish follows)
     int sticky_err = 0;
     // Linked mode (frame/compress.rs:62-93): the reference's src ring (prefix + ext_dict) expressed in
-    // stream coordinates; the dependent blocks of a batch run as ONE chain on the GPU.
+    // stream coordinates (`win`); the dependent blocks of a batch run as ONE chain on the GPU.
     PinBuf lstage;                      // stream bytes [lbase, lbase + lstage_len)
     size_t lstage_len = 0;
     uint64_t lbase = 0;                 // stream position of lstage[0]
     uint64_t proc_pos = 0;              // stream position of the first byte not yet compressed
     uint64_t frame_start = 0;           // stream position of the current frame's first byte (history never reaches before it)
-    uint64_t vbase = 0;                 // stream position of the reference's src[0]
-    uint64_t v_src_start = 0;           // == src_start == src_end between blocks
-    uint64_t dict_stream = 0;           // stream position of ext_dict[0]
-    uint32_t ext_dict_len = 0;
+    LinkedWindow win;
     std::vector<uint32_t> tbl_state;    // the persistent HashTable4K
     std::vector<lz4flex_chain_block> cblocks;
     bool linked_fast = false;           // Linked frame written with the throughput encoder: blocks parsed independently
@@ -181,9 +165,9 @@ struct lz4flex_frame_encoder {
         int rc = emit(hdr, (size_t)n);
         if (rc) return rc;
         if (content_len != 0) {   // second or later frame of this encoder: reset compressor state
-            content_len = 0; src_stream_offset = 0; src_len = 0;
+            content_len = 0; tbl.so = 0; src_len = 0;
             content_hasher.reset(0);
-            ext_dict_len = 0; v_src_start = 0; vbase = proc_pos;
+            win.reset(proc_pos);
             std::fill(tbl_state.begin(), tbl_state.end(), 0u);
         }
         if (fi.block_mode == 1 && tbl_state.empty()) tbl_state.assign(4096, 0u);
@@ -214,7 +198,6 @@ struct lz4flex_frame_encoder {
     // -- 64 blocks of 64 KiB: one launch of a fraction of a millisecond instead of 64 x 8 ms of chain).  Any LZ4 frame decoder
     // returns the input; JSON, 64 KiB blocks: ratio 0.2216 (the reference's Linked frame 0.2226, independent blocks 0.2307).
     // compress_mode exact keeps the reference's bytes (write_blocks_linked below).
-    static constexpr size_t FAST_HISTORY = 32768;
     int write_blocks_linked_fast(size_t total) {
         const size_t mbs = block_size_bytes(fi.block_size);
         const size_t nblk = (total + mbs - 1) / mbs;
@@ -264,37 +247,12 @@ struct lz4flex_frame_encoder {
         uint64_t pos = proc_pos;
         for (size_t i = 0; i < nblk; i++) {
             const size_t len = std::min(mbs, left);
-            // :266-271 reposition near 2 GiB
-            uint32_t repos = 0;
-            if (src_stream_offset + mbs + WINDOW_SIZE >= (uint64_t)(0xFFFFFFFFu / 2)) {
-                repos = (uint32_t)(src_stream_offset - ext_dict_len);
-                src_stream_offset = ext_dict_len;
-            }
-            const uint64_t v_src_end = v_src_start + len;
             lz4flex_chain_block& b = cblocks[i];
-            b.in_off = vbase - lbase;
-            b.in_len = (uint32_t)v_src_end;
-            b.in_pos = (uint32_t)v_src_start;
-            b.dict_off = ext_dict_len ? dict_stream - lbase : 0;
-            b.dict_len = ext_dict_len;
-            b.so = (uint32_t)src_stream_offset;
-            b.repos = repos;
-            b.flags = 0;
+            b = win.next(mbs, len);                          // (stream positions; the stage starts at lbase)
+            b.in_off -= lbase;
+            if (b.dict_len) b.dict_off -= lbase;
             out_off[i] = i * stride; out_cap[i] = (uint32_t)stride;
             bstart[i] = pos; blen[i] = (uint32_t)len;
-            // :324-356 buffer / offset maintenance
-            v_src_start += len;
-            if (v_src_start >= mbs + WINDOW_SIZE) {
-                dict_stream = vbase + v_src_end - WINDOW_SIZE;
-                ext_dict_len = (uint32_t)WINDOW_SIZE;
-                src_stream_offset += v_src_end;
-                vbase += v_src_end;
-                v_src_start = 0;
-            } else if (v_src_start + ext_dict_len > WINDOW_SIZE) {
-                const uint64_t delta = std::min<uint64_t>(ext_dict_len, v_src_start + ext_dict_len - WINDOW_SIZE);
-                dict_stream += delta;
-                ext_dict_len -= (uint32_t)delta;
-            }
             pos += len; left -= len;
         }
         const uint32_t first = 0, count = (uint32_t)nblk;
@@ -308,7 +266,7 @@ struct lz4flex_frame_encoder {
         }
         proc_pos += total;
         // drop history the window can no longer reach
-        const uint64_t keep_from = ext_dict_len ? std::min(vbase, dict_stream) : vbase;
+        const uint64_t keep_from = win.keep_from();
         if (keep_from > lbase) {
             const size_t drop = (size_t)(keep_from - lbase);
             memmove(lstage.data(), lstage.data() + drop, lstage_len - drop);
@@ -345,16 +303,13 @@ struct lz4flex_frame_encoder {
         if (dst.size() < stride * nblk) dst.resize(stride * nblk);
         in_off.resize(nblk); out_off.resize(nblk); in_len.resize(nblk); out_cap.resize(nblk);
         out_len.resize(nblk); flags.resize(nblk); status.resize(nblk);
-        uint64_t so = src_stream_offset;
+        TableOffset t = tbl;             // (committed below, once the launch and every write went through)
         size_t consumed = 0;
         for (size_t i = 0; i < nblk; i++) {
             const size_t len = std::min(mbs, have - i * mbs);
-            // reposition near 2 GiB (frame/compress.rs:266-271): the table collapses to "all zero, offset 0"
-            if (so + mbs + WINDOW_SIZE >= (uint64_t)(0xFFFFFFFFu / 2)) so = 0;
             in_off[i] = i * mbs; in_len[i] = (uint32_t)len;
             out_off[i] = i * stride; out_cap[i] = (uint32_t)stride;
-            flags[i] = so == 0 ? LZ4FLEX_BLOCK_FRAME_FIRST : LZ4FLEX_BLOCK_FRAME_CONTINUATION;
-            so += len;
+            flags[i] = t.next(mbs, len);
             consumed += len;
         }
         int rc = lz4flex_compress_batch(nullptr, base, in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk,
@@ -365,7 +320,7 @@ struct lz4flex_frame_encoder {
             if (status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
             if ((rc = emit_block(base + in_off[i], in_len[i], dst.data() + out_off[i], out_len[i]))) return rc;
         }
-        src_stream_offset = so;
+        tbl = t;
         if (direct) return 0;
         // keep an unconsumed tail (never happens: callers pass every staged byte or whole blocks)
         if (consumed < src_len) memmove(src.data(), src.data() + consumed, src_len - consumed);
@@ -529,6 +484,33 @@ struct lz4flex_frame_decoder {
         pending_zero = true;
     }
 
+    // One block off the stream into `comp` (frame/decompress.rs:231-278): BlockInfo word, EndMark, BlockTooBig, payload, optional
+    // block checksum.  END: the EndMark (handled once the staged blocks are decoded); EOFS: no more bytes where a BlockInfo starts --
+    // Ok(0), the frame stays open (:231-238; pending_zero is set); ERR: fail() was called and the payload, if any, taken back;
+    // RAW / COMP: a stored / compressed block of `len` bytes at comp[at].  Everything below RAW ends the gathering.
+    enum BlockKind { END, EOFS, ERR, RAW, COMP };
+    struct BlockRead { BlockKind kind; size_t at, len; };
+    BlockRead read_block(size_t mbs) {
+        uint8_t bi[4];
+        if (read_exact(bi, 4) != 0) {
+            if (io_failed) { fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0}; }
+            pending_zero = true;
+            return {EOFS, 0, 0};
+        }
+        const uint32_t size = rd32(bi);
+        if (size == 0) return {END, 0, 0};
+        const size_t len = size & ~BLOCK_UNCOMPRESSED_SIZE_BIT, at = comp.size();
+        if (len > mbs) { fail(-LZ4FLEX_FE_BLOCK_TOO_BIG); return {ERR, 0, 0}; }
+        comp.resize(at + len);
+        if (len && read_exact(comp.data() + at, len) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0}; }
+        if (fi.block_checksums) {
+            uint8_t c[4];
+            if (read_exact(c, 4) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0}; }
+            if (XxHash32::oneshot(0, comp.data() + at, len) != rd32(c)) { comp.resize(at); fail(-LZ4FLEX_FE_BLOCK_CHECKSUM); return {ERR, 0, 0}; }
+        }
+        return {(size & BLOCK_UNCOMPRESSED_SIZE_BIT) ? RAW : COMP, at, len};
+    }
+
     // Independent frames: gather blocks up to the batch size, decode them in one launch.
     // Round 6, `direct`: the reader asked for at least a block's worth of bytes (lz4flex_frame_decompress: for all of them) -- the blocks
     // are decoded STRAIGHT INTO ITS BUFFER, slot i at i * block size, and the number of bytes delivered is returned (0: nothing went that
@@ -549,26 +531,11 @@ struct lz4flex_frame_decoder {
         bool saw_end = false;
         const size_t out_budget = std::max<size_t>(batch_bytes, mbs) * (batch_auto ? 4u : 1u);   // bytes of output reserved per launch
         while (slots.size() < max_blocks && (slots.empty() || out_need + mbs <= out_budget)) {
-            uint8_t bi[4];
-            const int rc = read_exact(bi, 4);
-            if (rc != 0) {
-                if (io_failed) fail(-LZ4FLEX_FE_IO);
-                else pending_zero = true;   // UnexpectedEof on the block header => Ok(0), frame stays open (:231-238)
-                break;
-            }
-            const uint32_t size = rd32(bi);
-            if (size == 0) { saw_end = true; break; }   // EndMark: handled after the staged blocks are decoded
-            const bool raw = (size & BLOCK_UNCOMPRESSED_SIZE_BIT) != 0;
-            const size_t len = size & ~BLOCK_UNCOMPRESSED_SIZE_BIT;
-            if (len > mbs) { fail(-LZ4FLEX_FE_BLOCK_TOO_BIG); break; }
-            const size_t at = comp.size();
-            comp.resize(at + len);
-            if (len && read_exact(comp.data() + at, len) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); break; }
-            if (fi.block_checksums) {
-                uint8_t c[4];
-                if (read_exact(c, 4) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); break; }
-                if (XxHash32::oneshot(0, comp.data() + at, len) != rd32(c)) { comp.resize(at); fail(-LZ4FLEX_FE_BLOCK_CHECKSUM); break; }
-            }
+            const BlockRead b = read_block(mbs);
+            saw_end = b.kind == END;
+            if (b.kind < RAW) break;
+            const bool raw = b.kind == RAW;
+            const size_t at = b.at, len = b.len;
             Slot s{raw, out_need, in_off.size(), len};
             // An LZ4 block expands by less than 255x (one length byte adds at most 255 output bytes), so min(block size,
             // 255 len + 64) is as good a sink as the reference's block-size buffer and a frame of tiny blocks cannot make the
@@ -652,28 +619,11 @@ struct lz4flex_frame_decoder {
         // (sink positions are 32-bit: an explicit batch size of 4 GiB or more must not wrap them)
         const size_t pos_blocks = (size_t)((0xFFFFFFFFull - carry) / mbs) - 1u;
         while (in_off.size() < std::min(max_blocks, pos_blocks) && (in_off.empty() || (in_off.size() + 1) * mbs <= out_budget)) {
-            uint8_t bi[4];
-            const int rc = read_exact(bi, 4);
-            if (rc != 0) {
-                if (io_failed) fail(-LZ4FLEX_FE_IO);
-                else pending_zero = true;                    // UnexpectedEof on the block header => Ok(0), the frame stays open (:231-238)
-                break;
-            }
-            const uint32_t size = rd32(bi);
-            if (size == 0) { saw_end = true; break; }
-            const bool raw = (size & BLOCK_UNCOMPRESSED_SIZE_BIT) != 0;
-            const size_t len = size & ~BLOCK_UNCOMPRESSED_SIZE_BIT;
-            if (len > mbs) { fail(-LZ4FLEX_FE_BLOCK_TOO_BIG); break; }
-            const size_t at = comp.size();
-            comp.resize(at + len);
-            if (len && read_exact(comp.data() + at, len) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); break; }
-            if (fi.block_checksums) {
-                uint8_t c[4];
-                if (read_exact(c, 4) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); break; }
-                if (XxHash32::oneshot(0, comp.data() + at, len) != rd32(c)) { comp.resize(at); fail(-LZ4FLEX_FE_BLOCK_CHECKSUM); break; }
-            }
-            if (raw) { raw_tail = true; raw_at = at; raw_len = len; break; }
-            in_off.push_back(at); in_len.push_back((uint32_t)len);
+            const BlockRead b = read_block(mbs);
+            saw_end = b.kind == END;
+            if (b.kind < RAW) break;
+            if (b.kind == RAW) { raw_tail = true; raw_at = b.at; raw_len = b.len; break; }
+            in_off.push_back(b.at); in_len.push_back((uint32_t)b.len);
         }
         const size_t nb = in_off.size();
         if (ldst.size() < carry + (nb + 1) * mbs) ldst.resize(carry + (nb + 1) * mbs);

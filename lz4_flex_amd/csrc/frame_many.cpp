@@ -25,30 +25,18 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "frame_plan.h"
 #include "lz4_ctx.h"
 #include "lz4_device.h"
 
 namespace {
 
 using namespace lz4flex_dev;
+using namespace lz4flex_plan;   // block sizes, FAST_HISTORY, STREAM_MAX (the streams the batch path takes), TableOffset, LinkedWindow
 
-constexpr uint32_t UNCOMPRESSED_BIT = 0x80000000u;
-constexpr uint64_t WINDOW_SIZE = 65536, FAST_HISTORY = 32768;
 constexpr uint32_t CHAIN_MAX = 65536u;                   // blocks per chained decode batch (LZ4FLEX_MEM_CHAINED)
 // ("decompress_level_chains", default 1 024: from this many Linked streams in one call on their blocks are decoded a level per launch -- the groups loop)
 constexpr uint64_t MAX_SLOTS = 1ull << 26;               // block-table entries per decompress_many call (12 bytes each on the host and on the device)
-constexpr uint64_t STREAM_MAX = 0x7FFF0000ull - (8u << 20);   // longer streams take the one-shot path (table reposition near 2 GiB, frame/compress.rs:266-271)
-
-size_t block_bytes(int code) {                           // BlockSize::get_size, frame/header.rs:68-77
-    switch (code) {
-        case 4: return 64u << 10;
-        case 5: return 256u << 10;
-        case 6: return 1u << 20;
-        case 7: return 4u << 20;
-        default: return 0;
-    }
-}
-int block_size_from_buf_length(uint64_t n) { return n > 256u * 1024 ? 7 : (n > 64u * 1024 ? 5 : 4); }   // frame/header.rs:57-67
 
 #define TRY_HIP(expr)                                                        \
     do {                                                                     \
@@ -61,29 +49,13 @@ int block_size_from_buf_length(uint64_t n) { return n > 256u * 1024 ? 7 : (n > 6
         if (rc_) return rc_;           \
     } while (0)
 
-// descriptor arrays: one host image, one device copy (scratch slot 0)
-struct Desc {
-    std::vector<uint8_t> h;
-    uint8_t* d = nullptr;
-    size_t take(size_t bytes) {
-        const size_t at = (h.size() + 63) / 64 * 64;
-        h.resize(at + bytes, 0);
-        return at;
-    }
-    template <class T> T* host(size_t at) { return reinterpret_cast<T*>(h.data() + at); }
-    template <class T> T* dev(size_t at) const { return reinterpret_cast<T*>(d + at); }
-    int upload(lz4flex_ctx* c, hipStream_t s) {
-        void* p = nullptr;
-        TRY_RC(ctx_scratch(c, 0, h.size() + 64, &p));
-        d = (uint8_t*)p;
-        if (!h.empty()) TRY_HIP(hipMemcpyAsync(d, h.data(), h.size(), hipMemcpyHostToDevice, s));
-        return 0;
-    }
-    template <class T> int fetch(size_t at, size_t count, hipStream_t s) {
-        if (count) TRY_HIP(hipMemcpyAsync(h.data() + at, d + at, count * sizeof(T), hipMemcpyDeviceToHost, s));
-        return 0;
-    }
-};
+// descriptor arrays (Desc, lz4_ctx.h): the device copy is scratch slot 0, the whole image goes up
+int upload(lz4flex_ctx* c, Desc& D, hipStream_t s) {
+    void* p = nullptr;
+    TRY_RC(ctx_scratch(c, 0, D.bytes() + 64, &p));
+    TRY_HIP(D.upload(p, D.bytes(), s));
+    return 0;
+}
 
 // ---- the streams the batch path leaves out: FrameEncoder / FrameDecoder over flat buffers, one stream at a time
 int compress_one(const uint8_t* d_in, uint64_t len, const lz4flex_frame_info* info, uint8_t* d_out, uint64_t cap, uint64_t* out_len,
@@ -125,8 +97,8 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
     uint64_t nb64 = 0;
     for (uint32_t i = 0; i < n; i++) {
         code[i] = info->block_size ? info->block_size : block_size_from_buf_length(in_len[i]);
-        const size_t mbs = block_bytes(code[i]);
-        if (mbs == 0) return -LZ4FLEX_E_INVALID_ARG;                                   // (Max8MB is legacy-decode only, frame/header.rs:287)
+        const size_t mbs = block_size_bytes(code[i]);
+        if (mbs == 0 || code[i] == 8) return -LZ4FLEX_E_INVALID_ARG;                   // (Max8MB is legacy-decode only, frame/header.rs:287)
         if (in_len[i] > STREAM_MAX) { slow.push_back(i); continue; }
         fast.push_back(i);
         nb64 += (in_len[i] + mbs - 1) / mbs;
@@ -138,7 +110,6 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
                  a_in_off = D.take(8ull * nb), a_comp_off = D.take(8ull * nb), a_in_len = D.take(4ull * nb), a_flags = D.take(4ull * nb),
                  a_comp_cap = D.take(4ull * nb), a_cb = (exact && linked) ? D.take(sizeof(lz4flex_chain_block) * (size_t)nb) : 0,
                  a_first = (exact && linked) ? D.take(4ull * nf) : 0, a_count = (exact && linked) ? D.take(4ull * nf) : 0;
-    const size_t up_bytes = D.h.size();
     // (results: written by the device)
     const size_t a_comp_len = D.take(4ull * nb), a_comp_st = D.take(4ull * nb), a_dst_off = D.take(8ull * nb), a_pay_off = D.take(8ull * nb),
                  a_pay_len = D.take(4ull * nb), a_sums = D.take(4ull * nb), a_csum = D.take(4ull * nf), a_flen = D.take(8ull * nf),
@@ -158,7 +129,7 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
         uint32_t b = 0;
         for (uint32_t f = 0; f < nf; f++) {
             const uint32_t i = fast[f];
-            const size_t mbs = block_bytes(code[i]);
+            const size_t mbs = block_size_bytes(code[i]);
             big |= mbs > 65536;
             const uint32_t cnt = (uint32_t)((in_len[i] + mbs - 1) / mbs);
             ManyStream& m = ms[f];
@@ -172,10 +143,10 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
             m.hdr_len = (uint32_t)hl;
             soff[f] = in_off[i]; slen[f] = (uint32_t)in_len[i];
             if (cb) { D.host<uint32_t>(a_first)[f] = b; D.host<uint32_t>(a_count)[f] = cnt; }
-            // the reference's window bookkeeping for a Linked frame (frame/compress.rs:324-356), in coordinates of the stream: the
-            // block's prefix starts at vbase, its external dictionary (the 64 KiB in front of the prefix) at dict_stream
-            uint64_t vbase = 0, v_src_start = 0, dict_stream = 0, sso = 0;
-            uint32_t ext = 0;
+            // table mode (Independent) / window (Linked) of the reference's encoder, block after block: frame_plan.h.  No stream here
+            // is longer than STREAM_MAX, so neither ever repositions: FRAME_FIRST is block 0 alone, every chain block's repos is 0
+            TableOffset tbl;
+            LinkedWindow win;
             for (uint32_t k = 0; k < cnt; k++, b++) {
                 const uint64_t at = (uint64_t)k * mbs;
                 const uint32_t len = (uint32_t)std::min<uint64_t>(mbs, in_len[i] - at);
@@ -183,26 +154,17 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
                 b_cap[b] = (uint32_t)((lz4flex_get_maximum_output_size(len) + 63) / 64 * 64);
                 b_co[b] = comp_bytes; comp_bytes += b_cap[b];
                 if (!exact) b_fl[b] = (linked && k > 0) ? LZ4FLEX_BLOCK_HISTORY(std::min<uint64_t>(at, FAST_HISTORY)) : 0u;
-                else b_fl[b] = k == 0 ? LZ4FLEX_BLOCK_FRAME_FIRST : LZ4FLEX_BLOCK_FRAME_CONTINUATION;   // (Independent; frame/compress.rs:357-367)
+                else b_fl[b] = tbl.next(mbs, len);                                         // (read by the Independent path only)
                 if (cb) {
-                    const uint64_t v_src_end = v_src_start + len;
                     lz4flex_chain_block& q = cb[b];
-                    q.in_off = in_off[i] + vbase; q.in_len = (uint32_t)v_src_end; q.in_pos = (uint32_t)v_src_start;
-                    q.dict_off = ext ? in_off[i] + dict_stream : 0; q.dict_len = ext; q.so = (uint32_t)sso; q.repos = 0; q.flags = 0;
-                    v_src_start += len;
-                    if (v_src_start >= mbs + WINDOW_SIZE) {
-                        dict_stream = vbase + v_src_end - WINDOW_SIZE; ext = (uint32_t)WINDOW_SIZE;
-                        sso += v_src_end; vbase += v_src_end; v_src_start = 0;
-                    } else if (v_src_start + ext > WINDOW_SIZE) {
-                        const uint64_t delta = std::min<uint64_t>(ext, v_src_start + ext - WINDOW_SIZE);
-                        dict_stream += delta; ext -= (uint32_t)delta;
-                    }
+                    q = win.next(mbs, len);                                                // (stream positions; the stream starts at in_off[i])
+                    q.in_off += in_off[i];
+                    if (q.dict_len) q.dict_off += in_off[i];
                 }
             }
         }
     }
-    (void)up_bytes;
-    TRY_RC(D.upload(c, s));
+    TRY_RC(upload(c, D, s));
     void* comp = nullptr;
     TRY_RC(ctx_scratch(c, 1, (size_t)comp_bytes + 64, &comp));
     if (nb) {
@@ -220,8 +182,8 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
                                        D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st), nb, bsum ? 1 : 0,
                                        D.dev<uint32_t>(a_csum), out, D.dev<uint64_t>(a_dst_off), D.dev<uint64_t>(a_pay_off), D.dev<uint32_t>(a_pay_len),
                                        D.dev<uint32_t>(a_sums), D.dev<uint64_t>(a_flen), D.dev<int32_t>(a_verdict), s));
-    TRY_RC(D.fetch<uint64_t>(a_flen, nf, s));
-    TRY_RC(D.fetch<int32_t>(a_verdict, nf, s));
+    TRY_HIP(D.fetch<uint64_t>(a_flen, nf, s));
+    TRY_HIP(D.fetch<int32_t>(a_verdict, nf, s));
     TRY_HIP(hipStreamSynchronize(s));
     for (uint32_t f = 0; f < nf; f++) {
         const uint32_t i = fast[f];
@@ -256,7 +218,7 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         const size_t a_off = H.take(8ull * n), a_len = H.take(8ull * n), a_heads = H.take(32ull * n);
         memcpy(H.host<uint64_t>(a_off), in_off, 8ull * n);
         memcpy(H.host<uint64_t>(a_len), in_len, 8ull * n);
-        TRY_RC(H.upload(c, s));
+        TRY_RC(upload(c, H, s));
         TRY_HIP(launch_frame_many_heads(in, H.dev<uint64_t>(a_off), H.dev<uint64_t>(a_len), n, H.dev<uint8_t>(a_heads), s));
         TRY_HIP(hipMemcpyAsync(heads.data(), H.dev<uint8_t>(a_heads), 32ull * n, hipMemcpyDeviceToHost, s));
         TRY_HIP(hipStreamSynchronize(s));
@@ -269,7 +231,7 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         ManyFrame& m = W.host<ManyFrame>(a_fr)[i];
         m.off = in_off[i]; m.len = in_len[i]; m.skip = 1;
         const int64_t hl = lz4flex_frame_info_read(heads.data() + 32ull * i, (size_t)std::min<uint64_t>(32, in_len[i]), &fi[i], nullptr);
-        const size_t bs = hl < 0 ? 0 : block_bytes(fi[i].block_size);
+        const size_t bs = hl < 0 ? 0 : block_size_bytes(fi[i].block_size);
         // (a header that does not parse, a legacy frame, an output a chained batch cannot address: the streaming decoder's business)
         if (hl < 0 || fi[i].legacy_frame || bs == 0 || (fi[i].block_mode == 1 && out_cap[i] > 0xFFFFFFFFull - 2 * bs)) { again[i] = 1; continue; }
         const uint64_t cap_blocks = out_cap[i] / bs + 2;
@@ -280,11 +242,11 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         slots += cap_blocks;
     }
     const size_t a_pay = W.take(8ull * slots), a_word = W.take(4ull * slots), a_info = W.take(32ull * n);
-    TRY_RC(W.upload(c, s));
+    TRY_RC(upload(c, W, s));
     TRY_HIP(launch_frame_many_walk(in, W.dev<ManyFrame>(a_fr), n, W.dev<uint64_t>(a_pay), W.dev<uint32_t>(a_word), W.dev<uint32_t>(a_info), s));
-    TRY_RC(W.fetch<uint64_t>(a_pay, slots, s));
-    TRY_RC(W.fetch<uint32_t>(a_word, slots, s));
-    TRY_RC(W.fetch<uint32_t>(a_info, 8ull * n, s));
+    TRY_HIP(W.fetch<uint64_t>(a_pay, slots, s));
+    TRY_HIP(W.fetch<uint32_t>(a_word, slots, s));
+    TRY_HIP(W.fetch<uint32_t>(a_info, 8ull * n, s));
     TRY_HIP(hipStreamSynchronize(s));
     // ---- 3. the batch: compressed blocks (Independent: plain; Linked: chained, level by level), stored blocks (one copy launch)
     std::vector<Entry> plain, chained;
@@ -303,12 +265,12 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         const size_t plain0 = plain.size(), chained0 = chained.size(), r0 = r_in.size(), p0 = p_off.size();
         bool ok = true;
         for (uint32_t k = 0; k < cnt && ok; k++) {
-            const uint32_t w = W.host<uint32_t>(a_word)[m.slot + k], len = w & ~UNCOMPRESSED_BIT;
+            const uint32_t w = W.host<uint32_t>(a_word)[m.slot + k], len = w & ~BLOCK_UNCOMPRESSED_SIZE_BIT;
             const uint64_t po = W.host<uint64_t>(a_pay)[m.slot + k], pos = (uint64_t)k * bs;
             if (len == 0 || pos >= out_cap[i]) { ok = false; break; }
             const uint32_t cap = (uint32_t)std::min<uint64_t>(bs, out_cap[i] - pos);
             if (m.flags & 1u) { p_off.push_back(po); p_len.push_back(len); p_stream.push_back(i); }
-            if (w & UNCOMPRESSED_BIT) {
+            if (w & BLOCK_UNCOMPRESSED_SIZE_BIT) {
                 if (len > cap || (k + 1 != cnt && len != bs)) { ok = false; break; }
                 r_in.push_back(po); r_out.push_back(out_off[i] + pos); r_len.push_back(len);
                 raw_bytes[i] += len;
@@ -366,7 +328,7 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         if (nr) { memcpy(B.host<uint64_t>(b_rin), r_in.data(), 8ull * nr); memcpy(B.host<uint64_t>(b_rout), r_out.data(), 8ull * nr); memcpy(B.host<uint32_t>(b_rlen), r_len.data(), 4ull * nr); }
         if (nk) { memcpy(B.host<uint64_t>(b_poff), p_off.data(), 8ull * nk); memcpy(B.host<uint32_t>(b_plen), p_len.data(), 4ull * nk); }
     }
-    TRY_RC(B.upload(c, s));
+    TRY_RC(upload(c, B, s));
     if (nk) {                                          // frame/decompress.rs:255-261,275-278: block checksums, before anything is decoded
         TRY_RC(lz4flex_xxh32_batch_device(in, B.dev<uint64_t>(b_poff), B.dev<uint32_t>(b_plen), nk, 0, B.dev<uint32_t>(b_psum), s));
         TRY_HIP(launch_frame_sums_check(in, B.dev<uint64_t>(b_poff), B.dev<uint32_t>(b_plen), B.dev<uint32_t>(b_psum), nk, B.dev<uint32_t>(b_bad), s));
@@ -410,9 +372,9 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
                                            B.dev<uint32_t>(b_cap) + o, B.dev<uint32_t>(b_olen) + o, B.dev<int32_t>(b_st) + o, B.dev<uint64_t>(b_det) + 2 * o, &ext,
                                            LZ4FLEX_MEM_DEVICE | LZ4FLEX_MEM_CHAINED, s));
     }
-    TRY_RC(B.fetch<uint32_t>(b_olen, ne, s));
-    TRY_RC(B.fetch<int32_t>(b_st, ne, s));
-    TRY_RC(B.fetch<uint32_t>(b_bad, nk, s));
+    TRY_HIP(B.fetch<uint32_t>(b_olen, ne, s));
+    TRY_HIP(B.fetch<int32_t>(b_st, ne, s));
+    TRY_HIP(B.fetch<uint32_t>(b_bad, nk, s));
     TRY_HIP(hipStreamSynchronize(s));
     // ---- 4. verdicts
     std::vector<uint64_t> produced(raw_bytes);
@@ -442,7 +404,7 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         TRY_HIP(hipMemcpyAsync(B.dev<uint64_t>(b_coff), B.host<uint64_t>(b_coff), 8ull * m, hipMemcpyHostToDevice, s));
         TRY_HIP(hipMemcpyAsync(B.dev<uint32_t>(b_clen), B.host<uint32_t>(b_clen), 4ull * m, hipMemcpyHostToDevice, s));
         TRY_RC(lz4flex_xxh32_batch_device(out, B.dev<uint64_t>(b_coff), B.dev<uint32_t>(b_clen), m, 0, B.dev<uint32_t>(b_csum), s));
-        TRY_RC(B.fetch<uint32_t>(b_csum, m, s));
+        TRY_HIP(B.fetch<uint32_t>(b_csum, m, s));
         TRY_HIP(hipStreamSynchronize(s));
         for (uint32_t j = 0; j < m; j++)
             if (B.host<uint32_t>(b_csum)[j] != W.host<uint32_t>(a_info)[8ull * cs[j] + 4]) again[cs[j]] = 1;

@@ -1,11 +1,12 @@
 // lz4_ctx.h -- the host layer's private state: struct lz4flex_ctx (opaque in include/lz4flex_amd.h) and the few helpers every host file
-// that works on a context needs (capi.cpp, frame_many.cpp).  Host only, not installed, no kernel includes it.
+// that works on a context needs (capi.cpp, frame_many.cpp; sharded.cpp: Desc alone).  Host only, not installed, no kernel includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace lz4flex_dev {
 
@@ -16,6 +17,27 @@ struct Layout {
     size_t align;
     size_t end = 0;               // the bytes taken so far (aligned)
     size_t take(size_t bytes) { const size_t at = end; end = align_up(end + bytes, align); return at; }
+};
+
+// Descriptor and result arrays of one call, one behind the other at 64-byte starts: a host image and its device copy.  The caller
+// owns the device memory (frame_many.cpp: context scratch slot 0; sharded.cpp: an allocation of its own) and maps the hipError_t.
+// take(0) returns the offset the next take returns too: an array of no elements shares its start with its neighbour and is never touched.
+struct Desc {
+    Layout l{64};
+    std::vector<uint8_t> h;
+    uint8_t* d = nullptr;
+    size_t take(size_t bytes) { const size_t at = l.take(bytes); h.resize(l.end, 0); return at; }
+    size_t bytes() const { return l.end; }
+    template <class T> T* host(size_t at) { return reinterpret_cast<T*>(h.data() + at); }
+    template <class T> T* dev(size_t at) const { return reinterpret_cast<T*>(d + at); }
+    // the image's first `n` bytes (what the device only writes may lie behind them) to `dev_mem`, which holds bytes() of them
+    hipError_t upload(void* dev_mem, size_t n, hipStream_t s) {
+        d = (uint8_t*)dev_mem;
+        return n ? hipMemcpyAsync(d, h.data(), n, hipMemcpyHostToDevice, s) : hipSuccess;
+    }
+    template <class T> hipError_t fetch(size_t at, size_t count, hipStream_t s) {
+        return count ? hipMemcpyAsync(h.data() + at, d + at, count * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
+    }
 };
 
 // the calling thread's device for the lifetime of the guard: the context's one (err: what selecting it answered)

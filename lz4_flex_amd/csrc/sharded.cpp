@@ -24,11 +24,14 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "frame_plan.h"
+#include "lz4_ctx.h"
+#include "lz4_device.h"
 
 namespace {
 
-constexpr uint32_t UNCOMPRESSED_BIT = 0x80000000u;
-constexpr uint64_t WINDOW_SIZE = 65536;
+using lz4flex_dev::Desc;
+using namespace lz4flex_plan;   // block sizes, BLOCK_UNCOMPRESSED_SIZE_BIT, TableOffset
 
 // ---- the few RCCL entry points used (rccl.h: ncclResult_t f(...), 0 = ncclSuccess; ncclUint8 = 1, ncclUint64 = 5)
 struct Rccl {
@@ -72,16 +75,6 @@ bool force_collectives() {
     return e && !strcmp(e, "1");
 }
 
-size_t block_bytes(int code) {
-    switch (code) {
-        case 4: return 64u << 10;
-        case 5: return 256u << 10;
-        case 6: return 1u << 20;
-        case 7: return 4u << 20;
-        default: return 0;
-    }
-}
-
 struct DevBuf {                       // a device allocation that frees itself
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -112,7 +105,7 @@ extern "C" {
 // Worst-case bytes of the segment a rank produces for local_len bytes (what the root must be able to receive per rank is
 // bounded by the same figure): the blocks stored raw + 8 bytes of BlockInfo / checksum each.
 uint64_t lz4flex_frame_segment_bound(uint64_t local_len, const lz4flex_frame_info* info) {
-    const size_t bs = info ? block_bytes(info->block_size) : 0;
+    const size_t bs = info && info->block_size != 8 ? block_size_bytes(info->block_size) : 0;   // (Max8MB is legacy-decode only)
     if (!bs) return 0;
     const uint64_t n = (local_len + bs - 1) / bs;
     return local_len + 8 * n + 16;
@@ -123,8 +116,8 @@ int lz4flex_frame_compress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank, 
                                    uint64_t frame_cap, uint64_t* frame_len, void* hip_stream) {
     if (!info || world < 1 || rank < 0 || rank >= world || root < 0 || root >= world || (local_len && !local)) return -LZ4FLEX_E_INVALID_ARG;
     if (info->block_mode != 0 || info->content_checksum || info->has_content_size || info->legacy_frame) return -LZ4FLEX_E_UNSUPPORTED;
-    const size_t bs = block_bytes(info->block_size);
-    if (!bs) return -LZ4FLEX_E_INVALID_ARG;                        // an explicit block size (Auto is a property of a stream, not of a shard)
+    const size_t bs = block_size_bytes(info->block_size);
+    if (!bs || info->block_size == 8) return -LZ4FLEX_E_INVALID_ARG;                        // an explicit block size (Auto is a property of a stream, not of a shard)
     const bool coll = world > 1 || (nccl_comm != nullptr && force_collectives());     // the exchange goes through RCCL
     const bool self = coll && world == 1;                                             // ... the root's own segment too (send + receive to itself)
     if (coll && (!nccl_comm || !rccl().ok)) return -LZ4FLEX_E_UNSUPPORTED;
@@ -141,41 +134,33 @@ int lz4flex_frame_compress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank, 
     TRY_HIP(seg.alloc(lz4flex_frame_segment_bound(local_len, info)));
     if (n) {
         TRY_HIP(comp.alloc(stride * n));
-        // descriptor arrays: in_off, comp_off, seg_off (n + 1) [u64]; in_len, cap, comp_len, status, flags [u32]; scratch 16 n
-        const size_t o_in_off = 0, o_comp_off = 8ull * n, o_seg_off = 16ull * n, o_in_len = 24ull * n + 8, o_cap = o_in_len + 4ull * n,
-                     o_clen = o_cap + 4ull * n, o_st = o_clen + 4ull * n, o_fl = o_st + 4ull * n, o_scr = (o_fl + 4ull * n + 15) & ~15ull,
-                     total = o_scr + 16ull * n;
-        TRY_HIP(desc.alloc(total));
-        std::vector<uint8_t> h(o_scr, 0);
-        // per-block table mode of a FrameEncoder that has already written first_block blocks (frame/compress.rs:266-271,:357-367)
-        uint64_t so = 0;
-        const uint64_t limit = 0xFFFFFFFFull / 2;
-        std::vector<uint32_t> fl(n);
-        for (uint64_t k = 0; k < first_block + n; k++) {
-            if (so + bs + WINDOW_SIZE >= limit) so = 0;
-            if (k >= first_block) fl[k - first_block] = so == 0 ? LZ4FLEX_BLOCK_FRAME_FIRST : LZ4FLEX_BLOCK_FRAME_CONTINUATION;
-            so += bs;
-        }
+        Desc D;           // (the assembler's scratch, o_scr, is taken last so that one layout gives the device size: its host bytes, behind `up`, are never uploaded or read)
+        const size_t o_in_off = D.take(8ull * n), o_comp_off = D.take(8ull * n), o_seg_off = D.take(8ull * n + 8), o_in_len = D.take(4ull * n),
+                     o_cap = D.take(4ull * n), o_clen = D.take(4ull * n), o_st = D.take(4ull * n), o_fl = D.take(4ull * n), up = D.bytes(),
+                     o_scr = D.take(16ull * n);
+        TRY_HIP(desc.alloc(D.bytes()));
+        // per-block table mode of a FrameEncoder that has already written first_block full blocks (frame_plan.h)
+        TableOffset tbl;
+        for (uint64_t k = 0; k < first_block; k++) (void)tbl.next(bs, bs);
         for (uint32_t i = 0; i < n; i++) {
-            ((uint64_t*)(h.data() + o_in_off))[i] = (uint64_t)i * bs;
-            ((uint64_t*)(h.data() + o_comp_off))[i] = (uint64_t)i * stride;
-            ((uint32_t*)(h.data() + o_in_len))[i] = (uint32_t)std::min<uint64_t>(bs, local_len - (uint64_t)i * bs);
-            ((uint32_t*)(h.data() + o_cap))[i] = (uint32_t)stride;
-            ((uint32_t*)(h.data() + o_fl))[i] = fl[i];
+            const uint32_t len = (uint32_t)std::min<uint64_t>(bs, local_len - (uint64_t)i * bs);
+            D.host<uint64_t>(o_in_off)[i] = (uint64_t)i * bs;
+            D.host<uint64_t>(o_comp_off)[i] = (uint64_t)i * stride;
+            D.host<uint32_t>(o_in_len)[i] = len;
+            D.host<uint32_t>(o_cap)[i] = (uint32_t)stride;
+            D.host<uint32_t>(o_fl)[i] = tbl.next(bs, len);
         }
-        uint8_t* d = desc.as<uint8_t>();
-        TRY_HIP(hipMemcpyAsync(d, h.data(), o_scr, hipMemcpyHostToDevice, s));
-        TRY_RC(lz4flex_compress_batch(ctx, local, (const uint64_t*)(d + o_in_off), (const uint32_t*)(d + o_in_len), (const uint32_t*)(d + o_fl), n,
-                                      comp.p, (const uint64_t*)(d + o_comp_off), (const uint32_t*)(d + o_cap), (uint32_t*)(d + o_clen),
-                                      (int32_t*)(d + o_st), LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
-        TRY_RC(lz4flex_frame_assemble_device(local, (const uint64_t*)(d + o_in_off), (const uint32_t*)(d + o_in_len), comp.p,
-                                             (const uint64_t*)(d + o_comp_off), (const uint32_t*)(d + o_clen), n, info->block_checksums, seg.p,
-                                             (uint64_t*)(d + o_seg_off), d + o_scr, s));
-        std::vector<int32_t> st(n);
-        TRY_HIP(hipMemcpyAsync(st.data(), d + o_st, 4ull * n, hipMemcpyDeviceToHost, s));
-        TRY_HIP(hipMemcpyAsync(&seg_bytes, d + o_seg_off + 8ull * n, 8, hipMemcpyDeviceToHost, s));
+        TRY_HIP(D.upload(desc.p, up, s));
+        TRY_RC(lz4flex_compress_batch(ctx, local, D.dev<uint64_t>(o_in_off), D.dev<uint32_t>(o_in_len), D.dev<uint32_t>(o_fl), n, comp.p,
+                                      D.dev<uint64_t>(o_comp_off), D.dev<uint32_t>(o_cap), D.dev<uint32_t>(o_clen), D.dev<int32_t>(o_st),
+                                      LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
+        TRY_RC(lz4flex_frame_assemble_device(local, D.dev<uint64_t>(o_in_off), D.dev<uint32_t>(o_in_len), comp.p, D.dev<uint64_t>(o_comp_off),
+                                             D.dev<uint32_t>(o_clen), n, info->block_checksums, seg.p, D.dev<uint64_t>(o_seg_off),
+                                             D.dev<uint8_t>(o_scr), s));
+        TRY_HIP(D.fetch<int32_t>(o_st, n, s));
+        TRY_HIP(hipMemcpyAsync(&seg_bytes, D.dev<uint64_t>(o_seg_off) + n, 8, hipMemcpyDeviceToHost, s));
         TRY_HIP(hipStreamSynchronize(s));
-        for (uint32_t i = 0; i < n; i++) if (st[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
+        for (uint32_t i = 0; i < n; i++) if (D.host<int32_t>(o_st)[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
     }
     return 0;
     }();
@@ -261,7 +246,7 @@ int lz4flex_frame_decompress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank
             else if (fi.legacy_frame || fi.block_mode != 0 || fi.content_checksum) meta[3] = LZ4FLEX_E_UNSUPPORTED;
             else {
                 hdr_len = (uint32_t)hl;
-                const uint32_t bs = (uint32_t)block_bytes(fi.block_size);
+                const uint32_t bs = (uint32_t)block_size_bytes(fi.block_size);
                 uint32_t max_blocks = (uint32_t)std::min<uint64_t>(1u << 26, std::max<uint64_t>(1024, 4 * (frame_bytes / bs) + 16));
                 for (;;) {
                     if (d_off.p) { (void)hipFree(d_off.p); d_off.p = nullptr; }
@@ -295,7 +280,7 @@ int lz4flex_frame_decompress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank
     }
     if (meta[3]) return root_rc ? root_rc : -(int)meta[3];
     const uint64_t nb = meta[0];
-    const size_t bs = block_bytes((int)meta[1]);
+    const size_t bs = block_size_bytes((int)meta[1]);
     const bool has_bc = meta[2] != 0;
     const uint32_t tail = has_bc ? 4u : 0u;
     if (info_out) { memset(info_out, 0, sizeof *info_out); info_out->block_size = (int)meta[1]; info_out->block_checksums = has_bc; }
@@ -323,7 +308,7 @@ int lz4flex_frame_decompress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank
         partition(nb, world, r, &l2, &h2);
         if (l2 == h2) { *a = *b = 0; return; }
         *a = h_off[(size_t)l2];
-        *b = h_off[(size_t)h2 - 1] + (h_word[(size_t)h2 - 1] & ~UNCOMPRESSED_BIT) + tail;
+        *b = h_off[(size_t)h2 - 1] + (h_word[(size_t)h2 - 1] & ~BLOCK_UNCOMPRESSED_SIZE_BIT) + tail;
     };
     // ---- every rank's blocks are contiguous in the frame: one transfer per rank
     uint64_t a = 0, b = 0;
@@ -359,11 +344,11 @@ int lz4flex_frame_decompress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank
     std::vector<uint32_t> c_len, c_cap, r_len, p_len;
     for (uint32_t i = 0; i < n; i++) {
         const uint64_t po = h_off[(size_t)(lo + i)] - a;
-        const uint32_t w = h_word[(size_t)(lo + i)], len = w & ~UNCOMPRESSED_BIT;
+        const uint32_t w = h_word[(size_t)(lo + i)], len = w & ~BLOCK_UNCOMPRESSED_SIZE_BIT;
         const uint64_t dst = (uint64_t)i * bs;
         const uint32_t cap = (uint32_t)std::min<uint64_t>(bs, out_cap > dst ? out_cap - dst : 0);
         p_off.push_back(po); p_len.push_back(len);
-        if (w & UNCOMPRESSED_BIT) {
+        if (w & BLOCK_UNCOMPRESSED_SIZE_BIT) {
             if (len > cap) return -LZ4FLEX_FE_OUTPUT_FULL;
             r_in.push_back(po); r_out.push_back(dst); r_len.push_back(len);
         } else {
@@ -371,42 +356,36 @@ int lz4flex_frame_decompress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank
         }
     }
     const uint32_t nc = (uint32_t)c_in.size(), nr = (uint32_t)r_in.size();
-    // device arrays: [c_in c_out | r_in r_out | p_off] u64, then [c_len c_cap c_olen c_st | r_len | p_len p_sum] u32
-    const size_t o_cin = 0, o_cout = 8ull * nc, o_rin = 16ull * nc, o_rout = o_rin + 8ull * nr, o_poff = o_rout + 8ull * nr,
-                 o_clen = o_poff + 8ull * n, o_ccap = o_clen + 4ull * nc, o_colen = o_ccap + 4ull * nc, o_cst = o_colen + 4ull * nc,
-                 o_rlen = o_cst + 4ull * nc, o_plen = o_rlen + 4ull * nr, o_psum = o_plen + 4ull * n, tot = o_psum + 4ull * n;
+    Desc D;
+    auto put = [&](const void* src, size_t bytes) { const size_t at = D.take(bytes); if (bytes) memcpy(D.host<uint8_t>(at), src, bytes); return at; };
+    const size_t o_cin = put(c_in.data(), 8ull * nc), o_cout = put(c_out.data(), 8ull * nc), o_rin = put(r_in.data(), 8ull * nr),
+                 o_rout = put(r_out.data(), 8ull * nr), o_poff = put(p_off.data(), 8ull * n), o_clen = put(c_len.data(), 4ull * nc),
+                 o_ccap = put(c_cap.data(), 4ull * nc), o_rlen = put(r_len.data(), 4ull * nr), o_plen = put(p_len.data(), 4ull * n);
+    const size_t o_colen = D.take(4ull * nc), o_cst = D.take(4ull * nc), o_psum = D.take(4ull * n), o_bad = D.take(4ull * n);   // (results)
     DevBuf dd;
-    TRY_HIP(dd.alloc(tot));
-    std::vector<uint8_t> h(tot, 0);
-    auto put = [&](size_t at, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + at, src, bytes); };
-    put(o_cin, c_in.data(), 8ull * nc); put(o_cout, c_out.data(), 8ull * nc); put(o_rin, r_in.data(), 8ull * nr); put(o_rout, r_out.data(), 8ull * nr);
-    put(o_poff, p_off.data(), 8ull * n); put(o_clen, c_len.data(), 4ull * nc); put(o_ccap, c_cap.data(), 4ull * nc);
-    put(o_rlen, r_len.data(), 4ull * nr); put(o_plen, p_len.data(), 4ull * n);
-    uint8_t* d = dd.as<uint8_t>();
-    TRY_HIP(hipMemcpyAsync(d, h.data(), tot, hipMemcpyHostToDevice, s));
+    TRY_HIP(dd.alloc(D.bytes()));
+    TRY_HIP(D.upload(dd.p, D.bytes(), s));
     if (has_bc) {                                                    // frame/decompress.rs:255-261,275-278: verify before decoding
-        TRY_RC(lz4flex_xxh32_batch_device(local, (const uint64_t*)(d + o_poff), (const uint32_t*)(d + o_plen), n, 0, (uint32_t*)(d + o_psum), s));
-        std::vector<uint32_t> sums(n), stored(n);
-        TRY_HIP(hipMemcpyAsync(sums.data(), d + o_psum, 4ull * n, hipMemcpyDeviceToHost, s));
-        for (uint32_t i = 0; i < n; i++) TRY_HIP(hipMemcpyAsync(&stored[i], local + p_off[i] + p_len[i], 4, hipMemcpyDeviceToHost, s));
+        TRY_RC(lz4flex_xxh32_batch_device(local, D.dev<uint64_t>(o_poff), D.dev<uint32_t>(o_plen), n, 0, D.dev<uint32_t>(o_psum), s));
+        TRY_HIP(lz4flex_dev::launch_frame_sums_check(local, D.dev<uint64_t>(o_poff), D.dev<uint32_t>(o_plen), D.dev<uint32_t>(o_psum), n,
+                                                     D.dev<uint32_t>(o_bad), s));
+        TRY_HIP(D.fetch<uint32_t>(o_bad, n, s));
         TRY_HIP(hipStreamSynchronize(s));
-        for (uint32_t i = 0; i < n; i++) if (sums[i] != stored[i]) return -LZ4FLEX_FE_BLOCK_CHECKSUM;
+        for (uint32_t i = 0; i < n; i++) if (D.host<uint32_t>(o_bad)[i]) return -LZ4FLEX_FE_BLOCK_CHECKSUM;
     }
-    if (nc) TRY_RC(lz4flex_decompress_batch(ctx, local, (const uint64_t*)(d + o_cin), (const uint32_t*)(d + o_clen), nc, out, (const uint64_t*)(d + o_cout),
-                                            (const uint32_t*)(d + o_ccap), (uint32_t*)(d + o_colen), (int32_t*)(d + o_cst), nullptr,
+    if (nc) TRY_RC(lz4flex_decompress_batch(ctx, local, D.dev<uint64_t>(o_cin), D.dev<uint32_t>(o_clen), nc, out, D.dev<uint64_t>(o_cout),
+                                            D.dev<uint32_t>(o_ccap), D.dev<uint32_t>(o_colen), D.dev<int32_t>(o_cst), nullptr,
                                             LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
-    if (nr) TRY_RC(lz4flex_copy_batch_device(local, (const uint64_t*)(d + o_rin), (const uint32_t*)(d + o_rlen), out, (const uint64_t*)(d + o_rout), nr, s));
-    std::vector<uint32_t> olen(nc);
-    std::vector<int32_t> st(nc);
-    if (nc) {
-        TRY_HIP(hipMemcpyAsync(olen.data(), d + o_colen, 4ull * nc, hipMemcpyDeviceToHost, s));
-        TRY_HIP(hipMemcpyAsync(st.data(), d + o_cst, 4ull * nc, hipMemcpyDeviceToHost, s));
-    }
+    if (nr) TRY_RC(lz4flex_copy_batch_device(local, D.dev<uint64_t>(o_rin), D.dev<uint32_t>(o_rlen), out, D.dev<uint64_t>(o_rout), nr, s));
+    TRY_HIP(D.fetch<uint32_t>(o_colen, nc, s));
+    TRY_HIP(D.fetch<int32_t>(o_cst, nc, s));
     TRY_HIP(hipStreamSynchronize(s));
+    const uint32_t* olen = D.host<uint32_t>(o_colen);
+    const int32_t* st = D.host<int32_t>(o_cst);
     uint64_t produced = 0;
     for (uint32_t i = 0, ci = 0, ri = 0; i < n; i++) {
         uint32_t got;
-        if (h_word[(size_t)(lo + i)] & UNCOMPRESSED_BIT) got = r_len[ri++];
+        if (h_word[(size_t)(lo + i)] & BLOCK_UNCOMPRESSED_SIZE_BIT) got = r_len[ri++];
         else {
             if (st[ci] != 0) { if (detail) detail->inner = st[ci]; return -LZ4FLEX_FE_DECOMPRESSION; }
             got = olen[ci++];
