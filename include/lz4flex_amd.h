@@ -86,7 +86,9 @@ const char *lz4flex_build_id(void);
  * the setting "decompress_shared_dict" (no workspace), then the packed entries lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed
  * with lz4flex_packed_work_size, lz4flex_compress_packed_scratch_bound and the read-only setting "packed_scan_tile" (no workspace in the
  * context: the caller brings it), then the dictionary sets lz4flex_dict_set_create / _free / _count with lz4flex_compress_batch_dict_set and
- * lz4flex_decompress_batch_dict_set (no workspace in the context: a set owns its memory) -- a caller detects them by the symbol. */
+ * lz4flex_decompress_batch_dict_set (no workspace in the context: a set owns its memory), then the partial decode
+ * lz4flex_decompress_batch_partial / lz4flex_decompress_partial_into with the setting "decompress_partial" (no workspace) -- a caller
+ * detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -135,6 +137,10 @@ int64_t lz4flex_decompress_into(const uint8_t *in, size_t in_len, uint8_t *out, 
 /* block::decompress_into_with_dict, src/block/decompress.rs:462-468 */
 int64_t lz4flex_decompress_into_with_dict(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap,
                                           const uint8_t *dict, size_t dict_len, lz4flex_err_detail *detail);
+/* The first min(size, target) bytes of one block: a one-block host batch of lz4flex_decompress_batch_partial (its contract, below).
+ * Returns the bytes written or -code; there is no OutputTooSmall, so of `detail` only hip_error can be set. */
+int64_t lz4flex_decompress_partial_into(const uint8_t *in, size_t in_len, uint8_t *out, size_t target,
+                                        lz4flex_err_detail *detail /* nullable */);
 /* block::uncompressed_size, src/block/mod.rs:151-157: returns the LE u32 prefix or -EXPECTED_ANOTHER_BYTE */
 int64_t lz4flex_uncompressed_size(const uint8_t *in, size_t in_len);
 /* block::decompress_size_prepended, src/block/decompress.rs:493-496; out_cap must be >= the prefix */
@@ -419,6 +425,54 @@ int lz4flex_decompress_batch_shared_dict(lz4flex_ctx *ctx, const void *in_base, 
                                          uint32_t *out_len, int32_t *status, uint64_t *detail /* nullable */,
                                          const void *dict, uint32_t dict_len, int mem_kind, void *hip_stream);
 
+/* PARTIAL DECODE: the first target[i] bytes of every block of a batch (a record header, the first rows of a page, a format sniff over
+ * thousands of stored blocks) -- C liblz4's LZ4_decompress_safe_partial as a batch; its cost is that of the bytes asked for, not of the
+ * block.  mem_kind: LZ4FLEX_MEM_HOST (staged, synchronous; the output staging is sized from target[], not from the blocks) or
+ * LZ4FLEX_MEM_DEVICE (every pointer device memory, asynchronous on hip_stream, allocates nothing); LZ4FLEX_MEM_BIG_BLOCKS may be ORed in
+ * (a hint: results do not depend on it); LZ4FLEX_MEM_CHAINED is refused.  No dictionaries, no out_pos prefixes, no chains.
+ *   The contract, for block i of n = in_len[i] bytes and target = target[i] (lines: src/block/decompress.rs):
+ *       if n == 0: ExpectedAnotherByte                                     (:207-209, before anything else)
+ *       op = 0
+ *       while op < target:
+ *           token; literal length with all its length bytes                 (ExpectedAnotherByte if the input ends inside them)
+ *           if lit > n - ip: LiteralOutOfBounds                             (the FULL length is checked, in the reference's order)
+ *           copy min(lit, target - op) literals; op += that; ip += lit
+ *           if op == target: stop, status 0
+ *           if ip >= n: stop, status 0                                      (the block's normal end, :366-368)
+ *           if n - ip < 2: ExpectedAnotherByte
+ *           offset; if 0: OffsetZero
+ *           match length with all its length bytes                          (ExpectedAnotherByte if the input ends inside them)
+ *           if offset > op: OffsetOutOfBounds
+ *           copy min(ml, target - op) match bytes (byte-serial forward semantics, overlap included); op += that
+ *           if op == target: stop, status 0                                 (the "a match is followed by a token" check is NOT made here)
+ *           if ip >= n: ExpectedAnotherByte                                 (:439-443)
+ *       out_len = op, status 0
+ *   - A valid block of size S: out_len = min(S, target), the bytes are the first out_len bytes lz4flex_decompress_batch produces, status
+ *     0.  target >= S behaves as lz4flex_decompress_batch with out_cap = target.
+ *   - There is no LZ4FLEX_E_OUTPUT_TOO_SMALL and no detail array: target is a wish, not a capacity that can be violated.
+ *   - An error the reference would meet before target bytes exist is reported, in the reference's order; an error behind that point is
+ *     not seen.  target == 0 on a non-empty block: status 0, out_len 0, nothing is read.
+ *   - On error out_len is 0 and the target bytes of the sink may hold anything.
+ *   - Nothing is ever written at or behind out_off[i] + target[i], nothing in front of out_off[i].  This is strict: the sink ends at target.
+ *   The kernels: the sequence decoder (lz4_decompress_seq.hip: a wavefront per block, a lane per sequence) in its partial form at every n:
+ *     a chunk of sequences is cut in front of the one that reaches or crosses the target, that one is executed alone by the wavefront,
+ *     clipped, and the block's tile loop ends there -- no tile of 3 840 compressed bytes behind the one that holds the stop is staged or
+ *     walked.  Blocks it hands back (an empty block, more than 4 GiB - 64 KiB of input, errors in front of the stop, an irregular
+ *     token list -- also one whose irregularity lies behind the stop, inside the stop's tile) are decoded again in the reference's order,
+ *     sixteen lanes per block, up to their target (lz4_decompress.hip lz4_decompress_partial_kernel: the definition above, literally).
+ *     Setting "decompress_partial" (default 1): 0 = every block in the reference's order, sixteen lanes per block (A/B measurements,
+ *     tests); "decompress_variant" 1 pinned has the same effect.  "decompress_second_pass" 0 leaves handed-back blocks marked 0x7F000001.
+ *     Measured on an MI355X (tools/partial_bench.py, one session, profiles/r13_partial.txt; 64 KiB JSON tiles, device-resident, ms per
+ *     call for 4 096 / 16 384 blocks): a full decode 0.48 / 1.66; this entry at target 64: 0.056 / 0.143, at 4 096: 0.082 / 0.232, at
+ *     65 536: 0.49 / 1.74 (level with the plain sequence decoder, 0.49 / 1.74).  "decompress_partial" 0 at the same targets: 0.010 /
+ *     0.011, 0.47 / 0.65, 5.9 / 8.5 -- the reference's order wins where the target is a few dozen bytes (the sequence decoder stages and
+ *     walks one whole tile of 3 840 compressed bytes whatever the target) and loses from a few KiB on.
+ * Returns 0 or -code for call-level failures (-LZ4FLEX_E_INVALID_ARG: a missing array, a mem_kind other than HOST / DEVICE
+ * (| BIG_BLOCKS); the arguments are checked before a context is looked at); n == 0 returns 0; -LZ4FLEX_E_NO_DEVICE without a device. */
+int lz4flex_decompress_batch_partial(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                     uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *target,
+                                     uint32_t *out_len, int32_t *status, int mem_kind, void *hip_stream);
+
 /* ---- dictionary sets: K prepared dictionaries, one id per block ----------------------------------------------------------------
  * The *_shared_dict entries prepare their one dictionary again on every call (the digest kernel, one wavefront; a MEM_HOST call
  * stages the dictionary again), and a batch whose records belong to a handful of dictionaries -- one per table or per column -- has
@@ -525,7 +579,7 @@ int lz4flex_decompress_batch_dict_set(lz4flex_ctx *ctx, const void *in_base, con
  *   a call that holds at least this many Linked streams decodes block k of every stream in ONE launch -- a plain batch whose prefixes
  *   the launches before it have written -- instead of a workgroup per block that polls its predecessor: thousands of short streams,
  *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict);
- *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict);
+ *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict); "decompress_partial" (see lz4flex_decompress_batch_partial);
  *   "packed_scan_tile" (read-only: the sizes one workgroup of the packed entries' offset scan takes, see the packed batches).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
  * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.

@@ -232,6 +232,22 @@ def decompress_with_dict(input, min_uncompressed_size, ext_dict):
     return bytes(out[:n])
 
 
+def decompress_partial(input, n):
+    """The first min(size, n) bytes of the block `input` (lz4flex_decompress_partial_into: liblz4's LZ4_decompress_safe_partial).  An
+    error the reference would meet before n bytes exist is raised as block::decompress raises it; one behind that point is not seen,
+    and there is no OutputTooSmall."""
+    lib = L.load()
+    ip, ilen, _k = _buf(input)
+    out = bytearray(max(int(n), 1))
+    o = (C.c_uint8 * len(out)).from_buffer(out)
+    d = L.ErrDetail()
+    r = lib.lz4flex_decompress_partial_into(ip, ilen, C.cast(o, C.c_void_p), int(n), C.byref(d))
+    del o
+    if r < 0:
+        _raise_decode(int(-r), d)
+    return bytes(out[:r])
+
+
 def uncompressed_size(input):
     """block::uncompressed_size (mod.rs:151-157): (size, rest)"""
     if len(input) < 4:
@@ -423,6 +439,37 @@ def decompress_blocks_device(src, in_off, in_len, stream=None):
     device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and an empty slot.
     A block of more than 4 GiB - 1 decompressed bytes (the decoders' u32 out_cap) raises ValueError."""
     return _size_then_decode_device("lz4flex_decompress_batch", src, in_off, in_len, stream)
+
+
+# ---- partial decode: the first target[i] bytes of every block (lz4flex_decompress_batch_partial) ------------------------------------
+def decompress_batch_partial(in_buf, in_off, in_len, out_buf, out_off, target, ctx=None):
+    """lz4flex_decompress_batch_partial over host buffers: the first min(size, target[i]) bytes of block in_buf[in_off[i] : + in_len[i]]
+    into out_buf[out_off[i] : + target[i]]; nothing is written behind target[i] bytes of a sink.  Returns (out_len[u32], status[i32]):
+    there is no OutputTooSmall and no detail."""
+    return _host_call("lz4flex_decompress_batch_partial", ctx, in_buf, in_off, in_len, (out_buf, out_off, target))
+
+
+def decompress_blocks_partial_device(src, in_off, in_len, target, stream=None):
+    """Raw blocks in device memory, the first target[i] bytes of each: src is a uint8 torch tensor on the GPU, in_off / in_len / target
+    integer tensors.  The output is packed by an exclusive prefix sum of `target` (ONE host synchronisation: the total, to allocate
+    exactly that), then one lz4flex_decompress_batch_partial (MEM_DEVICE, asynchronous on `stream`, default the current one).  Returns
+    (out, out_off, out_len, status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]], out_len[i] =
+    min(size, target[i]); a block that fails in front of its target gets its status and out_len 0."""
+    import torch
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
+    if int(target.numel()) != n:
+        raise ValueError("in_off and target differ in length")
+    want = target.to(device=dev, dtype=torch.int64) & 0xFFFFFFFF
+    out_off = torch.cumsum(want, 0) - want
+    total = int(want.sum()) if n else 0                  # the one synchronisation
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n:
+        d_target = torch.where(want >= 0x80000000, want - 0x100000000, want).to(torch.int32).contiguous()     # (the bit pattern of a u32)
+        _device_call("lz4flex_decompress_batch_partial", [src, d_off, d_len], n, [out, out_off, d_target, out_len, status],
+                     False, sp)
+    return out[:total], out_off, out_len, status
 
 
 # ---- per-block dictionaries (lz4flex_*_batch_ex) --------------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 //   run_device_batch MEM_DEVICE: the caller's BatchCall as it is, on the caller's stream;
 //   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode (the
 //                    SharedDictArgs set-up, launch_compress_any) and launch_decode (the chain bracket and the choice between the
-//                    shared-dictionary, the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
+//                    shared-dictionary, the partial, the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
 //                    shape, launch_redo is the second pass behind every first-pass decoder).
 // The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
 // DeviceGuard, Layout, GrowBuf) are in lz4_ctx.h; the integer settings are one table (SETTINGS) that lz4flex_set_tuning and
@@ -97,6 +97,7 @@ enum class Redo {
     Chain,        // launch_decompress_chain_redo: a chained batch's marked blocks depend on each other -- in chain order
     SharedDict,   // launch_decompress_shared_dict: with the batch's one dictionary
     DictSet,      // launch_decompress_dict_set: with each block's dictionary out of the batch's set
+    Partial,      // launch_decompress_partial: out_cap is a target (lz4flex_decompress_batch_partial)
 };
 static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, Redo how = Redo::Blocks, const uint8_t* dict = nullptr,
                               uint32_t dict_len = 0, const DictSetArgs* set = nullptr) {
@@ -106,6 +107,7 @@ static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream
     if (how == Redo::Chain) return launch_decompress_chain_redo(r, s);
     if (how == Redo::DictSet) return launch_decompress_dict_set(r, *set, s);
     if (how == Redo::SharedDict) return launch_decompress_shared_dict(r, dict, dict_len, s);
+    if (how == Redo::Partial) return launch_decompress_partial(r, s);
     return launch_decompress(r, c->dec_lanes, s);
 }
 
@@ -221,6 +223,15 @@ static hipError_t launch_decompress_set(lz4flex_ctx* c, const DecompressArgs& a,
     if (!c->dec_shared || c->dec_variant == 1) return launch_decompress_dict_set(a, set, s);
     const hipError_t e = launch_decompress_seq_dict_set(a, set, DECODE_REDO, s);
     return e != hipSuccess ? e : launch_redo(c, a, s, Redo::DictSet, nullptr, 0, &set);
+}
+
+// lz4flex_decompress_batch_partial: a.out_cap holds the targets.  The sequence decoder's partial form at every n (its work is bounded by
+// the target, not by the block); the blocks it marks are decoded again in the reference's order, up to their target.
+// "decompress_partial" 0 / "decompress_variant" 1: that order for every block.
+static hipError_t launch_decompress_partial_any(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s) {
+    if (!c->dec_partial || c->dec_variant == 1) return launch_decompress_partial(a, s);
+    const hipError_t e = launch_decompress_seq_partial(a, DECODE_REDO, s);
+    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::Partial);
 }
 
 // Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
@@ -439,6 +450,7 @@ struct BatchCall {
     uint32_t n_chains = 0;
     bool has_ext = false;                   // the caller handed an extension struct over, whatever it holds: such a host batch takes the general path
     bool chained = false;                   // LZ4FLEX_MEM_CHAINED
+    bool partial = false;                   // lz4flex_decompress_batch_partial: out_cap holds TARGETS (no dictionary, prefix or chain; no detail)
     bool big = false;                       // LZ4FLEX_MEM_BIG_BLOCKS, or -- host batches -- what the lengths say
     hipStream_t stream = nullptr;           // DEVICE batches: the caller's (NULL = HIP's null stream); host batches: the context's
 };
@@ -489,7 +501,8 @@ static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
         a.debug_giveup = (uint32_t)c->chain_giveup;
     }
     hipError_t le;
-    if (b.set) le = launch_decompress_set(c, a, set_args_of(c, b), s);
+    if (b.partial) { a.detail = nullptr; le = launch_decompress_partial_any(c, a, s); }
+    else if (b.set) le = launch_decompress_set(c, a, set_args_of(c, b), s);
     else if (b.shared_dict && b.shared_len) le = launch_decompress_shared(c, a, b.shared_dict, b.shared_len, s);
     // "decompress_variant" 1 and blocks with dictionaries: the reference-order kernel (a chain has no such form)
     else le = ((c->dec_variant != 1 || b.chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, b.big) : launch_decompress(a, c->dec_lanes, s);
@@ -660,6 +673,7 @@ const Setting SETTINGS[] = {
     {"size_scan_serial", &lz4flex_ctx::size_serial, is_flag, false},
     {"compress_shared_dict", &lz4flex_ctx::comp_shared, is_flag, false},
     {"decompress_shared_dict", &lz4flex_ctx::dec_shared, is_flag, false},
+    {"decompress_partial", &lz4flex_ctx::dec_partial, is_flag, false},
     // (the sizes one workgroup of the packed entries' offset scan takes: lz4_device.h PACKED_SCAN_TILE; the tests cut their batches around it)
     {"packed_scan_tile", &lz4flex_ctx::packed_tile, read_only, false},
     // (what "compress_subwindows" 0 decides by: n * 4 <= this -> 4, n * 3 <= this -> 3, n * 2 <= this -> 2)
@@ -835,7 +849,7 @@ static int run_host_small(lz4flex_ctx* c, const BatchCall& b) {
     BatchCall dv = batch_of(b.compress, d + at_in, (const uint64_t*)(d + at_in_off), (const uint32_t*)(d + at_in_len), n, d + at_out,
                             (const uint64_t*)(d + at_out_off), (const uint32_t*)(d + at_out_cap), (uint32_t*)(d + at_out_len),
                             (int32_t*)(d + at_status), s);
-    dv.big = host_big(b);
+    dv.big = host_big(b); dv.partial = b.partial;
     dv.flags = b.flags ? (const uint32_t*)(d + at_flags) : nullptr;
     dv.detail = (uint64_t*)(d + at_detail);
     if ((rc = launch_batch(c, dv))) return rc;
@@ -935,7 +949,7 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
     BatchCall dv = batch_of(b.compress, d + a_in, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, d + a_out,
                             (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap), (uint32_t*)(dd + at_out_len),
                             (int32_t*)(dd + at_status), s);
-    dv.chained = b.chained; dv.big = host_big(b);
+    dv.chained = b.chained; dv.big = host_big(b); dv.partial = b.partial;
     dv.flags = b.flags ? (const uint32_t*)(dd + at_flags) : nullptr;
     dv.detail = (uint64_t*)(dd + at_detail);
     if (has_dict) { dv.dict_base = d + a_dict; dv.dict_off = (const uint64_t*)(dd + at_dict_off); dv.dict_len = (const uint32_t*)(dd + at_dict_len); }
@@ -1172,6 +1186,19 @@ int lz4flex_decompress_batch_shared_dict(lz4flex_ctx* ctx, const void* in_base, 
     if (n == 0) return 0;
     if (!dict || !dict_len)
         return lz4flex_decompress_batch(ctx, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, detail, mem_kind, hip_stream);
+    const int rc = begin_batch(&ctx);
+    return rc ? rc : run_batch(ctx, b, k);
+}
+
+int lz4flex_decompress_batch_partial(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                     void* out_base, const uint64_t* out_off, const uint32_t* target, uint32_t* out_len, int32_t* status,
+                                     int mem_kind, void* hip_stream) {
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, target, out_len, status, hip_stream);
+    b.partial = true;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
     const int rc = begin_batch(&ctx);
     return rc ? rc : run_batch(ctx, b, k);
 }
@@ -1741,6 +1768,24 @@ int64_t lz4flex_decompress_into(const uint8_t* in, size_t in_len, uint8_t* out, 
 int64_t lz4flex_decompress_into_with_dict(const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap,
                                           const uint8_t* dict, size_t dict_len, lz4flex_err_detail* detail) {
     return decompress_common(in, in_len, out, out_cap, dict, dict_len, true, detail);
+}
+
+// a one-block host batch of lz4flex_decompress_batch_partial (no OutputTooSmall: of `detail`, hip_error alone can be set)
+int64_t lz4flex_decompress_partial_into(const uint8_t* in, size_t in_len, uint8_t* out, size_t target, lz4flex_err_detail* detail) {
+    if (in_len > 0xFFFFFFFFull || target > 0xFFFFFFFFull) return -LZ4FLEX_E_INVALID_ARG;
+    if (detail) memset(detail, 0, sizeof *detail);
+    lz4flex_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
+    const uint32_t len = (uint32_t)in_len, want = (uint32_t)target;
+    uint32_t olen = 0;
+    int32_t st = 0;
+    static uint8_t sink_dummy = 0;
+    BatchCall b = batch_of(false, in ? in : &EMPTY, &OFF0, &len, 1, out ? out : &sink_dummy, &OFF0, &want, &olen, &st);
+    b.partial = true;
+    rc = run_host_batch(c, b);
+    if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
+    return st ? -(int64_t)st : (int64_t)olen;
 }
 
 int lz4flex_xxh32_batch_device(const void* base, const uint64_t* off, const uint32_t* len, uint32_t n, uint32_t seed,

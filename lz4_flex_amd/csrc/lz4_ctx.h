@@ -130,6 +130,7 @@ struct lz4flex_ctx {
     bool shared_counted = false;  // the last shared-dictionary call ran the throughput encoder: its digest counter is what "debug_shared_dict_items" reads
     const struct lz4flex_dict_set* set_counted = nullptr;   // the set of the last lz4flex_compress_batch_dict_set call that ran the throughput encoder: what "debug_dict_set_items" reads (capi.cpp checks that it still exists)
     int dec_shared = 1;           // "decompress_shared_dict": 1 = lz4flex_decompress_batch_shared_dict runs the sequence decoder's dictionary form; 0 = every block through decode_block<16, true>, the per-block path (A/B measurements, tests)
+    int dec_partial = 1;          // "decompress_partial": 1 = lz4flex_decompress_batch_partial runs the sequence decoder's partial form; 0 = every block through decode_block<16, false, true>, the reference's order (A/B measurements, tests)
     int packed_tile = 0;          // "packed_scan_tile" (read-only): the sizes one workgroup of the packed entries' offset scan takes
     int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
 };

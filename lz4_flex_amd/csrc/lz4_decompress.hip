@@ -95,7 +95,11 @@ __device__ __forceinline__ void group_copy_periodic(uint8_t* dst, uint32_t offse
 }
 
 // Decode one block with a group of G lanes. Returns the status code; *produced = bytes written.
-template <int G, bool USE_DICT>
+// PARTIAL (lz4flex_decompress_batch_partial; not with a dictionary or a sink position): `cap` is a TARGET, not a capacity -- the block
+// is decoded until `cap` bytes exist or it ends, whichever comes first.  The sequence that crosses the target is clipped to it and
+// ends the decode with status 0 (no OutputTooSmall); every check the reference makes before that point is made in its order, nothing
+// behind it is looked at, and no byte at or behind out + cap is written.
+template <int G, bool USE_DICT, bool PARTIAL = false>
 __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, uint32_t ilen, uint8_t* out,
                                                 uint32_t out_pos, uint32_t cap, const uint8_t* __restrict__ dict,
                                                 uint32_t dict_len, uint32_t g, uint32_t* produced,
@@ -107,6 +111,7 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
     if (!USE_DICT) dict_len = 0u;
     uint32_t ip = 0u, op = out_pos;
     for (;;) {
+        if (PARTIAL && op >= cap) break;   // the target is reached: what follows is not looked at
         // ---- token + (when far from the input end) an 8-byte window of what follows --------
         const bool win = ip + 8u <= ilen;
         uint64_t w;
@@ -130,8 +135,11 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
             }
             if (lit > ilen - ip) return LZ4FLEX_DEV_E_LITERAL_OUT_OF_BOUNDS;
             if (lit > cap - op) {
-                *det_expected = (uint64_t)op + lit;
-                return LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+                if (!PARTIAL) {
+                    *det_expected = (uint64_t)op + lit;
+                    return LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+                }
+                lit = cap - op;           // the run crosses the target: its first cap - op bytes, exactly (no 8-byte store, no wild copy below)
             }
             if (win && lit <= 7u && cap - op >= 8u) {
                 // the literals are bytes 1..lit of the window: one 8-byte store by lane 0; the
@@ -143,6 +151,7 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
             }
             op += lit;
             ip += lit;
+            if (PARTIAL && op >= cap) break;   // (ip means nothing behind a clipped run: the decode is over)
         }
         if (ip >= ilen) break;   // decompress.rs:366-368: normal end, last sequence is literal-only
         // ---- offset + match length (decompress.rs:373-391) ---------------------------------
@@ -163,16 +172,22 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
             }
             if (acc > 0xFFFFFFFFull) {   // (same order as below: the offset check comes first)
                 if (offset > op + dict_len) return LZ4FLEX_DEV_E_OFFSET_OUT_OF_BOUNDS;
-                *det_expected = (uint64_t)op + acc;
-                return LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+                if (!PARTIAL) {
+                    *det_expected = (uint64_t)op + acc;
+                    return LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+                }
+                acc = 0xFFFFFFFFull;      // (clipped to the target below)
             }
             ml = (uint32_t)acc;
         }
         // ---- bounds (decompress.rs:398-408; unsafe-flavour order) --------------------------
         if (offset > op + dict_len) return LZ4FLEX_DEV_E_OFFSET_OUT_OF_BOUNDS;
         if (ml > cap - op) {
-            *det_expected = (uint64_t)op + ml;
-            return LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+            if (!PARTIAL) {
+                *det_expected = (uint64_t)op + ml;
+                return LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+            }
+            ml = cap - op;                // the match crosses the target: its first cap - op bytes (wild is false below: ml + 3 > cap - op)
         }
         // ---- external dictionary part (decompress.rs:410-426, copy_from_dict :85-109) ------
         if (USE_DICT && offset > op) {
@@ -196,6 +211,7 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
         }
         wave_fence();
         op += ml;
+        if (PARTIAL && op >= cap) break;   // a match that ends at the target is not asked for the token behind it
         if (ip >= ilen) return LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE;   // decompress.rs:439-443
     }
     *produced = op - out_pos;
@@ -231,6 +247,33 @@ __global__ void __launch_bounds__(256) lz4_decompress_blocks_kernel(DecompressAr
             a.detail[2u * b + 1u] = st == LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL ? (uint64_t)cap : 0u;
         }
     }
+}
+
+// lz4flex_decompress_batch_partial in the reference's order: decode_block<16, false, true> with out_cap[b] as block b's target.  The
+// definition of the entry's results ("decompress_partial" 0, "decompress_variant" 1: every block) and the second pass behind the
+// sequence decoder's partial form (only_status != 0: the blocks it marked).  No detail: there is no OutputTooSmall.
+__global__ void __launch_bounds__(256) lz4_decompress_partial_kernel(DecompressArgs a) {
+    constexpr int G = 16;
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t b = tid / G;
+    const uint32_t g = tid % G;
+    if (b >= a.n) return;
+    if (a.only_status != 0 && a.status[b] != a.only_status) return;
+    uint32_t produced = 0u;
+    uint64_t expected = 0u;
+    const int32_t st = decode_block<G, false, true>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, a.out_cap[b], nullptr, 0u, g,
+                                                    &produced, &expected);
+    if (g == 0u) {
+        a.status[b] = st;
+        a.out_len[b] = st == 0 ? produced : 0u;
+    }
+}
+
+hipError_t launch_decompress_partial(const DecompressArgs& a, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lz4_decompress_partial_kernel, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a);
+    return hipGetLastError();
 }
 
 // lz4flex_decompress_batch_shared_dict: decode_block<16, true> with ONE dictionary for every block -- no per-block dictionary arrays, no

@@ -24,6 +24,16 @@
 //     written back 16 bytes per lane.  Sequences that do not fit a lane (literal runs > 64, matches > 273 bytes or overlapping
 //     their source, far matches > 64, anything with more than one length byte) are executed ALONE by the whole wavefront
 //     (exact_seq: decompress.rs:334-443 for one sequence of any shape) and cut the chunk in front of them.
+// PARTIAL form (lz4flex_decompress_batch_partial: the first target[b] bytes of block b; source tag Partial, no dictionary, no prefix): the
+// block's "capacity" is its TARGET and reaching it is the normal end.  setup_chunk cuts a chunk in front of the first sequence that
+// reaches or crosses the target -- before any of the chunk's checks are looked at, so nothing behind the stop can be an error -- and that
+// sequence is executed alone by the wavefront (exact_seq_partial: the reference's checks in their order, the copy clipped to the target,
+// status 0, no "a match is followed by a token" check for a match that ends at the target).  run_chunks and the tile loop leave through
+// `stopped`, which is not "the block ended": no tile behind the one that holds the stop is staged or walked -- the work is the target's,
+// not the block's.  The walk (lz4_seq_walk.h, unchanged) still covers the WHOLE tile that holds the stop before a chunk runs: if it finds
+// no chain in the bytes behind the stop (X_ERR), the block is handed back like any irregular one, and lz4_decompress_partial_kernel
+// (lz4_decompress.hip), which never looks behind the stop, decides it -- correct, and slower for that block only.  Nothing is stored at or
+// behind out + target: the window is written back in whole 16-byte units below OP and byte by byte up to OP, and OP never passes the target.
 // LDS per wavefront: token list 2 560 + tile 4 080 + window 3 584 + 16 = 10 240 bytes: 16 wavefronts per CU (4 096 blocks are one round of
 // wavefronts; 8 KiB windows -- 11 per CU, a fifth of the far matches -- were a quarter slower: DESIGN.md 5.2, profiles/r06_seq_decoder.txt).
 #include <hip/hip_runtime.h>
@@ -97,7 +107,7 @@ __device__ __forceinline__ void write_exact16(uint32_t dst, const u32x4& v, uint
 // output, positions below LO = PV - dl do not exist.  `out` and `dv` are both biased by -PV: a position p >= PV is out[p] (every
 // store: F starts at PV, a multiple of 16, so write_back's units lie where they lie without a dictionary and none begins in front of
 // the sink), a position in [LO, PV) is dv[p] (loads only).  A 16-byte load that straddles PV is put together byte by byte.
-template <class G, bool DICT = false>
+template <class G, bool DICT = false, bool PARTIAL = false>
 struct Dec {
     const g_u8* in;
     g_u8* out;
@@ -346,6 +356,58 @@ struct Dec {
         if (ip >= ilen) return false;              // a match is always followed by another token (decompress.rs:439-443)
         return true;
     }
+    // PARTIAL: the same with `cap` as the target (OP < cap on entry).  The lengths are checked in full, in the reference's order, and
+    // copied clipped to cap - OP; a copy that reaches the target ends the decode there (SEQ_STOP) and nothing behind it is looked at.
+    // (the outcome is a value, not two flags by reference: flags whose address is taken by a real call live in scratch memory)
+    enum : uint32_t { SEQ_BAD = 0u, SEQ_MORE = 1u, SEQ_END = 2u, SEQ_STOP = 3u };
+    __device__ uint32_t exact_seq_partial(uint32_t ip) {
+        const uint32_t t = uni(in[ip]);
+        ip += 1u;
+        uint32_t lit = t >> 4;
+        if (lit == 15u) {
+            for (;;) {
+                if (ip >= ilen) return SEQ_BAD;
+                const uint32_t b = uni(in[ip]);
+                ip += 1u;
+                lit += b;
+                if (lit > 0x7FFFFFFFu) return SEQ_BAD;
+                if (b != 255u) break;
+            }
+        }
+        if (lit > ilen - ip) return SEQ_BAD;
+        {
+            const uint32_t c = lit < cap - OP ? lit : cap - OP;
+            if (OP + c > POS_LIMIT) return SEQ_BAD;
+            coop_literals(ip, c);
+        }
+        if (OP >= cap) return SEQ_STOP;
+        ip += lit;
+        if (ip >= ilen) return SEQ_END;
+        if (ilen - ip < 2u) return SEQ_BAD;
+        const uint32_t offset = uni((uint32_t)in[ip] | ((uint32_t)in[ip + 1u] << 8));
+        ip += 2u;
+        if (offset == 0u) return SEQ_BAD;
+        uint32_t ml = 4u + (t & 15u);
+        if (ml == 19u) {
+            for (;;) {
+                if (ip >= ilen) return SEQ_BAD;
+                const uint32_t b = uni(in[ip]);
+                ip += 1u;
+                ml += b;
+                if (ml > 0x7FFFFFFFu) return SEQ_BAD;
+                if (b != 255u) break;
+            }
+        }
+        if (offset > OP) return SEQ_BAD;
+        {
+            const uint32_t c = ml < cap - OP ? ml : cap - OP;
+            if (OP + c > POS_LIMIT) return SEQ_BAD;
+            coop_match(offset, c);
+        }
+        if (OP >= cap) return SEQ_STOP;      // (a match that ends at the target is not asked for the token behind it)
+        if (ip >= ilen) return SEQ_BAD;
+        return SEQ_MORE;
+    }
 };
 
 // A chunk: up to 64 consecutive sequences of the tile's token list, lane = sequence, placed but not yet copied
@@ -359,8 +421,9 @@ struct Chunk {
 
 // Set-up of the chunk that starts at sequence sidx with `op` bytes in front of it -- of which the last `pending` are still being
 // produced by the chunk before (room for both is made here: a slide never moves a placed chunk).  false: the block is irregular.
-template <class G, bool DICT>
-__device__ __forceinline__ bool setup_chunk(Dec<G, DICT>& D, uint32_t t0, uint32_t n_tile, uint32_t sidx, uint32_t op, uint32_t pending, Chunk& C) {
+// PARTIAL (op < D.cap, the target): the chunk ends in front of the first sequence that reaches or crosses the target.
+template <class G, bool DICT, bool PARTIAL>
+__device__ __forceinline__ bool setup_chunk(Dec<G, DICT, PARTIAL>& D, uint32_t t0, uint32_t n_tile, uint32_t sidx, uint32_t op, uint32_t pending, Chunk& C) {
     const uint32_t lane = D.lane;
     const uint32_t ilr = D.ilen - t0;                          // the block's end, relative to t0
     const uint32_t nrem = n_tile - sidx;
@@ -384,6 +447,12 @@ __device__ __forceinline__ bool setup_chunk(Dec<G, DICT>& D, uint32_t t0, uint32
     {
         const uint64_t over = ballot(incl > G::BUDGET) & low_mask(nact);
         if (over != 0ull) nact = ctz64(over);
+    }
+    if constexpr (PARTIAL) {
+        // the sequences that end STRICTLY before the target (one that ends at it stops the decode and must not get the "followed by a
+        // token" check errm carries for its lane): the cut comes before errm is looked at -- what lies behind the stop is no error
+        const uint64_t reach = ballot(incl >= D.cap - op) & low_mask(nact);
+        if (reach != 0ull) nact = ctz64(reach);
     }
     uint32_t T = nact != 0u ? rdlane(incl, nact - 1u) : 0u;
     C.tp0 = rdlane(tpr, 0u);
@@ -478,8 +547,8 @@ __device__ __forceinline__ void lane_copy(const CopyPlan& P, uint64_t m) {
 }
 
 // The copies of a placed chunk (decompress.rs:276-280, 314-325, 357-361, 410-437).
-template <class G, bool DICT>
-__device__ __forceinline__ void exec_chunk(Dec<G, DICT>& D, const Chunk& C SQ_PROF_ARG) {
+template <class G, bool DICT, bool PARTIAL>
+__device__ __forceinline__ void exec_chunk(Dec<G, DICT, PARTIAL>& D, const Chunk& C SQ_PROF_ARG) {
     const uint32_t wb = LDS_WIN - D.W0;                        // window address of output position 0
     const uint32_t wl = wb + C.dst, wm = wl + C.lit;
     // ---- literals: 16 bytes per access, exact length ---------------------------------------------------------------------------
@@ -531,20 +600,26 @@ __device__ __forceinline__ void exec_chunk(Dec<G, DICT>& D, const Chunk& C SQ_PR
 
 // The chunks of one tile: sequences [0, n_tile) of the token list.  Two chunks are in flight: the next one is set up (token decode,
 // placement, checks, room in the window, requests for far sources) before the current one is copied.  false: the block is irregular.
-template <class G, bool DICT>
-__device__ __forceinline__ bool run_chunks(Dec<G, DICT>& D, uint32_t t0, uint32_t n_tile, bool& done SQ_PROF_ARG) {
+// PARTIAL: `stopped` = the target is reached (anywhere in the tile: the sequences behind the stop are not looked at), else as `done`.
+template <class G, bool DICT, bool PARTIAL>
+__device__ __forceinline__ bool run_chunks(Dec<G, DICT, PARTIAL>& D, uint32_t t0, uint32_t n_tile, bool& done, [[maybe_unused]] bool& stopped SQ_PROF_ARG) {
     uint32_t sidx = 0u;
     Chunk C;
-    if (!setup_chunk<G, DICT>(D, t0, n_tile, 0u, D.OP, 0u, C)) return false;
+    if (!setup_chunk<G, DICT, PARTIAL>(D, t0, n_tile, 0u, D.OP, 0u, C)) return false;
     SQ_TICK(4)
     for (;;) {
         if (C.nact == 0u) {                                    // the sequence alone, by the whole wavefront
-            if (!D.exact_seq(t0 + C.tp0, done)) return false;
+            if constexpr (PARTIAL) {
+                const uint32_t r = D.exact_seq_partial(t0 + C.tp0);
+                if (r == D.SEQ_BAD) return false;
+                if (r == D.SEQ_STOP) { stopped = true; return true; }
+                done = r == D.SEQ_END;
+            } else if (!D.exact_seq(t0 + C.tp0, done)) return false;
             sidx += 1u;
             SQ_TICK(9) SQ_COUNT(19, 1)
             if (done) return sidx == n_tile;
             if (sidx >= n_tile) return true;
-            if (!setup_chunk<G, DICT>(D, t0, n_tile, sidx, D.OP, 0u, C)) return false;
+            if (!setup_chunk<G, DICT, PARTIAL>(D, t0, n_tile, sidx, D.OP, 0u, C)) return false;
             SQ_TICK(4)
             continue;
         }
@@ -554,10 +629,10 @@ __device__ __forceinline__ bool run_chunks(Dec<G, DICT>& D, uint32_t t0, uint32_
         N.nact = 0u; N.T = 0u; N.tp0 = 0u; N.last = false; N.act = 0ull; N.haslit = 0ull; N.near = 0ull; N.far = 0ull;
         N.lit = 0u; N.ml = 0u; N.dst = 0u; N.src = 0u; N.lsr = 0u;
         N.f0 = u32x4{0u, 0u, 0u, 0u}; N.f1 = N.f0; N.f2 = N.f0; N.f3 = N.f0;
-        if (have_next) { if (!setup_chunk<G, DICT>(D, t0, n_tile, nsidx, nop, C.T, N)) return false; }
+        if (have_next) { if (!setup_chunk<G, DICT, PARTIAL>(D, t0, n_tile, nsidx, nop, C.T, N)) return false; }
         SQ_TICK(4)
 #ifndef LZ4S_EXP_NOEXEC         // timing experiments only (wrong bytes): chunks are placed, nothing is copied
-        exec_chunk<G, DICT>(D, C SQ_PROF_PASS);
+        exec_chunk<G, DICT, PARTIAL>(D, C SQ_PROF_PASS);
 #endif
         D.OP = nop;
         sidx = nsidx;
@@ -575,12 +650,15 @@ __device__ __forceinline__ bool run_chunks(Dec<G, DICT>& D, uint32_t t0, uint32_
 // Where the blocks' dictionaries come from.  OneDict: every block of the batch has the ONE dictionary dict[0, dict_len) (device memory,
 // dict_len != 0), and none has a prefix.  DictSetArgs (lz4_device.h): block b has the dictionary its id names in a prepared set -- or none
 // (dl = 0, so PV = LO = 0: the block decodes as it does without the dictionary form), or a refused id.
+// Partial: no dictionary and no prefix, and a.out_cap[b] is block b's TARGET (see the head of the file).
 struct NoDict {};
 struct OneDict { const uint8_t* dict; uint32_t dict_len; };
-template <class SRC> constexpr bool SRC_DICT = !__is_same(SRC, NoDict);
+struct Partial {};
+template <class SRC> constexpr bool SRC_DICT = !__is_same(SRC, NoDict) && !__is_same(SRC, Partial);
 template <class G, class SRC>
 __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code, SRC src) {
     constexpr bool DICT = SRC_DICT<SRC>;
+    constexpr bool PARTIAL = __is_same(SRC, Partial);
     extern __shared__ __attribute__((aligned(16))) uint8_t seq_lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
@@ -604,7 +682,7 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
     }
     // (every LDS access below goes by byte address from 0: the dynamic segment is the kernel's only LDS)
     if ((uint32_t)(uintptr_t)(lds_u8*)seq_lds != 0u) { if (lane == 0u) { a.status[b] = redo_code; a.out_len[b] = 0u; } return; }
-    Dec<G, DICT> D;
+    Dec<G, DICT, PARTIAL> D;
     D.in = (const g_u8*)(a.in_base + a.in_off[b]);
     D.out = (g_u8*)(a.out_base + a.out_off[b]);
     D.ilen = a.in_len[b];
@@ -627,10 +705,14 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
         D.dv = (const g_u8*)((uintptr_t)dict + dict_len - PFX);
         D.out = (g_u8*)((uintptr_t)(a.out_base + a.out_off[b]) - PFX);
         D.cap = (D.cap < POS_LIMIT - PFX ? D.cap : POS_LIMIT - PFX) + PFX;
-    } else {
+    } else if constexpr (!PARTIAL) {
         PFX = a.out_pos != nullptr ? uni(a.out_pos[b]) : 0u;
     }
     const uint32_t ilen = D.ilen;
+    if constexpr (PARTIAL) {
+        // nothing is asked for: nothing is read (an EMPTY block is an error before that, decompress.rs:207-209: handed back below)
+        if (D.cap == 0u && ilen != 0u) { if (lane == 0u) { a.status[b] = 0; a.out_len[b] = 0u; } return; }
+    }
     bool ok = ilen != 0u && ilen <= POS_LIMIT && PFX <= POS_LIMIT / 2u && D.cap >= PFX, done = false;     // (an empty block: decompress.rs:207-209, the reference-order kernel reports it)
     if (PFX != 0u && ok) { D.OP = PFX; D.reload_window(); }
     uint32_t entry = 0u;
@@ -663,12 +745,14 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
         SQ_TICK(3)
         // ---- the chunks -------------------------------------------------------------------------------------------------------------------
         bool tdone = false;
+        [[maybe_unused]] bool stopped = false;
 #ifdef LZ4S_EXP_NOCHUNKS       // timing experiments only (no output): the walks and the token list alone
         if (tile_exit >= ilr) { done = true; break; }
         entry = t0 + tile_exit;
         continue;
 #endif
-        if (!run_chunks<G, DICT>(D, t0, n_tile, tdone SQ_PROF_PASS)) { ok = false; break; }
+        if (!run_chunks<G, DICT, PARTIAL>(D, t0, n_tile, tdone, stopped SQ_PROF_PASS)) { ok = false; break; }
+        if constexpr (PARTIAL) { if (stopped) { done = true; break; } }     // the target is reached: no further tile is staged or walked
         if (tdone) { done = true; break; }
         if (tile_exit >= ilr) { ok = false; break; }        // the chain ran out without a last sequence
         entry = t0 + tile_exit;
@@ -713,6 +797,16 @@ hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* di
     if (dict == nullptr || dict_len == 0u || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
     typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
     hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::OneDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::OneDict{dict, dict_len});
+    return hipGetLastError();
+}
+
+// lz4flex_decompress_batch_partial: a.out_cap[b] is block b's target (the partial form of the kernel: no dictionary, no prefix, no
+// chain).  Irregular blocks get status `redo_code`; the caller runs launch_decompress_partial with only_status = redo_code behind this launch.
+hipError_t launch_decompress_seq_partial(const DecompressArgs& a, int32_t redo_code, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::Partial>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::Partial{});
     return hipGetLastError();
 }
 

@@ -169,6 +169,11 @@ hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t*
 // one decodes in the same launch, a refused id gets its status from whichever of the two sees the block first
 hipError_t launch_decompress_seq_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s);
 hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s);
+// lz4flex_decompress_batch_partial: a.out_cap[b] is block b's TARGET -- the first min(size, target) bytes of every block, no OutputTooSmall,
+// no detail, nothing stored at or behind out_off[b] + target.  The sequence decoder's partial form (irregular blocks are left with
+// status redo_code), and decode_block<16, false, true> in the reference's order: a.only_status 0 = every block, else the marked ones
+hipError_t launch_decompress_seq_partial(const DecompressArgs& a, int32_t redo_code, hipStream_t s);
+hipError_t launch_decompress_partial(const DecompressArgs& a, hipStream_t s);
 hipError_t launch_decompress_split(const DecompressArgs& a, hipStream_t s, int blocks_per_wg = 0);   // parser / copier wavefronts, no dict/prefix
 // parser -> emitter -> quad wavefronts (lz4_decompress_fused.hip: the split decoder's parser, the replay decoder's copy engine, no dict/prefix);
 // blocks of 512 KiB or more are left with status redo_code for a second pass of launch_decompress.  -DLZ4FLEX_TOOLS builds only (round 6)
