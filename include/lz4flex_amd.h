@@ -87,8 +87,10 @@ const char *lz4flex_build_id(void);
  * with lz4flex_packed_work_size, lz4flex_compress_packed_scratch_bound and the read-only setting "packed_scan_tile" (no workspace in the
  * context: the caller brings it), then the dictionary sets lz4flex_dict_set_create / _free / _count with lz4flex_compress_batch_dict_set and
  * lz4flex_decompress_batch_dict_set (no workspace in the context: a set owns its memory), then the partial decode
- * lz4flex_decompress_batch_partial / lz4flex_decompress_partial_into with the setting "decompress_partial" (no workspace) -- a caller
- * detects them by the symbol. */
+ * lz4flex_decompress_batch_partial / lz4flex_decompress_partial_into with the setting "decompress_partial" (no workspace), then the
+ * seekable frames lz4flex_frame_index_create / _free / _blocks / _content_size / _frame_bytes / _info / _table and
+ * lz4flex_frame_read_ranges with the settings "frame_range_pass_bytes" and "frame_range_checksums" (no workspace in the context beyond
+ * the scratch the *_many calls already grow: an index owns its tables) -- a caller detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -580,6 +582,7 @@ int lz4flex_decompress_batch_dict_set(lz4flex_ctx *ctx, const void *in_base, con
  *   the launches before it have written -- instead of a workgroup per block that polls its predecessor: thousands of short streams,
  *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict);
  *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict); "decompress_partial" (see lz4flex_decompress_batch_partial);
+ *   "frame_range_pass_bytes" and "frame_range_checksums" (see lz4flex_frame_read_ranges);
  *   "packed_scan_tile" (read-only: the sizes one workgroup of the packed entries' offset scan takes, see the packed batches).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
  * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.
@@ -706,6 +709,82 @@ int lz4flex_frame_compress_many(lz4flex_ctx *ctx, const void *in_base, const uin
 int lz4flex_frame_decompress_many(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint64_t *in_len, uint32_t n,
                                   void *out_base, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status,
                                   lz4flex_err_detail *detail, int mem_kind, void *hip_stream);
+
+/* ---- seekable frames: a block index and batched byte-range reads -----------------------------------------------------------------
+ * Every other frame entry decodes a frame from its first byte to its last (the reference's FrameDecoder has no other way,
+ * src/frame/decompress.rs:189-342).  The blocks of a BlockMode::Independent frame do not need each other, so a table of where each
+ * block lies and which content bytes it holds is enough to decode only the blocks a byte range touches.
+ * lz4flex_frame_index_create indexes the FIRST frame of frame[0 .. frame_len) (mem_kind LZ4FLEX_MEM_HOST: staged through the context's
+ *   scratch once; LZ4FLEX_MEM_DEVICE: read where it is): the header is parsed on the host (lz4flex_frame_info_read), the BlockInfo words
+ *   are walked on the device (one thread, as lz4flex_frame_walk_device), the decoded size of every compressed block comes from the size
+ *   scan of lz4flex_decompressed_size_batch (nothing is decoded; a stored block's size is its length) and the content offsets from the
+ *   packed entries' offset scan.  The index holds, in device memory it owns and in a host copy: content_off[0 .. blocks] (exclusive
+ *   sums of the decoded sizes; content_off[blocks] = the content size), payload_off[b] (of block b's payload in the frame) and
+ *   len_word[b] (its BlockInfo word: the payload's length, high bit = stored); and the frame info, the content size and frame_bytes,
+ *   the offset behind the EndMark and the content checksum (where a second frame would start; bytes behind it are not read).  Like a
+ *   dictionary set it belongs to the context's DEVICE: any context of that device may read through it, nothing in it is written after
+ *   create, it may be freed before or after the context.  create blocks until the index is ready; the frame may be freed or moved
+ *   afterwards -- lz4flex_frame_read_ranges takes the frame again.
+ *   An index exists only for a structurally sound frame: create returns the negative code, and fills detail, as
+ *   lz4flex_frame_decompress does for the same bytes when no checksum is wrong -- the earliest defect in stream order: the header's
+ *   errors (wrong magic, header checksum, reserved bits, block size, version, dictionary id, a skippable frame first); a compressed
+ *   block that does not scan or decodes to more than the block size, in front of where the walk stopped (that one block is decoded
+ *   once, with a sink of the block size: -LZ4FLEX_FE_DECOMPRESSION, detail = the decoder's inner / expected / actual); a truncated
+ *   frame (-LZ4FLEX_FE_IO; also one that ends where its EndMark should be, which a streaming reader takes for "no more bytes yet",
+ *   src/frame/decompress.rs:231-238) or -LZ4FLEX_FE_BLOCK_TOO_BIG where the walk stopped; -LZ4FLEX_FE_CONTENT_LENGTH when the header's content
+ *   size is not content_off[blocks].  NO CHECKSUM IS LOOKED AT by create.  -LZ4FLEX_E_UNSUPPORTED: BlockMode::Linked frames (a block
+ *   needs the 64 KiB in front of it, transitively: there is nothing to seek in) and legacy frames.  -LZ4FLEX_E_INVALID_ARG: out or
+ *   frame NULL, a mem_kind other than HOST / DEVICE (checked before a context is looked at); -LZ4FLEX_E_NO_DEVICE without a device.
+ *   _table copies the host tables out (blocks + 1, blocks, blocks entries; any pointer may be NULL).
+ * lz4flex_frame_read_ranges reads m ranges: range r is content bytes [range_off[r], range_off[r] + range_len[r]).  With S the content
+ *   size: out_len[r] = min(range_len[r], S - range_off[r]), 0 for range_off[r] >= S (clipped like a read at end of file, status 0); those
+ *   bytes -- what a full decode of the frame has at that position -- are written at out_base + out_off[r].  Nothing is written in front
+ *   of out_base + out_off[r] or at or behind out_base + out_off[r] + out_len[r]: strict, as for lz4flex_decompress_batch_partial.
+ *   Ranges whose output regions overlap are the caller's error.  range_off / range_len / out_off / out_len / status / detail
+ *   (nullable, m entries) are HOST arrays; frame and out_base are both DEVICE memory (LZ4FLEX_MEM_DEVICE: work on hip_stream) or both
+ *   HOST memory (LZ4FLEX_MEM_HOST: per range ONE copy of the frame span from its first touched block's BlockInfo word to the end of its
+ *   last one goes up -- a small read uploads only the blocks it touches -- and its bytes come back).  The call BLOCKS until the work is
+ *   done and may grow the context's scratch, as the *_many calls do.
+ *   Errors are per range: status[r] = -LZ4FLEX_FE_BLOCK_CHECKSUM when the stored XXH32 of a touched block does not match its payload
+ *   (frames with block checksums, stored blocks too; the payload is hashed WHOLE, also when one byte of the block is wanted; setting
+ *   "frame_range_checksums", default 1: 0 skips this); -LZ4FLEX_FE_DECOMPRESSION with detail[r].inner when a touched block does not
+ *   decode up to its last wanted byte, e.g. because the frame changed since create (a block that decodes without an error but to fewer
+ *   bytes than the index says: inner 0, expected / actual = the bytes wanted / produced).  Among several defects the first block in
+ *   stream order decides, within a block the checksum before the decode (the reference's order).  On error out_len[r] = 0 and the
+ *   range's own output region may hold anything; the other ranges are unaffected.
+ *   NOT VERIFIED: the content checksum, by neither call (a range read does not see the whole content); block checksums of blocks no range
+ *   touches; anything about a frame that differs from the one the index was made from beyond what the touched blocks show.
+ *   What a read launches: the host locates each range in the host tables (csrc/frame_range.h: binary search) and sends one 64-byte record per
+ *   range; frame_range_plan_kernel (a thread per touched block) writes the items of two lz4flex_decompress_batch_partial batches -- every
+ *   touched compressed block from its first byte up to the range's last byte in it, straight into out_base; a range's first block when
+ *   the range starts inside it (a "head") into scratch -- and of two copy batches (stored blocks' spans from the frame, heads' spans from
+ *   scratch); XXH32 + compare over the touched payloads; frame_range_verdict_kernel (a wavefront per range) folds the items' results
+ *   into the m verdicts that come back.  Many ranges that hit the same block decode it once each.  The ranges are cut into passes whose
+ *   scratch (heads; MEM_HOST: staged spans and outputs too) stays under the setting "frame_range_pass_bytes" (default 256 MiB; a pass
+ *   takes at least one range).  "decompress_partial" picks the partial decoder as for lz4flex_decompress_batch_partial.
+ *   Measured once on an MI355X (tools/frame_range_bench.py, one session, profiles/r14_frame_index.txt; 1 GiB of content, device-resident,
+ *     ms per blocking call): 16 384 blocks of 64 KiB JSON -- create 10.5 (the one-thread walk 6.1, the size scan 0.6); one range of 1 MiB
+ *     0.70, 16 of them 0.71, 1 024 ranges of 4 KiB 0.58, 65 536 of them 15.2 (nearly every one a head), the whole content as one range
+ *     2.07; lz4flex_frame_decompress_many of the same frame 8.75.  With block checksums: 16 x 1 MiB 1.10, "frame_range_checksums" 0: 0.70.
+ *     256 blocks of 4 MiB log lines -- create 6.4 (the size scan 6.1); one range of 1 MiB 10.1 against 5.0 for the full decode: NOT
+ *     cheaper -- a range that starts inside a 4 MiB block decodes it from its first byte with one wavefront (the time is the head's
+ *     partial-decode launch); 65 536 ranges of 4 KiB there take 7.7 s.  Random access pays off on frames of small blocks.
+ *   Call-level returns: -LZ4FLEX_E_INVALID_ARG for x == NULL or a mem_kind other than HOST / DEVICE; m == 0 returns 0; then
+ *   -LZ4FLEX_E_INVALID_ARG for a missing array, frame or out_base (all checked before a context is looked at) and for an index of another
+ *   device than the context's; -LZ4FLEX_E_NO_DEVICE without a device. */
+typedef struct lz4flex_frame_index lz4flex_frame_index;
+int lz4flex_frame_index_create(lz4flex_ctx *ctx, const void *frame, uint64_t frame_len, int mem_kind, lz4flex_frame_index **out,
+                               lz4flex_err_detail *detail /* nullable */);
+void lz4flex_frame_index_free(lz4flex_frame_index *x);                      /* NULL is harmless */
+uint32_t lz4flex_frame_index_blocks(const lz4flex_frame_index *x);
+uint64_t lz4flex_frame_index_content_size(const lz4flex_frame_index *x);    /* decoded bytes of the frame */
+uint64_t lz4flex_frame_index_frame_bytes(const lz4flex_frame_index *x);     /* offset behind EndMark (+ content checksum) */
+void lz4flex_frame_index_info(const lz4flex_frame_index *x, lz4flex_frame_info *out);
+int lz4flex_frame_index_table(const lz4flex_frame_index *x, uint64_t *content_off /* blocks + 1 */, uint64_t *payload_off /* blocks */,
+                              uint32_t *len_word /* blocks */);               /* host arrays, any may be NULL */
+int lz4flex_frame_read_ranges(lz4flex_ctx *ctx, const lz4flex_frame_index *x, const void *frame, const uint64_t *range_off,
+                              const uint64_t *range_len, uint32_t m, void *out_base, const uint64_t *out_off, uint64_t *out_len,
+                              int32_t *status, lz4flex_err_detail *detail /* nullable, m entries */, int mem_kind, void *hip_stream);
 
 /* ---- the frame across the GPUs of one node (one process per GPU, an RCCL communicator; BASELINE configs[3]) ----------------
  * FrameEncoder / FrameDecoder for BlockMode::Independent frames whose blocks are spread over `world` ranks: the per-block

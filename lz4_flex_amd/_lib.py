@@ -117,6 +117,14 @@ SIGNATURES = {
     "lz4flex_frame_walk_device": (_I32, [_VP, _U64, _U32, _I32, _U32, _U32, _VP, _VP, _VP, _VP]),
     "lz4flex_frame_compress_many": (_I32, [_VP, _VP, _VP, _VP, _U32, C.POINTER(FrameInfoC), _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_frame_decompress_many": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
+    "lz4flex_frame_index_create": (_I32, [_VP, _VP, _U64, _I32, C.POINTER(_VP), _VP]),
+    "lz4flex_frame_index_free": (None, [_VP]),
+    "lz4flex_frame_index_blocks": (_U32, [_VP]),
+    "lz4flex_frame_index_content_size": (_U64, [_VP]),
+    "lz4flex_frame_index_frame_bytes": (_U64, [_VP]),
+    "lz4flex_frame_index_info": (None, [_VP, C.POINTER(FrameInfoC)]),
+    "lz4flex_frame_index_table": (_I32, [_VP, _VP, _VP, _VP]),
+    "lz4flex_frame_read_ranges": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_frame_segment_bound": (_U64, [_U64, C.POINTER(FrameInfoC)]),
     "lz4flex_frame_compress_sharded": (_I32, [_VP, _VP, _I32, _I32, _I32, _VP, _U64, _U64, C.POINTER(FrameInfoC), _VP, _U64,
                                                C.POINTER(_U64), _VP]),

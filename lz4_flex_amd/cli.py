@@ -3,12 +3,14 @@
     python -m lz4_flex_amd.cli FILE            -> FILE.lz4          python -m lz4_flex_amd.cli FILE.lz4 -> FILE
     python -m lz4_flex_amd.cli [-d] [-o OUT]   (stdin -> stdout / OUT)
 Options as the reference's: --clean (delete the original), -f/--force (overwrite), -d/--decompress, -o/--out.
+Beyond the reference: --range OFF:LEN with a decompression writes just those bytes of the content (frame.FrameIndex.read: only the
+blocks the range touches are decoded; Independent frames; the content checksum is not verified).
 """
 import argparse
 import os
 import sys
 
-from .frame import FrameDecoder, FrameEncoder
+from .frame import FrameDecoder, FrameEncoder, FrameIndex
 
 LZ_EXTENSION = ".lz4"
 CHUNK = 4 << 20
@@ -34,7 +36,26 @@ def _copy(src, dst):     # io::copy
         n += len(b)
 
 
-def handle_file(path, out, clean, force, force_decompress, print_info=True):   # main.rs:82-164
+def _parse_range(text):
+    try:
+        off, _, length = text.partition(":")
+        off, length = int(off, 0), int(length, 0)
+    except ValueError:
+        raise SystemExit("--range wants OFF:LEN, two non-negative integers")
+    if off < 0 or length < 0:
+        raise SystemExit("--range wants OFF:LEN, two non-negative integers")
+    return off, length
+
+
+def _decode(fin, fout, byte_range):
+    if byte_range is None:
+        _copy(FrameDecoder.new(fin), fout)
+    else:
+        with FrameIndex(fin.read()) as index:
+            fout.write(index.read(*byte_range))
+
+
+def handle_file(path, out, clean, force, force_decompress, print_info=True, byte_range=None):   # main.rs:82-164
     decompress = path.endswith(LZ_EXTENSION)
     if force_decompress and not decompress:
         raise SystemExit("Can't determine an output filename")
@@ -50,7 +71,7 @@ def handle_file(path, out, clean, force, force_decompress, print_info=True):   #
                 return
     if decompress:
         with open(path, "rb") as fin, open(out, "wb") as fout:
-            _copy(FrameDecoder.new(fin), fout)
+            _decode(fin, fout, byte_range)
     else:
         with open(path, "rb") as fin, open(out, "wb") as fout:
             tw = _TrackWriteSize(fout)
@@ -70,15 +91,21 @@ def main(argv=None):
     ap.add_argument("-d", "--decompress", action="store_true", help="force decompress")
     ap.add_argument("input_file", nargs="?", help="file to compress/decompress ('-' or absent: stdin)")
     ap.add_argument("-o", "--out", help="output file to write to. defaults to stdout")
+    ap.add_argument("--range", metavar="OFF:LEN", help="decompression: write only bytes [OFF, OFF + LEN) of the content")
     o = ap.parse_args(argv)
+    byte_range = _parse_range(o.range) if o.range else None
     if o.input_file and o.input_file != "-":
-        handle_file(o.input_file, o.out, o.clean, o.force, o.decompress)
+        if byte_range is not None and not o.input_file.endswith(LZ_EXTENSION):
+            raise SystemExit("--range goes with a decompression")
+        handle_file(o.input_file, o.out, o.clean, o.force, o.decompress, byte_range=byte_range)
         return 0
+    if byte_range is not None and not o.decompress:
+        raise SystemExit("--range goes with a decompression")
     fin = sys.stdin.buffer
     fout = open(o.out, "wb") if o.out else sys.stdout.buffer
     try:
         if o.decompress:
-            _copy(FrameDecoder.new(fin), fout)
+            _decode(fin, fout, byte_range)
         else:
             enc = FrameEncoder.new(fout)
             _copy(fin, enc)

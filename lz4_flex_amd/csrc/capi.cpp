@@ -674,6 +674,9 @@ const Setting SETTINGS[] = {
     {"compress_shared_dict", &lz4flex_ctx::comp_shared, is_flag, false},
     {"decompress_shared_dict", &lz4flex_ctx::dec_shared, is_flag, false},
     {"decompress_partial", &lz4flex_ctx::dec_partial, is_flag, false},
+    // (frame_index.cpp, lz4flex_frame_read_ranges: the scratch one pass of ranges may take; whether touched blocks' checksums are verified)
+    {"frame_range_pass_bytes", &lz4flex_ctx::range_pass_bytes, [](int v) { return v >= 1; }, false},
+    {"frame_range_checksums", &lz4flex_ctx::range_checksums, is_flag, false},
     // (the sizes one workgroup of the packed entries' offset scan takes: lz4_device.h PACKED_SCAN_TILE; the tests cut their batches around it)
     {"packed_scan_tile", &lz4flex_ctx::packed_tile, read_only, false},
     // (what "compress_subwindows" 0 decides by: n * 4 <= this -> 4, n * 3 <= this -> 3, n * 2 <= this -> 2)

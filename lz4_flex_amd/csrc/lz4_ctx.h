@@ -132,6 +132,8 @@ struct lz4flex_ctx {
     int dec_shared = 1;           // "decompress_shared_dict": 1 = lz4flex_decompress_batch_shared_dict runs the sequence decoder's dictionary form; 0 = every block through decode_block<16, true>, the per-block path (A/B measurements, tests)
     int dec_partial = 1;          // "decompress_partial": 1 = lz4flex_decompress_batch_partial runs the sequence decoder's partial form; 0 = every block through decode_block<16, false, true>, the reference's order (A/B measurements, tests)
     int packed_tile = 0;          // "packed_scan_tile" (read-only): the sizes one workgroup of the packed entries' offset scan takes
+    int range_pass_bytes = 256 << 20;   // "frame_range_pass_bytes": lz4flex_frame_read_ranges cuts its ranges into passes whose scratch (heads; MEM_HOST: the staged spans and outputs too) stays under this; a pass takes at least one range
+    int range_checksums = 1;      // "frame_range_checksums": 1 = a range read verifies the block checksums of the blocks it touches (frames that have them); 0 = not (A/B measurements, tests)
     int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
 };
 

@@ -12,6 +12,8 @@
 #define LZ4FLEX_DEV_E_UNSUPPORTED 68        // lz4_packed.hip: a raw block that decompresses to more than the decoders' u32 out_cap holds
 #define LZ4FLEX_DEV_E_INVALID_ARG 64        // a sink position behind the sink's end (out_pos > out_cap): the reference panics there
 
+namespace lz4flex_range { struct RangeRec; }   // frame_range.h
+
 namespace lz4flex_dev {
 
 // All pointers are device pointers.
@@ -280,6 +282,38 @@ hipError_t launch_packed_finish(const int32_t* pre, const uint64_t* size, const 
 hipError_t launch_packed_gather(const uint8_t* scratch, const uint64_t* src_off, const uint64_t* size, const uint64_t* off,
                                 const uint32_t* in_len, uint32_t n, uint32_t prefix, uint64_t total_cap, uint8_t* out, uint32_t* out_len,
                                 int32_t* status, hipStream_t s);
+// frame_range.hip (frame_index.cpp: lz4flex_frame_index_create / lz4flex_frame_read_ranges).
+// The index: scan_len[b] = what launch_size_scan measures of walked block b (0 for a stored block), *first_bad = ~0; then size[b] (holding
+// the scan's sizes) becomes the block's decoded bytes and *first_bad the first compressed block with scan_st != 0 or more than block_size bytes
+hipError_t launch_frame_index_prep(const uint32_t* word, uint32_t n, uint32_t* scan_len, uint32_t* first_bad, hipStream_t s);
+hipError_t launch_frame_index_sizes(const uint32_t* word, const int32_t* scan_st, uint32_t n, uint32_t block_size, uint64_t* size, uint32_t* first_bad,
+                                    hipStream_t s);
+// One pass of range reads: n_ranges records (frame_range.h RangeRec, slots ascending) over the index's device tables -> the items of two
+// partial-decode batches (a_*: a slot per touched block, sink = the output; b_*: a slot per range, sink = scratch) and of two copy
+// batches (c_*: per touched block, from the input; d_*: per range, from scratch).  Offsets are relative to the pass's bases.
+struct FrameRangePlan {
+    const lz4flex_range::RangeRec* rec;
+    const uint64_t* content_off;
+    const uint64_t* payload_off;
+    const uint32_t* len_word;
+    uint32_t n_ranges, n_slots;
+    uint64_t *a_in, *a_out, *b_in, *b_out, *c_src, *c_dst, *d_src, *d_dst;
+    uint32_t *a_len, *a_tgt, *b_len, *b_tgt, *c_len, *d_len;
+};
+hipError_t launch_frame_range_plan(const FrameRangePlan& p, hipStream_t s);
+// the items' results -> per range status (0, -LZ4FLEX_FE_BLOCK_CHECKSUM, -LZ4FLEX_FE_DECOMPRESSION), out_len and the detail words;
+// bad: nullable (launch_frame_sums_check's flags, a slot per touched block)
+struct FrameRangeVerdict {
+    const lz4flex_range::RangeRec* rec;
+    const uint32_t* len_word;
+    uint32_t n_ranges;
+    const uint32_t* bad;
+    const int32_t *a_st, *b_st;
+    const uint32_t *a_tgt, *a_olen, *b_tgt, *b_olen;
+    int32_t *status, *inner;
+    uint64_t *out_len, *expected, *actual;
+};
+hipError_t launch_frame_range_verdict(const FrameRangeVerdict& v, hipStream_t s);
 // DECODE_REDO: the status a first-pass decoder (sequence, workgroup, plan, fused) leaves on a block it does not decode: the host then runs a reference-order
 // kernel with only_status = DECODE_REDO over the batch (capi.cpp launch_redo)
 constexpr int32_t DECODE_REDO = 0x7F000001;

@@ -471,3 +471,135 @@ def decompress_frames_device(src, in_off, in_len, dst, out_off, out_cap, stream=
     if r != 0:
         raise DeviceError("lz4flex error %d: %s" % (-r, L.last_error()))
     return list(out_len[:n]), list(status[:n])
+
+
+# ---- seekable frames (include/lz4flex_amd.h "seekable frames": a block index, batched byte-range reads) --------------------------
+def _is_tensor(obj):
+    return hasattr(obj, "data_ptr") and hasattr(obj, "is_cuda")
+
+
+def _range_errors(n, status, detail, return_errors):
+    errs = [None] * n
+    for i in range(n):
+        if status[i] != 0:
+            errs[i] = _frame_error(int(-status[i]), detail[i])
+            if not return_errors:
+                raise errs[i]
+    return errs
+
+
+class FrameIndex:
+    """The block table of an Independent frame, made once on the GPU; `read` / `read_ranges` then decode only the blocks a byte range of
+    the CONTENT touches.  frame: bytes-like (a host frame; the index keeps the bytes) or a torch uint8 tensor on the GPU (a device
+    frame; the index keeps the tensor).  Raises the frame.Error lz4flex_frame_decompress would raise for a frame that is not
+    structurally sound; block.DeviceError for Linked and legacy frames and without a device.  The content checksum is never verified."""
+
+    def __init__(self, frame):
+        lib = L.load()
+        self._lib, self._h = lib, None
+        if _is_tensor(frame):
+            self._device, self._frame, self._len = True, frame, int(frame.numel())
+            ptr = C.c_void_p(frame.data_ptr())
+        else:
+            self._device, self._frame = False, _as_bytes(frame)
+            self._len = len(self._frame)
+            ptr = C.cast(C.c_char_p(self._frame or b"\0"), C.c_void_p)
+        h = C.c_void_p()
+        d = L.ErrDetail()
+        r = lib.lz4flex_frame_index_create(None, ptr, self._len, L.MEM_DEVICE if self._device else L.MEM_HOST, C.byref(h), C.byref(d))
+        if r != 0:
+            raise _frame_error(int(-r), d)
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            self._lib.lz4flex_frame_index_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def blocks(self):
+        return int(self._lib.lz4flex_frame_index_blocks(self._h))
+
+    @property
+    def content_size(self):
+        return int(self._lib.lz4flex_frame_index_content_size(self._h))
+
+    @property
+    def frame_bytes(self):
+        return int(self._lib.lz4flex_frame_index_frame_bytes(self._h))
+
+    @property
+    def frame_info(self):
+        c = L.FrameInfoC()
+        self._lib.lz4flex_frame_index_info(self._h, C.byref(c))
+        return FrameInfo._from_c(c)
+
+    def table(self):
+        """(content_off: blocks + 1 exclusive sums of the decoded sizes, payload_off, len_word) as lists"""
+        n = self.blocks
+        co, po, lw = (C.c_uint64 * (n + 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+        r = self._lib.lz4flex_frame_index_table(self._h, co, po, lw)
+        if r != 0:
+            raise DeviceError("lz4flex error %d: %s" % (-r, L.last_error()))
+        return list(co), list(po[:n]), list(lw[:n])
+
+    def read_ranges(self, ranges, return_errors=False):
+        """[(offset, length), ...] of the content -> a list of bytes, clipped at the content's end like a read at end of file.  A range
+        whose blocks fail raises the frame.Error (return_errors: comes back as the exception object, the other ranges as bytes).
+        A device frame's bytes are read on the GPU and copied to the host."""
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        m = len(ranges)
+        if m == 0:
+            return []
+        S = self.content_size
+        want = [min(n, S - o) if o < S else 0 for o, n in ranges]
+        out_off, at = [], 0
+        for v in want:
+            out_off.append(at); at += v
+        out_len, status, detail = (C.c_uint64 * m)(), (C.c_int32 * m)(), (L.ErrDetail * m)()
+        args = (_u64([o for o, _ in ranges]), _u64([n for _, n in ranges]), m)
+        if self._device:
+            import torch
+            dst = torch.empty(max(at, 1), dtype=torch.uint8, device=self._frame.device)
+            r = self._lib.lz4flex_frame_read_ranges(None, self._h, C.c_void_p(self._frame.data_ptr()), *args, C.c_void_p(dst.data_ptr()),
+                                                    _u64(out_off), out_len, status, detail, L.MEM_DEVICE, None)
+            out = bytes(dst.cpu().numpy().tobytes()) if r == 0 else b""
+        else:
+            out = _new_bytes(None, max(at, 1))
+            r = self._lib.lz4flex_frame_read_ranges(None, self._h, self._frame, *args, out, _u64(out_off), out_len, status, detail, L.MEM_HOST,
+                                                    None)
+        if r != 0:
+            raise DeviceError("lz4flex error %d: %s" % (-r, L.last_error()))
+        errs = _range_errors(m, status, detail, return_errors)
+        return [errs[i] if errs[i] is not None else out[out_off[i]:out_off[i] + int(out_len[i])] for i in range(m)]
+
+    def read(self, offset, length):
+        """content bytes [offset, offset + length), clipped at the content's end"""
+        return self.read_ranges([(offset, length)])[0]
+
+
+def read_ranges_device(index, src, ranges, dst, out_off, stream=None):
+    """device-resident frame `src` (the frame `index` was made from, a torch uint8 tensor) -> range i's bytes at dst[out_off[i] ..];
+    returns (out_len list, status list); the call has completed when it returns."""
+    ranges = [(int(o), int(n)) for o, n in ranges]
+    m = len(ranges)
+    out_len = (C.c_uint64 * max(m, 1))()
+    status = (C.c_int32 * max(m, 1))()
+    r = index._lib.lz4flex_frame_read_ranges(None, index._h, C.c_void_p(src.data_ptr()), _u64([o for o, _ in ranges]), _u64([n for _, n in ranges]),
+                                             m, C.c_void_p(dst.data_ptr()), _u64(out_off), out_len, status, None, L.MEM_DEVICE,
+                                             C.c_void_p(stream) if stream else None)
+    if r != 0:
+        raise DeviceError("lz4flex error %d: %s" % (-r, L.last_error()))
+    return list(out_len[:m]), list(status[:m])
