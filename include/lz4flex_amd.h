@@ -90,7 +90,9 @@ const char *lz4flex_build_id(void);
  * lz4flex_decompress_batch_partial / lz4flex_decompress_partial_into with the setting "decompress_partial" (no workspace), then the
  * seekable frames lz4flex_frame_index_create / _free / _blocks / _content_size / _frame_bytes / _info / _table and
  * lz4flex_frame_read_ranges with the settings "frame_range_pass_bytes" and "frame_range_checksums" (no workspace in the context beyond
- * the scratch the *_many calls already grow: an index owns its tables) -- a caller detects them by the symbol. */
+ * the scratch the *_many calls already grow: an index owns its tables), then partial decode against dictionaries
+ * lz4flex_decompress_batch_partial_shared_dict / lz4flex_decompress_batch_partial_dict_set / lz4flex_decompress_partial_into_with_dict (no
+ * new setting, no workspace) -- a caller detects them by the symbol. */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -143,6 +145,11 @@ int64_t lz4flex_decompress_into_with_dict(const uint8_t *in, size_t in_len, uint
  * Returns the bytes written or -code; there is no OutputTooSmall, so of `detail` only hip_error can be set. */
 int64_t lz4flex_decompress_partial_into(const uint8_t *in, size_t in_len, uint8_t *out, size_t target,
                                         lz4flex_err_detail *detail /* nullable */);
+/* The same against an external dictionary: a one-block host batch of lz4flex_decompress_batch_partial_shared_dict (its contract, below;
+ * dict == NULL or dict_len == 0: lz4flex_decompress_partial_into).  Returns the bytes written or -code (-LZ4FLEX_E_INVALID_ARG: a length
+ * beyond 32 bits, dict == NULL with dict_len != 0); of `detail` only hip_error can be set. */
+int64_t lz4flex_decompress_partial_into_with_dict(const uint8_t *in, size_t in_len, uint8_t *out, size_t target,
+                                                  const uint8_t *dict, size_t dict_len, lz4flex_err_detail *detail /* nullable */);
 /* block::uncompressed_size, src/block/mod.rs:151-157: returns the LE u32 prefix or -EXPECTED_ANOTHER_BYTE */
 int64_t lz4flex_uncompressed_size(const uint8_t *in, size_t in_len);
 /* block::decompress_size_prepended, src/block/decompress.rs:493-496; out_cap must be >= the prefix */
@@ -475,6 +482,44 @@ int lz4flex_decompress_batch_partial(lz4flex_ctx *ctx, const void *in_base, cons
                                      uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *target,
                                      uint32_t *out_len, int32_t *status, int mem_kind, void *hip_stream);
 
+/* PARTIAL DECODE AGAINST A DICTIONARY: the first target[i] bytes of every block of a batch whose blocks were compressed against ONE
+ * dictionary (lz4flex_compress_batch_shared_dict) -- a record's header or key prefix out of tens of thousands of small records, without
+ * decoding any of them in full.  `dict` (dict_len bytes, a HOST value in both memory kinds) lies in the same memory kind as the batch.
+ * mem_kind: LZ4FLEX_MEM_HOST (staged, synchronous: the batch, the output staging sized from target[], the dictionary once per call) or
+ * LZ4FLEX_MEM_DEVICE (asynchronous on hip_stream, allocates nothing); LZ4FLEX_MEM_BIG_BLOCKS may be ORed in (results do not depend on it);
+ * LZ4FLEX_MEM_CHAINED is refused.  No per-block dictionary arrays, no out_pos prefixes, no chains.
+ *   The contract is lz4flex_decompress_batch_partial's, with one line changed:
+ *           if offset > op + dict_len: OffsetOutOfBounds                    (dict_len untruncated, src/block/decompress.rs:399-401)
+ *     and the bytes of a match whose source lies in front of the output come from the dictionary's end (copy_from_dict, :85-109 /
+ *     :410-426), clipped to the target like every other copy.  Everything else carries over: out_len = min(S, target); no
+ *     LZ4FLEX_E_OUTPUT_TOO_SMALL and no detail array; errors in front of the target in the reference's order, errors behind it not seen;
+ *     target == 0 on a non-empty block: status 0, out_len 0, nothing is read; an empty block: LZ4FLEX_E_EXPECTED_ANOTHER_BYTE; on error
+ *     out_len is 0.  Strict: nothing is written at or behind out_off[i] + target[i], nothing in front of out_off[i], and nothing is ever
+ *     written into the dictionary.
+ *   Equalities: a target at or beyond a valid block's size gives the results of lz4flex_decompress_batch_shared_dict with out_cap =
+ *     target.  dict == NULL or dict_len == 0: the call is forwarded to lz4flex_decompress_batch_partial.  The results are those of
+ *     lz4flex_decompress_batch_partial_dict_set with a set of this one dictionary.
+ *   The kernels: the sequence decoder (lz4_decompress_seq.hip) in its form with both a dictionary and a target -- the dictionary's last
+ *     min(dict_len, 65 536) bytes are a virtual prefix in front of every block's output, the target counts from its end -- when the
+ *     settings "decompress_partial" and "decompress_shared_dict" are both 1 and "decompress_variant" is not 1; the blocks it hands back
+ *     (what the partial form hands back, and a block whose positions would pass 4 GiB - 64 KiB) are decoded again in the reference's
+ *     order, sixteen lanes per block, with the dictionary, up to their target (lz4_decompress.hip: the definition above, literally).
+ *     Otherwise every block goes through that kernel.  "decompress_second_pass" 0 leaves handed-back blocks marked 0x7F000001.
+ *     Measured on an MI355X (tools/partial_dict_bench.py, one session, profiles/r15_partial_dict.txt; blocks compressed against one 32 KiB
+ *     dictionary, device-resident, ms per call for 65 536 log records of 4 KiB / 16 384 JSON tiles of 64 KiB): the full
+ *     lz4flex_decompress_batch_shared_dict 0.56 / 1.93; this entry at target 64: 0.319 / 0.234, at 512: 0.335 / 0.237 (the set entry, K = 4:
+ *     0.335 / 0.233), at 4 096: 0.585 / 0.315, at 65 536: - / 1.942.  "decompress_partial" 0 at the same targets: 0.037 / 0.019, 0.231 /
+ *     0.112, 1.80 / 0.712, - / 8.48 -- as for the plain partial entry, the reference's order wins where the target is a few hundred bytes.
+ *     A full-size target is level with the full entry on the tiles and 4.5 % slower on the 4 KiB records (the block's last sequence is
+ *     cut off its chunk and executed alone): a caller that wants whole blocks calls the full entry.
+ * Returns 0 or -code for call-level failures (-LZ4FLEX_E_INVALID_ARG: a missing array -- target counts as one --, dict == NULL with
+ * dict_len != 0, a mem_kind other than HOST / DEVICE (| BIG_BLOCKS); the arguments are checked before a context is looked at); n == 0
+ * returns 0; -LZ4FLEX_E_NO_DEVICE without a device. */
+int lz4flex_decompress_batch_partial_shared_dict(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                                 uint32_t n, void *out_base, const uint64_t *out_off, const uint32_t *target,
+                                                 uint32_t *out_len, int32_t *status, const void *dict, uint32_t dict_len,
+                                                 int mem_kind, void *hip_stream);
+
 /* ---- dictionary sets: K prepared dictionaries, one id per block ----------------------------------------------------------------
  * The *_shared_dict entries prepare their one dictionary again on every call (the digest kernel, one wavefront; a MEM_HOST call
  * stages the dictionary again), and a batch whose records belong to a handful of dictionaries -- one per table or per column -- has
@@ -532,6 +577,19 @@ int lz4flex_decompress_batch_dict_set(lz4flex_ctx *ctx, const void *in_base, con
                                       uint32_t n, const uint32_t *dict_id, void *out_base, const uint64_t *out_off,
                                       const uint32_t *out_cap, uint32_t *out_len, int32_t *status, uint64_t *detail /* nullable */,
                                       const lz4flex_dict_set *set, int mem_kind, void *hip_stream);
+/* Partial decode against a set: lz4flex_decompress_batch_partial_shared_dict (its contract, settings and kernels) with block i's
+ * dictionary looked up by dict_id[i], the calls as for the two entries above: the arguments are checked before a context is looked at
+ * (-LZ4FLEX_E_INVALID_ARG for a missing array -- dict_id and target count --, set == NULL with n != 0, a mem_kind other than HOST / DEVICE
+ * (| BIG_BLOCKS)); n == 0 returns 0; a set of another device: -LZ4FLEX_E_INVALID_ARG; -LZ4FLEX_E_NO_DEVICE without a device.  MEM_HOST
+ * calls stage the batch (the output staging sized from target[]) and the ids, not the dictionaries.
+ *   dict_id[i] == 0xFFFFFFFF, or an id whose dictionary is empty: block i gets what lz4flex_decompress_batch_partial gives it.  A set of K =
+ *   1 and every id 0: the results of lz4flex_decompress_batch_partial_shared_dict with that dictionary.  Any other id >= k: status
+ *   LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written, the rest of the batch unaffected.  Nothing is written at or behind out_off[i] +
+ *   target[i], in front of out_off[i], or into the set. */
+int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len,
+                                              uint32_t n, const uint32_t *dict_id, void *out_base, const uint64_t *out_off,
+                                              const uint32_t *target, uint32_t *out_len, int32_t *status,
+                                              const lz4flex_dict_set *set, int mem_kind, void *hip_stream);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

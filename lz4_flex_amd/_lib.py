@@ -68,6 +68,7 @@ SIGNATURES = {
     "lz4flex_decompress_into": (_I64, [_VP, _SZ, _VP, _SZ, C.POINTER(ErrDetail)]),
     "lz4flex_decompress_into_with_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, C.POINTER(ErrDetail)]),
     "lz4flex_decompress_partial_into": (_I64, [_VP, _SZ, _VP, _SZ, C.POINTER(ErrDetail)]),
+    "lz4flex_decompress_partial_into_with_dict": (_I64, [_VP, _SZ, _VP, _SZ, _VP, _SZ, C.POINTER(ErrDetail)]),
     "lz4flex_uncompressed_size": (_I64, [_VP, _SZ]),
     "lz4flex_decompress_size_prepended": (_I64, [_VP, _SZ, _VP, _SZ, C.POINTER(ErrDetail)]),
     "lz4flex_compress_batch": (_I32, [_VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
@@ -78,6 +79,8 @@ SIGNATURES = {
     "lz4flex_decompress_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_decompress_batch_shared_dict": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _I32, _VP]),
     "lz4flex_decompress_batch_partial": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
+    "lz4flex_decompress_batch_partial_shared_dict": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _I32, _VP]),
+    "lz4flex_decompress_batch_partial_dict_set": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_dict_set_create": (_I32, [_VP, _VP, _VP, _VP, _U32, _I32, C.POINTER(_VP)]),
     "lz4flex_dict_set_free": (None, [_VP]),
     "lz4flex_dict_set_count": (_U32, [_VP]),

@@ -248,6 +248,22 @@ def decompress_partial(input, n):
     return bytes(out[:r])
 
 
+def decompress_partial_with_dict(input, n, ext_dict):
+    """The first min(size, n) bytes of the block `input`, which was compressed against `ext_dict` (lz4flex_decompress_partial_into_with_dict):
+    decompress_partial with block::decompress_with_dict's offset rule -- an offset may reach len(ext_dict) bytes in front of the output."""
+    lib = L.load()
+    ip, ilen, _k = _buf(input)
+    dp, dn, _k2 = _buf(ext_dict)
+    out = bytearray(max(int(n), 1))
+    o = (C.c_uint8 * len(out)).from_buffer(out)
+    d = L.ErrDetail()
+    r = lib.lz4flex_decompress_partial_into_with_dict(ip, ilen, C.cast(o, C.c_void_p), int(n), dp, dn, C.byref(d))
+    del o
+    if r < 0:
+        _raise_decode(int(-r), d)
+    return bytes(out[:r])
+
+
 def uncompressed_size(input):
     """block::uncompressed_size (mod.rs:151-157): (size, rest)"""
     if len(input) < 4:
@@ -282,7 +298,7 @@ def decompress_size_prepended_with_dict(input, ext_dict):
 #     name(ctx, in_base, in_off, in_len, [flags,] n, <what is particular to it>, out_len, status, [detail,] <more of that>, mem_kind, stream)
 # The host forms (numpy arrays in, numpy arrays out) are one _host_call each; the device forms (torch tensors) share _device_args and
 # _device_call, the three that compress into slots of the maximum output size _compress_slots_device, the three that decode blocks of
-# unknown sizes _size_then_decode_device.  A form keeps its docstring, what is particular to it, and its return.
+# unknown sizes _size_then_decode_device, the three that decode up to a target _partial_device.  A form keeps its docstring, what is particular to it, and its return.
 NO_DICT = 0xFFFFFFFF     # the dict_id of a block without a dictionary (lz4flex_dict_set_*, lz4flex_*_batch_dict_set)
 SIZE_MODES = {"prepended": L.SIZES_PREPENDED, "given": L.SIZES_GIVEN, "scan": L.SIZES_SCAN}     # lz4flex_decompress_batch_packed
 
@@ -449,14 +465,13 @@ def decompress_batch_partial(in_buf, in_off, in_len, out_buf, out_off, target, c
     return _host_call("lz4flex_decompress_batch_partial", ctx, in_buf, in_off, in_len, (out_buf, out_off, target))
 
 
-def decompress_blocks_partial_device(src, in_off, in_len, target, stream=None):
-    """Raw blocks in device memory, the first target[i] bytes of each: src is a uint8 torch tensor on the GPU, in_off / in_len / target
-    integer tensors.  The output is packed by an exclusive prefix sum of `target` (ONE host synchronisation: the total, to allocate
-    exactly that), then one lz4flex_decompress_batch_partial (MEM_DEVICE, asynchronous on `stream`, default the current one).  Returns
-    (out, out_off, out_len, status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]], out_len[i] =
-    min(size, target[i]); a block that fails in front of its target gets its status and out_len 0."""
+def _partial_device(name, src, in_off, in_len, target, stream, after_n=(), tail=(), **companions):
+    """The device recipe of the partial entries: the output is packed by an exclusive prefix sum of `target` (ONE host synchronisation:
+    the total, to allocate exactly that), then one
+        name(NULL, src, in_off, in_len, n, *after_n, out, out_off, target, out_len, status, *tail, mem_kind, stream)
+    Returns (out, out_off, out_len, status)."""
     import torch
-    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream, **companions)
     if int(target.numel()) != n:
         raise ValueError("in_off and target differ in length")
     want = target.to(device=dev, dtype=torch.int64) & 0xFFFFFFFF
@@ -467,9 +482,17 @@ def decompress_blocks_partial_device(src, in_off, in_len, target, stream=None):
     status = torch.zeros(n, dtype=torch.int32, device=dev)
     if n:
         d_target = torch.where(want >= 0x80000000, want - 0x100000000, want).to(torch.int32).contiguous()     # (the bit pattern of a u32)
-        _device_call("lz4flex_decompress_batch_partial", [src, d_off, d_len], n, [out, out_off, d_target, out_len, status],
-                     False, sp)
+        _device_call(name, [src, d_off, d_len], n, [*after_n, out, out_off, d_target, out_len, status, *tail], False, sp)
     return out[:total], out_off, out_len, status
+
+
+def decompress_blocks_partial_device(src, in_off, in_len, target, stream=None):
+    """Raw blocks in device memory, the first target[i] bytes of each: src is a uint8 torch tensor on the GPU, in_off / in_len / target
+    integer tensors.  The output is packed by an exclusive prefix sum of `target` (ONE host synchronisation: the total, to allocate
+    exactly that), then one lz4flex_decompress_batch_partial (MEM_DEVICE, asynchronous on `stream`, default the current one).  Returns
+    (out, out_off, out_len, status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]], out_len[i] =
+    min(size, target[i]); a block that fails in front of its target gets its status and out_len 0."""
+    return _partial_device("lz4flex_decompress_batch_partial", src, in_off, in_len, target, stream)
 
 
 # ---- per-block dictionaries (lz4flex_*_batch_ex) --------------------------------------------------------------------------------
@@ -548,6 +571,23 @@ def decompress_blocks_with_shared_dict_device(src, in_off, in_len, dictionary, s
                                     tail=[dictionary, dlen], dictionary=dictionary)
 
 
+def decompress_batch_partial_with_shared_dict(in_buf, in_off, in_len, dictionary, out_buf, out_off, target, ctx=None):
+    """lz4flex_decompress_batch_partial_shared_dict over host buffers: decompress_batch_partial for blocks that were compressed against
+    the ONE `dictionary` (bytes-like or a uint8 array) -- the first min(size, target[i]) bytes of every block into out_buf[out_off[i] : +
+    target[i]].  Returns (out_len[u32], status[i32])."""
+    d = _host_u8(dictionary)
+    return _host_call("lz4flex_decompress_batch_partial_shared_dict", ctx, in_buf, in_off, in_len, (out_buf, out_off, target),
+                      tail=[d, int(d.size)])
+
+
+def decompress_blocks_partial_with_shared_dict_device(src, in_off, in_len, target, dictionary, stream=None):
+    """decompress_blocks_partial_device for blocks that were compressed against the ONE `dictionary` (a uint8 torch tensor on the GPU of
+    src): one lz4flex_decompress_batch_partial_shared_dict into the same packed layout -- out_off is the exclusive prefix sum of
+    `target`.  Returns (out, out_off, out_len, status) as device tensors."""
+    return _partial_device("lz4flex_decompress_batch_partial_shared_dict", src, in_off, in_len, target, stream,
+                           tail=[dictionary, int(dictionary.numel())], dictionary=dictionary)
+
+
 # ---- dictionary sets: K prepared dictionaries, one id per block (lz4flex_dict_set_*, lz4flex_*_batch_dict_set) -------------
 class DictSet:
     """lz4flex_dict_set: `dictionaries` (a sequence of bytes-like objects or uint8 arrays; an empty one means "no dictionary" for its
@@ -609,6 +649,13 @@ def decompress_batch_with_dict_set(in_buf, in_off, in_len, dict_id, dict_set, ou
                       middle=[_host_ids(dict_id, len(in_off))], tail=[dict_set], detail=True)
 
 
+def decompress_batch_partial_with_dict_set(in_buf, in_off, in_len, dict_id, dict_set, out_buf, out_off, target, ctx=None):
+    """lz4flex_decompress_batch_partial_dict_set over host buffers: decompress_batch_partial with dictionary dict_id[i] of `dict_set`
+    (NO_DICT: none) for block i.  Returns (out_len[u32], status[i32]); an id the set does not have gives that block E_INVALID_ARG."""
+    return _host_call("lz4flex_decompress_batch_partial_dict_set", ctx, in_buf, in_off, in_len, (out_buf, out_off, target),
+                      middle=[_host_ids(dict_id, len(in_off))], tail=[dict_set])
+
+
 def _device_ids(dict_id, n, dev):
     """dict_id as n int64 on dev, and as the int32 bit pattern of n u32"""
     import torch
@@ -643,6 +690,14 @@ def decompress_blocks_with_dict_set_device(src, in_off, in_len, dict_id, dict_se
     # (a refused id is the decoder's to report)
     return _size_then_decode_device("lz4flex_decompress_batch_dict_set", src, in_off, in_len, stream, history=hist, after_n=[ids],
                                     tail=[dict_set], decoder_wins=L.E_INVALID_ARG)
+
+
+def decompress_blocks_partial_with_dict_set_device(src, in_off, in_len, target, dict_id, dict_set, stream=None):
+    """decompress_blocks_partial_device against a DictSet: src is a uint8 torch tensor on the set's GPU, block i's dictionary is
+    dict_id[i] (NO_DICT: none).  One lz4flex_decompress_batch_partial_dict_set into the same packed layout -- out_off is the exclusive
+    prefix sum of `target`.  Returns (out, out_off, out_len, status) as device tensors (an id the set does not have: E_INVALID_ARG)."""
+    _, ids = _device_ids(dict_id, int(in_off.numel()), src.device)
+    return _partial_device("lz4flex_decompress_batch_partial_dict_set", src, in_off, in_len, target, stream, after_n=[ids], tail=[dict_set])
 
 
 # ---- packed batches: one output buffer, the offsets computed on the device (lz4flex_*_batch_packed) ------------------------

@@ -8,7 +8,7 @@
 //   run_device_batch MEM_DEVICE: the caller's BatchCall as it is, on the caller's stream;
 //   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode (the
 //                    SharedDictArgs set-up, launch_compress_any) and launch_decode (the chain bracket and the choice between the
-//                    shared-dictionary, the partial, the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
+//                    shared-dictionary, the partial (with or without a dictionary), the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
 //                    shape, launch_redo is the second pass behind every first-pass decoder).
 // The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
 // DeviceGuard, Layout, GrowBuf) are in lz4_ctx.h; the integer settings are one table (SETTINGS) that lz4flex_set_tuning and
@@ -98,6 +98,8 @@ enum class Redo {
     SharedDict,   // launch_decompress_shared_dict: with the batch's one dictionary
     DictSet,      // launch_decompress_dict_set: with each block's dictionary out of the batch's set
     Partial,      // launch_decompress_partial: out_cap is a target (lz4flex_decompress_batch_partial)
+    PartialSharedDict,   // launch_decompress_partial_shared_dict: a target, with the batch's one dictionary
+    PartialDictSet,      // launch_decompress_partial_dict_set: a target, with each block's dictionary out of the batch's set
 };
 static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, Redo how = Redo::Blocks, const uint8_t* dict = nullptr,
                               uint32_t dict_len = 0, const DictSetArgs* set = nullptr) {
@@ -108,6 +110,8 @@ static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream
     if (how == Redo::DictSet) return launch_decompress_dict_set(r, *set, s);
     if (how == Redo::SharedDict) return launch_decompress_shared_dict(r, dict, dict_len, s);
     if (how == Redo::Partial) return launch_decompress_partial(r, s);
+    if (how == Redo::PartialSharedDict) return launch_decompress_partial_shared_dict(r, dict, dict_len, s);
+    if (how == Redo::PartialDictSet) return launch_decompress_partial_dict_set(r, *set, s);
     return launch_decompress(r, c->dec_lanes, s);
 }
 
@@ -232,6 +236,21 @@ static hipError_t launch_decompress_partial_any(lz4flex_ctx* c, const Decompress
     if (!c->dec_partial || c->dec_variant == 1) return launch_decompress_partial(a, s);
     const hipError_t e = launch_decompress_seq_partial(a, DECODE_REDO, s);
     return e != hipSuccess ? e : launch_redo(c, a, s, Redo::Partial);
+}
+
+// lz4flex_decompress_batch_partial_shared_dict / _dict_set: a.out_cap holds the targets and every block has the batch's one dictionary /
+// the one its id names.  The sequence decoder's form with both (Dec<G, true, true>) when "decompress_partial" and
+// "decompress_shared_dict" are both 1 and "decompress_variant" is not 1; the blocks it marks are decoded again in the reference's order,
+// with the dictionary, up to their target.  Otherwise that order for every block.
+static hipError_t launch_decompress_partial_shared(lz4flex_ctx* c, const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
+    if (!c->dec_partial || !c->dec_shared || c->dec_variant == 1) return launch_decompress_partial_shared_dict(a, dict, dict_len, s);
+    const hipError_t e = launch_decompress_seq_partial_dict(a, dict, dict_len, DECODE_REDO, s);
+    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::PartialSharedDict, dict, dict_len);
+}
+static hipError_t launch_decompress_partial_set(lz4flex_ctx* c, const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
+    if (!c->dec_partial || !c->dec_shared || c->dec_variant == 1) return launch_decompress_partial_dict_set(a, set, s);
+    const hipError_t e = launch_decompress_seq_partial_dict_set(a, set, DECODE_REDO, s);
+    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::PartialDictSet, nullptr, 0, &set);
 }
 
 // Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
@@ -450,7 +469,8 @@ struct BatchCall {
     uint32_t n_chains = 0;
     bool has_ext = false;                   // the caller handed an extension struct over, whatever it holds: such a host batch takes the general path
     bool chained = false;                   // LZ4FLEX_MEM_CHAINED
-    bool partial = false;                   // lz4flex_decompress_batch_partial: out_cap holds TARGETS (no dictionary, prefix or chain; no detail)
+    bool partial = false;                   // the *_partial calls: out_cap holds TARGETS (no detail; with shared_dict or set: the *_partial_shared_dict /
+                                            // *_partial_dict_set calls; never with dict_base, a prefix or a chain)
     bool big = false;                       // LZ4FLEX_MEM_BIG_BLOCKS, or -- host batches -- what the lengths say
     hipStream_t stream = nullptr;           // DEVICE batches: the caller's (NULL = HIP's null stream); host batches: the context's
 };
@@ -501,7 +521,12 @@ static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
         a.debug_giveup = (uint32_t)c->chain_giveup;
     }
     hipError_t le;
-    if (b.partial) { a.detail = nullptr; le = launch_decompress_partial_any(c, a, s); }
+    if (b.partial) {
+        a.detail = nullptr;
+        if (b.set) le = launch_decompress_partial_set(c, a, set_args_of(c, b), s);
+        else if (b.shared_dict && b.shared_len) le = launch_decompress_partial_shared(c, a, b.shared_dict, b.shared_len, s);
+        else le = launch_decompress_partial_any(c, a, s);
+    }
     else if (b.set) le = launch_decompress_set(c, a, set_args_of(c, b), s);
     else if (b.shared_dict && b.shared_len) le = launch_decompress_shared(c, a, b.shared_dict, b.shared_len, s);
     // "decompress_variant" 1 and blocks with dictionaries: the reference-order kernel (a chain has no such form)
@@ -1206,6 +1231,22 @@ int lz4flex_decompress_batch_partial(lz4flex_ctx* ctx, const void* in_base, cons
     return rc ? rc : run_batch(ctx, b, k);
 }
 
+int lz4flex_decompress_batch_partial_shared_dict(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                                 void* out_base, const uint64_t* out_off, const uint32_t* target, uint32_t* out_len, int32_t* status,
+                                                 const void* dict, uint32_t dict_len, int mem_kind, void* hip_stream) {
+    if (!dict && dict_len) return -LZ4FLEX_E_INVALID_ARG;
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, target, out_len, status, hip_stream);
+    b.partial = true; b.has_ext = true; b.shared_dict = (const uint8_t*)dict; b.shared_len = dict_len;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!dict || !dict_len)
+        return lz4flex_decompress_batch_partial(ctx, in_base, in_off, in_len, n, out_base, out_off, target, out_len, status, mem_kind, hip_stream);
+    const int rc = begin_batch(&ctx);
+    return rc ? rc : run_batch(ctx, b, k);
+}
+
 // ---- dictionary sets ----------------------------------------------------------------------------------------------------------
 int lz4flex_dict_set_create(lz4flex_ctx* ctx, const void* dict_base, const uint64_t* dict_off, const uint32_t* dict_len, uint32_t k,
                             int mem_kind, lz4flex_dict_set** out) {
@@ -1320,6 +1361,14 @@ int lz4flex_decompress_batch_dict_set(lz4flex_ctx* ctx, const void* in_base, con
                                       void* hip_stream) {
     BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
     b.detail = detail;
+    return run_dict_set_batch(ctx, b, dict_id, set, mem_kind, LZ4FLEX_MEM_BIG_BLOCKS);
+}
+
+int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n,
+                                              const uint32_t* dict_id, void* out_base, const uint64_t* out_off, const uint32_t* target,
+                                              uint32_t* out_len, int32_t* status, const lz4flex_dict_set* set, int mem_kind, void* hip_stream) {
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, target, out_len, status, hip_stream);
+    b.partial = true;
     return run_dict_set_batch(ctx, b, dict_id, set, mem_kind, LZ4FLEX_MEM_BIG_BLOCKS);
 }
 
@@ -1786,6 +1835,26 @@ int64_t lz4flex_decompress_partial_into(const uint8_t* in, size_t in_len, uint8_
     static uint8_t sink_dummy = 0;
     BatchCall b = batch_of(false, in ? in : &EMPTY, &OFF0, &len, 1, out ? out : &sink_dummy, &OFF0, &want, &olen, &st);
     b.partial = true;
+    rc = run_host_batch(c, b);
+    if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
+    return st ? -(int64_t)st : (int64_t)olen;
+}
+
+// a one-block host batch of lz4flex_decompress_batch_partial_shared_dict (no dictionary: of lz4flex_decompress_batch_partial)
+int64_t lz4flex_decompress_partial_into_with_dict(const uint8_t* in, size_t in_len, uint8_t* out, size_t target, const uint8_t* dict, size_t dict_len,
+                                                  lz4flex_err_detail* detail) {
+    if (in_len > 0xFFFFFFFFull || target > 0xFFFFFFFFull || dict_len > 0xFFFFFFFFull || (!dict && dict_len)) return -LZ4FLEX_E_INVALID_ARG;
+    if (!dict || !dict_len) return lz4flex_decompress_partial_into(in, in_len, out, target, detail);
+    if (detail) memset(detail, 0, sizeof *detail);
+    lz4flex_ctx* c;
+    int rc = default_ctx(&c);
+    if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
+    const uint32_t len = (uint32_t)in_len, want = (uint32_t)target;
+    uint32_t olen = 0;
+    int32_t st = 0;
+    static uint8_t sink_dummy = 0;
+    BatchCall b = batch_of(false, in ? in : &EMPTY, &OFF0, &len, 1, out ? out : &sink_dummy, &OFF0, &want, &olen, &st);
+    b.partial = true; b.has_ext = true; b.shared_dict = dict; b.shared_len = (uint32_t)dict_len;
     rc = run_host_batch(c, b);
     if (rc) { if (detail) detail->hip_error = g_last_hip; return rc; }
     return st ? -(int64_t)st : (int64_t)olen;

@@ -95,7 +95,7 @@ __device__ __forceinline__ void group_copy_periodic(uint8_t* dst, uint32_t offse
 }
 
 // Decode one block with a group of G lanes. Returns the status code; *produced = bytes written.
-// PARTIAL (lz4flex_decompress_batch_partial; not with a dictionary or a sink position): `cap` is a TARGET, not a capacity -- the block
+// PARTIAL (lz4flex_decompress_batch_partial, and with USE_DICT its _shared_dict / _dict_set forms; not with a sink position): `cap` is a TARGET, not a capacity -- the block
 // is decoded until `cap` bytes exist or it ends, whichever comes first.  The sequence that crosses the target is clipped to it and
 // ends the decode with status 0 (no OutputTooSmall); every check the reference makes before that point is made in its order, nothing
 // behind it is looked at, and no byte at or behind out + cap is written.
@@ -196,6 +196,9 @@ __device__ __forceinline__ int32_t decode_block(const uint8_t* __restrict__ in, 
             group_copy<G>(out + op, dict + dict_offset, n, g, false);
             op += n;
             if (n == ml) {
+                // (ml is clipped to the target: a dictionary part that reaches it is the whole match, and like a match in the block
+                // that ends at the target it is not asked for the token behind it)
+                if (PARTIAL && op >= cap) break;
                 if (ip >= ilen) return LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE;
                 continue;
             }
@@ -281,7 +284,9 @@ hipError_t launch_decompress_partial(const DecompressArgs& a, hipStream_t s) {
 // reference's check order, WITH the dictionary); 0: every block ("decompress_shared_dict" 0, "decompress_variant" 1).
 // lz4flex_decompress_batch_dict_set: the same with block b's dictionary looked up in a set (SET; dict / dict_len are not read then).  A
 // block without one decodes with dict_len 0; a refused id is status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written.
-template <bool SET>
+// PARTIAL (lz4flex_decompress_batch_partial_shared_dict / _dict_set): out_cap[b] is block b's target -- decode_block<16, true, true>, the
+// definition of those entries' results and the second pass behind the sequence decoder's form; no detail.
+template <bool SET, bool PARTIAL = false>
 __global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(DecompressArgs a, const uint8_t* dict, uint32_t dict_len, DictSetArgs set) {
     constexpr int G = 16;
     const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
@@ -295,11 +300,11 @@ __global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(Decompr
     bool found = true;
     if constexpr (SET) found = dict_set_find(set, b, dict, dict_len);
     const int32_t st = !found ? LZ4FLEX_DEV_E_INVALID_ARG
-                              : decode_block<G, true>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g, &produced, &expected);
+                              : decode_block<G, true, PARTIAL>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g, &produced, &expected);
     if (g == 0u) {
         a.status[b] = st;
         a.out_len[b] = st == 0 ? produced : 0u;
-        if (a.detail) {
+        if (!PARTIAL && a.detail) {
             a.detail[2u * b] = st == LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL ? expected : 0u;
             a.detail[2u * b + 1u] = st == LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL ? (uint64_t)cap : 0u;
         }
@@ -317,6 +322,20 @@ hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs
     if (a.n == 0u) return hipSuccess;
     if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel<true>, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, (const uint8_t*)nullptr, 0u, set);
+    return hipGetLastError();
+}
+
+hipError_t launch_decompress_partial_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (dict == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((lz4_decompress_shared_dict_kernel<false, true>), dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, dict, dict_len, DictSetArgs{});
+    return hipGetLastError();
+}
+
+hipError_t launch_decompress_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((lz4_decompress_shared_dict_kernel<true, true>), dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, (const uint8_t*)nullptr, 0u, set);
     return hipGetLastError();
 }
 

@@ -34,6 +34,17 @@
 // no chain in the bytes behind the stop (X_ERR), the block is handed back like any irregular one, and lz4_decompress_partial_kernel
 // (lz4_decompress.hip), which never looks behind the stop, decides it -- correct, and slower for that block only.  Nothing is stored at or
 // behind out + target: the window is written back in whole 16-byte units below OP and byte by byte up to OP, and OP never passes the target.
+// PARTIAL with DICT (lz4flex_decompress_batch_partial_shared_dict / _dict_set; source tags PartialOneDict / PartialDictSet): Dec<G, true,
+// true>.  The two forms compose with three adjustments.  (1) Positions are virtual, so the crossing sequence's offset check is
+// offset > OP - lo(), as in exact_seq; its copies (coop_match / big_match: vp, vbyte, pos_copy) pick their path by the CLIPPED length.
+// (2) The target is biased by PV like a capacity -- but a capacity that does not fit the position space may be cut (the block then ends
+// in the second pass as OutputTooSmall or decodes), a target may not: cut, it would be reached, and the decode would stop early with
+// status 0.  Such a target becomes one no position reaches; a block that really needs positions beyond POS_LIMIT is handed back by the
+// position checks.  The "nothing is asked for" exit tests the caller's target, before the bias.  (3) setup_chunk's cut and its
+// capacity check both compare with D.cap - op, biased on both sides; the OffsetOutOfBounds ballot (dm - lo()) stays behind the cut, so
+// an offset that reaches in front of the dictionary in a sequence behind the stop is no error.  The strict sink holds as it does
+// without a dictionary: F starts at PV, a multiple of 16, write_back's units lie below OP & ~15 in virtual positions, and OP never
+// passes the biased target.  A block of a set without a dictionary has PV = LO = 0 and decodes exactly as the plain partial form.
 // LDS per wavefront: token list 2 560 + tile 4 080 + window 3 584 + 16 = 10 240 bytes: 16 wavefronts per CU (4 096 blocks are one round of
 // wavefronts; 8 KiB windows -- 11 per CU, a fifth of the far matches -- were a quarter slower: DESIGN.md 5.2, profiles/r06_seq_decoder.txt).
 #include <hip/hip_runtime.h>
@@ -398,7 +409,7 @@ struct Dec {
                 if (b != 255u) break;
             }
         }
-        if (offset > OP) return SEQ_BAD;
+        if (offset > OP - lo()) return SEQ_BAD;
         {
             const uint32_t c = ml < cap - OP ? ml : cap - OP;
             if (OP + c > POS_LIMIT) return SEQ_BAD;
@@ -650,24 +661,30 @@ __device__ __forceinline__ bool run_chunks(Dec<G, DICT, PARTIAL>& D, uint32_t t0
 // Where the blocks' dictionaries come from.  OneDict: every block of the batch has the ONE dictionary dict[0, dict_len) (device memory,
 // dict_len != 0), and none has a prefix.  DictSetArgs (lz4_device.h): block b has the dictionary its id names in a prepared set -- or none
 // (dl = 0, so PV = LO = 0: the block decodes as it does without the dictionary form), or a refused id.
-// Partial: no dictionary and no prefix, and a.out_cap[b] is block b's TARGET (see the head of the file).
+// Partial: no dictionary and no prefix, and a.out_cap[b] is block b's TARGET (see the head of the file).  PartialOneDict / PartialDictSet:
+// a target, and the dictionary as OneDict / DictSetArgs give it.
 struct NoDict {};
 struct OneDict { const uint8_t* dict; uint32_t dict_len; };
 struct Partial {};
+struct PartialOneDict { const uint8_t* dict; uint32_t dict_len; };
+struct PartialDictSet { DictSetArgs set; };
 template <class SRC> constexpr bool SRC_DICT = !__is_same(SRC, NoDict) && !__is_same(SRC, Partial);
+template <class SRC> constexpr bool SRC_PARTIAL = __is_same(SRC, Partial) || __is_same(SRC, PartialOneDict) || __is_same(SRC, PartialDictSet);
+__device__ __forceinline__ const DictSetArgs& set_of(const DictSetArgs& s) { return s; }
+__device__ __forceinline__ const DictSetArgs& set_of(const PartialDictSet& s) { return s.set; }
 template <class G, class SRC>
 __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code, SRC src) {
     constexpr bool DICT = SRC_DICT<SRC>;
-    constexpr bool PARTIAL = __is_same(SRC, Partial);
+    constexpr bool PARTIAL = SRC_PARTIAL<SRC>;
     extern __shared__ __attribute__((aligned(16))) uint8_t seq_lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= a.n) return;
     [[maybe_unused]] const uint8_t* dict = nullptr;
     [[maybe_unused]] uint32_t dict_len = 0u;
-    if constexpr (__is_same(SRC, OneDict)) { dict = src.dict; dict_len = src.dict_len; }
-    if constexpr (__is_same(SRC, DictSetArgs)) {
-        if (!dict_set_find(src, b, dict, dict_len)) {
+    if constexpr (__is_same(SRC, OneDict) || __is_same(SRC, PartialOneDict)) { dict = src.dict; dict_len = src.dict_len; }
+    if constexpr (__is_same(SRC, DictSetArgs) || __is_same(SRC, PartialDictSet)) {
+        if (!dict_set_find(set_of(src), b, dict, dict_len)) {
             if (lane == 0u) {
                 a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG;
                 a.out_len[b] = 0u;
@@ -687,6 +704,7 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
     D.out = (g_u8*)(a.out_base + a.out_off[b]);
     D.ilen = a.in_len[b];
     D.cap = a.out_cap[b];
+    [[maybe_unused]] const uint32_t want = D.cap;     // PARTIAL: the caller's target (DICT biases D.cap below)
     D.lane = lane;
     D.OP = 0u; D.W0 = 0u; D.F = 0u;
     D.dv = nullptr; D.PV = 0u; D.LO = 0u;
@@ -704,14 +722,16 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
         D.PV = PFX; D.LO = PFX - dl;
         D.dv = (const g_u8*)((uintptr_t)dict + dict_len - PFX);
         D.out = (g_u8*)((uintptr_t)(a.out_base + a.out_off[b]) - PFX);
-        D.cap = (D.cap < POS_LIMIT - PFX ? D.cap : POS_LIMIT - PFX) + PFX;
+        // PARTIAL: the target counts from PV too -- and one the position space does not hold is never reached, not cut (head of the file)
+        if constexpr (PARTIAL) D.cap = D.cap <= POS_LIMIT - PFX ? D.cap + PFX : 0xFFFFFFFFu;
+        else D.cap = (D.cap < POS_LIMIT - PFX ? D.cap : POS_LIMIT - PFX) + PFX;
     } else if constexpr (!PARTIAL) {
         PFX = a.out_pos != nullptr ? uni(a.out_pos[b]) : 0u;
     }
     const uint32_t ilen = D.ilen;
     if constexpr (PARTIAL) {
         // nothing is asked for: nothing is read (an EMPTY block is an error before that, decompress.rs:207-209: handed back below)
-        if (D.cap == 0u && ilen != 0u) { if (lane == 0u) { a.status[b] = 0; a.out_len[b] = 0u; } return; }
+        if (want == 0u && ilen != 0u) { if (lane == 0u) { a.status[b] = 0; a.out_len[b] = 0u; } return; }
     }
     bool ok = ilen != 0u && ilen <= POS_LIMIT && PFX <= POS_LIMIT / 2u && D.cap >= PFX, done = false;     // (an empty block: decompress.rs:207-209, the reference-order kernel reports it)
     if (PFX != 0u && ok) { D.OP = PFX; D.reload_window(); }
@@ -818,6 +838,26 @@ hipError_t launch_decompress_seq_dict_set(const DecompressArgs& a, const DictSet
     if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
     typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
     hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, DictSetArgs>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, set);
+    return hipGetLastError();
+}
+
+// lz4flex_decompress_batch_partial_shared_dict / _dict_set: a.out_cap[b] is block b's target AND every block has the one dictionary / the
+// dictionary its id names (the kernel's form with both: no prefix, no chain).  Irregular blocks get status `redo_code`; the caller runs
+// launch_decompress_partial_shared_dict / launch_decompress_partial_dict_set with only_status = redo_code behind this launch.  A refused
+// id gets its final status here.
+hipError_t launch_decompress_seq_partial_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (dict == nullptr || dict_len == 0u || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::PartialOneDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::PartialOneDict{dict, dict_len});
+    return hipGetLastError();
+}
+
+hipError_t launch_decompress_seq_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
+    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::PartialDictSet>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::PartialDictSet{set});
     return hipGetLastError();
 }
 

@@ -176,6 +176,13 @@ hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs
 // status redo_code), and decode_block<16, false, true> in the reference's order: a.only_status 0 = every block, else the marked ones
 hipError_t launch_decompress_seq_partial(const DecompressArgs& a, int32_t redo_code, hipStream_t s);
 hipError_t launch_decompress_partial(const DecompressArgs& a, hipStream_t s);
+// lz4flex_decompress_batch_partial_shared_dict / _dict_set: the same with ONE dictionary for the batch / block b's dictionary out of a set;
+// OffsetOutOfBounds is offset > produced + dict_len.  The sequence decoder's form with both (a refused id gets its final status there), and
+// decode_block<16, true, true>: a.only_status 0 = every block, else the marked ones
+hipError_t launch_decompress_seq_partial_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s);
+hipError_t launch_decompress_seq_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s);
+hipError_t launch_decompress_partial_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s);
+hipError_t launch_decompress_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s);
 hipError_t launch_decompress_split(const DecompressArgs& a, hipStream_t s, int blocks_per_wg = 0);   // parser / copier wavefronts, no dict/prefix
 // parser -> emitter -> quad wavefronts (lz4_decompress_fused.hip: the split decoder's parser, the replay decoder's copy engine, no dict/prefix);
 // blocks of 512 KiB or more are left with status redo_code for a second pass of launch_decompress.  -DLZ4FLEX_TOOLS builds only (round 6)
