@@ -23,10 +23,14 @@
 //     greedy walk over the step is scalar (ballot, s_ff1, v_readlane) and touches no memory; the selected
 //     sequences are encoded lane-parallel straight into the segment's body (a prefix sum of their sizes places them);
 //   * segments are independent parses (a match never crosses a segment end) that may reference the whole window;
-//     after a barrier every worker places its segment's bytes: the literals left over at a segment's end are
-//     carried into the first sequence of the next segment (its token is written at that point).
+//     the literals left over at a segment's end are carried into the first sequence of the next segment (its token is
+//     written when the segments are placed).  Behind the matching barrier only the sizes are resolved (resolve_window:
+//     where every segment's output starts, kept with the window's other values in a record in LDS); the bytes of window k
+//     are copied while window k + 1 is matched, by whichever worker is done with its segment first (copy_segment, tickets
+//     from an LDS counter): the serial part between a window's two barriers is the resolve and the next window's load.
 // Memory traffic: the input twice (the indexer's stream, the workers' window) and the output once are 2.2 GiB per GiB of input; cand[] is
-// 2 GiB written + 2 GiB read back and the segment bodies are written and read once more -- the 512 workgroups' workspace (~340 KB each)
+// 2 GiB written + 2 GiB read back and the segment bodies are written and read once more (two sets of bodies per workgroup: window k + 1's
+// are written while window k's are read) -- the 512 workgroups' workspace (~420 KB each)
 // does not fit the L2s (32 MiB), so all of it crosses the fabric to the Infinity Cache: the counters on the L2's fabric side see ~10 GB
 // per GiB (7.7 x the algorithmic bytes; profiles/traffic.json), of which HBM itself has to serve the input and the output.
 #include <hip/hip_runtime.h>
@@ -115,28 +119,35 @@ constexpr uint32_t WORKER_LDS = CMP_OFF + 256u;
 constexpr uint32_t CHUNK = 1024u;         // the indexer streams the next window in 1 KiB chunks (16 steps)
 constexpr uint32_t CHUNK_SLOT = CHUNK + 16u;      // + the first bytes of the next chunk (positions 1021..1023 hash across the end)
 constexpr uint32_t IDX_DEPTH = 4u;        // chunks in flight (registers) ahead of the one being indexed
-// LDS layout (80 960 B with eleven workers: two workgroups per CU)
+// LDS layout (81 728 B with eleven workers: two workgroups per CU)
 constexpr uint32_t L_WIN = 0u;                              // the window + 64 B of slack for the 16-byte compares
 constexpr uint32_t L_TAB = WINDOW + 64u;                    // the indexer's table, 4096 x u16
 constexpr uint32_t L_STG = L_TAB + (2u << HBITS);
 constexpr uint32_t L_RING = L_STG + WORKERS * WORKER_LDS;   // the indexer's chunk slot(s)
 constexpr uint32_t L_META = L_RING + RING_SLOTS * CHUNK_SLOT;
-// L_META, words: 5 per worker (SegMeta), BlkCarry[2] (4), the drawn items (giq, 4), place_segment's mailbox (3), run_flag[2] (see index_window)
-constexpr uint32_t META_WORDS = 5u * WORKERS + 4u + 4u + 3u + 2u;
+// L_META, words: 5 per worker (SegMeta, the window being matched), BlkCarry[2] (4), the drawn items (giq, 4), resolve_window's mailbox (3),
+// run_flag[2] (see index_window), the ticket counter of the deferred copies (1), two copy records (window k's is record k & 1: PlaceRec)
+constexpr uint32_t M_TICKET = 5u * WORKERS + 13u;
+constexpr uint32_t M_REC = M_TICKET + 1u;
+constexpr uint32_t REC_SEG = 7u;                          // per segment: {out_pos, pend} and the segment's SegMeta
+constexpr uint32_t REC_UNI = REC_SEG * WORKERS;           // behind the segments: the window's uniform values (PlaceRec)
+constexpr uint32_t REC_WORDS = REC_UNI + 18u;
+constexpr uint32_t META_WORDS = M_REC + 2u * REC_WORDS;
 constexpr uint32_t LDS_BYTES = L_META + ((META_WORDS * 4u + 63u) & ~63u);
 static_assert(LDS_BYTES <= 81920u, "two workgroups per CU");
 static_assert(WORKERS >= 1u && WORKERS <= 15u && seg_lo(WORKERS) == WINDOW, "segments tile the window");
 // workspace per workgroup
 constexpr uint32_t SLOT_BYTES = 2u * WINDOW;                // cand[] of one window, transposed: see index_window
 constexpr uint32_t BODY_STRIDE = (SEG + SEG / 128u + 255u) / 256u * 256u + 256u;   // a segment's encoded bytes never exceed SEG + SEG/255 + 16
-constexpr uint32_t WS_BYTES = 2u * SLOT_BYTES + WORKERS * BODY_STRIDE;
+constexpr uint32_t BODY_SET = WORKERS * BODY_STRIDE;         // the bodies of one window; two sets: window k's is set k & 1 (its bytes are copied while window k + 1 is matched)
+constexpr uint32_t WS_BYTES = 2u * SLOT_BYTES + 2u * BODY_SET;
 static_assert(WS_BYTES % 256u == 0u, "workspace slots stay 256 B aligned");
 // per workgroup, behind everything else in the workspace: the staging slot of a dictionary item's window (stage_window) -- the window
 // and the 64 bytes of slack load_window reads behind it
 constexpr uint32_t STAGE_BYTES = WINDOW + 256u;
 constexpr uint32_t STAGE_READ = WINDOW + 64u;
 
-struct SegMeta {          // LDS, one per worker, valid between the two barriers of a window
+struct SegMeta {          // LDS, one per worker: written at the end of matching, copied into the window's record (resolve_window) behind the matching barrier
     uint32_t has;         // the segment holds at least one match
     uint32_t first_lit;   // literals from the segment start to its first match
     uint32_t first_ml;    // that match's length (its token is written when the segments are placed)
@@ -1212,16 +1223,41 @@ __device__ __forceinline__ void put_len_header(g_u8* dst, uint32_t lit, uint32_t
     });
 }
 
-// Place segment w of the current window (after the barrier: every worker's SegMeta is final).
-__device__ __attribute__((noinline)) void place_segment(lds_u8* lds, const uint8_t* __restrict__ gin_, uint32_t blk_len_, uint32_t win_idx_, bool last_win_,
-                              uint32_t wl_, uint32_t wbase_, uint32_t wskip_, uint32_t send_, const uint8_t* body_, uint8_t* gout_, uint32_t carry_slot_, uint32_t w_, uint32_t lane,
+// PLACING A WINDOW'S SEGMENTS happens in two parts (round 16).  resolve_window runs behind the matching barrier of window k (every
+// worker's SegMeta is final): sizes only -- where each segment's output starts and how many literals are pending in front of it --, left
+// with everything else the copies need in the window's record, PlaceRec k & 1 in LDS.  copy_segment moves one segment's bytes, needs
+// nothing from the LDS window, and runs a window later: a worker that is done matching its segment of window k + 1 draws segments of
+// window k from a ticket counter until none are left (wave_body), in the time it would otherwise wait at the barrier for the slowest
+// worker.  Before: barrier, place (wait for the own body stores, read the body back, copy literals, write), load, barrier -- ~30 k
+// cycles in which the indexer and the workers that were done stood still; now the part between the barriers is resolve + load.
+// PlaceRec, words: REC_SEG per segment {out_pos, pend, SegMeta}, then from REC_UNI on the uniform values below.
+constexpr uint32_t RU_COUNT = 0u;      // tickets: WORKERS, or 0 (a skipped item, no window yet)
+constexpr uint32_t RU_GIN = 1u;        // (two words) the item's first byte
+constexpr uint32_t RU_BLK_LEN = 3u;
+constexpr uint32_t RU_WIN_IDX = 4u;    // (which window of its block this is: kept for whoever reads a dump of the record, the copies do not need it)
+constexpr uint32_t RU_LAST_WIN = 5u;
+constexpr uint32_t RU_WL = 6u;
+constexpr uint32_t RU_WBASE = 7u;
+constexpr uint32_t RU_WSKIP = 8u;
+constexpr uint32_t RU_SEND = 9u;
+constexpr uint32_t RU_GOUT = 10u;      // (two words)
+constexpr uint32_t RU_RUNWIN = 12u;
+constexpr uint32_t RU_POISONED = 13u;
+constexpr uint32_t RU_OUT_LEN = 14u;   // (two words)
+constexpr uint32_t RU_STATUS = 16u;    // (two words)
+static_assert(RU_STATUS + 2u == REC_WORDS - REC_UNI, "the record holds the uniform values");
+// start of segment j of a window, clipped to its parsed part (a run window: segment 0 is the whole parsed part, the others are empty)
+__device__ __forceinline__ uint32_t seg_at(uint32_t j, uint32_t runwin, uint32_t wl, uint32_t wskip, uint32_t send) {
+    const uint32_t v = runwin ? (j == 0u ? wskip : wl) : seg_start(j, wskip, send);
+    return v < wl ? v : wl;
+}
+
+// Worker w's part of resolving the current window into record `rec_` (a word index into L_META): its segment's {out_pos, pend} and
+// SegMeta; the last worker hands the carry on; worker 0 writes the uniform values.
+__device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t rec_, const uint8_t* __restrict__ gin_, uint32_t blk_len_, uint32_t win_idx_, bool last_win_,
+                              uint32_t wl_, uint32_t wbase_, uint32_t wskip_, uint32_t send_, uint8_t* gout_, uint32_t carry_slot_, uint32_t w_, uint32_t lane,
                               uint32_t* out_len_, int32_t* status_, uint32_t* gcarry_, uint32_t iter_, uint32_t spins_max_, uint32_t runwin_) {
-    const g_u8* __restrict__ gin = uni_gptr<const g_u8>(gin_);
-    const uint32_t runwin = uni(runwin_);                          // a run window (index_window): segment 0 is the whole parsed part, the others are empty
-    const g_u8* body = uni_gptr<const g_u8>(body_);
-    g_u8* gout = uni_gptr<g_u8>(gout_);
-    g_u32* out_len = uni_gptr<g_u32>(out_len_);
-    g_i32* status = uni_gptr<g_i32>(status_);
+    const uint32_t runwin = uni(runwin_);                          // a run window (index_window)
     const uint32_t blk_len = uni(blk_len_), win_idx = uni(win_idx_), wl = uni(wl_), carry_slot = uni(carry_slot_), w = uni(w_);
     const uint32_t wbase = uni(wbase_), wskip = uni(wskip_);       // the window's first byte in the block; its first wskip positions are history
     const uint32_t spins_max = uni(spins_max_);                    // CARRY_SPINS (tests: 1 -- a window gives up at once)
@@ -1229,8 +1265,9 @@ __device__ __attribute__((noinline)) void place_segment(lds_u8* lds, const uint8
     const uint32_t send = uni(send_);
     const lds_u32* mp = (const lds_u32*)(lds + L_META);
     lds_u32* cp = (lds_u32*)(lds + L_META) + 5u * WORKERS;          // BlkCarry[2]
+    lds_u32* rec = (lds_u32*)(lds + L_META) + uni(rec_);
     // Where this window's output starts and how many literals the block has pending: from the previous window, which this
-    // workgroup placed itself (LDS) or, when the windows of a block are dealt to different workgroups (gcarry: a ring of
+    // workgroup resolved itself (LDS) or, when the windows of a block are dealt to different workgroups (gcarry: a ring of
     // {out_pos, pend, window} records per block in the workspace), another one did -- that wait is bounded, a window that gives
     // up poisons the rest of its block (pend bit 31): the block is left with status 66 and launch_compress_wave's second launch
     // encodes it again.
@@ -1274,63 +1311,134 @@ __device__ __attribute__((noinline)) void place_segment(lds_u8* lds, const uint8
             out_pos = cp[2u * (carry_slot ^ 1u)]; pend = cp[2u * (carry_slot ^ 1u) + 1u];
         }
     }
-    auto seg_at = [&](uint32_t j) -> uint32_t {                     // start of segment j, clipped to the parsed part of the window
-        const uint32_t v = runwin ? (j == 0u ? wskip : wl) : seg_start(j, wskip, send);
-        return v < wl ? v : wl;
+    // lane j holds the SegMeta of segment j (one LDS round trip for all of them, this is the serial part of a window); the prefix over
+    // the segments in front of this worker's is scalar
+    uint32_t m_has = 0u, m_fl = 0u, m_ml = 0u, m_tr = 0u, m_bl = 0u;
+    if (lane < WORKERS) { m_has = mp[5u * lane]; m_fl = mp[5u * lane + 1u]; m_ml = mp[5u * lane + 2u]; m_tr = mp[5u * lane + 3u]; m_bl = mp[5u * lane + 4u]; }
+    auto behind = [&](uint32_t j, uint32_t& op, uint32_t& pd) {     // {out_pos, pend} in front of segment j -> behind it
+        if (rdlane(m_has, j) != 0u) {
+            const uint32_t L = pd + rdlane(m_fl, j);
+            op += 1u + len_ext_bytes(L) + L + rdlane(m_bl, j);
+            pd = rdlane(m_tr, j);
+        } else {
+            pd += seg_at(j + 1u, runwin, wl, wskip, send) - seg_at(j, runwin, wl, wskip, send);
+        }
     };
-    auto seg_len = [&](uint32_t j) -> uint32_t { return seg_at(j + 1u) - seg_at(j); };
-    for (uint32_t j = 0; j < w; ++j) {
-        const uint32_t sl = seg_len(j);
-        if (mp[5u * j] != 0u) {
-            const uint32_t L = pend + mp[5u * j + 1u];
-            out_pos += 1u + len_ext_bytes(L) + L + mp[5u * j + 4u];
-            pend = mp[5u * j + 3u];
+    for (uint32_t j = 0; j < w; ++j) behind(j, out_pos, pend);
+    if (lane == w) {
+        lds_u32* sg = rec + REC_SEG * w;
+        sg[0] = out_pos; sg[1] = pend; sg[2] = m_has; sg[3] = m_fl; sg[4] = m_ml; sg[5] = m_tr; sg[6] = m_bl;
+    }
+    if (w == 0u && lane == 0u) {
+        lds_u32* ru = rec + REC_UNI;
+        const uint64_t pin = (uint64_t)gin_, pout = (uint64_t)gout_, plen = (uint64_t)out_len_, pst = (uint64_t)status_;
+        ru[RU_COUNT] = WORKERS;
+        ru[RU_GIN] = (uint32_t)pin; ru[RU_GIN + 1u] = (uint32_t)(pin >> 32);
+        ru[RU_BLK_LEN] = blk_len; ru[RU_WIN_IDX] = win_idx; ru[RU_LAST_WIN] = last_win ? 1u : 0u;
+        ru[RU_WL] = wl; ru[RU_WBASE] = wbase; ru[RU_WSKIP] = wskip; ru[RU_SEND] = send;
+        ru[RU_GOUT] = (uint32_t)pout; ru[RU_GOUT + 1u] = (uint32_t)(pout >> 32);
+        ru[RU_RUNWIN] = runwin; ru[RU_POISONED] = poisoned;
+        ru[RU_OUT_LEN] = (uint32_t)plen; ru[RU_OUT_LEN + 1u] = (uint32_t)(plen >> 32);
+        ru[RU_STATUS] = (uint32_t)pst; ru[RU_STATUS + 1u] = (uint32_t)(pst >> 32);
+    }
+    uint32_t eo = out_pos, ep = pend;
+    if (w == WORKERS - 1u && !last_win) behind(w, eo, ep);
+    if (w == WORKERS - 1u && !last_win && lane == 0u) {
+        // the next window's carry depends on sizes only: it is handed on here, a window before the bytes are copied (the windows of a
+        // block form a chain through global memory; with the copies inside it a block advanced one window per 4 microseconds)
+        if (gcarry != nullptr) {
+            g_u32* so = gcarry + 16u * ((win_idx + 1u) & (CARRY_SLOTS - 1u));
+            __hip_atomic_store(so, eo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(so + 1, ep | (poisoned << 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(so + 2, win_idx + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-            pend += sl;
+            cp[2u * carry_slot] = eo;
+            cp[2u * carry_slot + 1u] = ep;
         }
     }
-    const uint32_t sl = seg_len(w);
-    const uint32_t abs0 = wbase + seg_at(w);                       // block-relative start of this segment
-    if (gcarry != nullptr && w == WORKERS - 1u && !last_win && lane == 0u) {
-        // the next window's carry depends on sizes only: hand it on BEFORE the bytes are copied (the windows of a block form a
-        // chain through global memory; with the copies inside it a block advanced one window per 4 microseconds)
-        uint32_t eo = out_pos, ep = pend;
-        if (mp[5u * w] != 0u) {
-            const uint32_t L = pend + mp[5u * w + 1u];
-            eo += 1u + len_ext_bytes(L) + L + mp[5u * w + 4u];
-            ep = mp[5u * w + 3u];
-        } else {
-            ep += sl;
-        }
-        g_u32* so = gcarry + 16u * ((win_idx + 1u) & (CARRY_SLOTS - 1u));
-        __hip_atomic_store(so, eo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(so + 1, ep | (poisoned << 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(so + 2, win_idx + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (mp[5u * w] != 0u) {
-        const uint32_t fl = mp[5u * w + 1u], L = pend + fl, ml = mp[5u * w + 2u] - 4u, bl = mp[5u * w + 4u];
+}
+
+// up to PIECE bytes of a copy in flight: 16 per lane and the (< 16) bytes behind them, any alignment on either side
+constexpr uint32_t PIECE = 1024u;
+struct Piece { u32x4 v; uint32_t t; };
+__device__ __forceinline__ Piece piece_load(const g_u8* src, uint32_t n, uint32_t lane) {
+    Piece p;
+    p.v = u32x4{0u, 0u, 0u, 0u};
+    p.t = 0u;
+    if (16u * lane + 16u <= n) __builtin_memcpy(&p.v, (const void*)(src + 16u * lane), 16);
+    if ((n & ~15u) + lane < n) p.t = src[(n & ~15u) + lane];
+    return p;
+}
+__device__ __forceinline__ void piece_store(g_u8* dst, uint32_t n, uint32_t lane, const Piece& p) {
+    if (16u * lane + 16u <= n) __builtin_memcpy((void*)(dst + 16u * lane), &p.v, 16);
+    if ((n & ~15u) + lane < n) dst[(n & ~15u) + lane] = (uint8_t)p.t;
+}
+
+// The bytes of segment t of the window that record `rec_` describes: header, first-sequence literals (from the input), body (from body
+// set `bodies_`); behind the last segment of a block's last window the final literals, out_len and status.  Any worker wavefront, any segment.
+__device__ __attribute__((noinline)) void copy_segment(lds_u8* lds, uint32_t rec_, uint32_t t_, const uint8_t* bodies_, uint32_t lane) {
+    const lds_u32* rec = (const lds_u32*)(lds + L_META) + uni(rec_);
+    const uint32_t t = uni(t_);
+    const lds_u32* sg = rec + REC_SEG * t;
+    const lds_u32* ru = rec + REC_UNI;
+    auto rd = [&](const lds_u32* p) -> uint32_t { return uni(*p); };
+    auto rd_ptr = [&](const lds_u32* p) -> uint64_t { return ((uint64_t)rd(p + 1) << 32) | rd(p); };
+    const g_u8* __restrict__ gin = (const g_u8*)rd_ptr(ru + RU_GIN);
+    g_u8* gout = (g_u8*)rd_ptr(ru + RU_GOUT);
+    const g_u8* body = uni_gptr<const g_u8>(bodies_) + (size_t)t * BODY_STRIDE;
+    const uint32_t wl = rd(ru + RU_WL), wbase = rd(ru + RU_WBASE), wskip = rd(ru + RU_WSKIP), send = rd(ru + RU_SEND), runwin = rd(ru + RU_RUNWIN);
+    uint32_t out_pos = rd(sg), pend = rd(sg + 1);
+    const uint32_t abs0 = wbase + seg_at(t, runwin, wl, wskip, send);          // block-relative start of this segment
+    // Every position below follows from the sizes, so all loads are issued before the first store that waits for one: the first
+    // literals and the block's last literals where they are at most 1 KiB (Piece; longer ones are copied first, on their own), the
+    // body's first 4 KiB -- one memory round trip for a segment, not one per part.
+    const bool has = rd(sg + 2) != 0u;
+    const uint32_t fl = rd(sg + 3), L = pend + fl, ml = rd(sg + 4) - 4u, bl = has ? rd(sg + 6) : 0u;
+    const uint32_t lit_at = out_pos + 1u + len_ext_bytes(L), body_at = lit_at + L;
+    if (has) {
         put_len_header(gout + out_pos, L, ml < 15u ? ml : 15u, lane);
-        out_pos += 1u + len_ext_bytes(L);
-        copy_bytes(gout + out_pos, gin + (abs0 + fl - L), L, lane);
-        out_pos += L;
-        copy_bytes(gout + out_pos, body, bl, lane);
-        out_pos += bl;
-        pend = mp[5u * w + 3u];
+        out_pos = body_at + bl;
+        pend = rd(sg + 5);
     } else {
-        pend += sl;
+        pend += seg_at(t + 1u, runwin, wl, wskip, send) - seg_at(t, runwin, wl, wskip, send);
     }
-    if (w == WORKERS - 1u) {
-        if (last_win) {
-            // the block's last literals (compress.rs handle_last_literals): token, length bytes, bytes; no offset
-            put_len_header(gout + out_pos, pend, 0u, lane);
-            out_pos += 1u + len_ext_bytes(pend);
-            copy_bytes(gout + out_pos, gin + (blk_len - pend), pend, lane);
-            out_pos += pend;
-            if (lane == 0u) { *out_len = poisoned ? 0u : out_pos; *status = poisoned ? 66 /* a window never got its carry: launch_compress_wave's second launch encodes the block again */ : 0; }
-        } else if (lane == 0u) {
-            cp[2u * carry_slot] = out_pos;
-            cp[2u * carry_slot + 1u] = pend;
-        }
+    const bool fin = t == WORKERS - 1u && rd(ru + RU_LAST_WIN) != 0u;
+    const uint32_t blk_len = rd(ru + RU_BLK_LEN);
+    const uint32_t fin_at = out_pos + 1u + len_ext_bytes(pend);
+    if (fin) {
+        // the block's last literals (compress.rs handle_last_literals): token, length bytes, bytes; no offset
+        put_len_header(gout + out_pos, pend, 0u, lane);
+        out_pos = fin_at + pend;
+    }
+    const bool lit_small = has && L <= PIECE, fin_small = fin && pend <= PIECE;
+    if (has && !lit_small) copy_bytes(gout + lit_at, gin + (abs0 + fl - L), L, lane);
+    if (fin && !fin_small) copy_bytes(gout + fin_at, gin + (blk_len - pend), pend, lane);
+    Piece pl = piece_load(gin + (abs0 + fl - L), lit_small ? L : 0u, lane);
+    Piece pf = piece_load(gin + (blk_len - pend), fin_small ? pend : 0u, lane);
+    const uint32_t bh = bl < 4096u ? bl : 4096u, be = bh & ~15u;
+    u32x4 bv[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t o = 1024u * j + 16u * lane;
+        bv[j] = u32x4{0u, 0u, 0u, 0u};
+        if (o + 16u <= bh) __builtin_memcpy(&bv[j], (const void*)(body + o), 16);
+    }
+    uint32_t bt = 0u;
+    if (be + lane < bh) bt = body[be + lane];                         // (a body of more than 4 KiB: bh == be, its end is copied below)
+    piece_store(gout + lit_at, lit_small ? L : 0u, lane, pl);
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t o = 1024u * j + 16u * lane;
+        if (o + 16u <= bh) __builtin_memcpy((void*)(gout + body_at + o), &bv[j], 16);
+    }
+    if (be + lane < bh) gout[body_at + be + lane] = (uint8_t)bt;
+    piece_store(gout + fin_at, fin_small ? pend : 0u, lane, pf);
+    if (bl > 4096u) copy_bytes(gout + body_at + 4096u, body + 4096u, bl - 4096u, lane);
+    if (fin) {
+        const uint32_t poisoned = rd(ru + RU_POISONED);
+        g_u32* out_len = (g_u32*)rd_ptr(ru + RU_OUT_LEN);
+        g_i32* status = (g_i32*)rd_ptr(ru + RU_STATUS);
+        if (lane == 0u) { *out_len = poisoned ? 0u : out_pos; *status = poisoned ? 66 /* a window never got its carry: launch_compress_wave's second launch encodes the block again */ : 0; }
     }
 }
 
@@ -1386,7 +1494,7 @@ __device__ __attribute__((noinline)) void load_window(const uint8_t* __restrict_
 // DICTIONARIES (CompressArgs::dict_*, lz4flex_compress_batch_ex): the same as history, with h = min(dict_len, HIST) bytes that come
 // from the END of the block's dictionary (any h in [1, HIST]; the item is [dictionary tail | block], in_off = the block's in_off - h
 // so that item position p >= h is in_base[in_off + p]) -- windows advance by HIST, no sub-windows.  The windows the indexer and the
-// workers read go through the workgroup's staging slot (stage_window); place_segment reads literals only, never history.
+// workers read go through the workgroup's staging slot (stage_window); copy_segment reads literals only, never history, and from the input itself.
 // What the _shared_ kernels work on: the batch and the one dictionary of lz4flex_compress_batch_shared_dict.  Everything from item_load to
 // wave_body is a template on the argument type: with CompressArgs itself (every other kernel) the shared-dictionary code is not even
 // compiled (if constexpr), so those kernels are what they were.
@@ -1563,8 +1671,9 @@ __device__ __forceinline__ uint32_t keep_tag(const SetArgs& a, const Item& t) { 
 __device__ __forceinline__ bool keep_hit(const SetArgs&, const Item& t, uint32_t kept) { return kept == t.did + 1u; }
 
 // prof (nullable, tools only): cycle sums per role, [0] indexer busy, [1] indexer at barriers, [2] workers matching,
-// [3] workers at the barrier behind matching, [4] placing, [5] loading the next window, [6] at the barrier behind loading,
-// [7] windows
+// [3] workers at the barrier behind matching, [4] placing (the deferred copies of the window before, and the last window's copies),
+// [5] loading the next window, [6] at the barrier behind loading, [7] windows, [PROF_RESOLVE] resolving ([8 .. 26]: the variant builds')
+constexpr uint32_t PROF_RESOLVE = 27u;
 template <class A>
 __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, uint32_t* __restrict__ carry,
                                           unsigned long long* __restrict__ prof, const int32_t redo, const uint32_t carry_spins) {
@@ -1583,14 +1692,20 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
 #endif
     uint8_t* my_ws = ws + (size_t)blockIdx.x * WS_BYTES;
     uint8_t* slots = my_ws;                                        // two cand[] slots
-    uint8_t* bodies = my_ws + 2u * SLOT_BYTES;
+    uint8_t* bodies = my_ws + 2u * SLOT_BYTES;                       // two sets: window k's bodies are set k & 1
     uint8_t* stg = a.stage + (size_t)blockIdx.x * STAGE_BYTES;       // dictionary items: the window being indexed (stage_window)
 
     const bool wmode = carry != nullptr;                          // windows (not blocks) are dealt to the workgroups
     lds_u32* giq = (lds_u32*)(lds + L_META) + 5u * WORKERS + 4u;   // window mode: item indices drawn by thread 0
     uint32_t* wctr = wmode ? carry + CARRY_DWORDS * (size_t)a.n : nullptr;   // per-block window counters behind the carry slots
     Item it, ix;                                                  // the window being matched; the next one (the indexer runs one window ahead)
-    if (threadIdx.x == 0u) giq[6] = 0u;                           // place_segment's mailbox: no iteration yet
+    lds_u32* meta = (lds_u32*)(lds + L_META);
+    if (threadIdx.x == 0u) {
+        giq[6] = 0u;                                              // resolve_window's mailbox: no iteration yet
+        meta[M_TICKET] = 0u;
+        meta[M_REC + REC_UNI + RU_COUNT] = 0u;                    // no window to copy yet
+        meta[M_REC + REC_WORDS + REC_UNI + RU_COUNT] = 0u;
+    }
     if (wmode) {
         if (threadIdx.x == 0u) {
             uint32_t b = a.n, wn = 0u;
@@ -1663,12 +1778,12 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
     // (sums are kept in registers and added to prof[] once, when the workgroup is done: an atomic per tick made the
     // waits look twice as long as they are)
     uint64_t t_prev = prof ? __builtin_readcyclecounter() : 0ull;
-    uint64_t t_acc[7] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    uint64_t t_acc[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};      // ([7]: resolving)
     auto tick = [&](uint32_t slot) {
         if (prof) {
             const uint64_t t = __builtin_readcyclecounter();
 #pragma unroll
-            for (uint32_t i = 0; i < 7u; ++i) t_acc[i] += i == slot ? t - t_prev : 0ull;
+            for (uint32_t i = 0; i < 8u; ++i) t_acc[i] += i == slot ? t - t_prev : 0ull;
             t_prev = t;
         }
     };
@@ -1719,19 +1834,47 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
                 const RunGeom rg = run_geom(it);
                 lds_u32* mp = (lds_u32*)(lds + L_META) + 5u * w;
                 if (w == 0u) {
-                    emit_generic(bodies, 0u, 0u, 0u, 1u, rg.me - rg.ms, 1u, lane);
+                    emit_generic(bodies + (size_t)(k & 1u) * BODY_SET, 0u, 0u, 0u, 1u, rg.me - rg.ms, 1u, lane);
                     if (lane == 0u) { mp[0] = 1u; mp[1] = rg.ms - skip; mp[2] = rg.me - rg.ms; mp[3] = wl - rg.me; mp[4] = 2u + len_ext_bytes(rg.me - rg.ms - 4u); }
                 } else if (lane == 0u) {
                     mp[0] = 0u; mp[1] = 0u; mp[2] = 0u; mp[3] = 0u; mp[4] = 0u;
                 }
             } else if (s0 < s1) {
-                match_segment(slots + (size_t)(k & 1u) * SLOT_BYTES, bodies + (size_t)w * BODY_STRIDE, w, lane, s0, s1, mfl_end, mend, prof);
+                match_segment(slots + (size_t)(k & 1u) * SLOT_BYTES, bodies + (size_t)(k & 1u) * BODY_SET + (size_t)w * BODY_STRIDE, w, lane, s0, s1, mfl_end, mend, prof);
             } else if (lane == 0u) {                              // an empty segment (history only, or behind the block's end)
                 lds_u32* mp = (lds_u32*)(lds + L_META) + 5u * w;
                 mp[0] = 0u; mp[1] = 0u; mp[2] = 0u; mp[3] = 0u; mp[4] = 0u;
             }
         }
         tick(w == WORKERS ? 0u : 2u);
+        if (w != WORKERS) {
+            // The copies of the window before (record and body set (k - 1) & 1; none: no tickets).  Every worker draws until the tickets
+            // are gone, so all of them are done before the barrier below, which makes that record and that body set reusable.  The
+            // bodies were stored by other wavefronts: their release is the fence in front of the barrier a window ago, the acquire here.
+            const uint32_t rec = M_REC + ((k + 1u) & 1u) * REC_WORDS;
+            const uint32_t cnt = uni(meta[rec + REC_UNI + RU_COUNT]);
+            auto draw = [&]() -> uint32_t {
+                uint32_t t = 0u;
+                if (lane == 0u) t = __hip_atomic_fetch_add(meta + M_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                return uni(t);
+            };
+            uint32_t t = cnt != 0u ? draw() : cnt;
+            if (t < cnt) {
+#ifndef LZ4W_NO_PRIO
+                __builtin_amdgcn_s_setprio(0);                     // latency work: the wavefronts that are still matching issue first
+#endif
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                do {
+                    copy_segment(lds, rec, cnt - 1u - t, bodies + (size_t)((k + 1u) & 1u) * BODY_SET, lane);   // (the last segment first: it also has the block's last literals)
+                    t = draw();
+                } while (t < cnt);
+#ifndef LZ4W_NO_PRIO
+                __builtin_amdgcn_s_setprio(3);
+#endif
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this window's body: read by whoever draws the segment
+            tick(4u);
+        }
         __syncthreads();
         tick(w == WORKERS ? 1u : 3u);
         if (wmode && threadIdx.x == 0u) {                          // the window behind ix
@@ -1740,22 +1883,35 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
             giq[2] = b2; giq[3] = w2;
         }
         if (w != WORKERS) {
+            const uint32_t rec = M_REC + (k & 1u) * REC_WORDS;
+            if (threadIdx.x == 0u) meta[M_TICKET] = 0u;            // (every draw of the window before precedes the barrier above)
             if (it.skip) {
-                if (threadIdx.x == 0u) { a.out_len[it.blk] = 0u; a.status[it.blk] = ((HAS_DIGEST<A> || a.dict_len != nullptr) && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+                if (threadIdx.x == 0u) {
+                    a.out_len[it.blk] = 0u; a.status[it.blk] = ((HAS_DIGEST<A> || a.dict_len != nullptr) && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
+                    meta[rec + REC_UNI + RU_COUNT] = 0u;           // nothing to copy
+                }
             } else {
-                place_segment(lds, a.in_base + it.in_off, it.len, it.win, last_win, wl, win_base(it), win_skip(it), win_send(it), bodies + (size_t)w * BODY_STRIDE,
-                              a.out_base + a.out_off[it.blk], k & 1u, w, lane, a.out_len + it.blk, a.status + it.blk,
-                              wmode ? carry + CARRY_DWORDS * (size_t)it.blk : nullptr, k + 1u, carry_spins, run_flag[k & 1u]);
+                resolve_window(lds, rec, a.in_base + it.in_off, it.len, it.win, last_win, wl, win_base(it), win_skip(it), win_send(it),
+                               a.out_base + a.out_off[it.blk], k & 1u, w, lane, a.out_len + it.blk, a.status + it.blk,
+                               wmode ? carry + CARRY_DWORDS * (size_t)it.blk : nullptr, k + 1u, carry_spins, run_flag[k & 1u]);
             }
         }
-        tick(w == WORKERS ? 1u : 4u);
+        tick(w == WORKERS ? 1u : 7u);
         if (prof && threadIdx.x == 0u) atomicAdd(prof + 7, 1ull);
         it = ix;
         k += 1u;
         if (it.blk >= a.n) {
+            // the last window: copied at once, every worker its own segment
+            __syncthreads();
+            tick(w == WORKERS ? 1u : 6u);
+            const uint32_t lrec = M_REC + ((k + 1u) & 1u) * REC_WORDS;
+            if (w != WORKERS && meta[lrec + REC_UNI + RU_COUNT] != 0u) {
+                copy_segment(lds, lrec, w, bodies + (size_t)((k + 1u) & 1u) * BODY_SET, lane);
+                tick(4u);
+            }
             if (prof && lane == 0u)
-                for (uint32_t i = 0; i < 7u; ++i)
-                    if (t_acc[i] != 0ull) atomicAdd(prof + i, (unsigned long long)t_acc[i]);
+                for (uint32_t i = 0; i < 8u; ++i)
+                    if (t_acc[i] != 0ull) atomicAdd(prof + (i < 7u ? i : PROF_RESOLVE), (unsigned long long)t_acc[i]);
 #ifdef LZ4W_PROF_WORKERS    // tools: matching cycles per worker -> prof[16 + w] (the segment table above comes from these)
             if (prof && lane == 0u && w < WORKERS) atomicAdd(prof + 16u + w, (unsigned long long)t_acc[2]);
 #endif

@@ -197,7 +197,7 @@ size_t compress_wave_workspace_bytes(int n_workgroups);
 // where the last shared-dictionary launch on `workspace` counts the items whose first window started from the digest (device memory)
 const uint32_t* compress_wave_shared_counter(const void* workspace, int n_workgroups);
 hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_workgroups, hipStream_t s,
-                                unsigned long long* prof = nullptr,    // prof: 8 cycle counters (tools), nullable
+                                unsigned long long* prof = nullptr,    // prof: 32 cycle counters (tools; lz4_compress_wave.hip wave_body), nullable
                                 bool carry_wait = true,                // tests: false = a window that has to wait for its predecessor gives up at once
                                 const SharedDictArgs* shared_dict = nullptr,    // nullable: the batch's one dictionary (the _shared_ kernels)
                                 const DictSetArgs* dict_set = nullptr);         // nullable (not with shared_dict): a dictionary per block out of a set (the _set_ kernels)
