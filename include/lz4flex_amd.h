@@ -698,7 +698,8 @@ int lz4flex_frame_decoder_set_batch_bytes(lz4flex_frame_decoder *d, size_t bytes
 void lz4flex_frame_decoder_free(lz4flex_frame_decoder *d);
 
 /* One-shot helpers over flat host buffers: FrameEncoder::with_frame_info + write_all + finish,
- * and FrameDecoder::new + read_to_end (first frame only; *consumed = input bytes read). */
+ * and FrameDecoder::new + read_to_end (first frame only; *consumed = input bytes read -- on success where the reference's reader
+ * stands: behind the EndMark and content checksum, at the end of a cut input, or behind the empty block that ended the reading). */
 int64_t lz4flex_frame_compress(const uint8_t *in, size_t in_len, const lz4flex_frame_info *info,
                                uint8_t *out, size_t out_cap, lz4flex_err_detail *detail);
 int64_t lz4flex_frame_decompress(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap,
@@ -790,7 +791,11 @@ int lz4flex_frame_decompress_many(lz4flex_ctx *ctx, const void *in_base, const u
  *   once, with a sink of the block size: -LZ4FLEX_FE_DECOMPRESSION, detail = the decoder's inner / expected / actual); a truncated
  *   frame (-LZ4FLEX_FE_IO; also one that ends where its EndMark should be, which a streaming reader takes for "no more bytes yet",
  *   src/frame/decompress.rs:231-238) or -LZ4FLEX_FE_BLOCK_TOO_BIG where the walk stopped; -LZ4FLEX_FE_CONTENT_LENGTH when the header's content
- *   size is not content_off[blocks].  NO CHECKSUM IS LOOKED AT by create.  -LZ4FLEX_E_UNSUPPORTED: BlockMode::Linked frames (a block
+ *   size is not content_off[blocks].  A sound block of no bytes at all (a stored block of length 0, a compressed block that decodes to
+ *   nothing) ends the index as it ends the reader's read_to_end (src/frame/decompress.rs:344-349): the blocks in front of it are the
+ *   index, frame_bytes is the offset behind it, and neither the content size nor anything behind it is looked at.  (_info is the
+ *   header's FrameInfo verbatim in every case: its content_size and content_checksum say what the header says, not what such an index holds.)
+ *   NO CHECKSUM IS LOOKED AT by create.  -LZ4FLEX_E_UNSUPPORTED: BlockMode::Linked frames (a block
  *   needs the 64 KiB in front of it, transitively: there is nothing to seek in) and legacy frames.  -LZ4FLEX_E_INVALID_ARG: out or
  *   frame NULL, a mem_kind other than HOST / DEVICE (checked before a context is looked at); -LZ4FLEX_E_NO_DEVICE without a device.
  *   _table copies the host tables out (blocks + 1, blocks, blocks entries; any pointer may be NULL).

@@ -407,16 +407,29 @@ struct lz4flex_frame_decoder {
     std::vector<uint64_t> in_off, out_off, detail;
     std::vector<uint32_t> in_len, out_cap, out_len;
     std::vector<int32_t> status;
-    struct Item { size_t off, len; };     // decoded bytes waiting to be read: offsets into `out` (Independent) or `ldst` (Linked)
-    std::vector<Item> ready;   // decoded pieces in stream order (len 0 = a block that decoded to nothing)
+    struct Item { size_t off, len, src_end; };   // decoded bytes waiting to be read: offsets into `out` (Independent) or `ldst` (Linked)
+    std::vector<Item> ready;   // decoded pieces in stream order (len 0 = a block that decoded to nothing; src_end: the input read up to its end)
     size_t ready_idx = 0, ready_pos = 0;
     int pending_err = 0;       // surfaces after the pieces before it were delivered
     lz4flex_err_detail pending_detail{};
     bool pending_zero = false; // EndMark reached: one read() returns 0
-    // Linked-mode window (frame/decompress.rs:62-72): exact mirror of the reference's dst ring
     PinBuf ldst;
-    size_t ext_dict_offset = 0, ext_dict_len = 0, dst_start = 0;
+    size_t dst_start = 0;
     size_t lhave = 0;              // Linked: valid bytes in ldst (history + what the last call produced)
+    // Linked mode: the reference's dst ring (frame/decompress.rs:62-72,145-156,195-222), mirrored for the two things it decides -- the sink
+    // of a compressed block (a block size behind ring_start; once the ring has wrapped, everything up to the external dictionary's start,
+    // as much as TWO block sizes) and the positions an OutputTooSmall names.  The bytes themselves live in ldst.
+    size_t ext_dict_offset = 0, ext_dict_len = 0, ring_start = 0;
+    void ring_enter(size_t mbs) {                             // :195-222
+        if (ring_start + mbs > 2 * mbs + WINDOW_SIZE) { ext_dict_offset = ring_start - WINDOW_SIZE; ext_dict_len = WINDOW_SIZE; ring_start = 0; }
+        else if (ring_start + ext_dict_len > WINDOW_SIZE) {
+            const size_t delta = std::min(ext_dict_len, ring_start + ext_dict_len - WINDOW_SIZE);
+            ext_dict_offset += delta; ext_dict_len -= delta;
+        }
+    }
+    size_t ring_sink_end(size_t mbs) const { return ext_dict_len ? ext_dict_offset : ring_start + mbs; }   // :280-306
+    size_t in_total = 0;           // bytes taken from the reader
+    size_t zero_end = (size_t)-1;  // in_total behind the empty block that made the last read return 0 (lz4flex_frame_decompress: *consumed)
 
     bool io_failed = false;    // the read callback itself reported an error (not a short read)
     // read_exact; returns 0 ok, 1 clean EOF before any byte, -code on short read / error
@@ -424,10 +437,11 @@ struct lz4flex_frame_decoder {
         size_t got = 0;
         while (got < n) {
             const int64_t k = r(user, p + got, n - got);
-            if (k < 0) { io_failed = true; return -LZ4FLEX_FE_IO; }
+            if (k < 0) { io_failed = true; in_total += got; return -LZ4FLEX_FE_IO; }
             if (k == 0) break;
             got += (size_t)k;
         }
+        in_total += got;
         if (got_out) *got_out = got;
         if (got == n) return 0;
         return got == 0 ? 1 : -LZ4FLEX_FE_IO;
@@ -458,7 +472,7 @@ struct lz4flex_frame_decoder {
         have_frame = true;
         content_hasher.reset(0);
         content_len = 0;
-        ext_dict_len = 0; ext_dict_offset = 0; dst_start = 0;
+        ext_dict_len = 0; ext_dict_offset = 0; dst_start = 0; ring_start = 0;
         lhave = 0;                                            // Linked: ldst = [history | this launch's blocks], grown on demand, never shrunk
         return 0;
     }
@@ -487,28 +501,28 @@ struct lz4flex_frame_decoder {
     // One block off the stream into `comp` (frame/decompress.rs:231-278): BlockInfo word, EndMark, BlockTooBig, payload, optional
     // block checksum.  END: the EndMark (handled once the staged blocks are decoded); EOFS: no more bytes where a BlockInfo starts --
     // Ok(0), the frame stays open (:231-238; pending_zero is set); ERR: fail() was called and the payload, if any, taken back;
-    // RAW / COMP: a stored / compressed block of `len` bytes at comp[at].  Everything below RAW ends the gathering.
+    // RAW / COMP: a stored / compressed block of `len` bytes at comp[at], `end` = in_total behind it.  Everything below RAW ends the gathering.
     enum BlockKind { END, EOFS, ERR, RAW, COMP };
-    struct BlockRead { BlockKind kind; size_t at, len; };
+    struct BlockRead { BlockKind kind; size_t at, len, end; };
     BlockRead read_block(size_t mbs) {
         uint8_t bi[4];
         if (read_exact(bi, 4) != 0) {
-            if (io_failed) { fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0}; }
+            if (io_failed) { fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0, 0}; }
             pending_zero = true;
-            return {EOFS, 0, 0};
+            return {EOFS, 0, 0, 0};
         }
         const uint32_t size = rd32(bi);
-        if (size == 0) return {END, 0, 0};
+        if (size == 0) return {END, 0, 0, 0};
         const size_t len = size & ~BLOCK_UNCOMPRESSED_SIZE_BIT, at = comp.size();
-        if (len > mbs) { fail(-LZ4FLEX_FE_BLOCK_TOO_BIG); return {ERR, 0, 0}; }
+        if (len > mbs) { fail(-LZ4FLEX_FE_BLOCK_TOO_BIG); return {ERR, 0, 0, 0}; }
         comp.resize(at + len);
-        if (len && read_exact(comp.data() + at, len) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0}; }
+        if (len && read_exact(comp.data() + at, len) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0, 0}; }
         if (fi.block_checksums) {
             uint8_t c[4];
-            if (read_exact(c, 4) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0}; }
-            if (XxHash32::oneshot(0, comp.data() + at, len) != rd32(c)) { comp.resize(at); fail(-LZ4FLEX_FE_BLOCK_CHECKSUM); return {ERR, 0, 0}; }
+            if (read_exact(c, 4) != 0) { comp.resize(at); fail(-LZ4FLEX_FE_IO); return {ERR, 0, 0, 0}; }
+            if (XxHash32::oneshot(0, comp.data() + at, len) != rd32(c)) { comp.resize(at); fail(-LZ4FLEX_FE_BLOCK_CHECKSUM); return {ERR, 0, 0, 0}; }
         }
-        return {(size & BLOCK_UNCOMPRESSED_SIZE_BIT) ? RAW : COMP, at, len};
+        return {(size & BLOCK_UNCOMPRESSED_SIZE_BIT) ? RAW : COMP, at, len, in_total};
     }
 
     // Independent frames: gather blocks up to the batch size, decode them in one launch.
@@ -525,7 +539,7 @@ struct lz4flex_frame_decoder {
         comp.clear(); in_off.clear(); in_len.clear(); out_off.clear(); out_cap.clear();
         ready.clear(); ready_idx = 0; ready_pos = 0;
         ready_linked = false;
-        struct Slot { bool raw; size_t out_at; size_t idx; size_t raw_len; };
+        struct Slot { bool raw; size_t out_at; size_t idx; size_t raw_len; size_t end; };
         std::vector<Slot> slots;
         size_t out_need = 0;
         bool saw_end = false;
@@ -536,7 +550,7 @@ struct lz4flex_frame_decoder {
             if (b.kind < RAW) break;
             const bool raw = b.kind == RAW;
             const size_t at = b.at, len = b.len;
-            Slot s{raw, out_need, in_off.size(), len};
+            Slot s{raw, out_need, in_off.size(), len, b.end};
             // An LZ4 block expands by less than 255x (one length byte adds at most 255 output bytes), so min(block size,
             // 255 len + 64) is as good a sink as the reference's block-size buffer and a frame of tiny blocks cannot make the
             // read-ahead reserve (and the device arena mirror) gigabytes.
@@ -576,13 +590,13 @@ struct lz4flex_frame_decoder {
                 staged = true;
                 if (out.size() < out_need) out.resize(out_need);
             }
-            if (!direct) ready.push_back({s.out_at, plen});
+            if (!direct) ready.push_back({s.out_at, plen, s.end});
             else if (!staged) {
                 if (s.out_at != delivered && plen) memmove(direct + delivered, direct + s.out_at, plen);
                 delivered += plen;
             } else {
                 if (plen) memcpy(out.data() + staged_at, direct + s.out_at, plen);
-                ready.push_back({staged_at, plen});
+                ready.push_back({staged_at, plen, s.end});
                 staged_at += plen;
             }
         }
@@ -614,16 +628,18 @@ struct lz4flex_frame_decoder {
         dst_start = lhave;
         const size_t carry = dst_start;                      // bytes of history at the front of ldst
         bool saw_end = false, raw_tail = false;
-        size_t raw_at = 0, raw_len = 0;
+        size_t raw_at = 0, raw_len = 0, raw_end = 0;
+        std::vector<size_t> ends;                            // in_total behind each compressed block
         const size_t out_budget = std::max<size_t>(batch_bytes, mbs) * (batch_auto ? 4u : 1u);
-        // (sink positions are 32-bit: an explicit batch size of 4 GiB or more must not wrap them)
-        const size_t pos_blocks = (size_t)((0xFFFFFFFFull - carry) / mbs) - 1u;
+        // (sink positions are 32-bit: an explicit batch size of 4 GiB or more must not wrap them; halved, since a block may be
+        // given up to two block sizes of room, see below)
+        const size_t pos_blocks = ((size_t)((0xFFFFFFFFull - carry) / mbs) - 1u) / 2u;
         while (in_off.size() < std::min(max_blocks, pos_blocks) && (in_off.empty() || (in_off.size() + 1) * mbs <= out_budget)) {
             const BlockRead b = read_block(mbs);
             saw_end = b.kind == END;
             if (b.kind < RAW) break;
-            if (b.kind == RAW) { raw_tail = true; raw_at = b.at; raw_len = b.len; break; }
-            in_off.push_back(b.at); in_len.push_back((uint32_t)b.len);
+            if (b.kind == RAW) { raw_tail = true; raw_at = b.at; raw_len = b.len; raw_end = b.end; break; }
+            in_off.push_back(b.at); in_len.push_back((uint32_t)b.len); ends.push_back(b.end);
         }
         const size_t nb = in_off.size();
         if (ldst.size() < carry + (nb + 1) * mbs) ldst.resize(carry + (nb + 1) * mbs);
@@ -634,17 +650,29 @@ struct lz4flex_frame_decoder {
         std::vector<uint64_t> zero_off(nb, 0);
         size_t first = 0;
         bool failed = false;
+        // the pieces handed out: one for all the bytes, cut where a block decoded to nothing -- there a read returns 0 once (read_more() == 0,
+        // frame/decompress.rs:344-349) with the bytes in front of it delivered and the ones behind it still to come
+        size_t piece_at = 0;
+        auto empty_block = [&](size_t src_end) {
+            if (produced_total != piece_at) ready.push_back({carry + piece_at, produced_total - piece_at, src_end});
+            ready.push_back({carry + produced_total, 0, src_end});
+            piece_at = produced_total;
+        };
         // A launch assumes full blocks; the blocks behind a short one have to be decoded again from their real position.  A
         // frame of many short blocks (a flush() after every small write) would cost a launch and a re-decode of everything
         // behind it per block if every launch took the whole rest of the run: the run length is cut to a quarter whenever a
         // short block invalidates the blocks behind it and doubles again while launches end clean -- launches and decoded
         // blocks stay linear in the number of blocks.
-        size_t run = nb;
+        // A launch also gives every block a sink of one block size.  The reference's is larger right behind a wrap of its ring
+        // (ring_sink_end): a block that ran out of room there is decoded once more, alone, with the room the reference gives it.
+        size_t run = nb, roomy = (size_t)-1;                  // roomy: the block that is being given the ring's sink
         while (first < nb) {
-            const size_t m = std::min(run, nb - first);
+            const size_t m = first == roomy ? 1 : std::min(run, nb - first);
+            const size_t room = first == roomy ? ring_sink_end(mbs) - ring_start : mbs;
+            if (ldst.size() < carry + produced_total + (m - 1) * mbs + room) ldst.resize(carry + produced_total + (m - 1) * mbs + room);
             for (size_t k = 0; k < m; k++) {
                 pos[k] = (uint32_t)(carry + produced_total + k * mbs);
-                cap[k] = pos[k] + (uint32_t)mbs;
+                cap[k] = pos[k] + (uint32_t)(k == 0 ? room : mbs);
             }
             lz4flex_decompress_ext ext{};
             ext.out_pos = pos.data();
@@ -653,19 +681,28 @@ struct lz4flex_frame_decoder {
                                                        detail.data() + 2 * first, &ext, LZ4FLEX_MEM_HOST | LZ4FLEX_MEM_CHAINED, nullptr);
             if (rc) { fail(rc); pending_zero = false; failed = true; break; }
             size_t k = 0;
+            bool again = false;
             for (; k < m; k++) {
                 const size_t i = first + k;
+                if (i != roomy) ring_enter(mbs);
                 if (status[i] != 0) {
+                    if (status[i] == LZ4FLEX_E_OUTPUT_TOO_SMALL && i != roomy && ring_sink_end(mbs) - ring_start > mbs) { roomy = i; again = true; break; }
                     lz4flex_err_detail d{}; d.expected = detail[2 * i]; d.actual = detail[2 * i + 1]; d.inner = status[i];
+                    if (status[i] == LZ4FLEX_E_OUTPUT_TOO_SMALL) {     // (the positions the reference's sink has, frame/decompress.rs:288-305)
+                        d.expected = d.expected - pos[k] + ring_start;
+                        d.actual = ring_sink_end(mbs);
+                    }
                     fail(-LZ4FLEX_FE_DECOMPRESSION, &d);
                     pending_zero = false;
                     failed = true;
                     break;
                 }
                 produced_total += out_len[i];
+                ring_start += out_len[i];
+                if (out_len[i] == 0) empty_block(ends[i]);
                 if (out_len[i] != mbs) { k++; break; }        // the blocks behind a short one were given a wrong position
             }
-            run = k < m ? std::max<size_t>(1, m / 4) : std::min(nb, 2 * m);
+            if (!again) run = k < m ? std::max<size_t>(1, m / 4) : std::min(nb, 2 * m);
             first += k;
             if (failed) break;
         }
@@ -674,10 +711,12 @@ struct lz4flex_frame_decoder {
             if (ldst.size() < carry + produced_total + raw_len) ldst.resize(carry + produced_total + raw_len);
             memcpy(ldst.data() + carry + produced_total, comp.data() + raw_at, raw_len);
             produced_total += raw_len;
+            ring_enter(mbs);
+            ring_start += raw_len;
+            if (raw_len == 0) empty_block(raw_end);
         }
         // ---- hand the bytes out where they are (ready items index `ldst` in Linked mode); they stay there as history
-        if (produced_total) ready.push_back({carry, produced_total});
-        else if (!failed && !pending_err && (nb != 0 || raw_tail)) ready.push_back({carry, 0});     // (an empty block: read_more() == 0)
+        if (produced_total != piece_at) ready.push_back({carry + piece_at, produced_total - piece_at, 0});
         content_len += produced_total;
         if (fi.content_checksum && produced_total) content_hasher.write(ldst.data() + carry, produced_total);
         lhave = carry + produced_total;
@@ -695,7 +734,7 @@ struct lz4flex_frame_decoder {
                 if (it.len == 0 || ready_pos == it.len) {
                     const bool empty_block = it.len == 0;
                     ready_idx++; ready_pos = 0;
-                    if (empty_block) { *p = out.data(); return 0; }      // read_more() == 0: an empty slice
+                    if (empty_block) { zero_end = it.src_end; *p = out.data(); return 0; }      // read_more() == 0: an empty slice
                     continue;
                 }
                 *p = ready_base() + it.off + ready_pos;
@@ -726,7 +765,7 @@ struct lz4flex_frame_decoder {
         for (;;) {
             while (ready_idx < ready.size()) {
                 const Item& it = ready[ready_idx];
-                if (it.len == 0) { ready_idx++; ready_pos = 0; return 0; }   // read_more() == 0
+                if (it.len == 0) { zero_end = it.src_end; ready_idx++; ready_pos = 0; return 0; }   // read_more() == 0
                 const size_t n = std::min(it.len - ready_pos, len);
                 if (n == 0) return 0;   // zero-length destination
                 memcpy(buf, ready_base() + it.off + ready_pos, n);
@@ -871,7 +910,9 @@ int64_t lz4flex_frame_decompress(const uint8_t* in, size_t in_len, uint8_t* out,
         if (rc <= 0) break;
         pos += (size_t)rc;
     }
-    if (consumed) *consumed = fr.pos;
+    // (the decoder gathers blocks ahead of the one it hands out: where an empty block ended the reading, the reference's reader stands behind
+    // that block, frame/decompress.rs:344-349,392-407)
+    if (consumed) *consumed = rc == 0 && d->zero_end != (size_t)-1 ? d->zero_end : fr.pos;
     lz4flex_frame_decoder_free(d);
     return rc < 0 ? rc : (int64_t)pos;
 }

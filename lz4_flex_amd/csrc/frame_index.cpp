@@ -79,7 +79,7 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
         const size_t mb = (size_t)max_blocks;
         l = Layout{64};
         a_pay = l.take(8 * mb); a_word = l.take(4 * mb); a_info = l.take(16); a_scan_len = l.take(4 * mb); a_size = l.take(8 * mb);
-        a_scan_st = l.take(4 * mb); a_bad = l.take(4); a_content = l.take(8 * (mb + 1)); a_tiles = l.take(8 * (mb / PACKED_SCAN_TILE + 2));
+        a_scan_st = l.take(4 * mb); a_bad = l.take(8); a_content = l.take(8 * (mb + 1)); a_tiles = l.take(8 * (mb / PACKED_SCAN_TILE + 2));
         a_one = l.take(64);
         void* p = nullptr;
         TRY_RC(ctx_scratch(c, 0, l.end + 64, &p));
@@ -90,8 +90,8 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
         if (info[1] != 3u || max_blocks >= most) break;
         max_blocks = most;
     }
-    const uint32_t n = info[0], walk_st = info[1];
-    const uint64_t end = (uint64_t)info[2] | ((uint64_t)info[3] << 32);
+    uint32_t n = info[0], walk_st = info[1];
+    uint64_t end = (uint64_t)info[2] | ((uint64_t)info[3] << 32);
     uint64_t* d_pay = (uint64_t*)(w + a_pay);
     uint32_t* d_word = (uint32_t*)(w + a_word);
     uint32_t* d_scan_len = (uint32_t*)(w + a_scan_len);
@@ -104,13 +104,14 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
     if (n) TRY_HIP(launch_size_scan(f, d_pay, d_scan_len, nullptr, n, d_size, d_scan_st, c->size_serial, s));
     TRY_HIP(launch_frame_index_sizes(d_word, d_scan_st, n, bs, d_size, d_bad, s));
     TRY_HIP(launch_packed_scan(d_size, n, 1u, ~0ull, 0u, (uint64_t*)(w + a_tiles), d_content, nullptr, nullptr, nullptr, s));
-    uint32_t first_bad = 0;
+    uint32_t firsts[2] = {0, 0};
     uint64_t total = 0;
-    TRY_HIP(hipMemcpyAsync(&first_bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+    TRY_HIP(hipMemcpyAsync(firsts, d_bad, 8, hipMemcpyDeviceToHost, s));
     TRY_HIP(hipMemcpyAsync(&total, d_content + n, 8, hipMemcpyDeviceToHost, s));
     TRY_HIP(hipStreamSynchronize(s));
+    const uint32_t first_bad = firsts[0], first_empty = firsts[1];
     // ---- the earliest defect in stream order (frame/decompress.rs:231-332): a block that does not decode, in front of where the walk stopped
-    if (first_bad < n) {
+    if (first_bad < n && first_bad < first_empty) {
         // its error is the decoder's own: once through the ordinary batch path, the sink a block size as FrameDecoder's is
         struct One { uint64_t out_off; uint64_t det[2]; uint32_t cap, olen; int32_t st; } one{0, {0, 0}, bs, 0, 0};
         uint8_t* d_one = w + a_one;
@@ -126,14 +127,28 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
         if (detail) { detail->inner = one.st; detail->expected = one.det[0]; detail->actual = one.det[1]; }
         return -LZ4FLEX_FE_DECOMPRESSION;
     }
+    bool open_end = false;
+    if (first_empty < n) {
+        // A block of no bytes ends the reader's read_to_end with the content in front of it (frame/decompress.rs:344-349,392-407: no
+        // EndMark is reached, so neither the content size nor anything behind that block is looked at): the index is of the blocks in
+        // front of it and the frame ends behind it.
+        uint64_t pay = 0;
+        uint32_t word = 0;
+        TRY_HIP(hipMemcpyAsync(&total, d_content + first_empty, 8, hipMemcpyDeviceToHost, s));
+        TRY_HIP(hipMemcpyAsync(&pay, d_pay + first_empty, 8, hipMemcpyDeviceToHost, s));
+        TRY_HIP(hipMemcpyAsync(&word, d_word + first_empty, 4, hipMemcpyDeviceToHost, s));
+        TRY_HIP(hipStreamSynchronize(s));
+        n = first_empty; walk_st = 0u; open_end = true;
+        end = pay + (word & 0x7FFFFFFFu) + tail;
+    }
     if (walk_st == 1u) return -LZ4FLEX_FE_IO;
     if (walk_st == 2u) return -LZ4FLEX_FE_BLOCK_TOO_BIG;
     if (walk_st != 0u) return -LZ4FLEX_E_UNSUPPORTED;
-    if (fi.has_content_size && fi.content_size != total) {                          // :313-320
+    if (!open_end && fi.has_content_size && fi.content_size != total) {             // :313-320
         if (detail) { detail->expected = fi.content_size; detail->actual = total; }
         return -LZ4FLEX_FE_CONTENT_LENGTH;
     }
-    const uint64_t frame_bytes = end + (fi.content_checksum ? 4u : 0u);
+    const uint64_t frame_bytes = end + (fi.content_checksum && !open_end ? 4u : 0u);
     if (frame_bytes > frame_len) return -LZ4FLEX_FE_IO;                             // (the content checksum's bytes: :321-326)
     // ---- the index's own copy
     Layout o{64};

@@ -20,21 +20,27 @@ using lz4flex_range::RangeRec;
 __global__ void __launch_bounds__(256) frame_index_prep_kernel(const uint32_t* __restrict__ word, uint32_t n, uint32_t* __restrict__ scan_len,
                                                                uint32_t* __restrict__ first_bad) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0u) *first_bad = 0xFFFFFFFFu;
+    if (b == 0u) { first_bad[0] = 0xFFFFFFFFu; first_bad[1] = 0xFFFFFFFFu; }
     if (b >= n) return;
     const uint32_t w = word[b];
     scan_len[b] = (w & 0x80000000u) ? 0u : w;
 }
 
-// size[b] = the block's decoded bytes: a stored block's length, a compressed block's scanned size; *first_bad = the first compressed
-// block that does not scan or decodes to more than the frame's block size (its size counts as 0)
+// size[b] = the block's decoded bytes: a stored block's length, a compressed block's scanned size; first_bad[0] = the first compressed
+// block that does not scan or decodes to more than the frame's block size (its size counts as 0), first_bad[1] = the first sound block
+// of no bytes at all (there a reader's read_to_end ends, src/frame/decompress.rs:344-349)
 __global__ void __launch_bounds__(256) frame_index_sizes_kernel(const uint32_t* __restrict__ word, const int32_t* __restrict__ scan_st, uint32_t n,
                                                                 uint32_t block_size, uint64_t* __restrict__ size, uint32_t* __restrict__ first_bad) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n) return;
     const uint32_t w = word[b];
-    if (w & 0x80000000u) { size[b] = w & 0x7FFFFFFFu; return; }
+    if (w & 0x80000000u) {
+        size[b] = w & 0x7FFFFFFFu;
+        if ((w & 0x7FFFFFFFu) == 0u) atomicMin(first_bad + 1, b);
+        return;
+    }
     if (scan_st[b] != 0 || size[b] > block_size) { size[b] = 0ull; atomicMin(first_bad, b); }
+    else if (size[b] == 0ull) atomicMin(first_bad + 1, b);
 }
 
 hipError_t launch_frame_index_prep(const uint32_t* word, uint32_t n, uint32_t* scan_len, uint32_t* first_bad, hipStream_t s) {
