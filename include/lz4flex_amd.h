@@ -92,7 +92,8 @@ const char *lz4flex_build_id(void);
  * lz4flex_frame_read_ranges with the settings "frame_range_pass_bytes" and "frame_range_checksums" (no workspace in the context beyond
  * the scratch the *_many calls already grow: an index owns its tables), then partial decode against dictionaries
  * lz4flex_decompress_batch_partial_shared_dict / lz4flex_decompress_batch_partial_dict_set / lz4flex_decompress_partial_into_with_dict (no
- * new setting, no workspace) -- a caller detects them by the symbol. */
+ * new setting, no workspace) -- a caller detects them by the symbol -- then "compress_mode" 2 (high) with the setting "compress_depth" (no
+ * new symbol, no workspace beyond the encoder's: a caller detects the mode by lz4flex_set_tuning(ctx, "compress_mode", 2) == 0). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -194,7 +195,9 @@ int64_t lz4flex_decompress_size_prepended_with_dict(const uint8_t *in, size_t in
  * reach into them: with h >= 32 768 every position sees between 32 and 64 KiB of the stream behind it (a smaller h is not
  * used), all blocks of the batch still encode side by side, and the block can only be decoded behind those bytes (a Linked
  * frame, LZ4FLEX_MEM_CHAINED, or lz4flex_decompress_batch_ex with them as out_pos prefix / dictionary).  compress_mode exact
- * ignores the bits: the reference's bytes for dependent blocks come from lz4flex_compress_chains. */
+ * ignores the bits: the reference's bytes for dependent blocks come from lz4flex_compress_chains.  compress_mode high ignores them
+ * too: a raw lz4flex_compress_batch block is encoded as an independent block, which is valid behind any history (the frame layer
+ * writes its Linked frames with the throughput encoder in that mode). */
 #define LZ4FLEX_BLOCK_HISTORY(h) ((uint32_t)(h) << 8)
 
 /* Compress n independent blocks.  Block i reads in_base[in_off[i] .. +in_len[i]] and writes at
@@ -601,7 +604,51 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
  *   block are its history) -- a dependency-carrying Linked frame that any decoder returns to the input, with a ratio below the
  *   reference's and still one launch per batch of blocks; in mode 1 it holds the reference's bytes (one dependency chain,
  *   milliseconds per block).
- *   Environment: LZ4FLEX_COMPRESS_MODE=exact|fast.
+ *   2 = high (lz4_compress_high.hip): a deep search for SMALLER blocks, for data that is written once and read many times -- the
+ *   decoders cost the same whatever encoder wrote a block.  Every position looks at up to "compress_depth" earlier positions instead of
+ *   one, and the parse is lazy by one step.  The bytes are a function of the block and of "compress_depth" ALONE: never of the batch a
+ *   block travels in, the device, "compress_subwindows", "compress_deterministic", "compress_sliding_window" or the memory kind.
+ *   Where it applies -- every place an independent block without a dictionary is encoded: lz4flex_compress_batch (flag bits 0 and 1
+ *   are ignored as in mode 0, and so are the LZ4FLEX_BLOCK_HISTORY bits: see there), the scalar lz4flex_compress_into,
+ *   lz4flex_compress_prepend_size and lz4flex_compress_into_with_table (the table is ignored as in mode 0),
+ *   lz4flex_compress_batch_packed (its payloads are lz4flex_compress_batch's), and Independent frames through lz4flex_frame_encoder_*,
+ *   lz4flex_frame_compress, lz4flex_frame_compress_many and the sharded entry (store-raw rule and checksums unchanged).
+ *   Everything else gives MODE 0's bytes under mode 2, decided on the host per call: lz4flex_compress_batch_ex with dict_base,
+ *   lz4flex_compress_batch_shared_dict, lz4flex_compress_batch_dict_set, Linked frames; the scalar *_with_dict calls stay exact and
+ *   lz4flex_compress_chains is what it is in every mode.  The OUTPUT_TOO_SMALL rule (out_cap below get_maximum_output_size: status,
+ *   out_len 0, nothing written), LZ4FLEX_MEM_BIG_BLOCKS, the host staging and "MEM_DEVICE calls are asynchronous and allocate nothing"
+ *   hold as in mode 0; the kernel's scratch is the context's encoder workspace (not grown), ordered across streams like mode 1's
+ *   chain records.
+ *   The definition (tests/sim/high_encoder_model.c is the model; the kernel equals it byte for byte).  Positions below 65 536 form
+ *   chunk 0 = [0, 65 536) with base 0; a later position p lies in the chunk [p & ~32767, + 32 768) with base = chunk start - 32 768.
+ *   Every position p <= n - 12 has the hash (load32(p) * 2654435761u) >> 17; its candidates are the earlier positions q >= base(p)
+ *   with the same hash, nearest first, at most "compress_depth" of them (a collision counts).  A candidate matches if its first 4
+ *   bytes are equal; its length is counted up to min(chunk end, n - 5) - p; best[p] is the longest match of at least 4 bytes, the
+ *   nearest of equal ones.  Parse, from p = 0: best[p].len < 4, or p + 1 in the same chunk with best[p + 1].len > best[p].len: a
+ *   literal; otherwise the sequence (literals since the anchor, offset, len) and p += len; the trailing literals close the block.
+ *   Sizes in bytes, model == kernel (fast / exact: modes 0 / 1; HCn: liblz4 1.9.3 LZ4_compress_HC at level n; profiles/r16_high_mode.txt):
+ *     input                      n     fast    exact  depth 1  depth 4 depth 16 depth 64      HC3      HC9
+ *     compression_34k        34308    19373    19888    18537    16926    16335    16125    16255    15894
+ *     compression_65k        64723    36493    37150    34053    31186    29926    29549    29849    29086
+ *     compression_66k_JSON   66675    15216    15268    15574    13257    12843    12390    12542    12213
+ *     JSON tile              65536    14955    15033    15320    13035    12629    12181    12339    12029
+ *     log, 64 KiB            65536    19850    19908    19302    17957    17154    16780    17057    16409
+ *     log, 4 KiB              4096     1595     1575     1568     1501     1481     1473     1479     1474
+ *     log, 1 MiB           1048576   308925   309864   296949   274912   259570   252256   255599   239996
+ *     JSON x 4, 200 000     200000    44689    44837    45452    38370    37055    35495    35346    33361
+ *     zeros                 100000      407      404      409      409      409      409      403      403
+ *   Depth 16 is 6 % to 35 % below min(fast, exact) on every compressible item and within 2.4 % of HC level 3; random bytes are the
+ *   same 70 276 in every column; runs of one byte are a few bytes above mode 0 (a chunk end splits the run).
+ *   Time: MI355X, device-resident batches, ms per lz4flex_compress_batch call, one session (tools/high_bench.py), as mode 0 / mode 1 /
+ *   mode 2 at depth 4, 16, 64 (liblz4 HC level 3 / 9 on 16 host threads over the same blocks): 16 384 x 64 KiB JSON tiles 3.1 / 18.3
+ *   / 68 / 124 / 284 (HC 234 / 764), ratio 0.230 / 0.232 / 0.200 / 0.193 / 0.186 (HC 0.189 / 0.183); 65 536 x 4 KiB log records 6.3
+ *   / 5.8 / 30 / 45 / 59 (HC 663 / 820), ratio 0.391 / 0.393 / 0.370 / 0.361 / 0.360 (HC 0.362 / 0.360); 256 x 4 MiB log blocks 4.5
+ *   / 284 / 114 / 240 / 649 (HC 357 / 1 481), ratio 0.294 / 0.295 / 0.262 / 0.247 / 0.240 (HC 0.243 / 0.228) -- depth 16 costs 40 x
+ *   mode 0 on the tiles and is 1.9 x ahead of 16 CPU threads at HC level 3 there, 15 x on the records, 1.5 x on the 4 MiB blocks (a
+ *   block's chunks are serial in one workgroup); every block was decoded by the oracle's decoder
+ *   Environment: LZ4FLEX_COMPRESS_MODE=exact|fast|high (or 1|0|2).
+ * "compress_depth" ("compress_mode" 2 alone reads it): the candidates examined per position, 1 ... 256, default 16.  Encode time
+ *   grows with it, the blocks shrink (table above); the decoders do not care.
  * "compress_sliding_window" (throughput encoder): how far the 64 KiB windows of a block LONGER than 64 KiB advance.  2 (default
  *   since round 5) = by 48 KiB, so every window start has 16 ... 64 KiB of the block behind it -- the reference's window slides
  *   continuously (src/block/compress.rs:403-405); 4 MiB log blocks: ratio 0.2940 (the reference: 0.2947) for a third more indexing;

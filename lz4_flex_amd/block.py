@@ -78,9 +78,17 @@ def _buf(b):
 
 def set_compress_mode(mode, ctx=None):
     """Encoder of this thread's default context (or of `ctx`): "fast" = throughput encoder (own parse: a valid LZ4 block
-    that lz4_flex decodes to the input; default), "exact" = lz4_flex's own bytes (src/block/compress.rs:318-489)."""
-    v = {"fast": 0, "exact": 1}[mode]
+    that lz4_flex decodes to the input; default), "exact" = lz4_flex's own bytes (src/block/compress.rs:318-489), "high" = a deep
+    search for smaller blocks (set_compress_depth candidates per position; independent blocks without a dictionary -- dictionary calls
+    and Linked frames get "fast"'s bytes)."""
+    v = {"fast": 0, "exact": 1, "high": 2}[mode]
     _check(L.load().lz4flex_set_tuning(ctx, b"compress_mode", v), "lz4flex_set_tuning(compress_mode)")
+
+
+def set_compress_depth(depth, ctx=None):
+    """"compress_depth" of this thread's default context (or of `ctx`): the candidates compress mode "high" examines per position,
+    1 .. 256 (default 16).  The other modes do not read it."""
+    _check(L.load().lz4flex_set_tuning(ctx, b"compress_depth", int(depth)), "lz4flex_set_tuning(compress_depth)")
 
 
 def get_maximum_output_size(input_len):

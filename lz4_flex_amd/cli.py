@@ -4,12 +4,14 @@
     python -m lz4_flex_amd.cli [-d] [-o OUT]   (stdin -> stdout / OUT)
 Options as the reference's: --clean (delete the original), -f/--force (overwrite), -d/--decompress, -o/--out.
 Beyond the reference: --range OFF:LEN with a decompression writes just those bytes of the content (frame.FrameIndex.read: only the
-blocks the range touches are decoded; Independent frames; the content checksum is not verified).
+blocks the range touches are decoded; Independent frames; the content checksum is not verified); --high [--depth N] with a compression
+takes the deep-search encoder (block.set_compress_mode("high"), N candidates per position, default 16): smaller blocks, more encode time.
 """
 import argparse
 import os
 import sys
 
+from . import block
 from .frame import FrameDecoder, FrameEncoder, FrameIndex
 
 LZ_EXTENSION = ".lz4"
@@ -92,8 +94,20 @@ def main(argv=None):
     ap.add_argument("input_file", nargs="?", help="file to compress/decompress ('-' or absent: stdin)")
     ap.add_argument("-o", "--out", help="output file to write to. defaults to stdout")
     ap.add_argument("--range", metavar="OFF:LEN", help="decompression: write only bytes [OFF, OFF + LEN) of the content")
+    ap.add_argument("--high", action="store_true", help="compression: the deep-search encoder (smaller output, slower)")
+    ap.add_argument("--depth", type=int, metavar="N", help="with --high: candidates examined per position, 1 .. 256 (default 16)")
     o = ap.parse_args(argv)
     byte_range = _parse_range(o.range) if o.range else None
+    if o.depth is not None and not o.high:
+        raise SystemExit("--depth goes with --high")
+    if o.depth is not None and not 1 <= o.depth <= 256:
+        raise SystemExit("--depth wants 1 .. 256")
+    if o.high:
+        if o.decompress or (o.input_file and o.input_file.endswith(LZ_EXTENSION)):
+            raise SystemExit("--high goes with a compression")
+        block.set_compress_mode("high")
+        if o.depth is not None:
+            block.set_compress_depth(o.depth)
     if o.input_file and o.input_file != "-":
         if byte_range is not None and not o.input_file.endswith(LZ_EXTENSION):
             raise SystemExit("--range goes with a decompression")

@@ -357,8 +357,17 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
     hipError_t le;
     int rc;
     CompressArgs a = a_;
-    if (shared) c->shared_counted = c->comp_mode == 0;
-    if (c->comp_mode == 0) {
+    // "compress_mode" 2 (high) encodes independent blocks without a dictionary; a call with dictionaries takes the throughput encoder
+    const int mode = c->comp_mode == 2 ? ((a.dict_len || shared || set) ? 0 : 2) : c->comp_mode;
+    if (shared) c->shared_counted = mode == 0;
+    if (mode == 2) {
+        // its scratch is the (otherwise idle) throughput encoder's workspace, ordered across streams like that encoder's own launches;
+        // a workgroup holds most of a CU's LDS, so one per CU (wave_wgs is two per CU) and no more than the workspace has slices for
+        if ((rc = wave_ws_acquire(c, s))) return rc;
+        le = launch_compress_high(a, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2, (uint32_t)c->comp_depth, s);
+        const hipError_t re = c->wave.release(s);
+        if (le == hipSuccess) le = re;
+    } else if (mode == 0) {
         if ((rc = wave_ws_acquire(c, s))) return rc;
         if (set) HIP_TRY(hipMemsetAsync(set->counter, 0, 4, s));      // ("debug_dict_set_items" speaks of this call)
         CompressArgs aw = a;
@@ -497,7 +506,7 @@ static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
     if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
     if (b.set) {
         const DictSetArgs ds = set_args_of(c, b);
-        c->set_counted = c->comp_mode == 0 ? b.set : nullptr;
+        c->set_counted = c->comp_mode != 1 ? b.set : nullptr;       // ("compress_mode" 2: a set takes the throughput encoder)
         return launch_compress_any(c, a, b.big, b.stream, nullptr, &ds, b.set->mem);
     }
     SharedDictArgs sh{};
@@ -567,7 +576,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     if (!c) return -LZ4FLEX_E_NOMEM;
     c->device = device;
     c->packed_tile = (int)PACKED_SCAN_TILE;
-    if (const char* e = getenv("LZ4FLEX_COMPRESS_MODE")) c->comp_mode = (!strcmp(e, "exact") || !strcmp(e, "1")) ? 1 : 0;
+    if (const char* e = getenv("LZ4FLEX_COMPRESS_MODE")) c->comp_mode = (!strcmp(e, "exact") || !strcmp(e, "1")) ? 1 : (!strcmp(e, "high") || !strcmp(e, "2")) ? 2 : 0;
     if (const char* e = getenv("LZ4FLEX_SLIDING_WINDOW")) {      // "0", "1" or "2", nothing else ("off" used to read as 0 silently: ADVICE r4)
         if (!strcmp(e, "0") || !strcmp(e, "1") || !strcmp(e, "2")) c->comp_sliding = e[0] - '0';
         else { g_last_error = "LZ4FLEX_SLIDING_WINDOW must be 0, 1 or 2"; delete c; return -LZ4FLEX_E_INVALID_ARG; }
@@ -670,7 +679,8 @@ const Setting SETTINGS[] = {
          return v == 16;                                        // the other widths exist in variant builds only (-DLZ4FLEX_ALL_VARIANTS)
 #endif
      }, false},
-    {"compress_mode", &lz4flex_ctx::comp_mode, is_flag, false},
+    {"compress_mode", &lz4flex_ctx::comp_mode, up_to_2, false},
+    {"compress_depth", &lz4flex_ctx::comp_depth, [](int v) { return v >= 1 && v <= 256; }, false},      // "compress_mode" 2: candidates per position
     {"compress_subwindows", &lz4flex_ctx::comp_sub, [](int v) { return v >= 0 && v <= 4; }, false},
     {"compress_deterministic", &lz4flex_ctx::comp_det, is_flag, false},
     {"decompress_level_chains", &lz4flex_ctx::dec_level_chains, is_count, false},
@@ -1924,7 +1934,8 @@ int64_t lz4flex_compress_into_with_table(const uint8_t* in, size_t in_len, uint8
     lz4flex_ctx* dc = nullptr;
     int rc = default_ctx(&dc);
     if (rc) return rc;
-    t->ctx->comp_mode = dc->comp_mode;                         // the thread's encoder choice (throughput / reference-exact)
+    t->ctx->comp_mode = dc->comp_mode;                         // the thread's encoder choice (throughput / reference-exact / high)
+    t->ctx->comp_depth = dc->comp_depth;
     t->ctx->comp_variant = dc->comp_variant;
     const uint32_t len = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull);
     // Large: HashTable4K, cleared, stream offset 0 == the frame encoder's first block (LZ4FLEX_BLOCK_FRAME_FIRST);

@@ -171,7 +171,7 @@ struct lz4flex_frame_encoder {
             std::fill(tbl_state.begin(), tbl_state.end(), 0u);
         }
         if (fi.block_mode == 1 && tbl_state.empty()) tbl_state.assign(4096, 0u);
-        linked_fast = fi.block_mode == 1 && lz4flex_get_tuning(nullptr, "compress_mode") == 0;   // decided once per frame
+        linked_fast = fi.block_mode == 1 && lz4flex_get_tuning(nullptr, "compress_mode") != 1;   // decided once per frame
         frame_start = proc_pos;
         return 0;
     }
@@ -217,8 +217,12 @@ struct lz4flex_frame_encoder {
             flags[i] = LZ4FLEX_BLOCK_HISTORY(std::min<uint64_t>(have, FAST_HISTORY));
             left -= len;
         }
+        // (compress_mode high encodes independent blocks only: a Linked frame's blocks are the throughput encoder's)
+        const bool high = lz4flex_get_tuning(nullptr, "compress_mode") == 2;
+        if (high) (void)lz4flex_set_tuning(nullptr, "compress_mode", 0);
         int rc = lz4flex_compress_batch(nullptr, lstage.data(), in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk, dst.data(),
                                         out_off.data(), out_cap.data(), out_len.data(), status.data(), LZ4FLEX_MEM_HOST, nullptr);
+        if (high) (void)lz4flex_set_tuning(nullptr, "compress_mode", 2);
         if (rc) return rc;
         for (size_t i = 0; i < nblk; i++) {
             if (status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;

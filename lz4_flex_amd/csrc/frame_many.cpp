@@ -172,10 +172,16 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
             TRY_RC(lz4flex_compress_chains(c, in, D.dev<lz4flex_chain_block>(a_cb), nb, D.dev<uint32_t>(a_first), D.dev<uint32_t>(a_count), nf, comp,
                                            D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st),
                                            nullptr, LZ4FLEX_MEM_DEVICE, s));
-        else
-            TRY_RC(lz4flex_compress_batch(c, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), D.dev<uint32_t>(a_flags), nb, comp,
-                                          D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st),
-                                          LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
+        else {
+            // (compress_mode high encodes independent blocks only: Linked frames' blocks are the throughput encoder's)
+            const int mode = c->comp_mode;
+            if (linked && mode == 2) c->comp_mode = 0;
+            const int rc = lz4flex_compress_batch(c, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), D.dev<uint32_t>(a_flags), nb, comp,
+                                                  D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len),
+                                                  D.dev<int32_t>(a_comp_st), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s);
+            c->comp_mode = mode;
+            TRY_RC(rc);
+        }
     }
     if (csum && nf) TRY_RC(lz4flex_xxh32_batch_device(in, D.dev<uint64_t>(a_soff), D.dev<uint32_t>(a_slen), nf, 0, D.dev<uint32_t>(a_csum), s));   // frame/compress.rs:319-321
     TRY_HIP(launch_frame_many_assemble(D.dev<ManyStream>(a_ms), nf, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), (const uint8_t*)comp,

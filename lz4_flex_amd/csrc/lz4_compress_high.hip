@@ -1,0 +1,337 @@
+// lz4_compress_high.hip -- compress_mode 2 ("high"): a deep-search encoder for independent blocks without a dictionary.
+//
+// The bytes are DEFINED by the scalar model tests/sim/high_encoder_model.c (chunks, candidates, best[], the one-step lazy parse: see its
+// head comment and include/lz4flex_amd.h, "compress_mode"); this kernel computes the same function of (block, depth) in parallel.
+//
+// Persistent workgroups of 1 024 lanes; workgroup w takes the blocks w, w + G, w + 2 G, ... and a block's chunks one after the other.  No
+// workgroup ever waits for another one.  Per chunk (a window of at most 64 KiB: 32 KiB of history + the chunk; chunk 0: the chunk alone):
+//   1  stage     the window into LDS as aligned dwords (every later read of it is a dword pair / triple and a shift)
+//   2  sort      the window's positions, stably, by their 15-bit hash: three counting passes of 5 bits, 512 segments with private
+//                counter columns in LDS, the arrays in the workgroup's slice of the workspace (L2).  Behind it the candidates of a position
+//                are its LEFT NEIGHBOURS in the sorted array, nearest first -- no chains to chase.
+//   3  match     a lane per sorted index: up to `depth` left neighbours, 8 bytes per compare step; best[] (length, offset) to the workspace
+//   4  orbit     the parse is the orbit of the chunk's first position under next(p) (p + 1 for a literal, p + len for a match): a lane
+//                per tile of 64 positions computes every entry's exit (backwards, one pass), one lane hops from tile to tile, then a
+//                lane per entered tile counts and lists its matches (the window's LDS is free by then)
+//   5  sizes     a lane per sequence, a prefix sum
+//   6  emit      a lane per sequence; literal runs of 1 KiB or more are copied by the whole workgroup
+// Every step is a loop over items strided by the lanes, between workgroup barriers; no wavefront-level operation is used.
+#include "lz4_device.h"
+#include <algorithm>
+
+namespace lz4flex_dev {
+namespace high {
+
+constexpr uint32_t THREADS = 1024u;
+constexpr uint32_t CHUNK0 = 65536u, CHUNK = 32768u;      // the model's LZ4H_CHUNK0 / LZ4H_CHUNK
+constexpr uint32_t HASH_BITS = 15u;
+constexpr uint32_t SEGS = 512u, DIGIT_BITS = 5u, DIGITS = 1u << DIGIT_BITS;      // the sort: 3 passes of 5 bits
+constexpr uint32_t TILE = 64u;
+constexpr uint32_t MAX_SEQS = CHUNK0 / 4u;               // a match is 4 bytes or more
+constexpr uint32_t LONG_LIT = 1024u, MAX_LONG = CHUNK0 / LONG_LIT + 1u;
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+
+// LDS.  [0, L_BIG_END) is, one after the other: the window + the sort's counters | the exits (u16 per position) | the sequence lists
+constexpr uint32_t WIN_BYTES = CHUNK0 + 32u;             // the window from the aligned dword in front of it, and a triple's slack
+constexpr uint32_t L_CNT = WIN_BYTES;                    // u32[DIGITS * SEGS]
+constexpr uint32_t L_BIG_END = L_CNT + 4u * DIGITS * SEGS;
+constexpr uint32_t L_SEQPOS = 0u, L_SEQOFF = 4u * MAX_SEQS;
+constexpr uint32_t L_ENTRY = L_BIG_END;                  // u32[CHUNK0 / TILE]: where the orbit enters a tile
+constexpr uint32_t L_TCNT = L_ENTRY + 4u * (CHUNK0 / TILE);
+constexpr uint32_t L_TMP = L_TCNT + 4u * (CHUNK0 / TILE);      // u32[THREADS]: block_scan
+constexpr uint32_t L_MISC = L_TMP + 4u * THREADS;        // [0] the number of long literal runs, [1 ..] their sequences
+constexpr uint32_t LDS_BYTES = L_MISC + 4u * (1u + MAX_LONG + 2u);
+static_assert(2u * CHUNK0 <= L_BIG_END && 8u * MAX_SEQS <= L_BIG_END, "the exits and the sequence lists reuse the window's LDS");
+static_assert(LDS_BYTES <= 160u * 1024u, "one workgroup per CU");
+
+// the workgroup's slice of the workspace
+constexpr size_t W_SORT_A = 0, W_SORT_B = 2u * CHUNK0, W_LEN = 4u * CHUNK0, W_OFF = W_LEN + 2u * (CHUNK0 + 64u);
+constexpr size_t WS_PER_WG = (W_OFF + 2u * CHUNK0 + 255u) & ~(size_t)255u;
+
+__device__ __forceinline__ uint32_t umin(uint32_t x, uint32_t y) { return x < y ? x : y; }
+__device__ __forceinline__ uint32_t hash_of(uint32_t v) { return (v * 2654435761u) >> (32u - HASH_BITS); }
+// 4 / 8 / 1 bytes at byte offset x of the dword array w (LDS)
+__device__ __forceinline__ uint32_t ld32(const uint32_t* w, uint32_t x) {
+    const uint32_t i = x >> 2;
+    return (uint32_t)((((uint64_t)w[i + 1u] << 32) | w[i]) >> ((x & 3u) * 8u));
+}
+__device__ __forceinline__ uint64_t ld64(const uint32_t* w, uint32_t x) {
+    const uint32_t i = x >> 2, sh = (x & 3u) * 8u;
+    const uint64_t lo = ((uint64_t)w[i + 1u] << 32) | w[i];
+    return sh ? (lo >> sh) | ((uint64_t)w[i + 2u] << (64u - sh)) : lo;
+}
+__device__ __forceinline__ uint32_t ld8(const uint32_t* w, uint32_t x) { return (w[x >> 2] >> ((x & 3u) * 8u)) & 255u; }
+// the length bytes behind a token nibble of 15
+__device__ __forceinline__ uint32_t ext_bytes(uint32_t v) { return v >= 15u ? (v - 15u) / 255u + 1u : 0u; }
+__device__ __forceinline__ uint8_t* put_ext(uint8_t* o, uint32_t v) {
+    if (v >= 15u) {
+        v -= 15u;
+        for (; v >= 255u; v -= 255u) *o++ = 255u;
+        *o++ = (uint8_t)v;
+    }
+    return o;
+}
+
+// a[0, n) becomes its exclusive prefix sums, in place; returns the total.  tmp: blockDim.x words.  Called by every lane.
+__device__ uint32_t block_scan(uint32_t* a, uint32_t n, uint32_t* tmp) {
+    const uint32_t T = blockDim.x, t = threadIdx.x;
+    const uint32_t per = (n + T - 1u) / T;
+    const uint32_t i0 = umin(t * per, n), i1 = umin(i0 + per, n);
+    uint32_t sum = 0u;
+    for (uint32_t i = i0; i < i1; ++i) sum += a[i];
+    tmp[t] = sum;
+    __syncthreads();
+    for (uint32_t d = 1u; d < T; d <<= 1) {
+        const uint32_t v = t >= d ? tmp[t - d] : 0u;
+        __syncthreads();
+        tmp[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = tmp[t] - sum;
+    const uint32_t total = tmp[T - 1u];
+    for (uint32_t i = i0; i < i1; ++i) { const uint32_t v = a[i]; a[i] = run; run += v; }
+    __syncthreads();
+    return total;
+}
+
+// one stable counting pass of the sort: the elements src[0, np) (null: 0, 1, 2, ...) go to dst ordered by bits [shift, shift + 5) of
+// their hash.  Segment s = [s * seglen, + seglen) has the counter column cnt[d * SEGS + s]: nobody else touches it.
+__device__ void sort_pass(const uint32_t* win, uint32_t mis, const uint16_t* src, uint16_t* dst, uint32_t np, uint32_t shift, uint32_t* cnt,
+                          uint32_t* tmp) {
+    const uint32_t seglen = (np + SEGS - 1u) / SEGS;
+    for (uint32_t i = threadIdx.x; i < DIGITS * SEGS; i += blockDim.x) cnt[i] = 0u;
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < SEGS; s += blockDim.x) {
+        const uint32_t i0 = umin(s * seglen, np), i1 = umin(i0 + seglen, np);
+        for (uint32_t i = i0; i < i1; ++i) {
+            const uint32_t e = src ? src[i] : i;
+            cnt[((hash_of(ld32(win, mis + e)) >> shift) & (DIGITS - 1u)) * SEGS + s] += 1u;
+        }
+    }
+    __syncthreads();
+    block_scan(cnt, DIGITS * SEGS, tmp);
+    for (uint32_t s = threadIdx.x; s < SEGS; s += blockDim.x) {
+        const uint32_t i0 = umin(s * seglen, np), i1 = umin(i0 + seglen, np);
+        for (uint32_t i = i0; i < i1; ++i) {
+            const uint32_t e = src ? src[i] : i;
+            const uint32_t c = ((hash_of(ld32(win, mis + e)) >> shift) & (DIGITS - 1u)) * SEGS + s;
+            dst[cnt[c]] = (uint16_t)e;
+            cnt[c] += 1u;
+        }
+    }
+    __syncthreads();
+}
+
+// is position j of the chunk a literal?  L = its best length, next = best length of j + 1 (csize: the chunk's size)
+__device__ __forceinline__ bool is_literal(uint32_t j, uint32_t L, uint32_t next, uint32_t csize) {
+    return L < 4u || (j + 1u < csize && next > L);
+}
+
+__device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, uint8_t* ws, uint32_t depth) {
+    const uint32_t T = blockDim.x, t = threadIdx.x;
+    const uint32_t n = a.in_len[b], cap = a.out_cap[b];
+    const uint8_t* in = a.in_base + a.in_off[b];
+    uint8_t* out = a.out_base + a.out_off[b];
+    if ((uint64_t)cap < 20ull + (uint64_t)n * 110ull / 100ull) {      // get_maximum_output_size: the rule of every encoder here
+        if (t == 0u) { a.out_len[b] = 0u; a.status[b] = LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+        return;
+    }
+    uint32_t* win = (uint32_t*)lds;
+    uint32_t* cnt = (uint32_t*)(lds + L_CNT);
+    uint16_t* exitd = (uint16_t*)lds;
+    uint32_t* seqpos = (uint32_t*)(lds + L_SEQPOS);
+    uint32_t* seqoff = (uint32_t*)(lds + L_SEQOFF);
+    uint32_t* entry = (uint32_t*)(lds + L_ENTRY);
+    uint32_t* tcnt = (uint32_t*)(lds + L_TCNT);
+    uint32_t* tmp = (uint32_t*)(lds + L_TMP);
+    uint32_t* misc = (uint32_t*)(lds + L_MISC);
+    uint16_t* sort_a = (uint16_t*)(ws + W_SORT_A);
+    uint16_t* sort_b = (uint16_t*)(ws + W_SORT_B);
+    uint16_t* blen = (uint16_t*)(ws + W_LEN);
+    uint16_t* boff = (uint16_t*)(ws + W_OFF);
+
+    uint32_t anchor = 0u, opos = 0u;              // the same in every lane
+    if (n >= 12u) for (uint32_t cs = 0u; cs + 12u <= n;) {
+        const uint32_t ce = cs == 0u ? CHUNK0 : (cs + CHUNK < cs ? 0xFFFFFFFFu : cs + CHUNK);
+        const uint32_t base = cs == 0u ? 0u : cs - CHUNK, hist = cs - base;
+        const uint32_t end = umin(ce, n), mend = umin(ce, n - 5u);
+        const uint32_t wlen = end - base;                         // the window's bytes
+        const uint32_t np = umin(end, n - 11u) - base;            // ... and its positions with a hash (> hist)
+        const uint32_t cn = end - cs, csize = ce - cs;            // the chunk's positions that exist; its size
+        const uint32_t nh = np - hist;                            // ... and those with a hash
+
+        // 1  stage (the aligned dwords that hold the window: the first and the last one may reach 3 bytes past it, inside their dword)
+        const uint32_t mis = (uint32_t)((uintptr_t)(in + base) & 3u);
+        {
+            const uint32_t* src = (const uint32_t*)(in + base - mis);
+            const uint32_t ndw = (mis + wlen + 3u) >> 2;
+            for (uint32_t i = t; i < ndw; i += T) win[i] = src[i];
+        }
+        if (t == 0u) misc[0] = 0u;
+        __syncthreads();
+
+        // 2  sort
+        sort_pass(win, mis, nullptr, sort_a, np, 0u, cnt, tmp);
+        sort_pass(win, mis, sort_a, sort_b, np, DIGIT_BITS, cnt, tmp);
+        sort_pass(win, mis, sort_b, sort_a, np, 2u * DIGIT_BITS, cnt, tmp);
+
+        // 3  match
+        for (uint32_t j = nh + t; j <= cn; j += T) blen[j] = 0u;  // positions without a hash, and the one behind the block's end
+        for (uint32_t i = t; i < np; i += T) {
+            const uint32_t e = sort_a[i];
+            if (e < hist) continue;
+            const uint32_t lim = mend - (base + e), x = mis + e;
+            const uint32_t v = ld32(win, x), h = hash_of(v);
+            uint32_t bl = 0u, bo = 0u;
+            for (uint32_t k = 1u; k <= depth && k <= i; ++k) {
+                const uint32_t q = sort_a[i - k], y = mis + q;
+                const uint32_t c = ld32(win, y);
+                if (c != v) {
+                    if (hash_of(c) != h) break;                   // the bucket's end
+                    continue;                                     // a collision: one of the `depth`
+                }
+                uint32_t l = 4u;
+                bool open = true;
+                while (l + 8u <= lim) {
+                    const uint64_t d = ld64(win, x + l) ^ ld64(win, y + l);
+                    if (d) { l += (uint32_t)__builtin_ctzll(d) >> 3; open = false; break; }
+                    l += 8u;
+                }
+                if (open) while (l < lim && ld8(win, x + l) == ld8(win, y + l)) ++l;
+                if (l > lim) l = lim;                             // (the chunk ends less than 4 bytes behind the position)
+                if (l >= 4u && l > bl) { bl = l; bo = e - q; }
+                if (bl == lim) break;                             // nothing is longer, and an equal one does not replace it
+            }
+            blen[e - hist] = (uint16_t)bl;
+            boff[e - hist] = (uint16_t)bo;
+        }
+        __syncthreads();
+
+        // 4  orbit.  exitd[j]: where the walk that enters its tile at j leaves it, counted from the tile's end
+        const uint32_t ntile = (cn + TILE - 1u) / TILE;
+        for (uint32_t tl = t; tl < ntile; tl += T) {
+            const uint32_t ts = tl * TILE, te = umin(ts + TILE, cn);
+            entry[tl] = NONE;
+            uint32_t next = te < csize ? blen[te] : 0u;
+            for (uint32_t j = te; j-- > ts;) {
+                const uint32_t L = blen[j];
+                const uint32_t nx = is_literal(j, L, next, csize) ? j + 1u : j + L;
+                exitd[j] = (uint16_t)(nx >= te ? nx - te : exitd[nx]);
+                next = L;
+            }
+        }
+        __syncthreads();
+        if (t == 0u) {
+            for (uint32_t e = 0u; e < cn;) {
+                const uint32_t tl = e / TILE;
+                entry[tl] = e;
+                e = umin(tl * TILE + TILE, cn) + exitd[e];
+            }
+        }
+        __syncthreads();
+        for (uint32_t tl = t; tl < ntile; tl += T) {
+            const uint32_t te = umin(tl * TILE + TILE, cn);
+            uint32_t c = 0u;
+            if (entry[tl] != NONE)
+                for (uint32_t j = entry[tl]; j < te;) {
+                    const uint32_t L = blen[j];
+                    if (is_literal(j, L, blen[j + 1u], csize)) ++j; else { ++c; j += L; }
+                }
+            tcnt[tl] = c;
+        }
+        __syncthreads();
+        const uint32_t nseq = block_scan(tcnt, ntile, tmp);       // (the exits are dead from here on: the sequence lists take their LDS)
+        for (uint32_t tl = t; tl < ntile; tl += T) {
+            const uint32_t te = umin(tl * TILE + TILE, cn);
+            uint32_t c = tcnt[tl];
+            if (entry[tl] != NONE)
+                for (uint32_t j = entry[tl]; j < te;) {
+                    const uint32_t L = blen[j];
+                    if (is_literal(j, L, blen[j + 1u], csize)) ++j; else { seqpos[c++] = j; j += L; }
+                }
+        }
+        __syncthreads();
+
+        // 5  sizes: sequence k = the literals since the match before it (the first one: since `anchor`) + its match
+        for (uint32_t k = t; k < nseq; k += T) {
+            const uint32_t j = seqpos[k], L = blen[j];
+            const uint32_t from = k ? cs + seqpos[k - 1u] + blen[seqpos[k - 1u]] : anchor;
+            const uint32_t lit = cs + j - from;
+            seqoff[k] = 1u + ext_bytes(lit) + lit + 2u + ext_bytes(L - 4u);
+        }
+        __syncthreads();
+        const uint32_t bytes = block_scan(seqoff, nseq, tmp);
+        if ((uint64_t)opos + bytes > cap) {       // (cannot happen under the rule above: no store is ever made outside the slot)
+            if (t == 0u) { a.out_len[b] = 0u; a.status[b] = LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+            return;
+        }
+
+        // 6  emit
+        for (uint32_t k = t; k < nseq; k += T) {
+            const uint32_t j = seqpos[k], L = blen[j], off = boff[j];
+            const uint32_t from = k ? cs + seqpos[k - 1u] + blen[seqpos[k - 1u]] : anchor;
+            const uint32_t lit = cs + j - from, ml = L - 4u;
+            uint8_t* o = out + opos + seqoff[k];
+            *o++ = (uint8_t)((umin(lit, 15u) << 4) | umin(ml, 15u));
+            o = put_ext(o, lit);
+            if (lit < LONG_LIT) for (uint32_t i = 0u; i < lit; ++i) o[i] = in[from + i];
+            else misc[1u + atomicAdd(&misc[0], 1u)] = k;
+            o += lit;
+            *o++ = (uint8_t)off; *o++ = (uint8_t)(off >> 8);
+            put_ext(o, ml);
+        }
+        __syncthreads();
+        const uint32_t nlong = misc[0];
+        for (uint32_t i = 0u; i < nlong; ++i) {
+            const uint32_t k = misc[1u + i];
+            const uint32_t from = k ? cs + seqpos[k - 1u] + blen[seqpos[k - 1u]] : anchor;
+            const uint32_t lit = cs + seqpos[k] - from;
+            uint8_t* o = out + opos + seqoff[k] + 1u + ext_bytes(lit);
+            for (uint32_t x = t; x < lit; x += T) o[x] = in[from + x];
+        }
+        if (nseq) anchor = cs + seqpos[nseq - 1u] + blen[seqpos[nseq - 1u]];
+        opos += bytes;
+        __syncthreads();                          // (the next chunk's window overwrites the lists)
+        if (ce >= n) break;
+        cs = ce;
+    }
+
+    // the block's last literals
+    const uint32_t lit = n - anchor;
+    const uint64_t total = (uint64_t)opos + 1u + ext_bytes(lit) + lit;
+    if (total > cap) {
+        if (t == 0u) { a.out_len[b] = 0u; a.status[b] = LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL; }
+        return;
+    }
+    uint8_t* o = out + opos + 1u + ext_bytes(lit);
+    if (t == 0u) {
+        out[opos] = (uint8_t)(umin(lit, 15u) << 4);
+        put_ext(out + opos + 1u, lit);
+        a.out_len[b] = (uint32_t)total;
+        a.status[b] = 0;
+    }
+    for (uint32_t x = t; x < lit; x += T) o[x] = in[anchor + x];
+}
+
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_kernel(const CompressArgs a, uint8_t* ws, uint32_t depth) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        compress_block(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth);
+        __syncthreads();
+    }
+}
+
+}  // namespace high
+
+size_t compress_high_workspace_bytes(int n_workgroups) { return (size_t)n_workgroups * high::WS_PER_WG; }
+
+hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    const size_t fit = workspace_bytes / high::WS_PER_WG;
+    const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
+    if (g == 0u || depth == 0u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(high::lz4_compress_high_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
+    return hipGetLastError();
+}
+
+}  // namespace lz4flex_dev

@@ -201,6 +201,11 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
                                 bool carry_wait = true,                // tests: false = a window that has to wait for its predecessor gives up at once
                                 const SharedDictArgs* shared_dict = nullptr,    // nullable: the batch's one dictionary (the _shared_ kernels)
                                 const DictSetArgs* dict_set = nullptr);         // nullable (not with shared_dict): a dictionary per block out of a set (the _set_ kernels)
+// compress_mode 2 ("high", lz4_compress_high.hip): independent blocks without a dictionary, a.flags / slide / sub / dictionaries are not
+// read; the bytes are tests/sim/high_encoder_model.c's for (block, depth).  Persistent workgroups, one per block at a time, each with a
+// slice of `workspace` (compress_high_workspace_bytes(g) bytes for g of them): at most max_workgroups and as many as workspace_bytes holds
+size_t compress_high_workspace_bytes(int n_workgroups);
+hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, hipStream_t s);
 // a dictionary set's digests: bytes per dictionary, and the kernel that fills table[0 .. k)'s (a workgroup of one wavefront per
 // dictionary; cand_scratch: compress_wave_digest_scratch_bytes() bytes per dictionary, dead behind the launch)
 size_t compress_wave_digest_bytes();
