@@ -615,7 +615,8 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
  *   lz4flex_frame_compress, lz4flex_frame_compress_many and the sharded entry (store-raw rule and checksums unchanged).
  *   Everything else gives MODE 0's bytes under mode 2, decided on the host per call: lz4flex_compress_batch_ex with dict_base,
  *   lz4flex_compress_batch_shared_dict, lz4flex_compress_batch_dict_set, Linked frames; the scalar *_with_dict calls stay exact and
- *   lz4flex_compress_chains is what it is in every mode.  The OUTPUT_TOO_SMALL rule (out_cap below get_maximum_output_size: status,
+ *   lz4flex_compress_chains is what it is in every mode.  ("compress_high_dict" 1 hands the dictionary calls to mode 2 as well: see
+ *   there.)  The OUTPUT_TOO_SMALL rule (out_cap below get_maximum_output_size: status,
  *   out_len 0, nothing written), LZ4FLEX_MEM_BIG_BLOCKS, the host staging and "MEM_DEVICE calls are asynchronous and allocate nothing"
  *   hold as in mode 0; the kernel's scratch is the context's encoder workspace (not grown), ordered across streams like mode 1's
  *   chain records.
@@ -649,6 +650,45 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
  *   Environment: LZ4FLEX_COMPRESS_MODE=exact|fast|high (or 1|0|2).
  * "compress_depth" ("compress_mode" 2 alone reads it): the candidates examined per position, 1 ... 256, default 16.  Encode time
  *   grows with it, the blocks shrink (table above); the decoders do not care.
+ * "compress_high_dict" ("compress_mode" 2 alone reads it): 0 (default) = calls with dictionaries give mode 0's bytes, as above.  1 =
+ *   they take the high encoder's dictionary form: lz4flex_compress_batch_ex with dict_base, lz4flex_compress_batch_shared_dict,
+ *   lz4flex_compress_batch_dict_set, lz4flex_compress_into_with_dict and lz4flex_compress_prepend_size_with_dict.  The blocks are
+ *   ordinary dictionary blocks: lz4flex_decompress_batch_shared_dict, _dict_set, _ex and their partial forms read them as they read
+ *   any other.  Kept: the OUTPUT_TOO_SMALL rule; _ex: a block with a dictionary and flags[i] != 0 gets LZ4FLEX_E_INVALID_ARG, out_len
+ *   0, nothing written; sets: id 0xFFFFFFFF = no dictionary, an id >= K is refused in the same way; a block without a dictionary, or
+ *   with one of less than 4 bytes, gets mode 2's plain bytes (mixed batches included); MEM_HOST stages as in mode 0, MEM_DEVICE calls
+ *   allocate nothing; dictionaries may overlap each other and the inputs; Linked frames keep mode 0's bytes.  The shared entry
+ *   prepares its one dictionary once per call ("compress_high_digest" below).
+ *   The definition (tests/sim/high_dict_model.c; the kernel equals it byte for byte -- a function of block, dictionary and
+ *   "compress_depth" alone).  H = dict_len < 4 ? 0 : min(dict_len, 32 768); H == 0: the plain definition above.  Otherwise the stream
+ *   is S = [the dictionary's last H bytes | block] and EVERY chunk is 32 KiB: chunk c = block positions [c * 32 768, + 32 768), its
+ *   base 32 768 positions earlier in S and not below S's first byte -- chunk 0 sees the dictionary's tail and itself, every later
+ *   chunk the block alone; an offset is at most 65 535 (65 532 in practice).  Hashed positions: the block's p <= n - 12 and the
+ *   tail's q with q + 4 <= H (the three positions whose 4 bytes straddle the dictionary's end are never candidates: the dictionary's
+ *   order is a function of the dictionary alone).  Candidates, best[] and the parse are the plain definition's, lengths counted over
+ *   S (a match may start in the dictionary and run on into the block) up to min(chunk end, n - 5) - p; n < 12: literals only.
+ *   Sizes at depth 16 (no dictionary -> with it; oracle = the reference's compress_with_dict): a 4 KiB JSON record against a 32 KiB
+ *   dictionary 1 145 -> 604 (oracle 780), a 4 KiB text record 2 787 -> 1 799 (oracle 2 409); over 24 (block, dictionary) cases of
+ *   the two fixtures 65 502 -> 54 767 (oracle 67 576).
+ *   Measured: MI355X, device-resident batches against one 32 KiB dictionary, one session with the legs alternating
+ *   (tools/high_dict_bench.py, profiles/r17_high_dict.txt), ms per call and ratio; every block decoded by the oracle's decoder.
+ *   65 536 x 4 KiB log records: mode 0 with the dictionary 5.6 ms, 0.298; mode 1 with it 57.6, 0.315; mode 2 with it through
+ *   lz4flex_compress_batch_shared_dict at depth 4 / 16 / 64: 29.5 / 52.8 / 132 ms, 0.2705 / 0.2554 / 0.2499 (with
+ *   "compress_high_digest" 0 and through lz4flex_compress_batch_ex: 86 / 136 / 252 ms, the same bytes); mode 2 at depth 16 without a
+ *   dictionary 44.8 ms, 0.361.  16 384 x 64 KiB JSON tiles: mode 0 with the dictionary 5.0 ms, 0.200; mode 1 with it 67.4, 0.163;
+ *   mode 2 with it 607 / 1 178 / 1 985 ms, 0.1547 / 0.1478 / 0.1414 (digest 0 and _ex: 643 / 1 239 / 2 040); mode 2 at depth 16
+ *   without a dictionary 124 ms, 0.193.  The tiles' dictionary is a piece of the file the tiles repeat: most positions of chunk 0
+ *   find a match that runs to the chunk's end, and counting it (up to 32 KiB per position) is what the ten-fold time goes to -- the
+ *   plain form's known cost on runs, met on real data; the digest saves only the sort there.  (Read off the data's shape and the
+ *   digest's small gain, not profiled.)
+ *   Environment: LZ4FLEX_HIGH_DICT=1.
+ * "compress_high_digest" (the dictionary form of "compress_mode" 2, lz4flex_compress_batch_shared_dict alone): 1 (default) = a
+ *   kernel in front of the encoder sorts the dictionary tail's hashed positions ONCE per call (128 KiB in the encoder's workspace:
+ *   u16 sorted[H - 3] and the bucket bounds u16 start[32 769]); a block then sorts its own positions only, and a position's
+ *   candidates are its left neighbours of equal hash in its own order, then the digest's bucket from its end downwards -- nearest
+ *   first across both, the same count and the same stop: the same bytes.  0 = every block sorts the tail's positions with its own,
+ *   which is what lz4flex_compress_batch_ex and lz4flex_compress_batch_dict_set always do (a digest per dictionary of a set is not
+ *   kept yet).
  * "compress_sliding_window" (throughput encoder): how far the 64 KiB windows of a block LONGER than 64 KiB advance.  2 (default
  *   since round 5) = by 48 KiB, so every window start has 16 ... 64 KiB of the block behind it -- the reference's window slides
  *   continuously (src/block/compress.rs:403-405); 4 MiB log blocks: ratio 0.2940 (the reference: 0.2947) for a third more indexing;

@@ -79,8 +79,8 @@ def _buf(b):
 def set_compress_mode(mode, ctx=None):
     """Encoder of this thread's default context (or of `ctx`): "fast" = throughput encoder (own parse: a valid LZ4 block
     that lz4_flex decodes to the input; default), "exact" = lz4_flex's own bytes (src/block/compress.rs:318-489), "high" = a deep
-    search for smaller blocks (set_compress_depth candidates per position; independent blocks without a dictionary -- dictionary calls
-    and Linked frames get "fast"'s bytes)."""
+    search for smaller blocks (set_compress_depth candidates per position; independent blocks -- Linked frames get "fast"'s bytes, and so do
+    dictionary calls unless set_compress_high_dict(True))."""
     v = {"fast": 0, "exact": 1, "high": 2}[mode]
     _check(L.load().lz4flex_set_tuning(ctx, b"compress_mode", v), "lz4flex_set_tuning(compress_mode)")
 
@@ -89,6 +89,14 @@ def set_compress_depth(depth, ctx=None):
     """"compress_depth" of this thread's default context (or of `ctx`): the candidates compress mode "high" examines per position,
     1 .. 256 (default 16).  The other modes do not read it."""
     _check(L.load().lz4flex_set_tuning(ctx, b"compress_depth", int(depth)), "lz4flex_set_tuning(compress_depth)")
+
+
+def set_compress_high_dict(on, ctx=None):
+    """"compress_high_dict" of this thread's default context (or of `ctx`): with compress mode "high", True makes every call that
+    takes dictionaries (compress_with_dict, compress_prepend_size_with_dict, compress_batch_with_dict, _with_shared_dict,
+    _with_dict_set) search the dictionary's last 32 KiB as deeply as the block itself -- smaller blocks that every dictionary decoder
+    here reads; False (default): those calls give "fast"'s bytes.  The other modes do not read it."""
+    _check(L.load().lz4flex_set_tuning(ctx, b"compress_high_dict", 1 if on else 0), "lz4flex_set_tuning(compress_high_dict)")
 
 
 def get_maximum_output_size(input_len):
@@ -508,7 +516,8 @@ def compress_batch_with_dict(in_buf, in_off, in_len, dict_buf, dict_off, dict_le
     """lz4flex_compress_batch_ex over host buffers: block i = in_buf[in_off[i] : + in_len[i]] compressed against the dictionary
     dict_buf[dict_off[i] : + dict_len[i]] (dict_len[i] == 0: none) into out_buf[out_off[i] : + out_cap[i]] -- block::compress_into_with_dict
     as a batch.  compress_mode exact gives the reference's bytes; fast (the default) the throughput encoder's, which use the dictionary's
-    last 32 KiB.  Returns (out_len[u32], status[i32])."""
+    last 32 KiB; high gives fast's unless set_compress_high_dict(True), then a deep search of the block and of the dictionary's last
+    32 KiB (the same holds for the shared-dictionary and the dictionary-set forms below).  Returns (out_len[u32], status[i32])."""
     ext, _keep = _host_dict_ext(L.CompressExt, dict_buf, dict_off, dict_len)
     return _host_call("lz4flex_compress_batch_ex", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), before_n=[_u32(flags)],
                       tail=[C.byref(ext)])

@@ -357,13 +357,23 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
     hipError_t le;
     int rc;
     CompressArgs a = a_;
-    // "compress_mode" 2 (high) encodes independent blocks without a dictionary; a call with dictionaries takes the throughput encoder
-    const int mode = c->comp_mode == 2 ? ((a.dict_len || shared || set) ? 0 : 2) : c->comp_mode;
+    // "compress_mode" 2 (high) encodes independent blocks; a call with dictionaries takes its dictionary form with "compress_high_dict" 1
+    // and the throughput encoder otherwise
+    const bool with_dict = a.dict_len || shared || set;
+    const int mode = c->comp_mode == 2 ? ((with_dict && !c->comp_high_dict) ? 0 : 2) : c->comp_mode;
     if (shared) c->shared_counted = mode == 0;
+    if (set && mode == 2) c->set_counted = nullptr;              // (the set's counter is the throughput encoder's)
     if (mode == 2) {
         // its scratch is the (otherwise idle) throughput encoder's workspace, ordered across streams like that encoder's own launches;
         // a workgroup holds most of a CU's LDS, so one per CU (wave_wgs is two per CU) and no more than the workspace has slices for
         if ((rc = wave_ws_acquire(c, s))) return rc;
+        if (with_dict) {
+            HighDictArgs d{};
+            if (shared) { d.shared = shared->dict; d.shared_len = shared->len; }
+            if (set) { d.has_set = 1u; d.set = *set; }
+            le = launch_compress_high_dict(a, d, c->comp_high_digest != 0, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2,
+                                           (uint32_t)c->comp_depth, s);
+        } else
         le = launch_compress_high(a, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2, (uint32_t)c->comp_depth, s);
         const hipError_t re = c->wave.release(s);
         if (le == hipSuccess) le = re;
@@ -506,7 +516,7 @@ static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
     if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
     if (b.set) {
         const DictSetArgs ds = set_args_of(c, b);
-        c->set_counted = c->comp_mode != 1 ? b.set : nullptr;       // ("compress_mode" 2: a set takes the throughput encoder)
+        c->set_counted = c->comp_mode != 1 ? b.set : nullptr;       // ("compress_mode" 2: a set takes the throughput encoder unless "compress_high_dict" is 1)
         return launch_compress_any(c, a, b.big, b.stream, nullptr, &ds, b.set->mem);
     }
     SharedDictArgs sh{};
@@ -577,6 +587,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     c->device = device;
     c->packed_tile = (int)PACKED_SCAN_TILE;
     if (const char* e = getenv("LZ4FLEX_COMPRESS_MODE")) c->comp_mode = (!strcmp(e, "exact") || !strcmp(e, "1")) ? 1 : (!strcmp(e, "high") || !strcmp(e, "2")) ? 2 : 0;
+    if (const char* e = getenv("LZ4FLEX_HIGH_DICT")) c->comp_high_dict = !strcmp(e, "1") ? 1 : 0;
     if (const char* e = getenv("LZ4FLEX_SLIDING_WINDOW")) {      // "0", "1" or "2", nothing else ("off" used to read as 0 silently: ADVICE r4)
         if (!strcmp(e, "0") || !strcmp(e, "1") || !strcmp(e, "2")) c->comp_sliding = e[0] - '0';
         else { g_last_error = "LZ4FLEX_SLIDING_WINDOW must be 0, 1 or 2"; delete c; return -LZ4FLEX_E_INVALID_ARG; }
@@ -681,6 +692,8 @@ const Setting SETTINGS[] = {
      }, false},
     {"compress_mode", &lz4flex_ctx::comp_mode, up_to_2, false},
     {"compress_depth", &lz4flex_ctx::comp_depth, [](int v) { return v >= 1 && v <= 256; }, false},      // "compress_mode" 2: candidates per position
+    {"compress_high_dict", &lz4flex_ctx::comp_high_dict, is_flag, false},          // "compress_mode" 2: dictionary calls take its dictionary form
+    {"compress_high_digest", &lz4flex_ctx::comp_high_digest, is_flag, false},      // ... and a shared dictionary is sorted once per call
     {"compress_subwindows", &lz4flex_ctx::comp_sub, [](int v) { return v >= 0 && v <= 4; }, false},
     {"compress_deterministic", &lz4flex_ctx::comp_det, is_flag, false},
     {"decompress_level_chains", &lz4flex_ctx::dec_level_chains, is_count, false},
@@ -1767,6 +1780,23 @@ int64_t lz4flex_compress_into_with_dict(const uint8_t* in, size_t in_len, uint8_
                                         const uint8_t* dict, size_t dict_len) {
     if (in_len > 0x7FFFFFFFull) return -LZ4FLEX_E_INVALID_ARG;
     if (out_cap < lz4flex_get_maximum_output_size(in_len)) return -LZ4FLEX_E_OUTPUT_TOO_SMALL;   // compress.rs:338-340
+    {
+        // "compress_mode" 2 with "compress_high_dict" 1: the high encoder's dictionary form, as a batch of one (it reads the
+        // dictionary's last 32 KiB); every other setting: the reference's bytes below
+        lz4flex_ctx* c = nullptr;
+        if (default_ctx(&c) == 0 && c->comp_mode == 2 && c->comp_high_dict) {
+            if (dict_len > 65536u) { dict += dict_len - 65536u; dict_len = 65536u; }
+            const uint32_t len = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull), dlen = (uint32_t)dict_len;
+            uint32_t olen = 0;
+            int32_t st = 0;
+            BatchCall b = batch_of(true, in ? in : &EMPTY, &OFF0, &len, 1, out, &OFF0, &cap, &olen, &st);
+            b.has_ext = true; b.dict_base = dict ? dict : &EMPTY; b.dict_off = &OFF0; b.dict_len = &dlen;
+            const int rc = run_host_batch(c, b);
+            if (rc) return rc;
+            if (st) return -(int64_t)st;
+            return (int64_t)olen;
+        }
+    }
     // compress_into_sink_with_dict, compress.rs:554-568: table kind from the UNtruncated dictionary length,
     // then init_dict keeps the last 64 KiB (:572-574)
     const bool h4 = dict_len + in_len < 65535u;

@@ -1,7 +1,11 @@
-// lz4_compress_high.hip -- compress_mode 2 ("high"): a deep-search encoder for independent blocks without a dictionary.
+// lz4_compress_high.hip -- compress_mode 2 ("high"): a deep-search encoder for independent blocks, without a dictionary (the plain form)
+// and against one ("compress_high_dict" 1: the dictionary form, the same code as a template on the dictionary).
 //
 // The bytes are DEFINED by the scalar model tests/sim/high_encoder_model.c (chunks, candidates, best[], the one-step lazy parse: see its
-// head comment and include/lz4flex_amd.h, "compress_mode"); this kernel computes the same function of (block, depth) in parallel.
+// head comment and include/lz4flex_amd.h, "compress_mode"); this kernel computes the same function of (block, depth) in parallel.  The
+// dictionary form's definition is tests/sim/high_dict_model.c: the dictionary's last H <= 32 KiB bytes are chunk 0's history, every chunk
+// is 32 KiB, and nothing else changes -- here the differences are confined to chunk 0 (its geometry, stage_dict, the sort's enumeration
+// and, with the shared dictionary's digest, where a position's candidates come from).
 //
 // Persistent workgroups of 1 024 lanes; workgroup w takes the blocks w, w + G, w + 2 G, ... and a block's chunks one after the other.  No
 // workgroup ever waits for another one.  Per chunk (a window of at most 64 KiB: 32 KiB of history + the chunk; chunk 0: the chunk alone):
@@ -94,17 +98,28 @@ __device__ uint32_t block_scan(uint32_t* a, uint32_t n, uint32_t* tmp) {
     return total;
 }
 
+// a sort's enumeration of positions: the plain form's is 0, 1, 2, ... (and the argument is empty); the dictionary form's is first,
+// first + 1, ... with the three positions from gap_at on left out
+template <bool DICT> struct Positions { uint32_t first = 0u, gap_at = NONE; };
+template <> struct Positions<false> {};
+__device__ __forceinline__ uint32_t nth(Positions<false>, uint32_t i) { return i; }
+__device__ __forceinline__ uint32_t nth(Positions<true> ps, uint32_t i) {
+    const uint32_t e = i + ps.first;
+    return e >= ps.gap_at ? e + 3u : e;
+}
+
 // one stable counting pass of the sort: the elements src[0, np) (null: 0, 1, 2, ...) go to dst ordered by bits [shift, shift + 5) of
 // their hash.  Segment s = [s * seglen, + seglen) has the counter column cnt[d * SEGS + s]: nobody else touches it.
+template <bool DICT>
 __device__ void sort_pass(const uint32_t* win, uint32_t mis, const uint16_t* src, uint16_t* dst, uint32_t np, uint32_t shift, uint32_t* cnt,
-                          uint32_t* tmp) {
+                          uint32_t* tmp, Positions<DICT> ps = {}) {
     const uint32_t seglen = (np + SEGS - 1u) / SEGS;
     for (uint32_t i = threadIdx.x; i < DIGITS * SEGS; i += blockDim.x) cnt[i] = 0u;
     __syncthreads();
     for (uint32_t s = threadIdx.x; s < SEGS; s += blockDim.x) {
         const uint32_t i0 = umin(s * seglen, np), i1 = umin(i0 + seglen, np);
         for (uint32_t i = i0; i < i1; ++i) {
-            const uint32_t e = src ? src[i] : i;
+            const uint32_t e = src ? src[i] : nth(ps, i);
             cnt[((hash_of(ld32(win, mis + e)) >> shift) & (DIGITS - 1u)) * SEGS + s] += 1u;
         }
     }
@@ -113,7 +128,7 @@ __device__ void sort_pass(const uint32_t* win, uint32_t mis, const uint16_t* src
     for (uint32_t s = threadIdx.x; s < SEGS; s += blockDim.x) {
         const uint32_t i0 = umin(s * seglen, np), i1 = umin(i0 + seglen, np);
         for (uint32_t i = i0; i < i1; ++i) {
-            const uint32_t e = src ? src[i] : i;
+            const uint32_t e = src ? src[i] : nth(ps, i);
             const uint32_t c = ((hash_of(ld32(win, mis + e)) >> shift) & (DIGITS - 1u)) * SEGS + s;
             dst[cnt[c]] = (uint16_t)e;
             cnt[c] += 1u;
@@ -127,8 +142,42 @@ __device__ __forceinline__ bool is_literal(uint32_t j, uint32_t L, uint32_t next
     return L < 4u || (j + 1u < csize && next > L);
 }
 
-__device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, uint8_t* ws, uint32_t depth) {
+// The dictionary form's stage of chunk 0: the window is the dictionary's last H bytes (they end at dend, any alignment) and the block's
+// first blk bytes; window byte w is LDS byte mis + w with mis = (in - H) & 3, so the block's bytes arrive as aligned dwords.  A dword of
+// the tail is two aligned dwords of the dictionary and a funnel shift; nothing is read outside the aligned dwords that hold the tail and
+// the block, and the dword with bytes of both has one writer.
+__device__ void stage_dict(uint32_t* win, uint32_t mis, const uint8_t* dend, uint32_t H, const uint8_t* in, uint32_t blk) {
+    const uintptr_t d0 = (uintptr_t)dend - H;
+    const uintptr_t lo_ok = d0 & ~(uintptr_t)3, hi_ok = ((uintptr_t)dend - 1u) & ~(uintptr_t)3;
+    const uintptr_t a0 = d0 - mis;                               // where LDS byte 0 comes from
+    const uint32_t sh = (uint32_t)(a0 & 3u);
+    const uint32_t r = (mis + H) & 3u, jd = (mis + H) >> 2;      // the tail's bytes in the junction dword (0: none); the block's first dword
+    const uint32_t* bsrc = (const uint32_t*)(in - r);
+    const uint32_t ndw = (mis + H + blk + 3u) >> 2;
+    for (uint32_t i = threadIdx.x; i < ndw; i += blockDim.x) {
+        uint32_t v = 0u;
+        if (4u * i < mis + H) {
+            const uintptr_t p = (a0 & ~(uintptr_t)3) + 4u * (uintptr_t)i;
+            const uint32_t lo = (p >= lo_ok && p <= hi_ok) ? *(const uint32_t*)p : 0u;
+            const uint32_t hi = (sh != 0u && p + 4u >= lo_ok && p + 4u <= hi_ok) ? *(const uint32_t*)(p + 4u) : 0u;
+            v = __builtin_amdgcn_alignbyte(hi, lo, sh);
+        }
+        if (i >= jd) {
+            const uint32_t bv = bsrc[i - jd];
+            const uint32_t keep = (i == jd && r != 0u) ? (1u << (8u * r)) - 1u : 0u;
+            v = (v & keep) | (bv & ~keep);
+        }
+        win[i] = v;
+    }
+}
+
+// DICT: the block has the dictionary that ends at dend, its last H bytes are chunk 0's history (H == 0: none; the plain form's bytes).
+// dg_sorted / dg_start (nullable): the dictionary tail's digest (lz4_high_digest_kernel) -- chunk 0 sorts the block's positions only.
+template <bool DICT>
+__device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, uint8_t* ws, uint32_t depth, const uint8_t* dend = nullptr,
+                               uint32_t H_ = 0u, const uint16_t* dg_sorted = nullptr, const uint16_t* dg_start = nullptr) {
     const uint32_t T = blockDim.x, t = threadIdx.x;
+    const uint32_t H = DICT ? H_ : 0u;
     const uint32_t n = a.in_len[b], cap = a.out_cap[b];
     const uint8_t* in = a.in_base + a.in_off[b];
     uint8_t* out = a.out_base + a.out_off[b];
@@ -152,8 +201,11 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
 
     uint32_t anchor = 0u, opos = 0u;              // the same in every lane
     if (n >= 12u) for (uint32_t cs = 0u; cs + 12u <= n;) {
-        const uint32_t ce = cs == 0u ? CHUNK0 : (cs + CHUNK < cs ? 0xFFFFFFFFu : cs + CHUNK);
-        const uint32_t base = cs == 0u ? 0u : cs - CHUNK, hist = cs - base;
+        // (with a dictionary chunk 0 is [0, CHUNK) and its window starts H bytes in front of the block: base = -H, in u32 arithmetic)
+        const uint32_t ce = cs == 0u ? (H ? CHUNK : CHUNK0) : (cs + CHUNK < cs ? 0xFFFFFFFFu : cs + CHUNK);
+        const uint32_t base = cs == 0u ? 0u - H : cs - CHUNK, hist = cs - base;
+        const bool dchunk = DICT && cs == 0u && H != 0u;          // the window holds the dictionary's tail
+        const bool use_dg = dchunk && dg_sorted != nullptr;
         const uint32_t end = umin(ce, n), mend = umin(ce, n - 5u);
         const uint32_t wlen = end - base;                         // the window's bytes
         const uint32_t np = umin(end, n - 11u) - base;            // ... and its positions with a hash (> hist)
@@ -161,8 +213,9 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
         const uint32_t nh = np - hist;                            // ... and those with a hash
 
         // 1  stage (the aligned dwords that hold the window: the first and the last one may reach 3 bytes past it, inside their dword)
-        const uint32_t mis = (uint32_t)((uintptr_t)(in + base) & 3u);
-        {
+        const uint32_t mis = dchunk ? (uint32_t)(((uintptr_t)in - H) & 3u) : (uint32_t)((uintptr_t)(in + base) & 3u);
+        if (dchunk) stage_dict(win, mis, dend, H, in, end);
+        else {
             const uint32_t* src = (const uint32_t*)(in + base - mis);
             const uint32_t ndw = (mis + wlen + 3u) >> 2;
             for (uint32_t i = t; i < ndw; i += T) win[i] = src[i];
@@ -170,26 +223,52 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
         if (t == 0u) misc[0] = 0u;
         __syncthreads();
 
-        // 2  sort
-        sort_pass(win, mis, nullptr, sort_a, np, 0u, cnt, tmp);
-        sort_pass(win, mis, sort_a, sort_b, np, DIGIT_BITS, cnt, tmp);
-        sort_pass(win, mis, sort_b, sort_a, np, 2u * DIGIT_BITS, cnt, tmp);
+        // 2  sort.  With a dictionary: without the three positions whose 4 bytes straddle its end; with its digest: the block's alone
+        const uint32_t ns = use_dg ? nh : (dchunk ? np - 3u : np);
+        Positions<DICT> ps;
+        if constexpr (DICT) { ps.first = use_dg ? H : 0u; ps.gap_at = dchunk && !use_dg ? H - 3u : NONE; }
+        sort_pass<DICT>(win, mis, nullptr, sort_a, ns, 0u, cnt, tmp, ps);
+        sort_pass<DICT>(win, mis, sort_a, sort_b, ns, DIGIT_BITS, cnt, tmp);
+        sort_pass<DICT>(win, mis, sort_b, sort_a, ns, 2u * DIGIT_BITS, cnt, tmp);
 
         // 3  match
         for (uint32_t j = nh + t; j <= cn; j += T) blen[j] = 0u;  // positions without a hash, and the one behind the block's end
-        for (uint32_t i = t; i < np; i += T) {
+        for (uint32_t i = t; i < ns; i += T) {
             const uint32_t e = sort_a[i];
             if (e < hist) continue;
             const uint32_t lim = mend - (base + e), x = mis + e;
             const uint32_t v = ld32(win, x), h = hash_of(v);
             uint32_t bl = 0u, bo = 0u;
-            for (uint32_t k = 1u; k <= depth && k <= i; ++k) {
-                const uint32_t q = sort_a[i - k], y = mis + q;
-                const uint32_t c = ld32(win, y);
-                if (c != v) {
-                    if (hash_of(c) != h) break;                   // the bucket's end
-                    continue;                                     // a collision: one of the `depth`
+            // (with a digest: behind the position's own left neighbours of its hash, the digest's bucket from its end downwards --
+            // nearest first across both, the same `depth` and the same stop at the bucket's end)
+            uint32_t own = i, dg = 0u, dg0 = 0u;
+            bool in_own = true;
+            if (use_dg) { dg0 = dg_start[h]; dg = dg_start[h + 1u]; }
+            for (uint32_t k = 1u; k <= depth && (DICT || k <= i); ++k) {
+                uint32_t q, c;
+                if constexpr (!DICT) {
+                    q = sort_a[i - k];
+                    c = ld32(win, mis + q);
+                    if (c != v) {
+                        if (hash_of(c) != h) break;               // the bucket's end
+                        continue;                                 // a collision: one of the `depth`
+                    }
+                } else {
+                    bool have = false;
+                    if (in_own && own != 0u) {
+                        q = sort_a[--own];
+                        c = ld32(win, mis + q);
+                        have = c == v || hash_of(c) == h;
+                    }
+                    if (!have) {
+                        in_own = false;
+                        if (dg == dg0) break;                     // the bucket's end
+                        q = dg_sorted[--dg];
+                        c = ld32(win, mis + q);
+                    }
+                    if (c != v) continue;
                 }
+                const uint32_t y = mis + q;
                 uint32_t l = 4u;
                 bool open = true;
                 while (l + 8u <= lim) {
@@ -316,8 +395,69 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
 __global__ void __launch_bounds__(THREADS) lz4_compress_high_kernel(const CompressArgs a, uint8_t* ws, uint32_t depth) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
-        compress_block(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth);
+        compress_block<false>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth);
         __syncthreads();
+    }
+}
+
+// The dictionary form ("compress_high_dict" 1; the bytes: tests/sim/high_dict_model.c).  Block b's dictionary is the set's (d.set),
+// else the batch's one (d.shared), else a.dict_*; one of less than 4 bytes is none.  digest (nullable, with d.shared only): the slice
+// lz4_high_digest_kernel filled.
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_dict_kernel(const CompressArgs a, const HighDictArgs d, uint8_t* ws, const uint8_t* digest,
+                                                                         uint32_t depth) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        const uint8_t* dict = nullptr;
+        uint32_t dl = 0u;
+        bool ok = true;
+        if (d.has_set) ok = dict_set_find(d.set, b, dict, dl);
+        else if (d.shared) { dict = d.shared; dl = d.shared_len; }
+        else if (a.dict_len) {
+            dl = a.dict_len[b];
+            dict = a.dict_base + a.dict_off[b];
+            ok = dl == 0u || a.flags == nullptr || a.flags[b] == 0u;      // a dictionary and frame flags or history bits: refused
+        }
+        if (!ok) {
+            if (threadIdx.x == 0u) { a.out_len[b] = 0u; a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG; }
+            continue;
+        }
+        const uint32_t H = dl < 4u ? 0u : umin(dl, CHUNK);
+        compress_block<true>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth, dict + dl, H,
+                             digest ? (const uint16_t*)(digest + W_SORT_A) : nullptr, (const uint16_t*)(digest + W_SORT_B));
+        __syncthreads();
+    }
+}
+
+// The digest of one dictionary's tail: its hashed positions (q + 4 <= H) in the order the joint sort gives them, and the buckets' bounds.
+// One workgroup; `slice` is a workgroup's slice of the workspace: u16 sorted[H - 3] at W_SORT_A, u16 start[32 769] at W_SORT_B (the
+// positions with hash h are sorted[start[h] .. start[h + 1])).  len >= 4.
+__global__ void __launch_bounds__(THREADS) lz4_high_digest_kernel(const uint8_t* dict, uint32_t len, uint8_t* slice) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    const uint32_t T = blockDim.x, t = threadIdx.x;
+    uint32_t* win = (uint32_t*)lds;
+    uint32_t* cnt = (uint32_t*)(lds + L_CNT);
+    uint32_t* tmp = (uint32_t*)(lds + L_TMP);
+    uint16_t* sort_a = (uint16_t*)(slice + W_SORT_A);
+    uint16_t* sort_b = (uint16_t*)(slice + W_SORT_B);
+    const uint32_t H = umin(len, CHUNK), np = H - 3u;
+    const uint8_t* tail = dict + (len - H);
+    const uint32_t mis = (uint32_t)((uintptr_t)tail & 3u);
+    {
+        const uint32_t* src = (const uint32_t*)(tail - mis);
+        const uint32_t ndw = (mis + H + 3u) >> 2;
+        for (uint32_t i = t; i < ndw; i += T) win[i] = src[i];
+    }
+    __syncthreads();
+    sort_pass<false>(win, mis, nullptr, sort_a, np, 0u, cnt, tmp);
+    sort_pass<false>(win, mis, sort_a, sort_b, np, DIGIT_BITS, cnt, tmp);
+    sort_pass<false>(win, mis, sort_b, sort_a, np, 2u * DIGIT_BITS, cnt, tmp);
+    __threadfence_block();
+    __syncthreads();
+    uint16_t* start = sort_b;                     // (the second array is dead behind the last pass)
+    for (uint32_t i = t; i <= np; i += T) {
+        const uint32_t h0 = i ? hash_of(ld32(win, mis + sort_a[i - 1u])) + 1u : 0u;
+        const uint32_t h1 = i < np ? hash_of(ld32(win, mis + sort_a[i])) : 1u << HASH_BITS;
+        for (uint32_t h = h0; h <= h1; ++h) start[h] = (uint16_t)i;
     }
 }
 
@@ -331,6 +471,25 @@ hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t w
     const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
     if (g == 0u || depth == 0u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(high::lz4_compress_high_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
+    return hipGetLastError();
+}
+
+hipError_t launch_compress_high_dict(const CompressArgs& a, const HighDictArgs& d, bool use_digest, void* workspace, size_t workspace_bytes,
+                                     int max_workgroups, uint32_t depth, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    // the digest is a property of the batch's ONE dictionary; it takes the last slice of the workspace
+    const bool dg = use_digest && !d.has_set && d.shared != nullptr && d.shared_len >= 4u;
+    size_t fit = workspace_bytes / high::WS_PER_WG;
+    if (dg && fit) --fit;
+    const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
+    if (g == 0u || depth == 0u) return hipErrorInvalidValue;
+    uint8_t* digest = dg ? (uint8_t*)workspace + fit * high::WS_PER_WG : nullptr;
+    if (dg) {
+        hipLaunchKernelGGL(high::lz4_high_digest_kernel, dim3(1), dim3(high::THREADS), 0, s, d.shared, d.shared_len, digest);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(high::lz4_compress_high_dict_kernel, dim3(g), dim3(high::THREADS), 0, s, a, d, (uint8_t*)workspace, (const uint8_t*)digest, depth);
     return hipGetLastError();
 }
 

@@ -206,6 +206,19 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
 // slice of `workspace` (compress_high_workspace_bytes(g) bytes for g of them): at most max_workgroups and as many as workspace_bytes holds
 size_t compress_high_workspace_bytes(int n_workgroups);
 hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, hipStream_t s);
+// its dictionary form ("compress_high_dict" 1): the bytes are tests/sim/high_dict_model.c's for (block, dictionary, depth).  Block b's
+// dictionary is the set's (has_set), else the batch's one (shared, shared_len), else a.dict_* (with a.flags[b] != 0: refused like a
+// refused id -- status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written); a block without one, or with one of less than 4 bytes, gets
+// the plain form's bytes.  use_digest (the shared dictionary only): a kernel in front sorts the dictionary tail's positions once, into
+// the last slice of `workspace`, and every block sorts its own positions alone; else every block sorts the tail's with its own.
+struct HighDictArgs {
+    const uint8_t* shared;
+    uint32_t shared_len;
+    uint32_t has_set;
+    DictSetArgs set;
+};
+hipError_t launch_compress_high_dict(const CompressArgs& a, const HighDictArgs& d, bool use_digest, void* workspace, size_t workspace_bytes,
+                                     int max_workgroups, uint32_t depth, hipStream_t s);
 // a dictionary set's digests: bytes per dictionary, and the kernel that fills table[0 .. k)'s (a workgroup of one wavefront per
 // dictionary; cand_scratch: compress_wave_digest_scratch_bytes() bytes per dictionary, dead behind the launch)
 size_t compress_wave_digest_bytes();
