@@ -196,8 +196,9 @@ int64_t lz4flex_decompress_size_prepended_with_dict(const uint8_t *in, size_t in
  * used), all blocks of the batch still encode side by side, and the block can only be decoded behind those bytes (a Linked
  * frame, LZ4FLEX_MEM_CHAINED, or lz4flex_decompress_batch_ex with them as out_pos prefix / dictionary).  compress_mode exact
  * ignores the bits: the reference's bytes for dependent blocks come from lz4flex_compress_chains.  compress_mode high ignores them
- * too: a raw lz4flex_compress_batch block is encoded as an independent block, which is valid behind any history (the frame layer
- * writes its Linked frames with the throughput encoder in that mode). */
+ * too by default: a raw lz4flex_compress_batch block is encoded as an independent block, which is valid behind any history (the
+ * frame layer writes its Linked frames with the throughput encoder in that mode).  With "compress_high_linked" 1 it reads them: the
+ * last min(h, 32 768) bytes in front of the block are searched as deeply as the block itself (h < 4: none), see that setting. */
 #define LZ4FLEX_BLOCK_HISTORY(h) ((uint32_t)(h) << 8)
 
 /* Compress n independent blocks.  Block i reads in_base[in_off[i] .. +in_len[i]] and writes at
@@ -609,14 +610,16 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
  *   one, and the parse is lazy by one step.  The bytes are a function of the block and of "compress_depth" ALONE: never of the batch a
  *   block travels in, the device, "compress_subwindows", "compress_deterministic", "compress_sliding_window" or the memory kind.
  *   Where it applies -- every place an independent block without a dictionary is encoded: lz4flex_compress_batch (flag bits 0 and 1
- *   are ignored as in mode 0, and so are the LZ4FLEX_BLOCK_HISTORY bits: see there), the scalar lz4flex_compress_into,
+ *   are ignored as in mode 0, and so are the LZ4FLEX_BLOCK_HISTORY bits unless "compress_high_linked" is 1: see there), the scalar
+ *   lz4flex_compress_into,
  *   lz4flex_compress_prepend_size and lz4flex_compress_into_with_table (the table is ignored as in mode 0),
  *   lz4flex_compress_batch_packed (its payloads are lz4flex_compress_batch's), and Independent frames through lz4flex_frame_encoder_*,
  *   lz4flex_frame_compress, lz4flex_frame_compress_many and the sharded entry (store-raw rule and checksums unchanged).
  *   Everything else gives MODE 0's bytes under mode 2, decided on the host per call: lz4flex_compress_batch_ex with dict_base,
  *   lz4flex_compress_batch_shared_dict, lz4flex_compress_batch_dict_set, Linked frames; the scalar *_with_dict calls stay exact and
  *   lz4flex_compress_chains is what it is in every mode.  ("compress_high_dict" 1 hands the dictionary calls to mode 2 as well: see
- *   there.)  The OUTPUT_TOO_SMALL rule (out_cap below get_maximum_output_size: status,
+ *   there; "compress_high_linked" 1 does the same for Linked frames and the history bits.)  The OUTPUT_TOO_SMALL rule (out_cap below
+ *   get_maximum_output_size: status,
  *   out_len 0, nothing written), LZ4FLEX_MEM_BIG_BLOCKS, the host staging and "MEM_DEVICE calls are asynchronous and allocate nothing"
  *   hold as in mode 0; the kernel's scratch is the context's encoder workspace (not grown), ordered across streams like mode 1's
  *   chain records.
@@ -657,7 +660,7 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
  *   any other.  Kept: the OUTPUT_TOO_SMALL rule; _ex: a block with a dictionary and flags[i] != 0 gets LZ4FLEX_E_INVALID_ARG, out_len
  *   0, nothing written; sets: id 0xFFFFFFFF = no dictionary, an id >= K is refused in the same way; a block without a dictionary, or
  *   with one of less than 4 bytes, gets mode 2's plain bytes (mixed batches included); MEM_HOST stages as in mode 0, MEM_DEVICE calls
- *   allocate nothing; dictionaries may overlap each other and the inputs; Linked frames keep mode 0's bytes.  The shared entry
+ *   allocate nothing; dictionaries may overlap each other and the inputs; Linked frames keep mode 0's bytes ("compress_high_linked").  The shared entry
  *   prepares its one dictionary once per call ("compress_high_digest" below).
  *   The definition (tests/sim/high_dict_model.c; the kernel equals it byte for byte -- a function of block, dictionary and
  *   "compress_depth" alone).  H = dict_len < 4 ? 0 : min(dict_len, 32 768); H == 0: the plain definition above.  Otherwise the stream
@@ -682,6 +685,35 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
  *   plain form's known cost on runs, met on real data; the digest saves only the sort there.  (Read off the data's shape and the
  *   digest's small gain, not profiled.)
  *   Environment: LZ4FLEX_HIGH_DICT=1.
+ * "compress_high_linked" ("compress_mode" 2 alone reads it): 0 (default) = the LZ4FLEX_BLOCK_HISTORY bits are ignored and Linked
+ *   frames are written by the throughput encoder, as above.  1 = a block with h = flags[i] >> 8 bytes of its stream in front of it is
+ *   encoded by the high encoder's dictionary form with those bytes as its dictionary: block i gets exactly the bytes
+ *   tests/sim/high_dict_model.c gives (block, in_base[in_off[i] - h .. in_off[i]), "compress_depth") -- the bytes lz4flex_compress_batch_ex
+ *   gives the block under "compress_high_dict" 1 with the h bytes passed as its dictionary.  So: the last H = min(h, 32 768) bytes are
+ *   chunk 0's history and every chunk is 32 KiB; the three positions whose 4 bytes straddle the block's start are not hashed; h < 4
+ *   gives the plain definition's bytes, and so does a block of a history batch with h == 0 (flag bits 0 and 1 are ignored as ever;
+ *   blocks with and without history mix freely in one launch).  The bytes are a function of the block, the at most 32 KiB in front of
+ *   it and "compress_depth" alone -- never of the batch, the memory kind, the number of streams or how a stream was cut into write()
+ *   calls.  Where it applies: lz4flex_compress_batch with a flags array (one launch for all blocks: the history is input;
+ *   lz4flex_compress_batch_packed follows lz4flex_compress_batch, but carries no flag words and so no history), and Linked frames through lz4flex_frame_encoder_*, lz4flex_frame_compress and
+ *   lz4flex_frame_compress_many (one launch over all blocks of all streams; flags, the 32 KiB kept between write() calls, the
+ *   store-raw rule and the checksums are mode 0's).  Unchanged: lz4flex_compress_batch_ex (a block with a dictionary and flags[i] != 0
+ *   is still refused), "compress_mode" 0 and 1, Independent frames, lz4flex_compress_chains, the sharded entry (Linked frames do not
+ *   shard).  MEM_HOST stages the bytes in front of a block with it and refuses h > in_off[i], as in mode 0.  No read leaves the
+ *   aligned dwords that hold [in - H, in + n).  A history longer than 32 KiB is not used: the window is 64 KiB of LDS with 16-bit
+ *   positions.
+ *   Sizes at depth 16, payload bytes, independent -> linked (the model; the kernel equals it): 1 MiB of log in 64 KiB blocks 274 737
+ *   -> 259 660 (depth 4: 288 883 -> 275 002, depth 64: 268 474 -> 252 346; mode 0's Linked frame: about 0.29 of the input, 0.248
+ *   here); the text fixture in 16 KiB pieces 35 274 -> 30 192.
+ *   Measured: MI355X, device-resident, 1 GiB per shape, one session with the legs alternating (tools/high_linked_bench.py,
+ *   profiles/r18_high_linked.txt), every frame decoded by the oracle; ms per call and ratio as mode 0 Linked | mode 2 Independent at
+ *   depth 4 / 16 / 64 | mode 2 Linked at depth 4 / 16 / 64.  256 streams x 4 MiB of log in 64 KiB blocks through
+ *   lz4flex_frame_compress_many: 5.4, 0.2932 | 84 / 198 / 546, 0.2754 / 0.2620 / 0.2560 | 114 / 243 / 653, 0.2616 / 0.2468 / 0.2399 (a
+ *   64 KiB block with history is two 64 KiB windows instead of one); 4 096 streams x 256 KiB: 6.2, 0.2956 | 85 / 199 / 548 | 114 /
+ *   244 / 655, 0.2649 / 0.2505 / 0.2437; blocks of 4 MiB (one per stream): the same bytes and times with the setting on and off.  A
+ *   raw batch of 16 384 x 64 KiB JSON tiles, each behind 32 KiB of the tile in front: 4.7, 0.2199 | 68 / 123 / 283, 0.1999 / 0.1931 /
+ *   0.1857 | 113 / 211 / 472, 0.1878 / 0.1801 / 0.1715.
+ *   Environment: LZ4FLEX_HIGH_LINKED=1.
  * "compress_high_digest" (the dictionary form of "compress_mode" 2, lz4flex_compress_batch_shared_dict alone): 1 (default) = a
  *   kernel in front of the encoder sorts the dictionary tail's hashed positions ONCE per call (128 KiB in the encoder's workspace:
  *   u16 sorted[H - 3] and the bucket bounds u16 start[32 769]); a block then sorts its own positions only, and a position's

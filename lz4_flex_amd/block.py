@@ -79,8 +79,8 @@ def _buf(b):
 def set_compress_mode(mode, ctx=None):
     """Encoder of this thread's default context (or of `ctx`): "fast" = throughput encoder (own parse: a valid LZ4 block
     that lz4_flex decodes to the input; default), "exact" = lz4_flex's own bytes (src/block/compress.rs:318-489), "high" = a deep
-    search for smaller blocks (set_compress_depth candidates per position; independent blocks -- Linked frames get "fast"'s bytes, and so do
-    dictionary calls unless set_compress_high_dict(True))."""
+    search for smaller blocks (set_compress_depth candidates per position; independent blocks -- Linked frames get "fast"'s bytes unless
+    set_compress_high_linked(True), and so do dictionary calls unless set_compress_high_dict(True))."""
     v = {"fast": 0, "exact": 1, "high": 2}[mode]
     _check(L.load().lz4flex_set_tuning(ctx, b"compress_mode", v), "lz4flex_set_tuning(compress_mode)")
 
@@ -97,6 +97,14 @@ def set_compress_high_dict(on, ctx=None):
     _with_dict_set) search the dictionary's last 32 KiB as deeply as the block itself -- smaller blocks that every dictionary decoder
     here reads; False (default): those calls give "fast"'s bytes.  The other modes do not read it."""
     _check(L.load().lz4flex_set_tuning(ctx, b"compress_high_dict", 1 if on else 0), "lz4flex_set_tuning(compress_high_dict)")
+
+
+def set_compress_high_linked(on, ctx=None):
+    """"compress_high_linked" of this thread's default context (or of `ctx`): with compress mode "high", True makes a Linked frame's
+    blocks (and every batch block whose flag word carries LZ4FLEX_BLOCK_HISTORY bits) search the up to 32 KiB of their stream in
+    front of them as deeply as the block itself -- smaller frames that every LZ4 frame decoder reads; False (default): Linked frames
+    give "fast"'s bytes and the history bits are ignored.  The other modes do not read it."""
+    _check(L.load().lz4flex_set_tuning(ctx, b"compress_high_linked", 1 if on else 0), "lz4flex_set_tuning(compress_high_linked)")
 
 
 def get_maximum_output_size(input_len):

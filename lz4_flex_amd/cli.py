@@ -5,14 +5,16 @@
 Options as the reference's: --clean (delete the original), -f/--force (overwrite), -d/--decompress, -o/--out.
 Beyond the reference: --range OFF:LEN with a decompression writes just those bytes of the content (frame.FrameIndex.read: only the
 blocks the range touches are decoded; Independent frames; the content checksum is not verified); --high [--depth N] with a compression
-takes the deep-search encoder (block.set_compress_mode("high"), N candidates per position, default 16): smaller blocks, more encode time.
+takes the deep-search encoder (block.set_compress_mode("high"), N candidates per position, default 16): smaller blocks, more encode time;
+--linked with a compression writes a Linked frame (BlockMode.Linked: a block's matches reach into the blocks in front of it), and --high
+--linked searches that history as deeply as the block (block.set_compress_high_linked(True)).
 """
 import argparse
 import os
 import sys
 
 from . import block
-from .frame import FrameDecoder, FrameEncoder, FrameIndex
+from .frame import BlockMode, FrameDecoder, FrameEncoder, FrameIndex, FrameInfo
 
 LZ_EXTENSION = ".lz4"
 CHUNK = 4 << 20
@@ -57,7 +59,11 @@ def _decode(fin, fout, byte_range):
             fout.write(index.read(*byte_range))
 
 
-def handle_file(path, out, clean, force, force_decompress, print_info=True, byte_range=None):   # main.rs:82-164
+def _encoder(wtr, linked):
+    return FrameEncoder.with_frame_info(FrameInfo(block_mode=BlockMode.Linked), wtr) if linked else FrameEncoder.new(wtr)
+
+
+def handle_file(path, out, clean, force, force_decompress, print_info=True, byte_range=None, linked=False):   # main.rs:82-164
     decompress = path.endswith(LZ_EXTENSION)
     if force_decompress and not decompress:
         raise SystemExit("Can't determine an output filename")
@@ -77,7 +83,7 @@ def handle_file(path, out, clean, force, force_decompress, print_info=True, byte
     else:
         with open(path, "rb") as fin, open(out, "wb") as fout:
             tw = _TrackWriteSize(fout)
-            enc = FrameEncoder.new(tw)
+            enc = _encoder(tw, linked)
             n_in = _copy(fin, enc)
             enc.finish()
             if print_info:
@@ -96,6 +102,7 @@ def main(argv=None):
     ap.add_argument("--range", metavar="OFF:LEN", help="decompression: write only bytes [OFF, OFF + LEN) of the content")
     ap.add_argument("--high", action="store_true", help="compression: the deep-search encoder (smaller output, slower)")
     ap.add_argument("--depth", type=int, metavar="N", help="with --high: candidates examined per position, 1 .. 256 (default 16)")
+    ap.add_argument("--linked", action="store_true", help="compression: a Linked frame (blocks may refer to the blocks in front of them)")
     o = ap.parse_args(argv)
     byte_range = _parse_range(o.range) if o.range else None
     if o.depth is not None and not o.high:
@@ -108,10 +115,13 @@ def main(argv=None):
         block.set_compress_mode("high")
         if o.depth is not None:
             block.set_compress_depth(o.depth)
+        block.set_compress_high_linked(o.linked)
+    if o.linked and (o.decompress or (o.input_file and o.input_file.endswith(LZ_EXTENSION))):
+        raise SystemExit("--linked goes with a compression")
     if o.input_file and o.input_file != "-":
         if byte_range is not None and not o.input_file.endswith(LZ_EXTENSION):
             raise SystemExit("--range goes with a decompression")
-        handle_file(o.input_file, o.out, o.clean, o.force, o.decompress, byte_range=byte_range)
+        handle_file(o.input_file, o.out, o.clean, o.force, o.decompress, byte_range=byte_range, linked=o.linked)
         return 0
     if byte_range is not None and not o.decompress:
         raise SystemExit("--range goes with a decompression")
@@ -121,7 +131,7 @@ def main(argv=None):
         if o.decompress:
             _decode(fin, fout, byte_range)
         else:
-            enc = FrameEncoder.new(fout)
+            enc = _encoder(fout, o.linked)
             _copy(fin, enc)
             enc.finish()
     finally:

@@ -358,8 +358,10 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
     int rc;
     CompressArgs a = a_;
     // "compress_mode" 2 (high) encodes independent blocks; a call with dictionaries takes its dictionary form with "compress_high_dict" 1
-    // and the throughput encoder otherwise
+    // and the throughput encoder otherwise; one without dictionaries and with flags takes the same form with "compress_high_linked" 1, the
+    // LZ4FLEX_BLOCK_HISTORY bytes in front of a block as its dictionary
     const bool with_dict = a.dict_len || shared || set;
+    const bool with_history = !with_dict && a.flags && c->comp_high_linked;
     const int mode = c->comp_mode == 2 ? ((with_dict && !c->comp_high_dict) ? 0 : 2) : c->comp_mode;
     if (shared) c->shared_counted = mode == 0;
     if (set && mode == 2) c->set_counted = nullptr;              // (the set's counter is the throughput encoder's)
@@ -367,7 +369,9 @@ static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big,
         // its scratch is the (otherwise idle) throughput encoder's workspace, ordered across streams like that encoder's own launches;
         // a workgroup holds most of a CU's LDS, so one per CU (wave_wgs is two per CU) and no more than the workspace has slices for
         if ((rc = wave_ws_acquire(c, s))) return rc;
-        if (with_dict) {
+        if (with_history)
+            le = launch_compress_high_linked(a, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2, (uint32_t)c->comp_depth, s);
+        else if (with_dict) {
             HighDictArgs d{};
             if (shared) { d.shared = shared->dict; d.shared_len = shared->len; }
             if (set) { d.has_set = 1u; d.set = *set; }
@@ -588,6 +592,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     c->packed_tile = (int)PACKED_SCAN_TILE;
     if (const char* e = getenv("LZ4FLEX_COMPRESS_MODE")) c->comp_mode = (!strcmp(e, "exact") || !strcmp(e, "1")) ? 1 : (!strcmp(e, "high") || !strcmp(e, "2")) ? 2 : 0;
     if (const char* e = getenv("LZ4FLEX_HIGH_DICT")) c->comp_high_dict = !strcmp(e, "1") ? 1 : 0;
+    if (const char* e = getenv("LZ4FLEX_HIGH_LINKED")) c->comp_high_linked = !strcmp(e, "1") ? 1 : 0;
     if (const char* e = getenv("LZ4FLEX_SLIDING_WINDOW")) {      // "0", "1" or "2", nothing else ("off" used to read as 0 silently: ADVICE r4)
         if (!strcmp(e, "0") || !strcmp(e, "1") || !strcmp(e, "2")) c->comp_sliding = e[0] - '0';
         else { g_last_error = "LZ4FLEX_SLIDING_WINDOW must be 0, 1 or 2"; delete c; return -LZ4FLEX_E_INVALID_ARG; }
@@ -693,6 +698,7 @@ const Setting SETTINGS[] = {
     {"compress_mode", &lz4flex_ctx::comp_mode, up_to_2, false},
     {"compress_depth", &lz4flex_ctx::comp_depth, [](int v) { return v >= 1 && v <= 256; }, false},      // "compress_mode" 2: candidates per position
     {"compress_high_dict", &lz4flex_ctx::comp_high_dict, is_flag, false},          // "compress_mode" 2: dictionary calls take its dictionary form
+    {"compress_high_linked", &lz4flex_ctx::comp_high_linked, is_flag, false},      // ... LZ4FLEX_BLOCK_HISTORY bits are read, Linked frames keep the mode
     {"compress_high_digest", &lz4flex_ctx::comp_high_digest, is_flag, false},      // ... and a shared dictionary is sorted once per call
     {"compress_subwindows", &lz4flex_ctx::comp_sub, [](int v) { return v >= 0 && v <= 4; }, false},
     {"compress_deterministic", &lz4flex_ctx::comp_det, is_flag, false},
@@ -1966,6 +1972,8 @@ int64_t lz4flex_compress_into_with_table(const uint8_t* in, size_t in_len, uint8
     if (rc) return rc;
     t->ctx->comp_mode = dc->comp_mode;                         // the thread's encoder choice (throughput / reference-exact / high)
     t->ctx->comp_depth = dc->comp_depth;
+    t->ctx->comp_high_dict = dc->comp_high_dict;
+    t->ctx->comp_high_linked = dc->comp_high_linked;
     t->ctx->comp_variant = dc->comp_variant;
     const uint32_t len = (uint32_t)in_len, cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull);
     // Large: HashTable4K, cleared, stream offset 0 == the frame encoder's first block (LZ4FLEX_BLOCK_FRAME_FIRST);

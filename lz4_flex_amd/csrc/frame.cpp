@@ -217,8 +217,9 @@ struct lz4flex_frame_encoder {
             flags[i] = LZ4FLEX_BLOCK_HISTORY(std::min<uint64_t>(have, FAST_HISTORY));
             left -= len;
         }
-        // (compress_mode high encodes independent blocks only: a Linked frame's blocks are the throughput encoder's)
-        const bool high = lz4flex_get_tuning(nullptr, "compress_mode") == 2;
+        // (compress_mode high: a Linked frame's blocks are the throughput encoder's unless "compress_high_linked" is 1 -- then the
+        // history bits above are read by the high encoder, a block's dictionary is the stream in front of it)
+        const bool high = lz4flex_get_tuning(nullptr, "compress_mode") == 2 && lz4flex_get_tuning(nullptr, "compress_high_linked") != 1;
         if (high) (void)lz4flex_set_tuning(nullptr, "compress_mode", 0);
         int rc = lz4flex_compress_batch(nullptr, lstage.data(), in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk, dst.data(),
                                         out_off.data(), out_cap.data(), out_len.data(), status.data(), LZ4FLEX_MEM_HOST, nullptr);

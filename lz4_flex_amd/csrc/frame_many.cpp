@@ -173,9 +173,10 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
                                            D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st),
                                            nullptr, LZ4FLEX_MEM_DEVICE, s));
         else {
-            // (compress_mode high encodes independent blocks only: Linked frames' blocks are the throughput encoder's)
+            // (compress_mode high: Linked frames' blocks are the throughput encoder's unless "compress_high_linked" is 1 -- then the
+            // one launch over all blocks of all streams is the high encoder's, every block's history its dictionary)
             const int mode = c->comp_mode;
-            if (linked && mode == 2) c->comp_mode = 0;
+            if (linked && mode == 2 && !c->comp_high_linked) c->comp_mode = 0;
             const int rc = lz4flex_compress_batch(c, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), D.dev<uint32_t>(a_flags), nb, comp,
                                                   D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len),
                                                   D.dev<int32_t>(a_comp_st), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s);

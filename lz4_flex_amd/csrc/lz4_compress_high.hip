@@ -1,5 +1,6 @@
 // lz4_compress_high.hip -- compress_mode 2 ("high"): a deep-search encoder for independent blocks, without a dictionary (the plain form)
-// and against one ("compress_high_dict" 1: the dictionary form, the same code as a template on the dictionary).
+// and against one ("compress_high_dict" 1: the dictionary form, the same code as a template on the dictionary; "compress_high_linked" 1:
+// the same form with the block's own stream as its dictionary, LZ4FLEX_BLOCK_HISTORY).
 //
 // The bytes are DEFINED by the scalar model tests/sim/high_encoder_model.c (chunks, candidates, best[], the one-step lazy parse: see its
 // head comment and include/lz4flex_amd.h, "compress_mode"); this kernel computes the same function of (block, depth) in parallel.  The
@@ -173,7 +174,8 @@ __device__ void stage_dict(uint32_t* win, uint32_t mis, const uint8_t* dend, uin
 
 // DICT: the block has the dictionary that ends at dend, its last H bytes are chunk 0's history (H == 0: none; the plain form's bytes).
 // dg_sorted / dg_start (nullable): the dictionary tail's digest (lz4_high_digest_kernel) -- chunk 0 sorts the block's positions only.
-template <bool DICT>
+// HIST (with DICT): the dictionary is the block's own stream in front of it, dend == the block's start (the history form).
+template <bool DICT, bool HIST = false>
 __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, uint8_t* ws, uint32_t depth, const uint8_t* dend = nullptr,
                                uint32_t H_ = 0u, const uint16_t* dg_sorted = nullptr, const uint16_t* dg_start = nullptr) {
     const uint32_t T = blockDim.x, t = threadIdx.x;
@@ -214,9 +216,9 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
 
         // 1  stage (the aligned dwords that hold the window: the first and the last one may reach 3 bytes past it, inside their dword)
         const uint32_t mis = dchunk ? (uint32_t)(((uintptr_t)in - H) & 3u) : (uint32_t)((uintptr_t)(in + base) & 3u);
-        if (dchunk) stage_dict(win, mis, dend, H, in, end);
-        else {
-            const uint32_t* src = (const uint32_t*)(in + base - mis);
+        if (!HIST && dchunk) stage_dict(win, mis, dend, H, in, end);
+        else {                                                    // (HIST: the tail lies in front of the block -- one run of dwords)
+            const uint32_t* src = (const uint32_t*)((HIST && dchunk ? in - H : in + base) - mis);
             const uint32_t ndw = (mis + wlen + 3u) >> 2;
             for (uint32_t i = t; i < ndw; i += T) win[i] = src[i];
         }
@@ -428,6 +430,19 @@ __global__ void __launch_bounds__(THREADS) lz4_compress_high_dict_kernel(const C
     }
 }
 
+// The history form ("compress_high_linked" 1): the dictionary form with block b's dictionary = the a.flags[b] >> 8 bytes of its own
+// stream in front of it (LZ4FLEX_BLOCK_HISTORY; the low byte is not read).  It ends where the block starts, so chunk 0's window is one
+// run of aligned dwords: no read leaves the dwords that hold [in - H, in + n).  a.flags is not null, a's dictionaries are not read.
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_linked_kernel(const CompressArgs a, uint8_t* ws, uint32_t depth) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        const uint32_t h = a.flags[b] >> 8;
+        const uint32_t H = h < 4u ? 0u : umin(h, CHUNK);
+        compress_block<true, true>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth, a.in_base + a.in_off[b], H);
+        __syncthreads();
+    }
+}
+
 // The digest of one dictionary's tail: its hashed positions (q + 4 <= H) in the order the joint sort gives them, and the buckets' bounds.
 // One workgroup; `slice` is a workgroup's slice of the workspace: u16 sorted[H - 3] at W_SORT_A, u16 start[32 769] at W_SORT_B (the
 // positions with hash h are sorted[start[h] .. start[h + 1])).  len >= 4.
@@ -471,6 +486,16 @@ hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t w
     const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
     if (g == 0u || depth == 0u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(high::lz4_compress_high_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
+    return hipGetLastError();
+}
+
+hipError_t launch_compress_high_linked(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth,
+                                       hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    const size_t fit = workspace_bytes / high::WS_PER_WG;
+    const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
+    if (g == 0u || depth == 0u || a.flags == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(high::lz4_compress_high_linked_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
     return hipGetLastError();
 }
 

@@ -98,6 +98,7 @@ struct lz4flex_ctx {
     int comp_mode = 0;            // 0 = throughput ("wave") encoder, own parse (default); 1 = reference-exact encoder (lz4_flex's bytes); 2 = high (lz4_compress_high.hip: deep search, independent blocks without a dictionary; everything else as 0)
     int comp_depth = 16;          // "compress_depth": compress_mode 2, the candidates examined per position (1 .. 256)
     int comp_high_dict = 0;       // "compress_high_dict": compress_mode 2, 1 = calls with dictionaries take the high encoder's dictionary form (tests/sim/high_dict_model.c's bytes); 0 = the throughput encoder (default)
+    int comp_high_linked = 0;     // "compress_high_linked": compress_mode 2, 1 = LZ4FLEX_BLOCK_HISTORY bits are read (the block's history is its dictionary: tests/sim/high_dict_model.c's bytes) and Linked frames keep the mode; 0 = the bits are ignored, Linked frames take the throughput encoder (default)
     int comp_high_digest = 1;     // "compress_high_digest": the dictionary form, 1 = a shared dictionary's positions are sorted once per call; 0 = with every block's own (A/B measurements, tests)
     int comp_variant = 1;         // reference-exact encoder: 1 = group encoder + emitter wave (default), 3 = group encoder alone
     uint8_t* pcd_ws = nullptr;    // workgroup decoder, small batches: a parser and a copier workgroup per block hand token lists over through this (lz4_device.h pair_ws)

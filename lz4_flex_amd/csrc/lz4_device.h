@@ -219,6 +219,11 @@ struct HighDictArgs {
 };
 hipError_t launch_compress_high_dict(const CompressArgs& a, const HighDictArgs& d, bool use_digest, void* workspace, size_t workspace_bytes,
                                      int max_workgroups, uint32_t depth, hipStream_t s);
+// its history form ("compress_high_linked" 1): the dictionary form with block b's dictionary = the a.flags[b] >> 8 bytes of its own stream
+// in front of it (LZ4FLEX_BLOCK_HISTORY), readable at a.in_base + a.in_off[b] - h; the flag word's low byte and a's dictionaries are not
+// read, a.flags must not be null.  A block with h < 4 gets the plain form's bytes.
+hipError_t launch_compress_high_linked(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth,
+                                       hipStream_t s);
 // a dictionary set's digests: bytes per dictionary, and the kernel that fills table[0 .. k)'s (a workgroup of one wavefront per
 // dictionary; cand_scratch: compress_wave_digest_scratch_bytes() bytes per dictionary, dead behind the launch)
 size_t compress_wave_digest_bytes();

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Do two `hipcc -S` listings of lz4_compress_wave.hip hold the same instruction streams for the hot functions?
+"""Do two `hipcc -S` listings of lz4_compress_wave.hip (or of another kernel file of a namespace of lz4flex_dev, such as
+lz4_compress_high.hip with the function lz4_compress_high_kernel) hold the same instruction streams for the hot functions?
 
     python tools/isa_fn_diff.py PARENT.s CHANGE.s [function ...]        (default: match_segment index_window)
 
@@ -15,7 +16,7 @@ def functions(path, names):
     with open(path) as f:
         text = f.read()
     out = {}
-    pat = r"^(_ZN11lz4flex_dev4wave\d+(?:%s)\w*):.*?^\.Lfunc_end\d+:" % "|".join(names)
+    pat = r"^(_ZN11lz4flex_dev\d+[a-z]+\d+(?:%s)\w*):.*?^\.Lfunc_end\d+:" % "|".join(names)
     for m in re.finditer(pat, text, re.S | re.M):
         body = []
         for line in m.group(0).splitlines()[1:-1]:
@@ -33,7 +34,7 @@ def main():
     a, b = functions(sys.argv[1], names), functions(sys.argv[2], names)
     differ = False
     for k in sorted(set(a) | set(b)):
-        (ia, ra), (ib, rb) = a.get(k, ([], None)), b.get(k, ([], None))
+        (ia, ra), (ib, rb) = a.get(k, ([], ("-", "-"))), b.get(k, ([], ("-", "-")))      # ("-": the listing has no such function)
         d = list(difflib.unified_diff(ia, ib, lineterm="", n=0))
         print("%s: %d / %d instructions, VGPRs %s / %s, scratch %s / %s, %d diff lines" % (k[:64], len(ia), len(ib), ra[0], rb[0], ra[1], rb[1], len(d)))
         for line in d[:40]:
