@@ -93,7 +93,8 @@ const char *lz4flex_build_id(void);
  * the scratch the *_many calls already grow: an index owns its tables), then partial decode against dictionaries
  * lz4flex_decompress_batch_partial_shared_dict / lz4flex_decompress_batch_partial_dict_set / lz4flex_decompress_partial_into_with_dict (no
  * new setting, no workspace) -- a caller detects them by the symbol -- then "compress_mode" 2 (high) with the setting "compress_depth" (no
- * new symbol, no workspace beyond the encoder's: a caller detects the mode by lz4flex_set_tuning(ctx, "compress_mode", 2) == 0). */
+ * new symbol, no workspace beyond the encoder's: a caller detects the mode by lz4flex_set_tuning(ctx, "compress_mode", 2) == 0), then the
+ * dictionary trainer lz4flex_dict_train with lz4flex_dict_train_work_size (no setting, no workspace in the context: the caller brings it). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -594,6 +595,37 @@ int lz4flex_decompress_batch_partial_dict_set(lz4flex_ctx *ctx, const void *in_b
                                               uint32_t n, const uint32_t *dict_id, void *out_base, const uint64_t *out_off,
                                               const uint32_t *target, uint32_t *out_len, int32_t *status,
                                               const lz4flex_dict_set *set, int mem_kind, void *hip_stream);
+
+/* Train a dictionary from a batch of samples (lz4_dict_train.hip): sample i is in_base[in_off[i] .. + in_len[i]); the dictionary -- at
+ * most dict_cap <= 65 536 bytes, left-aligned in dict_out, *dict_len of them -- is a concatenation of segments of at most `segment`
+ * bytes (64 ... 2 048; 0 = 512) cut from the samples.  What it is for: lz4flex_compress_batch_shared_dict / lz4flex_dict_set_create and
+ * their decoders, for many small records that have no "earlier part of the file" to use.  The bytes are a function of the samples,
+ * dict_cap and segment ALONE (never of the device, the memory kind or the stream): tests/sim/dict_train_model.c is the definition, the
+ * kernels equal it byte for byte.  The rule, fastCover's restated so that every step is an integer computation with a fixed result:
+ *   a candidate is a position p of a sample with 8 bytes left; candidates are numbered through the batch; total = their number;
+ *   hash(p) = (LE64(sample[p .. p + 8)) * 0x9E3779B185EBCA87) >> 44; freq[h] counts the candidates of the whole batch with hash h;
+ *   first(p) = 0 if one of the segment - 1 candidates in front of p in its sample has p's hash, else 1;
+ *   w(p) = first(p) ? min(freq[hash(p)], 2^20 - 1) : 0; the score of a start s is the sum of w over [s, min(s + segment - 7, candidates
+ *   of the sample));  nseg = ceil(dict_cap / segment), E = max(1, min(nseg, total / (4 segment))), R = ceil(total / E);
+ *   step t = 0 .. 2 nseg - 1 (until no capacity is left or E steps in a row chose nothing) takes the start with the largest score among
+ *   the global numbers [r R, (r + 1) R), r = t mod E, the lowest number among equals, nothing at score 0: the segment is sample[s .. s +
+ *   min(segment, in_len - s)), clipped to the capacity left, and the counters of its candidates are set to 0;
+ *   the dictionary holds the segments in REVERSE order of choice -- the encoders look at a dictionary's tail, the best material is there.
+ * *status: 0, or LZ4FLEX_E_UNSUPPORTED (and *dict_len 0) for 2^32 candidates or more.  Samples may overlap and come in any order; they
+ * are only read.  Nothing is written outside dict_out[0 .. *dict_len), dict_len, status and work.
+ * mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, `work` holds lz4flex_dict_train_work_size(n) bytes (8-byte aligned; 4
+ *   MiB of counters and a few words per sample), the call is asynchronous on hip_stream, allocates nothing, copies nothing to the host
+ *   and never synchronises: 2 nseg + a few launches whose shape depends on n, dict_cap and segment alone -- or LZ4FLEX_MEM_HOST -- staged
+ *   through the context and synchronous; `work` is ignored.  LZ4FLEX_MEM_BIG_BLOCKS may be ORed in (samples of any u32 length are taken
+ *   either way); LZ4FLEX_MEM_CHAINED is refused.
+ * The arguments are checked before a context or a device is looked at: -LZ4FLEX_E_INVALID_ARG for a segment that is not 0 and outside
+ *   64 ... 2 048, dict_cap > 65 536, dict_len or status NULL, dict_out NULL with dict_cap != 0, in_off or in_len NULL with n != 0, a
+ *   mem_kind other than HOST / DEVICE (| BIG_BLOCKS), work NULL in a DEVICE call.  n == 0 or dict_cap == 0: returns 0 with *dict_len = 0,
+ *   *status = 0 (HOST: without a device; DEVICE: written by a kernel).  -LZ4FLEX_E_NO_DEVICE without a device: there is no CPU path. */
+size_t lz4flex_dict_train_work_size(uint32_t n);
+int lz4flex_dict_train(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
+                       void *dict_out, uint32_t dict_cap, uint32_t segment /* 0 = 512 */, uint32_t *dict_len /* 1, written */,
+                       int32_t *status /* 1, written */, void *work, int mem_kind, void *hip_stream);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

@@ -350,14 +350,15 @@ def _arg(a):
 
 
 def _host_call(name, ctx, in_buf, in_off, in_len, out=None, before_n=(), middle=(), tail=(), detail=False, len_dtype=np.uint32,
-               mem_kind=L.MEM_HOST):
+               mem_kind=L.MEM_HOST, per_call=False):
     """The host marshaller:
         name(ctx, in_base, in_off, in_len, *before_n, n, *middle, [out_base, out_off, out_cap,] out_len, status, [detail,] *tail, mem_kind, NULL)
     in_buf is bytes-like or a uint8 array, in_off / in_len and `out` = (out_buf, out_off, out_cap) anything numpy converts; before_n,
     middle and tail hold what is particular to the entry, each as _arg takes it.  Returns the arrays the call wrote: (out_len[len_dtype],
-    status[i32]) and, with `detail`, detail[n, 2] u64."""
+    status[i32]) and, with `detail`, detail[n, 2] u64; per_call: the entry writes ONE length and ONE status for the whole batch."""
     n = len(in_off)
-    results = [np.zeros(n, dtype=len_dtype), np.zeros(n, dtype=np.int32)] + ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
+    m = 1 if per_call else n
+    results = [np.zeros(m, dtype=len_dtype), np.zeros(m, dtype=np.int32)] + ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
     slots = [] if out is None else [out[0], _np(out[1], np.uint64), _np(out[2], np.uint32)]
     args = [_host_u8(in_buf), _np(in_off, np.uint64), _np(in_len, np.uint32), *before_n, n, *middle, *slots, *results, *tail]
     _check(getattr(L.load(), name)(ctx, *map(_arg, args), mem_kind, None), name)
@@ -806,3 +807,44 @@ def compress_blocks_packed_device(src, in_off, in_len, capacity, prepend_size=Tr
         _device_call("lz4flex_compress_batch_packed", [src, d_off, d_len], n,
                      [prefix, scratch, int(scratch_cap), out, capacity, int(align), out_off, out_len, status, work], big_blocks, sp, ctx)
     return out[:capacity], out_off, out_len, status
+
+
+# ---- a dictionary from the data (lz4flex_dict_train) ---------------------------------------------------------------------------
+def train_dictionary_batch(in_buf, in_off, in_len, dict_size=32768, segment=512, ctx=None):
+    """lz4flex_dict_train over host buffers: a dictionary of at most dict_size (<= 65 536) bytes cut from the samples in_buf[in_off[i] :
+    + in_len[i]], in segments of at most `segment` bytes (64 ... 2 048) -- the ones whose 8-byte windows are the most frequent in the
+    whole batch, the best at the tail.  The bytes are a function of the samples, dict_size and segment alone.  Returns bytes: what
+    DictSet([...]), the *_with_shared_dict calls and *_with_dict take."""
+    out = np.zeros(max(int(dict_size), 1), dtype=np.uint8)
+    length, status = _host_call("lz4flex_dict_train", ctx, in_buf, in_off, in_len, middle=[out, int(dict_size), int(segment)], tail=[None],
+                                per_call=True)
+    if status[0]:
+        raise ValueError("train_dictionary: the samples have 2^32 positions or more (status %d)" % status[0])
+    return out[:int(length[0])].tobytes()
+
+
+def train_dictionary(samples, dict_size=32768, segment=512, ctx=None):
+    """train_dictionary_batch of a list of bytes-likes (or uint8 arrays)."""
+    parts = [_host_u8(s) for s in samples]
+    lens = np.array([p.size for p in parts], dtype=np.uint32)
+    offs = np.zeros(len(parts), dtype=np.uint64)
+    if len(parts):
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    flat = np.concatenate(parts) if len(parts) and int(lens.sum(dtype=np.uint64)) else np.zeros(1, dtype=np.uint8)
+    return train_dictionary_batch(flat, offs, lens, dict_size, segment, ctx)
+
+
+def train_dictionary_device(src, in_off, in_len, dict_size=32768, segment=512, stream=None):
+    """Samples in device memory: src is a uint8 torch tensor on the GPU, sample i is src[in_off[i] : + in_len[i]].  One lz4flex_dict_train
+    (MEM_DEVICE, asynchronous on `stream`, default the current one; the workspace of lz4flex_dict_train_work_size(n) bytes is allocated
+    here): no host synchronisation, nothing copied to the host.  Returns (dictionary, dict_len) as device tensors: dictionary has
+    dict_size bytes of which the first dict_len[0] are the dictionary (dictionary[:int(dict_len)] is what the *_shared_dict_device calls
+    take)."""
+    import torch
+    dict_size = int(dict_size)
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
+    out = torch.zeros(max(dict_size, 1), dtype=torch.uint8, device=dev)
+    res = torch.zeros(2, dtype=torch.int32, device=dev)          # dict_len, status
+    work = torch.empty(int(L.load().lz4flex_dict_train_work_size(n)), dtype=torch.uint8, device=dev)
+    _device_call("lz4flex_dict_train", [src, d_off, d_len], n, [out, dict_size, int(segment), res[0:1], res[1:2], work], False, sp)
+    return out[:dict_size], res[0:1]

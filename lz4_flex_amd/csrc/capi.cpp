@@ -1682,6 +1682,62 @@ int lz4flex_compress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const u
     return packed_scatter_to_host(c, (const uint8_t*)d_out, std::min<uint64_t>(out_off[n], out_bytes), (uint8_t*)out_base, out_off, out_len, status, n);
 }
 
+// ---- a dictionary from a batch of samples (lz4_dict_train.hip) -------------------------------------------------------------------
+size_t lz4flex_dict_train_work_size(uint32_t n) { return dict_train_work_bytes(n); }
+
+// DEVICE: the launches on the caller's stream, nothing else.  HOST: [input span | in_off in_len | dict_len status dict | work] in the
+// arena, one transfer down (the two words and dict_cap bytes), one synchronisation.
+int lz4flex_dict_train(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* dict_out,
+                       uint32_t dict_cap, uint32_t segment, uint32_t* dict_len, int32_t* status, void* work, int mem_kind, void* hip_stream) {
+    if (segment != 0u && (segment < 64u || segment > 2048u)) return -LZ4FLEX_E_INVALID_ARG;
+    if (dict_cap > DICT_KEEP || !dict_len || !status || (dict_cap && !dict_out)) return -LZ4FLEX_E_INVALID_ARG;
+    if (n && (!in_off || !in_len)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED; BIG_BLOCKS changes nothing)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && !work) return -LZ4FLEX_E_INVALID_ARG;
+    const uint32_t seg = segment ? segment : 512u;
+    const bool nothing = n == 0u || dict_cap == 0u;
+    if (nothing && k.where == Mem::Host) { *dict_len = 0u; *status = 0; return 0; }
+    int rc;
+    if ((rc = begin_batch(&ctx))) return rc;
+    if (k.where == Mem::Device) {
+        const hipError_t le = launch_dict_train((const uint8_t*)in_base, in_off, in_len, n, (uint8_t*)dict_out, dict_cap, seg, dict_len, status,
+                                                work, (hipStream_t)hip_stream);
+        return le != hipSuccess ? hip_fail(le, "dict train launch") : 0;
+    }
+    DeviceGuard guard(ctx->device);
+    HIP_TRY(guard.err);
+    const Span sp = span_of(in_off, in_len, n);
+    const size_t in_bytes = sp.bytes();
+    Layout l{16};
+    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n);
+    const size_t up_bytes = l.end;
+    const size_t at_res = l.take(8), at_dict = l.take(dict_cap);
+    const size_t desc_bytes = l.end;
+    if ((rc = ensure_buf(ctx->pin, desc_bytes))) return rc;
+    const size_t a_desc = align_up(in_bytes + 64, 256), a_work = a_desc + align_up(desc_bytes, 256);
+    if ((rc = ensure_buf(ctx->arena, a_work + dict_train_work_bytes(n) + 256))) return rc;
+    uint8_t* hp = ctx->pin.p;
+    for (uint32_t i = 0; i < n; i++) {
+        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
+        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
+    }
+    uint8_t* d = ctx->arena.p;
+    uint8_t* dd = d + a_desc;
+    hipStream_t s = ctx->stream;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(d, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
+    const hipError_t le = launch_dict_train(d, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, dd + at_dict, dict_cap, seg,
+                                            (uint32_t*)(dd + at_res), (int32_t*)(dd + at_res + 4), d + a_work, s);
+    if (le != hipSuccess) return hip_fail(le, "dict train launch");
+    HIP_TRY(hipMemcpyAsync(hp + at_res, dd + at_res, desc_bytes - at_res, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(dict_len, hp + at_res, 4);
+    memcpy(status, hp + at_res + 4, 4);
+    if (*dict_len) memcpy(dict_out, hp + at_dict, std::min<uint32_t>(*dict_len, dict_cap));
+    return 0;
+}
+
 // ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------
 static const uint64_t OFF0 = 0;
 static const uint8_t EMPTY = 0;

@@ -312,6 +312,12 @@ hipError_t launch_packed_finish(const int32_t* pre, const uint64_t* size, const 
 hipError_t launch_packed_gather(const uint8_t* scratch, const uint64_t* src_off, const uint64_t* size, const uint64_t* off,
                                 const uint32_t* in_len, uint32_t n, uint32_t prefix, uint64_t total_cap, uint8_t* out, uint32_t* out_len,
                                 int32_t* status, hipStream_t s);
+// lz4_dict_train.hip (lz4flex_dict_train): a dictionary of at most dict_cap <= 65 536 bytes cut from the n samples, segments of k bytes
+// (64 ... 2 048) chosen by the rule of tests/sim/dict_train_model.c.  Every pointer is device memory; work: dict_train_work_bytes(n) bytes,
+// 8-byte aligned.  n == 0 or dict_cap == 0: *dict_len = 0, *status = 0 from a one-lane kernel.  Nothing is copied to the host.
+size_t dict_train_work_bytes(uint32_t n);
+hipError_t launch_dict_train(const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* dict_out,
+                             uint32_t dict_cap, uint32_t k, uint32_t* dict_len, int32_t* status, void* work, hipStream_t s);
 // frame_range.hip (frame_index.cpp: lz4flex_frame_index_create / lz4flex_frame_read_ranges).
 // The index: scan_len[b] = what launch_size_scan measures of walked block b (0 for a stored block), *first_bad = ~0; then size[b] (holding
 // the scan's sizes) becomes the block's decoded bytes and *first_bad the first compressed block with scan_st != 0 or more than block_size bytes
