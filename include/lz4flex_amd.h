@@ -794,7 +794,8 @@ int lz4flex_dict_train(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in
  *   "frame_range_pass_bytes" and "frame_range_checksums" (see lz4flex_frame_read_ranges);
  *   "packed_scan_tile" (read-only: the sizes one workgroup of the packed entries' offset scan takes, see the packed batches).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
- * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.
+ * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.  "debug_exact_dict_piece" (set only; a count, 0 = no
+ * limit): "compress_mode" 1 calls with dictionaries build their chain records in pieces of at most that many blocks.
  * The key is looked at before a context is: an unknown key and a refused "debug_" key answer -LZ4FLEX_E_INVALID_ARG on any machine,
  * a known key with ctx NULL needs the default context and with it a device (-LZ4FLEX_E_NO_DEVICE without one).  The same for
  * lz4flex_get_tuning. */

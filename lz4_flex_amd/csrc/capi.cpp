@@ -7,7 +7,7 @@
 //                    lz4_flex-shaped scalar calls -- 1-block batches -- take);
 //   run_device_batch MEM_DEVICE: the caller's BatchCall as it is, on the caller's stream;
 //   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode (the
-//                    SharedDictArgs set-up, launch_compress_any) and launch_decode (the chain bracket and the choice between the
+//                    DictSource set-up; launch_compress_any: encoder_for's choice, then that mode's launches) and launch_decode (the chain bracket and the choice between the
 //                    shared-dictionary, the partial (with or without a dictionary), the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
 //                    shape, launch_redo is the second pass behind every first-pass decoder).
 // The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
@@ -253,75 +253,6 @@ static hipError_t launch_decompress_partial_set(lz4flex_ctx* c, const Decompress
     return e != hipSuccess ? e : launch_redo(c, a, s, Redo::PartialDictSet, nullptr, 0, &set);
 }
 
-// Reference-exact encoder, MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks
-// of <= 64 KiB and the host cannot see the device-resident lengths, so a block that breaks the promise is flagged on the
-// device (its bytes would be a valid block, but not lz4_flex's) instead of passing silently.
-__global__ void lz4flex_flag_long_blocks_kernel(const uint32_t* in_len, uint32_t n, uint32_t* out_len, int32_t* status, const uint32_t* dict_len) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n && in_len[b] > 65536u && (dict_len == nullptr || dict_len[b] == 0u)) { status[b] = LZ4FLEX_E_INVALID_ARG; out_len[b] = 0u; }
-}
-
-// lz4flex_compress_batch_ex, reference-exact mode: block i's one-block chain for the chain kernel -- the record
-// lz4flex_compress_into_with_dict builds on the host (compress.rs:554-583: the table kind from the UNtruncated dictionary length, the
-// dictionary's last 64 KiB, input_stream_offset = their length), built here because a DEVICE batch's lengths are device memory.
-// count[i] = 1 for a block with a dictionary, 0 (not encoded by the chain kernel) for the others and for refused ones: a dictionary
-// with flags, or an input the u32 stream positions cannot hold (status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written).
-__global__ void lz4flex_dict_chain_records_kernel(const uint64_t* in_off, const uint32_t* in_len, const uint32_t* flags,
-                                                  const uint64_t* dict_off, const uint32_t* dict_len, uint32_t n,
-                                                  lz4flex_chain_block* rec, uint32_t* count, uint32_t* out_len, int32_t* status) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n) return;
-    const uint32_t dl = dict_len[b], len = in_len[b];
-    uint32_t cnt = 0u;
-    if (dl != 0u) {
-        if ((flags != nullptr && flags[b] != 0u) || len > 0x7FFFFFFFu) {
-            status[b] = LZ4FLEX_E_INVALID_ARG;
-            out_len[b] = 0u;
-        } else {
-            const uint32_t tl = dl > 65536u ? 65536u : dl;
-            lz4flex_chain_block r;
-            r.in_off = in_off[b];
-            r.dict_off = dict_off[b] + (dl - tl);
-            r.in_len = len;
-            r.in_pos = 0u;
-            r.dict_len = tl;
-            r.so = tl;
-            r.repos = 0u;
-            r.flags = ((uint64_t)dl + len < 65535u ? 1u : 0u) | 2u;
-            rec[b] = r;
-            cnt = 1u;
-        }
-    }
-    count[b] = cnt;
-}
-
-// lz4flex_compress_batch_shared_dict, reference-exact mode: the per-block dictionary arrays the chain records are built from -- every
-// block has the one dictionary (offset 0 of dict_base, `len` bytes)
-__global__ void lz4flex_fill_shared_dict_kernel(uint64_t* dict_off, uint32_t* dict_len, uint32_t n, uint32_t len) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < n) { dict_off[b] = 0ull; dict_len[b] = len; }
-}
-// lz4flex_compress_batch_dict_set, reference-exact mode: the per-block dictionary arrays of one piece, from the set's table.  dict_off
-// is relative to `base` (the set's allocation) and names where the dictionary WOULD begin if all of `len` were kept: the records kernel
-// above adds len - min(len, 64 KiB), which lands on the first kept byte (u64 arithmetic: the intermediate may wrap).  A refused id gets
-// dict_len 1 (the block encoder leaves the block alone) and flag 1 (the records kernel refuses a dictionary with flags: status
-// LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written).
-__global__ void lz4flex_fill_set_dict_kernel(DictSetArgs set, const uint8_t* base, uint32_t n, uint64_t* dict_off, uint32_t* dict_len, uint32_t* flags) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n) return;
-    const uint32_t id = set.dict_id[b];
-    uint64_t off = 0ull;
-    uint32_t len = 0u, flag = 0u;
-    if (id != DICT_ID_NONE) {
-        if (id >= set.k) { len = 1u; flag = 1u; }
-        else {
-            const DictSetRec r = set.table[id];
-            len = r.len;
-            off = (uint64_t)(r.end - base) - r.len;
-        }
-    }
-    dict_off[b] = off; dict_len[b] = len; flags[b] = flag;
-}
 // MEM_HOST batches whose results are sparse in the output span (compress: ~15 KB used of every 72 KB stride):
 // pack the produced bytes densely on the device so that ONE transfer brings them to the host.
 __global__ void __launch_bounds__(256) lz4flex_pack_results_kernel(const uint8_t* src, const uint64_t* src_off, const uint32_t* len,
@@ -348,120 +279,74 @@ static int wave_ws_acquire(lz4flex_ctx* c, hipStream_t s) {
     return 0;
 }
 
-// the encoders for independent blocks: throughput mode (own parse, any block length) or the reference-exact one
-// shared (nullable): ONE dictionary for every block (lz4flex_compress_batch_shared_dict; a has no dictionaries and no flags then)
-// set (nullable, not with shared): a dictionary per block out of a prepared set (lz4flex_compress_batch_dict_set; a has no dictionaries
-// and no flags then); set_base: the set's allocation
-static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a_, bool big, hipStream_t s, const SharedDictArgs* shared = nullptr,
-                               const DictSetArgs* set = nullptr, const uint8_t* set_base = nullptr) {
-    hipError_t le;
-    int rc;
-    CompressArgs a = a_;
-    // "compress_mode" 2 (high) encodes independent blocks; a call with dictionaries takes its dictionary form with "compress_high_dict" 1
-    // and the throughput encoder otherwise; one without dictionaries and with flags takes the same form with "compress_high_linked" 1, the
-    // LZ4FLEX_BLOCK_HISTORY bytes in front of a block as its dictionary
-    const bool with_dict = a.dict_len || shared || set;
-    const bool with_history = !with_dict && a.flags && c->comp_high_linked;
-    const int mode = c->comp_mode == 2 ? ((with_dict && !c->comp_high_dict) ? 0 : 2) : c->comp_mode;
-    if (shared) c->shared_counted = mode == 0;
-    if (set && mode == 2) c->set_counted = nullptr;              // (the set's counter is the throughput encoder's)
-    if (mode == 2) {
-        // its scratch is the (otherwise idle) throughput encoder's workspace, ordered across streams like that encoder's own launches;
-        // a workgroup holds most of a CU's LDS, so one per CU (wave_wgs is two per CU) and no more than the workspace has slices for
-        if ((rc = wave_ws_acquire(c, s))) return rc;
-        if (with_history)
-            le = launch_compress_high_linked(a, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2, (uint32_t)c->comp_depth, s);
-        else if (with_dict) {
-            HighDictArgs d{};
-            if (shared) { d.shared = shared->dict; d.shared_len = shared->len; }
-            if (set) { d.has_set = 1u; d.set = *set; }
-            le = launch_compress_high_dict(a, d, c->comp_high_digest != 0, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2,
-                                           (uint32_t)c->comp_depth, s);
-        } else
-        le = launch_compress_high(a, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs), c->wave_wgs / 2, (uint32_t)c->comp_depth, s);
-        const hipError_t re = c->wave.release(s);
-        if (le == hipSuccess) le = re;
-    } else if (mode == 0) {
-        if ((rc = wave_ws_acquire(c, s))) return rc;
-        if (set) HIP_TRY(hipMemsetAsync(set->counter, 0, 4, s));      // ("debug_dict_set_items" speaks of this call)
-        CompressArgs aw = a;
-        aw.slide = c->comp_sliding == 2 ? 49152u : (c->comp_sliding == 1 ? 32768u : 0u);
-        // sub-windows (lz4_compress_wave.hip Item::sub): batches that leave at least half / three quarters of the persistent workgroups
-        // without a block cut their blocks of <= 64 KiB into 2 / 3 / 4 items each
-        aw.sub = c->comp_det ? 1u : c->comp_sub != 0 ? (uint32_t)c->comp_sub
-                                  : (a.n * 4u <= (uint32_t)c->wave_wgs ? 4u : (a.n * 3u <= (uint32_t)c->wave_wgs ? 3u : (a.n * 2u <= (uint32_t)c->wave_wgs ? 2u : 1u)));
-        le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0, shared, set);
-        if (le == hipSuccess) HIP_TRY(c->wave.release(s));
-    } else {
-        // (blocks with a dictionary are left alone by both launches below and encoded by the chain kernel behind them)
-        // (a shared dictionary: every block has it, the chain kernel encodes them all)
-        // (a set: which blocks have one is in the table -- the block encoder runs piece by piece below, behind the arrays it reads)
-        const int enc_bits = c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant);
-        le = (shared || set) ? hipSuccess : launch_compress(a, enc_bits, s);
-        if (le == hipSuccess && !big && a.n && !shared && !set) {
-            hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, a.in_len, a.n, a.out_len, a.status,
-                               a.dict_len);
-            le = hipGetLastError();
-        }
-        if (le == hipSuccess && (a.dict_len || shared || set) && a.n) {
-            // one-block chains, their records in the (otherwise idle) throughput encoder's workspace: no allocation, ordered across
-            // streams like the encoder's own launches; batches larger than the workspace holds records for run in pieces
-            if ((rc = wave_ws_acquire(c, s))) return rc;
-            const size_t per = sizeof(lz4flex_chain_block) + 4u + (shared ? 12u : 0u) + (set ? 16u : 0u);
-            const uint32_t piece = (uint32_t)std::min<size_t>(compress_wave_workspace_bytes(c->wave_wgs) / per - 64u, 0x40000000u);
-            lz4flex_chain_block* rec = (lz4flex_chain_block*)c->wave_ws;
-            uint32_t* cnt = (uint32_t*)((uint8_t*)c->wave_ws + align_up(sizeof(lz4flex_chain_block) * (size_t)piece, 256));
-            if (shared) {
-                // the one dictionary as per-block arrays of one piece (every piece reads the same ones), behind the records in the workspace
-                uint64_t* soff = (uint64_t*)((uint8_t*)cnt + align_up(4u * (size_t)piece, 256));
-                uint32_t* slen = (uint32_t*)((uint8_t*)soff + align_up(8u * (size_t)piece, 256));
-                const uint32_t m = std::min<uint32_t>(piece, a.n);
-                hipLaunchKernelGGL(lz4flex_fill_shared_dict_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, soff, slen, m, shared->len);
-                le = hipGetLastError();
-                a.dict_base = shared->dict; a.dict_off = soff; a.dict_len = slen;
-            }
-            uint32_t* sflg = nullptr;
-            if (set) {
-                // a set: the per-block arrays of one piece, filled from the table in front of every piece, and a flag word per block
-                uint64_t* soff = (uint64_t*)((uint8_t*)cnt + align_up(4u * (size_t)piece, 256));
-                uint32_t* slen = (uint32_t*)((uint8_t*)soff + align_up(8u * (size_t)piece, 256));
-                sflg = (uint32_t*)((uint8_t*)slen + align_up(4u * (size_t)piece, 256));
-                a.dict_base = set_base; a.dict_off = soff; a.dict_len = slen;
-            }
-            for (uint32_t b0 = 0; b0 < a.n && le == hipSuccess; b0 += piece) {
-                const uint32_t m = std::min<uint32_t>(piece, a.n - b0);
-                const uint32_t d0 = (shared || set) ? 0u : b0;
-                const dim3 grid((m + 255u) / 256u), block(256);
-                if (set) {
-                    // the piece's arrays, then what the launches in front of the loop do for the other batches: the block encoder
-                    // takes the piece's blocks without a dictionary
-                    CompressArgs p = a;
-                    p.in_off += b0; p.in_len += b0; p.flags = nullptr; p.out_off += b0; p.out_cap += b0; p.out_len += b0; p.status += b0; p.n = m;
-                    DictSetArgs ps = *set;
-                    ps.dict_id += b0;
-                    hipLaunchKernelGGL(lz4flex_fill_set_dict_kernel, grid, block, 0, s, ps, set_base, m, (uint64_t*)a.dict_off, (uint32_t*)a.dict_len, sflg);
-                    le = hipGetLastError();
-                    if (le == hipSuccess) le = launch_compress(p, enc_bits, s);
-                    if (le == hipSuccess && !big) {
-                        hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, grid, block, 0, s, p.in_len, m, p.out_len, p.status, p.dict_len);
-                        le = hipGetLastError();
-                    }
-                    if (le != hipSuccess) break;
-                }
-                hipLaunchKernelGGL(lz4flex_dict_chain_records_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, a.in_off + b0, a.in_len + b0,
-                                   set ? sflg : (a.flags ? a.flags + b0 : nullptr), a.dict_off + d0, a.dict_len + d0, m, rec, cnt, a.out_len + b0, a.status + b0);
-                le = hipGetLastError();
-                if (le == hipSuccess)
-                    le = launch_compress_chain(a.in_base, rec, nullptr, cnt, m, a.out_base, a.out_off + b0, a.out_cap + b0, a.out_len + b0,
-                                               a.status + b0, nullptr, s, a.dict_base);
-            }
-            // (also behind a failed launch: whatever was enqueued on the workspace is ordered)
-            const hipError_t re = c->wave.release(s);
-            if (le == hipSuccess) le = re;
-        }
-    }
-    if (le != hipSuccess) return hip_fail(le, "kernel launch");
-    return 0;
+// Which encoder a compress call takes -- the effective mode and, for mode 2, the high encoder's form.  "compress_mode" 2 (high) encodes
+// independent blocks: a call with dictionaries (per-block ones, a shared one or a set) takes the dictionary form with
+// "compress_high_dict" 1 and the throughput encoder otherwise; one without dictionaries and with flags takes the history form with
+// "compress_high_linked" 1 (the LZ4FLEX_BLOCK_HISTORY bytes in front of a block are its dictionary) and the plain form otherwise.
+enum class HighForm { Plain, Dict, History };
+struct Encoder { int mode; HighForm form; };
+static Encoder encoder_for(const lz4flex_ctx* c, const CompressArgs& a, const DictSource& d) {
+    if (c->comp_mode != 2) return {c->comp_mode, HighForm::Plain};
+    if (a.dict_len || d.shared || d.has_set) return c->comp_high_dict ? Encoder{2, HighForm::Dict} : Encoder{0, HighForm::Plain};
+    return {2, a.flags && c->comp_high_linked ? HighForm::History : HighForm::Plain};
+}
+
+static int launched(hipError_t le) { return le != hipSuccess ? hip_fail(le, "kernel launch") : 0; }
+
+// mode 2: its scratch is the (otherwise idle) throughput encoder's workspace, ordered across streams like that encoder's own launches;
+// a workgroup holds most of a CU's LDS, so one per CU (wave_wgs is two per CU) and no more than the workspace has slices for
+static int compress_high(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, HighForm form, hipStream_t s) {
+    if (const int rc = wave_ws_acquire(c, s)) return rc;
+    const size_t bytes = compress_wave_workspace_bytes(c->wave_wgs);
+    const int wgs = c->wave_wgs / 2;
+    const uint32_t depth = (uint32_t)c->comp_depth;
+    hipError_t le = form == HighForm::History ? launch_compress_high_linked(a, c->wave_ws, bytes, wgs, depth, s)
+                    : form == HighForm::Dict  ? launch_compress_high_dict(a, d, c->comp_high_digest != 0, c->wave_ws, bytes, wgs, depth, s)
+                                              : launch_compress_high(a, c->wave_ws, bytes, wgs, depth, s);
+    const hipError_t re = c->wave.release(s);
+    return launched(le == hipSuccess ? re : le);
+}
+
+// mode 0: the throughput encoder (own parse, any block length)
+static int compress_throughput(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, hipStream_t s) {
+    if (const int rc = wave_ws_acquire(c, s)) return rc;
+    if (d.has_set) HIP_TRY(hipMemsetAsync(d.set.counter, 0, 4, s));      // ("debug_dict_set_items" speaks of this call)
+    CompressArgs aw = a;
+    aw.slide = c->comp_sliding == 2 ? 49152u : (c->comp_sliding == 1 ? 32768u : 0u);
+    // sub-windows (lz4_compress_wave.hip Item::sub): batches that leave at least half / three quarters of the persistent workgroups
+    // without a block cut their blocks of <= 64 KiB into 2 / 3 / 4 items each
+    aw.sub = c->comp_det ? 1u : c->comp_sub != 0 ? (uint32_t)c->comp_sub
+                              : (a.n * 4u <= (uint32_t)c->wave_wgs ? 4u : (a.n * 3u <= (uint32_t)c->wave_wgs ? 3u : (a.n * 2u <= (uint32_t)c->wave_wgs ? 2u : 1u)));
+    SharedDictArgs sh{};
+    sh.dict = d.shared; sh.len = d.shared_len; sh.use = (uint32_t)c->comp_shared;
+    const hipError_t le = launch_compress_wave(aw, c->wave_ws, c->wave_wgs, s, c->wave_prof, c->comp_carry_wait != 0, d.shared ? &sh : nullptr,
+                                               d.has_set ? &d.set : nullptr);
+    if (le == hipSuccess) HIP_TRY(c->wave.release(s));
+    return launched(le);
+}
+
+// mode 1: the reference-exact encoder (lz4_compress.hip launch_compress_exact).  A call with dictionaries builds its chain records in
+// the (otherwise idle) throughput encoder's workspace: no allocation, ordered across streams like that encoder's own launches
+static int compress_exact(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, bool big, hipStream_t s) {
+    const int enc_bits = c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant);
+    if (!((a.dict_len || d.shared || d.has_set) && a.n)) return launched(launch_compress_exact(a, d, enc_bits, big, nullptr, 0, 0, s));
+    if (const int rc = wave_ws_acquire(c, s)) return rc;
+    const hipError_t le = launch_compress_exact(a, d, enc_bits, big, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs),
+                                                (uint32_t)c->exact_dict_piece, s);
+    const hipError_t re = c->wave.release(s);                 // (also behind a failed launch: whatever was enqueued on the workspace is ordered)
+    return launched(le == hipSuccess ? re : le);
+}
+
+// the encoders for independent blocks.  d: the batch's shared dictionary or set (a has no dictionaries and no flags then), or neither;
+// set: the handle behind d.set (null without one)
+static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, const lz4flex_dict_set* set, bool big, hipStream_t s) {
+    const Encoder enc = encoder_for(c, a, d);
+    // ("debug_shared_dict_items" / "debug_dict_set_items" read the throughput encoder's counters: another encoder has nothing to show)
+    if (d.shared) c->shared_counted = enc.mode == 0;
+    if (set) c->set_counted = enc.mode == 0 ? set : nullptr;
+    if (enc.mode == 2) return compress_high(c, a, d, enc.form, s);
+    if (enc.mode == 0) return compress_throughput(c, a, d, s);
+    return compress_exact(c, a, d, big, s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -518,14 +403,10 @@ static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
     a.in_base = b.in_base; a.in_off = b.in_off; a.in_len = b.in_len; a.flags = b.flags;
     a.out_base = b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.out_len = b.out_len; a.status = b.status; a.n = b.n;
     if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
-    if (b.set) {
-        const DictSetArgs ds = set_args_of(c, b);
-        c->set_counted = c->comp_mode != 1 ? b.set : nullptr;       // ("compress_mode" 2: a set takes the throughput encoder unless "compress_high_dict" is 1)
-        return launch_compress_any(c, a, b.big, b.stream, nullptr, &ds, b.set->mem);
-    }
-    SharedDictArgs sh{};
-    sh.dict = b.shared_dict; sh.len = b.shared_len; sh.use = (uint32_t)c->comp_shared;
-    return launch_compress_any(c, a, b.big, b.stream, b.shared_dict && b.shared_len ? &sh : nullptr);
+    DictSource d{};
+    if (b.set) { d.has_set = 1u; d.set = set_args_of(c, b); }
+    else if (b.shared_dict && b.shared_len) { d.shared = b.shared_dict; d.shared_len = b.shared_len; }
+    return launch_compress_any(c, a, d, b.set, b.big, b.stream);
 }
 
 static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
@@ -736,6 +617,7 @@ const Setting SETTINGS[] = {
     // (what "compress_subwindows" 0 decides by: n * 4 <= this -> 4, n * 3 <= this -> 3, n * 2 <= this -> 2)
     {"compress_workgroups", &lz4flex_ctx::wave_wgs, read_only, false},
     {"debug_chain_giveup", &lz4flex_ctx::chain_giveup, is_count, true},
+    {"debug_exact_dict_piece", &lz4flex_ctx::exact_dict_piece, is_count, true},    // tests/test_gpu_exact_dict_pieces.py: more than one piece
     {"debug_fail_next_batch", &lz4flex_ctx::fail_next_batch, is_count, true},      // tests/test_gpu_sharded_native.py: one rank's call-level failure
 };
 const Setting* find_setting(const char* key) {
@@ -1859,16 +1741,13 @@ int64_t lz4flex_compress_into_with_dict(const uint8_t* in, size_t in_len, uint8_
             return (int64_t)olen;
         }
     }
-    // compress_into_sink_with_dict, compress.rs:554-568: table kind from the UNtruncated dictionary length,
-    // then init_dict keeps the last 64 KiB (:572-574)
-    const bool h4 = dict_len + in_len < 65535u;
-    if (dict_len > 65536u) { dict += dict_len - 65536u; dict_len = 65536u; }
-    std::vector<uint8_t> buf(dict_len + in_len + 16);
-    if (dict_len) memcpy(buf.data(), dict, dict_len);
-    if (in_len) memcpy(buf.data() + dict_len, in, in_len);
-    lz4flex_chain_block b{};
-    b.in_off = dict_len; b.dict_off = 0; b.in_len = (uint32_t)in_len; b.in_pos = 0; b.dict_len = (uint32_t)dict_len;
-    b.so = (uint32_t)dict_len; b.repos = 0; b.flags = (h4 ? 1u : 0u) | 2u;
+    // compress_into_sink_with_dict, compress.rs:554-568, as a one-block chain (dict_chain_record): the staging buffer holds the
+    // dictionary's last 64 KiB and the input behind them
+    const size_t kept = std::min<size_t>(dict_len, 65536u);
+    std::vector<uint8_t> buf(kept + in_len + 16);
+    if (kept) memcpy(buf.data(), dict + (dict_len - kept), kept);
+    if (in_len) memcpy(buf.data() + kept, in, in_len);
+    const lz4flex_chain_block b = dict_chain_record<lz4flex_chain_block>(kept, (uint32_t)in_len, kept, dict_len);
     const uint32_t first = 0, count = 1;
     const uint32_t cap = (uint32_t)std::min<size_t>(out_cap, 0xFFFFFFFFull);
     uint32_t olen = 0;

@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "lz4_device.h"
 
 namespace lz4flex_dev {
@@ -810,6 +812,75 @@ hipError_t launch_compress_chain(const uint8_t* in_base, const void* blocks, con
                        reinterpret_cast<const ChainBlock*>(blocks), chain_first, chain_count, n_chains, out_base, out_off,
                        out_cap, out_len, status, tbl_state, dict_base);
     return hipGetLastError();
+}
+
+// MEM_DEVICE batches without LZ4FLEX_MEM_BIG_BLOCKS: the u16-table kernel is only right for blocks of <= 64 KiB and the host cannot
+// see the device-resident lengths, so a block that breaks the promise is flagged on the device (its bytes would be a valid block, but
+// not lz4_flex's) instead of passing silently.  dict_len: as in lz4_compress_blocks_kernel -- not zero = the chain kernel's block
+__global__ void lz4flex_flag_long_blocks_kernel(const uint32_t* in_len, uint32_t n, uint32_t* out_len, int32_t* status, const uint32_t* dict_len) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n && in_len[b] > 65536u && (dict_len == nullptr || dict_len[b] == 0u)) { status[b] = LZ4FLEX_DEV_E_INVALID_ARG; out_len[b] = 0u; }
+}
+
+// Blocks b0 .. b0 + m of a batch with dictionaries: block b0 + i's one-block chain for the chain kernel (rec[i], dict_off counted from
+// dict_base), built here because a DEVICE batch's lengths are device memory.  count[i] = 1 for a block the chain kernel encodes, 0 for
+// the others and for refused ones: block_dict's refusals, or an input the u32 stream positions cannot hold (status
+// LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written).  not_plain (nullable; a set, whose blocks' dictionaries are in no array): not
+// zero = the block has a dictionary or a refused id -- what the block encoder reads as the piece's dict_len.
+__global__ void lz4flex_dict_chain_records_kernel(const CompressArgs a, const DictSource d, const uint8_t* dict_base, uint32_t b0, uint32_t m,
+                                                  ChainBlock* rec, uint32_t* count, uint32_t* not_plain) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t b = b0 + i, len = a.in_len[b];
+    const BlockDict k = block_dict(a, d, b);
+    const bool refuse = k.refused || (k.len != 0u && len > 0x7FFFFFFFu), chain = !refuse && k.len != 0u;
+    if (refuse) { a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG; a.out_len[b] = 0u; }
+    if (chain) rec[i] = dict_chain_record<ChainBlock>(a.in_off[b], len, (uint64_t)(k.end - dict_base), k.len);
+    count[i] = chain ? 1u : 0u;
+    if (not_plain) not_plain[i] = (refuse || chain) ? 1u : 0u;
+}
+
+hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int enc_bits, bool big, void* ws, size_t ws_bytes,
+                                 uint32_t max_piece, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    const bool set = d.has_set != 0u, shared = !set && d.shared != nullptr;
+    // blocks without a dictionary: the block encoder, which leaves the others alone, and the long-block flag.  Per-block dictionaries:
+    // dict_len says which those are, for the whole batch at once; a shared dictionary: none; a set: piece by piece, below
+    const auto plain = [&](const CompressArgs& p) {
+        hipError_t e = launch_compress(p, enc_bits, s);
+        if (e == hipSuccess && !big) {
+            hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((p.n + 255u) / 256u), dim3(256), 0, s, p.in_len, p.n, p.out_len, p.status, p.dict_len);
+            e = hipGetLastError();
+        }
+        return e;
+    };
+    hipError_t e = (set || shared) ? hipSuccess : plain(a);
+    if (!set && !shared && a.dict_len == nullptr) return e;
+    // one-block chains: per block of a piece a record, a count and -- a set -- the block encoder's word
+    const auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+    const size_t per = sizeof(ChainBlock) + 4u + (set ? 4u : 0u);
+    if (ws == nullptr || ws_bytes / per <= 64u) return hipErrorInvalidValue;
+    uint32_t piece = (uint32_t)std::min<size_t>(ws_bytes / per - 64u, 0x40000000u);
+    if (max_piece) piece = std::min(piece, max_piece);
+    ChainBlock* rec = (ChainBlock*)ws;
+    uint32_t* cnt = (uint32_t*)((uint8_t*)ws + up(sizeof(ChainBlock) * (size_t)piece));
+    uint32_t* not_plain = set ? (uint32_t*)((uint8_t*)cnt + up(4u * (size_t)piece)) : nullptr;
+    const uint8_t* dict_base = set ? (const uint8_t*)d.set.table : (shared ? d.shared : a.dict_base);
+    for (uint32_t b0 = 0; b0 < a.n && e == hipSuccess; b0 += piece) {
+        const uint32_t m = std::min<uint32_t>(piece, a.n - b0);
+        hipLaunchKernelGGL(lz4flex_dict_chain_records_kernel, dim3((m + 255u) / 256u), dim3(256), 0, s, a, d, dict_base, b0, m, rec, cnt, not_plain);
+        e = hipGetLastError();
+        if (e == hipSuccess && set) {
+            CompressArgs p = a;
+            p.in_off += b0; p.in_len += b0; p.flags = nullptr; p.out_off += b0; p.out_cap += b0; p.out_len += b0; p.status += b0; p.n = m;
+            p.dict_len = not_plain;
+            e = plain(p);
+        }
+        if (e == hipSuccess)
+            e = launch_compress_chain(a.in_base, rec, nullptr, cnt, m, a.out_base, a.out_off + b0, a.out_cap + b0, a.out_len + b0, a.status + b0,
+                                      nullptr, s, dict_base);
+    }
+    return e;
 }
 
 // MODE 0: the encoder wavefront alone (everything read from HBM/L2, output written inline).

@@ -405,10 +405,11 @@ __global__ void __launch_bounds__(THREADS) lz4_compress_high_kernel(const Compre
 // The dictionary form ("compress_high_dict" 1; the bytes: tests/sim/high_dict_model.c).  Block b's dictionary is the set's (d.set),
 // else the batch's one (d.shared), else a.dict_*; one of less than 4 bytes is none.  digest (nullable, with d.shared only): the slice
 // lz4_high_digest_kernel filled.
-__global__ void __launch_bounds__(THREADS) lz4_compress_high_dict_kernel(const CompressArgs a, const HighDictArgs d, uint8_t* ws, const uint8_t* digest,
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_dict_kernel(const CompressArgs a, const DictSource d, uint8_t* ws, const uint8_t* digest,
                                                                          uint32_t depth) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        // (block_dict's rule, lz4_device.h, written out: with the lookup in its place the compiler gives this kernel another instruction stream)
         const uint8_t* dict = nullptr;
         uint32_t dl = 0u;
         bool ok = true;
@@ -499,7 +500,7 @@ hipError_t launch_compress_high_linked(const CompressArgs& a, void* workspace, s
     return hipGetLastError();
 }
 
-hipError_t launch_compress_high_dict(const CompressArgs& a, const HighDictArgs& d, bool use_digest, void* workspace, size_t workspace_bytes,
+hipError_t launch_compress_high_dict(const CompressArgs& a, const DictSource& d, bool use_digest, void* workspace, size_t workspace_bytes,
                                      int max_workgroups, uint32_t depth, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     // the digest is a property of the batch's ONE dictionary; it takes the last slice of the workspace

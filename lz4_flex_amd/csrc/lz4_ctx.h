@@ -125,6 +125,7 @@ struct lz4flex_ctx {
     size_t plan_cap = 0;
     lz4flex_dev::OrderedWs plan;
     int chain_giveup = 0;         // tests: block chain_giveup - 1 of the next chained decode batches gives up without an error (the ordered second pass decodes it and everything behind it)
+    int exact_dict_piece = 0;     // tests: the reference-exact encoder's dictionary calls build their chain records in pieces of at most this many blocks (0: as many as the workspace holds)
     // many frames at once (frame_many.cpp): device scratch of the calls that run to completion before they return (compressed staging,
     // descriptor arrays, staged host buffers).  Grow-only, a hipMalloc when a larger job arrives; freed with the context.
     void* many_ws[4] = {nullptr, nullptr, nullptr, nullptr};

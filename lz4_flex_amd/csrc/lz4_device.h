@@ -80,7 +80,9 @@ struct CompressArgs {
     uint32_t sub;              // throughput encoder: 2 / 4 = blocks of at most 64 KiB are cut into that many sub-windows (small batches: lz4_compress_wave.hip Item::sub); else one window
     // nullable (all three or none): per-block external dictionaries (lz4flex_compress_batch_ex); dict_len[i] == 0 = block i has none.
     // Throughput encoder: the dictionary's last min(dict_len, 32 KiB) bytes are the block's history (lz4_compress_wave.hip Item);
-    // reference-exact encoder: lz4_compress_blocks_kernel leaves blocks with a dictionary alone (the chain kernel encodes them)
+    // reference-exact encoder: lz4_compress_blocks_kernel reads dict_len alone and leaves a block with dict_len[i] != 0 to the chain
+    // kernel (launch_compress_exact; for a dictionary set dict_len is that launcher's one word per block).  Which dictionary a block
+    // has when the batch has a shared one or a set: DictSource / block_dict below
     const uint8_t* dict_base;
     const uint64_t* dict_off;
     const uint32_t* dict_len;
@@ -110,7 +112,7 @@ struct DictSetRec {
 // (status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written)
 constexpr uint32_t DICT_ID_NONE = 0xFFFFFFFFu;
 struct DictSetArgs {
-    const DictSetRec* table;
+    const DictSetRec* table;   // the front of the set's one allocation: every record's bytes lie behind it (launch_compress_exact's offsets count from here)
     const uint32_t* dict_id;
     uint32_t k;
     uint32_t use;              // throughput encoder: 0 = no item starts from a digest ("compress_shared_dict" 0)
@@ -125,6 +127,45 @@ __device__ __forceinline__ bool dict_set_find(const DictSetArgs& st, uint32_t b,
     const DictSetRec r = st.table[id];
     dict = r.end - r.kept; dl = r.kept;
     return true;
+}
+
+// The dictionaries of a batch, for the encoders: a set (has_set), else the batch's one dictionary (shared, shared_len bytes of device
+// memory), else -- neither -- CompressArgs::dict_* where the batch has them.
+struct DictSource {
+    const uint8_t* shared;
+    uint32_t shared_len;
+    uint32_t has_set;
+    DictSetArgs set;
+};
+// Block b's dictionary: `end` is behind its last byte, `kept` of the bytes in front of `end` exist (a set keeps at most 64 KiB),
+// `len` is the caller's length, untruncated; len == 0 = the block has none.  refused: an id the set does not have, or a per-block
+// dictionary together with a non-zero flag word (frame flags or history bits) -- status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written.
+struct BlockDict { bool refused; const uint8_t* end; uint32_t kept, len; };
+__device__ __forceinline__ BlockDict block_dict(const CompressArgs& a, const DictSource& d, uint32_t b) {
+    BlockDict r{false, nullptr, 0u, 0u};
+    if (d.has_set) {
+        const uint32_t id = d.set.dict_id[b];
+        if (id == DICT_ID_NONE) return r;
+        if (id >= d.set.k) { r.refused = true; return r; }
+        const DictSetRec t = d.set.table[id];
+        r.end = t.end; r.kept = t.kept; r.len = t.len;
+    } else if (d.shared) {
+        r.end = d.shared + d.shared_len; r.kept = r.len = d.shared_len;
+    } else if (a.dict_len) {
+        r.kept = r.len = a.dict_len[b];
+        r.end = a.dict_base + a.dict_off[b] + r.len;
+        r.refused = r.len != 0u && a.flags != nullptr && a.flags[b] != 0u;
+    }
+    return r;
+}
+// The one-block chain of compress_into_with_dict (compress.rs:554-583) as a chain record (Rec: lz4_compress.hip ChainBlock, the header's
+// lz4flex_chain_block): the table kind from the UNtruncated dictionary length, the dictionary's last 64 KiB kept, input_stream_offset =
+// their length.  dict_end: the offset behind the dictionary's last byte, in whatever dict_off indexes.
+template <typename Rec>
+__host__ __device__ inline Rec dict_chain_record(uint64_t in_off, uint32_t in_len, uint64_t dict_end, uint64_t dict_len) {
+    const uint32_t kept = dict_len > 65536u ? 65536u : (uint32_t)dict_len;
+    // {in_off, dict_off, in_len, in_pos, dict_len, so, repos, flags}
+    return Rec{in_off, dict_end - kept, in_len, 0u, kept, kept, 0u, (dict_len + in_len < 65535u ? 1u : 0u) | 2u};
 }
 
 // plan / replay decoder (lz4_decompress_plan.hip, lz4_decompress_replay.hip; record format: lz4_plan_common.h)
@@ -207,17 +248,11 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
 size_t compress_high_workspace_bytes(int n_workgroups);
 hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, hipStream_t s);
 // its dictionary form ("compress_high_dict" 1): the bytes are tests/sim/high_dict_model.c's for (block, dictionary, depth).  Block b's
-// dictionary is the set's (has_set), else the batch's one (shared, shared_len), else a.dict_* (with a.flags[b] != 0: refused like a
-// refused id -- status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written); a block without one, or with one of less than 4 bytes, gets
-// the plain form's bytes.  use_digest (the shared dictionary only): a kernel in front sorts the dictionary tail's positions once, into
-// the last slice of `workspace`, and every block sorts its own positions alone; else every block sorts the tail's with its own.
-struct HighDictArgs {
-    const uint8_t* shared;
-    uint32_t shared_len;
-    uint32_t has_set;
-    DictSetArgs set;
-};
-hipError_t launch_compress_high_dict(const CompressArgs& a, const HighDictArgs& d, bool use_digest, void* workspace, size_t workspace_bytes,
+// dictionary is block_dict(a, d, b)'s (a refused block: status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written); a block without one,
+// or with one of less than 4 bytes, gets the plain form's bytes.  use_digest (the shared dictionary only): a kernel in front sorts the
+// dictionary tail's positions once, into the last slice of `workspace`, and every block sorts its own positions alone; else every block
+// sorts the tail's with its own.
+hipError_t launch_compress_high_dict(const CompressArgs& a, const DictSource& d, bool use_digest, void* workspace, size_t workspace_bytes,
                                      int max_workgroups, uint32_t depth, hipStream_t s);
 // its history form ("compress_high_linked" 1): the dictionary form with block b's dictionary = the a.flags[b] >> 8 bytes of its own stream
 // in front of it (LZ4FLEX_BLOCK_HISTORY), readable at a.in_base + a.in_off[b] - h; the flag word's low byte and a's dictionaries are not
@@ -239,6 +274,13 @@ hipError_t launch_compress_chain(const uint8_t* in_base, const void* blocks, con
                                  const uint32_t* chain_count, uint32_t n_chains, uint8_t* out_base,
                                  const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
                                  uint32_t* tbl_state, hipStream_t s, const uint8_t* dict_base = nullptr);
+// compress_mode 1 (reference-exact), independent blocks: launch_compress(a, enc_bits) for the blocks without a dictionary and -- !big:
+// the caller promised blocks of at most 64 KiB -- INVALID_ARG for those among them that are longer; then, where the batch has
+// dictionaries (a.dict_* or d), every block with one as a one-block chain of the chain kernel (dict_chain_record; refused: block_dict's
+// refusals and in_len > 0x7FFFFFFF).  The records are built on the device in ws (ws_bytes bytes, read with dictionaries only), in pieces
+// of as many blocks as it holds, at most max_piece of them (0: no limit; tests).
+hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int enc_bits, bool big, void* ws, size_t ws_bytes,
+                                 uint32_t max_piece, hipStream_t s);
 
 hipError_t launch_xxh32_batch(const uint8_t* base, const uint64_t* off, const uint32_t* len, uint32_t n, uint32_t seed,
                               uint32_t* out, hipStream_t s);

@@ -207,7 +207,7 @@ SETTINGS = ["decompress_lanes", "compress_mode", "compress_subwindows", "compres
             "decompress_blocks_per_wg", "decompress_variant", "decompress_second_pass", "decompress_pcd_pair", "compress_carry_wait",
             "compress_sliding_window", "compress_variant", "compress_lanes", "size_scan_serial", "compress_shared_dict",
             "decompress_shared_dict"]
-HOOKS = ["debug_chain_giveup", "debug_fail_next_batch"]            # set only
+HOOKS = ["debug_chain_giveup", "debug_fail_next_batch", "debug_exact_dict_piece"]            # set only
 READ_ONLY = ["compress_workgroups", "debug_shared_dict_items"]     # (dispatch_threshold_<i>, decoder_config_<i>: the two tests above)
 
 
