@@ -6,10 +6,11 @@
 //                    copies the results back (run_host_small: the one-transfer-each-way form for a few small blocks, which the
 //                    lz4_flex-shaped scalar calls -- 1-block batches -- take);
 //   run_device_batch MEM_DEVICE: the caller's BatchCall as it is, on the caller's stream;
-//   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode (the
-//                    DictSource set-up; launch_compress_any: encoder_for's choice, then that mode's launches) and launch_decode (the chain bracket and the choice between the
-//                    shared-dictionary, the partial (with or without a dictionary), the fast and the reference-order decoder; launch_decompress_fast picks the kernel by batch
-//                    shape, launch_redo is the second pass behind every first-pass decoder).
+//   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode
+//                    (launch_compress_any: encoder_for's choice, then that mode's launches) and launch_decode (the chain bracket, then
+//                    launch_decompress_form for a batch with a dictionary source or targets, else the fast or the reference-order
+//                    decoder; launch_decompress_fast picks the kernel by batch shape, launch_redo is the second pass behind every
+//                    first-pass decoder); dict_source_of describes the batch's dictionaries (DictSource) for both.
 // The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
 // DeviceGuard, Layout, GrowBuf) are in lz4_ctx.h; the integer settings are one table (SETTINGS) that lz4flex_set_tuning and
 // lz4flex_get_tuning walk.
@@ -91,28 +92,16 @@ static hipError_t chain_ws_begin(lz4flex_ctx* c, uint32_t n, hipStream_t s) {
 static hipError_t chain_ws_end(lz4flex_ctx* c, hipStream_t s) { return c->chain.release(s); }
 
 // The second pass behind a first-pass decoder: the blocks it left marked DECODE_REDO (errors, sinks too small, shapes it does not
-// take) are decoded again in the reference's order of checks.  "decompress_second_pass" 0 (tests) leaves them marked.
-enum class Redo {
-    Blocks,       // launch_decompress: side by side
-    Chain,        // launch_decompress_chain_redo: a chained batch's marked blocks depend on each other -- in chain order
-    SharedDict,   // launch_decompress_shared_dict: with the batch's one dictionary
-    DictSet,      // launch_decompress_dict_set: with each block's dictionary out of the batch's set
-    Partial,      // launch_decompress_partial: out_cap is a target (lz4flex_decompress_batch_partial)
-    PartialSharedDict,   // launch_decompress_partial_shared_dict: a target, with the batch's one dictionary
-    PartialDictSet,      // launch_decompress_partial_dict_set: a target, with each block's dictionary out of the batch's set
-};
-static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, Redo how = Redo::Blocks, const uint8_t* dict = nullptr,
-                              uint32_t dict_len = 0, const DictSetArgs* set = nullptr) {
+// take) are decoded again in the reference's order of checks, side by side, by the reference-order entry of the batch's form (d, partial).
+// chain: a chained batch's marked blocks depend on each other -- in chain order.  "decompress_second_pass" 0 (tests) leaves
+// them marked.
+static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, bool chain = false, const DictSource& d = DictSource{},
+                              bool partial = false) {
     if (!c->dec_second_pass) return hipSuccess;
     DecompressArgs r = a;
     r.only_status = DECODE_REDO;
-    if (how == Redo::Chain) return launch_decompress_chain_redo(r, s);
-    if (how == Redo::DictSet) return launch_decompress_dict_set(r, *set, s);
-    if (how == Redo::SharedDict) return launch_decompress_shared_dict(r, dict, dict_len, s);
-    if (how == Redo::Partial) return launch_decompress_partial(r, s);
-    if (how == Redo::PartialSharedDict) return launch_decompress_partial_shared_dict(r, dict, dict_len, s);
-    if (how == Redo::PartialDictSet) return launch_decompress_partial_dict_set(r, *set, s);
-    return launch_decompress(r, c->dec_lanes, s);
+    if (chain) return launch_decompress_chain_redo(r, s);
+    return launch_decompress(r, d, partial, c->dec_lanes, s);
 }
 
 static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a_, hipStream_t s, bool big_blocks = false) {
@@ -195,11 +184,11 @@ static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a
             if (e != hipSuccess) return e;
             a.pair_ws = nullptr;
         }
-        return launch_redo(c, a, s, a.chain_done ? Redo::Chain : Redo::Blocks);
+        return launch_redo(c, a, s, a.chain_done != nullptr);
     }
     if (v == 13) {
         // a wavefront per block, a lane per sequence (lz4_decompress_seq.hip); irregular blocks go to the reference-order kernel
-        const hipError_t e = launch_decompress_seq(a, DECODE_REDO, s);
+        const hipError_t e = launch_decompress_seq(a, DictSource{}, false, DECODE_REDO, s);
         return e != hipSuccess ? e : launch_redo(c, a, s);
     }
 #ifdef LZ4FLEX_TOOLS
@@ -212,45 +201,18 @@ static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a
     return launch_decompress_split(a, s, c->dec_blocks_per_wg);
 }
 
-// lz4flex_decompress_batch_shared_dict: every block of `a` (no per-block dictionaries, no prefix) against the ONE dictionary.  A wavefront
-// per block and a lane per sequence at every n (never worse than sixteen serial lanes per block); the blocks it marks are decoded again
-// in the reference's order with the dictionary.  "decompress_shared_dict" 0 / "decompress_variant" 1: that order for every block.
-static hipError_t launch_decompress_shared(lz4flex_ctx* c, const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
-    if (!c->dec_shared || c->dec_variant == 1) return launch_decompress_shared_dict(a, dict, dict_len, s);
-    const hipError_t e = launch_decompress_seq_dict(a, dict, dict_len, DECODE_REDO, s);
-    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::SharedDict, dict, dict_len);
-}
-
-// lz4flex_decompress_batch_dict_set: launch_decompress_shared with the dictionary looked up per block; the same two settings send every
-// block through the reference-order kernel
-static hipError_t launch_decompress_set(lz4flex_ctx* c, const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
-    if (!c->dec_shared || c->dec_variant == 1) return launch_decompress_dict_set(a, set, s);
-    const hipError_t e = launch_decompress_seq_dict_set(a, set, DECODE_REDO, s);
-    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::DictSet, nullptr, 0, &set);
-}
-
-// lz4flex_decompress_batch_partial: a.out_cap holds the targets.  The sequence decoder's partial form at every n (its work is bounded by
-// the target, not by the block); the blocks it marks are decoded again in the reference's order, up to their target.
-// "decompress_partial" 0 / "decompress_variant" 1: that order for every block.
-static hipError_t launch_decompress_partial_any(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s) {
-    if (!c->dec_partial || c->dec_variant == 1) return launch_decompress_partial(a, s);
-    const hipError_t e = launch_decompress_seq_partial(a, DECODE_REDO, s);
-    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::Partial);
-}
-
-// lz4flex_decompress_batch_partial_shared_dict / _dict_set: a.out_cap holds the targets and every block has the batch's one dictionary /
-// the one its id names.  The sequence decoder's form with both (Dec<G, true, true>) when "decompress_partial" and
-// "decompress_shared_dict" are both 1 and "decompress_variant" is not 1; the blocks it marks are decoded again in the reference's order,
-// with the dictionary, up to their target.  Otherwise that order for every block.
-static hipError_t launch_decompress_partial_shared(lz4flex_ctx* c, const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
-    if (!c->dec_partial || !c->dec_shared || c->dec_variant == 1) return launch_decompress_partial_shared_dict(a, dict, dict_len, s);
-    const hipError_t e = launch_decompress_seq_partial_dict(a, dict, dict_len, DECODE_REDO, s);
-    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::PartialSharedDict, dict, dict_len);
-}
-static hipError_t launch_decompress_partial_set(lz4flex_ctx* c, const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
-    if (!c->dec_partial || !c->dec_shared || c->dec_variant == 1) return launch_decompress_partial_dict_set(a, set, s);
-    const hipError_t e = launch_decompress_seq_partial_dict_set(a, set, DECODE_REDO, s);
-    return e != hipSuccess ? e : launch_redo(c, a, s, Redo::PartialDictSet, nullptr, 0, &set);
+// The batches with a dictionary source or targets (lz4flex_decompress_batch_shared_dict / _dict_set / _partial / _partial_shared_dict /
+// _partial_dict_set; `a` has no per-block dictionaries, no prefix and no chain): form (d, partial).  A wavefront per block and a lane per
+// sequence at every n (never worse than sixteen serial lanes per block; a partial form's work is bounded by the target, not by the
+// block), and the blocks it marks decoded again in the reference's order, with the dictionary, up to their target -- unless
+// "decompress_variant" is 1, or the form has a dictionary source and "decompress_shared_dict" is 0, or it is partial and
+// "decompress_partial" is 0: then that order for every block.
+static hipError_t launch_decompress_form(lz4flex_ctx* c, const DecompressArgs& a, const DictSource& d, bool partial, hipStream_t s) {
+    const bool has_dict = d.has_set || d.shared;
+    const bool first_pass = c->dec_variant != 1 && (c->dec_shared || !has_dict) && (c->dec_partial || !partial);
+    if (!first_pass) return launch_decompress(a, d, partial, c->dec_lanes, s);
+    const hipError_t e = launch_decompress_seq(a, d, partial, DECODE_REDO, s);
+    return e != hipSuccess ? e : launch_redo(c, a, s, false, d, partial);
 }
 
 // MEM_HOST batches whose results are sparse in the output span (compress: ~15 KB used of every 72 KB stride):
@@ -394,8 +356,12 @@ static BatchCall batch_of(bool compress, const void* in_base, const uint64_t* in
     return b;
 }
 
-static DictSetArgs set_args_of(lz4flex_ctx* c, const BatchCall& b) {
-    return DictSetArgs{b.set->table, b.dict_id, b.set->k, (uint32_t)c->comp_shared, b.set->counter};
+// where the batch's dictionaries come from, either direction (a shared pointer with length 0 is no dictionary: the plain path)
+static DictSource dict_source_of(lz4flex_ctx* c, const BatchCall& b) {
+    DictSource d{};
+    if (b.set) { d.has_set = 1u; d.set = DictSetArgs{b.set->table, b.dict_id, b.set->k, (uint32_t)c->comp_shared, b.set->counter}; }
+    else if (b.shared_dict && b.shared_len) { d.shared = b.shared_dict; d.shared_len = b.shared_len; }
+    return d;
 }
 
 static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
@@ -403,10 +369,7 @@ static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
     a.in_base = b.in_base; a.in_off = b.in_off; a.in_len = b.in_len; a.flags = b.flags;
     a.out_base = b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.out_len = b.out_len; a.status = b.status; a.n = b.n;
     if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
-    DictSource d{};
-    if (b.set) { d.has_set = 1u; d.set = set_args_of(c, b); }
-    else if (b.shared_dict && b.shared_len) { d.shared = b.shared_dict; d.shared_len = b.shared_len; }
-    return launch_compress_any(c, a, d, b.set, b.big, b.stream);
+    return launch_compress_any(c, a, dict_source_of(c, b), b.set, b.big, b.stream);
 }
 
 static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
@@ -424,15 +387,10 @@ static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
         a.n_chains = b.n_chains;
         a.debug_giveup = (uint32_t)c->chain_giveup;
     }
+    const DictSource d = dict_source_of(c, b);
+    if (b.partial) a.detail = nullptr;
     hipError_t le;
-    if (b.partial) {
-        a.detail = nullptr;
-        if (b.set) le = launch_decompress_partial_set(c, a, set_args_of(c, b), s);
-        else if (b.shared_dict && b.shared_len) le = launch_decompress_partial_shared(c, a, b.shared_dict, b.shared_len, s);
-        else le = launch_decompress_partial_any(c, a, s);
-    }
-    else if (b.set) le = launch_decompress_set(c, a, set_args_of(c, b), s);
-    else if (b.shared_dict && b.shared_len) le = launch_decompress_shared(c, a, b.shared_dict, b.shared_len, s);
+    if (b.partial || d.has_set || d.shared) le = launch_decompress_form(c, a, d, b.partial, s);
     // "decompress_variant" 1 and blocks with dictionaries: the reference-order kernel (a chain has no such form)
     else le = ((c->dec_variant != 1 || b.chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, b.big) : launch_decompress(a, c->dec_lanes, s);
     if (chain) (void)chain_ws_end(c, s);                     // (also behind a failed launch: whatever was enqueued is ordered)

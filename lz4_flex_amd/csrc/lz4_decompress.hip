@@ -252,42 +252,13 @@ __global__ void __launch_bounds__(256) lz4_decompress_blocks_kernel(DecompressAr
     }
 }
 
-// lz4flex_decompress_batch_partial in the reference's order: decode_block<16, false, true> with out_cap[b] as block b's target.  The
-// definition of the entry's results ("decompress_partial" 0, "decompress_variant" 1: every block) and the second pass behind the
-// sequence decoder's partial form (only_status != 0: the blocks it marked).  No detail: there is no OutputTooSmall.
-__global__ void __launch_bounds__(256) lz4_decompress_partial_kernel(DecompressArgs a) {
-    constexpr int G = 16;
-    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t b = tid / G;
-    const uint32_t g = tid % G;
-    if (b >= a.n) return;
-    if (a.only_status != 0 && a.status[b] != a.only_status) return;
-    uint32_t produced = 0u;
-    uint64_t expected = 0u;
-    const int32_t st = decode_block<G, false, true>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, a.out_cap[b], nullptr, 0u, g,
-                                                    &produced, &expected);
-    if (g == 0u) {
-        a.status[b] = st;
-        a.out_len[b] = st == 0 ? produced : 0u;
-    }
-}
-
-hipError_t launch_decompress_partial(const DecompressArgs& a, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_decompress_partial_kernel, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// lz4flex_decompress_batch_shared_dict: decode_block<16, true> with ONE dictionary for every block -- no per-block dictionary arrays, no
-// workspace, any n.  only_status != 0: the second pass behind the sequence decoder's dictionary form (the blocks it marked, in the
-// reference's check order, WITH the dictionary); 0: every block ("decompress_shared_dict" 0, "decompress_variant" 1).
-// lz4flex_decompress_batch_dict_set: the same with block b's dictionary looked up in a set (SET; dict / dict_len are not read then).  A
-// block without one decodes with dict_len 0; a refused id is status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written.
-// PARTIAL (lz4flex_decompress_batch_partial_shared_dict / _dict_set): out_cap[b] is block b's target -- decode_block<16, true, true>, the
-// definition of those entries' results and the second pass behind the sequence decoder's form; no detail.
-template <bool SET, bool PARTIAL = false>
-__global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(DecompressArgs a, const uint8_t* dict, uint32_t dict_len, DictSetArgs set) {
+// Every form of a batch but the plain one (lz4_device.h: SRC and dict_find say where block b's dictionary comes from, PARTIAL that
+// out_cap[b] is its target) in the reference's order, sixteen lanes a block: decode_block<16, SRC is not NoDict, PARTIAL> -- no per-block
+// dictionary arrays, no prefix, no workspace, any n.  The definition of those entries' results (only_status 0: every block) and the
+// second pass behind the sequence decoder's form (only_status != 0: the blocks it marked).  A block of a set without a dictionary decodes
+// with dict_len 0; a refused id is status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written.  PARTIAL has no detail: there is no OutputTooSmall.
+template <class SRC, bool PARTIAL>
+__global__ void __launch_bounds__(256) lz4_decompress_form_kernel(DecompressArgs a, SRC src) {
     constexpr int G = 16;
     const uint32_t tid = blockIdx.x * 256u + threadIdx.x;
     const uint32_t b = tid / G;
@@ -297,10 +268,12 @@ __global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(Decompr
     const uint32_t cap = a.out_cap[b];
     uint32_t produced = 0u;
     uint64_t expected = 0u;
-    bool found = true;
-    if constexpr (SET) found = dict_set_find(set, b, dict, dict_len);
-    const int32_t st = !found ? LZ4FLEX_DEV_E_INVALID_ARG
-                              : decode_block<G, true, PARTIAL>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g, &produced, &expected);
+    const uint8_t* dict;
+    uint32_t dict_len;
+    const int32_t st = !dict_find(src, b, dict, dict_len)
+                           ? LZ4FLEX_DEV_E_INVALID_ARG
+                           : decode_block<G, !__is_same(SRC, NoDict), PARTIAL>(a.in_base + a.in_off[b], a.in_len[b], a.out_base + a.out_off[b], 0u, cap, dict, dict_len, g,
+                                                                                &produced, &expected);
     if (g == 0u) {
         a.status[b] = st;
         a.out_len[b] = st == 0 ? produced : 0u;
@@ -309,34 +282,6 @@ __global__ void __launch_bounds__(256) lz4_decompress_shared_dict_kernel(Decompr
             a.detail[2u * b + 1u] = st == LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL ? (uint64_t)cap : 0u;
         }
     }
-}
-
-hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (dict == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel<false>, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, dict, dict_len, DictSetArgs{});
-    return hipGetLastError();
-}
-
-hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(lz4_decompress_shared_dict_kernel<true>, dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, (const uint8_t*)nullptr, 0u, set);
-    return hipGetLastError();
-}
-
-hipError_t launch_decompress_partial_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (dict == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((lz4_decompress_shared_dict_kernel<false, true>), dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, dict, dict_len, DictSetArgs{});
-    return hipGetLastError();
-}
-
-hipError_t launch_decompress_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((lz4_decompress_shared_dict_kernel<true, true>), dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, (const uint8_t*)nullptr, 0u, set);
-    return hipGetLastError();
 }
 
 // Second pass behind a CHAINED batch (Linked frames: block i's prefix is what blocks 0..i-1 of the batch write).  The marked blocks
@@ -415,6 +360,25 @@ hipError_t launch_decompress(const DecompressArgs& a, int lanes_per_block, hipSt
         case 64: return d ? launch_g<64, true>(a, s) : launch_g<64, false>(a, s);
 #endif
         default: return hipErrorInvalidValue;
+    }
+}
+
+template <class SRC, bool PARTIAL>
+static hipError_t launch_form(const DecompressArgs& a, const SRC& src, hipStream_t s) {
+    hipLaunchKernelGGL((lz4_decompress_form_kernel<SRC, PARTIAL>), dim3((a.n + 15u) / 16u), dim3(256), 0, s, a, src);
+    return hipGetLastError();
+}
+
+hipError_t launch_decompress(const DecompressArgs& a, const DictSource& d, bool partial, int lanes_per_block, hipStream_t s) {
+    if (a.n == 0u) return hipSuccess;
+    if (!decode_form_ok(a, d, partial)) return hipErrorInvalidValue;
+    switch ((d.has_set ? 4 : d.shared != nullptr ? 2 : 0) + (partial ? 1 : 0)) {
+        case 0: return launch_decompress(a, lanes_per_block, s);
+        case 1: return launch_form<NoDict, true>(a, NoDict{}, s);
+        case 2: return launch_form<OneDict, false>(a, OneDict{d.shared, d.shared_len}, s);
+        case 3: return launch_form<OneDict, true>(a, OneDict{d.shared, d.shared_len}, s);
+        case 4: return launch_form<DictSetArgs, false>(a, d.set, s);
+        default: return launch_form<DictSetArgs, true>(a, d.set, s);
     }
 }
 

@@ -24,17 +24,17 @@
 //     written back 16 bytes per lane.  Sequences that do not fit a lane (literal runs > 64, matches > 273 bytes or overlapping
 //     their source, far matches > 64, anything with more than one length byte) are executed ALONE by the whole wavefront
 //     (exact_seq: decompress.rs:334-443 for one sequence of any shape) and cut the chunk in front of them.
-// PARTIAL form (lz4flex_decompress_batch_partial: the first target[b] bytes of block b; source tag Partial, no dictionary, no prefix): the
+// PARTIAL form (lz4flex_decompress_batch_partial: the first target[b] bytes of block b; PARTIAL with NoDict, no prefix): the
 // block's "capacity" is its TARGET and reaching it is the normal end.  setup_chunk cuts a chunk in front of the first sequence that
 // reaches or crosses the target -- before any of the chunk's checks are looked at, so nothing behind the stop can be an error -- and that
 // sequence is executed alone by the wavefront (exact_seq_partial: the reference's checks in their order, the copy clipped to the target,
 // status 0, no "a match is followed by a token" check for a match that ends at the target).  run_chunks and the tile loop leave through
 // `stopped`, which is not "the block ended": no tile behind the one that holds the stop is staged or walked -- the work is the target's,
 // not the block's.  The walk (lz4_seq_walk.h, unchanged) still covers the WHOLE tile that holds the stop before a chunk runs: if it finds
-// no chain in the bytes behind the stop (X_ERR), the block is handed back like any irregular one, and lz4_decompress_partial_kernel
+// no chain in the bytes behind the stop (X_ERR), the block is handed back like any irregular one, and lz4_decompress_form_kernel
 // (lz4_decompress.hip), which never looks behind the stop, decides it -- correct, and slower for that block only.  Nothing is stored at or
 // behind out + target: the window is written back in whole 16-byte units below OP and byte by byte up to OP, and OP never passes the target.
-// PARTIAL with DICT (lz4flex_decompress_batch_partial_shared_dict / _dict_set; source tags PartialOneDict / PartialDictSet): Dec<G, true,
+// PARTIAL with DICT (lz4flex_decompress_batch_partial_shared_dict / _dict_set; PARTIAL with OneDict / DictSetArgs): Dec<G, true,
 // true>.  The two forms compose with three adjustments.  (1) Positions are virtual, so the crossing sequence's offset check is
 // offset > OP - lo(), as in exact_seq; its copies (coop_match / big_match: vp, vbyte, pos_copy) pick their path by the CLIPPED length.
 // (2) The target is biased by PV like a capacity -- but a capacity that does not fit the position space may be cut (the block then ends
@@ -658,40 +658,27 @@ __device__ __forceinline__ bool run_chunks(Dec<G, DICT, PARTIAL>& D, uint32_t t0
 #else
 #define LZ4S_WAVES_ATTR
 #endif
-// Where the blocks' dictionaries come from.  OneDict: every block of the batch has the ONE dictionary dict[0, dict_len) (device memory,
-// dict_len != 0), and none has a prefix.  DictSetArgs (lz4_device.h): block b has the dictionary its id names in a prepared set -- or none
-// (dl = 0, so PV = LO = 0: the block decodes as it does without the dictionary form), or a refused id.
-// Partial: no dictionary and no prefix, and a.out_cap[b] is block b's TARGET (see the head of the file).  PartialOneDict / PartialDictSet:
-// a target, and the dictionary as OneDict / DictSetArgs give it.
-struct NoDict {};
-struct OneDict { const uint8_t* dict; uint32_t dict_len; };
-struct Partial {};
-struct PartialOneDict { const uint8_t* dict; uint32_t dict_len; };
-struct PartialDictSet { DictSetArgs set; };
-template <class SRC> constexpr bool SRC_DICT = !__is_same(SRC, NoDict) && !__is_same(SRC, Partial);
-template <class SRC> constexpr bool SRC_PARTIAL = __is_same(SRC, Partial) || __is_same(SRC, PartialOneDict) || __is_same(SRC, PartialDictSet);
-__device__ __forceinline__ const DictSetArgs& set_of(const DictSetArgs& s) { return s; }
-__device__ __forceinline__ const DictSetArgs& set_of(const PartialDictSet& s) { return s.set; }
-template <class G, class SRC>
+// SRC: where the blocks' dictionaries come from (lz4_device.h).  OneDict: none has a prefix.  DictSetArgs: block b has the dictionary its
+// id names in a prepared set -- or none (dl = 0, so PV = LO = 0: the block decodes as it does without the dictionary form), or a refused
+// id.  PARTIAL: no prefix, and a.out_cap[b] is block b's TARGET (see the head of the file).
+template <class G, class SRC, bool PARTIAL>
 __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(DecompressArgs a, int32_t redo_code, SRC src) {
-    constexpr bool DICT = SRC_DICT<SRC>;
-    constexpr bool PARTIAL = SRC_PARTIAL<SRC>;
+    constexpr bool DICT = !__is_same(SRC, NoDict);
     extern __shared__ __attribute__((aligned(16))) uint8_t seq_lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     if (b >= a.n) return;
     [[maybe_unused]] const uint8_t* dict = nullptr;
     [[maybe_unused]] uint32_t dict_len = 0u;
-    if constexpr (__is_same(SRC, OneDict) || __is_same(SRC, PartialOneDict)) { dict = src.dict; dict_len = src.dict_len; }
-    if constexpr (__is_same(SRC, DictSetArgs) || __is_same(SRC, PartialDictSet)) {
-        if (!dict_set_find(set_of(src), b, dict, dict_len)) {
-            if (lane == 0u) {
-                a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG;
-                a.out_len[b] = 0u;
-                if (a.detail) { a.detail[2u * b] = 0u; a.detail[2u * b + 1u] = 0u; }
-            }
-            return;
+    if (!dict_find(src, b, dict, dict_len)) {
+        if (lane == 0u) {
+            a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG;
+            a.out_len[b] = 0u;
+            if (a.detail) { a.detail[2u * b] = 0u; a.detail[2u * b + 1u] = 0u; }
         }
+        return;
+    }
+    if constexpr (__is_same(SRC, DictSetArgs)) {
         // (the wavefront's one record, said to be uniform: PV / LO / dv below are scalars as they are with the launch's one dictionary)
         const uint64_t dp = (uint64_t)(uintptr_t)dict;
         dict = (const uint8_t*)(uintptr_t)(((uint64_t)uni((uint32_t)(dp >> 32)) << 32) | uni((uint32_t)dp));
@@ -798,67 +785,27 @@ __global__ void __launch_bounds__(64) LZ4S_WAVES_ATTR lz4_decompress_seq_kernel(
 
 }  // namespace sq
 
-// Blocks without dictionary (a prefix in the sink is fine, round 6; one dictionary for the whole batch: launch_decompress_seq_dict).  Irregular blocks get status `redo_code`; the caller runs launch_decompress with
-// only_status = redo_code behind this launch.
-hipError_t launch_decompress_seq(const DecompressArgs& a, int32_t redo_code, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (a.dict_base != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;       // (a prefix -- out_pos -- is fine: see the kernel)
+// Every form of a batch (lz4_device.h): irregular blocks get status `redo_code`; the caller runs launch_decompress with the same
+// (d, partial) and only_status = redo_code behind this launch.
+template <class SRC, bool PARTIAL>
+static hipError_t launch_seq(const DecompressArgs& a, int32_t redo_code, const SRC& src, hipStream_t s) {
     typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
     static_assert(G::LDS <= 65536u, "the default limit of dynamic LDS: no function attribute to set per device");
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::NoDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::NoDict{});
+    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, SRC, PARTIAL>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, src);
     return hipGetLastError();
 }
 
-// Every block against the ONE dictionary dict[0, dict_len) (lz4flex_decompress_batch_shared_dict): the dictionary form of the kernel, no
-// per-block dictionary arrays, no prefix, no chain.  Irregular blocks get status `redo_code`; the caller runs
-// launch_decompress_shared_dict with only_status = redo_code behind this launch.
-hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s) {
+hipError_t launch_decompress_seq(const DecompressArgs& a, const DictSource& d, bool partial, int32_t redo_code, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
-    if (dict == nullptr || dict_len == 0u || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::OneDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::OneDict{dict, dict_len});
-    return hipGetLastError();
-}
-
-// lz4flex_decompress_batch_partial: a.out_cap[b] is block b's target (the partial form of the kernel: no dictionary, no prefix, no
-// chain).  Irregular blocks get status `redo_code`; the caller runs launch_decompress_partial with only_status = redo_code behind this launch.
-hipError_t launch_decompress_seq_partial(const DecompressArgs& a, int32_t redo_code, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::Partial>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::Partial{});
-    return hipGetLastError();
-}
-
-// Every block against the dictionary its id names in a set (lz4flex_decompress_batch_dict_set): the dictionary form with the
-// dictionary looked up per block.  Irregular blocks get status `redo_code`; the caller runs launch_decompress_dict_set with only_status
-// = redo_code behind this launch.  A refused id gets its final status here.
-hipError_t launch_decompress_seq_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, DictSetArgs>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, set);
-    return hipGetLastError();
-}
-
-// lz4flex_decompress_batch_partial_shared_dict / _dict_set: a.out_cap[b] is block b's target AND every block has the one dictionary / the
-// dictionary its id names (the kernel's form with both: no prefix, no chain).  Irregular blocks get status `redo_code`; the caller runs
-// launch_decompress_partial_shared_dict / launch_decompress_partial_dict_set with only_status = redo_code behind this launch.  A refused
-// id gets its final status here.
-hipError_t launch_decompress_seq_partial_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (dict == nullptr || dict_len == 0u || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::PartialOneDict>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::PartialOneDict{dict, dict_len});
-    return hipGetLastError();
-}
-
-hipError_t launch_decompress_seq_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s) {
-    if (a.n == 0u) return hipSuccess;
-    if (set.table == nullptr || set.dict_id == nullptr || a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;
-    typedef sq::Geo<LZ4S_R, LZ4S_KEEP> G;
-    hipLaunchKernelGGL((sq::lz4_decompress_seq_kernel<G, sq::PartialDictSet>), dim3(a.n), dim3(64), G::LDS, s, a, redo_code, sq::PartialDictSet{set});
-    return hipGetLastError();
+    if (!decode_form_ok(a, d, partial) || a.dict_base != nullptr || a.chain_done != nullptr) return hipErrorInvalidValue;       // (the plain form: a prefix -- out_pos -- is fine, see the kernel)
+    switch ((d.has_set ? 4 : d.shared != nullptr ? 2 : 0) + (partial ? 1 : 0)) {
+        case 0: return launch_seq<NoDict, false>(a, redo_code, NoDict{}, s);
+        case 1: return launch_seq<NoDict, true>(a, redo_code, NoDict{}, s);
+        case 2: return launch_seq<OneDict, false>(a, redo_code, OneDict{d.shared, d.shared_len}, s);
+        case 3: return launch_seq<OneDict, true>(a, redo_code, OneDict{d.shared, d.shared_len}, s);
+        case 4: return launch_seq<DictSetArgs, false>(a, redo_code, d.set, s);
+        default: return launch_seq<DictSetArgs, true>(a, redo_code, d.set, s);
+    }
 }
 
 }  // namespace lz4flex_dev

@@ -128,9 +128,18 @@ __device__ __forceinline__ bool dict_set_find(const DictSetArgs& st, uint32_t b,
     dict = r.end - r.kept; dl = r.kept;
     return true;
 }
+// The decode kernels' view of where a batch's dictionaries come from, a type per kind (a run-time ladder costs them instructions):
+// NoDict, OneDict -- every block has the ONE dictionary dict[0, dict_len) (device memory, dict_len != 0) -- or DictSetArgs.  dict_find:
+// block b's dictionary whatever the kind, as dict_set_find gives it
+struct NoDict {};
+struct OneDict { const uint8_t* dict; uint32_t dict_len; };
+__device__ __forceinline__ bool dict_find(const NoDict&, uint32_t, const uint8_t*& dict, uint32_t& dl) { dict = nullptr; dl = 0u; return true; }
+__device__ __forceinline__ bool dict_find(const OneDict& o, uint32_t, const uint8_t*& dict, uint32_t& dl) { dict = o.dict; dl = o.dict_len; return true; }
+__device__ __forceinline__ bool dict_find(const DictSetArgs& st, uint32_t b, const uint8_t*& dict, uint32_t& dl) { return dict_set_find(st, b, dict, dl); }
 
-// The dictionaries of a batch, for the encoders: a set (has_set), else the batch's one dictionary (shared, shared_len bytes of device
-// memory), else -- neither -- CompressArgs::dict_* where the batch has them.
+// The dictionaries of a batch, in both directions: a set (has_set), else the batch's one dictionary (shared, shared_len bytes of device
+// memory), else -- neither -- CompressArgs / DecompressArgs::dict_* where the batch has them.  The encoders' kernels read it
+// (block_dict); for the decoders it is a host-side descriptor that picks the kernel instance (NoDict / OneDict / DictSetArgs above).
 struct DictSource {
     const uint8_t* shared;
     uint32_t shared_len;
@@ -196,34 +205,30 @@ struct PlanArgs {
 size_t plan_slot_words();
 hipError_t launch_plan(const PlanArgs& a, hipStream_t s);
 
+// The decoders in the reference's check order (lz4_decompress.hip): a.only_status 0 = every block, else the marked ones.  The plain
+// form -- DecompressArgs's own per-block dictionaries, prefixes, lanes_per_block lanes a block:
 hipError_t launch_decompress(const DecompressArgs& a, int lanes_per_block, hipStream_t s);
+// A batch's FORM is (d, partial).  d: no dictionary source, ONE dictionary for every block (lz4flex_decompress_batch_shared_dict) or block
+// b's looked up in a set (_dict_set: a block without one decodes in the same launch, a refused id is LZ4FLEX_E_INVALID_ARG, out_len 0,
+// nothing written); OffsetOutOfBounds is offset > produced + dict_len.  partial (lz4flex_decompress_batch_partial*): a.out_cap[b] is block
+// b's TARGET -- the first min(size, target) bytes, no OutputTooSmall, no detail, nothing stored at or behind out_off[b] + target.
+// The form (no source, not partial) is the plain one above; every other form has sixteen lanes a block whatever lanes_per_block says.
+hipError_t launch_decompress(const DecompressArgs& a, const DictSource& d, bool partial, int lanes_per_block, hipStream_t s);
+// one block per wavefront, one LANE PER SEQUENCE (lz4_decompress_seq.hip, round 6), every form: speculative part walks give the token
+// positions, 64 sequences at a time are placed by a prefix sum and copied by their lanes; irregular blocks are left with status
+// redo_code (a refused id gets its final status here).  The second pass of a form is launch_decompress with the same (d, partial) and
+// only_status = redo_code.
+hipError_t launch_decompress_seq(const DecompressArgs& a, const DictSource& d, bool partial, int32_t redo_code, hipStream_t s);
+// What both refuse (hipErrorInvalidValue): a dictionary source or partial together with a.dict_base, a.out_pos or a.chain_done; a shared
+// pointer with length 0; a set without table or dict_id.  (The plain sequence form refuses a.dict_base and a.chain_done: a prefix is fine there.)
+inline bool decode_form_ok(const DecompressArgs& a, const DictSource& d, bool partial) {
+    if (!d.has_set && d.shared == nullptr && !partial) return true;
+    if (a.dict_base != nullptr || a.out_pos != nullptr || a.chain_done != nullptr) return false;
+    if (d.has_set) return d.set.table != nullptr && d.set.dict_id != nullptr;
+    return d.shared == nullptr || d.shared_len != 0u;
+}
 // the second pass of a CHAINED batch: the blocks whose status equals a.only_status, one after the other in chain order (one wavefront)
 hipError_t launch_decompress_chain_redo(const DecompressArgs& a, hipStream_t s);
-// one block per wavefront, one LANE PER SEQUENCE (lz4_decompress_seq.hip, round 6): speculative part walks give the token positions,
-// 64 sequences at a time are placed by a prefix sum and copied by their lanes; irregular blocks are left with status redo_code for a
-// second pass of launch_decompress (only_status = redo_code), which decodes them in the reference's check order
-hipError_t launch_decompress_seq(const DecompressArgs& a, int32_t redo_code, hipStream_t s);
-// the same with ONE dictionary dict[0, dict_len) (device memory, dict_len != 0) for every block of the batch: the kernel's dictionary
-// form (no per-block dictionary arrays, no prefix, no chain); the second pass is launch_decompress_shared_dict with only_status = redo_code
-hipError_t launch_decompress_seq_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s);
-// lz4_decompress.hip's decode_block<16, true> with that one dictionary: a.only_status 0 = every block, else the marked ones
-hipError_t launch_decompress_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s);
-// lz4flex_decompress_batch_dict_set: the two launches above with block b's dictionary looked up in a set (DictSetArgs); a block without
-// one decodes in the same launch, a refused id gets its status from whichever of the two sees the block first
-hipError_t launch_decompress_seq_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s);
-hipError_t launch_decompress_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s);
-// lz4flex_decompress_batch_partial: a.out_cap[b] is block b's TARGET -- the first min(size, target) bytes of every block, no OutputTooSmall,
-// no detail, nothing stored at or behind out_off[b] + target.  The sequence decoder's partial form (irregular blocks are left with
-// status redo_code), and decode_block<16, false, true> in the reference's order: a.only_status 0 = every block, else the marked ones
-hipError_t launch_decompress_seq_partial(const DecompressArgs& a, int32_t redo_code, hipStream_t s);
-hipError_t launch_decompress_partial(const DecompressArgs& a, hipStream_t s);
-// lz4flex_decompress_batch_partial_shared_dict / _dict_set: the same with ONE dictionary for the batch / block b's dictionary out of a set;
-// OffsetOutOfBounds is offset > produced + dict_len.  The sequence decoder's form with both (a refused id gets its final status there), and
-// decode_block<16, true, true>: a.only_status 0 = every block, else the marked ones
-hipError_t launch_decompress_seq_partial_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, int32_t redo_code, hipStream_t s);
-hipError_t launch_decompress_seq_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, int32_t redo_code, hipStream_t s);
-hipError_t launch_decompress_partial_shared_dict(const DecompressArgs& a, const uint8_t* dict, uint32_t dict_len, hipStream_t s);
-hipError_t launch_decompress_partial_dict_set(const DecompressArgs& a, const DictSetArgs& set, hipStream_t s);
 hipError_t launch_decompress_split(const DecompressArgs& a, hipStream_t s, int blocks_per_wg = 0);   // parser / copier wavefronts, no dict/prefix
 // parser -> emitter -> quad wavefronts (lz4_decompress_fused.hip: the split decoder's parser, the replay decoder's copy engine, no dict/prefix);
 // blocks of 512 KiB or more are left with status redo_code for a second pass of launch_decompress.  -DLZ4FLEX_TOOLS builds only (round 6)

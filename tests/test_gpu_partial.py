@@ -1,5 +1,5 @@
 """GPU (-m gpu): lz4flex_decompress_batch_partial -- the first target[i] bytes of every block, by the sequence decoder's partial form
-(lz4_decompress_seq.hip) and by the reference-order form behind it (lz4_decompress.hip lz4_decompress_partial_kernel).
+(lz4_decompress_seq.hip) and by the reference-order form behind it (lz4_decompress.hip lz4_decompress_form_kernel<NoDict, true>).
 
 Checker: tests/partial_model.py (the entry's contract in Python, pinned to the oracle by tests/test_partial_model.py) for status, out_len
 and bytes; for valid blocks also the oracle's own bytes, cut at the target.  Every sink is exactly `target` bytes between canaries: a
