@@ -7,10 +7,10 @@
 //                    lz4_flex-shaped scalar calls -- 1-block batches -- take);
 //   run_device_batch MEM_DEVICE: the caller's BatchCall as it is, on the caller's stream;
 //   launch_batch     ONE place that turns a BatchCall of device pointers into CompressArgs / DecompressArgs: launch_encode
-//                    (launch_compress_any: encoder_for's choice, then that mode's launches) and launch_decode (the chain bracket, then
-//                    launch_decompress_form for a batch with a dictionary source or targets, else the fast or the reference-order
-//                    decoder; launch_decompress_fast picks the kernel by batch shape, launch_redo is the second pass behind every
-//                    first-pass decoder); dict_source_of describes the batch's dictionaries (DictSource) for both.
+//                    (launch_compress_any: encode_route's choice, then that mode's launches) and launch_decode (the chain bracket,
+//                    decode_route's choice, then launch_first_pass -- that decoder's workspaces and kernels -- and launch_redo, the
+//                    second pass behind every first-pass decoder); dict_source_of describes the batch's dictionaries (DictSource)
+//                    for both.  Which kernel a batch takes is decided in lz4_route.h alone: pure functions, tested on the CPU.
 // The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
 // DeviceGuard, Layout, GrowBuf) are in lz4_ctx.h; the integer settings are one table (SETTINGS) that lz4flex_set_tuning and
 // lz4flex_get_tuning walk.
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "lz4_batch_entry.h"
 #include "lz4_ctx.h"
 #include "lz4_device.h"
 #include "lz4_plan_common.h"
@@ -75,10 +76,16 @@ static constexpr uint32_t DICT_KEEP = 65536u;
 // compress_variant -> launch_compress mode bits: 1 = encode_block + emitter wave (default), 3 = encode_block alone
 static inline int comp_mode_bits(int v) { return v == 1 ? 0x600 : 0; }
 
-static constexpr uint32_t PCD_MAX_BLOCKS = DISPATCH_PCD_256;     // up to here the default dispatch takes the workgroup decoder
-static constexpr uint32_t CHAIN_WS_BLOCKS = 65536u;      // blocks per chained decode batch (LZ4FLEX_MEM_CHAINED)
+// tools builds (-DLZ4FLEX_TOOLS) hold the plan / replay and the fused decoder.  plan_fits: BlockPlan's word indices are 32-bit,
+// a batch whose plans they cannot address is not the plan / replay decoder's
+#ifdef LZ4FLEX_TOOLS
+static constexpr bool TOOLS_BUILD = true;
+static bool plan_fits(uint32_t n) { return (uint64_t)n * plan_slot_words() <= 0xFFFFFFFFull; }
+#else
+static constexpr bool TOOLS_BUILD = false;
+static bool plan_fits(uint32_t) { return false; }
+#endif
 
-// the decoders for blocks without dictionary / prefix
 // The "done" words of a chained batch are the context's: two chained batches on different streams would clear and poll the same
 // flags (ADVICE r3 for the device path, r4 for the host path: ONE helper for both).  The event is recorded behind the memset too: a
 // call that fails between here and chain_ws_end still leaves ordered work of this stream on the words.
@@ -91,128 +98,79 @@ static hipError_t chain_ws_begin(lz4flex_ctx* c, uint32_t n, hipStream_t s) {
 }
 static hipError_t chain_ws_end(lz4flex_ctx* c, hipStream_t s) { return c->chain.release(s); }
 
+// The launches of a decode route (lz4_route.h decode_route chose it; nothing here decides).  A batch's form is (d, partial).
 // The second pass behind a first-pass decoder: the blocks it left marked DECODE_REDO (errors, sinks too small, shapes it does not
-// take) are decoded again in the reference's order of checks, side by side, by the reference-order entry of the batch's form (d, partial).
-// chain: a chained batch's marked blocks depend on each other -- in chain order.  "decompress_second_pass" 0 (tests) leaves
-// them marked.
-static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s, bool chain = false, const DictSource& d = DictSource{},
-                              bool partial = false) {
-    if (!c->dec_second_pass) return hipSuccess;
+// take) are decoded again in the reference's order of checks, side by side, by the reference-order entry of the batch's form --
+// Redo::ChainOrder: a chained batch's marked blocks depend on each other, in chain order.  "decompress_second_pass" 0
+// (tests) leaves them marked.
+static hipError_t launch_redo(lz4flex_ctx* c, const DecompressArgs& a, Redo redo, const DictSource& d, bool partial, hipStream_t s) {
+    if (redo == Redo::None || !c->dec_second_pass) return hipSuccess;
     DecompressArgs r = a;
     r.only_status = DECODE_REDO;
-    if (chain) return launch_decompress_chain_redo(r, s);
+    if (redo == Redo::ChainOrder) return launch_decompress_chain_redo(r, s);
     return launch_decompress(r, d, partial, c->dec_lanes, s);
 }
 
-static hipError_t launch_decompress_fast(lz4flex_ctx* c, const DecompressArgs& a_, hipStream_t s, bool big_blocks = false) {
-    DecompressArgs a = a_;
-    // 0: by batch shape (lz4_device.h DISPATCH_*; tools/dec_shapes.py measures every decoder on every shape, profiles/r06_decoder_shapes.txt):
-    //   * up to DISPATCH_PCD_256 blocks, or blocks known to be large: a whole WORKGROUP per block, token chain and copies parallel INSIDE the
-    //     block (lz4_decompress_pcd.hip) -- the decoder whose time for a block is not the length of the block's chain: 256 / 512 JSON blocks
-    //     0.14 / 0.23 ms, 256 x 4 MiB log blocks 4.7 ms, one 16 MiB block 14.6 ms;
-    //   * up to DISPATCH_SEQ_MAX blocks: a WAVEFRONT per block, a lane per sequence (lz4_decompress_seq.hip, round 6: it replaced the wave
-    //     decoder and its two-wavefront form, 0.74 / 1.01 ms for 1 024 / 4 096 JSON blocks): 768 / 2 304 / 4 096 / 8 192 / 12 288 JSON blocks
-    //     0.32 / 0.41 / 0.53 / 1.00 / 1.44 ms, 4 096 text / log / incompressible blocks 0.88 / 0.49 / 0.30 ms;
-    //   * larger batches: a LANE per block parses, four lanes copy (lz4_decompress_split.hip): 1.63 - 1.67 ms for any batch of 5 121 ...
-    //     16 384 JSON blocks -- the chain of one block.
-    int v = c->dec_variant != 0 ? c->dec_variant : ((a.n <= PCD_MAX_BLOCKS || big_blocks) ? 7 : (a.n <= DISPATCH_SEQ_MAX ? 13 : 4));
-    const int geo_req = v == 10 ? 2 : (v == 11 ? 3 : 0);  // (an explicit geometry holds for prefix / chained batches too)
-    // prefix mode (Linked frames): the workgroup decoder, or -- a batch whose prefixes are in memory already, not a CHAINED one -- the sequence decoder (round 6)
-    if (a.out_pos != nullptr && v != 8 && !(v == 13 && a.chain_done == nullptr)) v = 7;
-    if ((v == 12 || v == 13) && a.dict_base != nullptr) v = 4;
-    // the workgroup decoder's geometry by batch size (lz4_decompress_pcd.hip GeoMid*: smaller workgroups, more of them per CU); large
-    // blocks and chains keep the full workgroup (a chain is one block at a time, a large block wants the long tiles)
-    int pcd_geo = v == 8 ? 1 : geo_req;
-    if (c->dec_variant == 0 && v == 7 && !big_blocks && a.out_pos == nullptr && a.n > DISPATCH_PCD_1024) pcd_geo = a.n <= DISPATCH_PCD_512 ? 3 : 2;
-    // several chains side by side (chain_prev): one block per chain is runnable at a time, so the CHAINS are what fills the chip --
-    // tools/many_probe.py, 1 GiB of Linked JSON frames of 64 KiB blocks, 1 024 / 256 lanes per block: 256 chains 8.3 / 16.8 ms,
-    // 1 024 chains 8.3 / 6.1, 4 096 chains 9.0 / 6.7, 64 chains 20.5 / 63
-    if (c->dec_variant == 0 && v == 7 && a.chain_prev != nullptr && a.n_chains > DISPATCH_PCD_1024) pcd_geo = a.n_chains <= DISPATCH_PCD_512 ? 3 : 2;
-#ifdef LZ4FLEX_TOOLS
-    if (v == 9 && (uint64_t)a.n * plan_slot_words() > 0xFFFFFFFFull) v = 4;     // BlockPlan's word indices are 32-bit: such a batch takes the split decoder
-    if (v == 9) {
-        // plan / replay: every block is turned into a copy plan (one wavefront per block, everything that is parallel), then the
-        // plans are replayed (four lanes per block, the serial rest); blocks without a plan (errors, sinks too small, oversized) go
-        // to the reference-order kernel
-        const size_t slot = plan_slot_words();
-        const size_t need = (size_t)a.n * (slot * 4u + 32u) + 256u;
-        if (need > c->plan_cap) {
-            if (c->plan.used) { const hipError_t w = hipEventSynchronize(c->plan.done); if (w != hipSuccess) return w; }
-            if (c->plan_ws) (void)hipFree(c->plan_ws);
-            c->plan_ws = nullptr; c->plan_cap = 0;
-            const hipError_t m = hipMalloc((void**)&c->plan_ws, need);
-            if (m != hipSuccess) return m;
-            c->plan_cap = need;
-        }
-        hipError_t e = c->plan.acquire(s);
-        if (e != hipSuccess) return e;
-        PlanArgs pa;
-        pa.in_base = a.in_base; pa.in_off = a.in_off; pa.in_len = a.in_len; pa.out_off = a.out_off; pa.out_cap = a.out_cap;
-        pa.plans = (plan::BlockPlan*)c->plan_ws;
-        pa.words = (uint32_t*)(c->plan_ws + align_up((size_t)a.n * 32u, 256));
-        pa.out_len = a.out_len; pa.status = a.status; pa.n = a.n; pa.slot_words = (uint32_t)slot; pa.redo_code = DECODE_REDO;
-        e = launch_plan(pa, s);
-        if (e != hipSuccess) return e;
-        ReplayArgs ra;
-        ra.in_base = a.in_base; ra.out_base = a.out_base; ra.plans = pa.plans; ra.words = pa.words; ra.n = a.n; ra.max_turns = (uint32_t)(slot / plan::TURN_WORDS) + 2u;
-        e = launch_replay(ra, s);
-        if (e != hipSuccess) return e;
-        e = c->plan.release(s);
-        if (e != hipSuccess) return e;
-        if (a.detail) { const hipError_t z = hipMemsetAsync(a.detail, 0, 16ull * a.n, s); if (z != hipSuccess) return z; }
-        return launch_redo(c, a, s);
+// one block per workgroup (lz4_decompress_pcd.hip).  pair: a parser and a copier workgroup per block; the hand-over workspace is the
+// context's: launches on different streams are ordered by an event, as the encoder's are
+static hipError_t launch_workgroup(lz4flex_ctx* c, DecompressArgs a, const DecodeRoute& r, hipStream_t s) {
+    if (r.pair) {
+        const hipError_t w = c->pcd.acquire(s);
+        if (w != hipSuccess) return w;
+        const hipError_t m = hipMemsetAsync(c->pcd_ws, 0, 64ull * a.n, s);
+        if (m != hipSuccess) return m;
+        a.pair_ws = c->pcd_ws;
     }
-#endif
-    if (v == 7 || v == 8 || v == 10 || v == 11) {
-        // one block per workgroup; blocks it marks (errors, sinks too small) are decoded again in the reference's order
-        bool pair = false;
-        if (v >= 7 && v <= 8 && (c->dec_pcd_pair == 2 || (c->dec_pcd_pair == 1 && big_blocks)) && c->pcd_ws && a.n <= PCD_PAIR_MAX_BLOCKS) {
-            // few LARGE blocks: a parser and a copier workgroup each (half the CUs would idle otherwise; a block of one tile has
-            // nothing to overlap and would only pay the hand-over: 64 KiB JSON blocks 0.144 -> 0.156 ms).  2 = always (tests).  The hand-over workspace is the
-            // context's: launches on different streams are ordered by an event, as the encoder's are
-            const hipError_t w = c->pcd.acquire(s);
-            if (w != hipSuccess) return w;
-            const hipError_t m = hipMemsetAsync(c->pcd_ws, 0, 64ull * a.n, s);
-            if (m != hipSuccess) return m;
-            a.pair_ws = c->pcd_ws;
-            pair = true;
-        }
-        hipError_t e = launch_decompress_pcd(a, DECODE_REDO, s, pcd_geo);
-        if (e != hipSuccess) return e;
-        if (pair) {
-            e = c->pcd.release(s);
-            if (e != hipSuccess) return e;
-            a.pair_ws = nullptr;
-        }
-        return launch_redo(c, a, s, a.chain_done != nullptr);
-    }
-    if (v == 13) {
-        // a wavefront per block, a lane per sequence (lz4_decompress_seq.hip); irregular blocks go to the reference-order kernel
-        const hipError_t e = launch_decompress_seq(a, DictSource{}, false, DECODE_REDO, s);
-        return e != hipSuccess ? e : launch_redo(c, a, s);
-    }
-#ifdef LZ4FLEX_TOOLS
-    if (v == 12) {
-        // parser -> emitter -> quads (lz4_decompress_fused.hip); oversized blocks go to the reference-order kernel
-        const hipError_t e = launch_decompress_fused(a, DECODE_REDO, s);
-        return e != hipSuccess ? e : launch_redo(c, a, s);
-    }
-#endif
-    return launch_decompress_split(a, s, c->dec_blocks_per_wg);
+    const hipError_t e = launch_decompress_pcd(a, DECODE_REDO, s, r.pcd_geometry);
+    return e == hipSuccess && r.pair ? c->pcd.release(s) : e;
 }
 
-// The batches with a dictionary source or targets (lz4flex_decompress_batch_shared_dict / _dict_set / _partial / _partial_shared_dict /
-// _partial_dict_set; `a` has no per-block dictionaries, no prefix and no chain): form (d, partial).  A wavefront per block and a lane per
-// sequence at every n (never worse than sixteen serial lanes per block; a partial form's work is bounded by the target, not by the
-// block), and the blocks it marks decoded again in the reference's order, with the dictionary, up to their target -- unless
-// "decompress_variant" is 1, or the form has a dictionary source and "decompress_shared_dict" is 0, or it is partial and
-// "decompress_partial" is 0: then that order for every block.
-static hipError_t launch_decompress_form(lz4flex_ctx* c, const DecompressArgs& a, const DictSource& d, bool partial, hipStream_t s) {
-    const bool has_dict = d.has_set || d.shared;
-    const bool first_pass = c->dec_variant != 1 && (c->dec_shared || !has_dict) && (c->dec_partial || !partial);
-    if (!first_pass) return launch_decompress(a, d, partial, c->dec_lanes, s);
-    const hipError_t e = launch_decompress_seq(a, d, partial, DECODE_REDO, s);
-    return e != hipSuccess ? e : launch_redo(c, a, s, false, d, partial);
+#ifdef LZ4FLEX_TOOLS
+// plan / replay: every block is turned into a copy plan (one wavefront per block, everything that is parallel), then the plans are
+// replayed (four lanes per block, the serial rest); blocks without a plan (errors, sinks too small, oversized) are left to the second pass
+static hipError_t launch_plan_replay(lz4flex_ctx* c, const DecompressArgs& a, hipStream_t s) {
+    const size_t slot = plan_slot_words();
+    const size_t need = (size_t)a.n * (slot * 4u + 32u) + 256u;
+    if (need > c->plan_cap) {
+        if (c->plan.used) { const hipError_t w = hipEventSynchronize(c->plan.done); if (w != hipSuccess) return w; }
+        if (c->plan_ws) (void)hipFree(c->plan_ws);
+        c->plan_ws = nullptr; c->plan_cap = 0;
+        const hipError_t m = hipMalloc((void**)&c->plan_ws, need);
+        if (m != hipSuccess) return m;
+        c->plan_cap = need;
+    }
+    hipError_t e = c->plan.acquire(s);
+    if (e != hipSuccess) return e;
+    PlanArgs pa;
+    pa.in_base = a.in_base; pa.in_off = a.in_off; pa.in_len = a.in_len; pa.out_off = a.out_off; pa.out_cap = a.out_cap;
+    pa.plans = (plan::BlockPlan*)c->plan_ws;
+    pa.words = (uint32_t*)(c->plan_ws + align_up((size_t)a.n * 32u, 256));
+    pa.out_len = a.out_len; pa.status = a.status; pa.n = a.n; pa.slot_words = (uint32_t)slot; pa.redo_code = DECODE_REDO;
+    e = launch_plan(pa, s);
+    if (e != hipSuccess) return e;
+    ReplayArgs ra;
+    ra.in_base = a.in_base; ra.out_base = a.out_base; ra.plans = pa.plans; ra.words = pa.words; ra.n = a.n; ra.max_turns = (uint32_t)(slot / plan::TURN_WORDS) + 2u;
+    e = launch_replay(ra, s);
+    if (e != hipSuccess) return e;
+    e = c->plan.release(s);
+    if (e != hipSuccess) return e;
+    return a.detail ? hipMemsetAsync(a.detail, 0, 16ull * a.n, s) : hipSuccess;
+}
+#endif
+
+// the route's decoder over the batch: a first pass that marks what it leaves, or -- DEC_REFERENCE -- every block in the reference's order
+static hipError_t launch_first_pass(lz4flex_ctx* c, const DecompressArgs& a, const DecodeRoute& r, const DictSource& d, bool partial, hipStream_t s) {
+    switch (r.decoder) {
+        case DEC_REFERENCE: return launch_decompress(a, d, partial, c->dec_lanes, s);
+        case DEC_WORKGROUP: return launch_workgroup(c, a, r, s);
+        case DEC_SEQUENCE: return launch_decompress_seq(a, d, partial, DECODE_REDO, s);
+        case DEC_SPLIT: return launch_decompress_split(a, s, c->dec_blocks_per_wg);
+#ifdef LZ4FLEX_TOOLS
+        case DEC_PLAN: return launch_plan_replay(c, a, s);
+        case DEC_FUSED: return launch_decompress_fused(a, DECODE_REDO, s);
+#endif
+        default: return hipErrorInvalidValue;      // (decode_route names no decoder this build lacks)
+    }
 }
 
 // MEM_HOST batches whose results are sparse in the output span (compress: ~15 KB used of every 72 KB stride):
@@ -239,18 +197,6 @@ static int wave_ws_acquire(lz4flex_ctx* c, hipStream_t s) {
     if (!c->wave_ws || !c->wave.done) { g_last_error = "context without encoder workspace"; return -LZ4FLEX_E_INVALID_ARG; }
     HIP_TRY(c->wave.acquire(s));
     return 0;
-}
-
-// Which encoder a compress call takes -- the effective mode and, for mode 2, the high encoder's form.  "compress_mode" 2 (high) encodes
-// independent blocks: a call with dictionaries (per-block ones, a shared one or a set) takes the dictionary form with
-// "compress_high_dict" 1 and the throughput encoder otherwise; one without dictionaries and with flags takes the history form with
-// "compress_high_linked" 1 (the LZ4FLEX_BLOCK_HISTORY bytes in front of a block are its dictionary) and the plain form otherwise.
-enum class HighForm { Plain, Dict, History };
-struct Encoder { int mode; HighForm form; };
-static Encoder encoder_for(const lz4flex_ctx* c, const CompressArgs& a, const DictSource& d) {
-    if (c->comp_mode != 2) return {c->comp_mode, HighForm::Plain};
-    if (a.dict_len || d.shared || d.has_set) return c->comp_high_dict ? Encoder{2, HighForm::Dict} : Encoder{0, HighForm::Plain};
-    return {2, a.flags && c->comp_high_linked ? HighForm::History : HighForm::Plain};
 }
 
 static int launched(hipError_t le) { return le != hipSuccess ? hip_fail(le, "kernel launch") : 0; }
@@ -300,9 +246,11 @@ static int compress_exact(lz4flex_ctx* c, const CompressArgs& a, const DictSourc
 }
 
 // the encoders for independent blocks.  d: the batch's shared dictionary or set (a has no dictionaries and no flags then), or neither;
-// set: the handle behind d.set (null without one)
-static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, const lz4flex_dict_set* set, bool big, hipStream_t s) {
-    const Encoder enc = encoder_for(c, a, d);
+// set: the handle behind d.set (null without one); linked_frame: the frame layer's statement about the call.  Which encoder: lz4_route.h
+static int launch_compress_any(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, const lz4flex_dict_set* set, bool big, bool linked_frame,
+                               hipStream_t s) {
+    const EncodeRoute enc = encode_route(EncodeSettings{c->comp_mode, c->comp_high_dict, c->comp_high_linked},
+                                         EncodeShape{a.dict_len || d.shared || d.has_set, a.flags != nullptr, linked_frame});
     // ("debug_shared_dict_items" / "debug_dict_set_items" read the throughput encoder's counters: another encoder has nothing to show)
     if (d.shared) c->shared_counted = enc.mode == 0;
     if (set) c->set_counted = enc.mode == 0 ? set : nullptr;
@@ -342,6 +290,7 @@ struct BatchCall {
     bool partial = false;                   // the *_partial calls: out_cap holds TARGETS (no detail; with shared_dict or set: the *_partial_shared_dict /
                                             // *_partial_dict_set calls; never with dict_base, a prefix or a chain)
     bool big = false;                       // LZ4FLEX_MEM_BIG_BLOCKS, or -- host batches -- what the lengths say
+    bool linked_frame = false;              // compress: the blocks are a Linked frame's (compress_batch_entry: the frame layer says so)
     hipStream_t stream = nullptr;           // DEVICE batches: the caller's (NULL = HIP's null stream); host batches: the context's
 };
 
@@ -369,7 +318,7 @@ static int launch_encode(lz4flex_ctx* c, const BatchCall& b) {
     a.in_base = b.in_base; a.in_off = b.in_off; a.in_len = b.in_len; a.flags = b.flags;
     a.out_base = b.out_base; a.out_off = b.out_off; a.out_cap = b.out_cap; a.out_len = b.out_len; a.status = b.status; a.n = b.n;
     if (b.dict_base) { a.dict_base = b.dict_base; a.dict_off = b.dict_off; a.dict_len = b.dict_len; }
-    return launch_compress_any(c, a, dict_source_of(c, b), b.set, b.big, b.stream);
+    return launch_compress_any(c, a, dict_source_of(c, b), b.set, b.big, b.linked_frame, b.stream);
 }
 
 static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
@@ -389,10 +338,12 @@ static int launch_decode(lz4flex_ctx* c, const BatchCall& b) {
     }
     const DictSource d = dict_source_of(c, b);
     if (b.partial) a.detail = nullptr;
-    hipError_t le;
-    if (b.partial || d.has_set || d.shared) le = launch_decompress_form(c, a, d, b.partial, s);
-    // "decompress_variant" 1 and blocks with dictionaries: the reference-order kernel (a chain has no such form)
-    else le = ((c->dec_variant != 1 || b.chained) && !a.dict_base) ? launch_decompress_fast(c, a, s, b.big) : launch_decompress(a, c->dec_lanes, s);
+    const DecodeRoute r = decode_route(
+        DecodeSettings{c->dec_variant, c->dec_pcd_pair, c->dec_shared, c->dec_partial, c->pcd_ws != nullptr, TOOLS_BUILD, plan_fits(b.n)},
+        DecodeShape{b.n, b.big, b.out_pos != nullptr, b.chained, b.chain_prev != nullptr, b.n_chains, b.dict_base != nullptr,
+                    d.has_set || d.shared != nullptr, b.partial});
+    hipError_t le = launch_first_pass(c, a, r, d, b.partial, s);
+    if (le == hipSuccess) le = launch_redo(c, a, r.redo, d, b.partial, s);
     if (chain) (void)chain_ws_end(c, s);                     // (also behind a failed launch: whatever was enqueued is ordered)
     return le != hipSuccess ? hip_fail(le, "kernel launch") : 0;
 }
@@ -456,7 +407,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
             }
         }
         if (e == hipSuccess) e = c->wave.create();
-        if (e == hipSuccess) e = hipMalloc((void**)&c->chain_ws, 4u * CHAIN_WS_BLOCKS);
+        if (e == hipSuccess) e = hipMalloc((void**)&c->chain_ws, 4u * CHAIN_MAX_BLOCKS);
         if (e == hipSuccess) e = c->chain.create();
         if (e == hipSuccess) e = c->plan.create();
         if (e == hipSuccess) e = c->pcd.create();
@@ -543,14 +494,7 @@ const Setting SETTINGS[] = {
     {"compress_deterministic", &lz4flex_ctx::comp_det, is_flag, false},
     {"decompress_level_chains", &lz4flex_ctx::dec_level_chains, is_count, false},
     {"decompress_blocks_per_wg", &lz4flex_ctx::dec_blocks_per_wg, [](int v) { return v == 0 || v == 8 || v == 16 || v == 32 || v == 64; }, false},
-    {"decompress_variant", &lz4flex_ctx::dec_variant, [](int v) {
-         if (v != 0 && v != 1 && (v < 4 || v > 13)) return false;
-         if (v == 5 || v == 6) return false;                    // the wave decoder and its two-wavefront form: replaced by 13 in round 6
-#ifndef LZ4FLEX_TOOLS
-         if (v == 9 || v == 12) return false;                   // plan / replay, parser / emitter / quads: tools builds only
-#endif
-         return true;
-     }, false},
+    {"decompress_variant", &lz4flex_ctx::dec_variant, [](int v) { return decoder_variant(v, TOOLS_BUILD) != nullptr; }, false},    // lz4_route.h DECODER_VARIANTS
     {"decompress_second_pass", &lz4flex_ctx::dec_second_pass, is_flag, false},
     {"decompress_pcd_pair", &lz4flex_ctx::dec_pcd_pair, up_to_2, false},
     {"compress_carry_wait", &lz4flex_ctx::comp_carry_wait, is_flag, false},
@@ -592,12 +536,8 @@ bool key_allowed(const char* key) {
     return e && !strcmp(e, "1");
 }
 
-// "<prefix><i>": entry i of a list that ends where the key is refused
-int list_entry(const char* index, const int* t, int n) {
-    const int i = atoi(index);
-    if (i < 0 || i >= n || index[0] < '0' || index[0] > '9') return -LZ4FLEX_E_INVALID_ARG;
-    return t[i];
-}
+// "<prefix><i>": the i of a list that ends where the key is refused (-1: not a number)
+int list_index(const char* index) { return index[0] < '0' || index[0] > '9' ? -1 : atoi(index); }
 
 // "debug_shared_dict_items": the items of the last lz4flex_compress_batch_shared_dict call on this context whose first window started
 // from the digest (0: none yet, the reference-exact mode, "compress_shared_dict" 0); waits for the device
@@ -642,23 +582,19 @@ int lz4flex_set_tuning(lz4flex_ctx* c, const char* key, int value) {
 
 int lz4flex_get_tuning(lz4flex_ctx* c, const char* key) {
     if (!key) return -LZ4FLEX_E_INVALID_ARG;
-    // the batch sizes at which the default decoder dispatch changes kernel or geometry (lz4_device.h), in ascending order; the
-    // list ends where the key is refused.  tests/test_gpu_block.py builds its size matrix from it.
+    // the batch sizes at which the default decoder dispatch changes kernel or geometry (lz4_route.h DISPATCH_THRESHOLDS), in ascending
+    // order; the list ends where the key is refused.  tests/test_gpu_block.py builds its size matrix from it.
     if (!strncmp(key, "dispatch_threshold_", 19)) {
-        const int t[] = {(int)PCD_PAIR_MAX_BLOCKS, (int)DISPATCH_PCD_1024, (int)DISPATCH_PCD_512, (int)DISPATCH_PCD_256, (int)DISPATCH_SEQ_MAX,
-                         (int)DISPATCH_SPLIT_FULL};
-        return list_entry(key + 19, t, (int)(sizeof t / sizeof t[0]));
+        const int i = list_index(key + 19);
+        return i >= 0 && i < (int)(sizeof DISPATCH_THRESHOLDS / sizeof DISPATCH_THRESHOLDS[0]) ? (int)DISPATCH_THRESHOLDS[i] : -LZ4FLEX_E_INVALID_ARG;
     }
     // every decoder configuration this build can be pinned to, as variant * 1000 + parameter ("decompress_lanes" for variant 1,
-    // "decompress_blocks_per_wg" for variant 4, else 0); the list ends where the key is refused.  ONE list: tests/test_gpu_block.py's
-    // decoder matrix and tools/gpu_fuzz.py are generated from it (a decoder added here is tested there), no device needed.
+    // "decompress_blocks_per_wg" for variant 4, else 0); the list ends where the key is refused.  ONE list, read off lz4_route.h
+    // DECODER_VARIANTS: tests/test_gpu_block.py's decoder matrix and tools/gpu_fuzz.py are generated from it (a decoder added to the
+    // table is tested there), no device needed.
     if (!strncmp(key, "decoder_config_", 15)) {
-        const int t[] = {1016, 4008, 4032, 4064, 7000, 8000, 10000, 11000, 13000,
-#ifdef LZ4FLEX_TOOLS
-                         9000, 12000,
-#endif
-        };
-        return list_entry(key + 15, t, (int)(sizeof t / sizeof t[0]));
+        const int v = decoder_config(list_index(key + 15), TOOLS_BUILD);
+        return v >= 0 ? v : -LZ4FLEX_E_INVALID_ARG;
     }
     const bool set_items = !strcmp(key, "debug_dict_set_items");
     const bool items = set_items || !strcmp(key, "debug_shared_dict_items");
@@ -746,7 +682,7 @@ static int run_host_small(lz4flex_ctx* c, const BatchCall& b) {
     BatchCall dv = batch_of(b.compress, d + at_in, (const uint64_t*)(d + at_in_off), (const uint32_t*)(d + at_in_len), n, d + at_out,
                             (const uint64_t*)(d + at_out_off), (const uint32_t*)(d + at_out_cap), (uint32_t*)(d + at_out_len),
                             (int32_t*)(d + at_status), s);
-    dv.big = host_big(b); dv.partial = b.partial;
+    dv.big = host_big(b); dv.partial = b.partial; dv.linked_frame = b.linked_frame;
     dv.flags = b.flags ? (const uint32_t*)(d + at_flags) : nullptr;
     dv.detail = (uint64_t*)(d + at_detail);
     if ((rc = launch_batch(c, dv))) return rc;
@@ -769,7 +705,7 @@ static int run_host_small(lz4flex_ctx* c, const BatchCall& b) {
 static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
     const uint32_t n = b.n;
     if (n == 0) return 0;
-    if (b.chained && (n > CHAIN_WS_BLOCKS || !b.out_pos || b.dict_base)) return -LZ4FLEX_E_INVALID_ARG;
+    if (b.chained && (n > CHAIN_MAX_BLOCKS || !b.out_pos || b.dict_base)) return -LZ4FLEX_E_INVALID_ARG;
     if (b.chain_prev) return -LZ4FLEX_E_INVALID_ARG;                // several chains in one batch: DEVICE batches only (a host batch stages ONE output region)
     DeviceGuard guard(c->device);
     HIP_TRY(guard.err);
@@ -846,7 +782,7 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
     BatchCall dv = batch_of(b.compress, d + a_in, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, d + a_out,
                             (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap), (uint32_t*)(dd + at_out_len),
                             (int32_t*)(dd + at_status), s);
-    dv.chained = b.chained; dv.big = host_big(b); dv.partial = b.partial;
+    dv.chained = b.chained; dv.big = host_big(b); dv.partial = b.partial; dv.linked_frame = b.linked_frame;
     dv.flags = b.flags ? (const uint32_t*)(dd + at_flags) : nullptr;
     dv.detail = (uint64_t*)(dd + at_detail);
     if (has_dict) { dv.dict_base = d + a_dict; dv.dict_off = (const uint64_t*)(dd + at_dict_off); dv.dict_len = (const uint32_t*)(dd + at_dict_len); }
@@ -934,7 +870,7 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
 
 // DEVICE batches run on the caller's stream, on the caller's arrays
 static int run_device_batch(lz4flex_ctx* c, const BatchCall& b) {
-    if (b.chained ? (b.compress || b.n > CHAIN_WS_BLOCKS || !b.out_pos || b.dict_base) : b.chain_prev != nullptr) return -LZ4FLEX_E_INVALID_ARG;
+    if (b.chained ? (b.compress || b.n > CHAIN_MAX_BLOCKS || !b.out_pos || b.dict_base) : b.chain_prev != nullptr) return -LZ4FLEX_E_INVALID_ARG;
     return launch_batch(c, b);
 }
 
@@ -997,19 +933,26 @@ int run_batch(lz4flex_ctx* c, BatchCall& b, const MemKind& k) {
 
 }  // namespace
 
+// lz4_batch_entry.h: lz4flex_compress_batch, and what the frame layer calls for a Linked frame's blocks
+int lz4flex_dev::compress_batch_entry(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* flags,
+                                      uint32_t n, void* out_base, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
+                                      int mem_kind, void* hip_stream, bool linked_frame) {
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;
+    BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.flags = flags; b.linked_frame = linked_frame;
+    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
+    if ((rc = injected_failure(ctx))) return rc;
+    return run_batch(ctx, b, classify_mem(mem_kind, 0, ANY_FLAGS));      // (of the flags, DEVICE batches read BIG_BLOCKS alone)
+}
+
 extern "C" {
 
 int lz4flex_compress_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,
                            const uint32_t* flags, uint32_t n, void* out_base, const uint64_t* out_off,
                            const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int mem_kind,
                            void* hip_stream) {
-    int rc;
-    if ((rc = ctx_resolve(&ctx))) return rc;
-    BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
-    b.flags = flags;
-    if (!batch_arrays_ok(b)) return -LZ4FLEX_E_INVALID_ARG;
-    if ((rc = injected_failure(ctx))) return rc;
-    return run_batch(ctx, b, classify_mem(mem_kind, 0, ANY_FLAGS));      // (of the flags, DEVICE batches read BIG_BLOCKS alone)
+    return compress_batch_entry(ctx, in_base, in_off, in_len, flags, n, out_base, out_off, out_cap, out_len, status, mem_kind, hip_stream, false);
 }
 
 int lz4flex_compress_batch_ex(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len,

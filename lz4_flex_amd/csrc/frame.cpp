@@ -13,6 +13,7 @@
 #include "../../include/lz4flex_amd.h"
 #include "frame_plan.h"
 #include "host_pin.h"
+#include "lz4_batch_entry.h"
 #include "xxh32.h"
 
 namespace {
@@ -217,13 +218,9 @@ struct lz4flex_frame_encoder {
             flags[i] = LZ4FLEX_BLOCK_HISTORY(std::min<uint64_t>(have, FAST_HISTORY));
             left -= len;
         }
-        // (compress_mode high: a Linked frame's blocks are the throughput encoder's unless "compress_high_linked" is 1 -- then the
-        // history bits above are read by the high encoder, a block's dictionary is the stream in front of it)
-        const bool high = lz4flex_get_tuning(nullptr, "compress_mode") == 2 && lz4flex_get_tuning(nullptr, "compress_high_linked") != 1;
-        if (high) (void)lz4flex_set_tuning(nullptr, "compress_mode", 0);
-        int rc = lz4flex_compress_batch(nullptr, lstage.data(), in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk, dst.data(),
-                                        out_off.data(), out_cap.data(), out_len.data(), status.data(), LZ4FLEX_MEM_HOST, nullptr);
-        if (high) (void)lz4flex_set_tuning(nullptr, "compress_mode", 2);
+        // (a Linked frame's blocks: what compress_mode high does with them is encode_route's rule, lz4_route.h)
+        int rc = lz4flex_dev::compress_batch_entry(nullptr, lstage.data(), in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk, dst.data(),
+                                                   out_off.data(), out_cap.data(), out_len.data(), status.data(), LZ4FLEX_MEM_HOST, nullptr, true);
         if (rc) return rc;
         for (size_t i = 0; i < nblk; i++) {
             if (status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;

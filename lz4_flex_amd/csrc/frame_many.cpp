@@ -26,6 +26,7 @@
 
 #include "../../include/lz4flex_amd.h"
 #include "frame_plan.h"
+#include "lz4_batch_entry.h"
 #include "lz4_ctx.h"
 #include "lz4_device.h"
 
@@ -34,7 +35,6 @@ namespace {
 using namespace lz4flex_dev;
 using namespace lz4flex_plan;   // block sizes, FAST_HISTORY, STREAM_MAX (the streams the batch path takes), TableOffset, LinkedWindow
 
-constexpr uint32_t CHAIN_MAX = 65536u;                   // blocks per chained decode batch (LZ4FLEX_MEM_CHAINED)
 // ("decompress_level_chains", default 1 024: from this many Linked streams in one call on their blocks are decoded a level per launch -- the groups loop)
 constexpr uint64_t MAX_SLOTS = 1ull << 26;               // block-table entries per decompress_many call (12 bytes each on the host and on the device)
 
@@ -172,17 +172,12 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
             TRY_RC(lz4flex_compress_chains(c, in, D.dev<lz4flex_chain_block>(a_cb), nb, D.dev<uint32_t>(a_first), D.dev<uint32_t>(a_count), nf, comp,
                                            D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st),
                                            nullptr, LZ4FLEX_MEM_DEVICE, s));
-        else {
-            // (compress_mode high: Linked frames' blocks are the throughput encoder's unless "compress_high_linked" is 1 -- then the
-            // one launch over all blocks of all streams is the high encoder's, every block's history its dictionary)
-            const int mode = c->comp_mode;
-            if (linked && mode == 2 && !c->comp_high_linked) c->comp_mode = 0;
-            const int rc = lz4flex_compress_batch(c, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), D.dev<uint32_t>(a_flags), nb, comp,
-                                                  D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len),
-                                                  D.dev<int32_t>(a_comp_st), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s);
-            c->comp_mode = mode;
-            TRY_RC(rc);
-        }
+        else
+            // (one launch over all blocks of all streams; `linked`: what compress_mode high does with a Linked frame's blocks is
+            // encode_route's rule, lz4_route.h)
+            TRY_RC(compress_batch_entry(c, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), D.dev<uint32_t>(a_flags), nb, comp,
+                                        D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len),
+                                        D.dev<int32_t>(a_comp_st), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s, linked));
     }
     if (csum && nf) TRY_RC(lz4flex_xxh32_batch_device(in, D.dev<uint64_t>(a_soff), D.dev<uint32_t>(a_slen), nf, 0, D.dev<uint32_t>(a_csum), s));   // frame/compress.rs:319-321
     TRY_HIP(launch_frame_many_assemble(D.dev<ManyStream>(a_ms), nf, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), (const uint8_t*)comp,
@@ -289,14 +284,14 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
                 n_comp[i] += 1;
             }
         }
-        if (ok && fi[i].block_mode == 1 && n_comp[i] > CHAIN_MAX) ok = false;
+        if (ok && fi[i].block_mode == 1 && n_comp[i] > CHAIN_MAX_BLOCKS) ok = false;
         if (!ok) {
             again[i] = 1; raw_bytes[i] = 0; n_comp[i] = 0;
             plain.resize(plain0); chained.resize(chained0); r_in.resize(r0); r_out.resize(r0); r_len.resize(r0);
             p_off.resize(p0); p_len.resize(p0); p_stream.resize(p0);
         }
     }
-    // chained groups: whole streams, at most CHAIN_MAX blocks per call, each ordered by (block index, stream)
+    // chained groups: whole streams, at most CHAIN_MAX_BLOCKS blocks per call, each ordered by (block index, stream)
     struct Group { size_t lo, hi; };
     std::vector<Group> groups;
     {
@@ -305,7 +300,7 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
             size_t hi = at;
             const uint32_t st = chained[at].stream;
             while (hi < chained.size() && chained[hi].stream == st) hi++;
-            if (hi - lo > CHAIN_MAX) { groups.push_back({lo, at}); lo = at; }
+            if (hi - lo > CHAIN_MAX_BLOCKS) { groups.push_back({lo, at}); lo = at; }
             at = hi;
         }
         if (chained.size() > lo) groups.push_back({lo, chained.size()});

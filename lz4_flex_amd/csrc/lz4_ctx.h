@@ -95,7 +95,7 @@ struct lz4flex_ctx {
     lz4flex_dev::GrowBuf pay{true, 1u << 20};      // pinned host staging for compacted results of MEM_HOST compress batches
     int dec_lanes = 16;           // lanes per block, decode
     int comp_lanes = 8;           // lanes per block, encode
-    int comp_mode = 0;            // 0 = throughput ("wave") encoder, own parse (default); 1 = reference-exact encoder (lz4_flex's bytes); 2 = high (lz4_compress_high.hip: deep search, independent blocks without a dictionary; everything else as 0)
+    int comp_mode = 0;            // 0 = throughput ("wave") encoder, own parse (default); 1 = reference-exact encoder (lz4_flex's bytes); 2 = high (lz4_compress_high.hip: deep search; which calls keep it and in which form is lz4_route.h encode_route, with the two settings below).  No call writes a setting: lz4flex_set_tuning, the constructor's environment reads and lz4flex_compress_into_with_table's copy are the writers
     int comp_depth = 16;          // "compress_depth": compress_mode 2, the candidates examined per position (1 .. 256)
     int comp_high_dict = 0;       // "compress_high_dict": compress_mode 2, 1 = calls with dictionaries take the high encoder's dictionary form (tests/sim/high_dict_model.c's bytes); 0 = the throughput encoder (default)
     int comp_high_linked = 0;     // "compress_high_linked": compress_mode 2, 1 = LZ4FLEX_BLOCK_HISTORY bits are read (the block's history is its dictionary: tests/sim/high_dict_model.c's bytes) and Linked frames keep the mode; 0 = the bits are ignored, Linked frames take the throughput encoder (default)
@@ -104,7 +104,7 @@ struct lz4flex_ctx {
     uint8_t* pcd_ws = nullptr;    // workgroup decoder, small batches: a parser and a copier workgroup per block hand token lists over through this (lz4_device.h pair_ws)
     lz4flex_dev::OrderedWs pcd;
     int dec_pcd_pair = 1;         // 1: two workgroups per block for batches of few large blocks; 0: never, 2: whenever the batch is small enough (tests, measurements)
-    uint32_t* chain_ws = nullptr; // chained decode batches (Linked frames): one "done" word per block, CHAIN_WS_BLOCKS of them
+    uint32_t* chain_ws = nullptr; // chained decode batches (Linked frames): one "done" word per block, CHAIN_MAX_BLOCKS of them
     lz4flex_dev::OrderedWs chain;
     void* wave_ws = nullptr;      // wave encoder workspace: wave_wgs persistent workgroups; allocated by lz4flex_ctx_create
     lz4flex_dev::OrderedWs wave;
@@ -114,7 +114,7 @@ struct lz4flex_ctx {
     int comp_det = 0;             // "compress_deterministic": 1 = a block's bytes depend on the block and the settings alone (no sub-windows by batch size)
     int dec_level_chains = 1024;  // "decompress_level_chains": from this many Linked streams in one *_many call on, block k of every stream is one plain launch (frame_many.cpp); 0 = never
     int comp_sub = 0;             // throughput encoder, "compress_subwindows": 0 = by batch size, 1 = never, 2 / 4 = always that many sub-windows per block of <= 64 KiB
-    int dec_variant = 0;          // 0 = by batch size, 1 = window in HBM/L2 (lz4_decompress.hip), 4 = parser / copier split (lz4_decompress_split.hip), 7 = a workgroup per block (lz4_decompress_pcd.hip; 8: its test geometry; 10 / 11: 256 / 512 lanes), 13 = a wavefront per block, a lane per sequence (lz4_decompress_seq.hip); tools builds: 9 = plan / replay, 12 = parser / emitter / quads
+    int dec_variant = 0;          // "decompress_variant": 0 = by batch shape, else a pinned decoder -- the numbers are lz4_route.h's Decoder, what each one runs is DECODER_VARIANTS, which batch takes which is decode_route
     int comp_sliding = 2;         // throughput encoder: the windows of a block longer than 64 KiB advance by 48 KiB (2: every window start has 16 KiB of history) or 32 KiB (1: round 4's bytes); 0 = by 64 KiB (round 3's bytes, fastest)
     int comp_carry_wait = 1;      // tests: 0 = a window of the throughput encoder that has to wait for its predecessor's carry gives up at once (the block then takes the second launch)
     int dec_second_pass = 1;      // tests: 0 leaves the blocks a first-pass decoder marked (status DECODE_REDO) instead of decoding them again

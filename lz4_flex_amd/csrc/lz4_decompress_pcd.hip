@@ -93,7 +93,7 @@ using GeoTest = Geo<2048u, 256u, 64u, 128u, 2u, 512u, 1024u>;        // tests: b
 // (JSON block alone: 1 024 lanes 0.14 ms, 512 lanes 0.20, 256 lanes 0.30, 128 lanes 0.50) and the CU hold more of them: 512 lanes and
 // 53 KB -- two per CU -- win for 257 ... 512 blocks (JSON 512 blocks: 0.23 instead of 0.28 ms), 256 lanes and 29 KB -- four per CU --
 // for 513 ... 1 024 (1 024 blocks: 0.38 instead of 0.52); above that a pair of wavefronts per block is ahead
-// (profiles/r04_decoder_shapes.txt; capi.cpp launch_decompress_fast holds the thresholds).
+// (profiles/r04_decoder_shapes.txt; lz4_route.h decode_route holds the thresholds).
 using GeoMid512 = Geo<8192u, 1024u, 64u, 512u, 2u, 8192u, 16384u>;
 using GeoMid256 = Geo<4096u, 512u, 64u, 256u, 2u, 6144u, 8192u>;
 

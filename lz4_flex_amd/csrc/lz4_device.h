@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lz4_route.h"   // PCD_PAIR_MAX_BLOCKS, the DISPATCH_* batch sizes and decode_route / encode_route: which kernel a batch takes (host-only, plain integers)
+
 #define LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL 1
 #define LZ4FLEX_DEV_E_LITERAL_OUT_OF_BOUNDS 2
 #define LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE 3
@@ -40,7 +42,7 @@ struct DecompressArgs {
     // with chain_done: nullable; n words.  Set => the batch holds SEVERAL chains (N Linked frames side by side): block i's predecessor
     // is block chain_prev[i] (< i), 0xFFFFFFFF = the first block of its chain (nothing of the batch lies before it).  Null: i - 1.
     const uint32_t* chain_prev;
-    uint32_t n_chains;         // with chain_prev: the number of chains (0 = unknown); picks the workgroup size (capi.cpp)
+    uint32_t n_chains;         // with chain_prev: the number of chains (0 = unknown); picks the workgroup size (lz4_route.h decode_route)
     // lz4_decompress_pcd_kernel: nullable.  Set (n <= PCD_PAIR_MAX_BLOCKS, the first 64 n bytes zero before the launch) => every block
     // gets TWO workgroups: one parses its tiles and hands the token lists over through this workspace, the other copies
     // (lz4_decompress_pcd.hip "roles"); decompress_pcd_pair_ws_bytes() bytes
@@ -48,21 +50,6 @@ struct DecompressArgs {
     // lz4_decompress_pcd_kernel, tests only: block debug_giveup - 1 of a chained batch gives up as if a wait had timed out (0: none)
     uint32_t debug_giveup;
 };
-constexpr uint32_t PCD_PAIR_MAX_BLOCKS = 128u;
-// The batch sizes at which launch_decompress_fast (capi.cpp) changes decoder and launch_decompress_split its geometry: ONE
-// table, read by the dispatch AND (through lz4flex_get_tuning "dispatch_threshold_<i>") by the tests, whose decoder matrix is
-// every threshold and its successor -- a threshold edit cannot leave a size class untested (a wrong result lived a round in
-// batches of 5 121 ... 16 383 blocks because one geometry was never run on real data).
-constexpr uint32_t DISPATCH_PCD_1024 = 256u;         // <= : a workgroup of 1 024 lanes per block (one per CU); also for large blocks and chains at any count
-constexpr uint32_t DISPATCH_PCD_512 = 512u;          // <= : 512 lanes per block (two per CU)
-constexpr uint32_t DISPATCH_PCD_256 = 640u;          // <= : 256 lanes per block (four per CU)
-// round 6: above, a wavefront per block and a lane per sequence (lz4_decompress_seq.hip) -- its time grows with the batch (16 wavefronts per
-// CU: 4 096 blocks are one round), the split decoder's is one block's chain whatever the batch: JSON tiles 768 / 4 096 / 8 192 / 12 288 /
-// 14 336 / 16 384 blocks 0.32 / 0.53 / 1.00 / 1.44 / 1.63 / 1.82 ms against 0.35 (256 lanes per block) / 1.01 / 1.63 / 1.64 / 1.65 / 1.67;
-// text and log tiles are ahead at every size (16 384 blocks: 2.76 against 3.53, 1.57 against 2.25 ms) -- the threshold is the JSON one
-// (profiles/r06_decoder_shapes.txt)
-constexpr uint32_t DISPATCH_SEQ_MAX = 14336u;        // <= : a wavefront per block, a lane per sequence; above: the split decoder
-constexpr uint32_t DISPATCH_SPLIT_FULL = 64u * 256u;  // (not a change of kernel: from here on every CU holds a workgroup of the split decoder; the tests want this size too)
 size_t decompress_pcd_pair_ws_bytes();
 
 struct CompressArgs {
@@ -398,7 +385,7 @@ struct FrameRangeVerdict {
 };
 hipError_t launch_frame_range_verdict(const FrameRangeVerdict& v, hipStream_t s);
 // DECODE_REDO: the status a first-pass decoder (sequence, workgroup, plan, fused) leaves on a block it does not decode: the host then runs a reference-order
-// kernel with only_status = DECODE_REDO over the batch (capi.cpp launch_redo)
+// kernel with only_status = DECODE_REDO over the batch (capi.cpp launch_redo; which routes have one: lz4_route.h Redo)
 constexpr int32_t DECODE_REDO = 0x7F000001;
 
 }  // namespace lz4flex_dev

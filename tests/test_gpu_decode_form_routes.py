@@ -1,5 +1,5 @@
 """GPU (-m gpu): which decoder each of the six batched decode entries takes under each setting, and what every block of a small batch
-comes out as -- the routing table of capi.cpp's launch_decode, pinned from outside through the C ABI (MEM_DEVICE).
+comes out as -- the routing table of lz4_route.h's decode_route (tests/test_host_routes.py holds it for the CPU), pinned from outside through the C ABI (MEM_DEVICE).
 
 The six entries are the six forms of a batch: plain, one shared dictionary, a dictionary set, and each of those with partial targets.
 Each gets one batch of at most six blocks of a few hundred bytes: a valid block with matches (the dictionary forms: one whose first

@@ -1,7 +1,7 @@
 """GPU (-m gpu): the DEFAULT decoder dispatch at every batch size where it changes kernel or geometry.
 
 The size list is not written down here: it is read from the library (lz4flex_get_tuning "dispatch_threshold_<i>" = the table
-launch_decompress_fast and launch_decompress_split use, lz4_device.h) -- every threshold T, and T - 1 and T + 1 -- so a threshold
+decode_route and launch_decompress_split use, lz4_route.h) -- every threshold T, and T - 1 and T + 1 -- so a threshold
 edit cannot leave a size class untested (round 3: a wrong result in batches of 5 121 ... 16 383 blocks, a geometry that had only
 ever run on the adversarial batch).  Data: JSON, English text and log-line tiles in 64 KiB blocks, encoded by the reference-exact
 encoder (= the oracle's = lz4_flex's block bytes; tests/test_gpu_block.py pins that equality); every block must decode to its

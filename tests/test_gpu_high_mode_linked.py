@@ -480,6 +480,64 @@ def test_setting_0_a_linked_frame_is_mode_0s(block):
     assert frame.compress_frame(data, fi) == on
 
 
+RULE_SETTINGS = ("compress_mode", "compress_high_linked", "compress_high_dict")
+
+
+def rule_settings(lib):
+    return {k: lib.lz4flex_get_tuning(None, k.encode()) for k in RULE_SETTINGS}
+
+
+def frames_device(frame, streams, fi):
+    """frame.compress_frames_device over streams that lie back to back in device memory: the frames"""
+    import torch
+    from lz4_flex_amd import _lib
+    lib, dev = _lib.load(), torch.device("cuda", 0)
+    in_len = [len(s) for s in streams]
+    in_off = [sum(in_len[:i]) for i in range(len(streams))]
+    cap = [int(lib.lz4flex_frame_compress_bound(n, C.byref(fi._c()))) for n in in_len]
+    out_off = [sum(cap[:i]) for i in range(len(streams))]
+    src = torch.from_numpy(np.frombuffer(b"".join(streams), dtype=np.uint8).copy()).to(dev)
+    dst = torch.zeros(sum(cap), dtype=torch.uint8, device=dev)
+    out_len, st = frame.compress_frames_device(src, in_off, in_len, fi, dst, out_off, cap)
+    assert st == [0] * len(streams)
+    host = dst.cpu().numpy()
+    return [bytes(host[o:o + n]) for o, n in zip(out_off, out_len)]
+
+
+@pytest.mark.parametrize("entry", ["streaming encoder", "compress_frames_device"])
+@high_linked
+def test_the_frame_layer_leaves_the_settings_alone(block, entry):
+    """"compress_mode" 2 with "compress_high_linked" 0: a Linked frame is mode 0's, bytes for bytes, and the three settings the rule
+    reads are what they were behind the call -- a successful one and one that "debug_fail_next_batch" made fail.  Two blocks of 64 KiB,
+    the second with history; two streams side by side through the device entry."""
+    from lz4_flex_amd import _lib, frame
+    lib = _lib.load()
+    data = frame_streams()["jtk"][:70000]
+    fi = frame.FrameInfo(block_size=frame.BlockSize.Max64KB, block_mode=frame.BlockMode.Linked)
+
+    def run():
+        if entry == "streaming encoder":
+            return [stream_encode(frame, fi, data, 70001)]
+        return frames_device(frame, [data, data[1000:70000]], fi)
+
+    on = run()                                         # (mode high, the setting on: the history form's frame)
+    block.set_compress_high_linked(False)
+    block.set_compress_mode("fast")
+    fast = run()
+    assert on != fast and all(O.frame_decompress(f, 70000)[:2] == (0, d) for f, d in zip(fast, (data, data[1000:70000])))
+    block.set_compress_mode("high")
+    want = {"compress_mode": 2, "compress_high_linked": 0, "compress_high_dict": 0}
+    assert rule_settings(lib) == want
+    assert run() == fast
+    assert rule_settings(lib) == want
+    assert lib.lz4flex_set_tuning(None, b"debug_fail_next_batch", 1) == 0
+    with pytest.raises(frame.DeviceError, match="debug_fail_next_batch"):
+        run()
+    assert rule_settings(lib) == want
+    assert run() == fast                               # (the hook is spent, the next call is an ordinary one)
+    assert rule_settings(lib) == want
+
+
 @high_linked
 def test_packed_entry_follows_the_batch(block):
     """lz4flex_compress_batch_packed has no flag words: with the setting on its payloads are the batch's without flags, the plain model's"""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Decode time of every decoder kernel over a matrix of batch shapes (one process, one GPU call): which kernel should
-launch_decompress_fast (csrc/capi.cpp) pick for which shape.  Not the reported bench (bench.py).
+decode_route (csrc/lz4_route.h) pick for which shape.  Not the reported bench (bench.py).
 
   python tools/dec_shapes.py                      # the default matrix
   python tools/dec_shapes.py --shapes json:65536:256,log:4194304:256 --variants 6,7
