@@ -94,7 +94,9 @@ const char *lz4flex_build_id(void);
  * lz4flex_decompress_batch_partial_shared_dict / lz4flex_decompress_batch_partial_dict_set / lz4flex_decompress_partial_into_with_dict (no
  * new setting, no workspace) -- a caller detects them by the symbol -- then "compress_mode" 2 (high) with the setting "compress_depth" (no
  * new symbol, no workspace beyond the encoder's: a caller detects the mode by lz4flex_set_tuning(ctx, "compress_mode", 2) == 0), then the
- * dictionary trainer lz4flex_dict_train with lz4flex_dict_train_work_size (no setting, no workspace in the context: the caller brings it). */
+ * dictionary trainer lz4flex_dict_train with lz4flex_dict_train_work_size (no setting, no workspace in the context: the caller brings it),
+ * then the typed batches lz4flex_filter_batch / lz4flex_compress_batch_typed / lz4flex_decompress_batch_typed with the LZ4FLEX_FILTER_*
+ * constants and the setting "filter_bytewise" (no workspace in the context: the caller brings the tmp slots). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -626,6 +628,68 @@ size_t lz4flex_dict_train_work_size(uint32_t n);
 int lz4flex_dict_train(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
                        void *dict_out, uint32_t dict_cap, uint32_t segment /* 0 = 512 */, uint32_t *dict_len /* 1, written */,
                        int32_t *status /* 1, written */, void *work, int mem_kind, void *hip_stream);
+
+/* ---- typed batches: byte- and bit-shuffle filters around the codec (lz4_filter.hip) ---------------------------------------------
+ * Numeric data -- bf16 / fp32 weights, int64 ids and timestamps -- compresses far better once the bytes (or bits) of equal significance
+ * lie together: LZ4 behind a filter, as HDF5's shuffle / bitshuffle, Blosc and the data_type option of batched GPU LZ4 do it.  The
+ * filters are pure byte permutations of a block, defined exactly:
+ *
+ * A block is `L` bytes. `E` is the element size, one of {1, 2, 4, 8}: fp8/int8, bf16/fp16, fp32/int32, fp64/int64. Both filters map `L`
+ * bytes to `L` bytes.
+ *
+ * - SHUFFLE (1).
+ *   - `m = L / E`, rounded down.
+ *   - For element `e < m` and byte `j < E`: `out[j*m + e] = in[e*E + j]`.
+ *   - The last `L - m*E` bytes are copied unchanged to the same positions.
+ *   - `E = 1` is a copy.
+ * - BITSHUFFLE (2).
+ *   - `m8 = (L / E) / 8 * 8`.
+ *   - Plane `p = 8*j + k` holds bit `k` (LSB = 0) of byte `j` of every element, for `j < E` and `k < 8`.
+ *   - Plane `p` occupies `out[p*m8/8 .. (p+1)*m8/8)`.
+ *   - Bit `b` (LSB = 0) of byte `q` of plane `p` is bit `k` of `in[(8q + b)*E + j]`.
+ *   - The last `L - m8*E` bytes are copied unchanged to the same positions.
+ *   - In numpy: `packbits(unpackbits(x[:m8*E].reshape(m8, E), axis=1, bitorder='little').T, axis=1, bitorder='little')`.
+ *   - This is the arrangement the HDF5 bitshuffle filter gives one whole block, but no file compatibility is claimed. The definition
+ *     above is the contract.
+ * - The whole block is one transposition, with no sub-blocking. The inverse is the inverse permutation for the same `L` and `E`.
+ *   `FILTER_NONE (0)` is a copy.
+ *
+ * lz4flex_filter_batch: block i's in_len[i] bytes at in_base + in_off[i] are transformed (inverse != 0: by the inverse permutation) into
+ *   out_base + out_off[i]; offsets of any alignment; overlapping input and output regions are the caller's error.
+ * lz4flex_compress_batch_typed: the forward filter of every block goes into tmp_base + tmp_off[i] (a slot holds at least in_len[i]
+ *   bytes; typically a second buffer of the input's size with tmp_off = in_off), then the ordinary batch path runs with the slots as
+ *   input.  out, out_len and status are byte for byte what lz4flex_compress_batch (flags NULL) gives for the filtered bytes in a batch of
+ *   the same n, under the same settings, in every compress mode.
+ * lz4flex_decompress_batch_typed: lz4flex_decompress_batch runs into the tmp slots with capacity out_cap[i] (a slot holds at least
+ *   out_cap[i] bytes), then the inverse filter runs over L = out_len[i] of every block with status 0 -- read from the device arrays on the
+ *   same stream -- into out_base + out_off[i].  out_len, status and detail are exactly lz4flex_decompress_batch's; a block with status != 0
+ *   writes nothing to out_base; nothing is written behind out_off[i] + out_len[i] or in front of out_off[i].
+ * All three: filter == LZ4FLEX_FILTER_NONE behaves as the plain entry (lz4flex_filter_batch: as a copy) and does not touch tmp.  Nothing
+ *   outside [off, off + L) of a block is read or written, on either side.
+ * mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, asynchronous on hip_stream, nothing is allocated (one launch per
+ *   filter pass) -- or LZ4FLEX_MEM_HOST -- staged through the context and synchronous; tmp_base and tmp_off are ignored, the staging
+ *   arena holds the slots.  LZ4FLEX_MEM_BIG_BLOCKS may be ORed in (the codec reads it as in the plain entries; lz4flex_filter_batch takes
+ *   blocks of any u32 length either way); LZ4FLEX_MEM_CHAINED is refused.
+ * The arguments are checked before a context or a device is looked at: -LZ4FLEX_E_INVALID_ARG for an unknown filter, elem_size outside
+ *   {1, 2, 4, 8}, a mem_kind other than HOST / DEVICE (| BIG_BLOCKS) and, with n != 0, a missing array, or a missing tmp_base / tmp_off in a
+ *   DEVICE call with filter != NONE.  n == 0 returns 0.  -LZ4FLEX_E_NO_DEVICE without a device: there is no CPU path.
+ * Setting "filter_bytewise" (A/B measurements, tests): 1 = the kernels take every block by their narrow path (byte accesses), 0 (default)
+ *   = 16-byte accesses wherever every 16-byte store of a block can be aligned.  Not in scope: dictionaries, frames (the LZ4 frame header has
+ *   no field for a filter), the CLI. */
+#define LZ4FLEX_FILTER_NONE 0
+#define LZ4FLEX_FILTER_SHUFFLE 1
+#define LZ4FLEX_FILTER_BITSHUFFLE 2
+int lz4flex_filter_batch(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
+                         void *out_base, const uint64_t *out_off, int filter, uint32_t elem_size, int inverse, int mem_kind,
+                         void *hip_stream);
+int lz4flex_compress_batch_typed(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
+                                 void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
+                                 int filter, uint32_t elem_size, void *tmp_base, const uint64_t *tmp_off, int mem_kind,
+                                 void *hip_stream);
+int lz4flex_decompress_batch_typed(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
+                                   void *out_base, const uint64_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *status,
+                                   uint64_t *detail /* nullable: 2 per block */, int filter, uint32_t elem_size, void *tmp_base,
+                                   const uint64_t *tmp_off, int mem_kind, void *hip_stream);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

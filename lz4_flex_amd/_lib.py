@@ -15,6 +15,7 @@ FE_CONTENT_LENGTH, FE_OUTPUT_FULL = 30, 31
 E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED = 64, 65, 66, 67, 68
 MEM_HOST, MEM_DEVICE, MEM_BIG_BLOCKS, MEM_CHAINED = 0, 1, 0x100, 0x200
 SIZES_PREPENDED, SIZES_GIVEN, SIZES_SCAN = 0, 1, 2
+FILTER_NONE, FILTER_SHUFFLE, FILTER_BITSHUFFLE = 0, 1, 2
 BLOCK_DEFAULT, BLOCK_FRAME_FIRST, BLOCK_FRAME_CONTINUATION = 0, 2, 3
 
 
@@ -95,6 +96,9 @@ SIGNATURES = {
     "lz4flex_compress_batch_packed": (_I32, [_VP, _VP, _VP, _VP, _U32, _I32, _VP, _U64, _VP, _U64, _U32, _VP, _VP, _VP, _VP, _I32, _VP]),
     "lz4flex_dict_train_work_size": (_SZ, [_U32]),
     "lz4flex_dict_train": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _U32, _U32, _VP, _VP, _VP, _I32, _VP]),
+    "lz4flex_filter_batch": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _I32, _U32, _I32, _I32, _VP]),
+    "lz4flex_compress_batch_typed": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _I32, _U32, _VP, _VP, _I32, _VP]),
+    "lz4flex_decompress_batch_typed": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _U32, _VP, _VP, _I32, _VP]),
     "lz4flex_set_tuning": (_I32, [_VP, C.c_char_p, _I32]),
     "lz4flex_get_tuning": (_I32, [_VP, C.c_char_p]),
     "lz4flex_frame_encoder_new": (_VP, [C.POINTER(FrameInfoC), WRITE_FN, _VP]),

@@ -350,15 +350,17 @@ def _arg(a):
 
 
 def _host_call(name, ctx, in_buf, in_off, in_len, out=None, before_n=(), middle=(), tail=(), detail=False, len_dtype=np.uint32,
-               mem_kind=L.MEM_HOST, per_call=False):
+               mem_kind=L.MEM_HOST, per_call=False, results=True):
     """The host marshaller:
         name(ctx, in_base, in_off, in_len, *before_n, n, *middle, [out_base, out_off, out_cap,] out_len, status, [detail,] *tail, mem_kind, NULL)
     in_buf is bytes-like or a uint8 array, in_off / in_len and `out` = (out_buf, out_off, out_cap) anything numpy converts; before_n,
     middle and tail hold what is particular to the entry, each as _arg takes it.  Returns the arrays the call wrote: (out_len[len_dtype],
-    status[i32]) and, with `detail`, detail[n, 2] u64; per_call: the entry writes ONE length and ONE status for the whole batch."""
+    status[i32]) and, with `detail`, detail[n, 2] u64; per_call: the entry writes ONE length and ONE status for the whole batch; results
+    False: the entry has neither (lz4flex_filter_batch), () is returned."""
     n = len(in_off)
     m = 1 if per_call else n
-    results = [np.zeros(m, dtype=len_dtype), np.zeros(m, dtype=np.int32)] + ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
+    results = [] if not results else \
+        [np.zeros(m, dtype=len_dtype), np.zeros(m, dtype=np.int32)] + ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
     slots = [] if out is None else [out[0], _np(out[1], np.uint64), _np(out[2], np.uint32)]
     args = [_host_u8(in_buf), _np(in_off, np.uint64), _np(in_len, np.uint32), *before_n, n, *middle, *slots, *results, *tail]
     _check(getattr(L.load(), name)(ctx, *map(_arg, args), mem_kind, None), name)
@@ -848,3 +850,181 @@ def train_dictionary_device(src, in_off, in_len, dict_size=32768, segment=512, s
     work = torch.empty(int(L.load().lz4flex_dict_train_work_size(n)), dtype=torch.uint8, device=dev)
     _device_call("lz4flex_dict_train", [src, d_off, d_len], n, [out, dict_size, int(segment), res[0:1], res[1:2], work], False, sp)
     return out[:dict_size], res[0:1]
+
+
+# ---- typed batches: byte- and bit-shuffle filters around the codec (lz4flex_filter_batch, lz4flex_*_batch_typed) -----------------
+FILTERS = {"none": L.FILTER_NONE, "shuffle": L.FILTER_SHUFFLE, "bitshuffle": L.FILTER_BITSHUFFLE}
+
+
+def _filter_args(filter, elem_size):
+    """(filter, elem_size) as the C ABI takes them: "none" | "shuffle" | "bitshuffle" or 0 / 1 / 2, an element of 1, 2, 4 or 8 bytes"""
+    if isinstance(filter, str):
+        if filter not in FILTERS:
+            raise ValueError("filter must be one of %s or 0 / 1 / 2, not %r" % (", ".join(map(repr, FILTERS)), filter))
+        filter = FILTERS[filter]
+    elif isinstance(filter, bool) or not isinstance(filter, (int, np.integer)) or int(filter) not in FILTERS.values():
+        raise ValueError("filter must be one of %s or 0 / 1 / 2, not %r" % (", ".join(map(repr, FILTERS)), filter))
+    if isinstance(elem_size, bool) or not isinstance(elem_size, (int, np.integer)) or int(elem_size) not in (1, 2, 4, 8):
+        raise ValueError("elem_size must be 1, 2, 4 or 8, not %r" % (elem_size,))
+    return int(filter), int(elem_size)
+
+
+def _same_length(in_off, **others):
+    for name, a in others.items():
+        if len(a) != len(in_off):
+            raise ValueError("in_off and %s differ in length" % name)
+
+
+def filter_batch(in_buf, in_off, in_len, out_buf, out_off, filter, elem_size, inverse=False, ctx=None):
+    """lz4flex_filter_batch over host buffers: block i = in_buf[in_off[i] : + in_len[i]] goes through `filter` ("none" | "shuffle" |
+    "bitshuffle" or 0 / 1 / 2) for elements of elem_size bytes -- inverse: through its inverse -- into out_buf[out_off[i] : + in_len[i]]
+    (a uint8 array).  The permutations are defined in include/lz4flex_amd.h.  Returns None."""
+    f, e = _filter_args(filter, elem_size)
+    _same_length(in_off, in_len=in_len, out_off=out_off)
+    _host_call("lz4flex_filter_batch", ctx, in_buf, in_off, in_len, middle=[out_buf, _np(out_off, np.uint64)], tail=[f, e, 1 if inverse else 0],
+               results=False)
+
+
+def compress_batch_typed(in_buf, in_off, in_len, out_buf, out_off, out_cap, filter, elem_size, ctx=None):
+    """lz4flex_compress_batch_typed over host buffers: every block is filtered (filter_batch), then compressed as compress_batch does
+    it -- out_buf, out_len and status are compress_batch's for the filtered bytes.  Returns (out_len[u32], status[i32])."""
+    f, e = _filter_args(filter, elem_size)
+    _same_length(in_off, in_len=in_len, out_off=out_off, out_cap=out_cap)
+    return _host_call("lz4flex_compress_batch_typed", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), tail=[f, e, None, None])
+
+
+def decompress_batch_typed(in_buf, in_off, in_len, out_buf, out_off, out_cap, filter, elem_size, ctx=None):
+    """lz4flex_decompress_batch_typed over host buffers: every block is decoded as decompress_batch does it and, where its status is 0,
+    the inverse filter of its out_len[i] bytes goes to out_buf[out_off[i] : + out_len[i]]; a block that fails writes nothing.  Returns
+    (out_len[u32], status[i32], detail[n,2] u64): decompress_batch's."""
+    f, e = _filter_args(filter, elem_size)
+    _same_length(in_off, in_len=in_len, out_off=out_off, out_cap=out_cap)
+    return _host_call("lz4flex_decompress_batch_typed", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), detail=True,
+                      tail=[f, e, None, None])
+
+
+def filter_blocks_device(src, in_off, in_len, filter, elem_size, inverse=False, stream=None):
+    """Blocks in device memory through a filter (inverse: its inverse): src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
+    in_off[i] + in_len[i]].  One lz4flex_filter_batch (MEM_DEVICE, asynchronous on `stream`, default the current one): no host
+    synchronisation.  Returns (out, out_off): out has src's size, out_off = in_off -- block i's bytes are out[out_off[i] : out_off[i] +
+    in_len[i]], what lies between the blocks is not written."""
+    import torch
+    f, e = _filter_args(filter, elem_size)
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
+    out = torch.empty_like(src)
+    if n:
+        _device_call("lz4flex_filter_batch", [src, d_off, d_len], n, [out, d_off, f, e, 1 if inverse else 0], False, sp)
+    return out, d_off
+
+
+def compress_blocks_typed_device(src, in_off, in_len, filter, elem_size, stream=None):
+    """Blocks of numeric data in device memory, filtered and compressed: src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
+    in_off[i] + in_len[i]], elements of elem_size bytes.  One lz4flex_compress_batch_typed (MEM_DEVICE, asynchronous on `stream`, default
+    the current one) into slots of get_maximum_output_size(in_len[i]) bytes; the tmp slots are a second tensor of src's size.  Returns
+    (out, out_off, out_len, status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
+    import torch
+    f, e = _filter_args(filter, elem_size)
+    tmp_off = _device_args(src, in_off, in_len, stream)[2]
+    tmp = torch.empty_like(src)
+    return _compress_slots_device("lz4flex_compress_batch_typed", src, in_off, in_len, stream, tail=[f, e, tmp, tmp_off])
+
+
+def decompress_blocks_typed_device(src, in_off, in_len, out_cap, filter, elem_size, stream=None):
+    """What compress_blocks_typed_device wrote, back to the numeric data: src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
+    in_off[i] + in_len[i]] and decodes to at most out_cap[i] bytes (an integer tensor).  The output is packed by an exclusive prefix sum of
+    out_cap (ONE host synchronisation: the total, to allocate the output and the tmp slots), then one lz4flex_decompress_batch_typed
+    (MEM_DEVICE, asynchronous on `stream`, default the current one).  Returns (out, out_off, out_len, status) as device tensors: block i's
+    bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and nothing of it is written."""
+    import torch
+    f, e = _filter_args(filter, elem_size)
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
+    if int(out_cap.numel()) != n:
+        raise ValueError("in_off and out_cap differ in length")
+    cap = out_cap.to(device=dev, dtype=torch.int64) & 0xFFFFFFFF
+    out_off = torch.cumsum(cap, 0) - cap
+    total, longest = (int(v) for v in torch.stack([cap.sum(), d_len.max()]).cpu()) if n else (0, 0)      # the one synchronisation
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n:
+        tmp = torch.empty_like(out)
+        d_cap = torch.where(cap >= 0x80000000, cap - 0x100000000, cap).to(torch.int32).contiguous()      # (the bit pattern of a u32)
+        _device_call("lz4flex_decompress_batch_typed", [src, d_off, d_len], n, [out, out_off, d_cap, out_len, status, None, f, e, tmp, out_off],
+                     longest > 131072, sp)
+    return out[:total], out_off, out_len, status
+
+
+class CompressedTensor:
+    """What compress_tensor returns and decompress_tensor takes: the compressed blocks back to back in `data` (a uint8 device tensor),
+    block i at data[offsets[i] : offsets[i] + lengths[i]] (device tensors), and what the tensor was: shape, dtype, the block_bytes it was
+    cut into, the filter (0 / 1 / 2) its blocks went through."""
+    __slots__ = ("data", "offsets", "lengths", "shape", "dtype", "block_bytes", "filter")
+
+    def __init__(self, data, offsets, lengths, shape, dtype, block_bytes, filter):
+        self.data, self.offsets, self.lengths, self.shape, self.dtype = data, offsets, lengths, tuple(shape), dtype
+        self.block_bytes, self.filter = int(block_bytes), int(filter)
+
+    @property
+    def compressed_bytes(self):
+        return int(self.data.numel())
+
+
+def _tensor_blocks(total, block_bytes, dev):
+    """a buffer of `total` bytes cut into blocks of block_bytes (the last one shorter): (in_off, in_len) as int64 device tensors"""
+    import torch
+    n = (total + block_bytes - 1) // block_bytes
+    off = torch.arange(n, dtype=torch.int64, device=dev) * block_bytes
+    return off, torch.clamp(total - off, max=block_bytes)
+
+
+def compress_tensor(t, block_bytes=65536, filter="bitshuffle"):
+    """A contiguous device tensor of a dtype of 1, 2, 4 or 8 bytes, compressed: its bytes are cut into blocks of block_bytes (a multiple of
+    the element size), every block goes through `filter` for elements of t.element_size() bytes and the encoder (compress_mode as set).
+    Returns a CompressedTensor; decompress_tensor gives the tensor back bit for bit.  Raises ValueError for a dtype of another size, a
+    tensor that is not contiguous or not on the GPU, a block_bytes the element size does not divide."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or not t.is_contiguous():
+        raise ValueError("compress_tensor takes a contiguous tensor on the GPU")
+    f, e = _filter_args(filter, 1)[0], t.element_size()
+    if e not in (1, 2, 4, 8):
+        raise ValueError("compress_tensor takes dtypes of 1, 2, 4 or 8 bytes, not %s (%d bytes)" % (t.dtype, e))
+    block_bytes = int(block_bytes)
+    if block_bytes <= 0 or block_bytes % e or block_bytes > 0x7FFFFFFF:
+        raise ValueError("block_bytes must be a positive multiple of the element size (%d) below 2 GiB, not %d" % (e, block_bytes))
+    src = t.reshape(-1).view(torch.uint8)
+    dev, total = t.device, int(src.numel())
+    in_off, in_len = _tensor_blocks(total, block_bytes, dev)
+    n = int(in_off.numel())
+    if n == 0:
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+        return CompressedTensor(torch.empty(0, dtype=torch.uint8, device=dev), empty, empty.to(torch.int32), t.shape, t.dtype, block_bytes, f)
+    out, out_off, out_len, status = compress_blocks_typed_device(src, in_off, in_len, f, e)
+    lens = out_len.to(torch.int64)
+    offsets = torch.cumsum(lens, 0) - lens
+    bad, size = (int(v) for v in torch.stack([(status != 0).sum(), lens.sum()]).cpu())
+    if bad:
+        raise CompressError("compress_tensor: %d of %d blocks failed" % (bad, n))
+    data = torch.empty(max(size, 1), dtype=torch.uint8, device=dev)
+    _check(L.load().lz4flex_copy_batch_device(_arg(out), _arg(out_off), _arg(out_len), _arg(data), _arg(offsets), n,
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lz4flex_copy_batch_device")
+    return CompressedTensor(data[:size], offsets, out_len, t.shape, t.dtype, block_bytes, f)
+
+
+def decompress_tensor(rec):
+    """The tensor a CompressedTensor holds, on the GPU of its data, bit for bit."""
+    import torch
+    e = torch.empty(0, dtype=rec.dtype).element_size()
+    count = 1
+    for d in rec.shape:
+        count *= int(d)
+    total, dev = count * e, rec.data.device
+    if total == 0:
+        return torch.empty(rec.shape, dtype=rec.dtype, device=dev)
+    _, caps = _tensor_blocks(total, rec.block_bytes, dev)
+    if int(caps.numel()) != int(rec.offsets.numel()):
+        raise ValueError("decompress_tensor: %d blocks for a tensor of %d" % (int(rec.offsets.numel()), int(caps.numel())))
+    out, _, out_len, status = decompress_blocks_typed_device(rec.data, rec.offsets, rec.lengths, caps, rec.filter, e)
+    bad = int(((status != 0) | (out_len.to(torch.int64) != caps)).sum())
+    if bad:
+        raise DecompressError("decompress_tensor: %d of %d blocks failed" % (bad, int(caps.numel())))
+    return out.view(rec.dtype).reshape(rec.shape)

@@ -508,6 +508,7 @@ const Setting SETTINGS[] = {
      }, false},
     {"compress_lanes", &lz4flex_ctx::comp_lanes, [](int v) { return v == 8 || v == 16; }, false},
     {"size_scan_serial", &lz4flex_ctx::size_serial, is_flag, false},
+    {"filter_bytewise", &lz4flex_ctx::filter_bytewise, is_flag, false},
     {"compress_shared_dict", &lz4flex_ctx::comp_shared, is_flag, false},
     {"decompress_shared_dict", &lz4flex_ctx::dec_shared, is_flag, false},
     {"decompress_partial", &lz4flex_ctx::dec_partial, is_flag, false},
@@ -1519,6 +1520,151 @@ int lz4flex_dict_train(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in
     memcpy(status, hp + at_res + 4, 4);
     if (*dict_len) memcpy(dict_out, hp + at_dict, std::min<uint32_t>(*dict_len, dict_cap));
     return 0;
+}
+
+// ---- typed batches: the shuffle / bitshuffle filters around the codec (lz4_filter.hip) ------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+enum class Typed { Filter, Compress, Decompress };
+
+bool filter_args_ok(int filter, uint32_t elem) {
+    return (filter == LZ4FLEX_FILTER_NONE || filter == LZ4FLEX_FILTER_SHUFFLE || filter == LZ4FLEX_FILTER_BITSHUFFLE) &&
+           (elem == 1u || elem == 2u || elem == 4u || elem == 8u);
+}
+
+int launch_filter_checked(lz4flex_ctx* c, const uint8_t* in_base, const uint64_t* in_off, const uint32_t* len, const int32_t* gate, uint8_t* out_base,
+                          const uint64_t* out_off, uint32_t n, int filter, uint32_t elem, bool inverse, hipStream_t s) {
+    const FilterArgs f{in_base, in_off, len, gate, out_base, out_off, n, (uint32_t)c->filter_bytewise};
+    const hipError_t le = launch_filter(f, filter, elem, inverse, s);
+    return le != hipSuccess ? hip_fail(le, "filter launch") : 0;
+}
+
+// One typed call on device memory, b holding the call's arrays (Filter: no out_cap / out_len / status).  Compress: the forward filter
+// into the tmp slots, the encoders on the slots.  Decompress: the decoders into the tmp slots, the inverse filter over out_len[i] bytes of
+// every block with status 0, read from the device arrays on the same stream.
+int typed_on_device(lz4flex_ctx* c, Typed op, BatchCall b, int filter, uint32_t elem, bool inverse, uint8_t* tmp_base, const uint64_t* tmp_off) {
+    hipStream_t s = b.stream;
+    if (op == Typed::Filter) return launch_filter_checked(c, b.in_base, b.in_off, b.in_len, nullptr, b.out_base, b.out_off, b.n, filter, elem, inverse, s);
+    if (op == Typed::Compress) {
+        if (const int rc = launch_filter_checked(c, b.in_base, b.in_off, b.in_len, nullptr, tmp_base, tmp_off, b.n, filter, elem, false, s)) return rc;
+        return compress_batch_entry(c, tmp_base, tmp_off, b.in_len, nullptr, b.n, b.out_base, b.out_off, b.out_cap, b.out_len, b.status,
+                                    LZ4FLEX_MEM_DEVICE | (b.big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s, false);
+    }
+    uint8_t* const out_base = b.out_base;
+    const uint64_t* const out_off = b.out_off;
+    b.out_base = tmp_base; b.out_off = tmp_off;
+    if (const int rc = run_device_batch(c, b)) return rc;
+    return launch_filter_checked(c, tmp_base, tmp_off, b.out_len, b.status, out_base, out_off, b.n, filter, elem, true, s);
+}
+
+// MEM_HOST: [input span | tmp slots | output span | descriptors up, results down] in the arena -- the tmp slots mirror the input span
+// (compress) or the output span (decompress) -- one synchronisation for the results, one for the output span, which comes down to
+// page-locked memory; every block that has bytes (Filter: all of them; else status 0) is copied to its place, the rest of the caller's
+// buffer stays as it is.
+int typed_on_host(lz4flex_ctx* c, Typed op, const BatchCall& b, int filter, uint32_t elem, bool inverse, bool big) {
+    const uint32_t n = b.n;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    const bool codec = op != Typed::Filter;
+    const Span in_span = span_of(b.in_off, b.in_len, n);
+    const Span out_span = span_of(b.out_off, codec ? b.out_cap : b.in_len, n);
+    const size_t in_bytes = in_span.bytes(), out_bytes = out_span.bytes();
+    const size_t tmp_bytes = op == Typed::Compress ? in_bytes : op == Typed::Decompress ? out_bytes : 0;
+    Layout l{16};
+    const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_tmp_off = l.take(8ull * n), at_in_len = l.take(4ull * n),
+                 at_out_cap = l.take(4ull * n);
+    const size_t up_bytes = l.end;
+    const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n);
+    const size_t desc_bytes = l.end;
+    int rc;
+    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
+    const size_t a_tmp = align_up(in_bytes + 64, 256), a_out = a_tmp + align_up(tmp_bytes + 64, 256), a_desc = a_out + align_up(out_bytes + 64, 256);
+    if ((rc = ensure_buf(c->arena, a_desc + desc_bytes + 256))) return rc;
+    if ((rc = ensure_buf(c->pay, out_bytes + 16))) return rc;
+    uint8_t* hp = c->pin.p;
+    for (uint32_t i = 0; i < n; i++) {
+        ((uint64_t*)(hp + at_in_off))[i] = b.in_off[i] - in_span.lo;
+        ((uint64_t*)(hp + at_out_off))[i] = b.out_off[i] - out_span.lo;
+        ((uint64_t*)(hp + at_tmp_off))[i] = op == Typed::Compress ? b.in_off[i] - in_span.lo : b.out_off[i] - out_span.lo;
+        ((uint32_t*)(hp + at_in_len))[i] = b.in_len[i];
+        ((uint32_t*)(hp + at_out_cap))[i] = codec ? b.out_cap[i] : 0u;
+    }
+    uint8_t* d = c->arena.p;
+    uint8_t* dd = d + a_desc;
+    hipStream_t s = c->stream;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(d, b.in_base + in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
+    BatchCall dv = batch_of(op == Typed::Compress, d, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, d + a_out,
+                            (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap), (uint32_t*)(dd + at_out_len),
+                            (int32_t*)(dd + at_status), s);
+    dv.big = big;
+    if (op == Typed::Decompress) dv.detail = (uint64_t*)(dd + at_detail);
+    if ((rc = typed_on_device(c, op, dv, filter, elem, inverse, d + a_tmp, (const uint64_t*)(dd + at_tmp_off)))) return rc;
+    if (codec) HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, d + a_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t* r_len = (const uint32_t*)(hp + at_out_len);
+    const int32_t* r_st = (const int32_t*)(hp + at_status);
+    const uint64_t* r_det = (const uint64_t*)(hp + at_detail);
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t bytes = b.in_len[i];
+        if (codec) {
+            b.out_len[i] = r_len[i];
+            b.status[i] = r_st[i];
+            if (b.detail) { b.detail[2 * i] = b.compress ? 0 : r_det[2 * i]; b.detail[2 * i + 1] = b.compress ? 0 : r_det[2 * i + 1]; }
+            bytes = r_st[i] == 0 ? r_len[i] : 0u;
+        }
+        if (bytes) memcpy(b.out_base + b.out_off[i], c->pay.p + (b.out_off[i] - out_span.lo), bytes);
+    }
+    return 0;
+}
+
+// what the three typed entries share: their checks in their order (arguments, then the context), then the memory kind's path
+int typed_entry(lz4flex_ctx* ctx, Typed op, BatchCall b, int filter, uint32_t elem, bool inverse, void* tmp_base, const uint64_t* tmp_off, int mem_kind) {
+    if (!filter_args_ok(filter, elem)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED; Filter: BIG_BLOCKS changes nothing)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (b.n == 0) return 0;
+    if (!b.in_off || !b.in_len || !b.out_off) return -LZ4FLEX_E_INVALID_ARG;
+    if (op != Typed::Filter && (!b.out_cap || !b.out_len || !b.status)) return -LZ4FLEX_E_INVALID_ARG;
+    const bool slots = op != Typed::Filter && filter != LZ4FLEX_FILTER_NONE;
+    if (slots && k.where == Mem::Device && (!tmp_base || !tmp_off)) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;
+    if (!(op == Typed::Compress && slots) && (rc = injected_failure(ctx))) return rc;     // (compress_batch_entry has the hook of a filtered compress)
+    if (op != Typed::Filter && !slots) {               // FILTER_NONE: the plain entry's path, tmp is not touched
+        b.big = k.big;
+        return k.where == Mem::Host ? run_host_batch(ctx, b) : run_device_batch(ctx, b);
+    }
+    if (k.where == Mem::Device) { b.big = k.big; return typed_on_device(ctx, op, b, filter, elem, inverse, (uint8_t*)tmp_base, tmp_off); }
+    return typed_on_host(ctx, op, b, filter, elem, inverse, k.big || (op != Typed::Filter && host_big(b)));
+}
+
+}  // namespace
+
+extern "C" {
+
+int lz4flex_filter_batch(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* out_base,
+                         const uint64_t* out_off, int filter, uint32_t elem_size, int inverse, int mem_kind, void* hip_stream) {
+    const BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, nullptr, nullptr, nullptr, hip_stream);
+    return typed_entry(ctx, Typed::Filter, b, filter, elem_size, inverse != 0, nullptr, nullptr, mem_kind);
+}
+
+int lz4flex_compress_batch_typed(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* out_base,
+                                 const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status, int filter,
+                                 uint32_t elem_size, void* tmp_base, const uint64_t* tmp_off, int mem_kind, void* hip_stream) {
+    const BatchCall b = batch_of(true, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    return typed_entry(ctx, Typed::Compress, b, filter, elem_size, false, tmp_base, tmp_off, mem_kind);
+}
+
+int lz4flex_decompress_batch_typed(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* out_base,
+                                   const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status, uint64_t* detail, int filter,
+                                   uint32_t elem_size, void* tmp_base, const uint64_t* tmp_off, int mem_kind, void* hip_stream) {
+    BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
+    b.detail = detail;
+    return typed_entry(ctx, Typed::Decompress, b, filter, elem_size, true, tmp_base, tmp_off, mem_kind);
 }
 
 // ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------

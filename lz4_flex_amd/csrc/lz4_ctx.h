@@ -140,6 +140,7 @@ struct lz4flex_ctx {
     int range_pass_bytes = 256 << 20;   // "frame_range_pass_bytes": lz4flex_frame_read_ranges cuts its ranges into passes whose scratch (heads; MEM_HOST: the staged spans and outputs too) stays under this; a pass takes at least one range
     int range_checksums = 1;      // "frame_range_checksums": 1 = a range read verifies the block checksums of the blocks it touches (frames that have them); 0 = not (A/B measurements, tests)
     int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
+    int filter_bytewise = 0;      // "filter_bytewise": 1 = the shuffle / bitshuffle kernels (lz4_filter.hip) take every block by their narrow path, byte accesses (A/B measurements, tests)
 };
 
 namespace lz4flex_dev {

@@ -352,6 +352,23 @@ hipError_t launch_packed_gather(const uint8_t* scratch, const uint64_t* src_off,
 size_t dict_train_work_bytes(uint32_t n);
 hipError_t launch_dict_train(const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint8_t* dict_out,
                              uint32_t dict_cap, uint32_t k, uint32_t* dict_len, int32_t* status, void* work, hipStream_t s);
+// lz4_filter.hip (lz4flex_filter_batch, lz4flex_compress_batch_typed, lz4flex_decompress_batch_typed): the byte permutation `filter` for
+// elements of `elem` bytes (1, 2, 4, 8), or its inverse, of every block: len[i] bytes from in_base + in_off[i] to out_base + out_off[i]
+// (any alignment; the regions do not overlap).  gate: nullable; set => only the blocks with gate[i] == 0 (a decoder's status).  Nothing
+// outside [off, off + len) is read or written.  One launch, no workspace.
+enum : int { FILTER_NONE = 0, FILTER_SHUFFLE = 1, FILTER_BITSHUFFLE = 2 };     // the header's LZ4FLEX_FILTER_*
+constexpr uint32_t FILTER_TILE_ELEMS = 1024u;        // the elements of one (block, tile) work item
+struct FilterArgs {
+    const uint8_t* in_base;
+    const uint64_t* in_off;
+    const uint32_t* len;
+    const int32_t* gate;
+    uint8_t* out_base;
+    const uint64_t* out_off;
+    uint32_t n;
+    uint32_t bytewise;         // "filter_bytewise": 1 = every block by the narrow path (byte accesses)
+};
+hipError_t launch_filter(const FilterArgs& a, int filter, uint32_t elem, bool inverse, hipStream_t s);
 // frame_range.hip (frame_index.cpp: lz4flex_frame_index_create / lz4flex_frame_read_ranges).
 // The index: scan_len[b] = what launch_size_scan measures of walked block b (0 for a stored block), *first_bad = ~0; then size[b] (holding
 // the scan's sizes) becomes the block's decoded bytes and *first_bad the first compressed block with scan_st != 0 or more than block_size bytes
