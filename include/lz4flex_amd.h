@@ -96,7 +96,9 @@ const char *lz4flex_build_id(void);
  * new symbol, no workspace beyond the encoder's: a caller detects the mode by lz4flex_set_tuning(ctx, "compress_mode", 2) == 0), then the
  * dictionary trainer lz4flex_dict_train with lz4flex_dict_train_work_size (no setting, no workspace in the context: the caller brings it),
  * then the typed batches lz4flex_filter_batch / lz4flex_compress_batch_typed / lz4flex_decompress_batch_typed with the LZ4FLEX_FILTER_*
- * constants and the setting "filter_bytewise" (no workspace in the context: the caller brings the tmp slots). */
+ * constants and the setting "filter_bytewise" (no workspace in the context: the caller brings the tmp slots), then the flag
+ * LZ4FLEX_FILTER_DELTA (0x10) for the `filter` argument of those three entries, with LZ4FLEX_DELTA_RESTART (no new symbol, no setting: a
+ * caller detects it by lz4flex_filter_batch(NULL, ..., n = 0, ..., filter = 0x10, ...) == 0). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -653,6 +655,21 @@ int lz4flex_dict_train(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in
  *     above is the contract.
  * - The whole block is one transposition, with no sub-blocking. The inverse is the inverse permutation for the same `L` and `E`.
  *   `FILTER_NONE (0)` is a copy.
+ * - DELTA (flag 0x10, ORed into one of the three above: the valid values of `filter` are 0, 1, 2, 0x10, 0x11 and 0x12). A difference
+ *   stage in front of the base filter, as Parquet's delta encoding and Blosc's delta filter have one: in a monotone column -- timestamps,
+ *   sorted ids -- neighbours differ by little, and the differences' high planes are runs where the values' low planes are noise. It does
+ *   not help floating-point weights, so it is never a default.
+ *   - Forward. `m = L / E`. Element `x[e]` is the little-endian unsigned integer of `E` bytes at `in[e*E]`.
+ *     `d[e] = x[e]` where `e % LZ4FLEX_DELTA_RESTART == 0`, otherwise `d[e] = (x[e] - x[e-1]) mod 2^(8E)`. The last `L - m*E` bytes stay
+ *     where they are. The forward typed filter is the base filter (same `L` and `E`) applied to the block of `d`.
+ *   - Inverse. The base filter's inverse, then `x[e] = (d[r] + ... + d[e]) mod 2^(8E)` with `r = e - e % LZ4FLEX_DELTA_RESTART`.
+ *   - The restart every 1 024 elements keeps a tile's work inside one wavefront (no scan over the block, no workspace, one launch) and
+ *     costs nothing in ratio.
+ *   - `E = 1` is a bytewise delta; `DELTA | SHUFFLE` with `E = 1` is the delta alone. With BITSHUFFLE, the up to 7 elements behind `m8`
+ *     are differenced like all the others; only their placement is "unchanged".
+ *   - `E = 2`, `L = 7`: `01 00 03 00 02 00 AA` becomes `01 00 02 00 FF FF AA` (DELTA alone).
+ *   - `E = 1`, `L = 1026`, every byte 5: the result is 5, then 1 023 zeros, then 5, then 0.
+ *   - Everything below holds with the flag set; `filter != LZ4FLEX_FILTER_NONE` includes 0x10: a DEVICE call with the flag needs tmp.
  *
  * lz4flex_filter_batch: block i's in_len[i] bytes at in_base + in_off[i] are transformed (inverse != 0: by the inverse permutation) into
  *   out_base + out_off[i]; offsets of any alignment; overlapping input and output regions are the caller's error.
@@ -679,6 +696,8 @@ int lz4flex_dict_train(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in
 #define LZ4FLEX_FILTER_NONE 0
 #define LZ4FLEX_FILTER_SHUFFLE 1
 #define LZ4FLEX_FILTER_BITSHUFFLE 2
+#define LZ4FLEX_FILTER_DELTA 0x10
+#define LZ4FLEX_DELTA_RESTART 1024
 int lz4flex_filter_batch(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
                          void *out_base, const uint64_t *out_off, int filter, uint32_t elem_size, int inverse, int mem_kind,
                          void *hip_stream);

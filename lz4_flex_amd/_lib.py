@@ -16,6 +16,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED = 64, 65, 66, 67, 68
 MEM_HOST, MEM_DEVICE, MEM_BIG_BLOCKS, MEM_CHAINED = 0, 1, 0x100, 0x200
 SIZES_PREPENDED, SIZES_GIVEN, SIZES_SCAN = 0, 1, 2
 FILTER_NONE, FILTER_SHUFFLE, FILTER_BITSHUFFLE = 0, 1, 2
+FILTER_DELTA = 0x10                  # a flag ORed into the three above
 BLOCK_DEFAULT, BLOCK_FRAME_FIRST, BLOCK_FRAME_CONTINUATION = 0, 2, 3
 
 

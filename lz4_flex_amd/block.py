@@ -856,8 +856,11 @@ def train_dictionary_device(src, in_off, in_len, dict_size=32768, segment=512, s
 FILTERS = {"none": L.FILTER_NONE, "shuffle": L.FILTER_SHUFFLE, "bitshuffle": L.FILTER_BITSHUFFLE}
 
 
-def _filter_args(filter, elem_size):
-    """(filter, elem_size) as the C ABI takes them: "none" | "shuffle" | "bitshuffle" or 0 / 1 / 2, an element of 1, 2, 4 or 8 bytes"""
+def _filter_args(filter, elem_size, delta=False):
+    """(filter, elem_size) as the C ABI takes them: "none" | "shuffle" | "bitshuffle" or 0 / 1 / 2, an element of 1, 2, 4 or 8 bytes;
+    delta (a bool) ORs LZ4FLEX_FILTER_DELTA into the filter"""
+    if not isinstance(delta, bool):
+        raise ValueError("delta must be a bool, not %r" % (delta,))
     if isinstance(filter, str):
         if filter not in FILTERS:
             raise ValueError("filter must be one of %s or 0 / 1 / 2, not %r" % (", ".join(map(repr, FILTERS)), filter))
@@ -866,7 +869,7 @@ def _filter_args(filter, elem_size):
         raise ValueError("filter must be one of %s or 0 / 1 / 2, not %r" % (", ".join(map(repr, FILTERS)), filter))
     if isinstance(elem_size, bool) or not isinstance(elem_size, (int, np.integer)) or int(elem_size) not in (1, 2, 4, 8):
         raise ValueError("elem_size must be 1, 2, 4 or 8, not %r" % (elem_size,))
-    return int(filter), int(elem_size)
+    return int(filter) | (L.FILTER_DELTA if delta else 0), int(elem_size)
 
 
 def _same_length(in_off, **others):
@@ -875,41 +878,43 @@ def _same_length(in_off, **others):
             raise ValueError("in_off and %s differ in length" % name)
 
 
-def filter_batch(in_buf, in_off, in_len, out_buf, out_off, filter, elem_size, inverse=False, ctx=None):
+def filter_batch(in_buf, in_off, in_len, out_buf, out_off, filter, elem_size, inverse=False, ctx=None, delta=False):
     """lz4flex_filter_batch over host buffers: block i = in_buf[in_off[i] : + in_len[i]] goes through `filter` ("none" | "shuffle" |
     "bitshuffle" or 0 / 1 / 2) for elements of elem_size bytes -- inverse: through its inverse -- into out_buf[out_off[i] : + in_len[i]]
-    (a uint8 array).  The permutations are defined in include/lz4flex_amd.h.  Returns None."""
-    f, e = _filter_args(filter, elem_size)
+    (a uint8 array).  delta=True puts the difference stage (LZ4FLEX_FILTER_DELTA: element minus its neighbour, restarting every 1 024
+    elements) in front of the filter.  The transforms are defined in include/lz4flex_amd.h.  Returns None."""
+    f, e = _filter_args(filter, elem_size, delta)
     _same_length(in_off, in_len=in_len, out_off=out_off)
     _host_call("lz4flex_filter_batch", ctx, in_buf, in_off, in_len, middle=[out_buf, _np(out_off, np.uint64)], tail=[f, e, 1 if inverse else 0],
                results=False)
 
 
-def compress_batch_typed(in_buf, in_off, in_len, out_buf, out_off, out_cap, filter, elem_size, ctx=None):
+def compress_batch_typed(in_buf, in_off, in_len, out_buf, out_off, out_cap, filter, elem_size, ctx=None, delta=False):
     """lz4flex_compress_batch_typed over host buffers: every block is filtered (filter_batch), then compressed as compress_batch does
-    it -- out_buf, out_len and status are compress_batch's for the filtered bytes.  Returns (out_len[u32], status[i32])."""
-    f, e = _filter_args(filter, elem_size)
+    it -- out_buf, out_len and status are compress_batch's for the filtered bytes.  delta: as in filter_batch.  Returns (out_len[u32],
+    status[i32])."""
+    f, e = _filter_args(filter, elem_size, delta)
     _same_length(in_off, in_len=in_len, out_off=out_off, out_cap=out_cap)
     return _host_call("lz4flex_compress_batch_typed", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), tail=[f, e, None, None])
 
 
-def decompress_batch_typed(in_buf, in_off, in_len, out_buf, out_off, out_cap, filter, elem_size, ctx=None):
+def decompress_batch_typed(in_buf, in_off, in_len, out_buf, out_off, out_cap, filter, elem_size, ctx=None, delta=False):
     """lz4flex_decompress_batch_typed over host buffers: every block is decoded as decompress_batch does it and, where its status is 0,
     the inverse filter of its out_len[i] bytes goes to out_buf[out_off[i] : + out_len[i]]; a block that fails writes nothing.  Returns
-    (out_len[u32], status[i32], detail[n,2] u64): decompress_batch's."""
-    f, e = _filter_args(filter, elem_size)
+    (out_len[u32], status[i32], detail[n,2] u64): decompress_batch's.  delta: what the blocks were compressed with."""
+    f, e = _filter_args(filter, elem_size, delta)
     _same_length(in_off, in_len=in_len, out_off=out_off, out_cap=out_cap)
     return _host_call("lz4flex_decompress_batch_typed", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), detail=True,
                       tail=[f, e, None, None])
 
 
-def filter_blocks_device(src, in_off, in_len, filter, elem_size, inverse=False, stream=None):
+def filter_blocks_device(src, in_off, in_len, filter, elem_size, inverse=False, stream=None, delta=False):
     """Blocks in device memory through a filter (inverse: its inverse): src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
     in_off[i] + in_len[i]].  One lz4flex_filter_batch (MEM_DEVICE, asynchronous on `stream`, default the current one): no host
     synchronisation.  Returns (out, out_off): out has src's size, out_off = in_off -- block i's bytes are out[out_off[i] : out_off[i] +
-    in_len[i]], what lies between the blocks is not written."""
+    in_len[i]], what lies between the blocks is not written.  delta: as in filter_batch."""
     import torch
-    f, e = _filter_args(filter, elem_size)
+    f, e = _filter_args(filter, elem_size, delta)
     dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
     out = torch.empty_like(src)
     if n:
@@ -917,26 +922,28 @@ def filter_blocks_device(src, in_off, in_len, filter, elem_size, inverse=False, 
     return out, d_off
 
 
-def compress_blocks_typed_device(src, in_off, in_len, filter, elem_size, stream=None):
+def compress_blocks_typed_device(src, in_off, in_len, filter, elem_size, stream=None, delta=False):
     """Blocks of numeric data in device memory, filtered and compressed: src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
     in_off[i] + in_len[i]], elements of elem_size bytes.  One lz4flex_compress_batch_typed (MEM_DEVICE, asynchronous on `stream`, default
     the current one) into slots of get_maximum_output_size(in_len[i]) bytes; the tmp slots are a second tensor of src's size.  Returns
-    (out, out_off, out_len, status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]]."""
+    (out, out_off, out_len, status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]].  delta: as in
+    filter_batch."""
     import torch
-    f, e = _filter_args(filter, elem_size)
+    f, e = _filter_args(filter, elem_size, delta)
     tmp_off = _device_args(src, in_off, in_len, stream)[2]
     tmp = torch.empty_like(src)
     return _compress_slots_device("lz4flex_compress_batch_typed", src, in_off, in_len, stream, tail=[f, e, tmp, tmp_off])
 
 
-def decompress_blocks_typed_device(src, in_off, in_len, out_cap, filter, elem_size, stream=None):
+def decompress_blocks_typed_device(src, in_off, in_len, out_cap, filter, elem_size, stream=None, delta=False):
     """What compress_blocks_typed_device wrote, back to the numeric data: src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
     in_off[i] + in_len[i]] and decodes to at most out_cap[i] bytes (an integer tensor).  The output is packed by an exclusive prefix sum of
     out_cap (ONE host synchronisation: the total, to allocate the output and the tmp slots), then one lz4flex_decompress_batch_typed
     (MEM_DEVICE, asynchronous on `stream`, default the current one).  Returns (out, out_off, out_len, status) as device tensors: block i's
-    bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and nothing of it is written."""
+    bytes are out[out_off[i] : out_off[i] + out_len[i]]; a block that fails gets its status and nothing of it is written.  delta: what
+    the blocks were compressed with."""
     import torch
-    f, e = _filter_args(filter, elem_size)
+    f, e = _filter_args(filter, elem_size, delta)
     dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream)
     if int(out_cap.numel()) != n:
         raise ValueError("in_off and out_cap differ in length")
@@ -957,12 +964,12 @@ def decompress_blocks_typed_device(src, in_off, in_len, out_cap, filter, elem_si
 class CompressedTensor:
     """What compress_tensor returns and decompress_tensor takes: the compressed blocks back to back in `data` (a uint8 device tensor),
     block i at data[offsets[i] : offsets[i] + lengths[i]] (device tensors), and what the tensor was: shape, dtype, the block_bytes it was
-    cut into, the filter (0 / 1 / 2) its blocks went through."""
-    __slots__ = ("data", "offsets", "lengths", "shape", "dtype", "block_bytes", "filter")
+    cut into, the filter (0 / 1 / 2) its blocks went through, and whether the delta stage ran in front of it."""
+    __slots__ = ("data", "offsets", "lengths", "shape", "dtype", "block_bytes", "filter", "delta")
 
-    def __init__(self, data, offsets, lengths, shape, dtype, block_bytes, filter):
+    def __init__(self, data, offsets, lengths, shape, dtype, block_bytes, filter, delta=False):
         self.data, self.offsets, self.lengths, self.shape, self.dtype = data, offsets, lengths, tuple(shape), dtype
-        self.block_bytes, self.filter = int(block_bytes), int(filter)
+        self.block_bytes, self.filter, self.delta = int(block_bytes), int(filter), bool(delta)
 
     @property
     def compressed_bytes(self):
@@ -977,15 +984,16 @@ def _tensor_blocks(total, block_bytes, dev):
     return off, torch.clamp(total - off, max=block_bytes)
 
 
-def compress_tensor(t, block_bytes=65536, filter="bitshuffle"):
+def compress_tensor(t, block_bytes=65536, filter="bitshuffle", delta=False):
     """A contiguous device tensor of a dtype of 1, 2, 4 or 8 bytes, compressed: its bytes are cut into blocks of block_bytes (a multiple of
     the element size), every block goes through `filter` for elements of t.element_size() bytes and the encoder (compress_mode as set).
+    delta=True differences the elements as integers first (monotone integer columns: timestamps, sorted ids; no gain for floating point).
     Returns a CompressedTensor; decompress_tensor gives the tensor back bit for bit.  Raises ValueError for a dtype of another size, a
     tensor that is not contiguous or not on the GPU, a block_bytes the element size does not divide."""
     import torch
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or not t.is_contiguous():
         raise ValueError("compress_tensor takes a contiguous tensor on the GPU")
-    f, e = _filter_args(filter, 1)[0], t.element_size()
+    f, e = _filter_args(filter, 1, delta)[0] & ~L.FILTER_DELTA, t.element_size()
     if e not in (1, 2, 4, 8):
         raise ValueError("compress_tensor takes dtypes of 1, 2, 4 or 8 bytes, not %s (%d bytes)" % (t.dtype, e))
     block_bytes = int(block_bytes)
@@ -997,8 +1005,8 @@ def compress_tensor(t, block_bytes=65536, filter="bitshuffle"):
     n = int(in_off.numel())
     if n == 0:
         empty = torch.empty(0, dtype=torch.int64, device=dev)
-        return CompressedTensor(torch.empty(0, dtype=torch.uint8, device=dev), empty, empty.to(torch.int32), t.shape, t.dtype, block_bytes, f)
-    out, out_off, out_len, status = compress_blocks_typed_device(src, in_off, in_len, f, e)
+        return CompressedTensor(torch.empty(0, dtype=torch.uint8, device=dev), empty, empty.to(torch.int32), t.shape, t.dtype, block_bytes, f, delta)
+    out, out_off, out_len, status = compress_blocks_typed_device(src, in_off, in_len, f, e, delta=delta)
     lens = out_len.to(torch.int64)
     offsets = torch.cumsum(lens, 0) - lens
     bad, size = (int(v) for v in torch.stack([(status != 0).sum(), lens.sum()]).cpu())
@@ -1007,7 +1015,7 @@ def compress_tensor(t, block_bytes=65536, filter="bitshuffle"):
     data = torch.empty(max(size, 1), dtype=torch.uint8, device=dev)
     _check(L.load().lz4flex_copy_batch_device(_arg(out), _arg(out_off), _arg(out_len), _arg(data), _arg(offsets), n,
                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "lz4flex_copy_batch_device")
-    return CompressedTensor(data[:size], offsets, out_len, t.shape, t.dtype, block_bytes, f)
+    return CompressedTensor(data[:size], offsets, out_len, t.shape, t.dtype, block_bytes, f, delta)
 
 
 def decompress_tensor(rec):
@@ -1023,7 +1031,7 @@ def decompress_tensor(rec):
     _, caps = _tensor_blocks(total, rec.block_bytes, dev)
     if int(caps.numel()) != int(rec.offsets.numel()):
         raise ValueError("decompress_tensor: %d blocks for a tensor of %d" % (int(rec.offsets.numel()), int(caps.numel())))
-    out, _, out_len, status = decompress_blocks_typed_device(rec.data, rec.offsets, rec.lengths, caps, rec.filter, e)
+    out, _, out_len, status = decompress_blocks_typed_device(rec.data, rec.offsets, rec.lengths, caps, rec.filter, e, delta=rec.delta)
     bad = int(((status != 0) | (out_len.to(torch.int64) != caps)).sum())
     if bad:
         raise DecompressError("decompress_tensor: %d of %d blocks failed" % (bad, int(caps.numel())))

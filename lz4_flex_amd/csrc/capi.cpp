@@ -1529,8 +1529,12 @@ namespace {
 
 enum class Typed { Filter, Compress, Decompress };
 
+static_assert(LZ4FLEX_FILTER_DELTA == FILTER_DELTA && LZ4FLEX_DELTA_RESTART == FILTER_TILE_ELEMS, "the header's delta constants are the kernels'");
+
 bool filter_args_ok(int filter, uint32_t elem) {
-    return (filter == LZ4FLEX_FILTER_NONE || filter == LZ4FLEX_FILTER_SHUFFLE || filter == LZ4FLEX_FILTER_BITSHUFFLE) &&
+    if (filter < 0 || (filter & ~(LZ4FLEX_FILTER_DELTA | 3)) != 0) return false;
+    const int base = filter & ~LZ4FLEX_FILTER_DELTA;     // the flag rides on the value: launch_filter takes them together
+    return (base == LZ4FLEX_FILTER_NONE || base == LZ4FLEX_FILTER_SHUFFLE || base == LZ4FLEX_FILTER_BITSHUFFLE) &&
            (elem == 1u || elem == 2u || elem == 4u || elem == 8u);
 }
 

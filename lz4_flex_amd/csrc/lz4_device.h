@@ -355,8 +355,9 @@ hipError_t launch_dict_train(const uint8_t* in_base, const uint64_t* in_off, con
 // lz4_filter.hip (lz4flex_filter_batch, lz4flex_compress_batch_typed, lz4flex_decompress_batch_typed): the byte permutation `filter` for
 // elements of `elem` bytes (1, 2, 4, 8), or its inverse, of every block: len[i] bytes from in_base + in_off[i] to out_base + out_off[i]
 // (any alignment; the regions do not overlap).  gate: nullable; set => only the blocks with gate[i] == 0 (a decoder's status).  Nothing
-// outside [off, off + len) is read or written.  One launch, no workspace.
-enum : int { FILTER_NONE = 0, FILTER_SHUFFLE = 1, FILTER_BITSHUFFLE = 2 };     // the header's LZ4FLEX_FILTER_*
+// outside [off, off + len) is read or written.  One launch, no workspace.  `filter` may carry FILTER_DELTA: the difference stage in front
+// of the permutation (inverse: the prefix sums behind its inverse), restarting every FILTER_TILE_ELEMS elements, in the same launch.
+enum : int { FILTER_NONE = 0, FILTER_SHUFFLE = 1, FILTER_BITSHUFFLE = 2, FILTER_DELTA = 0x10 };     // the header's LZ4FLEX_FILTER_*; DELTA is a flag ORed into the other three
 constexpr uint32_t FILTER_TILE_ELEMS = 1024u;        // the elements of one (block, tile) work item
 struct FilterArgs {
     const uint8_t* in_base;
