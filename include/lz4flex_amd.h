@@ -98,7 +98,9 @@ const char *lz4flex_build_id(void);
  * then the typed batches lz4flex_filter_batch / lz4flex_compress_batch_typed / lz4flex_decompress_batch_typed with the LZ4FLEX_FILTER_*
  * constants and the setting "filter_bytewise" (no workspace in the context: the caller brings the tmp slots), then the flag
  * LZ4FLEX_FILTER_DELTA (0x10) for the `filter` argument of those three entries, with LZ4FLEX_DELTA_RESTART (no new symbol, no setting: a
- * caller detects it by lz4flex_filter_batch(NULL, ..., n = 0, ..., filter = 0x10, ...) == 0). */
+ * caller detects it by lz4flex_filter_batch(NULL, ..., n = 0, ..., filter = 0x10, ...) == 0), then the fit batches lz4flex_fit_batch /
+ * lz4flex_compress_batch_fit with lz4flex_compress_fit_work_size and the setting "fit_serial" (no workspace in the context: the caller
+ * brings scratch and work; a caller detects them by the symbol). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -710,6 +712,71 @@ int lz4flex_decompress_batch_typed(lz4flex_ctx *ctx, const void *in_base, const 
                                    uint64_t *detail /* nullable: 2 per block */, int filter, uint32_t elem_size, void *tmp_base,
                                    const uint64_t *tmp_off, int mem_kind, void *hip_stream);
 
+/* ---- fit batches: compress into a fixed capacity (lz4_fit.hip) -- liblz4's LZ4_compress_destSize as a batch -----------------------
+ * "How much of my input fits in this slot?"  lz4flex_fit_batch cuts a FINISHED block to a capacity; lz4flex_compress_batch_fit runs the
+ * batch encoder in front of it.  The compress-side mirror of lz4flex_decompress_batch_partial.
+ *
+ * THE RULE (tests/fit_model.py is the same rule as a program).  Given a valid block `B` with sequences `j = 0 .. S-1` (literals `l_j`,
+ * match `m_j`, offset `d_j`; the last one has no match), the `n` source bytes `B` decodes to, and a capacity `cap`.  Write `c_j` for the
+ * compressed offset of sequence j's token and `p_j` for its decoded offset, and
+ *     `ext(x) = 0 if x < 15 else 1 + (x-15)/255`          (integer division: the length bytes behind a token's nibble)
+ *     `tail(L) = 1 + ext(L) + L`                           (a final run of L literals, compressed)
+ *     `Lfit(r, avail)` = the largest `L` in `[0, avail]` with `tail(L) <= r`.
+ *   1. `B` fits: if `len(B) <= cap`, the output is `B` byte for byte, `in_used = n`, and nothing is walked.
+ *   2. `B` does not fit: the best candidate over all `k` with `c_k < cap`.
+ *      Plain(k): sequences `0 .. k-1` unchanged, then a final run of `L = Lfit(cap - c_k, n - p_k)` literals.  Legal iff `L >= Lmin`,
+ *        `Lmin = 0` for `k = 0`, else `max(5, 12 - m_{k-1})` (the format's end rules: the last 5 bytes are literals, the last match
+ *        starts at least 12 bytes before the end).  `used = p_k + L`, `size = c_k + tail(L)`.
+ *      Clipped(k), only when `m_k >= 5`: sequences `0 .. k-1`, then sequence `k` with its literals and its match cut to `m'`, then a
+ *        final run `L`.  With `h = 1 + ext(l_k) + l_k + 2` and `b = cap - c_k - h - 1` it needs `b >= 5`;
+ *        `m' = min(m_k - 1, 18 + 255*(b - 5))`, and `max(5, 12 - m') <= b` is required;
+ *        `L = Lfit(cap - c_k - h - ext(m'-4), n - p_k - l_k - m')`, legal iff `L >= max(5, 12 - m')`.
+ *        `used = p_k + l_k + m' + L`, `size = c_k + h + ext(m'-4) + tail(L)`.
+ *      A candidate whose sequences alone decode to more than `n` bytes (`p_k > n`, `p_k + l_k + m' > n`: a wrong src_len) is not legal.
+ *      Choice: the largest `used`; ties go to the smallest size, then the smallest `k`, then Plain before Clipped.  The maximum is over
+ *        EVERY such k, not the last one alone (a sequence with `l >= 15`, `m = 4` costs as many compressed bytes as it decodes).
+ *      The final literals are read from the source at the decoded position: `src[used - L, used)`.
+ *   3. No candidate -- only at `cap == 0`: status LZ4FLEX_E_OUTPUT_TOO_SMALL, out_len 0, in_used 0, nothing is written.
+ *   Errors: every sequence whose token lies in front of cap (`c_k < cap`) is parsed in the reference's check order
+ *   (decompress.rs:249-443: all of its length bytes, its offset, the token that must follow a match), and the first error met is the
+ *   block's status -- the DecompressError code, out_len 0, in_used 0, nothing written.  Nothing of a sequence at or behind cap is looked
+ *   at: an error there is not seen (the partial decoder's contract), and neither is any error of a block that fits.
+ *
+ * lz4flex_fit_batch: block i = blk_len[i] bytes at blk_base + blk_off[i], its source the src_len[i] bytes at src_base + src_off[i], cut to
+ *   out_cap[i] bytes at out_base + out_off[i]; out_len[i] = the bytes written, in_used[i] = the source bytes they decode to, status[i] = 0
+ *   or a code as above.  src_len[i] is the caller's promise of what block i decodes to; it is not checked -- with a wrong promise the
+ *   output is still a structurally valid block inside out_cap[i], its content unspecified.  Nothing outside [out_off[i], out_off[i] +
+ *   out_len[i]) is written, nothing of a block at or behind blk_len[i] and nothing of a source at or behind src_len[i] is read.  The
+ *   primitive does not know which encoder wrote the block: every "compress_mode" alike.  It takes SELF-CONTAINED blocks only: there is no
+ *   history input, so a block compressed against a dictionary or against a stream's history, whose matches reach in front of its own
+ *   output, is refused with LZ4FLEX_E_OFFSET_OUT_OF_BOUNDS where such a match lies in front of the cut (it is copied where it fits whole).
+ * lz4flex_compress_batch_fit: lz4flex_compress_batch (no flags, the context's settings) into `scratch`, slots of
+ *   lz4flex_get_maximum_output_size(in_len[i]) bytes back to back whose offsets are scanned on the device -- scratch_cap >=
+ *   lz4flex_compress_packed_scratch_bound(sum of in_len, n, 0) always suffices; a block whose slot ends behind scratch_cap gets
+ *   LZ4FLEX_E_OUTPUT_TOO_SMALL (the packed entry's rule) -- then the fit pass from the slots.  Block i's result is exactly
+ *   fit(lz4flex_compress_batch's bytes for the same batch under the same settings, its input, out_cap[i]), in "compress_mode" 0, 1 and 2
+ *   alike; out_cap[i] >= lz4flex_get_maximum_output_size(in_len[i]) gives lz4flex_compress_batch's bytes and in_used[i] = in_len[i].  A
+ *   block the encoder fails keeps that status (out_len 0, in_used 0).  work: lz4flex_compress_fit_work_size(n) bytes, 8-byte aligned.
+ *   Known cost: the encoder encodes all in_len[i] bytes whatever out_cap[i] is.
+ * mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, asynchronous on hip_stream, nothing is allocated; lz4flex_fit_batch is one
+ *   launch plus the launch for the blocks it hands to its reference-order pass -- or LZ4FLEX_MEM_HOST -- staged through the context and
+ *   synchronous; scratch and work are ignored.  LZ4FLEX_MEM_BIG_BLOCKS may be ORed in (lz4flex_fit_batch: changes nothing; the encoder reads
+ *   it as in the plain entry); LZ4FLEX_MEM_CHAINED is refused.
+ * The arguments are checked before a context or a device is looked at: -LZ4FLEX_E_INVALID_ARG for a mem_kind other than HOST / DEVICE
+ *   (| BIG_BLOCKS) and, with n != 0, a missing array (DEVICE: a missing scratch or work).  n == 0 returns 0.  -LZ4FLEX_E_NO_DEVICE without a
+ *   device: there is no CPU path.
+ * Setting "fit_serial" (tests, A/B): 1 = every block is cut by the reference-order pass, a lane per block; 0 (default) = a wavefront per
+ *   block, that pass for the blocks it gives up (every error among them).  Same results.
+ * Not in scope: flags, dictionaries, history (neither entry takes them; lz4flex_fit_batch with a per-block history length is the
+ *   follow-up that would let a caller compose them), frames. */
+int lz4flex_fit_batch(lz4flex_ctx *ctx, const void *blk_base, const uint64_t *blk_off, const uint32_t *blk_len, const void *src_base,
+                      const uint64_t *src_off, const uint32_t *src_len, uint32_t n, void *out_base, const uint64_t *out_off,
+                      const uint32_t *out_cap, uint32_t *out_len, uint32_t *in_used, int32_t *status, int mem_kind, void *hip_stream);
+size_t lz4flex_compress_fit_work_size(uint32_t n);
+int lz4flex_compress_batch_fit(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
+                               void *scratch, uint64_t scratch_cap, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
+                               uint32_t *out_len, uint32_t *in_used, int32_t *status, void *work, int mem_kind, void *hip_stream);
+
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own
  *   parse -- any LZ4 decoder returns the input; ratio within a percent of the reference's, usually better), 1 = the
@@ -874,7 +941,7 @@ int lz4flex_decompress_batch_typed(lz4flex_ctx *ctx, const void *in_base, const 
  *   the launches before it have written -- instead of a workgroup per block that polls its predecessor: thousands of short streams,
  *   4 096 x 256 KiB 6.7 -> 3.1 ms per GiB; 0 = never; tests set 1); "compress_shared_dict" (see lz4flex_compress_batch_shared_dict);
  *   "decompress_shared_dict" (see lz4flex_decompress_batch_shared_dict); "decompress_partial" (see lz4flex_decompress_batch_partial);
- *   "frame_range_pass_bytes" and "frame_range_checksums" (see lz4flex_frame_read_ranges);
+ *   "frame_range_pass_bytes" and "frame_range_checksums" (see lz4flex_frame_read_ranges); "fit_serial" (see the fit batches);
  *   "packed_scan_tile" (read-only: the sizes one workgroup of the packed entries' offset scan takes, see the packed batches).
  * Keys that start with "debug_" inject faults for this library's own tests; they are unsupported and refused
  * (-LZ4FLEX_E_INVALID_ARG) unless the process runs with LZ4FLEX_TEST_HOOKS=1.  "debug_exact_dict_piece" (set only; a count, 0 = no

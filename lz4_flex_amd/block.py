@@ -350,17 +350,18 @@ def _arg(a):
 
 
 def _host_call(name, ctx, in_buf, in_off, in_len, out=None, before_n=(), middle=(), tail=(), detail=False, len_dtype=np.uint32,
-               mem_kind=L.MEM_HOST, per_call=False, results=True):
+               mem_kind=L.MEM_HOST, per_call=False, results=True, in_used=False):
     """The host marshaller:
-        name(ctx, in_base, in_off, in_len, *before_n, n, *middle, [out_base, out_off, out_cap,] out_len, status, [detail,] *tail, mem_kind, NULL)
+        name(ctx, in_base, in_off, in_len, *before_n, n, *middle, [out_base, out_off, out_cap,] out_len, [in_used,] status, [detail,] *tail, mem_kind, NULL)
     in_buf is bytes-like or a uint8 array, in_off / in_len and `out` = (out_buf, out_off, out_cap) anything numpy converts; before_n,
     middle and tail hold what is particular to the entry, each as _arg takes it.  Returns the arrays the call wrote: (out_len[len_dtype],
     status[i32]) and, with `detail`, detail[n, 2] u64; per_call: the entry writes ONE length and ONE status for the whole batch; results
-    False: the entry has neither (lz4flex_filter_batch), () is returned."""
+    False: the entry has neither (lz4flex_filter_batch), () is returned; in_used: the fit entries' in_used[u32] between the two."""
     n = len(in_off)
     m = 1 if per_call else n
     results = [] if not results else \
-        [np.zeros(m, dtype=len_dtype), np.zeros(m, dtype=np.int32)] + ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
+        [np.zeros(m, dtype=len_dtype)] + ([np.zeros(m, dtype=np.uint32)] if in_used else []) + [np.zeros(m, dtype=np.int32)] + \
+        ([np.zeros((n, 2), dtype=np.uint64)] if detail else [])
     slots = [] if out is None else [out[0], _np(out[1], np.uint64), _np(out[2], np.uint32)]
     args = [_host_u8(in_buf), _np(in_off, np.uint64), _np(in_len, np.uint32), *before_n, n, *middle, *slots, *results, *tail]
     _check(getattr(L.load(), name)(ctx, *map(_arg, args), mem_kind, None), name)
@@ -959,6 +960,96 @@ def decompress_blocks_typed_device(src, in_off, in_len, out_cap, filter, elem_si
         _device_call("lz4flex_decompress_batch_typed", [src, d_off, d_len], n, [out, out_off, d_cap, out_len, status, None, f, e, tmp, out_off],
                      longest > 131072, sp)
     return out[:total], out_off, out_len, status
+
+
+# ---- fit batches: compress into a fixed capacity (lz4flex_fit_batch, lz4flex_compress_batch_fit) --------------------------------------
+def fit_batch(blk_buf, blk_off, blk_len, src_buf, src_off, src_len, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_fit_batch over host buffers: the finished block blk_buf[blk_off[i] : + blk_len[i]], which decodes to src_buf[src_off[i] : +
+    src_len[i]], cut to at most out_cap[i] bytes at out_buf[out_off[i]:] (a uint8 array) -- the block itself when it fits, else the
+    valid block inside the capacity that decodes to the longest prefix of the source (the rule: include/lz4flex_amd.h).  Returns
+    (out_len[u32], in_used[u32], status[i32]): block i's bytes are out_buf[out_off[i] : out_off[i] + out_len[i]] and decode to the first
+    in_used[i] source bytes; an error of the block in front of the cut is its status, out_cap[i] == 0 gives E_OUTPUT_TOO_SMALL."""
+    _same_length(blk_off, blk_len=blk_len, src_off=src_off, src_len=src_len, out_off=out_off, out_cap=out_cap)
+    return _host_call("lz4flex_fit_batch", ctx, blk_buf, blk_off, blk_len, (out_buf, out_off, out_cap),
+                      before_n=[_host_u8(src_buf), _np(src_off, np.uint64), _np(src_len, np.uint32)], in_used=True)
+
+
+def compress_batch_fit(in_buf, in_off, in_len, out_buf, out_off, out_cap, ctx=None):
+    """lz4flex_compress_batch_fit over host buffers: every block in_buf[in_off[i] : + in_len[i]] is compressed as compress_batch does it
+    (compress_mode as set) and cut to out_cap[i] bytes as fit_batch does it.  Returns (out_len[u32], in_used[u32], status[i32]); out_cap[i]
+    >= get_maximum_output_size(in_len[i]) gives compress_batch's bytes and in_used[i] = in_len[i].  The encoder encodes all of every
+    block whatever its capacity."""
+    _same_length(in_off, in_len=in_len, out_off=out_off, out_cap=out_cap)
+    return _host_call("lz4flex_compress_batch_fit", ctx, in_buf, in_off, in_len, (out_buf, out_off, out_cap), middle=[None, 0], tail=[None],
+                      in_used=True)
+
+
+def compress_fit(data, cap):
+    """`data` compressed into at most `cap` bytes (LZ4_compress_destSize; a batch of one): (block, used) -- block decodes to data[:used]."""
+    cap = int(cap)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    src = _host_u8(data)
+    out_len, used, status = compress_batch_fit(src if src.size else np.zeros(1, dtype=np.uint8), [0], [src.size], out, [0], [cap])
+    if status[0] == L.E_OUTPUT_TOO_SMALL:
+        raise CompressOutputTooSmall("no LZ4 block fits %d bytes" % cap)
+    if status[0]:
+        raise DeviceError("lz4flex error %d: %s" % (status[0], L.last_error()))
+    return out[:int(out_len[0])].tobytes(), int(used[0])
+
+
+def _fit_slots_device(dev, n, out_cap):
+    """the output of the two fit device forms: slots of out_cap[i] bytes back to back (ONE host synchronisation: the total, to allocate
+    exactly that).  Returns (out, out_off, out_cap as the int32 bit pattern of u32, out_len, in_used, status)."""
+    import torch
+    if int(out_cap.numel()) != n:
+        raise ValueError("in_off and out_cap differ in length")
+    cap = out_cap.to(device=dev, dtype=torch.int64) & 0xFFFFFFFF
+    out_off = torch.cumsum(cap, 0) - cap
+    total = int(cap.sum()) if n else 0
+    d_cap = torch.where(cap >= 0x80000000, cap - 0x100000000, cap).to(torch.int32).contiguous()
+    return (torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total], out_off, d_cap, torch.zeros(n, dtype=torch.int32, device=dev),
+            torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+
+
+def fit_blocks_device(blocks, blk_off, blk_len, src, src_off, src_len, out_cap, stream=None):
+    """Finished blocks and their sources in device memory, cut to out_cap[i] bytes each: blocks and src are uint8 torch tensors on one
+    GPU, block i is blocks[blk_off[i] : + blk_len[i]] and decodes to src[src_off[i] : + src_len[i]].  The output is packed by an exclusive
+    prefix sum of out_cap (ONE host synchronisation: the total), then one lz4flex_fit_batch (MEM_DEVICE, asynchronous on `stream`,
+    default the current one).  Returns (out, out_off, out_len, in_used, status) as device tensors: block i's bytes are out[out_off[i] :
+    out_off[i] + out_len[i]] and decode to the first in_used[i] bytes of its source."""
+    import torch
+    dev, n, b_off, b_len, sp = _device_args(blocks, blk_off, blk_len, stream, source=src)
+    if int(src_off.numel()) != n or int(src_len.numel()) != n:
+        raise ValueError("blk_off, src_off and src_len differ in length")
+    s_off = src_off.to(device=dev, dtype=torch.int64).contiguous()
+    s_len = src_len.to(device=dev, dtype=torch.int32).contiguous()
+    out, out_off, d_cap, out_len, used, status = _fit_slots_device(dev, n, out_cap)
+    if n:
+        _device_call("lz4flex_fit_batch", [blocks, b_off, b_len, src, s_off, s_len], n, [out, out_off, d_cap, out_len, used, status], False, sp)
+    return out, out_off, out_len, used, status
+
+
+def compress_blocks_fit_device(src, in_off, in_len, out_cap, stream=None, scratch_cap=None):
+    """Blocks in device memory, compressed into out_cap[i] bytes each: src is a uint8 torch tensor on the GPU, block i is src[in_off[i] :
+    in_off[i] + in_len[i]].  The output is packed by an exclusive prefix sum of out_cap (ONE host synchronisation: the total and the
+    longest block), then one lz4flex_compress_batch_fit (MEM_DEVICE, asynchronous on `stream`, default the current one); the scratch slots
+    and the workspace are allocated here, by torch's allocator on the CURRENT stream, and released on return as in the other device forms:
+    a `stream` other than the current one has to be ordered with it by the caller.  scratch_cap: another capacity for the scratch slots
+    (default: what always suffices); blocks whose slot ends behind it get E_OUTPUT_TOO_SMALL.  Returns (out, out_off, out_len, in_used,
+    status) as device tensors: block i's bytes are out[out_off[i] : out_off[i] + out_len[i]] and decode to src[in_off[i] : in_off[i] +
+    in_used[i]]."""
+    import torch
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream, wide_len=True)
+    out, out_off, d_cap, out_len, used, status = _fit_slots_device(dev, n, out_cap)
+    if n:
+        lib = L.load()
+        total_in, longest = (int(v) for v in torch.stack([d_len.sum(), d_len.max()]).cpu())
+        scratch_cap = int(lib.lz4flex_compress_packed_scratch_bound(total_in, n, 0)) if scratch_cap is None else int(scratch_cap)
+        scratch = torch.empty(max(scratch_cap, 1), dtype=torch.uint8, device=dev)
+        work = torch.empty(int(lib.lz4flex_compress_fit_work_size(n)), dtype=torch.uint8, device=dev)
+        _device_call("lz4flex_compress_batch_fit", [src, d_off, d_len.to(torch.int32)], n,
+                     [scratch, scratch_cap, out, out_off, d_cap, out_len, used, status, work], longest > 65536, sp)
+    return out, out_off, out_len, used, status
 
 
 class CompressedTensor:

@@ -509,6 +509,7 @@ const Setting SETTINGS[] = {
     {"compress_lanes", &lz4flex_ctx::comp_lanes, [](int v) { return v == 8 || v == 16; }, false},
     {"size_scan_serial", &lz4flex_ctx::size_serial, is_flag, false},
     {"filter_bytewise", &lz4flex_ctx::filter_bytewise, is_flag, false},
+    {"fit_serial", &lz4flex_ctx::fit_serial, is_flag, false},
     {"compress_shared_dict", &lz4flex_ctx::comp_shared, is_flag, false},
     {"decompress_shared_dict", &lz4flex_ctx::dec_shared, is_flag, false},
     {"decompress_partial", &lz4flex_ctx::dec_partial, is_flag, false},
@@ -522,6 +523,7 @@ const Setting SETTINGS[] = {
     {"debug_chain_giveup", &lz4flex_ctx::chain_giveup, is_count, true},
     {"debug_exact_dict_piece", &lz4flex_ctx::exact_dict_piece, is_count, true},    // tests/test_gpu_exact_dict_pieces.py: more than one piece
     {"debug_fail_next_batch", &lz4flex_ctx::fail_next_batch, is_count, true},      // tests/test_gpu_sharded_native.py: one rank's call-level failure
+    {"debug_fit_first_pass", &lz4flex_ctx::fit_first_pass, is_flag, true},         // tests/test_gpu_fit.py: which blocks does the wavefront pass finish?
 };
 const Setting* find_setting(const char* key) {
     for (const Setting& s : SETTINGS) if (!strcmp(key, s.key)) return &s;
@@ -1669,6 +1671,129 @@ int lz4flex_decompress_batch_typed(lz4flex_ctx* ctx, const void* in_base, const 
     BatchCall b = batch_of(false, in_base, in_off, in_len, n, out_base, out_off, out_cap, out_len, status, hip_stream);
     b.detail = detail;
     return typed_entry(ctx, Typed::Decompress, b, filter, elem_size, true, tmp_base, tmp_off, mem_kind);
+}
+
+// ---- fit batches: a finished block cut to a capacity (lz4_fit.hip) -------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+int launch_fit_checked(lz4flex_ctx* c, const FitArgs& a, bool gated, hipStream_t s) {
+    const hipError_t le = launch_fit(a, gated ? 1 : 0, c->fit_first_pass ? 2 : c->fit_serial, s);
+    return le != hipSuccess ? hip_fail(le, "fit launch") : 0;
+}
+
+// lz4flex_compress_batch_fit on device memory (a.blk_* are this function's to fill): scratch slots of get_maximum_output_size bytes back to
+// back, their offsets scanned on the device (lz4_packed.hip), the encoder into them, the fit pass from them.  A slot beyond scratch_cap
+// has capacity 0: the encoder answers OUTPUT_TOO_SMALL for that block and the fit pass leaves it at that.
+int compress_fit_on_device(lz4flex_ctx* c, FitArgs a, uint8_t* scratch, uint64_t scratch_cap, void* work, bool big, hipStream_t s) {
+    const PackedWork w = packed_work(work, a.n);
+    uint32_t* const enc_len = (uint32_t*)w.size;             // (the sizes are read by the scan alone: the encoder's lengths take their place)
+    hipError_t e = launch_packed_sizes(PACKED_SIZES_SLOTS, a.src_base, a.src_off, a.src_len, nullptr, nullptr, a.n, 0u, w.size, nullptr, nullptr, w.pre, s);
+    if (e == hipSuccess) e = launch_packed_scan(w.size, a.n, 1u, scratch_cap, 0u, w.tiles, w.aux_off, w.place, w.aux_len, w.pre, s);
+    if (e == hipSuccess) e = hipMemsetAsync(enc_len, 0, 4ull * a.n, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.status, 0, 4ull * a.n, s);
+    if (e != hipSuccess) return hip_fail(e, "fit layout launch");
+    if (const int rc = compress_batch_entry(c, a.src_base, a.src_off, a.src_len, nullptr, a.n, scratch, w.place, w.aux_len, enc_len, a.status,
+                                            LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s, false)) return rc;
+    a.blk_base = scratch; a.blk_off = w.place; a.blk_len = enc_len;
+    return launch_fit_checked(c, a, true, s);
+}
+
+// MEM_HOST, both entries: [block span | source span | output span | descriptors up, results down | work] in the arena (compress: no
+// block span, the scratch slots in the context's scratch); one synchronisation; the output span comes down to page-locked memory and
+// every block with status 0 is copied to its place, the rest of the caller's buffer stays as it is.
+int fit_on_host(lz4flex_ctx* c, const FitArgs& a, bool compress, bool big) {
+    const uint32_t n = a.n;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    const Span blk_span = compress ? Span{0, 0} : span_of(a.blk_off, a.blk_len, n);
+    const Span src_span = span_of(a.src_off, a.src_len, n);
+    const Span out_span = span_of(a.out_off, a.out_cap, n);
+    const size_t blk_bytes = blk_span.bytes(), src_bytes = src_span.bytes(), out_bytes = out_span.bytes();
+    uint64_t slots = 0;
+    if (compress) for (uint32_t i = 0; i < n; i++) { slots += lz4flex_get_maximum_output_size(a.src_len[i]); big |= a.src_len[i] > 65536u; }
+    Layout l{16};
+    const size_t at_blk_off = l.take(8ull * n), at_src_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_blk_len = l.take(4ull * n),
+                 at_src_len = l.take(4ull * n), at_out_cap = l.take(4ull * n);
+    const size_t up_bytes = l.end;
+    const size_t at_out_len = l.take(4ull * n), at_used = l.take(4ull * n), at_status = l.take(4ull * n);
+    const size_t desc_bytes = l.end;
+    int rc;
+    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
+    const size_t a_src = align_up(blk_bytes + 64, 256), a_out = a_src + align_up(src_bytes + 64, 256), a_desc = a_out + align_up(out_bytes + 64, 256),
+                 a_work = a_desc + align_up(desc_bytes, 256);
+    if ((rc = ensure_buf(c->arena, a_work + (compress ? packed_work_bytes(n) : 0) + 256))) return rc;
+    if ((rc = ensure_buf(c->pay, out_bytes + 16))) return rc;
+    void* d_scratch = nullptr;
+    if (compress && (rc = ctx_scratch(c, 0, (size_t)slots + 256, &d_scratch))) return rc;
+    uint8_t* hp = c->pin.p;
+    for (uint32_t i = 0; i < n; i++) {
+        ((uint64_t*)(hp + at_blk_off))[i] = compress ? 0 : a.blk_off[i] - blk_span.lo;
+        ((uint64_t*)(hp + at_src_off))[i] = a.src_off[i] - src_span.lo;
+        ((uint64_t*)(hp + at_out_off))[i] = a.out_off[i] - out_span.lo;
+        ((uint32_t*)(hp + at_blk_len))[i] = compress ? 0 : a.blk_len[i];
+        ((uint32_t*)(hp + at_src_len))[i] = a.src_len[i];
+        ((uint32_t*)(hp + at_out_cap))[i] = a.out_cap[i];
+    }
+    uint8_t* d = c->arena.p;
+    uint8_t* dd = d + a_desc;
+    hipStream_t s = c->stream;
+    if (blk_bytes) HIP_TRY(hipMemcpyAsync(d, a.blk_base + blk_span.lo, blk_bytes, hipMemcpyHostToDevice, s));
+    if (src_bytes) HIP_TRY(hipMemcpyAsync(d + a_src, a.src_base + src_span.lo, src_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
+    const FitArgs dv{d, (const uint64_t*)(dd + at_blk_off), (const uint32_t*)(dd + at_blk_len), d + a_src, (const uint64_t*)(dd + at_src_off),
+                     (const uint32_t*)(dd + at_src_len), n, d + a_out, (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap),
+                     (uint32_t*)(dd + at_out_len), (uint32_t*)(dd + at_used), (int32_t*)(dd + at_status)};
+    if ((rc = compress ? compress_fit_on_device(c, dv, (uint8_t*)d_scratch, slots, d + a_work, big, s) : launch_fit_checked(c, dv, false, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, d + a_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t* r_len = (const uint32_t*)(hp + at_out_len);
+    const uint32_t* r_used = (const uint32_t*)(hp + at_used);
+    const int32_t* r_st = (const int32_t*)(hp + at_status);
+    for (uint32_t i = 0; i < n; i++) {
+        a.out_len[i] = r_len[i];
+        a.in_used[i] = r_used[i];
+        a.status[i] = r_st[i];
+        if (r_st[i] == 0 && r_len[i]) memcpy(a.out_base + a.out_off[i], c->pay.p + (a.out_off[i] - out_span.lo), r_len[i]);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lz4flex_fit_batch(lz4flex_ctx* ctx, const void* blk_base, const uint64_t* blk_off, const uint32_t* blk_len, const void* src_base,
+                      const uint64_t* src_off, const uint32_t* src_len, uint32_t n, void* out_base, const uint64_t* out_off, const uint32_t* out_cap,
+                      uint32_t* out_len, uint32_t* in_used, int32_t* status, int mem_kind, void* hip_stream) {
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED; BIG_BLOCKS changes nothing)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!blk_off || !blk_len || !src_off || !src_len || !out_off || !out_cap || !out_len || !in_used || !status) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = begin_batch(&ctx))) return rc;
+    const FitArgs a{(const uint8_t*)blk_base, blk_off, blk_len, (const uint8_t*)src_base, src_off, src_len, n, (uint8_t*)out_base, out_off, out_cap,
+                    out_len, in_used, status};
+    return k.where == Mem::Device ? launch_fit_checked(ctx, a, false, (hipStream_t)hip_stream) : fit_on_host(ctx, a, false, false);
+}
+
+size_t lz4flex_compress_fit_work_size(uint32_t n) { return packed_work_bytes(n); }
+
+int lz4flex_compress_batch_fit(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* scratch,
+                               uint64_t scratch_cap, void* out_base, const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len,
+                               uint32_t* in_used, int32_t* status, void* work, int mem_kind, void* hip_stream) {
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!in_off || !in_len || !out_off || !out_cap || !out_len || !in_used || !status) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && (!work || !scratch)) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;                  // (compress_batch_entry has the "debug_fail_next_batch" hook)
+    const FitArgs a{nullptr, nullptr, nullptr, (const uint8_t*)in_base, in_off, in_len, n, (uint8_t*)out_base, out_off, out_cap, out_len, in_used, status};
+    if (k.where == Mem::Device) return compress_fit_on_device(ctx, a, (uint8_t*)scratch, scratch_cap, work, k.big, (hipStream_t)hip_stream);
+    return fit_on_host(ctx, a, true, k.big);
 }
 
 // ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------

@@ -140,6 +140,8 @@ struct lz4flex_ctx {
     int range_pass_bytes = 256 << 20;   // "frame_range_pass_bytes": lz4flex_frame_read_ranges cuts its ranges into passes whose scratch (heads; MEM_HOST: the staged spans and outputs too) stays under this; a pass takes at least one range
     int range_checksums = 1;      // "frame_range_checksums": 1 = a range read verifies the block checksums of the blocks it touches (frames that have them); 0 = not (A/B measurements, tests)
     int size_serial = 0;          // "size_scan_serial": 1 = lz4flex_decompressed_size_batch measures every block with its serial (reference-order) pass (tests)
+    int fit_serial = 0;           // "fit_serial": 1 = lz4flex_fit_batch / lz4flex_compress_batch_fit cut every block with the serial (reference-order) pass (tests, A/B)
+    int fit_first_pass = 0;       // "debug_fit_first_pass" (test hook): 1 = the fit entries run their wavefront pass alone, the blocks it gives up stay marked FIT_REDO
     int filter_bytewise = 0;      // "filter_bytewise": 1 = the shuffle / bitshuffle kernels (lz4_filter.hip) take every block by their narrow path, byte accesses (A/B measurements, tests)
 };
 

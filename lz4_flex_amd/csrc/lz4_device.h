@@ -309,6 +309,21 @@ hipError_t launch_copy_batch(const uint8_t* src_base, const uint64_t* src_off, c
 constexpr int32_t SIZE_SCAN_REDO = 0x7F000003;
 hipError_t launch_size_scan(const uint8_t* in_base, const uint64_t* in_off, const uint32_t* in_len, const uint32_t* history, uint32_t n,
                             uint64_t* out_size, int32_t* status, int serial_only, hipStream_t s);
+// lz4_fit.hip (lz4flex_fit_batch, lz4flex_compress_batch_fit): every finished block blk_base + blk_off[i] (blk_len[i] bytes, decoding to the
+// src_len[i] bytes at src_base + src_off[i]) cut to out_cap[i] bytes at out_base + out_off[i] by the fit rule (include/lz4flex_amd.h);
+// in_used[i] = the source bytes the result decodes to.  A wavefront per block; the blocks it leaves marked FIT_REDO are taken again in the
+// reference's check order, a lane per block, behind it.  gated: status[i] is read first and a block with status[i] != 0 keeps it (out_len
+// and in_used 0: the encoder in front of this pass failed it).  serial_only 1: the second pass for every block (tests, A/B); 2: the first
+// pass alone, a block it gives up keeps status FIT_REDO (the test hook "debug_fit_first_pass": which blocks does the wavefront pass finish?).
+constexpr int32_t FIT_REDO = 0x7F000004;
+struct FitArgs {
+    const uint8_t* blk_base; const uint64_t* blk_off; const uint32_t* blk_len;
+    const uint8_t* src_base; const uint64_t* src_off; const uint32_t* src_len;
+    uint32_t n;
+    uint8_t* out_base; const uint64_t* out_off; const uint32_t* out_cap;
+    uint32_t* out_len; uint32_t* in_used; int32_t* status;
+};
+hipError_t launch_fit(const FitArgs& a, int gated, int serial_only, hipStream_t s);
 // lz4_packed.hip (lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed): the output layout of a batch, computed on the device.
 constexpr uint32_t PACKED_SCAN_TILE = 1024u;         // the sizes one workgroup scans ("packed_scan_tile")
 enum : int {

@@ -1,5 +1,5 @@
-// lz4_seq_walk.h -- the tile WALK of the one-block-per-wavefront kernels: the sequence decoder (lz4_decompress_seq.hip) and the size
-// scan (lz4_size_scan.hip).  Both follow a block's token chain (the reference's `ip`, decompress.rs:244-332, positions only) the same
+// lz4_seq_walk.h -- the tile WALK of the one-block-per-wavefront kernels: the sequence decoder (lz4_decompress_seq.hip), the size
+// scan (lz4_size_scan.hip) and the fit pass (lz4_fit.hip).  All follow a block's token chain (the reference's `ip`, decompress.rs:244-332, positions only) the same
 // way, and this is that way, once.
 //
 // The compressed stream is consumed in tiles of 3 840 bytes staged in LDS; a tile is cut into 64 parts of 60 bytes and lane k walks
@@ -15,6 +15,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "lz4_device.h"
 #include "lz4_pcd_common.h"
 
 namespace lz4flex_dev {
@@ -293,6 +294,76 @@ __device__ __forceinline__ Token decode_token(uint32_t idx, uint32_t ilr) {
     t.nxt = t.lend + (t.m15 ? 3u : 2u);
     t.lastm = ballot(t.lend >= ilr);
     return t;
+}
+
+// ---- a length run, by the whole wavefront (the size scan's and the fit pass's sequences that no lane takes) ------------------------------
+// a length run at q (read_integer, decompress.rs:160-174 via :336-340 / :386-391), 64 bytes per load: adds its value to v, q behind it.
+// false: the input ends inside the run, or v passes POS_LIMIT
+__device__ __forceinline__ bool run_len(const g_u8* in, uint32_t ilen, uint32_t lane, uint32_t& q, uint32_t& v) {
+    for (;;) {
+        const uint32_t p = q + lane;
+        const uint32_t b = p < ilen ? (uint32_t)in[p] : 255u;
+        const uint64_t stop = ballot(p < ilen && b != 255u);
+        SW_JOIN();
+        if (stop != 0ull) {
+            const uint32_t k = ctz64(stop);
+            const uint64_t add = 255ull * k + rdlane(b, k);
+            if ((uint64_t)v + add > POS_LIMIT) return false;
+            v += (uint32_t)add;
+            q += k + 1u;
+            return true;
+        }
+        if (ilen - q <= 64u) return false;
+        if ((uint64_t)v + 255u * 64u > POS_LIMIT) return false;
+        v += 255u * 64u;
+        q += 64u;
+    }
+}
+
+// One sequence of any shape at ip by the whole wavefront, in the reference's check order (decompress.rs:334-443), lengths only.  op: bytes
+// produced in front of it (advanced); hist: bytes in front of the block's output an offset may reach; lit, ml: its lengths.  false: an
+// error, or a position beyond POS_LIMIT -- the kernel's serial pass names it.  last: the block ended here (ml = 0).
+static __device__ bool wave_seq(const g_u8* in, uint32_t ilen, uint32_t lane, uint32_t hist, uint32_t ip, uint32_t& op, uint32_t& lit,
+                                uint32_t& ml, bool& last) {
+    const uint32_t t = uni(in[ip]);
+    ip += 1u;
+    lit = t >> 4;
+    ml = 0u;
+    if (lit == 15u && !run_len(in, ilen, lane, ip, lit)) return false;
+    if (lit > ilen - ip || (uint64_t)op + lit > POS_LIMIT) return false;
+    op += lit;
+    ip += lit;
+    if (ip >= ilen) { last = true; return true; }
+    if (ilen - ip < 2u) return false;
+    const uint32_t offset = uni((uint32_t)in[ip] | ((uint32_t)in[ip + 1u] << 8));
+    ip += 2u;
+    if (offset == 0u) return false;
+    ml = 4u + (t & 15u);
+    if (ml == 19u && !run_len(in, ilen, lane, ip, ml)) return false;
+    if ((uint64_t)offset > (uint64_t)op + hist) return false;
+    if ((uint64_t)op + ml > POS_LIMIT) return false;
+    op += ml;
+    if (ip >= ilen) return false;              // a match is always followed by another token (:439-443)
+    return true;
+}
+
+// ---- what a chunk of 64 decoded tokens says, one ballot per reference check (ilr: the block's end relative to t0) -------------------------
+// errm: lanes whose sequence fails a check that needs no position (literals past the input :336-340 / :346-348, an offset missing
+// :373-375, no token behind a match :439-443, offset zero :168-173); bigm: lanes whose sequence has more length bytes than a lane reads
+__device__ __forceinline__ void chunk_masks(const Token& t, uint32_t ilr, uint64_t& errm, uint64_t& bigm) {
+    errm = ballot(t.l15 && t.tpr + 1u >= ilr) | ballot(t.lend > ilr) |
+           (~t.lastm & (ballot(t.lend + 2u > ilr) | ballot(t.nxt >= ilr) | ballot(t.off == 0u)));
+    bigm = t.biglit | (~t.lastm & ballot(t.m15 && t.e2 == 255u));
+}
+
+// ---- the serial passes' length run: read_integer (decompress.rs:160-174), 64-bit positions ------------------------------------------------
+__device__ __forceinline__ int32_t read_integer(const uint8_t* in, uint64_t ilen, uint64_t& ip, uint64_t& v) {   // :160-174
+    for (;;) {
+        if (ip >= ilen) return LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE;
+        const uint32_t extra = in[ip++];
+        v += extra;
+        if (extra != 0xFFu) return 0;
+    }
 }
 
 }  // namespace sw

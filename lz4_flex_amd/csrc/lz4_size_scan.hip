@@ -35,53 +35,8 @@ constexpr uint32_t LDS_BYTES = LDS_TILE + TILE_LDS;
 static_assert(((PT + 1u + LITMAX) & ~3u) + 8u <= PT + TMARGIN, "a lane's offset and match length byte lie inside the staged bytes");
 
 // ---- measuring --------------------------------------------------------------------------------------------------------------------
-// a length run at q (read_integer, decompress.rs:160-174 via :336-340 / :386-391), 64 bytes per load: adds its value to v, q behind it.
-// false: the input ends inside the run, or v passes POS_LIMIT
-__device__ __forceinline__ bool run_len(const g_u8* in, uint32_t ilen, uint32_t lane, uint32_t& q, uint32_t& v) {
-    for (;;) {
-        const uint32_t p = q + lane;
-        const uint32_t b = p < ilen ? (uint32_t)in[p] : 255u;
-        const uint64_t stop = ballot(p < ilen && b != 255u);
-        SW_JOIN();
-        if (stop != 0ull) {
-            const uint32_t k = ctz64(stop);
-            const uint64_t add = 255ull * k + rdlane(b, k);
-            if ((uint64_t)v + add > POS_LIMIT) return false;
-            v += (uint32_t)add;
-            q += k + 1u;
-            return true;
-        }
-        if (ilen - q <= 64u) return false;
-        if ((uint64_t)v + 255u * 64u > POS_LIMIT) return false;
-        v += 255u * 64u;
-        q += 64u;
-    }
-}
-
-// One sequence of any shape at ip by the whole wavefront, in the reference's check order (decompress.rs:334-443), lengths only.  op: bytes
-// produced in front of it (advanced).  false: an error, or a size beyond POS_LIMIT -- the serial pass names it.  done: the block ended here.
-__device__ bool measure_seq(const g_u8* in, uint32_t ilen, uint32_t lane, uint32_t hist, uint32_t ip, uint32_t& op, bool& done) {
-    const uint32_t t = uni(in[ip]);
-    ip += 1u;
-    uint32_t lit = t >> 4;
-    if (lit == 15u && !run_len(in, ilen, lane, ip, lit)) return false;
-    if (lit > ilen - ip || (uint64_t)op + lit > POS_LIMIT) return false;
-    op += lit;
-    ip += lit;
-    if (ip >= ilen) { done = true; return true; }
-    if (ilen - ip < 2u) return false;
-    const uint32_t offset = uni((uint32_t)in[ip] | ((uint32_t)in[ip + 1u] << 8));
-    ip += 2u;
-    if (offset == 0u) return false;
-    uint32_t ml = 4u + (t & 15u);
-    if (ml == 19u && !run_len(in, ilen, lane, ip, ml)) return false;
-    if ((uint64_t)offset > (uint64_t)op + hist) return false;
-    if ((uint64_t)op + ml > POS_LIMIT) return false;
-    op += ml;
-    if (ip >= ilen) return false;              // a match is always followed by another token (:439-443)
-    return true;
-}
-
+// (a length run by the whole wavefront: run_len, lz4_seq_walk.h)
+// (one sequence of any shape by the whole wavefront: wave_seq, lz4_seq_walk.h)
 // The sequences [0, n_tile) of the tile's token list, 64 at a time.  op advances; false: the block goes to the serial pass.
 __device__ __forceinline__ bool run_chunks(const g_u8* in, uint32_t ilen, uint32_t lane, uint32_t hist, uint32_t t0, uint32_t n_tile,
                                            uint32_t& op, bool& done) {
@@ -92,12 +47,10 @@ __device__ __forceinline__ bool run_chunks(const g_u8* in, uint32_t ilen, uint32
         const uint32_t nrem = n_tile - sidx;
         // token, lengths, offset (decompress.rs:249-258, 334-391)
         const Token t = decode_token<LITMAX>(sidx + (lane < nrem ? lane : nrem - 1u), ilr);
-        const uint32_t tpr = t.tpr, lit = t.lit, lend = t.lend, off = t.off, e2 = t.e2, mlx = t.mlx, nxt = t.nxt;
-        const bool l15 = t.l15, m15 = t.m15;
-        const uint64_t biglit = t.biglit, lastm = t.lastm;
-        const uint64_t errm = ballot(l15 && tpr + 1u >= ilr) | ballot(lend > ilr) |                         // :336-340, :346-348
-                              (~lastm & (ballot(lend + 2u > ilr) | ballot(nxt >= ilr) | ballot(off == 0u))); // :373-375, :439-443, :168-173
-        const uint64_t bigm = biglit | (~lastm & ballot(m15 && e2 == 255u));                               // more length bytes
+        const uint32_t tpr = t.tpr, lit = t.lit, off = t.off, mlx = t.mlx;
+        const uint64_t lastm = t.lastm;
+        uint64_t errm, bigm;
+        chunk_masks(t, ilr, errm, bigm);
         uint32_t nact = nrem < 64u ? nrem : 64u;
         {
             const uint64_t bm = bigm & low_mask(nact);
@@ -105,7 +58,8 @@ __device__ __forceinline__ bool run_chunks(const g_u8* in, uint32_t ilen, uint32
         }
         if (nact == 0u) {                                      // the sequence alone, by the whole wavefront
             const uint32_t tp0 = rdlane(tpr, 0u);
-            if (!measure_seq(in, ilen, lane, hist, t0 + tp0, op, done)) return false;
+            uint32_t sl, sm;
+            if (!wave_seq(in, ilen, lane, hist, t0 + tp0, op, sl, sm, done)) return false;
             sidx += 1u;
             if (done) return sidx == n_tile;
             continue;
@@ -170,14 +124,6 @@ __global__ void __launch_bounds__(64) lz4_size_scan_kernel(const uint8_t* in_bas
 }
 
 // ---- the serial pass: decompress.rs:201-449 for one block per lane, lengths only, 64-bit positions -----------------------------------
-__device__ __forceinline__ int32_t read_integer(const uint8_t* in, uint64_t ilen, uint64_t& ip, uint64_t& v) {   // :160-174
-    for (;;) {
-        if (ip >= ilen) return LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE;
-        const uint32_t extra = in[ip++];
-        v += extra;
-        if (extra != 0xFFu) return 0;
-    }
-}
 __device__ int32_t measure_block(const uint8_t* in, uint64_t ilen, uint64_t hist, uint64_t& size) {
     if (ilen == 0u) return LZ4FLEX_DEV_E_EXPECTED_ANOTHER_BYTE;           // :207-209
     uint64_t ip = 0u, op = 0u;
