@@ -27,7 +27,8 @@
 //     written when the segments are placed).  Behind the matching barrier only the sizes are resolved (resolve_window:
 //     where every segment's output starts, kept with the window's other values in a record in LDS); the bytes of window k
 //     are copied while window k + 1 is matched, by whichever worker is done with its segment first (copy_segment, tickets
-//     from an LDS counter): the serial part between a window's two barriers is the resolve and the next window's load.
+//     from an LDS counter).  The sizes are resolved by the indexer wavefront, which has nothing else to do there (round 23): the
+//     serial part between a window's two barriers is the next window's load.
 // Memory traffic: the input twice (the indexer's stream, the workers' window) and the output once are 2.2 GiB per GiB of input; cand[] is
 // 2 GiB written + 2 GiB read back and the segment bodies are written and read once more (two sets of bodies per workgroup: window k + 1's
 // are written while window k's are read) -- the 512 workgroups' workspace (~420 KB each)
@@ -119,15 +120,16 @@ constexpr uint32_t WORKER_LDS = CMP_OFF + 256u;
 constexpr uint32_t CHUNK = 1024u;         // the indexer streams the next window in 1 KiB chunks (16 steps)
 constexpr uint32_t CHUNK_SLOT = CHUNK + 16u;      // + the first bytes of the next chunk (positions 1021..1023 hash across the end)
 constexpr uint32_t IDX_DEPTH = 4u;        // chunks in flight (registers) ahead of the one being indexed
-// LDS layout (81 728 B with eleven workers: two workgroups per CU)
+// LDS layout (81 664 B with eleven workers: two workgroups per CU)
 constexpr uint32_t L_WIN = 0u;                              // the window + 64 B of slack for the 16-byte compares
 constexpr uint32_t L_TAB = WINDOW + 64u;                    // the indexer's table, 4096 x u16
 constexpr uint32_t L_STG = L_TAB + (2u << HBITS);
 constexpr uint32_t L_RING = L_STG + WORKERS * WORKER_LDS;   // the indexer's chunk slot(s)
 constexpr uint32_t L_META = L_RING + RING_SLOTS * CHUNK_SLOT;
-// L_META, words: 5 per worker (SegMeta, the window being matched), BlkCarry[2] (4), the drawn items (giq, 4), resolve_window's mailbox (3),
+// L_META, words: 5 per worker (SegMeta, the window being matched), BlkCarry[2] (4), the drawn items (giq, 4),
 // run_flag[2] (see index_window), the ticket counter of the deferred copies (1), two copy records (window k's is record k & 1: PlaceRec)
-constexpr uint32_t M_TICKET = 5u * WORKERS + 13u;
+constexpr uint32_t M_RUN = 5u * WORKERS + 8u;
+constexpr uint32_t M_TICKET = M_RUN + 2u;
 constexpr uint32_t M_REC = M_TICKET + 1u;
 constexpr uint32_t REC_SEG = 7u;                          // per segment: {out_pos, pend} and the segment's SegMeta
 constexpr uint32_t REC_UNI = REC_SEG * WORKERS;           // behind the segments: the window's uniform values (PlaceRec)
@@ -147,7 +149,7 @@ static_assert(WS_BYTES % 256u == 0u, "workspace slots stay 256 B aligned");
 constexpr uint32_t STAGE_BYTES = WINDOW + 256u;
 constexpr uint32_t STAGE_READ = WINDOW + 64u;
 
-struct SegMeta {          // LDS, one per worker: written at the end of matching, copied into the window's record (resolve_window) behind the matching barrier
+struct SegMeta {          // LDS, one per worker: written at the end of matching, copied into the window's record (resolve_window, the indexer) behind the matching barrier
     uint32_t has;         // the segment holds at least one match
     uint32_t first_lit;   // literals from the segment start to its first match
     uint32_t first_ml;    // that match's length (its token is written when the segments are placed)
@@ -1224,14 +1226,15 @@ __device__ __forceinline__ void put_len_header(g_u8* dst, uint32_t lit, uint32_t
 }
 
 // PLACING A WINDOW'S SEGMENTS happens in two parts (round 16).  resolve_window runs behind the matching barrier of window k (every
-// worker's SegMeta is final): sizes only -- where each segment's output starts and how many literals are pending in front of it --, left
+// worker's SegMeta is final), on the indexer wavefront while the workers load window k + 1 (round 23; the workers ran it until then, in
+// front of that load): sizes only -- where each segment's output starts and how many literals are pending in front of it --, left
 // with everything else the copies need in the window's record, PlaceRec k & 1 in LDS.  copy_segment moves one segment's bytes, needs
 // nothing from the LDS window, and runs a window later: a worker that is done matching its segment of window k + 1 draws segments of
 // window k from a ticket counter until none are left (wave_body), in the time it would otherwise wait at the barrier for the slowest
 // worker.  Before: barrier, place (wait for the own body stores, read the body back, copy literals, write), load, barrier -- ~30 k
-// cycles in which the indexer and the workers that were done stood still; now the part between the barriers is resolve + load.
+// cycles in which the indexer and the workers that were done stood still; now the part between the barriers is the load, with the resolve beside it.
 // PlaceRec, words: REC_SEG per segment {out_pos, pend, SegMeta}, then from REC_UNI on the uniform values below.
-constexpr uint32_t RU_COUNT = 0u;      // tickets: WORKERS, or 0 (a skipped item, no window yet)
+constexpr uint32_t RU_COUNT = 0u;      // tickets: WORKERS, or 0 (a skipped item, a window whose carry never came, no window yet)
 constexpr uint32_t RU_GIN = 1u;        // (two words) the item's first byte
 constexpr uint32_t RU_BLK_LEN = 3u;
 constexpr uint32_t RU_WIN_IDX = 4u;    // (which window of its block this is: kept for whoever reads a dump of the record, the copies do not need it)
@@ -1242,7 +1245,7 @@ constexpr uint32_t RU_WSKIP = 8u;
 constexpr uint32_t RU_SEND = 9u;
 constexpr uint32_t RU_GOUT = 10u;      // (two words)
 constexpr uint32_t RU_RUNWIN = 12u;
-constexpr uint32_t RU_POISONED = 13u;
+constexpr uint32_t RU_POISONED = 13u;   // (its carry never came, RU_COUNT is 0: like RU_WIN_IDX, for the reader of a dump)
 constexpr uint32_t RU_OUT_LEN = 14u;   // (two words)
 constexpr uint32_t RU_STATUS = 16u;    // (two words)
 static_assert(RU_STATUS + 2u == REC_WORDS - REC_UNI, "the record holds the uniform values");
@@ -1252,13 +1255,16 @@ __device__ __forceinline__ uint32_t seg_at(uint32_t j, uint32_t runwin, uint32_t
     return v < wl ? v : wl;
 }
 
-// Worker w's part of resolving the current window into record `rec_` (a word index into L_META): its segment's {out_pos, pend} and
-// SegMeta; the last worker hands the carry on; worker 0 writes the uniform values.
+// Resolving the current window into record `rec_` (a word index into L_META), by ONE wavefront: the indexer, which has nothing else to
+// do between a window's two barriers (round 23; until then every worker resolved its own segment there and the next window's load
+// waited for it).  Lane j < WORKERS holds SegMeta j after one LDS round trip, one uniform loop carries {out_pos, pend} over the
+// segments, lane j writes segment j's words, lane 0 the uniform values and the carry out.  A window whose carry never came (window
+// mode) has nothing to copy: its block gets status 66 here and its successors are told.
 __device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t rec_, const uint8_t* __restrict__ gin_, uint32_t blk_len_, uint32_t win_idx_, bool last_win_,
-                              uint32_t wl_, uint32_t wbase_, uint32_t wskip_, uint32_t send_, uint8_t* gout_, uint32_t carry_slot_, uint32_t w_, uint32_t lane,
-                              uint32_t* out_len_, int32_t* status_, uint32_t* gcarry_, uint32_t iter_, uint32_t spins_max_, uint32_t runwin_) {
+                              uint32_t wl_, uint32_t wbase_, uint32_t wskip_, uint32_t send_, uint8_t* gout_, uint32_t carry_slot_, uint32_t lane,
+                              uint32_t* out_len_, int32_t* status_, uint32_t* gcarry_, uint32_t spins_max_, uint32_t runwin_) {
     const uint32_t runwin = uni(runwin_);                          // a run window (index_window)
-    const uint32_t blk_len = uni(blk_len_), win_idx = uni(win_idx_), wl = uni(wl_), carry_slot = uni(carry_slot_), w = uni(w_);
+    const uint32_t blk_len = uni(blk_len_), win_idx = uni(win_idx_), wl = uni(wl_), carry_slot = uni(carry_slot_);
     const uint32_t wbase = uni(wbase_), wskip = uni(wskip_);       // the window's first byte in the block; its first wskip positions are history
     const uint32_t spins_max = uni(spins_max_);                    // CARRY_SPINS (tests: 1 -- a window gives up at once)
     const bool last_win = uni((uint32_t)last_win_) != 0u;
@@ -1266,6 +1272,9 @@ __device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t r
     const lds_u32* mp = (const lds_u32*)(lds + L_META);
     lds_u32* cp = (lds_u32*)(lds + L_META) + 5u * WORKERS;          // BlkCarry[2]
     lds_u32* rec = (lds_u32*)(lds + L_META) + uni(rec_);
+    // lane j holds the SegMeta of segment j (one LDS round trip for all of them; it is under way while the carry is fetched)
+    uint32_t m_has = 0u, m_fl = 0u, m_ml = 0u, m_tr = 0u, m_bl = 0u;
+    if (lane < WORKERS) { m_has = mp[5u * lane]; m_fl = mp[5u * lane + 1u]; m_ml = mp[5u * lane + 2u]; m_tr = mp[5u * lane + 3u]; m_bl = mp[5u * lane + 4u]; }
     // Where this window's output starts and how many literals the block has pending: from the previous window, which this
     // workgroup resolved itself (LDS) or, when the windows of a block are dealt to different workgroups (gcarry: a ring of
     // {out_pos, pend, window} records per block in the workspace), another one did -- that wait is bounded, a window that gives
@@ -1275,31 +1284,17 @@ __device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t r
     uint32_t out_pos = 0u, pend = 0u, poisoned = 0u;
     if (win_idx != 0u) {
         if (gcarry != nullptr) {
-            // ONE wavefront of the workgroup polls global memory (with all eight of all 512 workgroups polling the same few
-            // cache lines the carry took 60 microseconds per window to get through); the others wait for it in LDS
-            const uint32_t iter = uni(iter_);
-            typedef volatile __attribute__((address_space(3))) uint32_t lds_vu32;
-            lds_vu32* box = (lds_vu32*)(lds + L_META) + 5u * WORKERS + 8u;     // {out_pos, pend | poisoned << 31, iteration}
+            // this wavefront alone polls global memory (with every wavefront of all 512 workgroups polling the same few cache lines
+            // the carry took 60 microseconds per window to get through); the workers are loading the next window meanwhile
 #ifndef LZ4W_NO_PRIO
             __builtin_amdgcn_s_setprio(0);             // waiting is not work: the polls below must not issue before the CU's other workgroup's matching
 #endif
-            if (w == WORKERS - 1u) {
-                g_u32* sl = gcarry + 16u * (win_idx & (CARRY_SLOTS - 1u));
-                uint32_t spins = 0u;
-                while (__hip_atomic_load(sl + 2, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != win_idx && ++spins < spins_max) __builtin_amdgcn_s_sleep(16);
-                out_pos = __hip_atomic_load(sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pend = __hip_atomic_load(sl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (spins >= spins_max) pend = 0x80000000u;
-                if (lane == 0u) { box[0] = out_pos; box[1] = pend; }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (lane == 0u) box[2] = iter;
-            } else {
-                uint32_t spins = 0u;
-                while (box[2] != iter && ++spins < (CARRY_SPINS << 4)) __builtin_amdgcn_s_sleep(2);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                out_pos = box[0];
-                pend = spins >= (CARRY_SPINS << 4) ? 0x80000000u : box[1];
-            }
+            g_u32* sl = gcarry + 16u * (win_idx & (CARRY_SLOTS - 1u));
+            uint32_t spins = 0u;
+            while (__hip_atomic_load(sl + 2, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != win_idx && ++spins < spins_max) __builtin_amdgcn_s_sleep(16);
+            out_pos = __hip_atomic_load(sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pend = __hip_atomic_load(sl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (spins >= spins_max) pend = 0x80000000u;
 #ifndef LZ4W_NO_PRIO
             __builtin_amdgcn_s_setprio(3);
 #endif
@@ -1308,13 +1303,9 @@ __device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t r
             if (poisoned) { out_pos = 0u; pend = 0u; }
             out_pos = uni(out_pos); pend = uni(pend); poisoned = uni(poisoned);
         } else {
-            out_pos = cp[2u * (carry_slot ^ 1u)]; pend = cp[2u * (carry_slot ^ 1u) + 1u];
+            out_pos = uni(cp[2u * (carry_slot ^ 1u)]); pend = uni(cp[2u * (carry_slot ^ 1u) + 1u]);
         }
     }
-    // lane j holds the SegMeta of segment j (one LDS round trip for all of them, this is the serial part of a window); the prefix over
-    // the segments in front of this worker's is scalar
-    uint32_t m_has = 0u, m_fl = 0u, m_ml = 0u, m_tr = 0u, m_bl = 0u;
-    if (lane < WORKERS) { m_has = mp[5u * lane]; m_fl = mp[5u * lane + 1u]; m_ml = mp[5u * lane + 2u]; m_tr = mp[5u * lane + 3u]; m_bl = mp[5u * lane + 4u]; }
     auto behind = [&](uint32_t j, uint32_t& op, uint32_t& pd) {     // {out_pos, pend} in front of segment j -> behind it
         if (rdlane(m_has, j) != 0u) {
             const uint32_t L = pd + rdlane(m_fl, j);
@@ -1324,15 +1315,19 @@ __device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t r
             pd += seg_at(j + 1u, runwin, wl, wskip, send) - seg_at(j, runwin, wl, wskip, send);
         }
     };
-    for (uint32_t j = 0; j < w; ++j) behind(j, out_pos, pend);
-    if (lane == w) {
-        lds_u32* sg = rec + REC_SEG * w;
-        sg[0] = out_pos; sg[1] = pend; sg[2] = m_has; sg[3] = m_fl; sg[4] = m_ml; sg[5] = m_tr; sg[6] = m_bl;
+    uint32_t my_op = 0u, my_pd = 0u;                                // lane j: {out_pos, pend} in front of segment j
+    for (uint32_t j = 0; j < WORKERS; ++j) {
+        if (lane == j) { my_op = out_pos; my_pd = pend; }
+        behind(j, out_pos, pend);                                   // (behind the last segment: the next window's carry)
     }
-    if (w == 0u && lane == 0u) {
+    if (lane < WORKERS) {
+        lds_u32* sg = rec + REC_SEG * lane;
+        sg[0] = my_op; sg[1] = my_pd; sg[2] = m_has; sg[3] = m_fl; sg[4] = m_ml; sg[5] = m_tr; sg[6] = m_bl;
+    }
+    if (lane == 0u) {
         lds_u32* ru = rec + REC_UNI;
         const uint64_t pin = (uint64_t)gin_, pout = (uint64_t)gout_, plen = (uint64_t)out_len_, pst = (uint64_t)status_;
-        ru[RU_COUNT] = WORKERS;
+        ru[RU_COUNT] = poisoned ? 0u : WORKERS;
         ru[RU_GIN] = (uint32_t)pin; ru[RU_GIN + 1u] = (uint32_t)(pin >> 32);
         ru[RU_BLK_LEN] = blk_len; ru[RU_WIN_IDX] = win_idx; ru[RU_LAST_WIN] = last_win ? 1u : 0u;
         ru[RU_WL] = wl; ru[RU_WBASE] = wbase; ru[RU_WSKIP] = wskip; ru[RU_SEND] = send;
@@ -1340,20 +1335,24 @@ __device__ __attribute__((noinline)) void resolve_window(lds_u8* lds, uint32_t r
         ru[RU_RUNWIN] = runwin; ru[RU_POISONED] = poisoned;
         ru[RU_OUT_LEN] = (uint32_t)plen; ru[RU_OUT_LEN + 1u] = (uint32_t)(plen >> 32);
         ru[RU_STATUS] = (uint32_t)pst; ru[RU_STATUS + 1u] = (uint32_t)(pst >> 32);
+        if (poisoned) {
+            // a window never got its carry: launch_compress_wave's second launch encodes the block again (every later window of the
+            // block is poisoned too and writes the same two values)
+            *uni_gptr<g_u32>(out_len_) = 0u;
+            *uni_gptr<g_i32>(status_) = 66;
+        }
     }
-    uint32_t eo = out_pos, ep = pend;
-    if (w == WORKERS - 1u && !last_win) behind(w, eo, ep);
-    if (w == WORKERS - 1u && !last_win && lane == 0u) {
+    if (!last_win && lane == 0u) {
         // the next window's carry depends on sizes only: it is handed on here, a window before the bytes are copied (the windows of a
         // block form a chain through global memory; with the copies inside it a block advanced one window per 4 microseconds)
         if (gcarry != nullptr) {
             g_u32* so = gcarry + 16u * ((win_idx + 1u) & (CARRY_SLOTS - 1u));
-            __hip_atomic_store(so, eo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(so + 1, ep | (poisoned << 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(so, out_pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(so + 1, pend | (poisoned << 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(so + 2, win_idx + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-            cp[2u * carry_slot] = eo;
-            cp[2u * carry_slot + 1u] = ep;
+            cp[2u * carry_slot] = out_pos;
+            cp[2u * carry_slot + 1u] = pend;
         }
     }
 }
@@ -1435,10 +1434,9 @@ __device__ __attribute__((noinline)) void copy_segment(lds_u8* lds, uint32_t rec
     piece_store(gout + fin_at, fin_small ? pend : 0u, lane, pf);
     if (bl > 4096u) copy_bytes(gout + body_at + 4096u, body + 4096u, bl - 4096u, lane);
     if (fin) {
-        const uint32_t poisoned = rd(ru + RU_POISONED);
         g_u32* out_len = (g_u32*)rd_ptr(ru + RU_OUT_LEN);
         g_i32* status = (g_i32*)rd_ptr(ru + RU_STATUS);
-        if (lane == 0u) { *out_len = poisoned ? 0u : out_pos; *status = poisoned ? 66 /* a window never got its carry: launch_compress_wave's second launch encodes the block again */ : 0; }
+        if (lane == 0u) { *out_len = out_pos; *status = 0; }           // (a poisoned window has no tickets: resolve_window has left status 66)
     }
 }
 
@@ -1672,8 +1670,11 @@ __device__ __forceinline__ bool keep_hit(const SetArgs&, const Item& t, uint32_t
 
 // prof (nullable, tools only): cycle sums per role, [0] indexer busy, [1] indexer at barriers, [2] workers matching,
 // [3] workers at the barrier behind matching, [4] placing (the deferred copies of the window before, and the last window's copies),
-// [5] loading the next window, [6] at the barrier behind loading, [7] windows, [PROF_RESOLVE] resolving ([8 .. 26]: the variant builds')
+// [5] loading the next window, [6] at the barrier behind loading, [7] windows, [PROF_RESOLVE] the workers between the matching barrier
+// and the load (the ticket reset; until round 23 they resolved the window there), [PROF_IDX_RESOLVE] the indexer resolving the window
+// -- part of neither [0] nor [1] ([8 .. 26]: the variant builds')
 constexpr uint32_t PROF_RESOLVE = 27u;
+constexpr uint32_t PROF_IDX_RESOLVE = 28u;
 template <class A>
 __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, uint32_t* __restrict__ carry,
                                           unsigned long long* __restrict__ prof, const int32_t redo, const uint32_t carry_spins) {
@@ -1701,7 +1702,6 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
     Item it, ix;                                                  // the window being matched; the next one (the indexer runs one window ahead)
     lds_u32* meta = (lds_u32*)(lds + L_META);
     if (threadIdx.x == 0u) {
-        giq[6] = 0u;                                              // resolve_window's mailbox: no iteration yet
         meta[M_TICKET] = 0u;
         meta[M_REC + REC_UNI + RU_COUNT] = 0u;                    // no window to copy yet
         meta[M_REC + REC_WORDS + REC_UNI + RU_COUNT] = 0u;
@@ -1727,7 +1727,7 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
     if (it.blk >= a.n) return;
     uint32_t k = 0u;
 
-    lds_u32* run_flag = (lds_u32*)(lds + L_META) + 5u * WORKERS + 11u;   // [slot]: the window whose cand[] slot this would be is a run window
+    lds_u32* run_flag = (lds_u32*)(lds + L_META) + M_RUN;   // [slot]: the window whose cand[] slot this would be is a run window
     // shared-dictionary batches, the indexer wavefront (the only one that stages): bytes [0, h) of the staging slot hold the dictionary's
     // tail -- the first window of the previous item left them there and nothing has overwritten them since (a later window of a long
     // item does); the first window of the next item then stages the block part only
@@ -1814,8 +1814,23 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
     for (;;) {
         const uint32_t wl = win_len(it);
         const bool last_win = it.win + 1u == it.nwin;
+        // a copy ticket of the window before (record and body set (k - 1) & 1), one lane asks
+        const uint32_t crec = M_REC + ((k + 1u) & 1u) * REC_WORDS;
+        auto draw = [&]() -> uint32_t {
+            uint32_t t = 0u;
+            if (lane == 0u) t = __hip_atomic_fetch_add(meta + M_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            return uni(t);
+        };
         if (w == WORKERS) {
             if (ix.blk < a.n) do_index(ix, (k + 1u) & 1u, true);
+#ifdef LZ4W_EXP_IDX_TICKET   // tools: the indexer draws ONE copy ticket in its slack in front of the matching barrier (measured and not kept: profiles/r23_indexer_resolve.txt)
+            const uint32_t icnt = uni(meta[crec + REC_UNI + RU_COUNT]);
+            const uint32_t itk = icnt != 0u ? draw() : icnt;
+            if (itk < icnt) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                copy_segment(lds, crec, icnt - 1u - itk, bodies + (size_t)((k + 1u) & 1u) * BODY_SET, lane);
+            }
+#endif
         } else if (!it.skip) {
             const uint32_t base = win_base(it), skip = win_skip(it);
             uint32_t s0 = seg_start(w, skip, win_send(it));
@@ -1851,13 +1866,8 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
             // The copies of the window before (record and body set (k - 1) & 1; none: no tickets).  Every worker draws until the tickets
             // are gone, so all of them are done before the barrier below, which makes that record and that body set reusable.  The
             // bodies were stored by other wavefronts: their release is the fence in front of the barrier a window ago, the acquire here.
-            const uint32_t rec = M_REC + ((k + 1u) & 1u) * REC_WORDS;
+            const uint32_t rec = crec;
             const uint32_t cnt = uni(meta[rec + REC_UNI + RU_COUNT]);
-            auto draw = [&]() -> uint32_t {
-                uint32_t t = 0u;
-                if (lane == 0u) t = __hip_atomic_fetch_add(meta + M_TICKET, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                return uni(t);
-            };
             uint32_t t = cnt != 0u ? draw() : cnt;
             if (t < cnt) {
 #ifndef LZ4W_NO_PRIO
@@ -1882,21 +1892,35 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
             if (ix.blk < a.n) item_draw(a, wctr, ix.blk, b2, w2);
             giq[2] = b2; giq[3] = w2;
         }
+        // Between the barriers the workers only load the next window; the indexer, which would stand at the load barrier, resolves
+        // this one (record k & 1: read from the load barrier on -- the copy tickets a window later, or the workgroup's last window
+        // behind its extra barrier -- and the workers write SegMeta again only behind it).
         if (w != WORKERS) {
-            const uint32_t rec = M_REC + (k & 1u) * REC_WORDS;
             if (threadIdx.x == 0u) meta[M_TICKET] = 0u;            // (every draw of the window before precedes the barrier above)
+        } else {
+            const uint32_t rec = M_REC + (k & 1u) * REC_WORDS;
             if (it.skip) {
-                if (threadIdx.x == 0u) {
+                if (lane == 0u) {
                     a.out_len[it.blk] = 0u; a.status[it.blk] = ((HAS_DIGEST<A> || a.dict_len != nullptr) && it.skip == 2u) ? LZ4FLEX_DEV_E_INVALID_ARG : LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL;
                     meta[rec + REC_UNI + RU_COUNT] = 0u;           // nothing to copy
                 }
             } else {
+#ifndef LZ4W_NO_PRIO
+                __builtin_amdgcn_s_setprio(3);                     // the serial part of a window: the load barrier must not wait for this
+#endif
                 resolve_window(lds, rec, a.in_base + it.in_off, it.len, it.win, last_win, wl, win_base(it), win_skip(it), win_send(it),
-                               a.out_base + a.out_off[it.blk], k & 1u, w, lane, a.out_len + it.blk, a.status + it.blk,
-                               wmode ? carry + CARRY_DWORDS * (size_t)it.blk : nullptr, k + 1u, carry_spins, run_flag[k & 1u]);
+                               a.out_base + a.out_off[it.blk], k & 1u, lane, a.out_len + it.blk, a.status + it.blk,
+                               wmode ? carry + CARRY_DWORDS * (size_t)it.blk : nullptr, carry_spins, run_flag[k & 1u]);
+#ifndef LZ4W_NO_PRIO
+#ifdef LZ4W_EXP_IDX_PRIO
+                __builtin_amdgcn_s_setprio(LZ4W_EXP_IDX_PRIO);
+#else
+                __builtin_amdgcn_s_setprio(0);
+#endif
+#endif
             }
         }
-        tick(w == WORKERS ? 1u : 7u);
+        tick(7u);
         if (prof && threadIdx.x == 0u) atomicAdd(prof + 7, 1ull);
         it = ix;
         k += 1u;
@@ -1911,7 +1935,7 @@ __device__ __forceinline__ void wave_body(const A& a, uint8_t* __restrict__ ws, 
             }
             if (prof && lane == 0u)
                 for (uint32_t i = 0; i < 8u; ++i)
-                    if (t_acc[i] != 0ull) atomicAdd(prof + (i < 7u ? i : PROF_RESOLVE), (unsigned long long)t_acc[i]);
+                    if (t_acc[i] != 0ull) atomicAdd(prof + (i < 7u ? i : (w == WORKERS ? PROF_IDX_RESOLVE : PROF_RESOLVE)), (unsigned long long)t_acc[i]);
 #ifdef LZ4W_PROF_WORKERS    // tools: matching cycles per worker -> prof[16 + w] (the segment table above comes from these)
             if (prof && lane == 0u && w < WORKERS) atomicAdd(prof + 16u + w, (unsigned long long)t_acc[2]);
 #endif

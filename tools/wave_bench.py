@@ -73,10 +73,12 @@ def main():
         assert lib.lz4flex_debug_wave_prof(ctx, 0, vals) == 0
         v = list(vals)
         nw = max(v[7], 1)
-        # (sums over the worker wavefronts; "place": the deferred copies of the window before; [27]: lz4_compress_wave.hip PROF_RESOLVE)
+        # (sums over the worker wavefronts; "place": the deferred copies of the window before; [27], [28]: lz4_compress_wave.hip PROF_RESOLVE
+        # -- the workers between the matching barrier and the load -- and PROF_IDX_RESOLVE -- the indexer resolving the window, which is
+        # in neither idx_busy nor idx_barrier)
         names = ["idx_busy", "idx_barrier", "match(sum of workers)", "wait_after_match", "place(deferred copies)", "load_window", "wait_after_load"]
-        print("per window cycles: " + ", ".join("%s=%.0f" % (nm, x / nw) for nm, x in zip(names, v)) + ", resolve=%.0f" % (v[27] / nw) +
-              " windows=%d" % v[7], flush=True)
+        print("per window cycles: " + ", ".join("%s=%.0f" % (nm, x / nw) for nm, x in zip(names, v)) + ", resolve(sum of workers)=%.0f" % (v[27] / nw) +
+              ", idx_resolve=%.0f" % (v[28] / nw) + " windows=%d" % v[7], flush=True)
         if os.environ.get("LZ4W_PROF_WORKERS"):                  # -DLZ4W_PROF_WORKERS variant build
             print("matching cycles per window by worker: " + ", ".join("w%d=%.0f" % (i, x / nw) for i, x in enumerate(v[16:32]) if x), flush=True)
         elif v[13]:
