@@ -6,6 +6,7 @@ Options as the reference's: --clean (delete the original), -f/--force (overwrite
 Beyond the reference: --range OFF:LEN with a decompression writes just those bytes of the content (frame.FrameIndex.read: only the
 blocks the range touches are decoded; Independent frames; the content checksum is not verified); --high [--depth N] with a compression
 takes the deep-search encoder (block.set_compress_mode("high"), N candidates per position, default 16): smaller blocks, more encode time;
+--high --optimal parses its matches by price instead of lazily (block.set_compress_parse("optimal")): smaller again;
 --linked with a compression writes a Linked frame (BlockMode.Linked: a block's matches reach into the blocks in front of it), and --high
 --linked searches that history as deeply as the block (block.set_compress_high_linked(True)).
 """
@@ -102,6 +103,7 @@ def main(argv=None):
     ap.add_argument("--range", metavar="OFF:LEN", help="decompression: write only bytes [OFF, OFF + LEN) of the content")
     ap.add_argument("--high", action="store_true", help="compression: the deep-search encoder (smaller output, slower)")
     ap.add_argument("--depth", type=int, metavar="N", help="with --high: candidates examined per position, 1 .. 256 (default 16)")
+    ap.add_argument("--optimal", action="store_true", help="with --high: the optimal parse (smaller output again, slower)")
     ap.add_argument("--linked", action="store_true", help="compression: a Linked frame (blocks may refer to the blocks in front of them)")
     o = ap.parse_args(argv)
     byte_range = _parse_range(o.range) if o.range else None
@@ -109,12 +111,16 @@ def main(argv=None):
         raise SystemExit("--depth goes with --high")
     if o.depth is not None and not 1 <= o.depth <= 256:
         raise SystemExit("--depth wants 1 .. 256")
+    if o.optimal and not o.high:
+        raise SystemExit("--optimal goes with --high")
     if o.high:
         if o.decompress or (o.input_file and o.input_file.endswith(LZ_EXTENSION)):
             raise SystemExit("--high goes with a compression")
         block.set_compress_mode("high")
         if o.depth is not None:
             block.set_compress_depth(o.depth)
+        if o.optimal:
+            block.set_compress_parse("optimal")
         block.set_compress_high_linked(o.linked)
     if o.linked and (o.decompress or (o.input_file and o.input_file.endswith(LZ_EXTENSION))):
         raise SystemExit("--linked goes with a compression")

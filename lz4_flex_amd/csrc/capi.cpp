@@ -207,10 +207,10 @@ static int compress_high(lz4flex_ctx* c, const CompressArgs& a, const DictSource
     if (const int rc = wave_ws_acquire(c, s)) return rc;
     const size_t bytes = compress_wave_workspace_bytes(c->wave_wgs);
     const int wgs = c->wave_wgs / 2;
-    const uint32_t depth = (uint32_t)c->comp_depth;
-    hipError_t le = form == HighForm::History ? launch_compress_high_linked(a, c->wave_ws, bytes, wgs, depth, s)
-                    : form == HighForm::Dict  ? launch_compress_high_dict(a, d, c->comp_high_digest != 0, c->wave_ws, bytes, wgs, depth, s)
-                                              : launch_compress_high(a, c->wave_ws, bytes, wgs, depth, s);
+    const uint32_t depth = (uint32_t)c->comp_depth, parse = (uint32_t)c->comp_parse;
+    hipError_t le = form == HighForm::History ? launch_compress_high_linked(a, c->wave_ws, bytes, wgs, depth, parse, s)
+                    : form == HighForm::Dict  ? launch_compress_high_dict(a, d, c->comp_high_digest != 0, c->wave_ws, bytes, wgs, depth, parse, s)
+                                              : launch_compress_high(a, c->wave_ws, bytes, wgs, depth, parse, s);
     const hipError_t re = c->wave.release(s);
     return launched(le == hipSuccess ? re : le);
 }
@@ -381,6 +381,7 @@ int lz4flex_ctx_create(lz4flex_ctx** out, int device) {
     c->device = device;
     c->packed_tile = (int)PACKED_SCAN_TILE;
     if (const char* e = getenv("LZ4FLEX_COMPRESS_MODE")) c->comp_mode = (!strcmp(e, "exact") || !strcmp(e, "1")) ? 1 : (!strcmp(e, "high") || !strcmp(e, "2")) ? 2 : 0;
+    if (const char* e = getenv("LZ4FLEX_HIGH_PARSE")) c->comp_parse = (!strcmp(e, "optimal") || !strcmp(e, "1")) ? 1 : 0;
     if (const char* e = getenv("LZ4FLEX_HIGH_DICT")) c->comp_high_dict = !strcmp(e, "1") ? 1 : 0;
     if (const char* e = getenv("LZ4FLEX_HIGH_LINKED")) c->comp_high_linked = !strcmp(e, "1") ? 1 : 0;
     if (const char* e = getenv("LZ4FLEX_SLIDING_WINDOW")) {      // "0", "1" or "2", nothing else ("off" used to read as 0 silently: ADVICE r4)
@@ -487,6 +488,7 @@ const Setting SETTINGS[] = {
      }, false},
     {"compress_mode", &lz4flex_ctx::comp_mode, up_to_2, false},
     {"compress_depth", &lz4flex_ctx::comp_depth, [](int v) { return v >= 1 && v <= 256; }, false},      // "compress_mode" 2: candidates per position
+    {"compress_parse", &lz4flex_ctx::comp_parse, is_flag, false},                  // "compress_mode" 2: 0 = the one-step lazy parse, 1 = the optimal one
     {"compress_high_dict", &lz4flex_ctx::comp_high_dict, is_flag, false},          // "compress_mode" 2: dictionary calls take its dictionary form
     {"compress_high_linked", &lz4flex_ctx::comp_high_linked, is_flag, false},      // ... LZ4FLEX_BLOCK_HISTORY bits are read, Linked frames keep the mode
     {"compress_high_digest", &lz4flex_ctx::comp_high_digest, is_flag, false},      // ... and a shared dictionary is sorted once per call
@@ -2083,6 +2085,7 @@ int64_t lz4flex_compress_into_with_table(const uint8_t* in, size_t in_len, uint8
     if (rc) return rc;
     t->ctx->comp_mode = dc->comp_mode;                         // the thread's encoder choice (throughput / reference-exact / high)
     t->ctx->comp_depth = dc->comp_depth;
+    t->ctx->comp_parse = dc->comp_parse;
     t->ctx->comp_high_dict = dc->comp_high_dict;
     t->ctx->comp_high_linked = dc->comp_high_linked;
     t->ctx->comp_variant = dc->comp_variant;

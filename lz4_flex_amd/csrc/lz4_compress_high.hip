@@ -15,12 +15,14 @@
 //                counter columns in LDS, the arrays in the workgroup's slice of the workspace (L2).  Behind it the candidates of a position
 //                are its LEFT NEIGHBOURS in the sorted array, nearest first -- no chains to chase.
 //   3  match     a lane per sorted index: up to `depth` left neighbours, 8 bytes per compare step; best[] (length, offset) to the workspace
+//   3 1/2        ("compress_parse" 1 only: tests/sim/high_optimal_model.c) best[].len becomes len'[], the length the optimal parse takes at
+//                each position -- a backward pass over prices, a wavefront per segment of 2 048 positions (optimal_lengths)
 //   4  orbit     the parse is the orbit of the chunk's first position under next(p) (p + 1 for a literal, p + len for a match): a lane
 //                per tile of 64 positions computes every entry's exit (backwards, one pass), one lane hops from tile to tile, then a
 //                lane per entered tile counts and lists its matches (the window's LDS is free by then)
 //   5  sizes     a lane per sequence, a prefix sum
 //   6  emit      a lane per sequence; literal runs of 1 KiB or more are copied by the whole workgroup
-// Every step is a loop over items strided by the lanes, between workgroup barriers; no wavefront-level operation is used.
+// Every step but 3 1/2 is a loop over items strided by the lanes, between workgroup barriers, without wavefront-level operations.
 #include "lz4_device.h"
 #include <algorithm>
 
@@ -138,9 +140,88 @@ __device__ void sort_pass(const uint32_t* win, uint32_t mis, const uint16_t* src
     __syncthreads();
 }
 
-// is position j of the chunk a literal?  L = its best length, next = best length of j + 1 (csize: the chunk's size)
+// is position j of the chunk a literal?  L = its best length, next = best length of j + 1 (csize: the chunk's size).  PARSE 1: L is the
+// length the optimal parse chose for j, and that is all there is to read
+template <uint32_t PARSE = 0u>
 __device__ __forceinline__ bool is_literal(uint32_t j, uint32_t L, uint32_t next, uint32_t csize) {
+    if constexpr (PARSE != 0u) return L < 4u;
     return L < 4u || (j + 1u < csize && next > L);
+}
+
+// ---- "compress_parse" 1: the optimal parse (tests/sim/high_optimal_model.c), one wavefront per segment of SEG positions
+constexpr uint32_t SEG = 2048u, SHORT_MAX = 35u;
+constexpr uint32_t NO_CANDIDATE = 0x80000000u;
+static_assert(2u * CHUNK0 <= L_BIG_END, "a cost (u16) per position of the chunk takes the window's LDS");
+
+template <int CTRL, int ROWS = 0xf>
+__device__ __forceinline__ uint32_t dpp_or(uint32_t old, uint32_t v) {      // v moved by CTRL; a lane without a source (or outside ROWS): old
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, ROWS, 0xf, false);
+}
+// the minimum over the wavefront's 64 lanes, as a uniform value
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+    v = umin(v, dpp_or<0x111>(NONE, v));          // row_shr:1, 2, 4, 8: lane 15 of a row holds the row's minimum
+    v = umin(v, dpp_or<0x112>(NONE, v));
+    v = umin(v, dpp_or<0x114>(NONE, v));
+    v = umin(v, dpp_or<0x118>(NONE, v));
+    v = umin(v, dpp_or<0x142, 0xa>(NONE, v));     // row_bcast:15 into rows 1 and 3
+    v = umin(v, dpp_or<0x143, 0xc>(NONE, v));     // row_bcast:31 into rows 2 and 3: lane 63 holds the wavefront's
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// blen[0, cn) (best[].len of the chunk's positions) becomes len'[]; cost: u16[cn] of LDS.  Called by every lane of the workgroup, between
+// two barriers of the caller's.  Wavefront v takes the segments v, v + 16, ...: a segment reads and writes nothing of another one.
+//   lane k holds w = CO(j + 1 + k), the cost behind a sequence of k + 1 bytes at j (0 from the segment's end on), and prices one
+//   candidate: lane 0 the literal, lane l - 1 the match of l bytes -- a short one (4 <= l <= 35, l < L, l <= room) or the full one
+//   (l == L <= 64); a full length above 64 is priced in lane 63 from cost[j + L] in LDS.  The step is the minimum of (cost << 6) | rank
+//   (rank 0: the full length, 36 - l: a short one, 63: the literal -- the model's ties), then w moves up by one lane and lane 0
+//   takes the new cost.
+//   A segment goes in runs of 64 positions, lane i of a run = position jb + i: the lengths arrive, and the full length's price and the
+//   short lengths' limit are worked out, for 64 positions at once; a step reads its three values by lane number and leaves its
+//   minimum in lane i; the run's len'[] and costs are decoded and stored together.  (best[].len is 0 or at least 4.)
+__device__ void optimal_lengths(uint16_t* blen, uint32_t cn, uint16_t* cost) {
+    const uint32_t lane = threadIdx.x & 63u, l = lane + 1u;
+    // what the lane's literal / short match adds to w << 6, and its length for the limit (the literal: 0, below every limit)
+    const uint32_t own_add = lane == 0u ? (1u << 6) | 63u
+                             : (l >= 4u && l <= SHORT_MAX) ? ((3u + (l >= 19u ? 1u : 0u)) << 6) | (SHORT_MAX + 1u - l) : NO_CANDIDATE;
+    const uint32_t own_len = lane == 0u ? 0u : l;
+    const uint32_t nwave = blockDim.x >> 6, nseg = (cn + SEG - 1u) / SEG;
+    for (uint32_t sg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); sg < nseg; sg += nwave) {
+        const uint32_t s0 = sg * SEG, se = umin(s0 + SEG, cn);
+        const uint32_t nb = (se - s0 + 63u) >> 6;
+        uint32_t w = 0u;
+        uint32_t Lnext = s0 + (nb - 1u) * 64u + lane < se ? blen[s0 + (nb - 1u) * 64u + lane] : 0u;
+        for (uint32_t bk = nb; bk-- > 0u;) {
+            const uint32_t jb = s0 + bk * 64u;
+            const uint32_t Lv = Lnext;
+            Lnext = bk ? blen[jb - 64u + lane] : 0u;
+            const uint32_t roomv = se - (jb + lane);              // (lanes behind the segment's end: not read)
+            const uint32_t Lpv = umin(Lv, roomv);
+            const uint32_t fullv = (3u + ext_bytes(Lpv < 4u ? 0u : Lpv - 4u)) << 6;
+            const uint32_t limv = max(umin(Lv, roomv + 1u), 1u);  // a short l: l < L and l <= room; the literal always
+            uint32_t keyv = 0u;
+            for (uint32_t i = umin(64u, se - jb); i-- > 0u;) {
+                const uint32_t L = (uint32_t)__builtin_amdgcn_readlane((int)Lv, (int)i);
+                const uint32_t full = (uint32_t)__builtin_amdgcn_readlane((int)fullv, (int)i);
+                const uint32_t lim = (uint32_t)__builtin_amdgcn_readlane((int)limv, (int)i);
+                uint32_t add = own_len < lim ? own_add : NO_CANDIDATE;
+                add = l == L ? full : add;
+                uint32_t key = (w << 6) + add;
+                if (L > 64u) {                                    // (its cost lies in a run that is stored: j + L > jb + 63)
+                    const uint32_t x = jb + i + L;
+                    const uint32_t far = x < se ? cost[x] : 0u;
+                    if (lane == 63u) key = (far << 6) + full;
+                }
+                const uint32_t m = wave_min(key);
+                if (lane == i) keyv = m;
+                w = dpp_or<0x138>(m >> 6, w);                     // wave_shr:1; lane 0 keeps the new cost
+            }
+            if (jb + lane < se) {
+                const uint32_t r = keyv & 63u;
+                blen[jb + lane] = (uint16_t)(r == 0u ? Lv : (r == 63u ? 0u : SHORT_MAX + 1u - r));
+                cost[jb + lane] = (uint16_t)(keyv >> 6);
+            }
+        }
+    }
 }
 
 // The dictionary form's stage of chunk 0: the window is the dictionary's last H bytes (they end at dend, any alignment) and the block's
@@ -175,7 +256,8 @@ __device__ void stage_dict(uint32_t* win, uint32_t mis, const uint8_t* dend, uin
 // DICT: the block has the dictionary that ends at dend, its last H bytes are chunk 0's history (H == 0: none; the plain form's bytes).
 // dg_sorted / dg_start (nullable): the dictionary tail's digest (lz4_high_digest_kernel) -- chunk 0 sorts the block's positions only.
 // HIST (with DICT): the dictionary is the block's own stream in front of it, dend == the block's start (the history form).
-template <bool DICT, bool HIST = false>
+// PARSE: "compress_parse" -- 1 adds step 3 1/2 (optimal_lengths) and the walk reads its lengths without the lazy test.
+template <bool DICT, bool HIST = false, uint32_t PARSE = 0u>
 __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, uint8_t* ws, uint32_t depth, const uint8_t* dend = nullptr,
                                uint32_t H_ = 0u, const uint16_t* dg_sorted = nullptr, const uint16_t* dg_start = nullptr) {
     const uint32_t T = blockDim.x, t = threadIdx.x;
@@ -288,6 +370,12 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
         }
         __syncthreads();
 
+        // 3 1/2  the optimal parse: best[].len becomes len'[] (the window's LDS is dead, the exits take it behind the barrier)
+        if constexpr (PARSE != 0u) {
+            optimal_lengths(blen, cn, (uint16_t*)lds);
+            __syncthreads();
+        }
+
         // 4  orbit.  exitd[j]: where the walk that enters its tile at j leaves it, counted from the tile's end
         const uint32_t ntile = (cn + TILE - 1u) / TILE;
         for (uint32_t tl = t; tl < ntile; tl += T) {
@@ -296,7 +384,7 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
             uint32_t next = te < csize ? blen[te] : 0u;
             for (uint32_t j = te; j-- > ts;) {
                 const uint32_t L = blen[j];
-                const uint32_t nx = is_literal(j, L, next, csize) ? j + 1u : j + L;
+                const uint32_t nx = is_literal<PARSE>(j, L, next, csize) ? j + 1u : j + L;
                 exitd[j] = (uint16_t)(nx >= te ? nx - te : exitd[nx]);
                 next = L;
             }
@@ -316,7 +404,7 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
             if (entry[tl] != NONE)
                 for (uint32_t j = entry[tl]; j < te;) {
                     const uint32_t L = blen[j];
-                    if (is_literal(j, L, blen[j + 1u], csize)) ++j; else { ++c; j += L; }
+                    if (is_literal<PARSE>(j, L, blen[j + 1u], csize)) ++j; else { ++c; j += L; }
                 }
             tcnt[tl] = c;
         }
@@ -328,7 +416,7 @@ __device__ void compress_block(const CompressArgs& a, uint32_t b, uint8_t* lds, 
             if (entry[tl] != NONE)
                 for (uint32_t j = entry[tl]; j < te;) {
                     const uint32_t L = blen[j];
-                    if (is_literal(j, L, blen[j + 1u], csize)) ++j; else { seqpos[c++] = j; j += L; }
+                    if (is_literal<PARSE>(j, L, blen[j + 1u], csize)) ++j; else { seqpos[c++] = j; j += L; }
                 }
         }
         __syncthreads();
@@ -401,6 +489,15 @@ __global__ void __launch_bounds__(THREADS) lz4_compress_high_kernel(const Compre
         __syncthreads();
     }
 }
+// ("compress_parse" 1 has three kernels of its own, each written like its parse 0 one: behind a shared body the compiler gives the
+// parse 0 kernels other instruction streams than they had before the setting existed)
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_optimal_kernel(const CompressArgs a, uint8_t* ws, uint32_t depth) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        compress_block<false, false, 1u>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth);
+        __syncthreads();
+    }
+}
 
 // The dictionary form ("compress_high_dict" 1; the bytes: tests/sim/high_dict_model.c).  Block b's dictionary is the set's (d.set),
 // else the batch's one (d.shared), else a.dict_*; one of less than 4 bytes is none.  digest (nullable, with d.shared only): the slice
@@ -430,6 +527,30 @@ __global__ void __launch_bounds__(THREADS) lz4_compress_high_dict_kernel(const C
         __syncthreads();
     }
 }
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_dict_optimal_kernel(const CompressArgs a, const DictSource d, uint8_t* ws,
+                                                                                 const uint8_t* digest, uint32_t depth) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        const uint8_t* dict = nullptr;                            // (the ladder of lz4_compress_high_dict_kernel)
+        uint32_t dl = 0u;
+        bool ok = true;
+        if (d.has_set) ok = dict_set_find(d.set, b, dict, dl);
+        else if (d.shared) { dict = d.shared; dl = d.shared_len; }
+        else if (a.dict_len) {
+            dl = a.dict_len[b];
+            dict = a.dict_base + a.dict_off[b];
+            ok = dl == 0u || a.flags == nullptr || a.flags[b] == 0u;
+        }
+        if (!ok) {
+            if (threadIdx.x == 0u) { a.out_len[b] = 0u; a.status[b] = LZ4FLEX_DEV_E_INVALID_ARG; }
+            continue;
+        }
+        const uint32_t H = dl < 4u ? 0u : umin(dl, CHUNK);
+        compress_block<true, false, 1u>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth, dict + dl, H,
+                                        digest ? (const uint16_t*)(digest + W_SORT_A) : nullptr, (const uint16_t*)(digest + W_SORT_B));
+        __syncthreads();
+    }
+}
 
 // The history form ("compress_high_linked" 1): the dictionary form with block b's dictionary = the a.flags[b] >> 8 bytes of its own
 // stream in front of it (LZ4FLEX_BLOCK_HISTORY; the low byte is not read).  It ends where the block starts, so chunk 0's window is one
@@ -440,6 +561,15 @@ __global__ void __launch_bounds__(THREADS) lz4_compress_high_linked_kernel(const
         const uint32_t h = a.flags[b] >> 8;
         const uint32_t H = h < 4u ? 0u : umin(h, CHUNK);
         compress_block<true, true>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth, a.in_base + a.in_off[b], H);
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(THREADS) lz4_compress_high_linked_optimal_kernel(const CompressArgs a, uint8_t* ws, uint32_t depth) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
+    for (uint32_t b = blockIdx.x; b < a.n; b += gridDim.x) {
+        const uint32_t h = a.flags[b] >> 8;
+        const uint32_t H = h < 4u ? 0u : umin(h, CHUNK);
+        compress_block<true, true, 1u>(a, b, lds, ws + (size_t)blockIdx.x * WS_PER_WG, depth, a.in_base + a.in_off[b], H);
         __syncthreads();
     }
 }
@@ -481,41 +611,41 @@ __global__ void __launch_bounds__(THREADS) lz4_high_digest_kernel(const uint8_t*
 
 size_t compress_high_workspace_bytes(int n_workgroups) { return (size_t)n_workgroups * high::WS_PER_WG; }
 
-hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, hipStream_t s) {
+hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, uint32_t parse, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     const size_t fit = workspace_bytes / high::WS_PER_WG;
     const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
-    if (g == 0u || depth == 0u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(high::lz4_compress_high_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
+    if (g == 0u || depth == 0u || parse > 1u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(parse ? high::lz4_compress_high_optimal_kernel : high::lz4_compress_high_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
     return hipGetLastError();
 }
 
 hipError_t launch_compress_high_linked(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth,
-                                       hipStream_t s) {
+                                       uint32_t parse, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     const size_t fit = workspace_bytes / high::WS_PER_WG;
     const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
-    if (g == 0u || depth == 0u || a.flags == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(high::lz4_compress_high_linked_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
+    if (g == 0u || depth == 0u || parse > 1u || a.flags == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(parse ? high::lz4_compress_high_linked_optimal_kernel : high::lz4_compress_high_linked_kernel, dim3(g), dim3(high::THREADS), 0, s, a, (uint8_t*)workspace, depth);
     return hipGetLastError();
 }
 
 hipError_t launch_compress_high_dict(const CompressArgs& a, const DictSource& d, bool use_digest, void* workspace, size_t workspace_bytes,
-                                     int max_workgroups, uint32_t depth, hipStream_t s) {
+                                     int max_workgroups, uint32_t depth, uint32_t parse, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     // the digest is a property of the batch's ONE dictionary; it takes the last slice of the workspace
     const bool dg = use_digest && !d.has_set && d.shared != nullptr && d.shared_len >= 4u;
     size_t fit = workspace_bytes / high::WS_PER_WG;
     if (dg && fit) --fit;
     const uint32_t g = (uint32_t)std::min<size_t>(std::min<size_t>(a.n, fit), (size_t)(max_workgroups > 0 ? max_workgroups : 0));
-    if (g == 0u || depth == 0u) return hipErrorInvalidValue;
+    if (g == 0u || depth == 0u || parse > 1u) return hipErrorInvalidValue;
     uint8_t* digest = dg ? (uint8_t*)workspace + fit * high::WS_PER_WG : nullptr;
     if (dg) {
         hipLaunchKernelGGL(high::lz4_high_digest_kernel, dim3(1), dim3(high::THREADS), 0, s, d.shared, d.shared_len, digest);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(high::lz4_compress_high_dict_kernel, dim3(g), dim3(high::THREADS), 0, s, a, d, (uint8_t*)workspace, (const uint8_t*)digest, depth);
+    hipLaunchKernelGGL(parse ? high::lz4_compress_high_dict_optimal_kernel : high::lz4_compress_high_dict_kernel, dim3(g), dim3(high::THREADS), 0, s, a, d, (uint8_t*)workspace, (const uint8_t*)digest, depth);
     return hipGetLastError();
 }
 

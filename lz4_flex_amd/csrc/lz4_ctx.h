@@ -97,6 +97,7 @@ struct lz4flex_ctx {
     int comp_lanes = 8;           // lanes per block, encode
     int comp_mode = 0;            // 0 = throughput ("wave") encoder, own parse (default); 1 = reference-exact encoder (lz4_flex's bytes); 2 = high (lz4_compress_high.hip: deep search; which calls keep it and in which form is lz4_route.h encode_route, with the two settings below).  No call writes a setting: lz4flex_set_tuning, the constructor's environment reads and lz4flex_compress_into_with_table's copy are the writers
     int comp_depth = 16;          // "compress_depth": compress_mode 2, the candidates examined per position (1 .. 256)
+    int comp_parse = 0;           // "compress_parse": compress_mode 2, 0 = the one-step lazy parse (default), 1 = the optimal parse over the same best[] (tests/sim/high_optimal_model.c's bytes)
     int comp_high_dict = 0;       // "compress_high_dict": compress_mode 2, 1 = calls with dictionaries take the high encoder's dictionary form (tests/sim/high_dict_model.c's bytes); 0 = the throughput encoder (default)
     int comp_high_linked = 0;     // "compress_high_linked": compress_mode 2, 1 = LZ4FLEX_BLOCK_HISTORY bits are read (the block's history is its dictionary: tests/sim/high_dict_model.c's bytes) and Linked frames keep the mode; 0 = the bits are ignored, Linked frames take the throughput encoder (default)
     int comp_high_digest = 1;     // "compress_high_digest": the dictionary form, 1 = a shared dictionary's positions are sorted once per call; 0 = with every block's own (A/B measurements, tests)

@@ -237,20 +237,22 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
 // compress_mode 2 ("high", lz4_compress_high.hip): independent blocks without a dictionary, a.flags / slide / sub / dictionaries are not
 // read; the bytes are tests/sim/high_encoder_model.c's for (block, depth).  Persistent workgroups, one per block at a time, each with a
 // slice of `workspace` (compress_high_workspace_bytes(g) bytes for g of them): at most max_workgroups and as many as workspace_bytes holds
+// parse ("compress_parse"): 0 = the lazy parse, 1 = the optimal one (tests/sim/high_optimal_model.c's bytes, all three forms; kernels of
+// its own, the same workspace)
 size_t compress_high_workspace_bytes(int n_workgroups);
-hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, hipStream_t s);
+hipError_t launch_compress_high(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth, uint32_t parse, hipStream_t s);
 // its dictionary form ("compress_high_dict" 1): the bytes are tests/sim/high_dict_model.c's for (block, dictionary, depth).  Block b's
 // dictionary is block_dict(a, d, b)'s (a refused block: status LZ4FLEX_E_INVALID_ARG, out_len 0, nothing written); a block without one,
 // or with one of less than 4 bytes, gets the plain form's bytes.  use_digest (the shared dictionary only): a kernel in front sorts the
 // dictionary tail's positions once, into the last slice of `workspace`, and every block sorts its own positions alone; else every block
 // sorts the tail's with its own.
 hipError_t launch_compress_high_dict(const CompressArgs& a, const DictSource& d, bool use_digest, void* workspace, size_t workspace_bytes,
-                                     int max_workgroups, uint32_t depth, hipStream_t s);
+                                     int max_workgroups, uint32_t depth, uint32_t parse, hipStream_t s);
 // its history form ("compress_high_linked" 1): the dictionary form with block b's dictionary = the a.flags[b] >> 8 bytes of its own stream
 // in front of it (LZ4FLEX_BLOCK_HISTORY), readable at a.in_base + a.in_off[b] - h; the flag word's low byte and a's dictionaries are not
 // read, a.flags must not be null.  A block with h < 4 gets the plain form's bytes.
 hipError_t launch_compress_high_linked(const CompressArgs& a, void* workspace, size_t workspace_bytes, int max_workgroups, uint32_t depth,
-                                       hipStream_t s);
+                                       uint32_t parse, hipStream_t s);
 // a dictionary set's digests: bytes per dictionary, and the kernel that fills table[0 .. k)'s (a workgroup of one wavefront per
 // dictionary; cand_scratch: compress_wave_digest_scratch_bytes() bytes per dictionary, dead behind the launch)
 size_t compress_wave_digest_bytes();
