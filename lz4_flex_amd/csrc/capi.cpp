@@ -12,8 +12,8 @@
 //                    second pass behind every first-pass decoder); dict_source_of describes the batch's dictionaries (DictSource)
 //                    for both.  Which kernel a batch takes is decided in lz4_route.h alone: pure functions, tested on the CPU.
 // The context and the helpers shared with frame_many.cpp (OrderedWs: the rule that orders a per-context workspace across streams;
-// DeviceGuard, Layout, GrowBuf) are in lz4_ctx.h; the integer settings are one table (SETTINGS) that lz4flex_set_tuning and
-// lz4flex_get_tuning walk.
+// DeviceGuard, GrowBuf) are in lz4_ctx.h; how EVERY MEM_HOST call stages its columns and regions is lz4_host_stage.h (HostStage, opened
+// on a context by stage_open); the integer settings are one table (SETTINGS) that lz4flex_set_tuning and lz4flex_get_tuning walk.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -190,6 +190,15 @@ __global__ void __launch_bounds__(256) lz4flex_pack_results_kernel(const uint8_t
 static int ensure_buf(GrowBuf& b, size_t need) {
     const hipError_t e = b.ensure(need);
     return e == hipSuccess ? 0 : hip_fail(e, b.pinned ? "hipHostMalloc (staging)" : "hipMalloc (staging)");
+}
+
+// a MEM_HOST call's plan (lz4_host_stage.h) onto the context: the page-locked buffer holds the column image, the arena the regions
+static int stage_open(lz4flex_ctx* c, HostStage& st) {
+    int rc;
+    if ((rc = ensure_buf(c->pin, st.total()))) return rc;
+    if ((rc = ensure_buf(c->arena, st.arena_bytes))) return rc;
+    st.hp = c->pin.p; st.d = c->arena.p; st.s = c->stream;
+    return 0;
 }
 
 // the throughput encoder's workspace (it also holds the reference-exact mode's dictionary chain records): ordered across streams
@@ -636,11 +645,30 @@ Span span_of(const uint64_t* off, const uint32_t* len, uint32_t n) {
 }
 
 // host arrays are visible: a batch with a block beyond 64 KiB (compress) / 128 KiB compressed (decompress) is one of "large" blocks
-bool host_big(const BatchCall& b) {
-    const uint32_t limit = b.compress ? 65536u : 131072u;
+bool host_big(const uint32_t* len, uint32_t n, bool compress) {
+    const uint32_t limit = compress ? 65536u : 131072u;
     bool big = false;
-    for (uint32_t i = 0; i < b.n; i++) big |= b.in_len[i] > limit;
+    for (uint32_t i = 0; i < n; i++) big |= len[i] > limit;
     return big;
+}
+
+// a codec call's fetched result columns to the caller's arrays (detail: what a decoder reports, zero for compress)
+void copy_results(const BatchCall& b, const uint32_t* r_len, const int32_t* r_st, const uint64_t* r_det) {
+    memcpy(b.out_len, r_len, 4ull * b.n);
+    memcpy(b.status, r_st, 4ull * b.n);
+    if (!b.detail) return;
+    if (b.compress) memset(b.detail, 0, 16ull * b.n);
+    else memcpy(b.detail, r_det, 16ull * b.n);
+}
+
+// every block with status 0 (st null: every block) and a length goes from page-locked memory -- src_off(i) of `src` -- to its place in
+// the caller's buffer; nothing else of that buffer is written: a failed block and the gaps between blocks stay the caller's.  limit: the
+// bytes `src` holds, a block that ends behind them is left alone too
+template <class SrcOff>
+void scatter_good(uint8_t* out_base, const uint64_t* out_off, const uint32_t* len, const int32_t* st, uint32_t n, const uint8_t* src, SrcOff src_off,
+                  uint64_t limit = ~0ull) {
+    for (uint32_t i = 0; i < n; i++)
+        if ((!st || st[i] == 0) && len[i] && (uint64_t)src_off(i) + len[i] <= limit) memcpy(out_base + out_off[i], src + src_off(i), len[i]);
 }
 
 }  // namespace
@@ -649,7 +677,8 @@ bool host_big(const BatchCall& b) {
 // (descriptors + input, from page-locked staging), the kernels, ONE transfer down (results + output), one synchronisation -- the
 // general path below costs two transfers each way from pageable memory and two synchronisations (0.16 / 0.38 ms per 64 KiB block in
 // round 3).  Same semantics: a block that failed leaves the caller's bytes alone.  For batches without dictionaries, prefixes or a
-// chain only: run_host_batch sees to that.
+// chain only: run_host_batch sees to that.  The input blocks and the output slots are columns of the image here (64-byte starts, a slot
+// per block), and the image is the arena's one region.
 static constexpr uint32_t SMALL_BATCH_BLOCKS = 8u;
 static constexpr size_t SMALL_BATCH_BYTES = 4u << 20;
 static int run_host_small(lz4flex_ctx* c, const BatchCall& b) {
@@ -658,52 +687,40 @@ static int run_host_small(lz4flex_ctx* c, const BatchCall& b) {
     auto out_slot = [&](uint32_t i) { return align_up((size_t)b.out_cap[i] + 16, 64); };
     size_t in_bytes = 0, out_bytes = 0;
     for (uint32_t i = 0; i < n; i++) { in_bytes += in_slot(i); out_bytes += out_slot(i); }
-    // [up: in_off out_off in_len out_cap flags | input blocks]  [down: out_len status detail | output slots]
-    Layout l{64};
-    const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_in_len = l.take(4ull * n), at_out_cap = l.take(4ull * n),
-                 at_flags = l.take(4ull * n), at_in = l.take(in_bytes);
-    const size_t up_bytes = l.end;
-    const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n), at_out = l.take(out_bytes);
-    const size_t total = l.end;
+    HostStage st(64);
+    const auto in_off = st.up<uint64_t>(n), out_off = st.up<uint64_t>(n);
+    const auto in_len = st.up<uint32_t>(n), out_cap = st.up<uint32_t>(n), flags = st.up<uint32_t>(n);
+    const auto in = st.up<uint8_t>(in_bytes);
+    const auto out_len = st.down<uint32_t>(n);
+    const auto status = st.down<int32_t>(n);
+    const auto detail = st.down<uint64_t>(2ull * n);
+    const auto out = st.down<uint8_t>(out_bytes);
+    st.columns();
     int rc;
-    if ((rc = ensure_buf(c->pin, total))) return rc;
-    if ((rc = ensure_buf(c->arena, total + 256))) return rc;
-    uint8_t* hp = c->pin.p;
-    uint8_t* d = c->arena.p;
+    if ((rc = stage_open(c, st))) return rc;
+    uint64_t *const in_at = st.host(in_off), *const out_at = st.host(out_off);
     size_t ia = 0, oa = 0;
     for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = ia;
-        ((uint64_t*)(hp + at_out_off))[i] = oa;
-        ((uint32_t*)(hp + at_in_len))[i] = b.in_len[i];
-        ((uint32_t*)(hp + at_out_cap))[i] = b.out_cap[i];
-        ((uint32_t*)(hp + at_flags))[i] = b.flags ? b.flags[i] : 0u;
-        if (b.in_len[i]) memcpy(hp + at_in + ia, b.in_base + b.in_off[i], b.in_len[i]);
+        in_at[i] = ia;
+        out_at[i] = oa;
+        if (b.in_len[i]) memcpy(st.host(in) + ia, b.in_base + b.in_off[i], b.in_len[i]);
         ia += in_slot(i);
         oa += out_slot(i);
     }
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(d, hp, up_bytes, hipMemcpyHostToDevice, s));
+    st.fill(in_len, b.in_len); st.fill(out_cap, b.out_cap);
+    if (b.flags) st.fill(flags, b.flags); else st.zero(flags);
+    HIP_TRY(st.send_columns());
     // the batch as it lies in the arena
-    BatchCall dv = batch_of(b.compress, d + at_in, (const uint64_t*)(d + at_in_off), (const uint32_t*)(d + at_in_len), n, d + at_out,
-                            (const uint64_t*)(d + at_out_off), (const uint32_t*)(d + at_out_cap), (uint32_t*)(d + at_out_len),
-                            (int32_t*)(d + at_status), s);
-    dv.big = host_big(b); dv.partial = b.partial; dv.linked_frame = b.linked_frame;
-    dv.flags = b.flags ? (const uint32_t*)(d + at_flags) : nullptr;
-    dv.detail = (uint64_t*)(d + at_detail);
+    BatchCall dv = batch_of(b.compress, st.dev(in), st.dev(in_off), st.dev(in_len), n, st.dev(out), st.dev(out_off), st.dev(out_cap), st.dev(out_len),
+                            st.dev(status), st.s);
+    dv.big = host_big(b.in_len, n, b.compress); dv.partial = b.partial; dv.linked_frame = b.linked_frame;
+    dv.flags = b.flags ? st.dev(flags) : nullptr;
+    dv.detail = st.dev(detail);
     if ((rc = launch_batch(c, dv))) return rc;
-    HIP_TRY(hipMemcpyAsync(hp + at_out_len, d + at_out_len, total - at_out_len, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t* r_det = (const uint64_t*)(hp + at_detail);
-    oa = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t len = ((const uint32_t*)(hp + at_out_len))[i];
-        const int32_t st = ((const int32_t*)(hp + at_status))[i];
-        b.out_len[i] = len;
-        b.status[i] = st;
-        if (b.detail) { b.detail[2 * i] = b.compress ? 0 : r_det[2 * i]; b.detail[2 * i + 1] = b.compress ? 0 : r_det[2 * i + 1]; }
-        if (st == 0 && len) memcpy(b.out_base + b.out_off[i], hp + at_out + oa, len);
-        oa += out_slot(i);
-    }
+    HIP_TRY(st.fetch_columns(out_len));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    copy_results(b, st.host(out_len), st.host(status), st.host(detail));
+    scatter_good(b.out_base, b.out_off, st.host(out_len), st.host(status), n, st.host(out), [&](uint32_t i) { return out_at[i]; });
     return 0;
 }
 
@@ -740,73 +757,53 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
             if (!b.compress || b.dict_len[i]) dict_span.add(b.dict_off[i], b.dict_len[i]);
         dict_span = dict_span.closed();
     }
-    const size_t in_bytes = in_span.bytes(), out_bytes = out_span.bytes();
-    const size_t dict_bytes = has_shared ? (size_t)b.shared_len : has_dict ? dict_span.bytes() : 0;
-    // descriptor block (pinned host mirror and device copy share one layout)
-    Layout l{16};
-    const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_dict_off = l.take(has_dict ? 8ull * n : 0),
-                 at_in_len = l.take(4ull * n), at_out_cap = l.take(4ull * n), at_flags = l.take(b.flags ? 4ull * n : 0),
-                 at_dict_len = l.take(has_dict ? 4ull * n : 0), at_out_pos = l.take(has_pos ? 4ull * n : 0),
-                 at_dict_id = l.take(b.set ? 4ull * n : 0);
-    const size_t desc_in_bytes = l.end;
-    const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n);
-    const size_t desc_bytes = l.end;
+    const size_t out_bytes = out_span.bytes();
+    HostStage st;
+    const auto in_off = st.up<uint64_t>(n), out_off = st.up<uint64_t>(n), dict_off = st.up<uint64_t>(has_dict ? n : 0);
+    const auto in_len = st.up<uint32_t>(n), out_cap = st.up<uint32_t>(n), flags = st.up<uint32_t>(b.flags ? n : 0),
+               dict_len = st.up<uint32_t>(has_dict ? n : 0), out_pos = st.up<uint32_t>(has_pos ? n : 0), dict_id = st.up<uint32_t>(b.set ? n : 0);
+    const auto out_len = st.down<uint32_t>(n);
+    const auto status = st.down<int32_t>(n);
+    const auto detail = st.down<uint64_t>(2ull * n);
+    const Region r_in = st.region(in_span.bytes(), 64), r_out = st.region(out_bytes, 64),
+                 r_dict = st.region(has_shared ? (size_t)b.shared_len : has_dict ? dict_span.bytes() : 0, 64);
+    st.columns();
     int rc;
-    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
-    const size_t a_in = 0, a_out = align_up(in_bytes + 64, 256), a_dict = a_out + align_up(out_bytes + 64, 256),
-                 a_desc = a_dict + align_up(dict_bytes + 64, 256);
-    if ((rc = ensure_buf(c->arena, a_desc + desc_bytes + 256))) return rc;
-    uint8_t* hp = c->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = b.in_off[i] - in_span.lo;
-        ((uint64_t*)(hp + at_out_off))[i] = b.out_off[i] - out_span.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = b.in_len[i];
-        ((uint32_t*)(hp + at_out_cap))[i] = b.out_cap[i];
-        if (b.flags) ((uint32_t*)(hp + at_flags))[i] = b.flags[i];
-        if (has_dict) {
-            ((uint64_t*)(hp + at_dict_off))[i] = (b.compress && !b.dict_len[i]) ? 0u : b.dict_off[i] - dict_span.lo;
-            ((uint32_t*)(hp + at_dict_len))[i] = b.dict_len[i];
-        }
-        if (has_pos) ((uint32_t*)(hp + at_out_pos))[i] = b.out_pos[i];
-    }
-    if (b.set) memcpy(hp + at_dict_id, b.dict_id, 4ull * n);      // (the ids travel with the batch; the dictionaries are on the device already)
-    uint8_t* d = c->arena.p;
-    hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, b.in_base + in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
-    if (dict_bytes)
-        HIP_TRY(hipMemcpyAsync(d + a_dict, has_shared ? b.shared_dict : b.dict_base + dict_span.lo, dict_bytes, hipMemcpyHostToDevice, s));
+    if ((rc = stage_open(c, st))) return rc;
+    st.fill_offsets(in_off, b.in_off, in_span.lo); st.fill_offsets(out_off, b.out_off, out_span.lo);
+    st.fill_offsets(dict_off, b.dict_off, dict_span.lo, b.compress ? b.dict_len : nullptr);
+    st.fill(in_len, b.in_len); st.fill(out_cap, b.out_cap); st.fill(flags, b.flags); st.fill(dict_len, b.dict_len); st.fill(out_pos, b.out_pos);
+    st.fill(dict_id, b.dict_id);                                  // (the ids travel with the batch; the dictionaries are on the device already)
+    hipStream_t s = st.s;
+    HIP_TRY(st.send(r_in, b.in_base + in_span.lo));
+    HIP_TRY(st.send(r_dict, has_shared ? b.shared_dict : has_dict ? b.dict_base + dict_span.lo : nullptr));
     if (has_pos && out_bytes) {
         // prefix mode: the sink already holds bytes [0, out_pos) that matches may reference; in a chained batch only what lies
         // before the FIRST block's position exists yet (the rest is what the batch produces)
         const size_t up = b.chained ? std::min<size_t>(out_bytes, (size_t)(b.out_off[0] - out_span.lo) + b.out_pos[0]) : out_bytes;
-        if (up) HIP_TRY(hipMemcpyAsync(d + a_out, b.out_base + out_span.lo, up, hipMemcpyHostToDevice, s));
+        HIP_TRY(st.send(r_out, b.out_base + out_span.lo, up));
     }
-    HIP_TRY(hipMemcpyAsync(d + a_desc, hp, desc_in_bytes, hipMemcpyHostToDevice, s));
-    uint8_t* dd = d + a_desc;
+    HIP_TRY(st.send_columns());
     // the batch as it lies in the arena
-    BatchCall dv = batch_of(b.compress, d + a_in, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, d + a_out,
-                            (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap), (uint32_t*)(dd + at_out_len),
-                            (int32_t*)(dd + at_status), s);
-    dv.chained = b.chained; dv.big = host_big(b); dv.partial = b.partial; dv.linked_frame = b.linked_frame;
-    dv.flags = b.flags ? (const uint32_t*)(dd + at_flags) : nullptr;
-    dv.detail = (uint64_t*)(dd + at_detail);
-    if (has_dict) { dv.dict_base = d + a_dict; dv.dict_off = (const uint64_t*)(dd + at_dict_off); dv.dict_len = (const uint32_t*)(dd + at_dict_len); }
-    if (has_shared) { dv.shared_dict = d + a_dict; dv.shared_len = b.shared_len; }
-    if (has_pos) dv.out_pos = (const uint32_t*)(dd + at_out_pos);
-    if (b.set) { dv.set = b.set; dv.dict_id = (const uint32_t*)(dd + at_dict_id); }
+    BatchCall dv = batch_of(b.compress, st.dev(r_in), st.dev(in_off), st.dev(in_len), n, st.dev(r_out), st.dev(out_off), st.dev(out_cap),
+                            st.dev(out_len), st.dev(status), s);
+    dv.chained = b.chained; dv.big = host_big(b.in_len, n, b.compress); dv.partial = b.partial; dv.linked_frame = b.linked_frame;
+    dv.flags = st.dev_opt(flags);
+    dv.detail = st.dev(detail);
+    if (has_dict) { dv.dict_base = st.dev(r_dict); dv.dict_off = st.dev(dict_off); dv.dict_len = st.dev(dict_len); }
+    if (has_shared) { dv.shared_dict = st.dev(r_dict); dv.shared_len = b.shared_len; }
+    dv.out_pos = st.dev_opt(out_pos);
+    if (b.set) { dv.set = b.set; dv.dict_id = st.dev(dict_id); }
     if ((rc = launch_batch(c, dv))) return rc;
-    HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
+    HIP_TRY(st.fetch_columns(out_len));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t* r_len = (const uint32_t*)(hp + at_out_len);
-    const int32_t* r_st = (const int32_t*)(hp + at_status);
-    const uint64_t* r_det = (const uint64_t*)(hp + at_detail);
+    const uint32_t* r_len = st.host(out_len);
+    const int32_t* r_st = st.host(status);
+    copy_results(b, r_len, r_st, st.host(detail));
     uint64_t produced = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        b.out_len[i] = r_len[i];
-        b.status[i] = r_st[i];
-        if (b.detail) { b.detail[2 * i] = b.compress ? 0 : r_det[2 * i]; b.detail[2 * i + 1] = b.compress ? 0 : r_det[2 * i + 1]; }
+    for (uint32_t i = 0; i < n; i++)
         if (r_st[i] == 0) produced += r_len[i];
-    }
+    uint8_t* const d_out = st.dev(r_out);
     // copy results back: dense outputs in one transfer, sparse ones block by block
     if (out_bytes && produced * 2 >= out_bytes && !has_pos) {
         // every successful block owns [out_off, out_off+len); failed blocks must leave the caller's bytes alone
@@ -825,33 +822,25 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
         }
         all_ok = all_ok && cap_sum == (uint64_t)out_bytes;
         if (all_ok) {
-            if (out_bytes > short_tail) HIP_TRY(hipMemcpyAsync(b.out_base + out_span.lo, d + a_out, out_bytes - (size_t)short_tail, hipMemcpyDeviceToHost, s));
+            if (out_bytes > short_tail) HIP_TRY(hipMemcpyAsync(b.out_base + out_span.lo, d_out, out_bytes - (size_t)short_tail, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             return 0;
         }
     }
     // sparse results, many blocks: pack them on the device into the (now free) input region, one transfer to pinned
     // memory, scatter on the host.  A per-block hipMemcpy to pageable memory costs ~10 us each.
-    if (!has_pos && n >= 16u && produced != 0 && produced <= (uint64_t)align_up(in_bytes + 64, 256) &&
-        ensure_buf(c->pay, (size_t)produced) == 0) {
-        uint64_t* h_dense = (uint64_t*)(hp + at_detail);          // reuse the detail slot (16 B per block >= 8 B)
+    if (!has_pos && n >= 16u && produced != 0 && produced <= (uint64_t)r_in.room && ensure_buf(c->pay, (size_t)produced) == 0) {
+        uint64_t* h_dense = st.host(detail);                      // reuse the detail slot (16 B per block >= 8 B)
         uint64_t at = 0;
         for (uint32_t i = 0; i < n; i++) { h_dense[i] = at; if (r_st[i] == 0) at += r_len[i]; }
-        uint64_t* d_dense = (uint64_t*)(dd + at_detail);
-        HIP_TRY(hipMemcpyAsync(d_dense, h_dense, 8ull * n, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(lz4flex_pack_results_kernel, dim3(n), dim3(256), 0, s, d + a_out,
-                           (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_len),
-                           (const int32_t*)(dd + at_status), d_dense, d + a_in, n);
+        HIP_TRY(hipMemcpyAsync(st.dev(detail), h_dense, 8ull * n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(lz4flex_pack_results_kernel, dim3(n), dim3(256), 0, s, d_out, st.dev(out_off), st.dev(out_len), st.dev(status),
+                           st.dev(detail), st.dev(r_in), n);
         const hipError_t pe = hipGetLastError();              // (reading it clears it: read once)
         if (pe != hipSuccess) return hip_fail(pe, "pack kernel launch");
-        HIP_TRY(hipMemcpyAsync(c->pay.p, d + a_in, (size_t)produced, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(c->pay.p, st.dev(r_in), (size_t)produced, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        at = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            if (r_st[i] != 0 || r_len[i] == 0) continue;
-            memcpy(b.out_base + b.out_off[i], c->pay.p + at, r_len[i]);
-            at += r_len[i];
-        }
+        scatter_good(b.out_base, b.out_off, r_len, r_st, n, c->pay.p, [&](uint32_t i) { return h_dense[i]; });
         return 0;
     }
     if (b.chained) {
@@ -859,15 +848,14 @@ static int run_host_batch(lz4flex_ctx* c, const BatchCall& b) {
         uint64_t lo = b.out_off[0] + b.out_pos[0], hi = lo;
         for (uint32_t i = 0; i < n; i++)
             if (r_st[i] == 0) hi = std::max<uint64_t>(hi, b.out_off[i] + b.out_pos[i] + r_len[i]);
-        if (hi > lo) HIP_TRY(hipMemcpyAsync(b.out_base + lo, d + a_out + (lo - out_span.lo), (size_t)(hi - lo), hipMemcpyDeviceToHost, s));
+        if (hi > lo) HIP_TRY(hipMemcpyAsync(b.out_base + lo, d_out + (lo - out_span.lo), (size_t)(hi - lo), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return 0;
     }
     for (uint32_t i = 0; i < n; i++) {
         if (r_st[i] != 0 || r_len[i] == 0) continue;
         const uint32_t pos = has_pos ? b.out_pos[i] : 0u;
-        HIP_TRY(hipMemcpyAsync(b.out_base + b.out_off[i] + pos, d + a_out + (b.out_off[i] - out_span.lo) + pos, r_len[i],
-                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(b.out_base + b.out_off[i] + pos, d_out + (b.out_off[i] - out_span.lo) + pos, r_len[i], hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
@@ -1215,35 +1203,23 @@ int lz4flex_decompressed_size_batch(lz4flex_ctx* ctx, const void* in_base, const
     DeviceGuard guard(ctx->device);
     HIP_TRY(guard.err);
     const Span sp = span_of(in_off, in_len, n);
-    const size_t in_bytes = sp.bytes();
-    // [in_off in_len history | out_size status], the same layout in pinned memory and behind the input in the arena
-    Layout l{16};
-    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n), at_hist = l.take(history ? 4ull * n : 0);
-    const size_t up_bytes = l.end;
-    const size_t at_size = l.take(8ull * n), at_status = l.take(4ull * n);
-    const size_t desc_bytes = l.end;
-    if ((rc = ensure_buf(ctx->pin, desc_bytes))) return rc;
-    const size_t a_desc = align_up(in_bytes + 64, 256);
-    if ((rc = ensure_buf(ctx->arena, a_desc + desc_bytes + 256))) return rc;
-    uint8_t* hp = ctx->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
-        if (history) ((uint32_t*)(hp + at_hist))[i] = history[i];
-    }
-    uint8_t* d = ctx->arena.p;
-    uint8_t* dd = d + a_desc;
-    hipStream_t s = ctx->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
-    const hipError_t le = launch_size_scan(d, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len),
-                                           history ? (const uint32_t*)(dd + at_hist) : nullptr, n, (uint64_t*)(dd + at_size),
-                                           (int32_t*)(dd + at_status), ctx->size_serial, s);
+    HostStage st;
+    const auto c_off = st.up<uint64_t>(n);
+    const auto c_len = st.up<uint32_t>(n), c_hist = st.up<uint32_t>(history ? n : 0);
+    const auto c_size = st.down<uint64_t>(n);
+    const auto c_status = st.down<int32_t>(n);
+    const Region r_in = st.region(sp.bytes(), 64);
+    st.columns();
+    if ((rc = stage_open(ctx, st))) return rc;
+    st.fill_offsets(c_off, in_off, sp.lo); st.fill(c_len, in_len); st.fill(c_hist, history);
+    HIP_TRY(st.send(r_in, (const uint8_t*)in_base + sp.lo));
+    HIP_TRY(st.send_columns());
+    const hipError_t le = launch_size_scan(st.dev(r_in), st.dev(c_off), st.dev(c_len), st.dev_opt(c_hist), n, st.dev(c_size), st.dev(c_status),
+                                           ctx->size_serial, st.s);
     if (le != hipSuccess) return hip_fail(le, "size scan launch");
-    HIP_TRY(hipMemcpyAsync(hp + at_size, dd + at_size, desc_bytes - at_size, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out_size, hp + at_size, 8ull * n);
-    memcpy(status, hp + at_status, 4ull * n);
+    HIP_TRY(st.fetch_columns(c_size));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    st.read(c_size, out_size); st.read(c_status, status);
     return 0;
 }
 
@@ -1317,8 +1293,7 @@ int packed_scatter_to_host(lz4flex_ctx* c, const uint8_t* d_out, uint64_t used, 
     if ((rc = ensure_buf(c->pay, (size_t)used))) return rc;
     HIP_TRY(hipMemcpyAsync(c->pay.p, d_out, (size_t)used, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; i++)
-        if (st[i] == 0 && len[i] && off[i] + len[i] <= used) memcpy(out_base + off[i], c->pay.p + off[i], len[i]);
+    scatter_good(out_base, off, len, st, n, c->pay.p, [&](uint32_t i) { return off[i]; }, used);
     return 0;
 }
 
@@ -1351,38 +1326,30 @@ int lz4flex_decompress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const
                    out_len, status, detail, work, k.big, (hipStream_t)hip_stream};
     if (k.where == Mem::Device) return (rc = packed_decode_layout(ctx, d)) ? rc : packed_decode_run(ctx, d);
 
-    // MEM_HOST: [input span | descriptors up, results down | work] in the arena; the output buffer is sized once the layout is known
+    // MEM_HOST: the work area behind the columns; the output buffer (scratch slot 0) is sized once the layout is known
     lz4flex_ctx* c = ctx;
     DeviceGuard guard(c->device);
     HIP_TRY(guard.err);
     const Span sp = span_of(in_off, in_len, n);
-    const size_t in_bytes = sp.bytes();
-    const bool given = size_mode == LZ4FLEX_SIZES_GIVEN;
-    Layout l{16};
-    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n), at_sizes = l.take(given ? 4ull * n : 0);
-    const size_t up_bytes = l.end;
-    const size_t at_out_off = l.take(8ull * n + 8), at_out_cap = l.take(4ull * n), at_out_len = l.take(4ull * n), at_status = l.take(4ull * n),
-                 at_detail = l.take(16ull * n);
-    const size_t desc_bytes = l.end;
-    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
-    const size_t a_desc = align_up(in_bytes + 64, 256), a_work = a_desc + align_up(desc_bytes, 256);
-    if ((rc = ensure_buf(c->arena, a_work + packed_work_bytes(n) + 256))) return rc;
-    uint8_t* hp = c->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
-        if (given) ((uint32_t*)(hp + at_sizes))[i] = sizes[i];
-    }
-    uint8_t* dv = c->arena.p;
-    uint8_t* dd = dv + a_desc;
-    hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(dv, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
-    d.in_base = dv; d.in_off = (const uint64_t*)(dd + at_in_off); d.in_len = (const uint32_t*)(dd + at_in_len);
-    d.sizes = given ? (const uint32_t*)(dd + at_sizes) : nullptr;
-    d.out_off = (uint64_t*)(dd + at_out_off); d.out_cap = (uint32_t*)(dd + at_out_cap); d.out_len = (uint32_t*)(dd + at_out_len);
-    d.status = (int32_t*)(dd + at_status); d.detail = (uint64_t*)(dd + at_detail); d.work = dv + a_work; d.stream = s;
-    d.big = k.big || [&] { bool big = false; for (uint32_t i = 0; i < n; i++) big |= in_len[i] > 131072u; return big; }();
+    HostStage st;
+    const auto c_in_off = st.up<uint64_t>(n);
+    const auto c_in_len = st.up<uint32_t>(n), c_sizes = st.up<uint32_t>(size_mode == LZ4FLEX_SIZES_GIVEN ? n : 0);
+    const auto c_out_off = st.down<uint64_t>(n + 1ull);
+    const auto c_out_cap = st.down<uint32_t>(n), c_out_len = st.down<uint32_t>(n);
+    const auto c_status = st.down<int32_t>(n);
+    const auto c_detail = st.down<uint64_t>(2ull * n);
+    const Region r_in = st.region(sp.bytes(), 64);
+    st.columns();
+    const Region r_work = st.region(packed_work_bytes(n), 0);
+    if ((rc = stage_open(c, st))) return rc;
+    st.fill_offsets(c_in_off, in_off, sp.lo); st.fill(c_in_len, in_len); st.fill(c_sizes, sizes);
+    hipStream_t s = st.s;
+    HIP_TRY(st.send(r_in, (const uint8_t*)in_base + sp.lo));
+    HIP_TRY(st.send_columns());
+    d.in_base = st.dev(r_in); d.in_off = st.dev(c_in_off); d.in_len = st.dev(c_in_len); d.sizes = st.dev_opt(c_sizes);
+    d.out_off = st.dev(c_out_off); d.out_cap = st.dev(c_out_cap); d.out_len = st.dev(c_out_len);
+    d.status = st.dev(c_status); d.detail = st.dev(c_detail); d.work = st.dev(r_work); d.stream = s;
+    d.big = k.big || host_big(in_len, n, false);
     if ((rc = packed_decode_layout(c, d))) return rc;
     uint64_t need = 0;
     HIP_TRY(hipMemcpyAsync(&need, d.out_off + n, 8, hipMemcpyDeviceToHost, s));
@@ -1392,13 +1359,10 @@ int lz4flex_decompress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const
     if ((rc = ctx_scratch(c, 0, (size_t)used + 256, &d_out))) return rc;
     d.out_base = (uint8_t*)d_out;
     if ((rc = packed_decode_run(c, d))) return rc;
-    HIP_TRY(hipMemcpyAsync(hp + at_out_off, dd + at_out_off, desc_bytes - at_out_off, hipMemcpyDeviceToHost, s));
+    HIP_TRY(st.fetch_columns(c_out_off));
     HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out_off, hp + at_out_off, 8ull * n + 8);
-    memcpy(out_cap, hp + at_out_cap, 4ull * n);
-    memcpy(out_len, hp + at_out_len, 4ull * n);
-    memcpy(status, hp + at_status, 4ull * n);
-    if (detail) memcpy(detail, hp + at_detail, 16ull * n);
+    st.read(c_out_off, out_off); st.read(c_out_cap, out_cap); st.read(c_out_len, out_len); st.read(c_status, status);
+    if (detail) st.read(c_detail, detail);
     return packed_scatter_to_host(c, (const uint8_t*)d_out, used, (uint8_t*)out_base, out_off, out_len, status, n);
 }
 
@@ -1419,8 +1383,8 @@ int lz4flex_compress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const u
             const uint64_t slot = lz4flex_get_maximum_output_size(in_len[i]) + prefix;
             slots += slot;
             packed_bound += (slot + align - 1u) & ~(uint64_t)(align - 1u);
-            big |= in_len[i] > 65536u;
         }
+        big = big || host_big(in_len, n, true);
         if (scratch_cap < slots) return -LZ4FLEX_E_INVALID_ARG;
     }
     int rc;
@@ -1429,52 +1393,43 @@ int lz4flex_compress_batch_packed(lz4flex_ctx* ctx, const void* in_base, const u
                      out_off, out_len, status, work, big, (hipStream_t)hip_stream};
     if (k.where == Mem::Device) return packed_compress_run(ctx, d);
 
-    // MEM_HOST: [input span | descriptors up, results down | work] in the arena, the scratch slots and the packed stream in the context's scratch
+    // MEM_HOST: the work area behind the columns, the scratch slots and the packed stream in the context's scratch slots 0 and 1
     lz4flex_ctx* c = ctx;
     DeviceGuard guard(c->device);
     HIP_TRY(guard.err);
     const Span sp = span_of(in_off, in_len, n);
-    const size_t in_bytes = sp.bytes();
-    Layout l{16};
-    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n);
-    const size_t up_bytes = l.end;
-    const size_t at_out_off = l.take(8ull * n + 8), at_out_len = l.take(4ull * n), at_status = l.take(4ull * n);
-    const size_t desc_bytes = l.end;
-    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
-    const size_t a_desc = align_up(in_bytes + 64, 256), a_work = a_desc + align_up(desc_bytes, 256);
-    if ((rc = ensure_buf(c->arena, a_work + packed_work_bytes(n) + 256))) return rc;
+    HostStage st;
+    const auto c_in_off = st.up<uint64_t>(n);
+    const auto c_in_len = st.up<uint32_t>(n);
+    const auto c_out_off = st.down<uint64_t>(n + 1ull);
+    const auto c_out_len = st.down<uint32_t>(n);
+    const auto c_status = st.down<int32_t>(n);
+    const Region r_in = st.region(sp.bytes(), 64);
+    st.columns();
+    const Region r_work = st.region(packed_work_bytes(n), 0);
+    if ((rc = stage_open(c, st))) return rc;
     const uint64_t out_bytes = std::min<uint64_t>(packed_bound, total_cap);
     void *d_scratch = nullptr, *d_out = nullptr;
     if ((rc = ctx_scratch(c, 0, (size_t)slots + 256, &d_scratch))) return rc;
     if ((rc = ctx_scratch(c, 1, (size_t)out_bytes + 256, &d_out))) return rc;
-    uint8_t* hp = c->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
-    }
-    uint8_t* dv = c->arena.p;
-    uint8_t* dd = dv + a_desc;
-    hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(dv, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
-    d.in_base = dv; d.in_off = (const uint64_t*)(dd + at_in_off); d.in_len = (const uint32_t*)(dd + at_in_len);
+    st.fill_offsets(c_in_off, in_off, sp.lo); st.fill(c_in_len, in_len);
+    HIP_TRY(st.send(r_in, (const uint8_t*)in_base + sp.lo));
+    HIP_TRY(st.send_columns());
+    d.in_base = st.dev(r_in); d.in_off = st.dev(c_in_off); d.in_len = st.dev(c_in_len);
     d.scratch = (uint8_t*)d_scratch; d.scratch_cap = slots; d.out_base = (uint8_t*)d_out;
-    d.out_off = (uint64_t*)(dd + at_out_off); d.out_len = (uint32_t*)(dd + at_out_len); d.status = (int32_t*)(dd + at_status);
-    d.work = dv + a_work; d.stream = s;
+    d.out_off = st.dev(c_out_off); d.out_len = st.dev(c_out_len); d.status = st.dev(c_status);
+    d.work = st.dev(r_work); d.stream = st.s;
     if ((rc = packed_compress_run(c, d))) return rc;
-    HIP_TRY(hipMemcpyAsync(hp + at_out_off, dd + at_out_off, desc_bytes - at_out_off, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(out_off, hp + at_out_off, 8ull * n + 8);
-    memcpy(out_len, hp + at_out_len, 4ull * n);
-    memcpy(status, hp + at_status, 4ull * n);
+    HIP_TRY(st.fetch_columns(c_out_off));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    st.read(c_out_off, out_off); st.read(c_out_len, out_len); st.read(c_status, status);
     return packed_scatter_to_host(c, (const uint8_t*)d_out, std::min<uint64_t>(out_off[n], out_bytes), (uint8_t*)out_base, out_off, out_len, status, n);
 }
 
 // ---- a dictionary from a batch of samples (lz4_dict_train.hip) -------------------------------------------------------------------
 size_t lz4flex_dict_train_work_size(uint32_t n) { return dict_train_work_bytes(n); }
 
-// DEVICE: the launches on the caller's stream, nothing else.  HOST: [input span | in_off in_len | dict_len status dict | work] in the
-// arena, one transfer down (the two words and dict_cap bytes), one synchronisation.
+// DEVICE: the launches on the caller's stream, nothing else.  HOST: one transfer down (the two words and dict_cap bytes), one synchronisation.
 int lz4flex_dict_train(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, void* dict_out,
                        uint32_t dict_cap, uint32_t segment, uint32_t* dict_len, int32_t* status, void* work, int mem_kind, void* hip_stream) {
     if (segment != 0u && (segment < 64u || segment > 2048u)) return -LZ4FLEX_E_INVALID_ARG;
@@ -1496,33 +1451,26 @@ int lz4flex_dict_train(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in
     DeviceGuard guard(ctx->device);
     HIP_TRY(guard.err);
     const Span sp = span_of(in_off, in_len, n);
-    const size_t in_bytes = sp.bytes();
-    Layout l{16};
-    const size_t at_in_off = l.take(8ull * n), at_in_len = l.take(4ull * n);
-    const size_t up_bytes = l.end;
-    const size_t at_res = l.take(8), at_dict = l.take(dict_cap);
-    const size_t desc_bytes = l.end;
-    if ((rc = ensure_buf(ctx->pin, desc_bytes))) return rc;
-    const size_t a_desc = align_up(in_bytes + 64, 256), a_work = a_desc + align_up(desc_bytes, 256);
-    if ((rc = ensure_buf(ctx->arena, a_work + dict_train_work_bytes(n) + 256))) return rc;
-    uint8_t* hp = ctx->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = in_off[i] - sp.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = in_len[i];
-    }
-    uint8_t* d = ctx->arena.p;
-    uint8_t* dd = d + a_desc;
-    hipStream_t s = ctx->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d, (const uint8_t*)in_base + sp.lo, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
-    const hipError_t le = launch_dict_train(d, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, dd + at_dict, dict_cap, seg,
-                                            (uint32_t*)(dd + at_res), (int32_t*)(dd + at_res + 4), d + a_work, s);
+    HostStage st;
+    const auto c_in_off = st.up<uint64_t>(n);
+    const auto c_in_len = st.up<uint32_t>(n);
+    const auto c_res = st.down<uint32_t>(2);                  // two words side by side: the length, the status
+    const auto c_dict = st.down<uint8_t>(dict_cap);
+    const Region r_in = st.region(sp.bytes(), 64);
+    st.columns();
+    const Region r_work = st.region(dict_train_work_bytes(n), 0);
+    if ((rc = stage_open(ctx, st))) return rc;
+    st.fill_offsets(c_in_off, in_off, sp.lo); st.fill(c_in_len, in_len);
+    HIP_TRY(st.send(r_in, (const uint8_t*)in_base + sp.lo));
+    HIP_TRY(st.send_columns());
+    const hipError_t le = launch_dict_train(st.dev(r_in), st.dev(c_in_off), st.dev(c_in_len), n, st.dev(c_dict), dict_cap, seg, st.dev(c_res),
+                                            (int32_t*)(st.dev(c_res) + 1), st.dev(r_work), st.s);
     if (le != hipSuccess) return hip_fail(le, "dict train launch");
-    HIP_TRY(hipMemcpyAsync(hp + at_res, dd + at_res, desc_bytes - at_res, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    memcpy(dict_len, hp + at_res, 4);
-    memcpy(status, hp + at_res + 4, 4);
-    if (*dict_len) memcpy(dict_out, hp + at_dict, std::min<uint32_t>(*dict_len, dict_cap));
+    HIP_TRY(st.fetch_columns(c_res));
+    HIP_TRY(hipStreamSynchronize(st.s));
+    *dict_len = st.host(c_res)[0];
+    *status = (int32_t)st.host(c_res)[1];
+    if (*dict_len) st.read(c_dict, (uint8_t*)dict_out, std::min<uint32_t>(*dict_len, dict_cap));
     return 0;
 }
 
@@ -1567,10 +1515,9 @@ int typed_on_device(lz4flex_ctx* c, Typed op, BatchCall b, int filter, uint32_t 
     return launch_filter_checked(c, tmp_base, tmp_off, b.out_len, b.status, out_base, out_off, b.n, filter, elem, true, s);
 }
 
-// MEM_HOST: [input span | tmp slots | output span | descriptors up, results down] in the arena -- the tmp slots mirror the input span
-// (compress) or the output span (decompress) -- one synchronisation for the results, one for the output span, which comes down to
-// page-locked memory; every block that has bytes (Filter: all of them; else status 0) is copied to its place, the rest of the caller's
-// buffer stays as it is.
+// MEM_HOST: the tmp slots mirror the input span (compress) or the output span (decompress); one synchronisation; the output span comes
+// down to page-locked memory and every block that has bytes (Filter: all of them; else status 0) is copied to its place, the rest of the
+// caller's buffer stays as it is.
 int typed_on_host(lz4flex_ctx* c, Typed op, const BatchCall& b, int filter, uint32_t elem, bool inverse, bool big) {
     const uint32_t n = b.n;
     DeviceGuard guard(c->device);
@@ -1579,53 +1526,36 @@ int typed_on_host(lz4flex_ctx* c, Typed op, const BatchCall& b, int filter, uint
     const Span in_span = span_of(b.in_off, b.in_len, n);
     const Span out_span = span_of(b.out_off, codec ? b.out_cap : b.in_len, n);
     const size_t in_bytes = in_span.bytes(), out_bytes = out_span.bytes();
-    const size_t tmp_bytes = op == Typed::Compress ? in_bytes : op == Typed::Decompress ? out_bytes : 0;
-    Layout l{16};
-    const size_t at_in_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_tmp_off = l.take(8ull * n), at_in_len = l.take(4ull * n),
-                 at_out_cap = l.take(4ull * n);
-    const size_t up_bytes = l.end;
-    const size_t at_out_len = l.take(4ull * n), at_status = l.take(4ull * n), at_detail = l.take(16ull * n);
-    const size_t desc_bytes = l.end;
+    HostStage st;
+    const auto in_off = st.up<uint64_t>(n), out_off = st.up<uint64_t>(n), tmp_off = st.up<uint64_t>(n);
+    const auto in_len = st.up<uint32_t>(n), out_cap = st.up<uint32_t>(n);
+    const auto out_len = st.down<uint32_t>(n);
+    const auto status = st.down<int32_t>(n);
+    const auto detail = st.down<uint64_t>(2ull * n);
+    const Region r_in = st.region(in_bytes, 64), r_tmp = st.region(op == Typed::Compress ? in_bytes : op == Typed::Decompress ? out_bytes : 0, 64),
+                 r_out = st.region(out_bytes, 64);
+    st.columns();
     int rc;
-    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
-    const size_t a_tmp = align_up(in_bytes + 64, 256), a_out = a_tmp + align_up(tmp_bytes + 64, 256), a_desc = a_out + align_up(out_bytes + 64, 256);
-    if ((rc = ensure_buf(c->arena, a_desc + desc_bytes + 256))) return rc;
+    if ((rc = stage_open(c, st))) return rc;
     if ((rc = ensure_buf(c->pay, out_bytes + 16))) return rc;
-    uint8_t* hp = c->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_in_off))[i] = b.in_off[i] - in_span.lo;
-        ((uint64_t*)(hp + at_out_off))[i] = b.out_off[i] - out_span.lo;
-        ((uint64_t*)(hp + at_tmp_off))[i] = op == Typed::Compress ? b.in_off[i] - in_span.lo : b.out_off[i] - out_span.lo;
-        ((uint32_t*)(hp + at_in_len))[i] = b.in_len[i];
-        ((uint32_t*)(hp + at_out_cap))[i] = codec ? b.out_cap[i] : 0u;
-    }
-    uint8_t* d = c->arena.p;
-    uint8_t* dd = d + a_desc;
-    hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d, b.in_base + in_span.lo, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
-    BatchCall dv = batch_of(op == Typed::Compress, d, (const uint64_t*)(dd + at_in_off), (const uint32_t*)(dd + at_in_len), n, d + a_out,
-                            (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap), (uint32_t*)(dd + at_out_len),
-                            (int32_t*)(dd + at_status), s);
+    st.fill_offsets(in_off, b.in_off, in_span.lo); st.fill_offsets(out_off, b.out_off, out_span.lo);
+    if (op == Typed::Compress) st.fill_offsets(tmp_off, b.in_off, in_span.lo); else st.fill_offsets(tmp_off, b.out_off, out_span.lo);
+    st.fill(in_len, b.in_len);
+    if (codec) st.fill(out_cap, b.out_cap); else st.zero(out_cap);
+    hipStream_t s = st.s;
+    HIP_TRY(st.send(r_in, b.in_base + in_span.lo));
+    HIP_TRY(st.send_columns());
+    BatchCall dv = batch_of(op == Typed::Compress, st.dev(r_in), st.dev(in_off), st.dev(in_len), n, st.dev(r_out), st.dev(out_off), st.dev(out_cap),
+                            st.dev(out_len), st.dev(status), s);
     dv.big = big;
-    if (op == Typed::Decompress) dv.detail = (uint64_t*)(dd + at_detail);
-    if ((rc = typed_on_device(c, op, dv, filter, elem, inverse, d + a_tmp, (const uint64_t*)(dd + at_tmp_off)))) return rc;
-    if (codec) HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
-    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, d + a_out, out_bytes, hipMemcpyDeviceToHost, s));
+    if (op == Typed::Decompress) dv.detail = st.dev(detail);
+    if ((rc = typed_on_device(c, op, dv, filter, elem, inverse, st.dev(r_tmp), st.dev(tmp_off)))) return rc;
+    if (codec) HIP_TRY(st.fetch_columns(out_len));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, st.dev(r_out), out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t* r_len = (const uint32_t*)(hp + at_out_len);
-    const int32_t* r_st = (const int32_t*)(hp + at_status);
-    const uint64_t* r_det = (const uint64_t*)(hp + at_detail);
-    for (uint32_t i = 0; i < n; i++) {
-        uint32_t bytes = b.in_len[i];
-        if (codec) {
-            b.out_len[i] = r_len[i];
-            b.status[i] = r_st[i];
-            if (b.detail) { b.detail[2 * i] = b.compress ? 0 : r_det[2 * i]; b.detail[2 * i + 1] = b.compress ? 0 : r_det[2 * i + 1]; }
-            bytes = r_st[i] == 0 ? r_len[i] : 0u;
-        }
-        if (bytes) memcpy(b.out_base + b.out_off[i], c->pay.p + (b.out_off[i] - out_span.lo), bytes);
-    }
+    if (codec) copy_results(b, st.host(out_len), st.host(status), st.host(detail));
+    scatter_good(b.out_base, b.out_off, codec ? st.host(out_len) : b.in_len, codec ? st.host(status) : nullptr, n, c->pay.p,
+                 [&](uint32_t i) { return b.out_off[i] - out_span.lo; });
     return 0;
 }
 
@@ -1647,7 +1577,7 @@ int typed_entry(lz4flex_ctx* ctx, Typed op, BatchCall b, int filter, uint32_t el
         return k.where == Mem::Host ? run_host_batch(ctx, b) : run_device_batch(ctx, b);
     }
     if (k.where == Mem::Device) { b.big = k.big; return typed_on_device(ctx, op, b, filter, elem, inverse, (uint8_t*)tmp_base, tmp_off); }
-    return typed_on_host(ctx, op, b, filter, elem, inverse, k.big || (op != Typed::Filter && host_big(b)));
+    return typed_on_host(ctx, op, b, filter, elem, inverse, k.big || (op != Typed::Filter && host_big(b.in_len, b.n, b.compress)));
 }
 
 }  // namespace
@@ -1702,9 +1632,9 @@ int compress_fit_on_device(lz4flex_ctx* c, FitArgs a, uint8_t* scratch, uint64_t
     return launch_fit_checked(c, a, true, s);
 }
 
-// MEM_HOST, both entries: [block span | source span | output span | descriptors up, results down | work] in the arena (compress: no
-// block span, the scratch slots in the context's scratch); one synchronisation; the output span comes down to page-locked memory and
-// every block with status 0 is copied to its place, the rest of the caller's buffer stays as it is.
+// MEM_HOST, both entries (compress: no block span, a work area, the scratch slots in the context's scratch slot 0); one synchronisation;
+// the output span comes down to page-locked memory and every block with status 0 is copied to its place, the rest of the caller's
+// buffer stays as it is.
 int fit_on_host(lz4flex_ctx* c, const FitArgs& a, bool compress, bool big) {
     const uint32_t n = a.n;
     DeviceGuard guard(c->device);
@@ -1712,54 +1642,41 @@ int fit_on_host(lz4flex_ctx* c, const FitArgs& a, bool compress, bool big) {
     const Span blk_span = compress ? Span{0, 0} : span_of(a.blk_off, a.blk_len, n);
     const Span src_span = span_of(a.src_off, a.src_len, n);
     const Span out_span = span_of(a.out_off, a.out_cap, n);
-    const size_t blk_bytes = blk_span.bytes(), src_bytes = src_span.bytes(), out_bytes = out_span.bytes();
+    const size_t out_bytes = out_span.bytes();
     uint64_t slots = 0;
-    if (compress) for (uint32_t i = 0; i < n; i++) { slots += lz4flex_get_maximum_output_size(a.src_len[i]); big |= a.src_len[i] > 65536u; }
-    Layout l{16};
-    const size_t at_blk_off = l.take(8ull * n), at_src_off = l.take(8ull * n), at_out_off = l.take(8ull * n), at_blk_len = l.take(4ull * n),
-                 at_src_len = l.take(4ull * n), at_out_cap = l.take(4ull * n);
-    const size_t up_bytes = l.end;
-    const size_t at_out_len = l.take(4ull * n), at_used = l.take(4ull * n), at_status = l.take(4ull * n);
-    const size_t desc_bytes = l.end;
+    if (compress) {
+        for (uint32_t i = 0; i < n; i++) slots += lz4flex_get_maximum_output_size(a.src_len[i]);
+        big = big || host_big(a.src_len, n, true);
+    }
+    HostStage st;
+    const auto blk_off = st.up<uint64_t>(n), src_off = st.up<uint64_t>(n), out_off = st.up<uint64_t>(n);
+    const auto blk_len = st.up<uint32_t>(n), src_len = st.up<uint32_t>(n), out_cap = st.up<uint32_t>(n);
+    const auto out_len = st.down<uint32_t>(n), used = st.down<uint32_t>(n);
+    const auto status = st.down<int32_t>(n);
+    const Region r_blk = st.region(blk_span.bytes(), 64), r_src = st.region(src_span.bytes(), 64), r_out = st.region(out_bytes, 64);
+    st.columns();
+    const Region r_work = st.region(compress ? packed_work_bytes(n) : 0, 0);
     int rc;
-    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
-    const size_t a_src = align_up(blk_bytes + 64, 256), a_out = a_src + align_up(src_bytes + 64, 256), a_desc = a_out + align_up(out_bytes + 64, 256),
-                 a_work = a_desc + align_up(desc_bytes, 256);
-    if ((rc = ensure_buf(c->arena, a_work + (compress ? packed_work_bytes(n) : 0) + 256))) return rc;
+    if ((rc = stage_open(c, st))) return rc;
     if ((rc = ensure_buf(c->pay, out_bytes + 16))) return rc;
     void* d_scratch = nullptr;
     if (compress && (rc = ctx_scratch(c, 0, (size_t)slots + 256, &d_scratch))) return rc;
-    uint8_t* hp = c->pin.p;
-    for (uint32_t i = 0; i < n; i++) {
-        ((uint64_t*)(hp + at_blk_off))[i] = compress ? 0 : a.blk_off[i] - blk_span.lo;
-        ((uint64_t*)(hp + at_src_off))[i] = a.src_off[i] - src_span.lo;
-        ((uint64_t*)(hp + at_out_off))[i] = a.out_off[i] - out_span.lo;
-        ((uint32_t*)(hp + at_blk_len))[i] = compress ? 0 : a.blk_len[i];
-        ((uint32_t*)(hp + at_src_len))[i] = a.src_len[i];
-        ((uint32_t*)(hp + at_out_cap))[i] = a.out_cap[i];
-    }
-    uint8_t* d = c->arena.p;
-    uint8_t* dd = d + a_desc;
-    hipStream_t s = c->stream;
-    if (blk_bytes) HIP_TRY(hipMemcpyAsync(d, a.blk_base + blk_span.lo, blk_bytes, hipMemcpyHostToDevice, s));
-    if (src_bytes) HIP_TRY(hipMemcpyAsync(d + a_src, a.src_base + src_span.lo, src_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dd, hp, up_bytes, hipMemcpyHostToDevice, s));
-    const FitArgs dv{d, (const uint64_t*)(dd + at_blk_off), (const uint32_t*)(dd + at_blk_len), d + a_src, (const uint64_t*)(dd + at_src_off),
-                     (const uint32_t*)(dd + at_src_len), n, d + a_out, (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap),
-                     (uint32_t*)(dd + at_out_len), (uint32_t*)(dd + at_used), (int32_t*)(dd + at_status)};
-    if ((rc = compress ? compress_fit_on_device(c, dv, (uint8_t*)d_scratch, slots, d + a_work, big, s) : launch_fit_checked(c, dv, false, s))) return rc;
-    HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
-    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, d + a_out, out_bytes, hipMemcpyDeviceToHost, s));
+    if (compress) { st.zero(blk_off); st.zero(blk_len); }
+    else { st.fill_offsets(blk_off, a.blk_off, blk_span.lo); st.fill(blk_len, a.blk_len); }
+    st.fill_offsets(src_off, a.src_off, src_span.lo); st.fill_offsets(out_off, a.out_off, out_span.lo);
+    st.fill(src_len, a.src_len); st.fill(out_cap, a.out_cap);
+    hipStream_t s = st.s;
+    HIP_TRY(st.send(r_blk, a.blk_base + blk_span.lo));
+    HIP_TRY(st.send(r_src, a.src_base + src_span.lo));
+    HIP_TRY(st.send_columns());
+    const FitArgs dv{st.dev(r_blk), st.dev(blk_off), st.dev(blk_len), st.dev(r_src), st.dev(src_off), st.dev(src_len), n, st.dev(r_out),
+                     st.dev(out_off), st.dev(out_cap), st.dev(out_len), st.dev(used), st.dev(status)};
+    if ((rc = compress ? compress_fit_on_device(c, dv, (uint8_t*)d_scratch, slots, st.dev(r_work), big, s) : launch_fit_checked(c, dv, false, s))) return rc;
+    HIP_TRY(st.fetch_columns(out_len));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, st.dev(r_out), out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const uint32_t* r_len = (const uint32_t*)(hp + at_out_len);
-    const uint32_t* r_used = (const uint32_t*)(hp + at_used);
-    const int32_t* r_st = (const int32_t*)(hp + at_status);
-    for (uint32_t i = 0; i < n; i++) {
-        a.out_len[i] = r_len[i];
-        a.in_used[i] = r_used[i];
-        a.status[i] = r_st[i];
-        if (r_st[i] == 0 && r_len[i]) memcpy(a.out_base + a.out_off[i], c->pay.p + (a.out_off[i] - out_span.lo), r_len[i]);
-    }
+    st.read(out_len, a.out_len); st.read(used, a.in_used); st.read(status, a.status);
+    scatter_good(a.out_base, a.out_off, a.out_len, a.status, n, c->pay.p, [&](uint32_t i) { return a.out_off[i] - out_span.lo; });
     return 0;
 }
 
@@ -1849,51 +1766,39 @@ int lz4flex_compress_chains(lz4flex_ctx* ctx, const void* in_base, const lz4flex
     }
     is = is.closed();
     const Span os = span_of(out_off, out_cap, n_blocks);
-    const size_t in_bytes = is.bytes(), out_bytes = os.bytes();
-    Layout l{16};
-    const size_t at_blocks = l.take(sizeof(lz4flex_chain_block) * (size_t)n_blocks), at_first = l.take(4ull * n_chains),
-                 at_count = l.take(4ull * n_chains), at_out_off = l.take(8ull * n_blocks), at_out_cap = l.take(4ull * n_blocks);
-    const size_t desc_in = l.end;
-    const size_t at_out_len = l.take(4ull * n_blocks), at_status = l.take(4ull * n_blocks);
-    const size_t desc_bytes = l.end;
-    const size_t tbl_bytes = tbl_state ? 16384ull * n_chains : 0;
-    if ((rc = ensure_buf(c->pin, desc_bytes))) return rc;
-    const size_t a_in = 0, a_out = align_up(in_bytes + 64, 256), a_desc = a_out + align_up(out_bytes + 64, 256),
-                 a_tbl = a_desc + align_up(desc_bytes + 64, 256);
-    if ((rc = ensure_buf(c->arena, a_tbl + tbl_bytes + 256))) return rc;
-    uint8_t* hp = c->pin.p;
-    lz4flex_chain_block* hb = (lz4flex_chain_block*)(hp + at_blocks);
+    HostStage st;
+    const auto c_blocks = st.up<lz4flex_chain_block>(n_blocks);
+    const auto c_first = st.up<uint32_t>(n_chains), c_count = st.up<uint32_t>(n_chains);
+    const auto c_out_off = st.up<uint64_t>(n_blocks);
+    const auto c_out_cap = st.up<uint32_t>(n_blocks);
+    const auto c_out_len = st.down<uint32_t>(n_blocks);
+    const auto c_status = st.down<int32_t>(n_blocks);
+    const Region r_in = st.region(is.bytes(), 64), r_out = st.region(os.bytes(), 64);
+    st.columns(64);
+    const Region r_tbl = st.region(tbl_state ? 16384ull * n_chains : 0, 0);
+    if ((rc = stage_open(c, st))) return rc;
+    lz4flex_chain_block* hb = st.host(c_blocks);
     for (uint32_t i = 0; i < n_blocks; i++) {
         hb[i] = blocks[i];
         hb[i].in_off -= is.lo;
         hb[i].dict_off = blocks[i].dict_len ? blocks[i].dict_off - is.lo : 0;
-        ((uint64_t*)(hp + at_out_off))[i] = out_off[i] - os.lo;
-        ((uint32_t*)(hp + at_out_cap))[i] = out_cap[i];
     }
-    memcpy(hp + at_first, chain_first, 4ull * n_chains);
-    memcpy(hp + at_count, chain_count, 4ull * n_chains);
-    uint8_t* d = c->arena.p;
-    hipStream_t s = c->stream;
-    if (in_bytes) HIP_TRY(hipMemcpyAsync(d + a_in, (const uint8_t*)in_base + is.lo, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + a_desc, hp, desc_in, hipMemcpyHostToDevice, s));
-    if (tbl_state) HIP_TRY(hipMemcpyAsync(d + a_tbl, tbl_state, tbl_bytes, hipMemcpyHostToDevice, s));
-    uint8_t* dd = d + a_desc;
-    hipError_t le = launch_compress_chain(d + a_in, dd + at_blocks, (const uint32_t*)(dd + at_first),
-                                          (const uint32_t*)(dd + at_count), n_chains, d + a_out,
-                                          (const uint64_t*)(dd + at_out_off), (const uint32_t*)(dd + at_out_cap),
-                                          (uint32_t*)(dd + at_out_len), (int32_t*)(dd + at_status),
-                                          tbl_state ? (uint32_t*)(d + a_tbl) : nullptr, s);
+    st.fill(c_first, chain_first); st.fill(c_count, chain_count);
+    st.fill_offsets(c_out_off, out_off, os.lo); st.fill(c_out_cap, out_cap);
+    hipStream_t s = st.s;
+    HIP_TRY(st.send(r_in, (const uint8_t*)in_base + is.lo));
+    HIP_TRY(st.send_columns());
+    HIP_TRY(st.send(r_tbl, tbl_state));
+    hipError_t le = launch_compress_chain(st.dev(r_in), st.dev(c_blocks), st.dev(c_first), st.dev(c_count), n_chains, st.dev(r_out), st.dev(c_out_off),
+                                          st.dev(c_out_cap), st.dev(c_out_len), st.dev(c_status), tbl_state ? (uint32_t*)st.dev(r_tbl) : nullptr, s);
     if (le != hipSuccess) return hip_fail(le, "chain kernel launch");
-    HIP_TRY(hipMemcpyAsync(hp + at_out_len, dd + at_out_len, desc_bytes - at_out_len, hipMemcpyDeviceToHost, s));
-    if (tbl_state) HIP_TRY(hipMemcpyAsync(tbl_state, d + a_tbl, tbl_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(st.fetch_columns(c_out_len));
+    if (tbl_state) HIP_TRY(hipMemcpyAsync(tbl_state, st.dev(r_tbl), r_tbl.bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (uint32_t i = 0; i < n_blocks; i++) {
-        out_len[i] = ((const uint32_t*)(hp + at_out_len))[i];
-        status[i] = ((const int32_t*)(hp + at_status))[i];
+    st.read(c_out_len, out_len); st.read(c_status, status);
+    for (uint32_t i = 0; i < n_blocks; i++)
         if (status[i] == 0 && out_len[i])
-            HIP_TRY(hipMemcpyAsync((uint8_t*)out_base + out_off[i], d + a_out + (out_off[i] - os.lo), out_len[i],
-                                   hipMemcpyDeviceToHost, s));
-    }
+            HIP_TRY(hipMemcpyAsync((uint8_t*)out_base + out_off[i], st.dev(r_out) + (out_off[i] - os.lo), out_len[i], hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return 0;
 }

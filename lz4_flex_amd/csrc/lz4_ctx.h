@@ -1,5 +1,8 @@
 // lz4_ctx.h -- the host layer's private state: struct lz4flex_ctx (opaque in include/lz4flex_amd.h) and the few helpers every host file
 // that works on a context needs (capi.cpp, frame_many.cpp; sharded.cpp: Desc alone).  Host only, not installed, no kernel includes it.
+// Two helpers stage descriptor columns, both over Layout (lz4_host_stage.h): Desc, below, is a pageable image whose device memory the
+// caller owns (a scratch slot, an allocation of its own) -- the frame layer, which holds several at once; HostStage (lz4_host_stage.h) is
+// the context's ONE page-locked buffer and arena, with the arena's data regions -- capi.cpp's MEM_HOST calls, one at a time per context.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,16 +11,9 @@
 #include <cstdint>
 #include <vector>
 
+#include "lz4_host_stage.h"
+
 namespace lz4flex_dev {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// arrays laid out one behind the other, each start aligned: the layout a pinned host mirror and its device copy share
-struct Layout {
-    size_t align;
-    size_t end = 0;               // the bytes taken so far (aligned)
-    size_t take(size_t bytes) { const size_t at = end; end = align_up(end + bytes, align); return at; }
-};
 
 // Descriptor and result arrays of one call, one behind the other at 64-byte starts: a host image and its device copy.  The caller
 // owns the device memory (frame_many.cpp: context scratch slot 0; sharded.cpp: an allocation of its own) and maps the hipError_t.
