@@ -23,8 +23,10 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "frame_cols.h"
 #include "frame_plan.h"
 #include "frame_range.h"
+#include "frame_try.h"
 #include "lz4_ctx.h"
 #include "lz4_device.h"
 
@@ -48,17 +50,6 @@ using namespace lz4flex_dev;
 using lz4flex_plan::block_size_bytes;
 using lz4flex_range::RangeRec;
 
-#define TRY_HIP(expr)                                                        \
-    do {                                                                     \
-        const hipError_t e_ = (expr);                                        \
-        if (e_ != hipSuccess) return e_ == hipErrorOutOfMemory ? -LZ4FLEX_E_NOMEM : -LZ4FLEX_E_HIP; \
-    } while (0)
-#define TRY_RC(expr)                   \
-    do {                               \
-        const int rc_ = (expr);        \
-        if (rc_) return rc_;           \
-    } while (0)
-
 inline uint64_t up64(uint64_t v) { return (v + 63) / 64 * 64; }
 
 // ---- create: f = the frame in device memory
@@ -69,41 +60,33 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
     // a frame of that many bytes can hold at all (a block is at least its BlockInfo word)
     uint64_t max_blocks = frame_len / bs * 2 + 1024;
     const uint64_t most = frame_len / 4 + 1;
-    uint8_t* w = nullptr;
-    Layout l{64};
-    size_t a_pay = 0, a_word = 0, a_info = 0, a_scan_len = 0, a_size = 0, a_scan_st = 0, a_bad = 0, a_content = 0, a_tiles = 0, a_one = 0;
+    void* w = nullptr;                                 // scratch slot 0 holds the columns; they have no host image
+    IndexScratchCols a;
     uint32_t info[4] = {0, 0, 0, 0};
     for (;;) {
         max_blocks = std::min(max_blocks, most);
         if (max_blocks > 0x7FFFFFFFull) return -LZ4FLEX_E_UNSUPPORTED;
         const size_t mb = (size_t)max_blocks;
-        l = Layout{64};
-        a_pay = l.take(8 * mb); a_word = l.take(4 * mb); a_info = l.take(16); a_scan_len = l.take(4 * mb); a_size = l.take(8 * mb);
-        a_scan_st = l.take(4 * mb); a_bad = l.take(8); a_content = l.take(8 * (mb + 1)); a_tiles = l.take(8 * (mb / PACKED_SCAN_TILE + 2));
-        a_one = l.take(64);
-        void* p = nullptr;
-        TRY_RC(ctx_scratch(c, 0, l.end + 64, &p));
-        w = (uint8_t*)p;
-        TRY_HIP(launch_frame_walk(f, frame_len, hdr_len, tail, bs, (uint32_t)mb, (uint64_t*)(w + a_pay), (uint32_t*)(w + a_word), (uint32_t*)(w + a_info), s));
-        TRY_HIP(hipMemcpyAsync(info, w + a_info, 16, hipMemcpyDeviceToHost, s));
+        ColumnPlan l(64);
+        a = IndexScratchCols(l, mb, mb / PACKED_SCAN_TILE + 2);
+        TRY_RC(ctx_scratch(c, 0, l.total() + 64, &w));
+        TRY_HIP(launch_frame_walk(f, frame_len, hdr_len, tail, bs, (uint32_t)mb, ColumnPlan::view(w, a.pay), ColumnPlan::view(w, a.word),
+                                  ColumnPlan::view(w, a.info), s));
+        TRY_HIP(hipMemcpyAsync(info, ColumnPlan::view(w, a.info), 16, hipMemcpyDeviceToHost, s));
         TRY_HIP(hipStreamSynchronize(s));
         if (info[1] != 3u || max_blocks >= most) break;
         max_blocks = most;
     }
     uint32_t n = info[0], walk_st = info[1];
     uint64_t end = (uint64_t)info[2] | ((uint64_t)info[3] << 32);
-    uint64_t* d_pay = (uint64_t*)(w + a_pay);
-    uint32_t* d_word = (uint32_t*)(w + a_word);
-    uint32_t* d_scan_len = (uint32_t*)(w + a_scan_len);
-    uint64_t* d_size = (uint64_t*)(w + a_size);
-    int32_t* d_scan_st = (int32_t*)(w + a_scan_st);
-    uint32_t* d_bad = (uint32_t*)(w + a_bad);
-    uint64_t* d_content = (uint64_t*)(w + a_content);
+    uint64_t *d_pay = ColumnPlan::view(w, a.pay), *d_size = ColumnPlan::view(w, a.size), *d_content = ColumnPlan::view(w, a.content);
+    uint32_t *d_word = ColumnPlan::view(w, a.word), *d_scan_len = ColumnPlan::view(w, a.scan_len), *d_bad = ColumnPlan::view(w, a.bad);
+    int32_t* d_scan_st = ColumnPlan::view(w, a.scan_st);
     // ---- decoded sizes and their exclusive sums
     TRY_HIP(launch_frame_index_prep(d_word, n, d_scan_len, d_bad, s));
     if (n) TRY_HIP(launch_size_scan(f, d_pay, d_scan_len, nullptr, n, d_size, d_scan_st, c->size_serial, s));
     TRY_HIP(launch_frame_index_sizes(d_word, d_scan_st, n, bs, d_size, d_bad, s));
-    TRY_HIP(launch_packed_scan(d_size, n, 1u, ~0ull, 0u, (uint64_t*)(w + a_tiles), d_content, nullptr, nullptr, nullptr, s));
+    TRY_HIP(launch_packed_scan(d_size, n, 1u, ~0ull, 0u, ColumnPlan::view(w, a.tiles), d_content, nullptr, nullptr, nullptr, s));
     uint32_t firsts[2] = {0, 0};
     uint64_t total = 0;
     TRY_HIP(hipMemcpyAsync(firsts, d_bad, 8, hipMemcpyDeviceToHost, s));
@@ -114,7 +97,7 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
     if (first_bad < n && first_bad < first_empty) {
         // its error is the decoder's own: once through the ordinary batch path, the sink a block size as FrameDecoder's is
         struct One { uint64_t out_off; uint64_t det[2]; uint32_t cap, olen; int32_t st; } one{0, {0, 0}, bs, 0, 0};
-        uint8_t* d_one = w + a_one;
+        uint8_t* d_one = ColumnPlan::view(w, a.one);
         void* sink = nullptr;
         TRY_RC(ctx_scratch(c, 1, (size_t)bs + 64, &sink));
         TRY_HIP(hipMemcpyAsync(d_one, &one, sizeof one, hipMemcpyHostToDevice, s));
@@ -151,22 +134,22 @@ int index_build(lz4flex_ctx* c, const uint8_t* f, uint64_t frame_len, const lz4f
     const uint64_t frame_bytes = end + (fi.content_checksum && !open_end ? 4u : 0u);
     if (frame_bytes > frame_len) return -LZ4FLEX_FE_IO;                             // (the content checksum's bytes: :321-326)
     // ---- the index's own copy
-    Layout o{64};
-    const size_t o_content = o.take(8ull * (n + 1)), o_pay = o.take(8ull * n), o_word = o.take(4ull * n);
-    TRY_HIP(hipMalloc((void**)&x->mem, o.end + 64));
+    ColumnPlan o(64);
+    const IndexTableCols t(o, n);
+    TRY_HIP(hipMalloc((void**)&x->mem, o.total() + 64));
+    uint64_t *x_content = ColumnPlan::view(x->mem, t.content), *x_pay = ColumnPlan::view(x->mem, t.pay);
+    uint32_t* x_word = ColumnPlan::view(x->mem, t.word);
     x->content_off.resize((size_t)n + 1); x->payload_off.resize(n); x->len_word.resize(n);
-    TRY_HIP(hipMemcpyAsync(x->mem + o_content, d_content, 8ull * (n + 1), hipMemcpyDeviceToDevice, s));
+    TRY_HIP(hipMemcpyAsync(x_content, d_content, 8ull * (n + 1), hipMemcpyDeviceToDevice, s));
     TRY_HIP(hipMemcpyAsync(x->content_off.data(), d_content, 8ull * (n + 1), hipMemcpyDeviceToHost, s));
     if (n) {
-        TRY_HIP(hipMemcpyAsync(x->mem + o_pay, d_pay, 8ull * n, hipMemcpyDeviceToDevice, s));
-        TRY_HIP(hipMemcpyAsync(x->mem + o_word, d_word, 4ull * n, hipMemcpyDeviceToDevice, s));
+        TRY_HIP(hipMemcpyAsync(x_pay, d_pay, 8ull * n, hipMemcpyDeviceToDevice, s));
+        TRY_HIP(hipMemcpyAsync(x_word, d_word, 4ull * n, hipMemcpyDeviceToDevice, s));
         TRY_HIP(hipMemcpyAsync(x->payload_off.data(), d_pay, 8ull * n, hipMemcpyDeviceToHost, s));
         TRY_HIP(hipMemcpyAsync(x->len_word.data(), d_word, 4ull * n, hipMemcpyDeviceToHost, s));
     }
     TRY_HIP(hipStreamSynchronize(s));
-    x->d_content = (const uint64_t*)(x->mem + o_content);
-    x->d_payload = (const uint64_t*)(x->mem + o_pay);
-    x->d_word = (const uint32_t*)(x->mem + o_word);
+    x->d_content = x_content; x->d_payload = x_pay; x->d_word = x_word;
     x->device = c->device; x->blocks = n; x->content_size = total; x->frame_bytes = frame_bytes; x->info = fi; x->block_bytes = bs;
     return 0;
 }
@@ -177,58 +160,52 @@ struct PassOut { int32_t* status; uint64_t* out_len; lz4flex_err_detail* detail;
 int run_pass(lz4flex_ctx* c, const lz4flex_frame_index* x, const uint8_t* in, uint8_t* out, const RangeRec* recs, uint32_t R, uint32_t T,
              uint64_t head_total, const PassOut& res, hipStream_t s) {
     Desc D;
-    const size_t a_rec = D.take(sizeof(RangeRec) * (size_t)R);
-    const size_t up = D.bytes();                       // (everything behind the records is written by the device)
-    const size_t a_in = D.take(8ull * T), a_out = D.take(8ull * T), a_len = D.take(4ull * T), a_tgt = D.take(4ull * T), a_olen = D.take(4ull * T),
-                 a_st = D.take(4ull * T), c_src = D.take(8ull * T), c_dst = D.take(8ull * T), c_len = D.take(4ull * T), k_sum = D.take(4ull * T),
-                 k_bad = D.take(4ull * T), b_in = D.take(8ull * R), b_out = D.take(8ull * R), b_len = D.take(4ull * R), b_tgt = D.take(4ull * R),
-                 b_olen = D.take(4ull * R), b_st = D.take(4ull * R), d_src = D.take(8ull * R), d_dst = D.take(8ull * R), d_len = D.take(4ull * R);
-    const size_t v_st = D.take(4ull * R), v_inner = D.take(4ull * R), v_len = D.take(8ull * R), v_exp = D.take(8ull * R), v_act = D.take(8ull * R);
-    memcpy(D.host<RangeRec>(a_rec), recs, sizeof(RangeRec) * (size_t)R);
+    const RangePassCols a(D, R, T);
+    D.fill(a.rec, recs);
     void* p = nullptr;
-    TRY_RC(ctx_scratch(c, 0, D.bytes() + 64, &p));
-    TRY_HIP(D.upload(p, up, s));
+    TRY_RC(ctx_scratch(c, 0, D.total() + 64, &p));
+    TRY_HIP(D.upload(p, D.up_bytes, s));               // (the records: everything behind them is written by the device)
     void* heads = nullptr;
     if (head_total) TRY_RC(ctx_scratch(c, 1, (size_t)head_total + 64, &heads));
     FrameRangePlan pl{};
-    pl.rec = D.dev<RangeRec>(a_rec); pl.content_off = x->d_content; pl.payload_off = x->d_payload; pl.len_word = x->d_word;
+    pl.rec = D.dev(a.rec); pl.content_off = x->d_content; pl.payload_off = x->d_payload; pl.len_word = x->d_word;
     pl.n_ranges = R; pl.n_slots = T;
-    pl.a_in = D.dev<uint64_t>(a_in); pl.a_out = D.dev<uint64_t>(a_out); pl.a_len = D.dev<uint32_t>(a_len); pl.a_tgt = D.dev<uint32_t>(a_tgt);
-    pl.b_in = D.dev<uint64_t>(b_in); pl.b_out = D.dev<uint64_t>(b_out); pl.b_len = D.dev<uint32_t>(b_len); pl.b_tgt = D.dev<uint32_t>(b_tgt);
-    pl.c_src = D.dev<uint64_t>(c_src); pl.c_dst = D.dev<uint64_t>(c_dst); pl.c_len = D.dev<uint32_t>(c_len);
-    pl.d_src = D.dev<uint64_t>(d_src); pl.d_dst = D.dev<uint64_t>(d_dst); pl.d_len = D.dev<uint32_t>(d_len);
+    pl.a_in = D.dev(a.a_in); pl.a_out = D.dev(a.a_out); pl.a_len = D.dev(a.a_len); pl.a_tgt = D.dev(a.a_tgt);
+    pl.b_in = D.dev(a.b_in); pl.b_out = D.dev(a.b_out); pl.b_len = D.dev(a.b_len); pl.b_tgt = D.dev(a.b_tgt);
+    pl.c_src = D.dev(a.c_src); pl.c_dst = D.dev(a.c_dst); pl.c_len = D.dev(a.c_len);
+    pl.d_src = D.dev(a.d_src); pl.d_dst = D.dev(a.d_dst); pl.d_len = D.dev(a.d_len);
     TRY_HIP(launch_frame_range_plan(pl, s));
     const bool sums = x->info.block_checksums && c->range_checksums && T;
     if (sums) {                                        // frame/decompress.rs:255-261,275-278: the whole payload, before anything is decoded
-        TRY_HIP(launch_xxh32_batch(in, pl.a_in, pl.a_len, T, 0u, D.dev<uint32_t>(k_sum), s));
-        TRY_HIP(launch_frame_sums_check(in, pl.a_in, pl.a_len, D.dev<uint32_t>(k_sum), T, D.dev<uint32_t>(k_bad), s));
+        TRY_HIP(launch_xxh32_batch(in, pl.a_in, pl.a_len, T, 0u, D.dev(a.k_sum), s));
+        TRY_HIP(launch_frame_sums_check(in, pl.a_in, pl.a_len, D.dev(a.k_sum), T, D.dev(a.k_bad), s));
     }
     const int big = x->block_bytes > 131072u ? LZ4FLEX_MEM_BIG_BLOCKS : 0;
     if (T)
-        TRY_RC(lz4flex_decompress_batch_partial(c, in, pl.a_in, pl.a_len, T, out, pl.a_out, pl.a_tgt, D.dev<uint32_t>(a_olen), D.dev<int32_t>(a_st),
+        TRY_RC(lz4flex_decompress_batch_partial(c, in, pl.a_in, pl.a_len, T, out, pl.a_out, pl.a_tgt, D.dev(a.a_olen), D.dev(a.a_st),
                                                 LZ4FLEX_MEM_DEVICE | big, s));
     if (head_total)
-        TRY_RC(lz4flex_decompress_batch_partial(c, in, pl.b_in, pl.b_len, R, heads, pl.b_out, pl.b_tgt, D.dev<uint32_t>(b_olen), D.dev<int32_t>(b_st),
+        TRY_RC(lz4flex_decompress_batch_partial(c, in, pl.b_in, pl.b_len, R, heads, pl.b_out, pl.b_tgt, D.dev(a.b_olen), D.dev(a.b_st),
                                                 LZ4FLEX_MEM_DEVICE | big, s));
     TRY_HIP(launch_copy_batch(in, pl.c_src, pl.c_len, out, pl.c_dst, T, s));                                   // stored blocks (:262-271)
     if (head_total) TRY_HIP(launch_copy_batch((const uint8_t*)heads, pl.d_src, pl.d_len, out, pl.d_dst, R, s));
     FrameRangeVerdict v{};
-    v.rec = pl.rec; v.len_word = x->d_word; v.n_ranges = R; v.bad = sums ? D.dev<uint32_t>(k_bad) : nullptr;
-    v.a_st = D.dev<int32_t>(a_st); v.b_st = D.dev<int32_t>(b_st); v.a_tgt = pl.a_tgt; v.a_olen = D.dev<uint32_t>(a_olen);
-    v.b_tgt = pl.b_tgt; v.b_olen = D.dev<uint32_t>(b_olen);
-    v.status = D.dev<int32_t>(v_st); v.inner = D.dev<int32_t>(v_inner); v.out_len = D.dev<uint64_t>(v_len);
-    v.expected = D.dev<uint64_t>(v_exp); v.actual = D.dev<uint64_t>(v_act);
+    v.rec = pl.rec; v.len_word = x->d_word; v.n_ranges = R; v.bad = sums ? D.dev(a.k_bad) : nullptr;
+    v.a_st = D.dev(a.a_st); v.b_st = D.dev(a.b_st); v.a_tgt = pl.a_tgt; v.a_olen = D.dev(a.a_olen);
+    v.b_tgt = pl.b_tgt; v.b_olen = D.dev(a.b_olen);
+    v.status = D.dev(a.v_st); v.inner = D.dev(a.v_inner); v.out_len = D.dev(a.v_len);
+    v.expected = D.dev(a.v_exp); v.actual = D.dev(a.v_act);
     TRY_HIP(launch_frame_range_verdict(v, s));
-    TRY_HIP(hipMemcpyAsync(D.host<uint8_t>(v_st), D.dev<uint8_t>(v_st), D.bytes() - v_st, hipMemcpyDeviceToHost, s));
+    TRY_HIP(D.fetch_columns(a.v_st, s));               // the five verdict columns, one copy
     TRY_HIP(hipStreamSynchronize(s));
     for (uint32_t r = 0; r < R; r++) {
-        res.status[r] = D.host<int32_t>(v_st)[r];
-        res.out_len[r] = D.host<uint64_t>(v_len)[r];
+        res.status[r] = D.host(a.v_st)[r];
+        res.out_len[r] = D.host(a.v_len)[r];
         if (res.detail) {
             memset(&res.detail[r], 0, sizeof res.detail[r]);
-            res.detail[r].inner = D.host<int32_t>(v_inner)[r];
-            res.detail[r].expected = D.host<uint64_t>(v_exp)[r];
-            res.detail[r].actual = D.host<uint64_t>(v_act)[r];
+            res.detail[r].inner = D.host(a.v_inner)[r];
+            res.detail[r].expected = D.host(a.v_exp)[r];
+            res.detail[r].actual = D.host(a.v_act)[r];
         }
     }
     return 0;

@@ -25,7 +25,9 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "frame_cols.h"
 #include "frame_plan.h"
+#include "frame_try.h"
 #include "lz4_batch_entry.h"
 #include "lz4_ctx.h"
 #include "lz4_device.h"
@@ -38,22 +40,12 @@ using namespace lz4flex_plan;   // block sizes, FAST_HISTORY, STREAM_MAX (the st
 // ("decompress_level_chains", default 1 024: from this many Linked streams in one call on their blocks are decoded a level per launch -- the groups loop)
 constexpr uint64_t MAX_SLOTS = 1ull << 26;               // block-table entries per decompress_many call (12 bytes each on the host and on the device)
 
-#define TRY_HIP(expr)                                                        \
-    do {                                                                     \
-        const hipError_t e_ = (expr);                                        \
-        if (e_ != hipSuccess) return e_ == hipErrorOutOfMemory ? -LZ4FLEX_E_NOMEM : -LZ4FLEX_E_HIP; \
-    } while (0)
-#define TRY_RC(expr)                   \
-    do {                               \
-        const int rc_ = (expr);        \
-        if (rc_) return rc_;           \
-    } while (0)
-
-// descriptor arrays (Desc, lz4_ctx.h): the device copy is scratch slot 0, the whole image goes up
+// descriptor columns (Desc, lz4_ctx.h; their names: frame_cols.h): the device copy is scratch slot 0, the WHOLE image goes up, the
+// zeros of the result columns included
 int upload(lz4flex_ctx* c, Desc& D, hipStream_t s) {
     void* p = nullptr;
-    TRY_RC(ctx_scratch(c, 0, D.bytes() + 64, &p));
-    TRY_HIP(D.upload(p, D.bytes(), s));
+    TRY_RC(ctx_scratch(c, 0, D.total() + 64, &p));
+    TRY_HIP(D.upload(p, D.total(), s));
     return 0;
 }
 
@@ -106,26 +98,14 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
     if (nb64 > 0x7FFFFFFFull) return -LZ4FLEX_E_INVALID_ARG;
     const uint32_t nb = (uint32_t)nb64, nf = (uint32_t)fast.size();
     Desc D;
-    const size_t a_ms = D.take(sizeof(ManyStream) * (size_t)nf), a_soff = D.take(8ull * nf), a_slen = D.take(4ull * nf),
-                 a_in_off = D.take(8ull * nb), a_comp_off = D.take(8ull * nb), a_in_len = D.take(4ull * nb), a_flags = D.take(4ull * nb),
-                 a_comp_cap = D.take(4ull * nb), a_cb = (exact && linked) ? D.take(sizeof(lz4flex_chain_block) * (size_t)nb) : 0,
-                 a_first = (exact && linked) ? D.take(4ull * nf) : 0, a_count = (exact && linked) ? D.take(4ull * nf) : 0;
-    // (results: written by the device)
-    const size_t a_comp_len = D.take(4ull * nb), a_comp_st = D.take(4ull * nb), a_dst_off = D.take(8ull * nb), a_pay_off = D.take(8ull * nb),
-                 a_pay_len = D.take(4ull * nb), a_sums = D.take(4ull * nb), a_csum = D.take(4ull * nf), a_flen = D.take(8ull * nf),
-                 a_verdict = D.take(4ull * nf);
+    const ManyEncodeCols<ManyStream> a(D, nf, nb, exact && linked);
     uint64_t comp_bytes = 0;
     bool big = false;
     {
-        ManyStream* ms = D.host<ManyStream>(a_ms);
-        uint64_t* soff = D.host<uint64_t>(a_soff);
-        uint32_t* slen = D.host<uint32_t>(a_slen);
-        uint64_t* b_in = D.host<uint64_t>(a_in_off);
-        uint64_t* b_co = D.host<uint64_t>(a_comp_off);
-        uint32_t* b_len = D.host<uint32_t>(a_in_len);
-        uint32_t* b_fl = D.host<uint32_t>(a_flags);
-        uint32_t* b_cap = D.host<uint32_t>(a_comp_cap);
-        lz4flex_chain_block* cb = (exact && linked) ? D.host<lz4flex_chain_block>(a_cb) : nullptr;
+        ManyStream* ms = D.host(a.ms);
+        uint64_t *soff = D.host(a.soff), *b_in = D.host(a.in_off), *b_co = D.host(a.comp_off);
+        uint32_t *slen = D.host(a.slen), *b_len = D.host(a.in_len), *b_fl = D.host(a.flags), *b_cap = D.host(a.comp_cap);
+        lz4flex_chain_block* cb = (exact && linked) ? D.host(a.cb) : nullptr;
         uint32_t b = 0;
         for (uint32_t f = 0; f < nf; f++) {
             const uint32_t i = fast[f];
@@ -142,7 +122,7 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
             if (hl < 0) return (int)hl;
             m.hdr_len = (uint32_t)hl;
             soff[f] = in_off[i]; slen[f] = (uint32_t)in_len[i];
-            if (cb) { D.host<uint32_t>(a_first)[f] = b; D.host<uint32_t>(a_count)[f] = cnt; }
+            if (cb) { D.host(a.first)[f] = b; D.host(a.count)[f] = cnt; }
             // table mode (Independent) / window (Linked) of the reference's encoder, block after block: frame_plan.h.  No stream here
             // is longer than STREAM_MAX, so neither ever repositions: FRAME_FIRST is block 0 alone, every chain block's repos is 0
             TableOffset tbl;
@@ -169,29 +149,26 @@ int compress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_o
     TRY_RC(ctx_scratch(c, 1, (size_t)comp_bytes + 64, &comp));
     if (nb) {
         if (exact && linked)
-            TRY_RC(lz4flex_compress_chains(c, in, D.dev<lz4flex_chain_block>(a_cb), nb, D.dev<uint32_t>(a_first), D.dev<uint32_t>(a_count), nf, comp,
-                                           D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st),
-                                           nullptr, LZ4FLEX_MEM_DEVICE, s));
+            TRY_RC(lz4flex_compress_chains(c, in, D.dev(a.cb), nb, D.dev(a.first), D.dev(a.count), nf, comp, D.dev(a.comp_off), D.dev(a.comp_cap),
+                                           D.dev(a.comp_len), D.dev(a.comp_st), nullptr, LZ4FLEX_MEM_DEVICE, s));
         else
             // (one launch over all blocks of all streams; `linked`: what compress_mode high does with a Linked frame's blocks is
             // encode_route's rule, lz4_route.h)
-            TRY_RC(compress_batch_entry(c, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), D.dev<uint32_t>(a_flags), nb, comp,
-                                        D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_cap), D.dev<uint32_t>(a_comp_len),
-                                        D.dev<int32_t>(a_comp_st), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s, linked));
+            TRY_RC(compress_batch_entry(c, in, D.dev(a.in_off), D.dev(a.in_len), D.dev(a.flags), nb, comp, D.dev(a.comp_off), D.dev(a.comp_cap),
+                                        D.dev(a.comp_len), D.dev(a.comp_st), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s, linked));
     }
-    if (csum && nf) TRY_RC(lz4flex_xxh32_batch_device(in, D.dev<uint64_t>(a_soff), D.dev<uint32_t>(a_slen), nf, 0, D.dev<uint32_t>(a_csum), s));   // frame/compress.rs:319-321
-    TRY_HIP(launch_frame_many_assemble(D.dev<ManyStream>(a_ms), nf, in, D.dev<uint64_t>(a_in_off), D.dev<uint32_t>(a_in_len), (const uint8_t*)comp,
-                                       D.dev<uint64_t>(a_comp_off), D.dev<uint32_t>(a_comp_len), D.dev<int32_t>(a_comp_st), nb, bsum ? 1 : 0,
-                                       D.dev<uint32_t>(a_csum), out, D.dev<uint64_t>(a_dst_off), D.dev<uint64_t>(a_pay_off), D.dev<uint32_t>(a_pay_len),
-                                       D.dev<uint32_t>(a_sums), D.dev<uint64_t>(a_flen), D.dev<int32_t>(a_verdict), s));
-    TRY_HIP(D.fetch<uint64_t>(a_flen, nf, s));
-    TRY_HIP(D.fetch<int32_t>(a_verdict, nf, s));
+    if (csum && nf) TRY_RC(lz4flex_xxh32_batch_device(in, D.dev(a.soff), D.dev(a.slen), nf, 0, D.dev(a.csum), s));   // frame/compress.rs:319-321
+    TRY_HIP(launch_frame_many_assemble(D.dev(a.ms), nf, in, D.dev(a.in_off), D.dev(a.in_len), (const uint8_t*)comp, D.dev(a.comp_off), D.dev(a.comp_len),
+                                       D.dev(a.comp_st), nb, bsum ? 1 : 0, D.dev(a.csum), out, D.dev(a.dst_off), D.dev(a.pay_off), D.dev(a.pay_len),
+                                       D.dev(a.sums), D.dev(a.flen), D.dev(a.verdict), s));
+    TRY_HIP(D.fetch(a.flen, nf, s));
+    TRY_HIP(D.fetch(a.verdict, nf, s));
     TRY_HIP(hipStreamSynchronize(s));
     for (uint32_t f = 0; f < nf; f++) {
         const uint32_t i = fast[f];
-        const int32_t v = D.host<int32_t>(a_verdict)[f];
+        const int32_t v = D.host(a.verdict)[f];
         status[i] = v == 0 ? 0 : (v == 1 ? -LZ4FLEX_FE_COMPRESSION : -LZ4FLEX_FE_OUTPUT_FULL);
-        out_len[i] = v == 0 ? D.host<uint64_t>(a_flen)[f] : 0;
+        out_len[i] = v == 0 ? D.host(a.flen)[f] : 0;
     }
     for (uint32_t i : slow) {
         lz4flex_frame_info fi = *info;
@@ -208,29 +185,58 @@ struct Entry {            // one compressed block of the batch
     uint32_t in_len, cap, pos;
 };
 
-int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* out,
-                           const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, lz4flex_err_detail* detail,
-                           hipStream_t s) {
-    std::vector<uint8_t> again(n, 0);                  // 1: the stream goes through lz4flex_frame_decompress
-    std::vector<lz4flex_frame_info> fi(n);
-    // ---- 1. headers
-    std::vector<uint8_t> heads(32ull * n);
-    {
-        Desc H;
-        const size_t a_off = H.take(8ull * n), a_len = H.take(8ull * n), a_heads = H.take(32ull * n);
-        memcpy(H.host<uint64_t>(a_off), in_off, 8ull * n);
-        memcpy(H.host<uint64_t>(a_len), in_len, 8ull * n);
-        TRY_RC(upload(c, H, s));
-        TRY_HIP(launch_frame_many_heads(in, H.dev<uint64_t>(a_off), H.dev<uint64_t>(a_len), n, H.dev<uint8_t>(a_heads), s));
-        TRY_HIP(hipMemcpyAsync(heads.data(), H.dev<uint8_t>(a_heads), 32ull * n, hipMemcpyDeviceToHost, s));
-        TRY_HIP(hipStreamSynchronize(s));
-    }
-    // ---- 2. the block tables
-    Desc W;
-    const size_t a_fr = W.take(sizeof(ManyFrame) * (size_t)n);
+struct Group { size_t lo, hi; };   // the chained entries of one chained call: whole streams, at most CHAIN_MAX_BLOCKS blocks, ordered by (block index, stream)
+
+// One call over device memory: its arguments, and what each of its four phases leaves for the next.  A phase ends where the stream is
+// waited for; each runs once, in the order below.
+struct ManyArgs {
+    lz4flex_ctx* c;
+    const uint8_t* in;
+    const uint64_t *in_off, *in_len;
+    uint32_t n;
+    uint8_t* out;
+    const uint64_t *out_off, *out_cap;
+    hipStream_t s;
+};
+struct ManyDecode : ManyArgs {
+    std::vector<uint8_t> again;                        // 1: the stream goes through lz4flex_frame_decompress
+    std::vector<lz4flex_frame_info> fi;
+    std::vector<uint8_t> heads;                        // 1 -> 2: the first 32 bytes of every frame
+    Desc W;                                            // 2 -> 3, 4: the frames and their block tables
+    ManyWalkCols<ManyFrame> wc;
+    std::vector<Entry> plain, chained;                 // 3 -> 4: the batch, its image, and what the verdicts need of the stored blocks
+    std::vector<Group> groups;
+    std::vector<uint32_t> p_stream;                    // the stream of every block checksum
+    std::vector<uint64_t> raw_bytes;                   // bytes of a stream's stored blocks
+    uint32_t np = 0, nc = 0, nr = 0, nk = 0, ne = 0;
+    Desc B;
+    ManyBatchCols bc;
+    explicit ManyDecode(const ManyArgs& a) : ManyArgs(a), again(n, 0), fi(n), heads(32ull * n), wc(W, n), raw_bytes(n, 0) {}
+    int read_heads();
+    int walk_tables();
+    void build_batch();
+    int run_batch();
+    int finish(uint64_t* out_len, int32_t* status, lz4flex_err_detail* detail);
+};
+
+// ---- 1. headers
+int ManyDecode::read_heads() {
+    Desc H;
+    const ManyHeadCols h(H, n);
+    H.fill(h.off, in_off);
+    H.fill(h.len, in_len);
+    TRY_RC(upload(c, H, s));
+    TRY_HIP(launch_frame_many_heads(in, H.dev(h.off), H.dev(h.len), n, H.dev(h.heads), s));
+    TRY_HIP(hipMemcpyAsync(heads.data(), H.dev(h.heads), 32ull * n, hipMemcpyDeviceToHost, s));
+    TRY_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ---- 2. the block tables
+int ManyDecode::walk_tables() {
     uint64_t slots = 0;
     for (uint32_t i = 0; i < n; i++) {
-        ManyFrame& m = W.host<ManyFrame>(a_fr)[i];
+        ManyFrame& m = W.host(wc.fr)[i];
         m.off = in_off[i]; m.len = in_len[i]; m.skip = 1;
         const int64_t hl = lz4flex_frame_info_read(heads.data() + 32ull * i, (size_t)std::min<uint64_t>(32, in_len[i]), &fi[i], nullptr);
         const size_t bs = hl < 0 ? 0 : block_size_bytes(fi[i].block_size);
@@ -243,32 +249,31 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         m.slot = (uint32_t)slots; m.slot_cap = (uint32_t)cap_blocks; m.skip = 0;
         slots += cap_blocks;
     }
-    const size_t a_pay = W.take(8ull * slots), a_word = W.take(4ull * slots), a_info = W.take(32ull * n);
+    wc.slots(W, slots, n);
     TRY_RC(upload(c, W, s));
-    TRY_HIP(launch_frame_many_walk(in, W.dev<ManyFrame>(a_fr), n, W.dev<uint64_t>(a_pay), W.dev<uint32_t>(a_word), W.dev<uint32_t>(a_info), s));
-    TRY_HIP(W.fetch<uint64_t>(a_pay, slots, s));
-    TRY_HIP(W.fetch<uint32_t>(a_word, slots, s));
-    TRY_HIP(W.fetch<uint32_t>(a_info, 8ull * n, s));
+    TRY_HIP(launch_frame_many_walk(in, W.dev(wc.fr), n, W.dev(wc.pay), W.dev(wc.word), W.dev(wc.info), s));
+    TRY_HIP(W.fetch(wc.pay, slots, s));
+    TRY_HIP(W.fetch(wc.word, slots, s));
+    TRY_HIP(W.fetch(wc.info, 8ull * n, s));
     TRY_HIP(hipStreamSynchronize(s));
-    // ---- 3. the batch: compressed blocks (Independent: plain; Linked: chained, level by level), stored blocks (one copy launch)
-    std::vector<Entry> plain, chained;
-    std::vector<uint64_t> r_in, r_out;
-    std::vector<uint32_t> r_len;
-    std::vector<uint64_t> p_off;                       // every payload, for the block checksums
-    std::vector<uint32_t> p_len, p_stream;
-    std::vector<uint64_t> raw_bytes(n, 0);             // bytes of a stream's stored blocks
-    std::vector<uint32_t> n_comp(n, 0);
+    return 0;
+}
+
+// ---- 3. the batch: compressed blocks (Independent: plain; Linked: chained, level by level), stored blocks (one copy launch)
+void ManyDecode::build_batch() {
+    std::vector<uint64_t> r_in, r_out, p_off;          // stored blocks; every payload, for the block checksums
+    std::vector<uint32_t> r_len, p_len, n_comp(n, 0);
     for (uint32_t i = 0; i < n; i++) {
         if (again[i]) continue;
-        const ManyFrame& m = W.host<ManyFrame>(a_fr)[i];
-        const uint32_t* nf = W.host<uint32_t>(a_info) + 8ull * i;
+        const ManyFrame& m = W.host(wc.fr)[i];
+        const uint32_t* nf = W.host(wc.info) + 8ull * i;
         if (nf[1] != 0) { again[i] = 1; continue; }                                  // does not parse (bytes behind the frame are not read: read_to_end ends with the frame)
         const uint32_t cnt = nf[0], bs = m.block_size;
         const size_t plain0 = plain.size(), chained0 = chained.size(), r0 = r_in.size(), p0 = p_off.size();
         bool ok = true;
         for (uint32_t k = 0; k < cnt && ok; k++) {
-            const uint32_t w = W.host<uint32_t>(a_word)[m.slot + k], len = w & ~BLOCK_UNCOMPRESSED_SIZE_BIT;
-            const uint64_t po = W.host<uint64_t>(a_pay)[m.slot + k], pos = (uint64_t)k * bs;
+            const uint32_t w = W.host(wc.word)[m.slot + k], len = w & ~BLOCK_UNCOMPRESSED_SIZE_BIT;
+            const uint64_t po = W.host(wc.pay)[m.slot + k], pos = (uint64_t)k * bs;
             if (len == 0 || pos >= out_cap[i]) { ok = false; break; }
             const uint32_t cap = (uint32_t)std::min<uint64_t>(bs, out_cap[i] - pos);
             if (m.flags & 1u) { p_off.push_back(po); p_len.push_back(len); p_stream.push_back(i); }
@@ -292,8 +297,6 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         }
     }
     // chained groups: whole streams, at most CHAIN_MAX_BLOCKS blocks per call, each ordered by (block index, stream)
-    struct Group { size_t lo, hi; };
-    std::vector<Group> groups;
     {
         size_t lo = 0, at = 0;
         while (at < chained.size()) {
@@ -307,48 +310,44 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         for (const Group& g : groups)
             std::stable_sort(chained.begin() + g.lo, chained.begin() + g.hi, [](const Entry& a, const Entry& b) { return a.k < b.k; });
     }
-    const uint32_t np = (uint32_t)plain.size(), nc = (uint32_t)chained.size(), nr = (uint32_t)r_in.size(), nk = (uint32_t)p_off.size(), ne = np + nc;
-    Desc B;
-    const size_t b_in = B.take(8ull * ne), b_out = B.take(8ull * ne), b_len = B.take(4ull * ne), b_cap = B.take(4ull * ne), b_pos = B.take(4ull * ne),
-                 b_prev = B.take(4ull * ne), b_rin = B.take(8ull * nr), b_rout = B.take(8ull * nr), b_rlen = B.take(4ull * nr),
-                 b_poff = B.take(8ull * nk), b_plen = B.take(4ull * nk);
-    const size_t b_olen = B.take(4ull * ne), b_st = B.take(4ull * ne), b_det = B.take(16ull * ne), b_psum = B.take(4ull * nk), b_bad = B.take(4ull * nk),
-                 b_coff = B.take(8ull * n), b_clen = B.take(4ull * n), b_csum = B.take(4ull * n);
-    {
-        std::vector<uint32_t> last(n, 0xFFFFFFFFu);    // a stream's latest compressed block in the current group
-        auto put = [&](uint32_t at, const Entry& e, uint32_t prev) {
-            B.host<uint64_t>(b_in)[at] = e.in_off; B.host<uint64_t>(b_out)[at] = e.out_off; B.host<uint32_t>(b_len)[at] = e.in_len;
-            B.host<uint32_t>(b_cap)[at] = e.cap; B.host<uint32_t>(b_pos)[at] = e.pos; B.host<uint32_t>(b_prev)[at] = prev;
-        };
-        for (uint32_t j = 0; j < np; j++) put(j, plain[j], 0xFFFFFFFFu);
-        for (const Group& g : groups)
-            for (size_t j = g.lo; j < g.hi; j++) {
-                const Entry& e = chained[j];
-                put(np + (uint32_t)j, e, last[e.stream]);
-                last[e.stream] = (uint32_t)(j - g.lo);                                 // (indices count from the group's first block)
-            }
-        if (nr) { memcpy(B.host<uint64_t>(b_rin), r_in.data(), 8ull * nr); memcpy(B.host<uint64_t>(b_rout), r_out.data(), 8ull * nr); memcpy(B.host<uint32_t>(b_rlen), r_len.data(), 4ull * nr); }
-        if (nk) { memcpy(B.host<uint64_t>(b_poff), p_off.data(), 8ull * nk); memcpy(B.host<uint32_t>(b_plen), p_len.data(), 4ull * nk); }
-    }
+    np = (uint32_t)plain.size(); nc = (uint32_t)chained.size(); nr = (uint32_t)r_in.size(); nk = (uint32_t)p_off.size(); ne = np + nc;
+    bc = ManyBatchCols(B, ne, nr, nk, n);
+    std::vector<uint32_t> last(n, 0xFFFFFFFFu);        // a stream's latest compressed block in the current group
+    auto put = [&](uint32_t at, const Entry& e, uint32_t prev) {
+        B.host(bc.in)[at] = e.in_off; B.host(bc.out)[at] = e.out_off; B.host(bc.len)[at] = e.in_len;
+        B.host(bc.cap)[at] = e.cap; B.host(bc.pos)[at] = e.pos; B.host(bc.prev)[at] = prev;
+    };
+    for (uint32_t j = 0; j < np; j++) put(j, plain[j], 0xFFFFFFFFu);
+    for (const Group& g : groups)
+        for (size_t j = g.lo; j < g.hi; j++) {
+            const Entry& e = chained[j];
+            put(np + (uint32_t)j, e, last[e.stream]);
+            last[e.stream] = (uint32_t)(j - g.lo);                                     // (indices count from the group's first block)
+        }
+    B.fill(bc.rin, r_in.data()); B.fill(bc.rout, r_out.data()); B.fill(bc.rlen, r_len.data());
+    B.fill(bc.poff, p_off.data()); B.fill(bc.plen, p_len.data());
+}
+
+int ManyDecode::run_batch() {
     TRY_RC(upload(c, B, s));
     if (nk) {                                          // frame/decompress.rs:255-261,275-278: block checksums, before anything is decoded
-        TRY_RC(lz4flex_xxh32_batch_device(in, B.dev<uint64_t>(b_poff), B.dev<uint32_t>(b_plen), nk, 0, B.dev<uint32_t>(b_psum), s));
-        TRY_HIP(launch_frame_sums_check(in, B.dev<uint64_t>(b_poff), B.dev<uint32_t>(b_plen), B.dev<uint32_t>(b_psum), nk, B.dev<uint32_t>(b_bad), s));
+        TRY_RC(lz4flex_xxh32_batch_device(in, B.dev(bc.poff), B.dev(bc.plen), nk, 0, B.dev(bc.psum), s));
+        TRY_HIP(launch_frame_sums_check(in, B.dev(bc.poff), B.dev(bc.plen), B.dev(bc.psum), nk, B.dev(bc.bad), s));
     }
-    if (nr) TRY_RC(lz4flex_copy_batch_device(in, B.dev<uint64_t>(b_rin), B.dev<uint32_t>(b_rlen), out, B.dev<uint64_t>(b_rout), nr, s));   // :262-271
+    if (nr) TRY_RC(lz4flex_copy_batch_device(in, B.dev(bc.rin), B.dev(bc.rlen), out, B.dev(bc.rout), nr, s));   // :262-271
     bool big = false;
     for (const Entry& e : plain) big |= e.in_len > 131072u;
     if (np)
-        TRY_RC(lz4flex_decompress_batch(c, in, B.dev<uint64_t>(b_in), B.dev<uint32_t>(b_len), np, out, B.dev<uint64_t>(b_out), B.dev<uint32_t>(b_cap),
-                                        B.dev<uint32_t>(b_olen), B.dev<int32_t>(b_st), B.dev<uint64_t>(b_det), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
+        TRY_RC(lz4flex_decompress_batch(c, in, B.dev(bc.in), B.dev(bc.len), np, out, B.dev(bc.out), B.dev(bc.cap), B.dev(bc.olen), B.dev(bc.st),
+                                        B.dev(bc.det), LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
     for (const Group& g : groups) {
         const size_t o = np + g.lo;
         lz4flex_decompress_ext ext{};
-        ext.out_pos = B.dev<uint32_t>(b_pos) + o;
-        ext.chain_prev = B.dev<uint32_t>(b_prev) + o;
+        ext.out_pos = B.dev(bc.pos) + o;
+        ext.chain_prev = B.dev(bc.prev) + o;
         {
             uint32_t chains = 0;                       // (level-by-level order: the blocks without a predecessor are the chains)
-            for (size_t j = g.lo; j < g.hi; j++) chains += B.host<uint32_t>(b_prev)[np + j] == 0xFFFFFFFFu ? 1u : 0u;
+            for (size_t j = g.lo; j < g.hi; j++) chains += B.host(bc.prev)[np + j] == 0xFFFFFFFFu ? 1u : 0u;
             ext.n_chains = chains;
         }
         const int level_min = lz4flex_get_tuning(c, "decompress_level_chains");
@@ -362,30 +361,32 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
                 while (e < g.hi && chained[e].k == chained[j].k) e++;
                 const size_t oj = np + j;
                 lz4flex_decompress_ext lv{};
-                lv.out_pos = B.dev<uint32_t>(b_pos) + oj;
-                TRY_RC(lz4flex_decompress_batch_ex(c, in, B.dev<uint64_t>(b_in) + oj, B.dev<uint32_t>(b_len) + oj, (uint32_t)(e - j), out, B.dev<uint64_t>(b_out) + oj,
-                                                   B.dev<uint32_t>(b_cap) + oj, B.dev<uint32_t>(b_olen) + oj, B.dev<int32_t>(b_st) + oj, B.dev<uint64_t>(b_det) + 2 * oj, &lv,
-                                                   LZ4FLEX_MEM_DEVICE, s));
+                lv.out_pos = B.dev(bc.pos) + oj;
+                TRY_RC(lz4flex_decompress_batch_ex(c, in, B.dev(bc.in) + oj, B.dev(bc.len) + oj, (uint32_t)(e - j), out, B.dev(bc.out) + oj, B.dev(bc.cap) + oj,
+                                                   B.dev(bc.olen) + oj, B.dev(bc.st) + oj, B.dev(bc.det) + 2 * oj, &lv, LZ4FLEX_MEM_DEVICE, s));
                 j = e;
             }
             continue;
         }
-        TRY_RC(lz4flex_decompress_batch_ex(c, in, B.dev<uint64_t>(b_in) + o, B.dev<uint32_t>(b_len) + o, (uint32_t)(g.hi - g.lo), out, B.dev<uint64_t>(b_out) + o,
-                                           B.dev<uint32_t>(b_cap) + o, B.dev<uint32_t>(b_olen) + o, B.dev<int32_t>(b_st) + o, B.dev<uint64_t>(b_det) + 2 * o, &ext,
-                                           LZ4FLEX_MEM_DEVICE | LZ4FLEX_MEM_CHAINED, s));
+        TRY_RC(lz4flex_decompress_batch_ex(c, in, B.dev(bc.in) + o, B.dev(bc.len) + o, (uint32_t)(g.hi - g.lo), out, B.dev(bc.out) + o, B.dev(bc.cap) + o,
+                                           B.dev(bc.olen) + o, B.dev(bc.st) + o, B.dev(bc.det) + 2 * o, &ext, LZ4FLEX_MEM_DEVICE | LZ4FLEX_MEM_CHAINED, s));
     }
-    TRY_HIP(B.fetch<uint32_t>(b_olen, ne, s));
-    TRY_HIP(B.fetch<int32_t>(b_st, ne, s));
-    TRY_HIP(B.fetch<uint32_t>(b_bad, nk, s));
+    TRY_HIP(B.fetch(bc.olen, ne, s));
+    TRY_HIP(B.fetch(bc.st, ne, s));
+    TRY_HIP(B.fetch(bc.bad, nk, s));
     TRY_HIP(hipStreamSynchronize(s));
-    // ---- 4. verdicts
+    return 0;
+}
+
+// ---- 4. verdicts and content checksums, then the streams that go through decompress_one
+int ManyDecode::finish(uint64_t* out_len, int32_t* status, lz4flex_err_detail* detail) {
     std::vector<uint64_t> produced(raw_bytes);
-    for (uint32_t j = 0; j < nk; j++) if (B.host<uint32_t>(b_bad)[j]) again[p_stream[j]] = 1;
+    for (uint32_t j = 0; j < nk; j++) if (B.host(bc.bad)[j]) again[p_stream[j]] = 1;
     auto judge = [&](const Entry& e, uint32_t at) {
         const uint32_t i = e.stream;
-        const ManyFrame& m = W.host<ManyFrame>(a_fr)[i];
-        const uint32_t cnt = W.host<uint32_t>(a_info)[8ull * i], got = B.host<uint32_t>(b_olen)[at];
-        if (B.host<int32_t>(b_st)[at] != 0 || (e.k + 1 != cnt && got != m.block_size)) again[i] = 1;   // an error; a short block inside the frame (flush())
+        const ManyFrame& m = W.host(wc.fr)[i];
+        const uint32_t cnt = W.host(wc.info)[8ull * i], got = B.host(bc.olen)[at];
+        if (B.host(bc.st)[at] != 0 || (e.k + 1 != cnt && got != m.block_size)) again[i] = 1;   // an error; a short block inside the frame (flush())
         produced[i] += got;
     };
     for (uint32_t j = 0; j < np; j++) judge(plain[j], j);
@@ -397,19 +398,19 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         if (fi[i].has_content_size && fi[i].content_size != produced[i]) { again[i] = 1; continue; }
         if (fi[i].content_checksum) {
             if (produced[i] > 0xFFFFFFFFull) { again[i] = 1; continue; }
-            B.host<uint64_t>(b_coff)[cs.size()] = out_off[i]; B.host<uint32_t>(b_clen)[cs.size()] = (uint32_t)produced[i];
+            B.host(bc.coff)[cs.size()] = out_off[i]; B.host(bc.clen)[cs.size()] = (uint32_t)produced[i];
             cs.push_back(i);
         }
     }
     if (!cs.empty()) {
         const uint32_t m = (uint32_t)cs.size();
-        TRY_HIP(hipMemcpyAsync(B.dev<uint64_t>(b_coff), B.host<uint64_t>(b_coff), 8ull * m, hipMemcpyHostToDevice, s));
-        TRY_HIP(hipMemcpyAsync(B.dev<uint32_t>(b_clen), B.host<uint32_t>(b_clen), 4ull * m, hipMemcpyHostToDevice, s));
-        TRY_RC(lz4flex_xxh32_batch_device(out, B.dev<uint64_t>(b_coff), B.dev<uint32_t>(b_clen), m, 0, B.dev<uint32_t>(b_csum), s));
-        TRY_HIP(B.fetch<uint32_t>(b_csum, m, s));
+        TRY_HIP(hipMemcpyAsync(B.dev(bc.coff), B.host(bc.coff), 8ull * m, hipMemcpyHostToDevice, s));
+        TRY_HIP(hipMemcpyAsync(B.dev(bc.clen), B.host(bc.clen), 4ull * m, hipMemcpyHostToDevice, s));
+        TRY_RC(lz4flex_xxh32_batch_device(out, B.dev(bc.coff), B.dev(bc.clen), m, 0, B.dev(bc.csum), s));
+        TRY_HIP(B.fetch(bc.csum, m, s));
         TRY_HIP(hipStreamSynchronize(s));
         for (uint32_t j = 0; j < m; j++)
-            if (B.host<uint32_t>(b_csum)[j] != W.host<uint32_t>(a_info)[8ull * cs[j] + 4]) again[cs[j]] = 1;
+            if (B.host(bc.csum)[j] != W.host(wc.info)[8ull * cs[j] + 4]) again[cs[j]] = 1;
     }
     for (uint32_t i = 0; i < n; i++) {
         if (detail) memset(&detail[i], 0, sizeof detail[i]);
@@ -417,6 +418,17 @@ int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in
         TRY_RC(decompress_one(in + in_off[i], in_len[i], out + out_off[i], out_cap[i], &out_len[i], &status[i], detail ? &detail[i] : nullptr, s));
     }
     return 0;
+}
+
+int decompress_many_device(lz4flex_ctx* c, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t n, uint8_t* out,
+                           const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len, int32_t* status, lz4flex_err_detail* detail,
+                           hipStream_t s) {
+    ManyDecode m(ManyArgs{c, in, in_off, in_len, n, out, out_off, out_cap, s});
+    TRY_RC(m.read_heads());
+    TRY_RC(m.walk_tables());
+    m.build_batch();
+    TRY_RC(m.run_batch());
+    return m.finish(out_len, status, detail);
 }
 
 // ---- host buffers: staged through device scratch (slots 2 and 3), then the device path

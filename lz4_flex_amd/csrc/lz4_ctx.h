@@ -1,8 +1,9 @@
 // lz4_ctx.h -- the host layer's private state: struct lz4flex_ctx (opaque in include/lz4flex_amd.h) and the few helpers every host file
 // that works on a context needs (capi.cpp, frame_many.cpp; sharded.cpp: Desc alone).  Host only, not installed, no kernel includes it.
-// Two helpers stage descriptor columns, both over Layout (lz4_host_stage.h): Desc, below, is a pageable image whose device memory the
-// caller owns (a scratch slot, an allocation of its own) -- the frame layer, which holds several at once; HostStage (lz4_host_stage.h) is
-// the context's ONE page-locked buffer and arena, with the arena's data regions -- capi.cpp's MEM_HOST calls, one at a time per context.
+// Descriptor columns are declared in ONE way, ColumnPlan (lz4_host_stage.h: typed Col<T>, up before down), and two helpers own the memory
+// behind a plan: Desc, below, is a pageable image whose device memory the caller owns (a scratch slot, an allocation of its own) -- the
+// frame layer, which holds several at once and names its columns in frame_cols.h; HostStage (lz4_host_stage.h) is the context's ONE
+// page-locked buffer and arena, with the arena's data regions -- capi.cpp's MEM_HOST calls, one at a time per context.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,24 +16,30 @@
 
 namespace lz4flex_dev {
 
-// Descriptor and result arrays of one call, one behind the other at 64-byte starts: a host image and its device copy.  The caller
-// owns the device memory (frame_many.cpp: context scratch slot 0; sharded.cpp: an allocation of its own) and maps the hipError_t.
-// take(0) returns the offset the next take returns too: an array of no elements shares its start with its neighbour and is never touched.
-struct Desc {
-    Layout l{64};
+// Descriptor and result columns of one call at 64-byte starts: a column plan, its host image and its device copy.  The caller owns
+// the device memory (frame_many.cpp: context scratch slot 0; sharded.cpp: an allocation of its own) and maps the hipError_t.  The
+// image grows, zeroed, to the columns declared so far whenever it is touched: a host pointer is not kept across a later declaration.
+struct Desc : ColumnPlan {
     std::vector<uint8_t> h;
     uint8_t* d = nullptr;
-    size_t take(size_t bytes) { const size_t at = l.take(bytes); h.resize(l.end, 0); return at; }
-    size_t bytes() const { return l.end; }
-    template <class T> T* host(size_t at) { return reinterpret_cast<T*>(h.data() + at); }
-    template <class T> T* dev(size_t at) const { return reinterpret_cast<T*>(d + at); }
-    // the image's first `n` bytes (what the device only writes may lie behind them) to `dev_mem`, which holds bytes() of them
+    Desc() : ColumnPlan(64) {}
+    uint8_t* image() { if (h.size() < total()) h.resize(total(), 0); return h.data(); }
+    template <class T> T* host(Col<T> c) { return view(image(), c); }
+    template <class T> T* dev(Col<T> c) const { return view(d, c); }
+    template <class T, class U> void fill(Col<T> c, const U* src) {
+        static_assert(sizeof(T) == sizeof(U), "a column takes its caller's array as it is");
+        if (c.count) memcpy(host(c), src, sizeof(T) * c.count);
+    }
+    // the image's first `n` bytes (up_bytes, or total(): what the device only writes lies behind up_bytes) to `dev_mem`, which holds total()
     hipError_t upload(void* dev_mem, size_t n, hipStream_t s) {
         d = (uint8_t*)dev_mem;
-        return n ? hipMemcpyAsync(d, h.data(), n, hipMemcpyHostToDevice, s) : hipSuccess;
+        return n ? hipMemcpyAsync(d, image(), n, hipMemcpyHostToDevice, s) : hipSuccess;
     }
-    template <class T> hipError_t fetch(size_t at, size_t count, hipStream_t s) {
-        return count ? hipMemcpyAsync(h.data() + at, d + at, count * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
+    template <class T> hipError_t fetch(Col<T> c, size_t count, hipStream_t s) {
+        return count ? hipMemcpyAsync(image() + c.at, d + c.at, count * sizeof(T), hipMemcpyDeviceToHost, s) : hipSuccess;
+    }
+    template <class T> hipError_t fetch_columns(Col<T> first, hipStream_t s) {      // from this column to the end, one copy
+        return hipMemcpyAsync(image() + first.at, d + first.at, from(first), hipMemcpyDeviceToHost, s);
     }
 };
 

@@ -1,7 +1,8 @@
 // lz4_host_stage.h -- how a MEM_HOST call of the C ABI mirrors the caller's host layout on the device (capi.cpp: every batched entry
-// point that takes LZ4FLEX_MEM_HOST).  Host only, no kernel includes it.  Two layers:
-//   StagePlan   pure arithmetic (no HIP header: tests/sim/host_stage_shim.cpp compiles it with g++ under LZ4FLEX_STAGE_PLAN_ONLY): the
-//               descriptor and result COLUMNS of a call, one image that page-locked memory and the arena share, and the REGIONS of the arena;
+// point that takes LZ4FLEX_MEM_HOST).  Host only, no kernel includes it.  Its layers:
+//   ColumnPlan  pure arithmetic (no HIP header: tests/sim/ compiles it with g++ under LZ4FLEX_STAGE_PLAN_ONLY): the descriptor and result
+//               COLUMNS of a call, one image that a host buffer and device memory share -- the frame layer's Desc (lz4_ctx.h) is one too;
+//   StagePlan   the columns and the REGIONS of the arena, the column image among them;
 //   HostStage   the plan bound to a context's page-locked buffer, its arena and its stream (capi.cpp stage_open grows the two buffers):
 //               typed views of the columns on either side, the fillers, the transfers.
 // The rule every path follows: the caller's offsets are rebased onto the span they cover (fill_offsets), the span goes up into a region
@@ -29,18 +30,26 @@ struct Layout {
 template <class T> struct Col { size_t at, count; };      // `count` elements at byte `at` of the column image
 struct Region { size_t at, bytes, room; };                // `bytes` at byte `at` of the arena; the next region starts `room` behind it
 
-// Declared in the caller's order: every up() before every down(), the regions in their order in the arena, columns() among them once
-// the last column is declared.  A column of 0 elements shares its start with its neighbour and is never touched (Desc's rule, lz4_ctx.h).
-struct StagePlan {
+// The columns of one image, declared in the caller's order: every up() before every down().  A column of 0 elements shares its start
+// with its neighbour and is never touched.  The one column arithmetic of the host layer: StagePlan (below) and Desc (lz4_ctx.h) are
+// column plans, frame_cols.h names the frame layer's columns over one.
+struct ColumnPlan {
     Layout cols;
     size_t up_bytes = 0;          // what the device reads lies in front of this, what it only writes behind
-    size_t arena_end = 0, arena_bytes = 256;
-    Region desc{0, 0, 0};         // where the column image lies in the arena
-    explicit StagePlan(size_t align = 16) : cols{align} {}
+    explicit ColumnPlan(size_t align = 16) : cols{align} {}
     template <class T> Col<T> up(size_t count) { const Col<T> c{cols.take(sizeof(T) * count), count}; up_bytes = cols.end; return c; }
     template <class T> Col<T> down(size_t count) { return Col<T>{cols.take(sizeof(T) * count), count}; }
     size_t total() const { return cols.end; }
     template <class T> size_t from(Col<T> c) const { return cols.end - c.at; }      // from this down column to the end
+    // the column in memory that holds the image at `base` (device scratch that has no host image: frame_index.cpp index_build)
+    template <class T> static T* view(void* base, Col<T> c) { return reinterpret_cast<T*>(static_cast<uint8_t*>(base) + c.at); }
+};
+
+// The columns and, in their order in the arena, the regions; columns() among them once the last column is declared.
+struct StagePlan : ColumnPlan {
+    size_t arena_end = 0, arena_bytes = 256;
+    Region desc{0, 0, 0};         // where the column image lies in the arena
+    explicit StagePlan(size_t align = 16) : ColumnPlan(align) {}
     // a region starts at a multiple of 256.  slack: the kernels read whole dwords / 16-byte units behind a region's last byte (the data
     // regions take 64); the 256 bytes behind the last region's last byte keep the same reads inside the allocation
     Region region(size_t bytes, size_t slack) {

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/lz4flex_amd.h"
+#include "frame_cols.h"
 #include "frame_plan.h"
 #include "lz4_ctx.h"
 #include "lz4_device.h"
@@ -31,6 +32,8 @@
 namespace {
 
 using lz4flex_dev::Desc;
+using lz4flex_dev::ShardDecodeCols;
+using lz4flex_dev::ShardEncodeCols;
 using namespace lz4flex_plan;   // block sizes, BLOCK_UNCOMPRESSED_SIZE_BIT, TableOffset
 
 // ---- the few RCCL entry points used (rccl.h: ncclResult_t f(...), 0 = ncclSuccess; ncclUint8 = 1, ncclUint64 = 5)
@@ -134,33 +137,29 @@ int lz4flex_frame_compress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank, 
     TRY_HIP(seg.alloc(lz4flex_frame_segment_bound(local_len, info)));
     if (n) {
         TRY_HIP(comp.alloc(stride * n));
-        Desc D;           // (the assembler's scratch, o_scr, is taken last so that one layout gives the device size: its host bytes, behind `up`, are never uploaded or read)
-        const size_t o_in_off = D.take(8ull * n), o_comp_off = D.take(8ull * n), o_seg_off = D.take(8ull * n + 8), o_in_len = D.take(4ull * n),
-                     o_cap = D.take(4ull * n), o_clen = D.take(4ull * n), o_st = D.take(4ull * n), o_fl = D.take(4ull * n), up = D.bytes(),
-                     o_scr = D.take(16ull * n);
-        TRY_HIP(desc.alloc(D.bytes()));
+        Desc D;
+        const ShardEncodeCols o(D, n);
+        TRY_HIP(desc.alloc(D.total()));
         // per-block table mode of a FrameEncoder that has already written first_block full blocks (frame_plan.h)
         TableOffset tbl;
         for (uint64_t k = 0; k < first_block; k++) (void)tbl.next(bs, bs);
         for (uint32_t i = 0; i < n; i++) {
             const uint32_t len = (uint32_t)std::min<uint64_t>(bs, local_len - (uint64_t)i * bs);
-            D.host<uint64_t>(o_in_off)[i] = (uint64_t)i * bs;
-            D.host<uint64_t>(o_comp_off)[i] = (uint64_t)i * stride;
-            D.host<uint32_t>(o_in_len)[i] = len;
-            D.host<uint32_t>(o_cap)[i] = (uint32_t)stride;
-            D.host<uint32_t>(o_fl)[i] = tbl.next(bs, len);
+            D.host(o.in_off)[i] = (uint64_t)i * bs;
+            D.host(o.comp_off)[i] = (uint64_t)i * stride;
+            D.host(o.in_len)[i] = len;
+            D.host(o.cap)[i] = (uint32_t)stride;
+            D.host(o.fl)[i] = tbl.next(bs, len);
         }
-        TRY_HIP(D.upload(desc.p, up, s));
-        TRY_RC(lz4flex_compress_batch(ctx, local, D.dev<uint64_t>(o_in_off), D.dev<uint32_t>(o_in_len), D.dev<uint32_t>(o_fl), n, comp.p,
-                                      D.dev<uint64_t>(o_comp_off), D.dev<uint32_t>(o_cap), D.dev<uint32_t>(o_clen), D.dev<int32_t>(o_st),
-                                      LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
-        TRY_RC(lz4flex_frame_assemble_device(local, D.dev<uint64_t>(o_in_off), D.dev<uint32_t>(o_in_len), comp.p, D.dev<uint64_t>(o_comp_off),
-                                             D.dev<uint32_t>(o_clen), n, info->block_checksums, seg.p, D.dev<uint64_t>(o_seg_off),
-                                             D.dev<uint8_t>(o_scr), s));
-        TRY_HIP(D.fetch<int32_t>(o_st, n, s));
-        TRY_HIP(hipMemcpyAsync(&seg_bytes, D.dev<uint64_t>(o_seg_off) + n, 8, hipMemcpyDeviceToHost, s));
+        TRY_HIP(D.upload(desc.p, D.up_bytes, s));          // (everything in front of the assembler's scratch)
+        TRY_RC(lz4flex_compress_batch(ctx, local, D.dev(o.in_off), D.dev(o.in_len), D.dev(o.fl), n, comp.p, D.dev(o.comp_off), D.dev(o.cap),
+                                      D.dev(o.clen), D.dev(o.st), LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
+        TRY_RC(lz4flex_frame_assemble_device(local, D.dev(o.in_off), D.dev(o.in_len), comp.p, D.dev(o.comp_off), D.dev(o.clen), n,
+                                             info->block_checksums, seg.p, D.dev(o.seg_off), D.dev(o.scr), s));
+        TRY_HIP(D.fetch(o.st, n, s));
+        TRY_HIP(hipMemcpyAsync(&seg_bytes, D.dev(o.seg_off) + n, 8, hipMemcpyDeviceToHost, s));
         TRY_HIP(hipStreamSynchronize(s));
-        for (uint32_t i = 0; i < n; i++) if (D.host<int32_t>(o_st)[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
+        for (uint32_t i = 0; i < n; i++) if (D.host(o.st)[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
     }
     return 0;
     }();
@@ -357,31 +356,27 @@ int lz4flex_frame_decompress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank
     }
     const uint32_t nc = (uint32_t)c_in.size(), nr = (uint32_t)r_in.size();
     Desc D;
-    auto put = [&](const void* src, size_t bytes) { const size_t at = D.take(bytes); if (bytes) memcpy(D.host<uint8_t>(at), src, bytes); return at; };
-    const size_t o_cin = put(c_in.data(), 8ull * nc), o_cout = put(c_out.data(), 8ull * nc), o_rin = put(r_in.data(), 8ull * nr),
-                 o_rout = put(r_out.data(), 8ull * nr), o_poff = put(p_off.data(), 8ull * n), o_clen = put(c_len.data(), 4ull * nc),
-                 o_ccap = put(c_cap.data(), 4ull * nc), o_rlen = put(r_len.data(), 4ull * nr), o_plen = put(p_len.data(), 4ull * n);
-    const size_t o_colen = D.take(4ull * nc), o_cst = D.take(4ull * nc), o_psum = D.take(4ull * n), o_bad = D.take(4ull * n);   // (results)
+    const ShardDecodeCols o(D, nc, nr, n);
+    D.fill(o.cin, c_in.data()); D.fill(o.cout, c_out.data()); D.fill(o.rin, r_in.data()); D.fill(o.rout, r_out.data()); D.fill(o.poff, p_off.data());
+    D.fill(o.clen, c_len.data()); D.fill(o.ccap, c_cap.data()); D.fill(o.rlen, r_len.data()); D.fill(o.plen, p_len.data());
     DevBuf dd;
-    TRY_HIP(dd.alloc(D.bytes()));
-    TRY_HIP(D.upload(dd.p, D.bytes(), s));
+    TRY_HIP(dd.alloc(D.total()));
+    TRY_HIP(D.upload(dd.p, D.total(), s));             // (the whole image, the result columns' zeros included)
     if (has_bc) {                                                    // frame/decompress.rs:255-261,275-278: verify before decoding
-        TRY_RC(lz4flex_xxh32_batch_device(local, D.dev<uint64_t>(o_poff), D.dev<uint32_t>(o_plen), n, 0, D.dev<uint32_t>(o_psum), s));
-        TRY_HIP(lz4flex_dev::launch_frame_sums_check(local, D.dev<uint64_t>(o_poff), D.dev<uint32_t>(o_plen), D.dev<uint32_t>(o_psum), n,
-                                                     D.dev<uint32_t>(o_bad), s));
-        TRY_HIP(D.fetch<uint32_t>(o_bad, n, s));
+        TRY_RC(lz4flex_xxh32_batch_device(local, D.dev(o.poff), D.dev(o.plen), n, 0, D.dev(o.psum), s));
+        TRY_HIP(lz4flex_dev::launch_frame_sums_check(local, D.dev(o.poff), D.dev(o.plen), D.dev(o.psum), n, D.dev(o.bad), s));
+        TRY_HIP(D.fetch(o.bad, n, s));
         TRY_HIP(hipStreamSynchronize(s));
-        for (uint32_t i = 0; i < n; i++) if (D.host<uint32_t>(o_bad)[i]) return -LZ4FLEX_FE_BLOCK_CHECKSUM;
+        for (uint32_t i = 0; i < n; i++) if (D.host(o.bad)[i]) return -LZ4FLEX_FE_BLOCK_CHECKSUM;
     }
-    if (nc) TRY_RC(lz4flex_decompress_batch(ctx, local, D.dev<uint64_t>(o_cin), D.dev<uint32_t>(o_clen), nc, out, D.dev<uint64_t>(o_cout),
-                                            D.dev<uint32_t>(o_ccap), D.dev<uint32_t>(o_colen), D.dev<int32_t>(o_cst), nullptr,
-                                            LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
-    if (nr) TRY_RC(lz4flex_copy_batch_device(local, D.dev<uint64_t>(o_rin), D.dev<uint32_t>(o_rlen), out, D.dev<uint64_t>(o_rout), nr, s));
-    TRY_HIP(D.fetch<uint32_t>(o_colen, nc, s));
-    TRY_HIP(D.fetch<int32_t>(o_cst, nc, s));
+    if (nc) TRY_RC(lz4flex_decompress_batch(ctx, local, D.dev(o.cin), D.dev(o.clen), nc, out, D.dev(o.cout), D.dev(o.ccap), D.dev(o.colen), D.dev(o.cst),
+                                            nullptr, LZ4FLEX_MEM_DEVICE | (bs > 65536 ? LZ4FLEX_MEM_BIG_BLOCKS : 0), s));
+    if (nr) TRY_RC(lz4flex_copy_batch_device(local, D.dev(o.rin), D.dev(o.rlen), out, D.dev(o.rout), nr, s));
+    TRY_HIP(D.fetch(o.colen, nc, s));
+    TRY_HIP(D.fetch(o.cst, nc, s));
     TRY_HIP(hipStreamSynchronize(s));
-    const uint32_t* olen = D.host<uint32_t>(o_colen);
-    const int32_t* st = D.host<int32_t>(o_cst);
+    const uint32_t* olen = D.host(o.colen);
+    const int32_t* st = D.host(o.cst);
     uint64_t produced = 0;
     for (uint32_t i = 0, ci = 0, ri = 0; i < n; i++) {
         uint32_t got;

@@ -64,14 +64,16 @@ def _run(world, fn):
 
 @pytest.mark.parametrize("mode", ["exact", "fast"])
 @pytest.mark.parametrize("world", [2, 4])
-@pytest.mark.parametrize("bs_code,n_blocks,tail,bc", [(4, 11, 12345, False), (4, 3, 0, True), (7, 5, 128 * 999, False)])
+@pytest.mark.parametrize("bs_code,n_blocks,tail,bc", [(4, 11, 12345, False), (4, 3, 0, True), (7, 5, 128 * 999, False), (4, 5, 1000, "incompressible")])
 def test_frame_across_ranks_through_the_c_abi(env, world, mode, bs_code, n_blocks, tail, bc):
     lib, L, mock, torch, sharded, workloads = env
     bs = {4: 65536, 7: 4 << 20}[bs_code]
     total = n_blocks * bs + tail - (tail % 128)
     nb_all = (total + bs - 1) // bs
     src = workloads.log_stream(0, total, device="cuda")
-    if bc:      # an incompressible block in the middle: stored raw
+    if bc == "incompressible":      # every block stored raw: a rank decodes no compressed block (block checksums on)
+        src = torch.from_numpy(np.random.default_rng(4).integers(0, 256, total, dtype=np.uint8)).cuda()
+    elif bc:    # an incompressible block in the middle: stored raw
         src[bs:bs + 5000] = torch.from_numpy(np.random.default_rng(3).integers(0, 256, 5000, dtype=np.uint8)).cuda()
     host = src.cpu().numpy().tobytes()
     torch.cuda.synchronize()
@@ -101,7 +103,7 @@ def test_frame_across_ranks_through_the_c_abi(env, world, mode, bs_code, n_block
     rc, back, used = O.frame_decompress(got, total)
     assert rc == 0 and back == host and used == len(got), "the oracle's FrameDecoder does not return the stream"
     if mode == "exact":
-        rc_o, exp = O.frame_compress(host, block_size=bs_code, block_checksums=bc)
+        rc_o, exp = O.frame_compress(host, block_size=bs_code, block_checksums=bool(bc))
         assert rc_o == 0 and got == exp, "the frame gathered from the ranks != the oracle's FrameEncoder bytes"
     # ---- and back: the root holds the frame, every rank receives and decodes its block range
     outs = [torch.zeros(max(ranges[r][1] - ranges[r][0], 1) * bs, dtype=torch.uint8, device="cuda") for r in range(world)]
