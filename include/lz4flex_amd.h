@@ -101,7 +101,9 @@ const char *lz4flex_build_id(void);
  * caller detects it by lz4flex_filter_batch(NULL, ..., n = 0, ..., filter = 0x10, ...) == 0), then the fit batches lz4flex_fit_batch /
  * lz4flex_compress_batch_fit with lz4flex_compress_fit_work_size and the setting "fit_serial" (no workspace in the context: the caller
  * brings scratch and work; a caller detects them by the symbol), then the setting "compress_parse" for "compress_mode" 2 (no new symbol,
- * no workspace beyond the encoder's: a caller detects it by lz4flex_set_tuning(ctx, "compress_parse", 1) == 0). */
+ * no workspace beyond the encoder's: a caller detects it by lz4flex_set_tuning(ctx, "compress_parse", 1) == 0), then the paged streams
+ * lz4flex_compress_paged with lz4flex_compress_paged_work_size, lz4flex_paged_pages_bound and lz4flex_paged_rounds_bound (no setting, no
+ * workspace in the context: the caller brings scratch and work; a caller detects them by the symbol). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -777,6 +779,68 @@ size_t lz4flex_compress_fit_work_size(uint32_t n);
 int lz4flex_compress_batch_fit(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
                                void *scratch, uint64_t scratch_cap, void *out_base, const uint64_t *out_off, const uint32_t *out_cap,
                                uint32_t *out_len, uint32_t *in_used, int32_t *status, void *work, int mem_kind, void *hip_stream);
+
+/* ---- paged streams: every stream cut into pages of page_size bytes, the loop on the device (lz4_paged.hip) ---------------------------
+ * "Cut each of my n streams into pages of P bytes."  Every page is a self-contained LZ4 block that holds as much of its stream as fits,
+ * page j + 1 starts where page j stopped: the LZ4_compress_destSize loop of fixed-output compression, with no host round trip between
+ * pages.  The read side exists: a page is an ordinary block, lz4flex_decompress_batch over the page table puts a stream back together,
+ * lz4flex_decompress_batch_partial reads into a page.
+ *
+ * THE RULE (tests/paged_model.py is the same rule as a program).  P = page_size; stream i is the in_len[i] bytes at in_base + in_off[i]
+ * and owns the table entries `[page_off[i], page_off[i+1])`, its capacity `C_i = page_off[i+1] - page_off[i]` pages.  Its state is
+ * `pos = 0`, `W = window_min`, `k = 0`.  A stream with `in_len == 0` is finished at once with 0 pages and status 0; a stream with
+ * `in_len != 0` and `C_i == 0` ends at once with LZ4FLEX_E_OUTPUT_TOO_SMALL.  One ROUND, for every stream that is still live:
+ *   Offer `w = min(W, in_len - pos)`.  `(block, out_len, used, st)` is the result of lz4flex_compress_batch_fit for the window
+ *     `src[pos, pos + w)` at capacity P, computed in ONE batch that holds all n streams' windows of this round -- a stream that is not
+ *     live has an empty window at capacity 0 whose result is ignored -- so n is the same in every round, and the bytes of
+ *     "compress_mode" 0, which depend on n through "compress_subwindows", are those of that one batch.
+ *   `st != 0`: the stream ends with that status; its pages so far stay valid.
+ *   Retry: `used == w`, `pos + w < in_len` and `W < window_max`.  Nothing is committed, `W = min(2 * W, window_max)`: the window fit
+ *     whole, so a larger one might fill the page better.
+ *   Commit otherwise: entry `e = page_off[i] + k`, `page_len[e] = out_len`, `page_src[e] = pos`, the block is the first out_len bytes of
+ *     page e at `out_base + e * P`; `pos += used`, `k += 1`.  If `pos == in_len` the stream is finished with status 0; else if
+ *     `k == C_i` it is out of pages and ends with LZ4FLEX_E_OUTPUT_TOO_SMALL.
+ *   A stream that is still live after max_rounds rounds ends with LZ4FLEX_E_OUTPUT_TOO_SMALL; `n_pages[i] < C_i` tells the two causes apart.
+ * Results: per stream `n_pages[i] = k`, `in_done[i] = pos`, status[i]; per committed entry page_len, page_src and the page's bytes.
+ * Invariants: page e decodes to `src[page_src[e], page_src[e+1])` (the last page of a stream: up to in_done[i]); pages are independent of
+ *   each other, any LZ4 block decoder reads them; every committed page of a stream that has more to come consumed at least
+ *   `Lfit(P, infinity)` bytes (Lfit: the fit rule's function above; Plain(0) is always a candidate), so `used >= 1` and the loop ends; W
+ *   only grows, so a stream retries at most as often as window_min doubles up to window_max.  Hence the two bounds, pure host functions
+ *   that need no device: lz4flex_paged_pages_bound(in_len, page_size) = `ceil(in_len / Lfit(page_size, infinity))` -- a capacity that
+ *   always suffices -- and lz4flex_paged_rounds_bound(max_in_len, page_size, window_min, window_max) = that bound plus the number of
+ *   doublings from window_min to window_max (0 selects the defaults, as below) -- a max_rounds that always suffices.  Both return 0 for
+ *   arguments the entry refuses.
+ * Why windows: a round encodes every byte it is offered, so the work follows what a page holds (a few window lengths), not what is left
+ *   of the stream.  Why they double: a window that fits a page whole says nothing about how much more would have fit; data that
+ *   compresses better than window_max / P leaves its pages underfilled (a run of zeros: window_max bytes per page, whatever P is).
+ * Arguments: `64 <= page_size <= 4 MiB`, `page_size <= window_min <= window_max <= 2^31`; 0 selects the defaults `window_min = 4 *
+ *   page_size`, `window_max = max(window_min, 65536)`.  Anything else is -LZ4FLEX_E_INVALID_ARG, and so are a mem_kind other than HOST /
+ *   DEVICE (| BIG_BLOCKS; LZ4FLEX_MEM_CHAINED is refused) and, with n != 0, a missing array (DEVICE: a missing scratch or work; HOST: a
+ *   page_off that counts down).  The arguments are checked before a context or a device is looked at; n == 0 returns 0;
+ *   -LZ4FLEX_E_NO_DEVICE without a device.  page_off has n + 1 values, counted in ENTRIES, not bytes.
+ * What may be written: the page file `[out_base, out_base + page_off[n] * P)` -- the bytes of a page behind its page_len are unspecified,
+ *   and so are the pages at or behind n_pages[i] --, the table entries of committed pages, the three per-stream results.  Nothing else:
+ *   table entries at or behind n_pages[i] stay untouched.
+ * mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, asynchronous on hip_stream, nothing is allocated and nothing is
+ *   synchronised; exactly max_rounds rounds are enqueued, each one the launches of lz4flex_compress_batch_fit plus one step kernel, a
+ *   lane per stream (a round in which no stream is live still costs its launches: size max_rounds by what the data can need, not by the
+ *   bound, when that is known).  scratch: `scratch_cap >= lz4flex_compress_packed_scratch_bound(sum of min(in_len[i], window_max), n, 0)`
+ *   always suffices; a window whose slot ends behind scratch_cap fails its stream with the encoder's LZ4FLEX_E_OUTPUT_TOO_SMALL, as in the
+ *   fit entry.  work: lz4flex_compress_paged_work_size(n) bytes, 8-byte aligned.  in_done and n_pages hold the loop's state between rounds.
+ *   LZ4FLEX_MEM_HOST -- staged through the context and synchronous; the number of rounds is min(max_rounds, the rounds bound of the
+ *   longest stream), computed from the host-visible lengths; scratch and work are ignored.  LZ4FLEX_MEM_BIG_BLOCKS is passed through
+ *   to the encoder in every round (HOST: also set when a window can be longer than 64 KiB).
+ * The context's settings apply unchanged: "compress_mode" 0 / 1 / 2, "compress_depth", "compress_parse", "fit_serial".
+ * Not in scope: dictionaries, history or linked pages (they need the fit pass's history form, the follow-up named above), filters,
+ *   frames, an early stop inside the encoders. */
+int lz4flex_compress_paged(lz4flex_ctx *ctx, const void *in_base, const uint64_t *in_off, const uint32_t *in_len, uint32_t n,
+                           uint32_t page_size, uint32_t window_min, uint32_t window_max, uint32_t max_rounds, void *out_base,
+                           const uint64_t *page_off /* n + 1, entries */, uint32_t *page_len, uint32_t *page_src, uint32_t *n_pages,
+                           uint32_t *in_done, int32_t *status, void *scratch, uint64_t scratch_cap, void *work, int mem_kind,
+                           void *hip_stream);
+size_t lz4flex_compress_paged_work_size(uint32_t n);
+uint64_t lz4flex_paged_pages_bound(uint32_t in_len, uint32_t page_size);
+uint32_t lz4flex_paged_rounds_bound(uint32_t max_in_len, uint32_t page_size, uint32_t window_min, uint32_t window_max);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

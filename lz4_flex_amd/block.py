@@ -1061,6 +1061,180 @@ def compress_blocks_fit_device(src, in_off, in_len, out_cap, stream=None, scratc
     return out, out_off, out_len, used, status
 
 
+# ---- paged streams: every stream cut into pages of page_size bytes (lz4flex_compress_paged) -----------------------------------------------
+class PagedStreams:
+    """What compress_paged / compress_paged_device return and decompress_paged / decompress_paged_device take: the page file `pages` (page
+    e is pages[e * page_size : e * page_size + page_len[e]], a self-contained LZ4 block that decodes to the stream's bytes from page_src[e]
+    on), the table page_len / page_src, stream i's entries [page_off[i], page_off[i] + n_pages[i]), and per stream in_done (the bytes its
+    pages hold) and status (0, or the code the stream ended with: its pages so far stay valid).  numpy arrays from the host form, device
+    tensors from the device form."""
+    __slots__ = ("page_size", "pages", "page_off", "page_len", "page_src", "n_pages", "in_done", "status")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+
+def paged_pages_bound(in_len, page_size):
+    """lz4flex_paged_pages_bound: the pages that always suffice for a stream of in_len bytes"""
+    return int(L.load().lz4flex_paged_pages_bound(int(in_len), int(page_size)))
+
+
+def paged_rounds_bound(max_in_len, page_size, window_min=0, window_max=0):
+    """lz4flex_paged_rounds_bound: the max_rounds that always suffices for streams of at most max_in_len bytes"""
+    return int(L.load().lz4flex_paged_rounds_bound(int(max_in_len), int(page_size), int(window_min), int(window_max)))
+
+
+def _paged_windows(page_size, window_min, window_max):
+    """the windows with the header's defaults resolved (the checks are the library's)"""
+    window_min = int(window_min) or 4 * int(page_size)
+    return window_min, int(window_max) or max(window_min, 65536)
+
+
+def compress_paged(streams, page_size, page_cap=None, window_min=0, window_max=0, max_rounds=None, ctx=None):
+    """lz4flex_compress_paged over host bytes: every stream (bytes-like) cut into pages of page_size bytes, each page a self-contained LZ4
+    block that holds as much of its stream as fits (the rule: include/lz4flex_amd.h; compress_mode as set).  page_cap: the pages stream i
+    may take (default: paged_pages_bound, which always suffices); max_rounds default: paged_rounds_bound of the longest stream.  Returns a
+    PagedStreams of numpy arrays; a stream that ran out of pages or rounds has status E_OUTPUT_TOO_SMALL and valid pages so far."""
+    page_size = int(page_size)
+    parts = [_host_u8(s) for s in streams]
+    n = len(parts)
+    in_len = np.array([p.size for p in parts], dtype=np.uint32)
+    in_off = np.zeros(n, dtype=np.uint64)
+    if n:
+        in_off[1:] = np.cumsum(in_len[:-1], dtype=np.uint64)
+    src = np.concatenate(parts + [np.zeros(1, dtype=np.uint8)])
+    cap = [paged_pages_bound(v, page_size) for v in in_len] if page_cap is None else [int(v) for v in page_cap]
+    if len(cap) != n:
+        raise ValueError("streams and page_cap differ in length")
+    page_off = np.zeros(n + 1, dtype=np.uint64)
+    page_off[1:] = np.cumsum(np.array(cap, dtype=np.uint64))
+    entries = int(page_off[n])
+    if max_rounds is None:
+        max_rounds = paged_rounds_bound(int(in_len.max()) if n else 0, page_size, window_min, window_max)
+    res = PagedStreams(page_size=page_size, pages=np.zeros(max(entries * page_size, 1), dtype=np.uint8)[:entries * page_size], page_off=page_off,
+                       page_len=np.zeros(entries, dtype=np.uint32), page_src=np.zeros(entries, dtype=np.uint32),
+                       n_pages=np.zeros(n, dtype=np.uint32), in_done=np.zeros(n, dtype=np.uint32), status=np.zeros(n, dtype=np.int32))
+    keep = [np.zeros(1, dtype=np.uint32) if a.size == 0 else a for a in (res.pages, res.page_len, res.page_src)]     # (an empty table still needs an address)
+    args = [src, in_off, in_len, n, page_size, int(window_min), int(window_max), int(max_rounds), keep[0], page_off, keep[1], keep[2],
+            res.n_pages, res.in_done, res.status, None, 0, None]
+    _check(L.load().lz4flex_compress_paged(ctx, *map(_arg, args), L.MEM_HOST, None), "lz4flex_compress_paged")
+    return res
+
+
+def decompress_paged(paged, ctx=None):
+    """The streams of a PagedStreams (host form) back as a list of bytes -- stream i's first in_done[i] bytes -- with ONE decompress_batch
+    over the page table: page e of stream i decodes to [page_src[e], page_src[e + 1]) of it (the last page: up to in_done[i])."""
+    P = int(paged.page_size)
+    n = len(paged.n_pages)
+    base = np.zeros(n + 1, dtype=np.uint64)
+    base[1:] = np.cumsum(paged.in_done.astype(np.uint64))
+    in_off, in_len, out_off, out_cap = [], [], [], []
+    for i in range(n):
+        first, k = int(paged.page_off[i]), int(paged.n_pages[i])
+        starts = [int(v) for v in paged.page_src[first:first + k]] + [int(paged.in_done[i])]
+        for j in range(k):
+            in_off.append((first + j) * P)
+            in_len.append(int(paged.page_len[first + j]))
+            out_off.append(int(base[i]) + starts[j])
+            out_cap.append(starts[j + 1] - starts[j])
+    out = np.zeros(max(int(base[n]), 1), dtype=np.uint8)
+    if in_off:
+        out_len, status, _ = decompress_batch(paged.pages, in_off, in_len, out, out_off, out_cap, ctx=ctx)
+        bad = np.nonzero((status != 0) | (out_len != np.array(out_cap, dtype=np.uint32)))[0]
+        if bad.size:
+            raise DecompressError("page entry %d does not decode to its slice (status %d)" % (in_off[int(bad[0])] // P, int(status[bad[0]])))
+    return [out[int(base[i]):int(base[i + 1])].tobytes() for i in range(n)]
+
+
+def compress_paged_device(src, in_off, in_len, page_size, page_cap=None, window_min=0, window_max=0, max_rounds=None, stream=None,
+                          scratch_cap=None):
+    """Streams in device memory cut into pages: src is a uint8 torch tensor on the GPU, stream i is src[in_off[i] : in_off[i] + in_len[i]].
+    page_cap (an integer tensor; default: lz4flex_paged_pages_bound of every length, computed on the device) gives the page table by an
+    exclusive prefix sum; ONE host synchronisation for the sizes (the entries, the longest stream, the scratch the windows need), then one
+    lz4flex_compress_paged (MEM_DEVICE, asynchronous on `stream`, default the current one: max_rounds rounds are enqueued, default the
+    rounds bound of the longest stream).  Scratch and workspace are allocated here, by torch's allocator on the CURRENT stream, as in the
+    other device forms.  Returns a PagedStreams of device tensors (page_len / page_src / n_pages / in_done: the int32 bit patterns of u32)."""
+    import torch
+    page_size = int(page_size)
+    dev, n, d_off, d_len, sp = _device_args(src, in_off, in_len, stream, wide_len=True)
+    lib = L.load()
+    window_min_r, window_max_r = _paged_windows(page_size, window_min, window_max)
+    if page_cap is None:
+        # lz4flex_paged_pages_bound(len) = ceil(len / lfit) for every length at once: lfit is the longest stream that takes one page
+        y = page_size - 17
+        lfit = 15 + y - y // 256 - (1 if y % 256 == 255 else 0)
+        if paged_pages_bound(lfit, page_size) != 1 or paged_pages_bound(lfit + 1, page_size) != 2:
+            raise ValueError("page_size %d: not a page size of lz4flex_compress_paged" % page_size)
+        cap = (d_len + (lfit - 1)) // lfit
+    else:
+        if int(page_cap.numel()) != n:
+            raise ValueError("in_off and page_cap differ in length")
+        cap = page_cap.to(device=dev, dtype=torch.int64)
+    page_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        page_off[1:] = torch.cumsum(cap, 0)
+        entries, longest, offered = (int(v) for v in torch.stack([page_off[n], d_len.max(), torch.clamp(d_len, max=window_max_r).sum()]).cpu())
+    else:
+        entries = longest = offered = 0
+    i32 = lambda m: torch.zeros(m, dtype=torch.int32, device=dev)     # noqa: E731
+    res = PagedStreams(page_size=page_size, pages=torch.empty(max(entries * page_size, 1), dtype=torch.uint8, device=dev)[:entries * page_size],
+                       page_off=page_off, page_len=i32(entries), page_src=i32(entries), n_pages=i32(n), in_done=i32(n), status=i32(n))
+    if n:
+        if max_rounds is None:
+            max_rounds = paged_rounds_bound(longest, page_size, window_min, window_max)
+        scratch_cap = int(lib.lz4flex_compress_packed_scratch_bound(offered, n, 0)) if scratch_cap is None else int(scratch_cap)
+        scratch = torch.empty(max(scratch_cap, 1), dtype=torch.uint8, device=dev)
+        work = torch.empty(int(lib.lz4flex_compress_paged_work_size(n)), dtype=torch.uint8, device=dev)
+        keep = [i32(1) if t.numel() == 0 else t for t in (res.pages, res.page_len, res.page_src)]
+        _device_call("lz4flex_compress_paged", [src, d_off, d_len.to(torch.int32)], n,
+                     [page_size, int(window_min), int(window_max), int(max_rounds), keep[0], page_off, keep[1], keep[2], res.n_pages, res.in_done,
+                      res.status, scratch, scratch_cap, work], min(longest, window_max_r) > 65536, sp)
+    return res
+
+
+def decompress_paged_device(paged, stream=None):
+    """The streams of a PagedStreams (device form) back in device memory, with ONE lz4flex_decompress_batch over the page table (the
+    table is turned into the batch's arrays by torch, with one host synchronisation for the number of committed pages and the total).
+    Returns (out, out_off, out_len, status): stream i's bytes are out[out_off[i] : out_off[i] + out_len[i]], out_len = in_done; status
+    is per stream, 0 or the largest code one of its pages failed with (a page that decodes to another length than its slice counts as
+    E_OUTPUT_TOO_SMALL)."""
+    import torch
+    P = int(paged.page_size)
+    dev = paged.pages.device
+    n = int(paged.n_pages.numel())
+    done = paged.in_done.to(torch.int64) & 0xFFFFFFFF
+    out_off = torch.cumsum(done, 0) - done
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    entries = int(paged.page_len.numel())
+    if n == 0 or entries == 0:
+        return torch.empty(0, dtype=torch.uint8, device=dev), out_off, done, status
+    first = paged.page_off[:n].to(torch.int64)
+    e = torch.arange(entries, dtype=torch.int64, device=dev)
+    owner = torch.clamp(torch.searchsorted(paged.page_off.to(torch.int64).contiguous(), e, right=True) - 1, 0, n - 1)
+    k = e - first[owner]
+    pages_of = (paged.n_pages.to(torch.int64) & 0xFFFFFFFF)[owner]
+    live = torch.nonzero(k < pages_of).flatten()                    # (a synchronisation: the committed pages)
+    start = (paged.page_src.to(torch.int64) & 0xFFFFFFFF)
+    nxt = torch.cat([start[1:], start[:1]])
+    end = torch.where(k + 1 < pages_of, nxt, done[owner])
+    b_off = (live * P).contiguous()
+    b_len = paged.page_len[live].contiguous()
+    b_out = (out_off[owner] + start)[live].contiguous()
+    b_cap = (end - start)[live].to(torch.int32).contiguous()
+    total = int(done.sum())
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    m = int(live.numel())
+    if m:
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        b_got, b_st = torch.zeros(m, dtype=torch.int32, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+        _device_call("lz4flex_decompress_batch", [paged.pages, b_off, b_len], m, [out, b_out, b_cap, b_got, b_st, None], P > 131072, C.c_void_p(stream))
+        b_st = torch.where((b_st == 0) & (b_got != b_cap), torch.full_like(b_st, L.E_OUTPUT_TOO_SMALL), b_st)
+        status.scatter_reduce_(0, owner[live], b_st, "amax", include_self=True)
+    return out[:total], out_off, done, status
+
+
 class CompressedTensor:
     """What compress_tensor returns and decompress_tensor takes: the compressed blocks back to back in `data` (a uint8 device tensor),
     block i at data[offsets[i] : offsets[i] + lengths[i]] (device tensors), and what the tensor was: shape, dtype, the block_bytes it was

@@ -1715,6 +1715,152 @@ int lz4flex_compress_batch_fit(lz4flex_ctx* ctx, const void* in_base, const uint
     return fit_on_host(ctx, a, true, k.big);
 }
 
+// ---- paged streams: every stream cut into pages of page_size bytes, the loop on the device (lz4_paged.hip) ------------------------------
+}  // extern "C"
+
+namespace {
+
+// Lfit(r, infinity) of the fit rule: the largest L with tail(L) <= r (r >= 1)
+uint32_t lfit_unbounded(uint32_t r) {
+    if (r <= 16u) return std::min(r - 1u, 14u);
+    const uint32_t y = r - 17u;
+    return 15u + y - (y >> 8) - ((y & 255u) == 255u ? 1u : 0u);
+}
+
+// the page size and the windows of a paged call, defaults resolved; false: not a legal combination
+bool paged_params(uint32_t page_size, uint32_t& window_min, uint32_t& window_max) {
+    if (page_size < 64u || page_size > (4u << 20)) return false;
+    if (window_min == 0u) window_min = 4u * page_size;
+    if (window_max == 0u) window_max = std::max(window_min, 65536u);
+    return page_size <= window_min && window_min <= window_max && window_max <= 0x80000000u;
+}
+
+uint32_t paged_doublings(uint32_t window_min, uint32_t window_max) {
+    uint32_t d = 0;
+    for (uint64_t w = window_min; w < window_max; w *= 2u) d++;
+    return d;
+}
+
+// the rounds of a paged call on device memory: the step (lz4_paged.hip), then max_rounds times the fit entry over the windows the
+// step laid out and the step behind it.  a's arrays, in_base and out_base are device memory; nothing is allocated or synchronised.
+int paged_on_device(lz4flex_ctx* c, const PagedArgs& a, const uint8_t* in_base, uint8_t* out_base, uint32_t max_rounds, uint8_t* scratch,
+                    uint64_t scratch_cap, void* work, bool big, hipStream_t s) {
+    const PagedWork w = paged_work(work, a.n);
+    const FitArgs round{nullptr, nullptr, nullptr, in_base, w.w_off, w.w_len, a.n, out_base, w.o_off, w.o_cap, w.r_len, w.r_used, w.r_st};
+    hipError_t e = launch_paged_step(a, w, PAGED_FIRST | (max_rounds == 0u ? PAGED_LAST : 0), s);
+    if (e != hipSuccess) return hip_fail(e, "paged step launch");
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        if (const int rc = compress_fit_on_device(c, round, scratch, scratch_cap, w.packed, big, s)) return rc;
+        e = launch_paged_step(a, w, r + 1u == max_rounds ? PAGED_LAST : PAGED_NEXT, s);
+        if (e != hipSuccess) return hip_fail(e, "paged step launch");
+    }
+    return 0;
+}
+
+struct PagedCall {
+    const uint8_t* in_base; const uint64_t* in_off; const uint32_t* in_len; uint32_t n;
+    uint32_t page_size, window_min, window_max, max_rounds;
+    uint8_t* out_base; const uint64_t* page_off; uint32_t* page_len; uint32_t* page_src; uint32_t* n_pages; uint32_t* in_done; int32_t* status;
+};
+
+// MEM_HOST: the streams' span and the descriptors go up, the rounds the lengths can need run as on device memory, the tables, the
+// results and the page file come down with one synchronisation; committed pages (their page_len bytes) and their table entries are
+// copied to their places, the rest of the caller's page file and tables stays as it is.
+int paged_on_host(lz4flex_ctx* c, const PagedCall& p, bool big) {
+    const uint32_t n = p.n;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    const Span in_span = span_of(p.in_off, p.in_len, n);
+    const uint64_t first = p.page_off[0], entries = p.page_off[n] - first;
+    const size_t out_bytes = (size_t)(entries * p.page_size);
+    uint64_t slots = 0;
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t w = std::min(p.in_len[i], p.window_max);
+        slots += lz4flex_get_maximum_output_size(w);
+        big = big || w > 65536u;
+        longest = std::max(longest, p.in_len[i]);
+    }
+    const uint32_t rounds = std::min(p.max_rounds, lz4flex_paged_rounds_bound(longest, p.page_size, p.window_min, p.window_max));
+    HostStage st;
+    const auto in_off = st.up<uint64_t>(n), page_off = st.up<uint64_t>((size_t)n + 1u);
+    const auto in_len = st.up<uint32_t>(n);
+    const auto page_len = st.down<uint32_t>((size_t)entries), page_src = st.down<uint32_t>((size_t)entries);
+    const auto n_pages = st.down<uint32_t>(n), in_done = st.down<uint32_t>(n);
+    const auto status = st.down<int32_t>(n);
+    const Region r_in = st.region(in_span.bytes(), 64), r_out = st.region(out_bytes, 64);
+    st.columns();
+    const Region r_work = st.region(paged_work_bytes(n), 0);
+    int rc;
+    if ((rc = stage_open(c, st))) return rc;
+    if ((rc = ensure_buf(c->pay, out_bytes + 16))) return rc;
+    void* d_scratch = nullptr;
+    if ((rc = ctx_scratch(c, 0, (size_t)slots + 256, &d_scratch))) return rc;
+    st.fill_offsets(in_off, p.in_off, in_span.lo); st.fill_offsets(page_off, p.page_off, first);
+    st.fill(in_len, p.in_len);
+    hipStream_t s = st.s;
+    HIP_TRY(st.send(r_in, p.in_base + in_span.lo));
+    HIP_TRY(st.send_columns());
+    const PagedArgs dv{st.dev(in_off), st.dev(in_len), n, p.page_size, p.window_min, p.window_max, st.dev(page_off), st.dev_opt(page_len),
+                       st.dev_opt(page_src), st.dev(n_pages), st.dev(in_done), st.dev(status)};
+    if ((rc = paged_on_device(c, dv, st.dev(r_in), st.dev(r_out), rounds, (uint8_t*)d_scratch, slots, st.dev(r_work), big, s))) return rc;
+    HIP_TRY(st.fetch_columns(page_len));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, st.dev(r_out), out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    st.read(n_pages, p.n_pages); st.read(in_done, p.in_done); st.read(status, p.status);
+    const uint32_t* h_len = st.host(page_len);
+    const uint32_t* h_src = st.host(page_src);
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t k = 0; k < p.n_pages[i]; k++) {
+            const uint64_t e = p.page_off[i] + k, r = e - first;
+            p.page_len[e] = h_len[r]; p.page_src[e] = h_src[r];
+            memcpy(p.out_base + e * p.page_size, c->pay.p + r * p.page_size, h_len[r]);
+        }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t lz4flex_paged_pages_bound(uint32_t in_len, uint32_t page_size) {
+    if (page_size < 64u || page_size > (4u << 20)) return 0;
+    const uint64_t L = lfit_unbounded(page_size);
+    return ((uint64_t)in_len + L - 1u) / L;
+}
+
+uint32_t lz4flex_paged_rounds_bound(uint32_t max_in_len, uint32_t page_size, uint32_t window_min, uint32_t window_max) {
+    if (!paged_params(page_size, window_min, window_max)) return 0;
+    return (uint32_t)(lz4flex_paged_pages_bound(max_in_len, page_size) + paged_doublings(window_min, window_max));
+}
+
+size_t lz4flex_compress_paged_work_size(uint32_t n) { return paged_work_bytes(n); }
+
+int lz4flex_compress_paged(lz4flex_ctx* ctx, const void* in_base, const uint64_t* in_off, const uint32_t* in_len, uint32_t n, uint32_t page_size,
+                           uint32_t window_min, uint32_t window_max, uint32_t max_rounds, void* out_base, const uint64_t* page_off,
+                           uint32_t* page_len, uint32_t* page_src, uint32_t* n_pages, uint32_t* in_done, int32_t* status, void* scratch,
+                           uint64_t scratch_cap, void* work, int mem_kind, void* hip_stream) {
+    if (!paged_params(page_size, window_min, window_max)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!in_off || !in_len || !page_off || !page_len || !page_src || !n_pages || !in_done || !status) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && (!work || !scratch)) return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Host)                                   // (the entries are visible: they count up)
+        for (uint32_t i = 0; i < n; i++)
+            if (page_off[i + 1] < page_off[i]) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;                  // (compress_batch_entry has the "debug_fail_next_batch" hook)
+    if (k.where == Mem::Device) {
+        const PagedArgs a{in_off, in_len, n, page_size, window_min, window_max, page_off, page_len, page_src, n_pages, in_done, status};
+        return paged_on_device(ctx, a, (const uint8_t*)in_base, (uint8_t*)out_base, max_rounds, (uint8_t*)scratch, scratch_cap, work, k.big,
+                               (hipStream_t)hip_stream);
+    }
+    const PagedCall p{(const uint8_t*)in_base, in_off, in_len, n, page_size, window_min, window_max, max_rounds, (uint8_t*)out_base, page_off,
+                      page_len, page_src, n_pages, in_done, status};
+    return paged_on_host(ctx, p, k.big);
+}
+
 // ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------
 static const uint64_t OFF0 = 0;
 static const uint8_t EMPTY = 0;

@@ -326,6 +326,28 @@ struct FitArgs {
     uint32_t* out_len; uint32_t* in_used; int32_t* status;
 };
 hipError_t launch_fit(const FitArgs& a, int gated, int serial_only, hipStream_t s);
+// lz4_paged.hip (lz4flex_compress_paged): the step in front of, between and behind the rounds of a paged call, a lane per stream -- it
+// commits the round behind it by the paged rule (include/lz4flex_amd.h) and lays out the next round's windows in the workspace; the
+// round itself is the fit entry over w.w_off / w.w_len -> w.o_off / w.o_cap with its results in w.r_len / w.r_used / w.r_st.
+enum : int { PAGED_NEXT = 0, PAGED_FIRST = 1, PAGED_LAST = 2 };     // bits.  FIRST: nothing to commit; LAST: nothing to lay out, what is live ends
+struct PagedArgs {
+    const uint64_t* in_off; const uint32_t* in_len; uint32_t n;
+    uint32_t page_size, window_min, window_max;
+    const uint64_t* page_off;                                       // n + 1, in entries
+    uint32_t* page_len; uint32_t* page_src;                         // per entry
+    uint32_t* n_pages; uint32_t* in_done; int32_t* status;          // per stream; n_pages and in_done are the loop's k and pos
+};
+// the arrays a paged call keeps in the caller's `work` (paged_work_bytes(n) bytes, any 8-byte aligned address)
+struct PagedWork {
+    void* packed;                                                   // the fit entry's own work area (packed_work_bytes(n))
+    uint64_t* w_off; uint64_t* o_off;                               // n each: the round's windows and pages
+    uint32_t* w_len; uint32_t* o_cap;
+    uint32_t* r_len; uint32_t* r_used; int32_t* r_st;               // n each: the round's results
+    uint32_t* win; uint32_t* live;                                  // n each: the window length W, 1 while the stream has rounds to come
+};
+size_t paged_work_bytes(uint32_t n);
+PagedWork paged_work(void* work, uint32_t n);
+hipError_t launch_paged_step(const PagedArgs& a, const PagedWork& w, int phase, hipStream_t s);
 // lz4_packed.hip (lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed): the output layout of a batch, computed on the device.
 constexpr uint32_t PACKED_SCAN_TILE = 1024u;         // the sizes one workgroup scans ("packed_scan_tile")
 enum : int {
