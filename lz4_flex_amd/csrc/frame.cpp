@@ -3,7 +3,7 @@
 // block framing, store-raw rule, checksums and the io::Write / io::Read behaviour live here;
 // every block's bytes are produced by the batched HIP kernels through the C ABI.  Where the
 // reference calls the block codec once per block (src/frame/compress.rs:282-298,
-// src/frame/decompress.rs:288-305) this layer gathers up to `batch_blocks` blocks per launch.
+// src/frame/decompress.rs:288-305) this layer gathers up to `batch_blocks` blocks per launch (the integer rules: frame_plan.h).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -20,7 +20,7 @@ namespace {
 
 using lz4flex::PinBuf;
 using lz4flex::XxHash32;
-using namespace lz4flex_plan;   // block sizes, BLOCK_UNCOMPRESSED_SIZE_BIT, WINDOW_SIZE, TableOffset, LinkedWindow
+using namespace lz4flex_plan;   // block sizes, BLOCK_UNCOMPRESSED_SIZE_BIT, WINDOW_SIZE, TableOffset, LinkedWindow, DecodeRing, DecodeRuns
 
 // src/frame/header.rs:11-34
 constexpr uint8_t FLG_RESERVED_MASK = 0x02, FLG_VERSION_MASK = 0xC0, FLG_SUPPORTED_VERSION_BITS = 0x40,
@@ -34,6 +34,47 @@ uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) 
 uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); }
 void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 void wr64(uint8_t* p, uint64_t v) { wr32(p, (uint32_t)v); wr32(p + 4, (uint32_t)(v >> 32)); }
+
+// FrameEncoder: the stream bytes [base, base + len) that wait for a launch or are the history of the blocks to come; page-locked (host_pin.h)
+struct Stage {
+    PinBuf buf;
+    size_t len = 0;
+    uint64_t base = 0;             // stream position of buf[0]
+    const uint8_t* at(uint64_t pos) const { return buf.data() + (size_t)(pos - base); }
+    // grows with the data, by doubling, to at most `limit` bytes
+    void append(const uint8_t* p, size_t n, size_t limit) {
+        if (buf.size() < len + n) buf.resize(std::min(limit, std::max(buf.size() * 2, len + n)));
+        memcpy(buf.data() + len, p, n);
+        len += n;
+    }
+    // forgets what lies in front of stream position `pos`
+    void drop_before(uint64_t pos) {
+        if (pos <= base) return;
+        const size_t drop = (size_t)(pos - base);
+        memmove(buf.data(), buf.data() + drop, len - drop);
+        len -= drop; base = pos;
+    }
+};
+
+// FrameEncoder: the block columns of one launch and the compressed slots they name, at a fixed stride
+struct EncodeBatch {
+    PinBuf dst;
+    std::vector<uint64_t> in_off, out_off;
+    std::vector<uint32_t> in_len, out_cap, out_len, flags;
+    std::vector<int32_t> status;
+    std::vector<lz4flex_chain_block> chain;
+    // `total` bytes at offset `first` of the launch's source, as blocks of `mbs` (the last may be partial): returns their number
+    size_t prepare(size_t total, size_t mbs, size_t first) {
+        const size_t nblk = (total + mbs - 1) / mbs, stride = slot_stride(mbs);
+        if (dst.size() < stride * nblk) dst.resize(stride * nblk);
+        in_off.resize(nblk); in_len.resize(nblk); flags.resize(nblk); out_off.resize(nblk); out_cap.resize(nblk); out_len.resize(nblk); status.resize(nblk);
+        for (size_t i = 0; i < nblk; i++) {
+            in_off[i] = first + i * mbs; in_len[i] = (uint32_t)std::min(mbs, total - i * mbs);
+            out_off[i] = i * stride; out_cap[i] = (uint32_t)stride;
+        }
+        return nblk;
+    }
+};
 
 }  // namespace
 
@@ -105,25 +146,12 @@ int64_t lz4flex_frame_info_read(const uint8_t* in, size_t in_len, lz4flex_frame_
 
 // ------------------------------------------------------------------------------------------
 // FrameEncoder
-// Blocks gathered per kernel launch.  A block is one serial chain on the device (a 4 MiB block takes 64x as long as
-// a 64 KiB one), so throughput needs MANY blocks in flight: by default at least 256 blocks per launch (one per
-// CU), capped at 1 GiB of staged input; an explicit set_batch_bytes is honoured exactly.
-static size_t blocks_per_launch(size_t batch_bytes, size_t mbs, bool automatic) {
-    size_t nb = std::max<size_t>(1, batch_bytes / mbs);
-    if (automatic) nb = std::max<size_t>(nb, std::min<size_t>(256, ((size_t)1 << 30) / mbs));
-    return nb;
-}
-
 struct lz4flex_frame_encoder {
     lz4flex_frame_info fi{};
     lz4flex_write_fn w = nullptr;
     void* user = nullptr;
-    PinBuf src;                    // staged uncompressed bytes (whole blocks + a partial tail); page-locked: host_pin.h
-    size_t src_len = 0;
-    PinBuf dst;                    // compressed blocks at a fixed stride
-    std::vector<uint64_t> in_off, out_off;
-    std::vector<uint32_t> in_len, out_cap, out_len, flags;
-    std::vector<int32_t> status;
+    Stage stage;                   // Independent: the bytes not yet compressed; Linked: the history the blocks to come can reach in front of them
+    EncodeBatch b;
     size_t batch_blocks = 0;       // blocks per kernel launch
     size_t batch_bytes = 64u << 20;
     bool batch_auto = true;        // no explicit set_batch_bytes: big blocks get enough blocks per launch to fill the GPU
@@ -133,16 +161,12 @@ struct lz4flex_frame_encoder {
     bool is_frame_open = false, data_to_frame_written = false;
     bool final_write = false;       // lz4flex_frame_compress: the write in progress is the stream's last (finish follows)
     int sticky_err = 0;
-    // Linked mode (frame/compress.rs:62-93): the reference's src ring (prefix + ext_dict) expressed in
-    // stream coordinates (`win`); the dependent blocks of a batch run as ONE chain on the GPU.
-    PinBuf lstage;                      // stream bytes [lbase, lbase + lstage_len)
-    size_t lstage_len = 0;
-    uint64_t lbase = 0;                 // stream position of lstage[0]
     uint64_t proc_pos = 0;              // stream position of the first byte not yet compressed
     uint64_t frame_start = 0;           // stream position of the current frame's first byte (history never reaches before it)
+    // Linked mode (frame/compress.rs:62-93): the reference's src ring (prefix + ext_dict) expressed in
+    // stream coordinates (`win`); the dependent blocks of a batch run as ONE chain on the GPU.
     LinkedWindow win;
     std::vector<uint32_t> tbl_state;    // the persistent HashTable4K
-    std::vector<lz4flex_chain_block> cblocks;
     bool linked_fast = false;           // Linked frame written with the throughput encoder: blocks parsed independently
 
     int emit(const uint8_t* p, size_t n) {
@@ -166,8 +190,8 @@ struct lz4flex_frame_encoder {
         int rc = emit(hdr, (size_t)n);
         if (rc) return rc;
         if (content_len != 0) {   // second or later frame of this encoder: reset compressor state
-            content_len = 0; tbl.so = 0; src_len = 0;
-            content_hasher.reset(0);
+            content_len = 0; tbl.so = 0;       // (nothing is staged between frames: try_finish flushed; a Linked frame's history
+            content_hasher.reset(0);           // stays where it is, out of the new frame's reach: win, frame_start)
             win.reset(proc_pos);
             std::fill(tbl_state.begin(), tbl_state.end(), 0u);
         }
@@ -194,182 +218,112 @@ struct lz4flex_frame_encoder {
         content_len += slen;
         return 0;
     }
+    // the blocks of a launch that went through, on the wire; `src`: what the batch's in_off count from
+    int emit_batch(const uint8_t* src, size_t nblk) {
+        for (size_t i = 0; i < nblk; i++) {
+            if (b.status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
+            const int rc = emit_block(src + b.in_off[i], b.in_len[i], b.dst.data() + b.out_off[i], b.out_len[i]);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+
+    // write_block (frame/compress.rs:261-371) for the `total` bytes at proc_pos in one launch, as blocks of <= block_size in order; the last
+    // may be partial.  Three forms: each fills what its entry point reads, calls it, and says what stays staged as history.
+    // Independent frame.  The blocks are the staged bytes, or (round 6) `direct`, bytes in the CALLER's buffer: a write of a whole batch, and the
+    // one-shot call's remainder, are compressed where they lie -- staging them cost a host copy of every byte (12 instead of 24 GiB/s
+    // through host buffers).  Nothing is history.
+    int write_blocks(size_t total, const uint8_t* direct = nullptr) {
+        const uint8_t* const src = direct ? direct : stage.at(proc_pos);
+        const size_t mbs = block_size_bytes(fi.block_size), nblk = b.prepare(total, mbs, 0);
+        TableOffset t = tbl;             // (committed below, once the launch and every write went through)
+        for (size_t i = 0; i < nblk; i++) b.flags[i] = t.next(mbs, b.in_len[i]);
+        int rc = lz4flex_compress_batch(nullptr, src, b.in_off.data(), b.in_len.data(), b.flags.data(), (uint32_t)nblk,
+                                        b.dst.data(), b.out_off.data(), b.out_cap.data(), b.out_len.data(), b.status.data(),
+                                        LZ4FLEX_MEM_HOST, nullptr);
+        if (rc || (rc = emit_batch(src, nblk))) return rc;
+        tbl = t;
+        proc_pos += total;
+        if (direct) stage.base = proc_pos; else stage.drop_before(proc_pos);      // (direct: the stage is empty and stays so)
+        return 0;
+    }
     // Linked frame, throughput encoder (compress_mode fast): a block's matches reach into the 32 KiB of the stream in front of it
     // (LZ4FLEX_BLOCK_HISTORY: the history is INPUT, so the blocks of a launch are still one batch and not one dependency chain
     // -- 64 blocks of 64 KiB: one launch of a fraction of a millisecond instead of 64 x 8 ms of chain).  Any LZ4 frame decoder
     // returns the input; JSON, 64 KiB blocks: ratio 0.2216 (the reference's Linked frame 0.2226, independent blocks 0.2307).
     // compress_mode exact keeps the reference's bytes (write_blocks_linked below).
     int write_blocks_linked_fast(size_t total) {
-        const size_t mbs = block_size_bytes(fi.block_size);
-        const size_t nblk = (total + mbs - 1) / mbs;
-        if (nblk == 0) return 0;
-        const size_t stride = (lz4flex_get_maximum_output_size(mbs) + 63) / 64 * 64;
-        if (dst.size() < stride * nblk) dst.resize(stride * nblk);
-        in_off.resize(nblk); out_off.resize(nblk); in_len.resize(nblk); out_cap.resize(nblk); out_len.resize(nblk); status.resize(nblk);
-        flags.resize(nblk);
-        const size_t base = (size_t)(proc_pos - lbase);
-        size_t left = total;
+        const size_t mbs = block_size_bytes(fi.block_size), nblk = b.prepare(total, mbs, (size_t)(proc_pos - stage.base));
         for (size_t i = 0; i < nblk; i++) {
-            const size_t len = std::min(mbs, left);
-            in_off[i] = base + i * mbs; in_len[i] = (uint32_t)len;
-            out_off[i] = i * stride; out_cap[i] = (uint32_t)stride;
             // what the stage holds in front of the block, as far as it belongs to THIS frame
-            const uint64_t have = std::min<uint64_t>(in_off[i], proc_pos + i * mbs - frame_start);
-            flags[i] = LZ4FLEX_BLOCK_HISTORY(std::min<uint64_t>(have, FAST_HISTORY));
-            left -= len;
+            const uint64_t have = std::min<uint64_t>(b.in_off[i], proc_pos + i * mbs - frame_start);
+            b.flags[i] = LZ4FLEX_BLOCK_HISTORY(std::min<uint64_t>(have, FAST_HISTORY));
         }
         // (a Linked frame's blocks: what compress_mode high does with them is encode_route's rule, lz4_route.h)
-        int rc = lz4flex_dev::compress_batch_entry(nullptr, lstage.data(), in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk, dst.data(),
-                                                   out_off.data(), out_cap.data(), out_len.data(), status.data(), LZ4FLEX_MEM_HOST, nullptr, true);
-        if (rc) return rc;
-        for (size_t i = 0; i < nblk; i++) {
-            if (status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
-            if ((rc = emit_block(lstage.data() + in_off[i], in_len[i], dst.data() + out_off[i], out_len[i]))) return rc;
-        }
+        int rc = lz4flex_dev::compress_batch_entry(nullptr, stage.buf.data(), b.in_off.data(), b.in_len.data(), b.flags.data(), (uint32_t)nblk,
+                                                   b.dst.data(), b.out_off.data(), b.out_cap.data(), b.out_len.data(), b.status.data(),
+                                                   LZ4FLEX_MEM_HOST, nullptr, true);
+        if (rc || (rc = emit_batch(stage.buf.data(), nblk))) return rc;
         proc_pos += total;
-        const uint64_t keep_from = std::max<uint64_t>(lbase, proc_pos >= FAST_HISTORY ? proc_pos - FAST_HISTORY : 0);   // the next block's history stays
-        const size_t drop = (size_t)(keep_from - lbase);
-        memmove(lstage.data(), lstage.data() + drop, lstage_len - drop);
-        lstage_len -= drop; lbase = keep_from;
+        stage.drop_before(proc_pos >= FAST_HISTORY ? proc_pos - FAST_HISTORY : 0);   // the next block's history stays
         return 0;
     }
-    // Linked mode: compress the stream bytes [proc_pos, proc_pos + total) as blocks of <= block_size, in order,
-    // with the reference's window bookkeeping (frame/compress.rs:261-371) done in stream coordinates.
+    // Linked frame, the reference's bytes: the blocks are ONE chain on the device, with the reference's window bookkeeping
+    // (frame/compress.rs:261-371) done in stream coordinates (`win` moves on before the launch)
     int write_blocks_linked(size_t total) {
-        if (linked_fast) return write_blocks_linked_fast(total);
-        const size_t mbs = block_size_bytes(fi.block_size);
-        const size_t nblk = (total + mbs - 1) / mbs;
-        if (nblk == 0) return 0;
-        const size_t stride = (lz4flex_get_maximum_output_size(mbs) + 63) / 64 * 64;
-        if (dst.size() < stride * nblk) dst.resize(stride * nblk);
-        cblocks.resize(nblk); out_off.resize(nblk); out_cap.resize(nblk); out_len.resize(nblk); status.resize(nblk);
-        std::vector<uint64_t> bstart(nblk);
-        std::vector<uint32_t> blen(nblk);
-        size_t left = total;
-        uint64_t pos = proc_pos;
+        const size_t mbs = block_size_bytes(fi.block_size), nblk = b.prepare(total, mbs, (size_t)(proc_pos - stage.base));
+        b.chain.resize(nblk);
         for (size_t i = 0; i < nblk; i++) {
-            const size_t len = std::min(mbs, left);
-            lz4flex_chain_block& b = cblocks[i];
-            b = win.next(mbs, len);                          // (stream positions; the stage starts at lbase)
-            b.in_off -= lbase;
-            if (b.dict_len) b.dict_off -= lbase;
-            out_off[i] = i * stride; out_cap[i] = (uint32_t)stride;
-            bstart[i] = pos; blen[i] = (uint32_t)len;
-            pos += len; left -= len;
+            lz4flex_chain_block& c = b.chain[i];
+            c = win.next(mbs, b.in_len[i]);                  // (stream positions; the stage starts at stage.base)
+            c.in_off -= stage.base;
+            if (c.dict_len) c.dict_off -= stage.base;
         }
         const uint32_t first = 0, count = (uint32_t)nblk;
-        int rc = lz4flex_compress_chains(nullptr, lstage.data(), cblocks.data(), (uint32_t)nblk, &first, &count, 1, dst.data(),
-                                         out_off.data(), out_cap.data(), out_len.data(), status.data(), tbl_state.data(),
+        int rc = lz4flex_compress_chains(nullptr, stage.buf.data(), b.chain.data(), (uint32_t)nblk, &first, &count, 1, b.dst.data(),
+                                         b.out_off.data(), b.out_cap.data(), b.out_len.data(), b.status.data(), tbl_state.data(),
                                          LZ4FLEX_MEM_HOST, nullptr);
-        if (rc) return rc;
-        for (size_t i = 0; i < nblk; i++) {
-            if (status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
-            if ((rc = emit_block(lstage.data() + (bstart[i] - lbase), blen[i], dst.data() + out_off[i], out_len[i]))) return rc;
-        }
+        if (rc || (rc = emit_batch(stage.buf.data(), nblk))) return rc;
         proc_pos += total;
-        // drop history the window can no longer reach
-        const uint64_t keep_from = win.keep_from();
-        if (keep_from > lbase) {
-            const size_t drop = (size_t)(keep_from - lbase);
-            memmove(lstage.data(), lstage.data() + drop, lstage_len - drop);
-            lstage_len -= drop; lbase = keep_from;
-        }
+        stage.drop_before(win.keep_from());                  // drop history the window can no longer reach
         return 0;
     }
-    int64_t write_linked(const uint8_t* buf, size_t len) {
-        const size_t mbs = block_size_bytes(fi.block_size);
-        // (exact mode: the blocks of a launch are ONE dependency chain on the device -- 64 of them keep a launch in the tens of
-        // milliseconds; throughput encoder: independent blocks, a full batch per launch)
-        const size_t per_launch = (linked_fast ? batch_blocks : std::min<size_t>(batch_blocks, 64)) * mbs;
-        const size_t total = len;
-        while (len) {
-            const size_t pending = (size_t)(lbase + lstage_len - proc_pos);
-            if (pending == per_launch) { int rc = write_blocks_linked(pending); if (rc) return sticky_err = rc; continue; }
-            const size_t n = std::min(per_launch - pending, len);
-            if (lstage.size() < lstage_len + n) lstage.resize(std::max(lstage.size() * 2, lstage_len + n));
-            memcpy(lstage.data() + lstage_len, buf, n);
-            lstage_len += n; buf += n; len -= n;
-        }
-        return (int64_t)total;
-    }
-
-    // write_block (frame/compress.rs:261-371) for `nblk` blocks in one launch; the last may be partial.  The blocks are the staged bytes, or
-    // (round 6) `avail` bytes at `direct` in the CALLER's buffer: a write of a whole batch, and the one-shot call's remainder, are compressed
-    // where they lie -- staging them cost a host copy of every byte (12 instead of 24 GiB/s through host buffers)
-    int write_blocks(size_t nblk, const uint8_t* direct = nullptr, size_t avail = 0) {
-        if (nblk == 0) return 0;
-        const uint8_t* const base = direct ? direct : src.data();
-        const size_t have = direct ? avail : src_len;
-        const size_t mbs = block_size_bytes(fi.block_size);
-        const size_t stride = (lz4flex_get_maximum_output_size(mbs) + 63) / 64 * 64;
-        if (dst.size() < stride * nblk) dst.resize(stride * nblk);
-        in_off.resize(nblk); out_off.resize(nblk); in_len.resize(nblk); out_cap.resize(nblk);
-        out_len.resize(nblk); flags.resize(nblk); status.resize(nblk);
-        TableOffset t = tbl;             // (committed below, once the launch and every write went through)
-        size_t consumed = 0;
-        for (size_t i = 0; i < nblk; i++) {
-            const size_t len = std::min(mbs, have - i * mbs);
-            in_off[i] = i * mbs; in_len[i] = (uint32_t)len;
-            out_off[i] = i * stride; out_cap[i] = (uint32_t)stride;
-            flags[i] = t.next(mbs, len);
-            consumed += len;
-        }
-        int rc = lz4flex_compress_batch(nullptr, base, in_off.data(), in_len.data(), flags.data(), (uint32_t)nblk,
-                                        dst.data(), out_off.data(), out_cap.data(), out_len.data(), status.data(),
-                                        LZ4FLEX_MEM_HOST, nullptr);
-        if (rc) return rc;
-        for (size_t i = 0; i < nblk; i++) {
-            if (status[i] != 0) return -LZ4FLEX_FE_COMPRESSION;
-            if ((rc = emit_block(base + in_off[i], in_len[i], dst.data() + out_off[i], out_len[i]))) return rc;
-        }
-        tbl = t;
-        if (direct) return 0;
-        // keep an unconsumed tail (never happens: callers pass every staged byte or whole blocks)
-        if (consumed < src_len) memmove(src.data(), src.data() + consumed, src_len - consumed);
-        src_len -= consumed;
-        return 0;
+    size_t pending() const { return (size_t)(stage.base + stage.len - proc_pos); }   // staged and not yet compressed
+    int write_pending() {
+        const size_t n = pending();
+        if (n == 0) return 0;
+        return fi.block_mode != 1 ? write_blocks(n) : linked_fast ? write_blocks_linked_fast(n) : write_blocks_linked(n);
     }
     // io::Write::write, frame/compress.rs:375-396
     int64_t write(const uint8_t* buf, size_t len) {
         if (sticky_err) return sticky_err;
         int rc;
         if (!is_frame_open && len != 0) { if ((rc = begin_frame(len))) return sticky_err = rc; }
-        if (fi.block_mode == 1) return write_linked(buf, len);
-        const size_t total = len;
-        const size_t mbs = block_size_bytes(fi.block_size);
+        const bool linked = fi.block_mode == 1;
+        const size_t total = len, mbs = block_size_bytes(fi.block_size);
+        // (exact-mode Linked: the blocks of a launch are ONE dependency chain on the device -- 64 of them keep a launch in the tens of
+        // milliseconds; everything else: independent blocks, a full batch per launch)
+        const size_t cap = (linked && !linked_fast ? std::min<size_t>(batch_blocks, 64) : batch_blocks) * mbs;
         while (len) {
-            const size_t cap = batch_blocks * mbs;
-            if (src_len == cap) {   // staging full: make space by writing the staged blocks
-                if ((rc = write_blocks(batch_blocks))) return sticky_err = rc;
+            if (pending() == cap) { if ((rc = write_pending())) return sticky_err = rc; continue; }   // staging full: the staged blocks make space
+            // No staging: a whole batch lies in the caller's buffer; or this is the one-shot call's remainder -- whatever is left is the
+            // frame's end, a partial last block included
+            if (!linked && pending() == 0 && (len >= cap || final_write)) {
+                const size_t n = std::min(cap, len);
+                if ((rc = write_blocks(n, buf))) return sticky_err = rc;
+                buf += n; len -= n;
                 continue;
             }
-            if (src_len == 0 && len >= cap) {   // a whole batch lies in the caller's buffer: no staging
-                if ((rc = write_blocks(batch_blocks, buf, cap))) return sticky_err = rc;
-                buf += cap; len -= cap;
-                continue;
-            }
-            if (final_write && src_len == 0) {  // the one-shot call's remainder: whatever is left is the frame's end, a partial last block included
-                if ((rc = write_blocks((len + mbs - 1) / mbs, buf, len))) return sticky_err = rc;
-                return (int64_t)total;
-            }
-            const size_t n = std::min(cap - src_len, len);
-            if (src.size() < src_len + n) src.resize(std::min(cap, std::max(src.size() * 2, src_len + n)));   // grows with the data
-            memcpy(src.data() + src_len, buf, n);
-            src_len += n; buf += n; len -= n;
+            const size_t n = std::min(cap - pending(), len);
+            stage.append(buf, n, linked ? (size_t)-1 : cap);   // (Independent: never more than a batch)
+            buf += n; len -= n;
         }
         return (int64_t)total;
     }
     // io::Write::flush, frame/compress.rs:398-403
     int flush() {
         if (sticky_err) return sticky_err;
-        if (fi.block_mode == 1 && is_frame_open) {
-            const size_t pending = (size_t)(lbase + lstage_len - proc_pos);
-            const int rc = pending ? write_blocks_linked(pending) : 0;
-            return rc ? (sticky_err = rc) : 0;
-        }
-        if (src_len == 0) return 0;
-        const size_t mbs = block_size_bytes(fi.block_size);
-        const int rc = write_blocks((src_len + mbs - 1) / mbs);
+        const int rc = write_pending();
         return rc ? (sticky_err = rc) : 0;
     }
     // try_finish, frame/compress.rs:173-187 (+ end_frame :209-230)
@@ -404,36 +358,31 @@ struct lz4flex_frame_decoder {
     uint64_t content_len = 0;
     size_t batch_bytes = 64u << 20;
     bool batch_auto = true;
-    // staged batch
-    PinBuf comp, out;          // page-locked staging (host_pin.h)
+    PinBuf comp, out;          // the staged batch; page-locked (host_pin.h)
     std::vector<uint64_t> in_off, out_off, detail;
     std::vector<uint32_t> in_len, out_cap, out_len;
     std::vector<int32_t> status;
+    // a gathered block: stored or compressed, its payload comp[at, at + len), `end` = in_total behind it, col: its place in the launch's
+    // columns (compressed blocks), out_at: where its sink starts in the launch's output
+    struct Slot { bool raw; size_t at, len, end, col, out_at; };
+    std::vector<Slot> slots;
+    size_t out_need = 0;       // bytes of output the gathered blocks were given
+    bool saw_end = false;      // the gathering stopped at the EndMark
     struct Item { size_t off, len, src_end; };   // decoded bytes waiting to be read: offsets into `out` (Independent) or `ldst` (Linked)
     std::vector<Item> ready;   // decoded pieces in stream order (len 0 = a block that decoded to nothing; src_end: the input read up to its end)
     size_t ready_idx = 0, ready_pos = 0;
+    bool ready_linked = false; // the ready items index `ldst` (a Linked frame's blocks stay where they were decoded)
     int pending_err = 0;       // surfaces after the pieces before it were delivered
     lz4flex_err_detail pending_detail{};
     bool pending_zero = false; // EndMark reached: one read() returns 0
-    PinBuf ldst;
-    size_t dst_start = 0;
-    size_t lhave = 0;              // Linked: valid bytes in ldst (history + what the last call produced)
-    // Linked mode: the reference's dst ring (frame/decompress.rs:62-72,145-156,195-222), mirrored for the two things it decides -- the sink
-    // of a compressed block (a block size behind ring_start; once the ring has wrapped, everything up to the external dictionary's start,
-    // as much as TWO block sizes) and the positions an OutputTooSmall names.  The bytes themselves live in ldst.
-    size_t ext_dict_offset = 0, ext_dict_len = 0, ring_start = 0;
-    void ring_enter(size_t mbs) {                             // :195-222
-        if (ring_start + mbs > 2 * mbs + WINDOW_SIZE) { ext_dict_offset = ring_start - WINDOW_SIZE; ext_dict_len = WINDOW_SIZE; ring_start = 0; }
-        else if (ring_start + ext_dict_len > WINDOW_SIZE) {
-            const size_t delta = std::min(ext_dict_len, ring_start + ext_dict_len - WINDOW_SIZE);
-            ext_dict_offset += delta; ext_dict_len -= delta;
-        }
-    }
-    size_t ring_sink_end(size_t mbs) const { return ext_dict_len ? ext_dict_offset : ring_start + mbs; }   // :280-306
+    PinBuf ldst;               // Linked: [the frame's last <= 64 KiB | what the last call produced], grown on demand, never shrunk
+    size_t lhave = 0;          // Linked: valid bytes in ldst
+    DecodeRing ring;           // Linked: the reference's dst ring, for the sink of a block and an OutputTooSmall's positions; the bytes live in ldst
     size_t in_total = 0;           // bytes taken from the reader
     size_t zero_end = (size_t)-1;  // in_total behind the empty block that made the last read return 0 (lz4flex_frame_decompress: *consumed)
-
     bool io_failed = false;    // the read callback itself reported an error (not a short read)
+    static constexpr size_t DIRECT_MIN = 1u << 20;    // a reader with less room than this gets its bytes from the staging buffer (small reads: one launch per read would cost more than the copy)
+
     // read_exact; returns 0 ok, 1 clean EOF before any byte, -code on short read / error
     int read_exact(uint8_t* p, size_t n, size_t* got_out = nullptr) {
         size_t got = 0;
@@ -474,16 +423,19 @@ struct lz4flex_frame_decoder {
         have_frame = true;
         content_hasher.reset(0);
         content_len = 0;
-        ext_dict_len = 0; ext_dict_offset = 0; dst_start = 0; ring_start = 0;
-        lhave = 0;                                            // Linked: ldst = [history | this launch's blocks], grown on demand, never shrunk
+        ring.reset(); lhave = 0;
         return 0;
     }
-    bool ready_linked = false;     // the ready items index `ldst` (a Linked frame's blocks stay where they were decoded)
     const uint8_t* ready_base() const { return (ready_linked ? ldst : out).data(); }
     void fail(int code, const lz4flex_err_detail* d = nullptr) {
         pending_err = code;
         if (d) pending_detail = *d; else memset(&pending_detail, 0, sizeof pending_detail);
     }
+    // what the kernels said about the launch's block `i`, as a DecompressionError's detail
+    lz4flex_err_detail block_detail(size_t i) const {
+        lz4flex_err_detail d{}; d.expected = detail[2 * i]; d.actual = detail[2 * i + 1]; d.inner = status[i]; return d;
+    }
+    void fail_block(const lz4flex_err_detail& d) { fail(-LZ4FLEX_FE_DECOMPRESSION, &d); pending_zero = false; }
     // EndMark handling, frame/decompress.rs:313-332
     void end_mark() {
         if (fi.has_content_size && content_len != fi.content_size) {
@@ -498,6 +450,11 @@ struct lz4flex_frame_decoder {
         }
         have_frame = false;
         pending_zero = true;
+    }
+    // what every decode ends with: an error surfaces after the pieces in front of it (and without a zero); else the EndMark, if that is where the gathering stopped
+    void close_batch() {
+        if (pending_err) pending_zero = false;
+        else if (saw_end && !pending_zero) end_mark();
     }
 
     // One block off the stream into `comp` (frame/decompress.rs:231-278): BlockInfo word, EndMark, BlockTooBig, payload, optional
@@ -526,84 +483,92 @@ struct lz4flex_frame_decoder {
         }
         return {(size & BLOCK_UNCOMPRESSED_SIZE_BIT) ? RAW : COMP, at, len, in_total};
     }
-
-    // Independent frames: gather blocks up to the batch size, decode them in one launch.
-    // Round 6, `direct`: the reader asked for at least a block's worth of bytes (lz4flex_frame_decompress: for all of them) -- the blocks
-    // are decoded STRAIGHT INTO ITS BUFFER, slot i at i * block size, and the number of bytes delivered is returned (0: nothing went that
-    // way, the ready list says what there is).  Staging them and copying them out was a host copy of every decoded byte: 12 instead of
-    // ~ 20 GiB/s through host buffers.  A slot that is not full (a flush() boundary, the frame's last block) is closed up by moving what
-    // follows it; a block that decodes to nothing -- after which read() returns 0 once, frame/decompress.rs:344-349 -- and everything
-    // behind it goes to the staging buffer as before.
-    size_t read_blocks_independent(uint8_t* direct = nullptr, size_t direct_len = 0) {
-        const size_t mbs = block_size_bytes(fi.block_size);
-        size_t max_blocks = blocks_per_launch(batch_bytes, mbs, batch_auto);
-        if (direct) max_blocks = std::min(max_blocks, direct_len / mbs);
-        comp.clear(); in_off.clear(); in_len.clear(); out_off.clear(); out_cap.clear();
+    // Blocks off the stream for one call: at most `max_blocks`, and no more than the launch's output budget.  Compressed blocks enter the
+    // launch's columns.  full_slots: every block gets a block size of output (a reader's buffer, slot i at i * block size; a Linked
+    // run), else what it can decode to (decode_slot_cap; a stored block its length).  raw_ends: a stored block is the last one taken.
+    void gather(size_t mbs, size_t max_blocks, bool full_slots, bool raw_ends) {
+        comp.clear(); in_off.clear(); in_len.clear(); out_off.clear(); out_cap.clear(); slots.clear();
         ready.clear(); ready_idx = 0; ready_pos = 0;
-        ready_linked = false;
-        struct Slot { bool raw; size_t out_at; size_t idx; size_t raw_len; size_t end; };
-        std::vector<Slot> slots;
-        size_t out_need = 0;
-        bool saw_end = false;
-        const size_t out_budget = std::max<size_t>(batch_bytes, mbs) * (batch_auto ? 4u : 1u);   // bytes of output reserved per launch
+        out_need = 0;
+        saw_end = false;
+        const size_t out_budget = launch_out_budget(batch_bytes, mbs, batch_auto);
         while (slots.size() < max_blocks && (slots.empty() || out_need + mbs <= out_budget)) {
-            const BlockRead b = read_block(mbs);
-            saw_end = b.kind == END;
-            if (b.kind < RAW) break;
-            const bool raw = b.kind == RAW;
-            const size_t at = b.at, len = b.len;
-            Slot s{raw, out_need, in_off.size(), len, b.end};
-            // An LZ4 block expands by less than 255x (one length byte adds at most 255 output bytes), so min(block size,
-            // 255 len + 64) is as good a sink as the reference's block-size buffer and a frame of tiny blocks cannot make the
-            // read-ahead reserve (and the device arena mirror) gigabytes.
-            const size_t cap_i = direct ? mbs : std::min<size_t>(mbs, 255u * len + 64u);
-            if (!raw) { in_off.push_back(at); in_len.push_back((uint32_t)len); out_off.push_back(out_need); out_cap.push_back((uint32_t)cap_i); out_need += cap_i; }
-            else { s.idx = at; out_need += direct ? mbs : len; }
-            slots.push_back(s);
+            const BlockRead blk = read_block(mbs);
+            saw_end = blk.kind == END;
+            if (blk.kind < RAW) break;
+            const bool raw = blk.kind == RAW;
+            const size_t room = full_slots ? mbs : raw ? blk.len : decode_slot_cap(mbs, blk.len);
+            slots.push_back({raw, blk.at, blk.len, blk.end, in_off.size(), out_need});
+            if (!raw) { in_off.push_back(blk.at); in_len.push_back((uint32_t)blk.len); out_off.push_back(out_need); out_cap.push_back((uint32_t)room); }
+            out_need += room;
+            if (raw && raw_ends) break;
         }
-        if (!direct && out.size() < out_need) out.resize(out_need);
-        uint8_t* const sink = direct ? direct : out.data();
         const size_t nb = in_off.size();
         out_len.assign(nb, 0); status.assign(nb, 0); detail.assign(2 * nb, 0);
-        if (nb) {
-            const int rc = lz4flex_decompress_batch(nullptr, comp.data(), in_off.data(), in_len.data(), (uint32_t)nb, sink,
-                                                    out_off.data(), out_cap.data(), out_len.data(), status.data(),
-                                                    detail.data(), LZ4FLEX_MEM_HOST, nullptr);
-            if (rc) { fail(rc); pending_zero = false; return 0; }
-        }
-        size_t delivered = 0;          // direct: bytes closed up at the front of the reader's buffer
-        bool staged = !direct;         // direct: a block decoded to nothing -- from there on the pieces wait in `out`
-        size_t staged_at = 0;
-        for (const Slot& s : slots) {
-            size_t plen;
-            if (s.raw) { memcpy(sink + s.out_at, comp.data() + s.idx, s.raw_len); plen = s.raw_len; }
-            else {
-                if (status[s.idx] != 0) {
-                    lz4flex_err_detail d{}; d.expected = detail[2 * s.idx]; d.actual = detail[2 * s.idx + 1]; d.inner = status[s.idx];
-                    fail(-LZ4FLEX_FE_DECOMPRESSION, &d);
-                    pending_zero = false;
-                    return delivered;   // pieces before this one were delivered / queued; the error surfaces after them
+    }
+
+    // Independent frames: the gathered compressed blocks decoded into `sink` by one launch; false: fail() was called
+    bool launch_independent(uint8_t* sink) {
+        if (in_off.empty()) return true;
+        const int rc = lz4flex_decompress_batch(nullptr, comp.data(), in_off.data(), in_len.data(), (uint32_t)in_off.size(), sink,
+                                                out_off.data(), out_cap.data(), out_len.data(), status.data(),
+                                                detail.data(), LZ4FLEX_MEM_HOST, nullptr);
+        if (rc) { fail(rc); pending_zero = false; }
+        return rc == 0;
+    }
+    // ... and a block's bytes at sink + out_at: a stored block placed, a compressed one checked; content length and hash move on.
+    // false: the block failed -- the pieces before it were delivered / queued, the error surfaces after them
+    bool take_slot(const Slot& s, uint8_t* sink, size_t* plen) {
+        if (s.raw) memcpy(sink + s.out_at, comp.data() + s.at, s.len);
+        else if (status[s.col] != 0) { fail_block(block_detail(s.col)); return false; }
+        *plen = s.raw ? s.len : out_len[s.col];
+        content_len += *plen;
+        if (fi.content_checksum) content_hasher.write(sink + s.out_at, *plen);
+        return true;
+    }
+    // Independent frames, staged: up to a batch of blocks decoded into `out` by one launch; every block is a piece of the ready list
+    void decode_independent() {
+        const size_t mbs = block_size_bytes(fi.block_size);
+        ready_linked = false;
+        gather(mbs, blocks_per_launch(batch_bytes, mbs, batch_auto), false, false);
+        if (out.size() < out_need) out.resize(out_need);
+        size_t plen;
+        if (launch_independent(out.data()))
+            for (const Slot& s : slots) {
+                if (!take_slot(s, out.data(), &plen)) break;
+                ready.push_back({s.out_at, plen, s.end});
+            }
+        close_batch();
+    }
+    // Independent frames, direct (round 6): the reader asked for at least a block's worth of bytes (lz4flex_frame_decompress: for all of
+    // them) -- the blocks are decoded STRAIGHT INTO ITS BUFFER, slot i at i * block size, and the number of bytes delivered is returned
+    // (0: nothing went that way, the ready list says what there is).  Staging them and copying them out was a host copy of every decoded
+    // byte: 12 instead of ~ 20 GiB/s through host buffers.  A slot that is not full (a flush() boundary, the frame's last block) is closed
+    // up by moving what follows it; a block that decodes to nothing -- after which read() returns 0 once, frame/decompress.rs:344-349 --
+    // and everything behind it goes to the staging buffer as pieces of the ready list.
+    size_t decode_independent_direct(uint8_t* buf, size_t len) {
+        const size_t mbs = block_size_bytes(fi.block_size);
+        ready_linked = false;
+        gather(mbs, std::min(blocks_per_launch(batch_bytes, mbs, batch_auto), len / mbs), true, false);
+        size_t delivered = 0, staged_at = 0, plen;
+        bool staged = false;           // a block decoded to nothing: from there on the pieces wait in `out`
+        if (launch_independent(buf))
+            for (const Slot& s : slots) {
+                if (!take_slot(s, buf, &plen)) break;
+                if (!staged && plen == 0) {
+                    staged = true;
+                    if (out.size() < out_need) out.resize(out_need);
                 }
-                plen = out_len[s.idx];
+                if (!staged) {
+                    if (s.out_at != delivered && plen) memmove(buf + delivered, buf + s.out_at, plen);
+                    delivered += plen;
+                } else {
+                    if (plen) memcpy(out.data() + staged_at, buf + s.out_at, plen);
+                    ready.push_back({staged_at, plen, s.end});
+                    staged_at += plen;
+                }
             }
-            content_len += plen;
-            if (fi.content_checksum) content_hasher.write(sink + s.out_at, plen);
-            if (direct && !staged && plen == 0) {
-                staged = true;
-                if (out.size() < out_need) out.resize(out_need);
-            }
-            if (!direct) ready.push_back({s.out_at, plen, s.end});
-            else if (!staged) {
-                if (s.out_at != delivered && plen) memmove(direct + delivered, direct + s.out_at, plen);
-                delivered += plen;
-            } else {
-                if (plen) memcpy(out.data() + staged_at, direct + s.out_at, plen);
-                ready.push_back({staged_at, plen, s.end});
-                staged_at += plen;
-            }
-        }
-        if (pending_err) { pending_zero = false; return delivered; }
-        if (saw_end && !pending_zero) end_mark();
+        close_batch();
         return delivered;
     }
 
@@ -613,167 +578,110 @@ struct lz4flex_frame_decoder {
     // given the position behind its predecessors as its initial sink position and the kernel makes it wait for them only where
     // a match really reaches behind its start -- the blocks of a frame written by this library's throughput encoder never do.
     // A block's decoded size is not in the frame: every block but a frame's last is taken to fill the block size, and the
-    // blocks behind one that did not (a flush() boundary, frame/compress.rs:398-403) are decoded again from their real position.
-    // A block stored raw ends a run (its bytes are placed by the host).
-    void read_block_linked() {
+    // blocks behind one that did not (a flush() boundary, frame/compress.rs:398-403) are decoded again from their real position
+    // (DecodeRuns).  A block stored raw ends a run (its bytes are placed by the host).
+    // What one call produces behind the `carry` bytes of history at the front of ldst: `produced` bytes, handed out where they are as
+    // one piece, cut where a block decoded to nothing -- there a read returns 0 once (read_more() == 0, frame/decompress.rs:344-349)
+    // with the bytes in front of it delivered and the ones behind it still to come.  piece_at: where the piece being made starts.
+    struct LinkedOut { size_t carry, produced, piece_at; };
+    void end_piece(LinkedOut& o, size_t src_end) {
+        if (o.produced != o.piece_at) ready.push_back({o.carry + o.piece_at, o.produced - o.piece_at, src_end});
+        o.piece_at = o.produced;
+    }
+    void empty_block(LinkedOut& o, size_t src_end) {
+        end_piece(o, src_end);
+        ready.push_back({o.carry + o.produced, 0, src_end});
+    }
+    void grow_ldst(size_t n) { if (ldst.size() < n) ldst.resize(n); }
+    // the run of `nb` compressed blocks: launches until every block sits behind its real predecessor; false: a launch or a block failed
+    // (fail() was called; what was decoded in front of it is still handed out)
+    bool decode_run(size_t mbs, size_t nb, LinkedOut& o) {
+        std::vector<uint32_t> pos(nb), cap(nb);
+        std::vector<uint64_t> zero_off(nb, 0);
+        DecodeRuns runs(nb);
+        for (size_t first = 0; first < nb;) {
+            const size_t m = runs.take(first), room = runs.first_room(first, mbs, ring);
+            grow_ldst(o.carry + o.produced + (m - 1) * mbs + room);
+            for (size_t k = 0; k < m; k++) {
+                pos[k] = (uint32_t)(o.carry + o.produced + k * mbs);
+                cap[k] = pos[k] + (uint32_t)(k == 0 ? room : mbs);
+            }
+            lz4flex_decompress_ext ext{}; ext.out_pos = pos.data();
+            const int rc = lz4flex_decompress_batch_ex(nullptr, comp.data(), in_off.data() + first, in_len.data() + first, (uint32_t)m,
+                                                       ldst.data(), zero_off.data(), cap.data(), out_len.data() + first, status.data() + first,
+                                                       detail.data() + 2 * first, &ext, LZ4FLEX_MEM_HOST | LZ4FLEX_MEM_CHAINED, nullptr);
+            if (rc) { fail(rc); pending_zero = false; return false; }
+            size_t k = 0;          // blocks of this launch that were accepted
+            bool retry = false, failed = false;
+            for (; k < m; k++) {
+                const size_t i = first + k;
+                if (!runs.is_roomy(i)) ring.enter(mbs);       // (once per block: the roomy block entered when it was first tried)
+                if (status[i] != 0) {
+                    retry = status[i] == LZ4FLEX_E_OUTPUT_TOO_SMALL && !runs.is_roomy(i) && ring.room(mbs) > mbs;
+                    if (!retry) {
+                        lz4flex_err_detail d = block_detail(i);
+                        if (status[i] == LZ4FLEX_E_OUTPUT_TOO_SMALL) ring.too_small(mbs, pos[k], &d.expected, &d.actual);
+                        fail_block(d);
+                        failed = true;
+                    }
+                    break;
+                }
+                o.produced += out_len[i];
+                ring.advance(out_len[i]);
+                if (out_len[i] == 0) empty_block(o, slots[i].end);
+                if (out_len[i] != mbs) { k++; break; }        // the blocks behind a short one were given a wrong position
+            }
+            if (failed) return false;
+            runs.ended(first, m, k, retry);
+            first += k;
+        }
+        return true;
+    }
+    // a block stored raw behind the run
+    void place_raw(size_t mbs, const Slot& s, LinkedOut& o) {
+        grow_ldst(o.carry + o.produced + s.len);
+        memcpy(ldst.data() + o.carry + o.produced, comp.data() + s.at, s.len);
+        o.produced += s.len;
+        ring.enter(mbs);
+        ring.advance(s.len);
+        if (s.len == 0) empty_block(o, s.end);
+    }
+    void decode_linked() {
         const size_t mbs = block_size_bytes(fi.block_size);
-        const size_t max_blocks = blocks_per_launch(batch_bytes, mbs, batch_auto);
-        ready.clear(); ready_idx = 0; ready_pos = 0;
-        comp.clear(); in_off.clear(); in_len.clear();
         ready_linked = true;
-        // ldst = carry (the frame's last <= 64 KiB) followed by this call's output.  The previous call's bytes were handed out
-        // straight from ldst (no copy), so they are moved to the front only now that they have been consumed.
+        // The previous call's bytes were handed out straight from ldst (no copy), so its last 64 KiB are moved to the front only now that
+        // they have been consumed.
         if (lhave > WINDOW_SIZE) {
             memmove(ldst.data(), ldst.data() + (lhave - WINDOW_SIZE), WINDOW_SIZE);
             lhave = WINDOW_SIZE;
         }
-        dst_start = lhave;
-        const size_t carry = dst_start;                      // bytes of history at the front of ldst
-        bool saw_end = false, raw_tail = false;
-        size_t raw_at = 0, raw_len = 0, raw_end = 0;
-        std::vector<size_t> ends;                            // in_total behind each compressed block
-        const size_t out_budget = std::max<size_t>(batch_bytes, mbs) * (batch_auto ? 4u : 1u);
-        // (sink positions are 32-bit: an explicit batch size of 4 GiB or more must not wrap them; halved, since a block may be
-        // given up to two block sizes of room, see below)
-        const size_t pos_blocks = ((size_t)((0xFFFFFFFFull - carry) / mbs) - 1u) / 2u;
-        while (in_off.size() < std::min(max_blocks, pos_blocks) && (in_off.empty() || (in_off.size() + 1) * mbs <= out_budget)) {
-            const BlockRead b = read_block(mbs);
-            saw_end = b.kind == END;
-            if (b.kind < RAW) break;
-            if (b.kind == RAW) { raw_tail = true; raw_at = b.at; raw_len = b.len; raw_end = b.end; break; }
-            in_off.push_back(b.at); in_len.push_back((uint32_t)b.len); ends.push_back(b.end);
-        }
+        LinkedOut o{lhave, 0, 0};
+        // 1. gather: a run of compressed blocks, and the stored block that ended it
+        gather(mbs, std::min(blocks_per_launch(batch_bytes, mbs, batch_auto), pos_blocks(o.carry, mbs)), true, true);
         const size_t nb = in_off.size();
-        if (ldst.size() < carry + (nb + 1) * mbs) ldst.resize(carry + (nb + 1) * mbs);
-        size_t produced_total = 0;                           // bytes of this call behind the carry
-        // ---- the run of compressed blocks: launches until every block sits behind its real predecessor
-        out_len.assign(nb, 0); status.assign(nb, 0); detail.assign(2 * nb, 0);
-        std::vector<uint32_t> pos(nb), cap(nb);
-        std::vector<uint64_t> zero_off(nb, 0);
-        size_t first = 0;
-        bool failed = false;
-        // the pieces handed out: one for all the bytes, cut where a block decoded to nothing -- there a read returns 0 once (read_more() == 0,
-        // frame/decompress.rs:344-349) with the bytes in front of it delivered and the ones behind it still to come
-        size_t piece_at = 0;
-        auto empty_block = [&](size_t src_end) {
-            if (produced_total != piece_at) ready.push_back({carry + piece_at, produced_total - piece_at, src_end});
-            ready.push_back({carry + produced_total, 0, src_end});
-            piece_at = produced_total;
-        };
-        // A launch assumes full blocks; the blocks behind a short one have to be decoded again from their real position.  A
-        // frame of many short blocks (a flush() after every small write) would cost a launch and a re-decode of everything
-        // behind it per block if every launch took the whole rest of the run: the run length is cut to a quarter whenever a
-        // short block invalidates the blocks behind it and doubles again while launches end clean -- launches and decoded
-        // blocks stay linear in the number of blocks.
-        // A launch also gives every block a sink of one block size.  The reference's is larger right behind a wrap of its ring
-        // (ring_sink_end): a block that ran out of room there is decoded once more, alone, with the room the reference gives it.
-        size_t run = nb, roomy = (size_t)-1;                  // roomy: the block that is being given the ring's sink
-        while (first < nb) {
-            const size_t m = first == roomy ? 1 : std::min(run, nb - first);
-            const size_t room = first == roomy ? ring_sink_end(mbs) - ring_start : mbs;
-            if (ldst.size() < carry + produced_total + (m - 1) * mbs + room) ldst.resize(carry + produced_total + (m - 1) * mbs + room);
-            for (size_t k = 0; k < m; k++) {
-                pos[k] = (uint32_t)(carry + produced_total + k * mbs);
-                cap[k] = pos[k] + (uint32_t)(k == 0 ? room : mbs);
-            }
-            lz4flex_decompress_ext ext{};
-            ext.out_pos = pos.data();
-            const int rc = lz4flex_decompress_batch_ex(nullptr, comp.data(), in_off.data() + first, in_len.data() + first, (uint32_t)m,
-                                                       ldst.data(), zero_off.data(), cap.data(), out_len.data() + first, status.data() + first,
-                                                       detail.data() + 2 * first, &ext, LZ4FLEX_MEM_HOST | LZ4FLEX_MEM_CHAINED, nullptr);
-            if (rc) { fail(rc); pending_zero = false; failed = true; break; }
-            size_t k = 0;
-            bool again = false;
-            for (; k < m; k++) {
-                const size_t i = first + k;
-                if (i != roomy) ring_enter(mbs);
-                if (status[i] != 0) {
-                    if (status[i] == LZ4FLEX_E_OUTPUT_TOO_SMALL && i != roomy && ring_sink_end(mbs) - ring_start > mbs) { roomy = i; again = true; break; }
-                    lz4flex_err_detail d{}; d.expected = detail[2 * i]; d.actual = detail[2 * i + 1]; d.inner = status[i];
-                    if (status[i] == LZ4FLEX_E_OUTPUT_TOO_SMALL) {     // (the positions the reference's sink has, frame/decompress.rs:288-305)
-                        d.expected = d.expected - pos[k] + ring_start;
-                        d.actual = ring_sink_end(mbs);
-                    }
-                    fail(-LZ4FLEX_FE_DECOMPRESSION, &d);
-                    pending_zero = false;
-                    failed = true;
-                    break;
-                }
-                produced_total += out_len[i];
-                ring_start += out_len[i];
-                if (out_len[i] == 0) empty_block(ends[i]);
-                if (out_len[i] != mbs) { k++; break; }        // the blocks behind a short one were given a wrong position
-            }
-            if (!again) run = k < m ? std::max<size_t>(1, m / 4) : std::min(nb, 2 * m);
-            first += k;
-            if (failed) break;
-        }
-        // ---- a block stored raw behind the run
-        if (!failed && !pending_err && raw_tail) {
-            if (ldst.size() < carry + produced_total + raw_len) ldst.resize(carry + produced_total + raw_len);
-            memcpy(ldst.data() + carry + produced_total, comp.data() + raw_at, raw_len);
-            produced_total += raw_len;
-            ring_enter(mbs);
-            ring_start += raw_len;
-            if (raw_len == 0) empty_block(raw_end);
-        }
-        // ---- hand the bytes out where they are (ready items index `ldst` in Linked mode); they stay there as history
-        if (produced_total != piece_at) ready.push_back({carry + piece_at, produced_total - piece_at, 0});
-        content_len += produced_total;
-        if (fi.content_checksum && produced_total) content_hasher.write(ldst.data() + carry, produced_total);
-        lhave = carry + produced_total;
-        if (pending_err) { pending_zero = false; return; }
-        if (saw_end && !pending_zero) end_mark();
+        grow_ldst(o.carry + (nb + 1) * mbs);
+        // 2. decode the run; 3. place a raw tail
+        if (decode_run(mbs, nb, o) && slots.size() > nb) place_raw(mbs, slots[nb], o);
+        // 4. hand the bytes out where they are (ready items index `ldst` in Linked mode); they stay there as history
+        end_piece(o, 0);
+        content_len += o.produced;
+        if (fi.content_checksum && o.produced) content_hasher.write(ldst.data() + o.carry, o.produced);
+        lhave = o.carry + o.produced;
+        close_batch();
     }
 
-    // io::Read::read, frame/decompress.rs:353-367
-    // io::BufRead::fill_buf, frame/decompress.rs:410-416: the decoded bytes not consumed yet (decodes more when there are
-    // none); *p stays valid until the next call on this decoder.  0 = end of frame / EOF, < 0 = -code.
-    int64_t fill_buf(const uint8_t** p, lz4flex_err_detail* d) {
+    // What read and fill_buf share (frame/decompress.rs:353-367, :410-416), in this order: the ready pieces, the pending error, the
+    // pending zero, the next frame's header, more blocks.  PIECE: ready[ready_idx] holds bytes for the caller to take; else the value to
+    // return -- 0 behind an empty block (read_more() == 0), at the end of a frame and at EOF, -code, or (`direct`, a reader's buffer
+    // of at least a block and DIRECT_MIN bytes, Independent frames) the number of bytes decoded straight into it.
+    static constexpr int64_t PIECE = INT64_MIN;
+    int64_t next_piece(lz4flex_err_detail* d, uint8_t* direct = nullptr, size_t direct_len = 0) {
         for (;;) {
-            while (ready_idx < ready.size()) {
+            if (ready_idx < ready.size()) {
                 const Item& it = ready[ready_idx];
-                if (it.len == 0 || ready_pos == it.len) {
-                    const bool empty_block = it.len == 0;
-                    ready_idx++; ready_pos = 0;
-                    if (empty_block) { zero_end = it.src_end; *p = out.data(); return 0; }      // read_more() == 0: an empty slice
-                    continue;
-                }
-                *p = ready_base() + it.off + ready_pos;
-                return (int64_t)(it.len - ready_pos);
-            }
-            if (pending_err) { if (d) *d = pending_detail; return pending_err; }
-            if (pending_zero) { pending_zero = false; *p = out.data(); return 0; }
-            if (!have_frame) {
-                lz4flex_err_detail hd{};
-                const int rc = read_frame_info(&hd);
-                if (rc == 1) { *p = out.data(); return 0; }
-                if (rc < 0) { if (d) *d = hd; return rc; }
-            }
-            if (fi.block_mode == 1) read_block_linked(); else read_blocks_independent();
-        }
-    }
-    // io::BufRead::consume, :418-421 (the reference asserts amt <= available)
-    int consume(size_t amt) {
-        if (amt == 0) return 0;
-        if (ready_idx >= ready.size()) return -LZ4FLEX_E_INVALID_ARG;
-        const Item& it = ready[ready_idx];
-        if (amt > it.len - ready_pos) return -LZ4FLEX_E_INVALID_ARG;
-        ready_pos += amt;
-        if (ready_pos == it.len) { ready_idx++; ready_pos = 0; }
-        return 0;
-    }
-    int64_t read(uint8_t* buf, size_t len, lz4flex_err_detail* d) {
-        for (;;) {
-            while (ready_idx < ready.size()) {
-                const Item& it = ready[ready_idx];
-                if (it.len == 0) { zero_end = it.src_end; ready_idx++; ready_pos = 0; return 0; }   // read_more() == 0
-                const size_t n = std::min(it.len - ready_pos, len);
-                if (n == 0) return 0;   // zero-length destination
-                memcpy(buf, ready_base() + it.off + ready_pos, n);
-                ready_pos += n;
-                if (ready_pos == it.len) { ready_idx++; ready_pos = 0; }
-                return (int64_t)n;
+                if (it.len != 0) return PIECE;
+                zero_end = it.src_end; ready_idx++; ready_pos = 0;
+                return 0;
             }
             if (pending_err) { if (d) *d = pending_detail; return pending_err; }
             if (pending_zero) { pending_zero = false; return 0; }
@@ -783,14 +691,45 @@ struct lz4flex_frame_decoder {
                 if (rc == 1) return 0;
                 if (rc < 0) { if (d) *d = hd; return rc; }
             }
-            if (fi.block_mode == 1) read_block_linked();
-            else if (len >= block_size_bytes(fi.block_size) && len >= DIRECT_MIN) {
-                const size_t n = read_blocks_independent(buf, len);
+            if (fi.block_mode == 1) decode_linked();
+            else if (direct && direct_len >= block_size_bytes(fi.block_size) && direct_len >= DIRECT_MIN) {
+                const size_t n = decode_independent_direct(direct, direct_len);
                 if (n) return (int64_t)n;
-            } else read_blocks_independent();
+            } else decode_independent();
         }
     }
-    static constexpr size_t DIRECT_MIN = 1u << 20;    // a reader with less room than this gets its bytes from the staging buffer (small reads: one launch per read would cost more than the copy)
+    void took(size_t n) {
+        ready_pos += n;
+        if (ready_pos == ready[ready_idx].len) { ready_idx++; ready_pos = 0; }
+    }
+    // io::BufRead::fill_buf, frame/decompress.rs:410-416: the decoded bytes not consumed yet (decodes more when there are
+    // none); *p stays valid until the next call on this decoder.  0 = end of frame / EOF (an empty slice), < 0 = -code.
+    int64_t fill_buf(const uint8_t** p, lz4flex_err_detail* d) {
+        const int64_t rc = next_piece(d);
+        if (rc == 0) *p = out.data();
+        if (rc != PIECE) return rc;
+        const Item& it = ready[ready_idx];
+        *p = ready_base() + it.off + ready_pos;
+        return (int64_t)(it.len - ready_pos);
+    }
+    // io::BufRead::consume, :418-421 (the reference asserts amt <= available)
+    int consume(size_t amt) {
+        if (amt == 0) return 0;
+        if (ready_idx >= ready.size() || amt > ready[ready_idx].len - ready_pos) return -LZ4FLEX_E_INVALID_ARG;
+        took(amt);
+        return 0;
+    }
+    // io::Read::read, frame/decompress.rs:353-367
+    int64_t read(uint8_t* buf, size_t len, lz4flex_err_detail* d) {
+        const int64_t rc = next_piece(d, buf, len);
+        if (rc != PIECE) return rc;
+        const Item& it = ready[ready_idx];
+        const size_t n = std::min(it.len - ready_pos, len);
+        if (n == 0) return 0;   // zero-length destination
+        memcpy(buf, ready_base() + it.off + ready_pos, n);
+        took(n);
+        return (int64_t)n;
+    }
 };
 
 extern "C" {

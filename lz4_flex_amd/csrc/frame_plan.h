@@ -1,7 +1,9 @@
 // frame_plan.h -- what a FrameEncoder decides about a block from the lengths of the blocks before it (reference
 // src/frame/header.rs, src/frame/compress.rs:261-371), stated once for frame.cpp (the streaming encoder), frame_many.cpp (N frames per
-// launch) and sharded.cpp (one frame across ranks).  Pure integer functions: host only, no HIP, no kernel includes it;
-// tests/test_frame_plan.py walks them on a CPU, past the table reposition near 2 GiB that no test reaches through the API.
+// launch) and sharded.cpp (one frame across ranks); and what frame.cpp's FrameDecoder decides about a Linked frame's block from the
+// decoded lengths of the blocks before it (src/frame/decompress.rs:195-222, :280-306): DecodeRing, DecodeRuns.  Pure integer functions: host
+// only, no HIP, no kernel includes it; tests/test_frame_plan.py walks them on a CPU, past the table reposition near 2 GiB that no test
+// reaches through the API and through ring wraps and relaunches that only a frame of the right shape reaches on the GPU.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -83,6 +85,68 @@ struct LinkedWindow {
             ext_dict_len -= (uint32_t)delta;
         }
         return b;
+    }
+};
+
+// ---- how a launch is sized (frame.cpp; the slot stride also sharded.cpp)
+// Blocks gathered per kernel launch.  A block is one serial chain on the device (a 4 MiB block takes 64x as long as a 64 KiB one), so
+// throughput needs MANY blocks in flight: by default at least 256 blocks per launch (one per CU), capped at 1 GiB of staged input; an
+// explicit set_batch_bytes is honoured exactly.
+inline size_t blocks_per_launch(size_t batch_bytes, size_t mbs, bool automatic) {
+    size_t nb = std::max<size_t>(1, batch_bytes / mbs);
+    if (automatic) nb = std::max<size_t>(nb, std::min<size_t>(256, ((size_t)1 << 30) / mbs));
+    return nb;
+}
+// encoder: the distance between the compressed slots of a launch
+inline size_t slot_stride(size_t mbs) { return (lz4flex_get_maximum_output_size(mbs) + 63) / 64 * 64; }
+// decoder: the sink of a compressed block of `len` bytes.  An LZ4 block expands by less than 255x (one length byte adds at most 255
+// output bytes), so this is as good a sink as the reference's block-size buffer and a frame of tiny blocks cannot make the read-ahead
+// reserve (and the device arena mirror) gigabytes.
+inline size_t decode_slot_cap(size_t mbs, size_t len) { return std::min<size_t>(mbs, 255u * len + 64u); }
+// decoder: bytes of output reserved per launch
+inline size_t launch_out_budget(size_t batch_bytes, size_t mbs, bool automatic) { return std::max(batch_bytes, mbs) * (automatic ? 4u : 1u); }
+// Linked decoder: blocks per launch behind `carry` bytes of history.  Sink positions are 32-bit: an explicit batch size of 4 GiB or
+// more must not wrap them; halved, since a block may be given up to two block sizes of room (DecodeRing::sink_end).
+inline size_t pos_blocks(size_t carry, size_t mbs) { return ((size_t)((0xFFFFFFFFull - carry) / mbs) - 1u) / 2u; }
+
+// Linked frame, decoding: the reference's dst ring of 2 block sizes + 64 KiB (frame/decompress.rs:62-72, :145-156) on lengths alone,
+// for the two things it decides: the sink of a compressed block -- a block size behind ring_start (the reference's dst_start); once
+// the ring has wrapped, everything up to the external dictionary's start, as much as TWO block sizes -- and the positions an
+// OutputTooSmall names.
+struct DecodeRing {
+    size_t ext_dict_offset = 0, ext_dict_len = 0, ring_start = 0;
+    void reset() { *this = DecodeRing(); }
+    // before every block (:195-222): wrap where a block no longer fits behind ring_start; else shrink the dictionary to the window
+    void enter(size_t mbs) {
+        if (ring_start + mbs > 2 * mbs + WINDOW_SIZE) { ext_dict_offset = ring_start - WINDOW_SIZE; ext_dict_len = WINDOW_SIZE; ring_start = 0; }
+        else if (ring_start + ext_dict_len > WINDOW_SIZE) {
+            const size_t delta = std::min<size_t>(ext_dict_len, ring_start + ext_dict_len - WINDOW_SIZE);
+            ext_dict_offset += delta; ext_dict_len -= delta;
+        }
+    }
+    size_t sink_end(size_t mbs) const { return ext_dict_len ? ext_dict_offset : ring_start + mbs; }   // :280-306
+    size_t room(size_t mbs) const { return sink_end(mbs) - ring_start; }
+    void advance(size_t n) { ring_start += n; }                                                       // :356-360, :418-421: the reader took the block
+    // a kernel's OutputTooSmall (expected, actual) of a block whose sink started at `pos`, as the reference's sink has them (:288-305)
+    void too_small(size_t mbs, uint64_t pos, uint64_t* expected, uint64_t* actual) const { *expected = *expected - pos + ring_start; *actual = sink_end(mbs); }
+};
+
+// Linked frame, decoding a run of `nb` compressed blocks: one launch gives every block a sink of one block size and takes every block
+// but a frame's last to fill it; the blocks behind one that did not (a flush() boundary) were given a wrong position and are decoded
+// again.  If every launch took the whole rest of the run, a frame of many short blocks would cost a launch and a re-decode of everything
+// behind it per block: the run length is cut to a quarter whenever a launch stops early and doubles while launches end clean, so launches
+// and decoded blocks stay linear in the number of blocks.  A block that ran out of room where the reference's sink is larger (right
+// behind a wrap of its ring) comes back once, alone, with that room: the roomy block.
+struct DecodeRuns {
+    size_t nb, run, roomy = (size_t)-1;
+    explicit DecodeRuns(size_t blocks) : nb(blocks), run(blocks) {}
+    bool is_roomy(size_t i) const { return i == roomy; }
+    size_t take(size_t first) const { return is_roomy(first) ? 1 : std::min(run, nb - first); }      // blocks of the launch that starts at `first`
+    size_t first_room(size_t first, size_t mbs, const DecodeRing& r) const { return is_roomy(first) ? r.room(mbs) : mbs; }
+    // the launch of `m` blocks at `first` accepted `k` of them; retry: block first + k comes back as the roomy one (`run` stays)
+    void ended(size_t first, size_t m, size_t k, bool retry) {
+        if (retry) roomy = first + k;
+        else run = k < m ? std::max<size_t>(1, m / 4) : std::min(nb, 2 * m);
     }
 };
 

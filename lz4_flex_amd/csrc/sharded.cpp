@@ -126,7 +126,7 @@ int lz4flex_frame_compress_sharded(lz4flex_ctx* ctx, void* nccl_comm, int rank, 
     if (coll && (!nccl_comm || !rccl().ok)) return -LZ4FLEX_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)hip_stream;
     const uint32_t n = (uint32_t)((local_len + bs - 1) / bs);
-    const uint64_t stride = (lz4flex_get_maximum_output_size(bs) + 63) / 64 * 64;
+    const uint64_t stride = slot_stride(bs);
     // ---- this rank's blocks -> its segment, on the device.  No rank may leave before a collective its peers will enter: whatever
     // fails in this phase (an allocation, a launch, a block) is SAID in the size all-gather below (seg_bytes = ~0) and every rank
     // returns there, this one with its own code.  The one thing that has to work first is the buffer the exchange itself uses.

@@ -274,8 +274,8 @@ static int enc_write(enc_t *e, const uint8_t *buf, size_t len) {
     return 0;
 }
 
-int64_t lz4o_frame_compress(const uint8_t *in, size_t in_len, const size_t *chunk_lens, size_t n_chunks,
-                            const lz4o_frame_info *fi, uint8_t *out, size_t out_cap, lz4o_err_detail *d) {
+static int64_t frame_compress(const uint8_t *in, size_t in_len, const size_t *chunk_lens, size_t n_chunks, int flush_each,
+                              const lz4o_frame_info *fi, uint8_t *out, size_t out_cap, lz4o_err_detail *d) {
     enc_t e; memset(&e, 0, sizeof e);
     e.fi = *fi; e.w = out; e.wcap = out_cap; e.content_base = in;
     e.table = lz4o__table_new();
@@ -288,6 +288,7 @@ int64_t lz4o_frame_compress(const uint8_t *in, size_t in_len, const size_t *chun
         if (n > in_len - pos) n = in_len - pos;
         rc = enc_write(&e, in + pos, n);
         pos += n;
+        if (!rc && flush_each && e.src_start != e.src_end) rc = enc_write_block(&e);   /* flush :398-403 */
     }
     /* finish(): try_finish :173-187 */
     if (!rc && e.src_start != e.src_end) rc = enc_write_block(&e);         /* flush :398-403 */
@@ -306,6 +307,16 @@ int64_t lz4o_frame_compress(const uint8_t *in, size_t in_len, const size_t *chun
     }
     lz4o__table_free(e.table); free(e.src); free(e.dst);
     return rc ? rc : (int64_t)e.wpos;
+}
+
+int64_t lz4o_frame_compress(const uint8_t *in, size_t in_len, const size_t *chunk_lens, size_t n_chunks,
+                            const lz4o_frame_info *fi, uint8_t *out, size_t out_cap, lz4o_err_detail *d) {
+    return frame_compress(in, in_len, chunk_lens, n_chunks, 0, fi, out, out_cap, d);
+}
+
+int64_t lz4o_frame_compress_flushed(const uint8_t *in, size_t in_len, const size_t *chunk_lens, size_t n_chunks,
+                                    const lz4o_frame_info *fi, uint8_t *out, size_t out_cap, lz4o_err_detail *d) {
+    return frame_compress(in, in_len, chunk_lens, n_chunks, 1, fi, out, out_cap, d);
 }
 
 /* ---------------------------------------------------------------------------------------- */

@@ -124,6 +124,10 @@ int64_t lz4o_frame_info_read(const uint8_t *in, size_t in_len, lz4o_frame_info *
  * write() calls (NULL => a single write of in_len bytes).  Returns bytes or -code. */
 int64_t lz4o_frame_compress(const uint8_t *in, size_t in_len, const size_t *chunk_lens, size_t n_chunks,
                             const lz4o_frame_info *fi, uint8_t *out, size_t out_cap, lz4o_err_detail *d);
+/* The same with a flush() behind every write (src/frame/compress.rs:398-403): a chunk that does not
+ * fill a block ends one, so the frame has short blocks in the middle. */
+int64_t lz4o_frame_compress_flushed(const uint8_t *in, size_t in_len, const size_t *chunk_lens, size_t n_chunks,
+                                    const lz4o_frame_info *fi, uint8_t *out, size_t out_cap, lz4o_err_detail *d);
 
 /* FrameDecoder::new(in).read_to_end() ONCE (src/frame/decompress.rs:352-408): decodes the
  * first frame, stops at its EndMark.  *consumed = input bytes read.  Returns bytes or -code. */

@@ -57,6 +57,8 @@ def lib():
         o.lz4o_frame_compress.restype = C.c_int64
         o.lz4o_frame_compress.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
                                           C.POINTER(FrameInfoO), C.c_char_p, C.c_size_t, C.POINTER(ErrDetail)]
+        o.lz4o_frame_compress_flushed.restype = C.c_int64
+        o.lz4o_frame_compress_flushed.argtypes = o.lz4o_frame_compress.argtypes
         o.lz4o_frame_decompress.restype = C.c_int64
         o.lz4o_frame_decompress.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t),
                                             C.POINTER(ErrDetail)]
@@ -149,17 +151,19 @@ def frame_info(content_size=None, block_size=0, block_mode=0, block_checksums=Fa
     return fi
 
 
-def frame_compress(data, chunks=None, **kw):
+def frame_compress(data, chunks=None, flush=False, **kw):
+    """flush: a flush() behind every write of `chunks` (a chunk that does not fill a block ends one)"""
     data = bytes(data)
     fi = frame_info(**kw)
-    cap = len(data) + len(data) // 100 + (len(data) // 65536 + 2) * 16 + 64
+    cap = len(data) + len(data) // 100 + (len(data) // 65536 + 2) * 16 + 64 + (16 * len(chunks) if flush else 0)
     out = C.create_string_buffer(cap)
     d = ErrDetail()
     if chunks is None:
         n = lib().lz4o_frame_compress(data, len(data), None, 0, C.byref(fi), out, cap, C.byref(d))
     else:
         arr = (C.c_size_t * len(chunks))(*chunks)
-        n = lib().lz4o_frame_compress(data, len(data), arr, len(chunks), C.byref(fi), out, cap, C.byref(d))
+        fn = lib().lz4o_frame_compress_flushed if flush else lib().lz4o_frame_compress
+        n = fn(data, len(data), arr, len(chunks), C.byref(fi), out, cap, C.byref(d))
     if n < 0:
         return -n, (int(d.expected), int(d.actual))
     return 0, out.raw[:n]

@@ -52,6 +52,15 @@ def shim():
         m.fp_table_modes.argtypes = [C.c_uint64, C.c_uint64, u64p, C.c_uint64, u32p]
         m.fp_linked_walk.restype = None
         m.fp_linked_walk.argtypes = [C.c_uint64, C.c_uint64, u64p, C.c_uint64, u64p, u64p]
+        for name, n_args in (("fp_blocks_per_launch", 3), ("fp_decode_slot_cap", 2), ("fp_launch_out_budget", 3), ("fp_pos_blocks", 2)):
+            getattr(m, name).restype = C.c_uint64
+            getattr(m, name).argtypes = [C.c_uint64, C.c_uint64] + [C.c_int] * (n_args - 2)
+        m.fp_decode_ring_walk.restype = None
+        m.fp_decode_ring_walk.argtypes = [C.c_uint64, u64p, C.c_uint64, u64p]
+        m.fp_decode_ring_too_small.restype = None
+        m.fp_decode_ring_too_small.argtypes = [C.c_uint64] * 7 + [u64p]
+        m.fp_decode_runs.restype = C.c_uint64
+        m.fp_decode_runs.argtypes = [C.c_uint64, C.POINTER(C.c_uint8), C.c_uint64, u64p, C.c_uint64]
         _m = m
     return _m
 
@@ -216,3 +225,120 @@ def test_stream_max_never_repositions(bs):
     got, _ = linked_walk(bs, lens)
     assert not got[:, 6].any()                         # repos
     assert int(got[:, 5].max()) < 1 << 31              # so
+
+
+# ---- the decoder's rules -----------------------------------------------------------------------------------------------------------
+class OracleRing:
+    """the oracle's decoder ring (oracle/lz4flex_frame.c, lz4o_frame_decompress; the reference's src/frame/decompress.rs:195-222, :280-306)
+    on lengths alone: a buffer of two block sizes and a window, the reader takes every block before the next one is decoded"""
+
+    def __init__(self, bs):
+        self.bs, self.size = bs, 2 * bs + WINDOW
+        self.dict_at = self.dict_n = self.at = 0
+
+    def block(self, produced):
+        """-> (sink end, dict_at, dict_n, at) as the block finds them"""
+        if self.at + self.bs > self.size:                                      # :202-210
+            self.dict_at, self.dict_n, self.at = self.at - WINDOW, WINDOW, 0
+        elif self.at + self.dict_n > WINDOW:                                   # :211-221
+            delta = min(self.dict_n, self.at + self.dict_n - WINDOW)
+            self.dict_at += delta
+            self.dict_n -= delta
+        sink_end = self.dict_at if self.dict_n else self.at + self.bs          # :280-306: dst[..ext_dict_offset] / dst[..dst_start + bs]
+        rec = (sink_end, self.dict_at, self.dict_n, self.at)
+        self.at += produced
+        return rec
+
+
+def ring_walk(bs, lens):
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    out = np.zeros((len(lens), 5), dtype=np.uint64)
+    p = C.POINTER(C.c_uint64)
+    shim().fp_decode_ring_walk(bs, lens.ctypes.data_as(p), len(lens), out.ctypes.data_as(p))
+    return out
+
+
+@pytest.mark.parametrize("bs", sorted(SIZES.values()))
+def test_decode_ring_random_blocks(bs):
+    rng = random.Random(2600 + bs)
+    for _ in range(20):
+        lens = [bs if rng.random() < 0.6 else rng.choice([0, 0, 1, 100, WINDOW - 1, WINDOW, WINDOW + 1, bs // 2, bs - 1, rng.randrange(bs + 1)])
+                for _ in range(400)]
+        lens = [min(n, bs) for n in lens]
+        ring = OracleRing(bs)
+        got = ring_walk(bs, lens)
+        wraps = 0
+        for i, n in enumerate(lens):
+            want = ring.block(n)
+            assert tuple(int(v) for v in got[i][:4]) == want, (i, n)
+            assert int(got[i][4]) == want[0] - want[3]
+            assert bs <= want[0] - want[3] <= 2 * bs          # a block always fits; the ring never gives more than two
+            wraps += i > 0 and want[3] == 0
+        assert wraps >= 5
+        assert max(int(r[4]) for r in got) > bs               # ... and right behind a wrap it does give more than one
+
+
+def test_decode_ring_too_small():
+    """(expected, actual) of a block whose sink started at `pos` of the launch's buffer become positions of the reference's sink:
+    the distance from the block's start carried over to ring_start, and where the ring's sink ends"""
+    m, out = shim(), (C.c_uint64 * 2)()
+    bs = 65536
+    m.fp_decode_ring_too_small(bs, 0, 0, 1000, 70000, 70000 + bs + 1, 70000 + bs, out)           # no dictionary: a block size behind ring_start
+    assert list(out) == [1000 + bs + 1, 1000 + bs]
+    m.fp_decode_ring_too_small(bs, 2 * bs, WINDOW, 0, 65536 + 3 * bs, 65536 + 5 * bs + 7, 65536 + 5 * bs, out)   # wrapped: up to the dictionary
+    assert list(out) == [2 * bs + 7, 2 * bs]
+    m.fp_decode_ring_too_small(bs, bs + 500, WINDOW - 500, 500, 0, bs + 9, bs, out)
+    assert list(out) == [500 + bs + 9, bs + 500]
+
+
+def decode_runs(kinds, bs=65536):
+    kind = (C.c_uint8 * len(kinds))(*kinds)
+    out = np.zeros((4 * len(kinds) + 4, 3), dtype=np.uint64)
+    n = shim().fp_decode_runs(bs, kind, len(kinds), out.ctypes.data_as(C.POINTER(C.c_uint64)), len(out))
+    assert n < len(out)
+    return [tuple(int(v) for v in row) for row in out[:n]]
+
+
+def test_decode_runs_tables():
+    """launches (first block, blocks, room of the first block) of a run of 16 blocks, written out by hand from the rule: start with run =
+    16; a launch takes min(run, what is left), the roomy block comes back alone; behind a launch that stopped early run = max(1, m / 4),
+    behind a clean one min(16, 2 m); the launch that sends a block back for the ring's room leaves run alone, and the one block that
+    comes back counts as a clean launch of one"""
+    B = 65536
+    assert decode_runs([0] * 16) == [(0, 16, B)]
+    # every block short: 16 -> 4 -> 1, then a clean launch of one (2) and a launch of two that stops behind its first block (1) in turn
+    assert decode_runs([1] * 16) == [(0, 16, B), (1, 4, B), (2, 1, B), (3, 2, B), (4, 1, B), (5, 2, B), (6, 1, B), (7, 2, B), (8, 1, B),
+                                     (9, 2, B), (10, 1, B), (11, 2, B), (12, 1, B), (13, 2, B), (14, 1, B), (15, 1, B)]
+    # block 5 short only: the launch accepts 0 .. 5 and stops early (4); clean launches double: 4, then 8 cut to the 6 that are left
+    assert decode_runs([0] * 5 + [1] + [0] * 10) == [(0, 16, B), (6, 4, B), (10, 6, B)]
+    # block 3 asks for the ring's room in a clean run: 0 .. 2 accepted, 3 alone with twice the room, then 2, 4, 8 cut to 6
+    assert decode_runs([0] * 3 + [2] + [0] * 12) == [(0, 16, B), (3, 1, 2 * B), (4, 2, B), (6, 4, B), (10, 6, B)]
+    # ... and with a short block 0 in front of it: (0, 16) stops behind block 0 (4); block 3 is the last of the next launch
+    assert decode_runs([1, 0, 0, 2] + [0] * 12) == [(0, 16, B), (1, 4, B), (3, 1, 2 * B), (4, 2, B), (6, 4, B), (10, 6, B)]
+    # launches and decoded blocks stay linear in the number of blocks, whatever the blocks
+    rng = random.Random(26)
+    for _ in range(50):
+        kinds = [rng.choice([0, 0, 0, 1, 2]) for _ in range(rng.randrange(1, 300))]
+        runs = decode_runs(kinds)
+        assert sum(m for _, m, _ in runs) <= 4 * len(kinds) + 16
+        assert runs[-1][0] + runs[-1][1] == len(kinds)
+
+
+def test_launch_sizes():
+    m = shim()
+    # blocks per launch: an explicit batch size exactly (at least one block); automatic: at least 256 blocks, within 1 GiB
+    assert [m.fp_blocks_per_launch(64 << 20, bs, 0) for bs in sorted(SIZES.values())] == [1024, 256, 64, 16]
+    assert [m.fp_blocks_per_launch(64 << 20, bs, 1) for bs in sorted(SIZES.values())] == [1024, 256, 256, 256]
+    assert m.fp_blocks_per_launch(1000, 65536, 0) == 1 and m.fp_blocks_per_launch(3 * 65536 + 5, 65536, 0) == 3
+    assert m.fp_blocks_per_launch(1 << 40, 4 << 20, 1) == 1 << 18
+    # the sink of a compressed block: what `len` bytes can decode to, at most a block
+    assert [m.fp_decode_slot_cap(65536, n) for n in (0, 1, 256, 257, 65536)] == [64, 319, 65344, 65536, 65536]
+    assert m.fp_decode_slot_cap(4 << 20, 16448) == 4194304 and m.fp_decode_slot_cap(4 << 20, 16447) == 255 * 16447 + 64
+    # output reserved per launch: the batch size (at least a block), four times that when the batch size is automatic
+    assert m.fp_launch_out_budget(64 << 20, 65536, 1) == 256 << 20 and m.fp_launch_out_budget(64 << 20, 65536, 0) == 64 << 20
+    assert m.fp_launch_out_budget(1000, 65536, 0) == 65536
+    # 32-bit sink positions: behind `carry` bytes, 2 n + 1 block sizes must stay below 2^32
+    for carry, bs in ((0, 65536), (65536, 65536), (65536, 4 << 20), (12345, 1 << 20)):
+        n = m.fp_pos_blocks(carry, bs)
+        assert carry + (2 * n + 1) * bs <= 0xFFFFFFFF < carry + (2 * (n + 1) + 2) * bs
+    assert m.fp_pos_blocks(65536, 65536) == 32766

@@ -8,7 +8,11 @@ copies with direction and bytes.
                                     two 64 KiB blocks and a 1 000-byte tail: text, random bytes, text.  Run it under
                                         rocprofv3 --kernel-trace --memory-copy-trace --output-format json -d DIR -o trace -- python ... run
                                     (no counters in that run); LZ4FLEX_LIB picks the build.
-  frame_calls_trace.py list DIR     the trace as one line per kernel ("K name") and per copy ("C direction bytes"), by start time.
+  frame_calls_trace.py run-stream   a second scenario, traced the same way: the streaming FrameEncoder and FrameDecoder and the two one-shot
+                                    calls, once each, on a Linked frame of eight writes with a flush behind each (65536 x 3, 1000,
+                                    65536, 30000, 65536 x 2 bytes) and on an Independent frame of five blocks and a 1 000-byte tail:
+                                    encoded in compress_mode fast and exact, each frame read back with read(65536) and read(1 MiB).
+  frame_calls_trace.py list DIR    the trace as one line per kernel ("K name") and per copy ("C direction bytes"), by start time.
                                     Small pageable copies are staged by the runtime and appear as its copy kernel, without a size:
   frame_calls_trace.py copies LOG   every hipMemcpy* call of a `run` whose stderr went to LOG under AMD_LOG_LEVEL=3 (the HIP
                                     runtime's own call log), in call order: "M direction bytes".
@@ -73,6 +77,42 @@ def run():
     print("frame_calls_trace: ok")
 
 
+def run_stream():
+    import io
+    import oracle_api as O
+    from lz4_flex_amd import block, frame as F
+    text = O.fixture_plain("compression_65k") + O.fixture_plain("compression_66k_JSON")
+    linked_chunks = [BS, BS, BS, 1000, BS, 30000, BS, BS]
+    for mode, chunks in ((1, linked_chunks), (0, [5 * BS + 1000])):
+        n = sum(chunks)
+        data = (text * (n // len(text) + 1))[:n]
+        info = F.FrameInfo(block_mode=F.BlockMode(mode), block_size=F.BlockSize.Max64KB)
+        for cm in ("fast", "exact"):
+            block.set_compress_mode(cm)
+            try:
+                buf, at = io.BytesIO(), 0
+                e = F.FrameEncoder.with_frame_info(info, buf)
+                for c in chunks:
+                    e.write(data[at:at + c]); e.flush()
+                    at += c
+                e.finish()
+                one = F.compress_frame(data, info)
+            finally:
+                block.set_compress_mode("fast")
+            for f in (buf.getvalue(), one):
+                assert O.frame_decompress(f, n) == (0, data, len(f))
+            for size in (BS, 1 << 20):
+                d, out = F.FrameDecoder.new(io.BytesIO(buf.getvalue())), []
+                while True:
+                    b = d.read(size)
+                    if not b:
+                        break
+                    out.append(b)
+                assert b"".join(out) == data
+            assert F.decompress_frame(one, n) == (data, len(one))
+    print("frame_calls_trace: stream ok")
+
+
 def short(name):
     name = re.sub(r"\s*\[clone .*$", "", name)
     return re.sub(r"^void\s+", "", re.sub(r"\(.*$", "", name)).strip()
@@ -112,6 +152,8 @@ def copies(log):
 if __name__ == "__main__":
     if len(sys.argv) >= 2 and sys.argv[1] == "run":
         run()
+    elif len(sys.argv) >= 2 and sys.argv[1] == "run-stream":
+        run_stream()
     elif len(sys.argv) == 3 and sys.argv[1] == "list":
         listing(sys.argv[2])
     elif len(sys.argv) == 3 and sys.argv[1] == "copies":
