@@ -103,7 +103,9 @@ const char *lz4flex_build_id(void);
  * brings scratch and work; a caller detects them by the symbol), then the setting "compress_parse" for "compress_mode" 2 (no new symbol,
  * no workspace beyond the encoder's: a caller detects it by lz4flex_set_tuning(ctx, "compress_parse", 1) == 0), then the paged streams
  * lz4flex_compress_paged with lz4flex_compress_paged_work_size, lz4flex_paged_pages_bound and lz4flex_paged_rounds_bound (no setting, no
- * workspace in the context: the caller brings scratch and work; a caller detects them by the symbol). */
+ * workspace in the context: the caller brings scratch and work; a caller detects them by the symbol), then their read side
+ * lz4flex_paged_read_ranges with lz4flex_paged_read_work_size and lz4flex_paged_range_pages_bound (no setting, no workspace in the
+ * context in MEM_DEVICE: the caller brings scratch and work; a caller detects them by the symbol). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -784,7 +786,7 @@ int lz4flex_compress_batch_fit(lz4flex_ctx *ctx, const void *in_base, const uint
  * "Cut each of my n streams into pages of P bytes."  Every page is a self-contained LZ4 block that holds as much of its stream as fits,
  * page j + 1 starts where page j stopped: the LZ4_compress_destSize loop of fixed-output compression, with no host round trip between
  * pages.  The read side exists: a page is an ordinary block, lz4flex_decompress_batch over the page table puts a stream back together,
- * lz4flex_decompress_batch_partial reads into a page.
+ * lz4flex_decompress_batch_partial reads into a page, and lz4flex_paged_read_ranges (below) reads byte ranges of the streams in one call.
  *
  * THE RULE (tests/paged_model.py is the same rule as a program).  P = page_size; stream i is the in_len[i] bytes at in_base + in_off[i]
  * and owns the table entries `[page_off[i], page_off[i+1])`, its capacity `C_i = page_off[i+1] - page_off[i]` pages.  Its state is
@@ -841,6 +843,77 @@ int lz4flex_compress_paged(lz4flex_ctx *ctx, const void *in_base, const uint64_t
 size_t lz4flex_compress_paged_work_size(uint32_t n);
 uint64_t lz4flex_paged_pages_bound(uint32_t in_len, uint32_t page_size);
 uint32_t lz4flex_paged_rounds_bound(uint32_t max_in_len, uint32_t page_size, uint32_t window_min, uint32_t window_max);
+
+/* ---- paged streams, the read side: m byte ranges in one call, planned on the device (lz4_paged_read.hip, paged_range.h) ---------------
+ * "Give me bytes [a, a + len) of stream i", m times, from the page file and the tables lz4flex_compress_paged wrote -- where it wrote
+ * them: in MEM_DEVICE the plan (which pages, which of them from the middle), the decode batches, the gather and the verdicts all run on
+ * the device; nothing is read back, nothing is allocated, nothing is synchronised.  The first eight arguments are what
+ * lz4flex_compress_paged produced: entry e of the table is the page at `pages + e * page_size`, e is absolute and page_off[0] need not
+ * be 0.  What lz4flex_frame_read_ranges is for indexed frames, with the plan on the device because the tables are born there.
+ *
+ * THE RULE (tests/paged_read_model.py is the same rule as a program; paged_range.h holds its integer part for the host and the kernels).
+ * Locating.  For range r: `i = range_stream[r]`, `first = page_off[i]`, `C = page_off[i+1] - first` (0 where page_off counts down),
+ *   `k = min(n_pages[i], C)`, `S = in_done[i]`.  `out_len[r] = min(range_len[r], S - range_off[r])`, 0 for `range_off[r] >= S`: a read at
+ *   end of file.  Those bytes are stream i's bytes at that position, written at `out_base + out_off[r]`.  Writes are strict: nothing in
+ *   front of that address, nothing at or behind `+ out_len[r]`, nothing else of out_base, nothing of the tables or the page file.  The
+ *   page that holds stream byte pos is the last `j < k` with `page_src[first + j] <= pos`; page j decodes to `[page_src[first+j],
+ *   page_src[first+j+1])`, the last page up to S.  A range touches pages `j0 .. j1`, `nb = j1 - j0 + 1`.
+ * Which page decodes where.  Every touched page whose start lies inside the range is decoded straight into the output
+ *   (lz4flex_decompress_batch_partial with target = the page's wanted bytes; the last page is clipped at the range's end).  If the range
+ *   starts inside page j0 (`s = range_off - page_src[first+j0] > 0`) that page is a HEAD: it is decoded into `scratch` up to its last
+ *   wanted byte, `head_bytes = min(range end, page end) - page start`, and `[s, head_bytes)` is copied out.  LZ4 has no other way into a
+ *   page than its first byte.  Several ranges that hit one page decode it once each.
+ * Capacities, in range order.  `slot_r` = the sum of nb over the ranges in front of r (whatever became of them); `head_off_r` = the sum
+ *   of their head_bytes, each rounded up to 64.  Range r is SERVED iff `slot_r + nb_r <= max_items` and, when it has a head,
+ *   `head_off_r + head_bytes_r <= scratch_cap` (a range without a head takes no scratch and is never refused for it).  A range that is
+ *   not served gets LZ4FLEX_E_OUTPUT_TOO_SMALL and out_len 0, nothing of it is written, the other ranges are unaffected -- the packed and
+ *   fit entries' rule.  lz4flex_paged_range_pages_bound(L, P), a pure host function: 0 for L = 0, 1 for L = 1, else
+ *   `2 + (L - 2) / Lfit(P, infinity)` -- the pages between a range's first and last page are non-final pages of their stream, and
+ *   lz4flex_compress_paged guarantees each of those at least Lfit(P, infinity) bytes; the first and the last page hold at least one byte of
+ *   the range each; 0 for a page size the paged entry refuses.  The sum of the bounds over the ranges is a max_items that always suffices
+ *   for tables lz4flex_compress_paged wrote; `m * roundup64(window_max)` is a scratch_cap that always suffices -- real needs are about one
+ *   page's decoded size per head.
+ * status[r], in this order (codes are positive, as in the batch entries):
+ *   1. `range_stream[r] >= n`: LZ4FLEX_E_INVALID_ARG.
+ *   2. clipped length 0: status 0, out_len 0, nothing planned.
+ *   3. not served: LZ4FLEX_E_OUTPUT_TOO_SMALL.
+ *   4. a table that contradicts itself for this range: LZ4FLEX_E_INVALID_ARG, nothing written.  That is: `k == 0` with bytes wanted; a
+ *      touched page with `page_len > page_size`, one that starts at or behind S, or at or behind the start of the page behind it (page_src
+ *      not ascending over the touched pages); a first page that does not hold range_off, another page that does not start inside the
+ *      range, a last page that ends in front of the range's end -- every item's output span lies inside `[0, out_len)` or its head slot.
+ *   5. the first touched page, in stream order, that does not deliver: the partial decoder's error code if it fails the page;
+ *      LZ4FLEX_E_EXPECTED_ANOTHER_BYTE if the page decodes without an error but to fewer bytes than wanted (the page ended before the
+ *      table says it does -- deliberately another code than the capacity code of 3).
+ *   On any error out_len[r] = 0; under 5 the range's own region may hold anything.
+ * Hostile tables (MEM_DEVICE: caller-supplied device memory): whatever page_len / page_src / n_pages / in_done hold, no page is read
+ *   outside `pages[e * P, e * P + P)` of an entry e inside the stream's `[first, first + C)`, and nothing is written outside a range's
+ *   region or its head slot: condition 4 is checked for every touched page of a served range before an item exists.
+ * Call-level returns, checked before a context or a device is looked at: -LZ4FLEX_E_INVALID_ARG for a mem_kind other than HOST / DEVICE
+ *   (| BIG_BLOCKS, which is passed to the decoder; LZ4FLEX_MEM_CHAINED is refused) and for a page_size outside 64 .. 4 MiB; then m == 0
+ *   returns 0; then -LZ4FLEX_E_INVALID_ARG for a missing array (the five tables, the three range arrays, out_off, out_len, status) and, in
+ *   DEVICE mode, a missing work or a missing scratch with scratch_cap != 0.  -LZ4FLEX_E_NO_DEVICE without a device.
+ * mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, asynchronous on hip_stream; a fixed sequence of launches, all sized by m
+ *   and max_items: locate (a lane per range), two offset scans (lz4_packed.hip's), check (a wavefront per range) and emit (a thread per
+ *   item slot), lz4flex_decompress_batch_partial over max_items bodies and over m heads, the gather, the verdict (a wavefront per
+ *   range).  A slot nobody owns is a one-byte block with target 0 -- the partial decoder reads nothing of it -- so an oversized max_items
+ *   costs empty decoder slots and the work arrays, not decode time.  work: lz4flex_paged_read_work_size(m, max_items) bytes, 8-byte
+ *   aligned; scratch and work may be overwritten.  "decompress_partial" picks the partial decoder as for lz4flex_decompress_batch_partial.
+ *   LZ4FLEX_MEM_HOST -- everything is host memory, staged through the context and synchronous; max_items, scratch, scratch_cap and work
+ *   are ignored: the host locates the ranges itself and sizes exactly (no range is refused under 3).  Per range ONE upload of the span of
+ *   its touched pages goes up and its bytes come back: a small read does not upload the page file.  The ranges are cut into passes under
+ *   the setting "frame_range_pass_bytes" (a pass takes at least one range).
+ * Measured on an MI355X (tools/paged_read_bench.py, one session, profiles/r25_paged_read.txt; device-resident, ms per call, host clock
+ *   around a synchronised call): 16 384 x 64 KiB JSON tiles in 4 KiB pages, every stream as one range 2.31 (block.decompress_paged_device
+ *   on the same tables, its synchronisation included: 2.46); 1 024 / 65 536 random 4 KiB ranges 0.26 / 1.96 (1 272 / 81 164 touched
+ *   pages); 65 536 ranges of 64 bytes 1.39.  A small call is bound by its dozen launches, a large one scales with the touched pages.
+ * Not in scope: dictionaries, history and filters on pages; de-duplicating ranges that hit one page; a skip-ahead decoder for heads. */
+uint32_t lz4flex_paged_range_pages_bound(uint32_t range_len, uint32_t page_size);
+size_t lz4flex_paged_read_work_size(uint32_t m, uint32_t max_items);
+int lz4flex_paged_read_ranges(lz4flex_ctx *ctx, const void *pages, uint32_t page_size, const uint64_t *page_off /* n + 1, entries */,
+                              const uint32_t *page_len, const uint32_t *page_src, const uint32_t *n_pages, const uint32_t *in_done,
+                              uint32_t n, const uint32_t *range_stream, const uint32_t *range_off, const uint32_t *range_len, uint32_t m,
+                              void *out_base, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint32_t max_items,
+                              void *scratch, uint64_t scratch_cap, void *work, int mem_kind, void *hip_stream);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

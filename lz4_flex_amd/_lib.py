@@ -108,6 +108,10 @@ SIGNATURES = {
     "lz4flex_compress_paged_work_size": (_SZ, [_U32]),
     "lz4flex_paged_pages_bound": (_U64, [_U32, _U32]),
     "lz4flex_paged_rounds_bound": (_U32, [_U32, _U32, _U32, _U32]),
+    "lz4flex_paged_range_pages_bound": (_U32, [_U32, _U32]),
+    "lz4flex_paged_read_work_size": (_SZ, [_U32, _U32]),
+    "lz4flex_paged_read_ranges": (_I32, [_VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _U64,
+                                          _VP, _I32, _VP]),
     "lz4flex_set_tuning": (_I32, [_VP, C.c_char_p, _I32]),
     "lz4flex_get_tuning": (_I32, [_VP, C.c_char_p]),
     "lz4flex_frame_encoder_new": (_VP, [C.POINTER(FrameInfoC), WRITE_FN, _VP]),

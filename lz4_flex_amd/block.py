@@ -1235,6 +1235,106 @@ def decompress_paged_device(paged, stream=None):
     return out[:total], out_off, done, status
 
 
+def paged_range_pages_bound(length, page_size):
+    """lz4flex_paged_range_pages_bound: the pages a range of `length` bytes can touch in tables compress_paged wrote"""
+    return int(L.load().lz4flex_paged_range_pages_bound(int(length), int(page_size)))
+
+
+def _paged_tables(paged):
+    """the five tables of a PagedStreams as lz4flex_paged_read_ranges takes them (an empty one still gets an address)"""
+    keep = [paged.pages, paged.page_off, paged.page_len, paged.page_src, paged.n_pages, paged.in_done]
+    if isinstance(paged.pages, np.ndarray):
+        keep = [_host_u8(keep[0]), _np(keep[1], np.uint64)] + [_np(a, np.uint32) for a in keep[2:]]
+        return [np.zeros(1, dtype=a.dtype) if a.size == 0 else a for a in keep]
+    return [a.new_zeros(1) if a.numel() == 0 else a.contiguous() for a in keep]
+
+
+def read_paged_ranges(paged, sid, off, length, ctx=None):
+    """lz4flex_paged_read_ranges over a PagedStreams of numpy arrays (MEM_HOST): range r is bytes [off[r], off[r] + length[r]) of stream
+    sid[r], clipped at the stream's in_done; length 0xFFFFFFFF with off 0 reads a whole stream.  Returns (list of bytes, status): the
+    bytes of a range with status != 0 are b"" (status: the rule's codes, include/lz4flex_amd.h)."""
+    sid, off, length = _np(sid, np.uint32), _np(off, np.uint32), _np(length, np.uint32)
+    m = len(sid)
+    if len(off) != m or len(length) != m:
+        raise ValueError("sid, off and length differ in length")
+    pages, page_off, page_len, page_src, n_pages, in_done = _paged_tables(paged)
+    n = len(paged.n_pages)
+    out_len, status = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.int32)
+    if m == 0:
+        return [], status
+    done = np.array([int(paged.in_done[i]) if i < n else 0 for i in sid], dtype=np.int64)
+    room = np.clip(np.minimum(length.astype(np.int64), done - off.astype(np.int64)), 0, None)
+    out_off = np.zeros(m, dtype=np.uint64)
+    out_off[1:] = np.cumsum(room[:-1])
+    out = np.zeros(max(int(room.sum()), 1), dtype=np.uint8)
+    args = [pages, int(paged.page_size), page_off, page_len, page_src, n_pages, in_done, n, sid, off, length, m, out, out_off, out_len, status,
+            0, None, 0, None]
+    _check(L.load().lz4flex_paged_read_ranges(ctx, *map(_arg, args), L.MEM_HOST, None), "lz4flex_paged_read_ranges")
+    return [out[int(o):int(o) + int(k)].tobytes() for o, k in zip(out_off, out_len)], status
+
+
+def read_paged_ranges_device(paged, sid, off, length, out=None, out_off=None, max_items=None, scratch_cap=None, stream=None):
+    """lz4flex_paged_read_ranges over a PagedStreams of device tensors (MEM_DEVICE, asynchronous on `stream`, default the current one):
+    sid / off / length are integer tensors (the low 32 bits count) or anything torch.as_tensor takes.  Nothing is read back from the
+    device unless a default needs it: out / out_off default to regions of min(length[r], in_done - off[r]) bytes back to back, computed
+    on the device (ONE synchronisation, for their sum; length 0xFFFFFFFF with off 0 reads whole streams); max_items defaults to the sum
+    of paged_range_pages_bound(length[r]) when `length` is host-visible, else to the number of table entries plus m -- and never to
+    more than that, which suffices for ranges that do not overlap; scratch_cap defaults to the default window_max of 65536 bytes per
+    range, 1 GiB at most (real needs are about one page's decoded size per head).  A range the capacities do not serve reports
+    E_OUTPUT_TOO_SMALL: pass larger ones.  Scratch and work come from torch's allocator on the CURRENT stream, as in the other device
+    forms.  Returns (out, out_off, out_len, status): range r's bytes are out[out_off[r] : out_off[r] + out_len[r]]; out_len / status
+    as int32 tensors (the bit patterns of u32 / the rule's codes)."""
+    import torch
+    dev = paged.pages.device
+    P = int(paged.page_size)
+    host_len = None if hasattr(length, "data_ptr") and length.device.type != "cpu" else [int(v) & 0xFFFFFFFF for v in np.asarray(length).reshape(-1)]
+
+    def u32(a):
+        # wrap-around intended: the library reads the bit pattern
+        a = torch.as_tensor(np.asarray(a, dtype=np.int64) if not hasattr(a, "data_ptr") else a)
+        return ((a.to(device=dev, dtype=torch.int64) + 0x80000000) % 0x100000000 - 0x80000000).to(torch.int32).contiguous()
+
+    d_sid, d_off, d_len = u32(sid), u32(off), u32(length)
+    m = int(d_sid.numel())
+    if int(d_off.numel()) != m or int(d_len.numel()) != m:
+        raise ValueError("sid, off and length differ in length")
+    n = int(paged.n_pages.numel())
+    out_len, status = torch.zeros(m, dtype=torch.int32, device=dev), torch.zeros(m, dtype=torch.int32, device=dev)
+    if out is None or out_off is None:
+        if out is not None or out_off is not None:
+            raise ValueError("out and out_off come together")
+        # every region as long as the range can get: min(length, in_done - off) needs the tables, which are on the device -- computed there
+        done = torch.cat([paged.in_done.to(torch.int64) & 0xFFFFFFFF, torch.zeros(1, dtype=torch.int64, device=dev)])
+        idx = torch.clamp(d_sid.to(torch.int64) & 0xFFFFFFFF, max=n)
+        room = torch.clamp(torch.minimum(d_len.to(torch.int64) & 0xFFFFFFFF, done[idx] - (d_off.to(torch.int64) & 0xFFFFFFFF)), min=0)
+        out_off = torch.cumsum(room, 0) - room
+        out = torch.empty(max(int(room.sum()) if m else 0, 1), dtype=torch.uint8, device=dev)     # (a synchronisation: the output's size)
+    else:
+        if out.device != dev or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor on the GPU of the pages")
+        out_off = out_off.to(device=dev, dtype=torch.int64).contiguous()
+        if int(out_off.numel()) != m:
+            raise ValueError("sid and out_off differ in length")
+    if m == 0:
+        return out, out_off, out_len, status
+    lib = L.load()
+    if max_items is None:
+        entries = int(paged.page_len.numel())
+        max_items = entries + m
+        if host_len is not None:
+            max_items = min(max_items, sum(paged_range_pages_bound(v, P) for v in host_len))
+    max_items = min(int(max_items), 0xFFFFFFFF)
+    scratch_cap = min(m * 65536, 1 << 30) if scratch_cap is None else int(scratch_cap)
+    scratch = torch.empty(max(scratch_cap, 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(lib.lz4flex_paged_read_work_size(m, max_items)), dtype=torch.uint8, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    pages, page_off, page_len, page_src, n_pages, in_done = _paged_tables(paged)
+    _device_call("lz4flex_paged_read_ranges", [pages, P, page_off.to(torch.int64), page_len, page_src, n_pages, in_done], n,
+                 [d_sid, d_off, d_len, m, out, out_off, out_len, status, max_items, scratch, scratch_cap, work], P > 131072, C.c_void_p(stream))
+    return out, out_off, out_len, status
+
+
 class CompressedTensor:
     """What compress_tensor returns and decompress_tensor takes: the compressed blocks back to back in `data` (a uint8 device tensor),
     block i at data[offsets[i] : offsets[i] + lengths[i]] (device tensors), and what the tensor was: shape, dtype, the block_bytes it was

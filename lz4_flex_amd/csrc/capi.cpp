@@ -1721,11 +1721,7 @@ int lz4flex_compress_batch_fit(lz4flex_ctx* ctx, const void* in_base, const uint
 namespace {
 
 // Lfit(r, infinity) of the fit rule: the largest L with tail(L) <= r (r >= 1)
-uint32_t lfit_unbounded(uint32_t r) {
-    if (r <= 16u) return std::min(r - 1u, 14u);
-    const uint32_t y = r - 17u;
-    return 15u + y - (y >> 8) - ((y & 255u) == 255u ? 1u : 0u);
-}
+uint32_t lfit_unbounded(uint32_t r) { return lz4flex_paged::lfit_page(r); }      // (paged_range.h: the read side's bound uses it too)
 
 // the page size and the windows of a paged call, defaults resolved; false: not a legal combination
 bool paged_params(uint32_t page_size, uint32_t& window_min, uint32_t& window_max) {
@@ -1859,6 +1855,166 @@ int lz4flex_compress_paged(lz4flex_ctx* ctx, const void* in_base, const uint64_t
     const PagedCall p{(const uint8_t*)in_base, in_off, in_len, n, page_size, window_min, window_max, max_rounds, (uint8_t*)out_base, page_off,
                       page_len, page_src, n_pages, in_done, status};
     return paged_on_host(ctx, p, k.big);
+}
+
+// ---- paged streams, the read side: m byte ranges in one call, planned on the device (lz4_paged_read.hip) ------------------------------
+}  // extern "C"
+
+namespace {
+
+using lz4flex_paged::RangeRec;
+
+// a call on device memory: a fixed sequence of launches sized by m and max_items; nothing is allocated, read back or synchronised
+int paged_read_on_device(lz4flex_ctx* c, const PagedReadArgs& a, const uint8_t* pages, uint8_t* out_base, uint8_t* scratch, void* work, bool big,
+                         hipStream_t s) {
+    const PagedReadWork w = paged_read_work(work, a.m, a.max_items);
+    hipError_t e = launch_paged_read_locate(a, w, s);
+    if (e == hipSuccess) e = launch_packed_scan(w.nb, a.m, 1u, ~0ull, 0u, w.tiles, w.slot, nullptr, nullptr, nullptr, s);
+    if (e == hipSuccess) e = launch_packed_scan(w.hb, a.m, lz4flex_paged::HEAD_ALIGN, ~0ull, 0u, w.tiles, w.head_off, nullptr, nullptr, nullptr, s);
+    if (e == hipSuccess) e = launch_paged_read_plan(a, w, s);
+    if (e != hipSuccess) return hip_fail(e, "paged read plan launch");
+    const int mem = LZ4FLEX_MEM_DEVICE | (big ? LZ4FLEX_MEM_BIG_BLOCKS : 0);
+    int rc;
+    if (a.max_items &&
+        (rc = lz4flex_decompress_batch_partial(c, pages, w.a_in, w.a_len, a.max_items, out_base, w.a_out, w.a_tgt, w.a_olen, w.a_st, mem, s))) return rc;
+    if (a.scratch_cap) {                                         // (no scratch: no range with a head is served, b_* is not read)
+        if ((rc = lz4flex_decompress_batch_partial(c, pages, w.b_in, w.b_len, a.m, scratch, w.b_out, w.b_tgt, w.b_olen, w.b_st, mem, s))) return rc;
+        e = launch_copy_batch(scratch, w.d_src, w.d_len, out_base, w.d_dst, a.m, s);
+        if (e != hipSuccess) return hip_fail(e, "paged read gather launch");
+    }
+    e = launch_paged_read_verdict(a, w, s);
+    return e != hipSuccess ? hip_fail(e, "paged read verdict launch") : 0;
+}
+
+struct PagedReadCall {
+    const uint8_t* pages; lz4flex_paged::Tables t;
+    const uint32_t* range_stream; const uint32_t* range_off; const uint32_t* range_len; uint32_t m;
+    uint8_t* out_base; const uint64_t* out_off; uint32_t* out_len; int32_t* status;
+};
+
+// One MEM_HOST pass: the ranges live[0 .. R) (located, sound, E touched pages in all) become R streams of a table of their own -- stream
+// q holds range q's touched pages and ends where its last page does --, the span of every range's pages goes up, the device path runs
+// with exactly the items and the scratch the pass needs, the results and the output come down with one synchronisation.
+int paged_read_pass(lz4flex_ctx* c, const PagedReadCall& p, const RangeRec* recs, const uint32_t* live, uint32_t R, uint64_t E, bool big) {
+    const uint32_t P = p.t.page_size;
+    uint64_t out_bytes = 0, head_bytes = 0;
+    for (uint32_t q = 0; q < R; q++) {
+        out_bytes += align_up(recs[live[q]].len, 64);
+        head_bytes += lz4flex_paged::head_slot_bytes(recs[live[q]]);
+    }
+    HostStage st;
+    const auto page_off = st.up<uint64_t>((size_t)R + 1u), out_off = st.up<uint64_t>(R);
+    const auto page_len = st.up<uint32_t>((size_t)E), page_src = st.up<uint32_t>((size_t)E);
+    const auto n_pages = st.up<uint32_t>(R), in_done = st.up<uint32_t>(R), r_stream = st.up<uint32_t>(R), r_off = st.up<uint32_t>(R), r_len = st.up<uint32_t>(R);
+    const auto out_len = st.down<uint32_t>(R);
+    const auto status = st.down<int32_t>(R);
+    const Region r_in = st.region((size_t)(E * P), 64), r_out = st.region((size_t)out_bytes, 64), r_heads = st.region((size_t)head_bytes, 64);
+    st.columns();
+    const Region r_work = st.region(paged_read_work_bytes(R, (uint32_t)E), 0);
+    int rc;
+    if ((rc = stage_open(c, st))) return rc;
+    if ((rc = ensure_buf(c->pay, (size_t)out_bytes + 16))) return rc;
+    hipStream_t s = st.s;
+    uint64_t e_at = 0, o_at = 0;
+    for (uint32_t q = 0; q < R; q++) {
+        const RangeRec& r = recs[live[q]];
+        const uint64_t e0 = r.first + r.j0;
+        const uint32_t j1 = r.j0 + r.nb - 1u;
+        st.host(page_off)[q] = e_at; st.host(out_off)[q] = o_at;
+        memcpy(st.host(page_len) + e_at, p.t.page_len + e0, 4ull * r.nb);
+        memcpy(st.host(page_src) + e_at, p.t.page_src + e0, 4ull * r.nb);
+        st.host(n_pages)[q] = r.nb;
+        st.host(in_done)[q] = j1 + 1u < r.k ? p.t.page_src[r.first + j1 + 1u] : r.S;
+        st.host(r_stream)[q] = q; st.host(r_off)[q] = r.off; st.host(r_len)[q] = r.len;
+        HIP_TRY(hipMemcpyAsync(st.dev(r_in) + e_at * P, p.pages + e0 * P, (size_t)r.nb * P, hipMemcpyHostToDevice, s));
+        e_at += r.nb; o_at += align_up(r.len, 64);
+    }
+    st.host(page_off)[R] = e_at;
+    HIP_TRY(st.send_columns());
+    PagedReadArgs dv{};
+    dv.t = lz4flex_paged::Tables{st.dev(page_off), st.dev(page_len), st.dev(page_src), st.dev(n_pages), st.dev(in_done), R, P};
+    dv.range_stream = st.dev(r_stream); dv.range_off = st.dev(r_off); dv.range_len = st.dev(r_len); dv.m = R;
+    dv.out_off = st.dev(out_off); dv.out_len = st.dev(out_len); dv.status = st.dev(status);
+    dv.max_items = (uint32_t)E; dv.scratch_cap = head_bytes;
+    if ((rc = paged_read_on_device(c, dv, st.dev(r_in), st.dev(r_out), st.dev(r_heads), st.dev(r_work), big, s))) return rc;
+    HIP_TRY(st.fetch_columns(out_len));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, st.dev(r_out), (size_t)out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t q = 0; q < R; q++) {
+        const uint32_t r = live[q];
+        p.status[r] = st.host(status)[q]; p.out_len[r] = st.host(out_len)[q];
+        if (p.status[r] == 0 && p.out_len[r]) memcpy(p.out_base + p.out_off[r], c->pay.p + st.host(out_off)[q], p.out_len[r]);
+    }
+    return 0;
+}
+
+// MEM_HOST: the host locates the ranges itself (paged_range.h, the functions the kernels run) and answers the ranges that need no
+// device -- no such stream, nothing wanted, a contradicting table; the others go up in passes of at most "frame_range_pass_bytes" of
+// staging (a pass takes at least one range).
+int paged_read_on_host(lz4flex_ctx* c, const PagedReadCall& p, bool big) {
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    std::vector<RangeRec> recs(p.m);
+    std::vector<uint32_t> live;
+    for (uint32_t r = 0; r < p.m; r++) {
+        RangeRec& q = recs[r];
+        lz4flex_paged::locate(p.t, p.range_stream[r], p.range_off[r], p.range_len[r], &q);
+        p.out_len[r] = 0u;
+        if (q.flags & lz4flex_paged::REC_NO_STREAM) { p.status[r] = LZ4FLEX_E_INVALID_ARG; continue; }
+        if (q.len == 0u) { p.status[r] = 0; continue; }
+        bool ok = (q.flags & lz4flex_paged::REC_BAD) == 0u;
+        for (uint32_t j = 0; ok && j < q.nb; j++) ok = lz4flex_paged::page_ok(p.t, q, q.j0 + j);
+        if (!ok) { p.status[r] = LZ4FLEX_E_INVALID_ARG; continue; }
+        live.push_back(r);
+    }
+    const uint64_t pass_bytes = (uint64_t)std::max(c->range_pass_bytes, 1);
+    for (size_t first = 0; first < live.size();) {
+        uint64_t bytes = 0, E = 0;
+        size_t i = first;
+        for (; i < live.size(); i++) {
+            const RangeRec& q = recs[live[i]];
+            const uint64_t cost = (uint64_t)q.nb * p.t.page_size + align_up(q.len, 64) + lz4flex_paged::head_slot_bytes(q);
+            if (i > first && (cost > pass_bytes - std::min(bytes, pass_bytes) || E + q.nb > 0x7FFFFFFFull)) break;
+            bytes += cost; E += q.nb;
+        }
+        if (E > 0xFFFFFFFFull) return -LZ4FLEX_E_UNSUPPORTED;
+        if (const int rc = paged_read_pass(c, p, recs.data(), live.data() + first, (uint32_t)(i - first), E, big)) return rc;
+        first = i;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t lz4flex_paged_range_pages_bound(uint32_t range_len, uint32_t page_size) { return lz4flex_paged::pages_bound(range_len, page_size); }
+
+size_t lz4flex_paged_read_work_size(uint32_t m, uint32_t max_items) { return paged_read_work_bytes(m, max_items); }
+
+int lz4flex_paged_read_ranges(lz4flex_ctx* ctx, const void* pages, uint32_t page_size, const uint64_t* page_off, const uint32_t* page_len,
+                              const uint32_t* page_src, const uint32_t* n_pages, const uint32_t* in_done, uint32_t n, const uint32_t* range_stream,
+                              const uint32_t* range_off, const uint32_t* range_len, uint32_t m, void* out_base, const uint64_t* out_off,
+                              uint32_t* out_len, int32_t* status, uint32_t max_items, void* scratch, uint64_t scratch_cap, void* work, int mem_kind,
+                              void* hip_stream) {
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (page_size < lz4flex_paged::PAGE_MIN || page_size > lz4flex_paged::PAGE_MAX) return -LZ4FLEX_E_INVALID_ARG;
+    if (m == 0) return 0;
+    if (!page_off || !page_len || !page_src || !n_pages || !in_done || !range_stream || !range_off || !range_len || !out_off || !out_len || !status)
+        return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && (!work || (!scratch && scratch_cap))) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;                  // (lz4flex_decompress_batch_partial has the "debug_fail_next_batch" hook)
+    const lz4flex_paged::Tables t{page_off, page_len, page_src, n_pages, in_done, n, page_size};
+    if (k.where == Mem::Device) {
+        const PagedReadArgs a{t, range_stream, range_off, range_len, m, out_off, out_len, status, max_items, scratch_cap};
+        return paged_read_on_device(ctx, a, (const uint8_t*)pages, (uint8_t*)out_base, (uint8_t*)scratch, work, k.big, (hipStream_t)hip_stream);
+    }
+    const PagedReadCall p{(const uint8_t*)pages, t, range_stream, range_off, range_len, m, (uint8_t*)out_base, out_off, out_len, status};
+    try {
+        return paged_read_on_host(ctx, p, k.big || page_size > 131072u);
+    } catch (...) { return -LZ4FLEX_E_NOMEM; }
 }
 
 // ---- scalar, lz4_flex-shaped: 1-block host batches ------------------------------------------

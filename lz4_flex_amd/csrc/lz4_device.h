@@ -4,7 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lz4_route.h"   // PCD_PAIR_MAX_BLOCKS, the DISPATCH_* batch sizes and decode_route / encode_route: which kernel a batch takes (host-only, plain integers)
+#include "paged_range.h" // the records of lz4flex_paged_read_ranges (plain integers, host and device)
+#include "lz4_route.h"  // PCD_PAIR_MAX_BLOCKS, the DISPATCH_* batch sizes and decode_route / encode_route: which kernel a batch takes (host-only, plain integers)
 
 #define LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL 1
 #define LZ4FLEX_DEV_E_LITERAL_OUT_OF_BOUNDS 2
@@ -348,6 +349,32 @@ struct PagedWork {
 size_t paged_work_bytes(uint32_t n);
 PagedWork paged_work(void* work, uint32_t n);
 hipError_t launch_paged_step(const PagedArgs& a, const PagedWork& w, int phase, hipStream_t s);
+// lz4_paged_read.hip (lz4flex_paged_read_ranges): m byte ranges of paged streams, planned on the device.  Every pointer is device memory.
+// The launches, in order: locate (a record per range; w.nb / w.hb: the sizes the two scans sum), launch_packed_scan twice (w.slot: align
+// 1; w.head_off: align HEAD_ALIGN), plan (who is served and sound, then the items of the decode batches A -- max_items entries, sink: the
+// output -- and B -- m entries, sink: the scratch -- and of the gather d_* from the scratch), the two partial decodes and the gather
+// (capi.cpp), verdict (status / out_len per range).
+struct PagedReadArgs {
+    lz4flex_paged::Tables t;
+    const uint32_t* range_stream; const uint32_t* range_off; const uint32_t* range_len; uint32_t m;
+    const uint64_t* out_off; uint32_t* out_len; int32_t* status;
+    uint32_t max_items; uint64_t scratch_cap;
+};
+// the arrays a call keeps in the caller's `work` (paged_read_work_bytes(m, max_items) bytes, any 8-byte aligned address)
+struct PagedReadWork {
+    lz4flex_paged::RangeRec* rec;                                   // m
+    uint64_t* nb; uint64_t* hb;                                     // m each: touched pages, head bytes
+    uint64_t* slot; uint64_t* head_off;                             // m + 1 each: their exclusive sums
+    uint64_t* tiles;                                                // the scans' tile sums
+    uint64_t* a_in; uint64_t* a_out; uint32_t* a_len; uint32_t* a_tgt; uint32_t* a_olen; int32_t* a_st;     // max_items each
+    uint64_t* b_in; uint64_t* b_out; uint64_t* d_src; uint64_t* d_dst;                                     // m each
+    uint32_t* b_len; uint32_t* b_tgt; uint32_t* b_olen; int32_t* b_st; uint32_t* d_len;                    // m each
+};
+size_t paged_read_work_bytes(uint32_t m, uint32_t max_items);
+PagedReadWork paged_read_work(void* work, uint32_t m, uint32_t max_items);
+hipError_t launch_paged_read_locate(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s);
+hipError_t launch_paged_read_plan(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s);
+hipError_t launch_paged_read_verdict(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s);
 // lz4_packed.hip (lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed): the output layout of a batch, computed on the device.
 constexpr uint32_t PACKED_SCAN_TILE = 1024u;         // the sizes one workgroup scans ("packed_scan_tile")
 enum : int {
