@@ -22,6 +22,14 @@
 //     4 steps a group snapshots the queue's tail and publishes its head; once per iteration it checks the buffer space for
 //     the iteration's pieces and touches the next 128-byte line of the compressed stream ahead of the parser, which keeps
 //     the parser's chunk loads out of HBM latency.
+//     A copier wavefront serves its blocks in lockstep, so a group that runs out of buffer space takes the whole wavefront out
+//     of the hot loop: a VISIT of service().  Since round 27 a visit writes back and slides EVERY live group of the wavefront
+//     (wave_flush_slide(): one function for the wavefront, trip counts taken once, four LDS reads in flight before their stores),
+//     so the groups come back for the next visit together: 90 visits per 64 KiB block where the rule before (only groups below
+//     FLUSH_AT bytes of space; the others asked for a visit of their own a few hundred bytes later) made 150.  A visit costs
+//     4.4 k cycles of its wavefront with 14.6 groups written back (before: 3.7 k with about 7), all visits 10.9 % of a copier
+//     wavefront's cycles (14.5 %): profiles/r27_split_visits.txt.  Round 3 had changed the INSIDE of the flush (four pieces at a
+//     time, inlined, per group) and left the number of visits alone: no gain.
 //
 // The parser is per-lane scalar code: lz4_split_parser.h also compiles for the host (tests/sim/), where it is checked
 // against the oracle.  Measurements, what bounds the kernel and the variants that were tried and dropped: DESIGN.md
@@ -40,7 +48,7 @@ namespace lz4flex_dev {
 #ifdef LZ4FLEX_PROFILE_PHASES
 // [0] parser wave cycles, [1] parser wave-steps, [2..6] lane sums: live steps, queue-full, window bubbles, exact path, records
 // [8] copier wave cycles, [9] copier wave 4-step iterations, [10] service visits, [11] group-steps with a piece,
-// [12] group-steps idle on an empty queue, [13] group-steps blocked/done, [14] cycles in service
+// [12] group-steps idle on an empty queue, [13] group-steps blocked/done, [14] cycles in service, [15] group write-backs in service
 __device__ unsigned long long g_split_prof[16];
 #define SP_ADD(k, v) atomicAdd(&g_split_prof[k], (unsigned long long)(v))
 #endif
@@ -54,11 +62,13 @@ template <> struct Word<4> { using type = uint32_t; };
 template <> struct Word<16> { using type = u32x4; };
 
 // G lanes per block, WB bytes per lane and piece, NS pieces in flight (a piece's global load is issued NS - 1 steps before its
-// bytes are stored); L = the block's LDS layout
-template <class L, uint32_t G, uint32_t WB, uint32_t NS>
+// bytes are stored); L = the block's LDS layout; FB: a visit of service() writes back every live group with less than FB bytes of space
+// (LZ4S_FLUSH_ALL: every group that has a complete 16-byte unit; L::FLUSH_AT: the rule up to round 26)
+constexpr uint32_t LZ4S_FLUSH_ALL = 0xFFFFFFFFu;
+template <class L, uint32_t G, uint32_t WB, uint32_t NS, uint32_t FB = LZ4S_FLUSH_ALL>
 struct Copier {
     static constexpr uint32_t PIECE = G * WB;
-    static_assert((WB == 4u || WB == 16u) && NS >= 2u && NS * PIECE + 64u + 64u <= L::FLUSH_AT && PIECE <= L::OUT_H, "geometry");
+    static_assert((WB == 4u || WB == 16u) && NS >= 2u && NS * PIECE + 64u + 64u <= L::FLUSH_AT && PIECE <= L::OUT_H && FB >= L::FLUSH_AT, "geometry");
     static constexpr uint32_t OUT_CAP = L::OUT_CAP, OUT_H = L::OUT_H, FLUSH_AT = L::FLUSH_AT, TAIL_OFF = L::TAIL_OFF;
     using word_t = typename Word<WB>::type;
     const uint8_t* gin;
@@ -78,7 +88,7 @@ struct Copier {
     uint32_t pf_v, pf_acc;
     uint32_t blocked, done;
 #ifdef LZ4FLEX_PROFILE_PHASES
-    uint32_t pr_piece, pr_idle, pr_blocked;
+    uint32_t pr_piece, pr_idle, pr_blocked, pr_flush;
 #endif
     enum : uint32_t { K_NONE = 0, K_MAINT = 1, K_RARE = R_RARE, K_CAREFUL = R_CAREFUL, K_FINISH = R_FINISH, K_LONG = 8 };
     static constexpr uint32_t LONG_LIT = 1024u, LONG_KEEP = 256u;     // literal runs from LONG_LIT bytes on: all but the last LONG_KEEP (+ < 64) bytes go memory to memory
@@ -116,6 +126,95 @@ struct Copier {
         }
         for (uint32_t p = fnew + g; p < op; p += G) gout[p] = lout[p - L0];
         F = op;
+    }
+    // Write-back and history slide of a visit of service(), for the whole wavefront at once (round 27).  flush_slide() above does the
+    // same for one group, one 16-byte unit per lane and iteration, and every iteration waits for its own LDS read (~130 cycles; up to
+    // 23 + 9 of them at 4 lanes per block); its loops end per group, so that the wavefront runs them under exec masks for as long as
+    // its fullest group needs.  Here every lane of the wavefront calls, the trip counts are the maximum over the groups, taken ONCE
+    // (a loop whose lanes leave at different times makes hipcc treat everything around it as divergent: section 5.2's compiler
+    // lesson), each lane's share is predicated inside, and four LDS reads are in flight before their four stores.  Not inlined, as
+    // wave_bulk_copy: its registers would be the kernel's.
+    //   wb_off, wb_n: the group writes lout[wb_off, wb_off + wb_n) to gdst[0, wb_n) (multiples of 16; wb_n = 0: nothing);
+    //   shift, keep:  then lout[shift, shift + keep) moves down to lout[0, keep) (shift a multiple of 16; keep = 0: nothing).
+    // The slide moves bytes DOWN inside one buffer (dst < src).  A batch reads [shift + i, shift + i + 64 G) of every group and then
+    // writes [i, i + 64 G); the next batch reads from shift + i + 64 G >= i + 64 G, above everything written so far; and a
+    // wavefront's LDS operations execute in the order they were issued.  So no read sees a byte that this slide has written, also
+    // when shift < keep (source and destination overlap).  A lane whose unit lies behind its group's end reads the group's first
+    // bytes (a valid address, the value is dropped) and stores nothing.
+    static __device__ __forceinline__ uint32_t wave_group_max(uint32_t v) {      // v: the same in the G lanes of a group (G = 4 or 8)
+        uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4 (rows of 16 lanes; lanes 0..3 keep v)
+        v = v > t ? v : t;
+        t = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x118, 0xF, 0xF, false);            // row_shr:8: lane 15 of a row has the row's maximum
+        v = v > t ? v : t;
+        const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 31);
+        const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 47), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+        const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
+        return ab > cd ? ab : cd;
+    }
+    static __device__ __attribute__((noinline)) void wave_flush_slide(lds_u8* lout, uint8_t* gdst, uint32_t g, uint32_t wb_off, uint32_t wb_n,
+                                                                      uint32_t shift, uint32_t keep) {
+        static_assert(G == 4u || G == 8u, "wave_group_max");
+        typedef __attribute__((address_space(1))) uint8_t g_u8;      // (named: a pointer that crossed a call is flat)
+        typedef u32x4 __attribute__((aligned(1))) u32x4_u;
+        typedef __attribute__((address_space(1))) u32x4_u g_u32x4_u;
+        typedef u32x4 __attribute__((address_space(3))) l_u32x4;
+        constexpr uint32_t U = 16u * G;                              // a group's bytes per wave instruction; a batch is four of them
+        g_u8* gd = (g_u8*)gdst;
+        const uint32_t idle = 16u * g;
+        const uint32_t wb_max = wave_group_max(wb_n);
+        for (uint32_t base = 0u; base < wb_max; base += 4u * U) {
+            const uint32_t i0 = base + 16u * g, i1 = i0 + U, i2 = i0 + 2u * U, i3 = i0 + 3u * U;
+            const bool p0 = i0 < wb_n, p1 = i1 < wb_n, p2 = i2 < wb_n, p3 = i3 < wb_n;
+            u32x4 v0 = *reinterpret_cast<const l_u32x4*>(lout + (p0 ? wb_off + i0 : idle));
+            u32x4 v1 = *reinterpret_cast<const l_u32x4*>(lout + (p1 ? wb_off + i1 : idle));
+            u32x4 v2 = *reinterpret_cast<const l_u32x4*>(lout + (p2 ? wb_off + i2 : idle));
+            u32x4 v3 = *reinterpret_cast<const l_u32x4*>(lout + (p3 ? wb_off + i3 : idle));
+            asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));      // all four reads are issued in front of the first store
+            if (p0) *reinterpret_cast<g_u32x4_u*>(gd + i0) = v0;
+            if (p1) *reinterpret_cast<g_u32x4_u*>(gd + i1) = v1;
+            if (p2) *reinterpret_cast<g_u32x4_u*>(gd + i2) = v2;
+            if (p3) *reinterpret_cast<g_u32x4_u*>(gd + i3) = v3;
+        }
+        const uint32_t keep_max = wave_group_max(keep);
+        for (uint32_t base = 0u; base < keep_max; base += 4u * U) {
+            const uint32_t i0 = base + 16u * g, i1 = i0 + U, i2 = i0 + 2u * U, i3 = i0 + 3u * U;
+            const bool p0 = i0 < keep, p1 = i1 < keep, p2 = i2 < keep, p3 = i3 < keep;
+            u32x4 v0 = *reinterpret_cast<const l_u32x4*>(lout + (p0 ? shift + i0 : idle));
+            u32x4 v1 = *reinterpret_cast<const l_u32x4*>(lout + (p1 ? shift + i1 : idle));
+            u32x4 v2 = *reinterpret_cast<const l_u32x4*>(lout + (p2 ? shift + i2 : idle));
+            u32x4 v3 = *reinterpret_cast<const l_u32x4*>(lout + (p3 ? shift + i3 : idle));
+            asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));      // all four reads are issued in front of the first store
+            if (p0) *reinterpret_cast<l_u32x4*>(lout + i0) = v0;
+            if (p1) *reinterpret_cast<l_u32x4*>(lout + i1) = v1;
+            if (p2) *reinterpret_cast<l_u32x4*>(lout + i2) = v2;
+            if (p3) *reinterpret_cast<l_u32x4*>(lout + i3) = v3;
+        }
+    }
+    // One visit serves the whole wavefront: every lane calls this; a group that is not done and has a complete 16-byte unit to write
+    // back (and less than FB bytes of space: by default every such group) writes back and slides, so that the wavefront's sixteen
+    // groups come back for the next visit together and not in two or three clusters.  What holds before and after, whatever FB is:
+    //   * no piece is in flight (run() drains its NS - 1 slots in front of service());
+    //   * L0 and F stay multiples of 16 (F = op & ~15, L0 = F - OUT_H);
+    //   * F >= L0 + OUT_H once L0 > 0 (F only grows between slides), so a far-match load, which starts below L0, reads written-back
+    //     bytes only: msrc + PIECE <= L0 + PIECE - 1 < L0 + OUT_H <= F;
+    //   * op - L0 >= min(op, OUT_H) after a slide (L0 = F - OUT_H <= op - OUT_H, or L0 = 0): near matches and the periodic path
+    //     find their history in LDS;
+    //   * nothing is written to gout at or beyond op & ~15: the last bytes are final_flush()'s;
+    //   * the generic paths (K_RARE, K_CAREFUL, K_FINISH) and bulk_literals (K_LONG) see the state flush_slide() leaves -- this is
+    //     flush_slide()'s arithmetic -- and go on calling flush_slide() / final_flush() themselves;
+    //   * a group that is done (finished, failed -- the parser ends a failed block with an R_FINISH record -- or without a block)
+    //     neither writes back nor slides: its wb_n and keep are 0.
+    __device__ __forceinline__ void wave_flush(bool live) {
+        const uint32_t fnew = op & ~15u;
+        const bool fl = live && fnew > F && (FB == LZ4S_FLUSH_ALL || out_space() < FB);
+        const uint32_t l0n = fnew > OUT_H ? fnew - OUT_H : 0u;      // multiple of 16
+        const bool sl = fl && l0n > L0;
+        wave_flush_slide(lout, gout + F, g, F - L0, fl ? fnew - F : 0u, sl ? l0n - L0 : 0u, sl ? op - l0n : 0u);
+        F = fl ? fnew : F;
+        L0 = sl ? l0n : L0;
+#ifdef LZ4FLEX_PROFILE_PHASES
+        pr_flush += fl;
+#endif
     }
     // A long literal run (incompressible data: a 64 KiB block is ONE run; round 3: 3.2 ms per GiB through 64-byte pieces and the LDS
     // buffer) goes memory to memory, 16 bytes per lane and four loads in flight, up to LONG_KEEP bytes before its end; the rest -- the end
@@ -320,8 +419,8 @@ struct Copier {
             const bool want = done == 0u && lit_rem >= LONG_LIT && (blocked == K_LONG || blocked == K_CAREFUL || blocked == K_FINISH);
             if (__any(want)) bulk_literals(want);              // (the whole wavefront: see wave_bulk_copy)
         }
+        wave_flush(done == 0u);                                // (the whole wavefront: see wave_flush_slide)
         if (done) return;
-        if (out_space() < FLUSH_AT) flush_slide();
         if (blocked == K_RARE) {   // a periodic match; the record's literals (if any) go first
             generic_literals(lit_src, lit_rem);
             lit_rem = 0u;
@@ -337,7 +436,7 @@ struct Copier {
     __device__ __forceinline__ void run() {
         Slot sl[NS];
 #ifdef LZ4FLEX_PROFILE_PHASES
-        pr_piece = pr_idle = pr_blocked = 0u;
+        pr_piece = pr_idle = pr_blocked = pr_flush = 0u;
         const unsigned long long t_begin = __builtin_readcyclecounter();
         unsigned long long t_service = 0ull;
         uint32_t iters = 0u, services = 0u;
@@ -374,7 +473,7 @@ struct Copier {
         if (g == 0u && head != head_pub) q.set_head(head);
         if (pf_acc + pf_v == 0x9E3779B9u && ilen == 0xFFFFFFFFu) gout[0] = 1;   // keeps the touch loads alive; never true
 #ifdef LZ4FLEX_PROFILE_PHASES
-        if (g == 0u) { SP_ADD(11, pr_piece); SP_ADD(12, pr_idle); SP_ADD(13, pr_blocked); }
+        if (g == 0u) { SP_ADD(11, pr_piece); SP_ADD(12, pr_idle); SP_ADD(13, pr_blocked); SP_ADD(15, pr_flush); }
         if (threadIdx.x % 64u == 0u) {
             SP_ADD(8, __builtin_readcyclecounter() - t_begin); SP_ADD(9, iters); SP_ADD(10, services); SP_ADD(14, t_service);
         }
@@ -396,6 +495,11 @@ struct Copier {
 // and 5, 6, 7 end at once; with two, wavefronts 0, 1 of four.
 #ifndef LZ4S_ISO_WAVES
 #define LZ4S_ISO_WAVES 12
+#endif
+// The copiers' write-back threshold (Copier's FB) in every instantiation of the kernel: all groups at every visit, or -DLZ4S_FLUSH_BELOW=<bytes of space>
+// for a timing build (712 = the rule up to round 26; profiles/r27_split_visits.txt has 712, 1080 and all side by side).
+#ifndef LZ4S_FLUSH_BELOW
+#define LZ4S_FLUSH_BELOW 0xFFFFFFFFu
 #endif
 template <uint32_t CW, uint32_t G> constexpr bool split_iso() { return G == 8u && CW == 8u && LZ4S_ISO_WAVES != 0; }
 template <uint32_t CW, uint32_t G> constexpr uint32_t split_waves() {
@@ -439,7 +543,7 @@ __global__ void __launch_bounds__((64 * split_waves<NB * G / 64, G>())) lz4_deco
         const uint32_t j = wave * (64u / G) + lane / G;
         const uint32_t b = first + j;
         const bool valid = b < a.n;
-        Copier<L, G, WB, NS> c;
+        Copier<L, G, WB, NS, LZ4S_FLUSH_BELOW> c;
         constexpr uint32_t BLK_LDS = L::BLK_LDS, TAIL_OFF = L::TAIL_OFF;
         c.g = lane % G;
         c.lout = lds + j * BLK_LDS;
@@ -456,7 +560,7 @@ __global__ void __launch_bounds__((64 * split_waves<NB * G / 64, G>())) lz4_deco
         c.gin_ld = c.ilen >= WB ? c.gin : g_pad;
         c.ilen_w = c.ilen >= WB ? c.ilen - WB : 0u;
         c.gout_ld = (valid && a.out_cap[b] >= WB) ? c.gout : g_pad;
-        c.blocked = Copier<L, G, WB, NS>::K_NONE;
+        c.blocked = Copier<L, G, WB, NS, LZ4S_FLUSH_BELOW>::K_NONE;
         c.done = valid ? 0u : 1u;
         __syncthreads();
         c.run();

@@ -148,6 +148,12 @@ def main():
                   "group-steps piece %d idle %d blocked %d" %
                   (v[0] / pw, v[1] / pw, v[0] / max(v[1], 1), v[2], 100.0 * v[3] / max(v[2], 1), 100.0 * v[4] / max(v[2], 1), 100.0 * v[5] / max(v[2], 1), v[6],
                    v[8] / pw, v[9] / pw, v[10] / pw, v[14] / pw, v[11], v[12], v[13]), flush=True)
+            # per copier wavefront (four per workgroup at 64 blocks per workgroup): how often it leaves its hot loop and what a visit costs
+            nw = 4 * pw
+            print("  visits: raw [8] %d [9] %d [10] %d [14] %d [15] %d [2] %d [3] %d | per copier wavefront (= per 64 KiB of a block's output): %.1f visits, "
+                  "%.0f cycles per visit, service %.2f%% of the wavefront's %.0f cycles, %.1f group write-backs per visit, %.0f wave steps" %
+                  (v[8], v[9], v[10], v[14], v[15], v[2], v[3], v[10] / nw, v[14] / max(v[10], 1), 100.0 * v[14] / max(v[8], 1), v[8] / nw,
+                   v[15] / max(v[10], 1), 4.0 * v[9] / nw), flush=True)
         if variant == 13 and hasattr(lib, "lz4flex_debug_seq_prof"):
             lib.lz4flex_debug_seq_prof.argtypes = [C.c_void_p, C.c_int]
             v = (C.c_ulonglong * 32)()

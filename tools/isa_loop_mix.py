@@ -38,7 +38,7 @@ def main():
             continue
         if kern is None:
             continue
-        if "s_endpgm" in l:
+        if l.startswith(".Lfunc_end"):          # (not s_endpgm: a kernel whose padding wavefronts end early has one in front of its loops)
             kern = None
             continue
         if l.startswith(".L") or l.startswith("; %bb"):
