@@ -73,9 +73,6 @@ static std::vector<const lz4flex_dict_set*> g_live_sets;
 static constexpr uint32_t DICT_SET_MAX = 1024u;
 static constexpr uint32_t DICT_KEEP = 65536u;
 
-// compress_variant -> launch_compress mode bits: 1 = encode_block + emitter wave (default), 3 = encode_block alone
-static inline int comp_mode_bits(int v) { return v == 1 ? 0x600 : 0; }
-
 // tools builds (-DLZ4FLEX_TOOLS) hold the plan / replay and the fused decoder.  plan_fits: BlockPlan's word indices are 32-bit,
 // a batch whose plans they cannot address is not the plan / replay decoder's
 #ifdef LZ4FLEX_TOOLS
@@ -245,10 +242,10 @@ static int compress_throughput(lz4flex_ctx* c, const CompressArgs& a, const Dict
 // mode 1: the reference-exact encoder (lz4_compress.hip launch_compress_exact).  A call with dictionaries builds its chain records in
 // the (otherwise idle) throughput encoder's workspace: no allocation, ordered across streams like that encoder's own launches
 static int compress_exact(lz4flex_ctx* c, const CompressArgs& a, const DictSource& d, bool big, hipStream_t s) {
-    const int enc_bits = c->comp_lanes | (big ? 0x100 : 0) | comp_mode_bits(c->comp_variant);
-    if (!((a.dict_len || d.shared || d.has_set) && a.n)) return launched(launch_compress_exact(a, d, enc_bits, big, nullptr, 0, 0, s));
+    const bool emitter = c->comp_variant == 1;     // "compress_variant": 1 = encode_block + emitter wavefront (default), 3 = encode_block alone
+    if (!((a.dict_len || d.shared || d.has_set) && a.n)) return launched(launch_compress_exact(a, d, c->comp_lanes, big, emitter, nullptr, 0, 0, s));
     if (const int rc = wave_ws_acquire(c, s)) return rc;
-    const hipError_t le = launch_compress_exact(a, d, enc_bits, big, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs),
+    const hipError_t le = launch_compress_exact(a, d, c->comp_lanes, big, emitter, c->wave_ws, compress_wave_workspace_bytes(c->wave_wgs),
                                                 (uint32_t)c->exact_dict_piece, s);
     const hipError_t re = c->wave.release(s);                 // (also behind a failed launch: whatever was enqueued on the workspace is ordered)
     return launched(le == hipSuccess ? re : le);

@@ -23,30 +23,29 @@
 //     clamped address and as early as its address is known.
 //   * the encoder wavefront issues no stores: sequences go through an LDS queue to the EMITTER wavefront of the
 //     workgroup, which writes tokens, literals, offsets, the block's length and status, and prefetches the
-//     input stream ahead of the encoders (see EmitQ / emitter_wave / the MODE list below).
+//     input stream ahead of the encoders (see EmitQ / emitter_wave / the two MODEs at the kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "lz4_device.h"
+#include "lz4_wave_prims.h"
 
 namespace lz4flex_dev {
 
-// Phase timing (tools/phase_profile.py builds a private copy with -DLZ4FLEX_PROFILE_PHASES; the shipped
-// library has none of it): wave-level s_memtime deltas accumulated per code region.
+// Phase timing (a variant build with -DLZ4FLEX_PROFILE_PHASES; the shipped library has none of it): wave-level
+// s_memtime deltas accumulated per code region, read back with lz4flex_debug_phase.
 #ifdef LZ4FLEX_PROFILE_PHASES
 __device__ unsigned long long g_phase_cycles[8];
 __device__ unsigned long long g_phase_counts[8];
 #define PHASE_DECL unsigned long long _pt = __builtin_readcyclecounter(); unsigned long long _pacc[8] = {0,0,0,0,0,0,0,0}; unsigned _pcnt[8] = {0,0,0,0,0,0,0,0};
 #define PHASE_MARK(k) { const unsigned long long _n = __builtin_readcyclecounter(); _pacc[k] += _n - _pt; _pcnt[k]++; _pt = _n; }
-#define PHASE_COUNT(k) _pcnt[k]++;
 #define PHASE_WAIT_VM asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #define PHASE_FLUSH if (threadIdx.x == 0) { for (int _k = 0; _k < 8; ++_k) { atomicAdd(&g_phase_cycles[_k], _pacc[_k]); atomicAdd(&g_phase_counts[_k], (unsigned long long)_pcnt[_k]); } }
 #else
 #define PHASE_DECL
 #define PHASE_MARK(k)
-#define PHASE_COUNT(k)
 #define PHASE_WAIT_VM
 #define PHASE_FLUSH
 #endif
@@ -169,14 +168,10 @@ __device__ __forceinline__ uint32_t emit_literals(uint8_t* out, uint32_t o, cons
     return o + lit_len;
 }
 
-// LDS-typed views: a generic pointer would make every access a FLAT instruction, which is as slow as a global one
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
-typedef uint32_t __attribute__((address_space(3), aligned(1))) lds_u32_unaligned;
-typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-typedef u32x4 __attribute__((address_space(3))) lds_u128;
+// LDS-typed views (lds_u8, u32x4: lz4_wave_prims.h): a generic pointer would make every access a FLAT instruction, which is as
+// slow as a global one
 typedef volatile u32x4 __attribute__((address_space(3))) lds_vu128;
 typedef volatile uint32_t __attribute__((address_space(3))) lds_vu32;
-typedef volatile uint64_t __attribute__((address_space(3))) lds_vu64;
 
 // Sequence queue between the encoder wave and the emitter wave of a workgroup (one per block, in LDS).
 // The encoder's chain is probe -> verify -> extend -> next probe; writing the sequence out (token, literals,
@@ -210,45 +205,15 @@ struct EmitQ {                       // LDS layout per block: 16 records of 16 B
     }
 };
 #define LZ4_EQ_BYTES (16u * LZ4_EQ_DEPTH + 16u)
-// MODE 4 adds, behind the queue, an LDS ring of the block's input around the encoder's position, written by the
-// emitter wave (which then doubles as the "filler"): {lo, hi} (8 B, + 8 B pad) and RING + RING_PAD bytes.
-#define LZ4_RG_SIZE 1024u       // ring bytes per block (power of two)
-#define LZ4_RG_PAD 16u          // mirror of ring bytes [0,16): unaligned reads across the wrap
-#define LZ4_RG_HIST 64u         // bytes kept behind the encoder's first probe
-#define LZ4_RG_CHUNK 128u       // filler granularity: 8 lanes x 16 B
-#define LZ4_EQ_BYTES_RING (LZ4_EQ_BYTES + 16u + LZ4_RG_SIZE + LZ4_RG_PAD)
-struct InRing {                      // encoder-side view
-    lds_u8* ctl;                     // {lo, hi}
-    lds_u8* ring;
-    __device__ __forceinline__ uint64_t window() const { return *reinterpret_cast<lds_vu64*>(ctl); }
-    __device__ __forceinline__ void set_window(uint32_t lo, uint32_t hi) const {
-        *reinterpret_cast<lds_vu64*>(ctl) = (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    // 8 bytes at any byte position: three ALIGNED dwords + two byte-funnel shifts (a misaligned ds_read stalls
-    // the LDS pipe for much longer than that; the mirror pad keeps the third dword inside the allocation)
-    __device__ __forceinline__ uint64_t ld64(uint32_t pos) const {
-        const uint32_t o = pos & (LZ4_RG_SIZE - 1u);
-        typedef uint32_t __attribute__((address_space(3))) lds_u32a;
-        lds_u32a* a = reinterpret_cast<lds_u32a*>(ring + (o & ~3u));
-        const uint32_t d0 = a[0], d1 = a[1], d2 = a[2];
-        const uint32_t sh = o & 3u;
-        const uint32_t v0 = __builtin_amdgcn_alignbyte(d1, d0, sh);
-        const uint32_t v1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-        return (uint64_t)v0 | ((uint64_t)v1 << 32);
-    }
-    __device__ __forceinline__ uint32_t ld8(uint32_t pos) const { return ring[pos & (LZ4_RG_SIZE - 1u)]; }
-};
-__device__ __forceinline__ InRing in_ring_of(const EmitQ& q) { return InRing{q.p + LZ4_EQ_BYTES, q.p + LZ4_EQ_BYTES + 16u}; }
 
 // HM: hash selection known at compile time (0: 4-byte hash, 1: 5-byte hash) or per block at run time (2)
 // EQ: sequences are pushed to the block's EmitQ (an emitter wave writes the output and the block's status)
 // instead of being written here; the return value is then LZ4FLEX_DEV_QUEUED unless the block was handled inline.
 #define LZ4FLEX_DEV_QUEUED 0x7FFFFFFF
-// RG (with EQ): current-side bytes come from the block's LDS input ring whenever the whole wave's reads are covered
-template <int G, typename TblT, int HM, bool EQ, bool RG>
+template <int G, typename TblT, int HM, bool EQ>
 __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, uint32_t n, uint8_t* __restrict__ out,
                                                 uint32_t cap, uint32_t flags, TblT* tbl, const Grp<G> grp,
-                                                uint32_t* produced, volatile uint32_t* progress, const EmitQ eq) {
+                                                uint32_t* produced, const EmitQ eq) {
     const uint32_t g = grp.g;
     if ((uint64_t)cap < max_output_size(n)) {   // compress.rs:338-340
         if (EQ && g == 0u) eq.set_head(LZ4_EQ_SELF);
@@ -262,8 +227,6 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
         return 0;
     }
     uint32_t q_head = 0u, q_tail = 0u;   // q_tail: last value read of the emitter's tail (it only grows)
-    const InRing rg = in_ring_of(eq);
-    uint32_t rg_lo = 0u, rg_hi = 0u;     // last window read from the filler (the real one only moves forward)
     const bool frame_tbl = (flags & 2u) != 0u;        // FrameEncoder: HashTable4K + hash5 always
     const bool continuation = (flags & 1u) != 0u;     // table holds only unreachable entries; pos 0 is probed
     const bool use_h5 = HM == 2 ? (frame_tbl || n >= 65535u) : (HM == 1);   // compress.rs:559-566
@@ -294,21 +257,6 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
     uint64_t x0 = 0ull;   // probe bytes of the FIRST batch of the current sequence: lanes 0 and 7 hold its first 15 literals
     uint32_t x0_base = 0xFFFFFFFFu;   // position lane 0's x0 was read from
     for (;;) {
-        // ------------------------------------------------------------------ may this step read the ring?  (wave-uniform)
-        bool fast = false;
-        if (RG) {
-            const uint32_t pfirst = probe_pos(base, i0);
-            if (g == 0u) eq.set_prog(pfirst);
-            // consecutive probe positions (i < 32) and every current-side read of the step inside [lo, hi)
-            bool ok = i0 + G <= 32u && pfirst + (10u * G + 16u) <= rg_hi && (rg_lo == 0u || rg_lo + 8u <= pfirst);
-            if (!__all(ok)) {
-                const uint64_t snap = rg.window();
-                rg_lo = (uint32_t)snap; rg_hi = (uint32_t)(snap >> 32);
-                ok = i0 + G <= 32u && pfirst + (10u * G + 16u) <= rg_hi && (rg_lo == 0u || rg_lo + 8u <= pfirst);
-            }
-            fast = __all(ok);
-            if (fast) { PHASE_COUNT(5) }
-        }
         // ------------------------------------------------------------------ probe batch
         if (i0 == 0u) { x0 = x; x0_base = base; }
         const uint32_t i = i0 + g;
@@ -359,8 +307,7 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
             if (vm != (((G == 32) ? 0xFFFFFFFFu : ((1u << G) - 1u)))) break;   // ran past end_check: last literals
             i0 += G;
             const uint32_t pn = probe_pos(base, i0 + g);
-            if (RG && fast && i0 + G <= 32u && __all(probe_pos(base, i0) + G + 8u <= rg_hi)) x = rg.ld64(pn);
-            else x = cld64(in + (pn <= end_check ? pn : 0u));
+            x = cld64(in + (pn <= end_check ? pn : 0u));
             continue;
         }
         uint32_t cur = grp.bcast_u(p, last);
@@ -374,15 +321,8 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
         const bool bk_ok0 = (cnd > g) && (cur > lit_start + g);
         const uint32_t fa = m4 + 8u * g, fb = c4 + 8u * g;
         const bool f8 = fa + 8u <= limit;                                     // a full 8-byte forward chunk
-        uint32_t bka;
-        uint64_t fwa;
-        if (RG && fast) {                     // current side from the ring (lanes with nothing to read re-read cur)
-            bka = rg.ld8(bk_ok0 ? cur - 1u - g : cur);
-            fwa = rg.ld64(f8 ? fa : cur);
-        } else {
-            bka = in[bk_ok0 ? cur - 1u - g : 0u];
-            fwa = cld64(in + (f8 ? fa : 0u));
-        }
+        const uint32_t bka = in[bk_ok0 ? cur - 1u - g : 0u];
+        const uint64_t fwa = cld64(in + (f8 ? fa : 0u));
         const uint32_t bkb = in[bk_ok0 ? cnd - 1u - g : 0u];
         const uint64_t fdiff = fwa ^ cld64(in + (f8 ? fb : 0u));
         uint32_t c = 0u;                      // equal bytes seen by this lane in the first forward round (0..8)
@@ -429,17 +369,9 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
         // ------------------------------------------------------------------ requests for the NEXT step: the bytes of
         // the cur-2 table update (compress.rs:460-461) and of the first probe batch after this match
         const uint32_t q = cur_end - 2u;
-        uint64_t qx, xn;                                                      // q + 8 <= n: matches end >= 6 bytes early
-        {
-            const bool pv = cur_end + g <= end_check;
-            if (RG && fast && __all(cur_end + G + 8u <= rg_hi)) {
-                qx = rg.ld64(q);
-                xn = rg.ld64(pv ? cur_end + g : q);
-            } else {
-                qx = cld64(in + q);
-                xn = cld64(in + (pv ? cur_end + g : 0u));
-            }
-        }
+        const bool pv = cur_end + g <= end_check;
+        const uint64_t qx = cld64(in + q);                                    // q + 8 <= n: matches end >= 6 bytes early
+        const uint64_t xn = cld64(in + (pv ? cur_end + g : 0u));
         // ---- backtrack (compress.rs:442-448), off the critical path: the next step only needs cur_end
         {
             uint32_t nb = (uint32_t)__builtin_ctz(~okm);                      // G..31 bits are 0 in okm => nb <= G
@@ -463,7 +395,7 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
             if (g == 0u) {
                 eq.put(q_head, lit_start, lit_len, offset, dl);
                 eq.set_head(q_head + 1u);
-                if (!RG) eq.set_prog(cur_end);
+                eq.set_prog(cur_end);
             }
             q_head += 1u;
         } else {
@@ -509,7 +441,6 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
         lit_start = cur_end;                                                  // compress.rs:487
         base = cur_end;
         i0 = 0u;
-        if (progress && g == 0u) *progress = cur_end;
         x = xn;
     }
     // handle_last_literals, compress.rs:237-247
@@ -534,17 +465,16 @@ __device__ __forceinline__ int32_t encode_block(const uint8_t* __restrict__ in, 
 
 // The emitter wave: lane group j pops block j's sequence records and writes the compressed block
 // (compress.rs:463-486, :237-247), then the block's length and status.  It also walks ahead of the encoder
-// touching the input lines it is about to read (see MODE 2 below).
-template <int G, bool RG>
+// touching the input lines it is about to read, so that the encoders' current-side loads hit L2 instead of paying the
+// first-touch HBM latency inside their serial chain (an in-order vmcnt makes self-prefetching useless: a load behind a
+// missing prefetch waits for it).
+template <int G>
 __device__ __forceinline__ void emitter_wave(const CompressArgs& a, uint32_t b, bool live, const EmitQ eq, const Grp<G> grp) {
     const uint32_t g = grp.g;
     const uint8_t* in = a.in_base + (live ? a.in_off[b] : 0ull);
     uint8_t* out = a.out_base + (live ? a.out_off[b] : 0ull);
     const uint32_t n = live ? a.in_len[b] : 0u;
     uint32_t o = 0u, tail = 0u, pf = 0u, acc = 0u;
-    const InRing rg = in_ring_of(eq);
-    const uint32_t n_fill = n & ~(LZ4_RG_CHUNK - 1u);   // whole chunks only; the encoder reads the tail from memory
-    uint32_t rlo = 0u, rhi = 0u;                       // the ring holds input positions [rlo, rhi)
     bool done = !live;
     for (;;) {
         if (!__any(!done)) break;
@@ -577,45 +507,13 @@ __device__ __forceinline__ void emitter_wave(const CompressArgs& a, uint32_t b, 
                 if (g == 0u) eq.set_tail(tail);
                 worked = true;
             }
+            // stream prefetch: keep the lines [pos, pos + LZ4_PF_AHEAD) of the input on their way into L2
             const uint32_t pos = eq.prog();
-            if (!RG) {
-                // stream prefetch: keep the lines [pos, pos + LZ4_PF_AHEAD) of the input on their way into L2
-                if (pf < pos) pf = pos & ~127u;
-                if (!done && pf + 128u * G < pos + LZ4_PF_AHEAD) {
-                    const uint32_t at = pf + 128u * g;
-                    if (at + 4u <= n) acc += *reinterpret_cast<const volatile uint32_t*>(in + (at & ~3u));
-                    pf += 128u * G;
-                }
-            }
-        }
-        if (RG) {
-            // ---- input ring: one 128-byte chunk per block and iteration, lanes 0..7 of the group 16 B each.
-            // The chunk [rhi, rhi+128) may overwrite ring positions below prog - HIST only; {lo, hi} are published
-            // after the data (a wave's LDS operations execute in order).
-            bool fill = false;
-            if (!done) {
-                const uint32_t pos = eq.prog();
-                if (pos >= rhi) {   // the ring is behind the encoder (start, long match): restart it around pos
-                    const uint32_t back = pos < LZ4_RG_HIST ? pos : LZ4_RG_HIST;
-                    rlo = rhi = (pos - back) & ~(LZ4_RG_CHUNK - 1u);
-                }
-                fill = rhi + LZ4_RG_CHUNK <= n_fill && rhi + LZ4_RG_CHUNK + LZ4_RG_HIST <= pos + LZ4_RG_SIZE;
-            }
-            if (__any(fill)) {
-                const bool mine = fill && g < 8u;
-                u32x4 v = {0u, 0u, 0u, 0u};
-                __builtin_memcpy(&v, in + (mine ? rhi + 16u * g : 0u), 16);
-                if (mine) {
-                    const uint32_t ro = (rhi + 16u * g) & (LZ4_RG_SIZE - 1u);
-                    *reinterpret_cast<lds_u128*>(rg.ring + ro) = v;
-                    if (ro == 0u) *reinterpret_cast<lds_u128*>(rg.ring + LZ4_RG_SIZE) = v;
-                }
-                if (fill) {
-                    rhi += LZ4_RG_CHUNK;
-                    if (rhi - rlo > LZ4_RG_SIZE) rlo = rhi - LZ4_RG_SIZE;
-                    if (g == 0u) rg.set_window(rlo, rhi);
-                    worked = true;
-                }
+            if (pf < pos) pf = pos & ~127u;
+            if (!done && pf + 128u * G < pos + LZ4_PF_AHEAD) {
+                const uint32_t at = pf + 128u * g;
+                if (at + 4u <= n) acc += *reinterpret_cast<const volatile uint32_t*>(in + (at & ~3u));
+                pf += 128u * G;
             }
         }
         if (!__any(worked)) __builtin_amdgcn_s_sleep(LZ4_EM_SLEEP);
@@ -840,14 +738,14 @@ __global__ void lz4flex_dict_chain_records_kernel(const CompressArgs a, const Di
     if (not_plain) not_plain[i] = (refuse || chain) ? 1u : 0u;
 }
 
-hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int enc_bits, bool big, void* ws, size_t ws_bytes,
-                                 uint32_t max_piece, hipStream_t s) {
+hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int lanes, bool big, bool emitter, void* ws,
+                                 size_t ws_bytes, uint32_t max_piece, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
     const bool set = d.has_set != 0u, shared = !set && d.shared != nullptr;
     // blocks without a dictionary: the block encoder, which leaves the others alone, and the long-block flag.  Per-block dictionaries:
     // dict_len says which those are, for the whole batch at once; a shared dictionary: none; a set: piece by piece, below
     const auto plain = [&](const CompressArgs& p) {
-        hipError_t e = launch_compress(p, enc_bits, s);
+        hipError_t e = launch_compress(p, lanes, big, emitter, s);
         if (e == hipSuccess && !big) {
             hipLaunchKernelGGL(lz4flex_flag_long_blocks_kernel, dim3((p.n + 255u) / 256u), dim3(256), 0, s, p.in_len, p.n, p.out_len, p.status, p.dict_len);
             e = hipGetLastError();
@@ -883,27 +781,23 @@ hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int
     return e;
 }
 
-// MODE 0: the encoder wavefront alone (everything read from HBM/L2, output written inline).
-// MODE 2: plus a second wavefront per workgroup that only walks ahead of the encoders and touches the input
-//         lines they are about to need, so that the encoders' current-side loads hit L2 instead of paying the
-//         first-touch HBM latency inside their serial chain (an in-order vmcnt makes self-prefetching useless:
-//         a load behind a missing prefetch waits for it).
-// MODE 3: (default) the second wavefront is the EMITTER: it pops the sequence records the encoders push into
-//         their LDS queues, writes the compressed blocks and their status, and does MODE 2's prefetch.
-// MODE 4: MODE 3 + the emitter also copies the input into an LDS ring per block that serves the encoders'
-//         current-side reads (experiment; measured slower than MODE 3).
+// MODE 3: the product.  A workgroup is the ENCODER wavefront and the EMITTER wavefront: the emitter pops the sequence records the
+//         encoders push into their LDS queues, writes the compressed blocks and their status, and prefetches the input ahead of
+//         the encoders (emitter_wave).
+// MODE 0: the encoder wavefront alone (everything read from HBM/L2, output written inline): the cross-check of
+//         -DLZ4FLEX_ALL_VARIANTS builds ("compress_variant" 3).
+// (MODE 2, a second wavefront that only prefetched, and MODE 4, MODE 3 + an LDS ring of the input filled by the emitter, measured
+// slower than MODE 3 and are gone: DESIGN.md section 5.3.)
 // BPW = blocks per workgroup = 64 / G.  With u16 tables a CU's 160 KiB of LDS hold two workgroups of eight
 // blocks.  (Measured with smaller workgroups: four workgroups of five blocks = 20 tables do fit, five of four
 // do not, and 16 384 blocks need 4 rounds either way; half-filled waves of four blocks are as fast as full ones.)
 template <int G, typename TblT, int MODE, int BPW>
 __global__ void __launch_bounds__(MODE == 0 ? 64 : 128) lz4_compress_blocks_kernel(CompressArgs a) {
-    constexpr bool EQ = MODE == 3 || MODE == 4;
-    constexpr bool RG = MODE == 4;
-    constexpr uint32_t EQB = RG ? LZ4_EQ_BYTES_RING : LZ4_EQ_BYTES;
+    static_assert(MODE == 0 || MODE == 3, "the encoder wavefront alone, or with the emitter wavefront");
+    constexpr bool EQ = MODE == 3;
     extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
     TblT* tables = reinterpret_cast<TblT*>(dyn_lds);                                        // [BPW][4096]
-    uint8_t* rings = dyn_lds + (size_t)BPW * 4096u * sizeof(TblT);                          // per-block side structures (MODE 2..4)
-    uint32_t* progress = reinterpret_cast<uint32_t*>(rings);                                // [BPW] (MODE 2)
+    uint8_t* queues = dyn_lds + (size_t)BPW * 4096u * sizeof(TblT);                         // [BPW] EmitQ (MODE 3)
     const uint32_t lane = threadIdx.x & 63u;
     Grp<G> grp;
     grp.g = lane % G;
@@ -913,51 +807,20 @@ __global__ void __launch_bounds__(MODE == 0 ? 64 : 128) lz4_compress_blocks_kern
     // a block with a dictionary (lz4flex_compress_batch_ex) is the chain kernel's: here it is treated as a slot behind the batch's end
     const bool dict_blk = a.dict_len != nullptr && j < BPW && b < a.n && a.dict_len[b] != 0u;
     if (EQ) {
-        // sequence queues (+ input rings, MODE 4) behind the tables; the second wave is the emitter
+        // sequence queues behind the tables; the second wave is the emitter
         if (threadIdx.x < BPW) {
-            const EmitQ q0{(lds_u8*)(rings + (size_t)threadIdx.x * EQB)};
+            const EmitQ q0{(lds_u8*)(queues + (size_t)threadIdx.x * LZ4_EQ_BYTES)};
             q0.set_head(0u); q0.set_tail(0u); q0.set_prog(0u);
-            if (RG) in_ring_of(q0).set_window(0u, 0u);
         }
         __syncthreads();
         if (threadIdx.x >= 64u) {
             const bool live = j < BPW && b < a.n && !dict_blk;
-            emitter_wave<G, RG>(a, b, live, EmitQ{(lds_u8*)(rings + (size_t)(live ? j : 0u) * EQB)}, grp);
-            return;
-        }
-    }
-    if (MODE == 2) {
-        if (threadIdx.x < BPW) progress[threadIdx.x] = 0u;
-        __syncthreads();
-        if (threadIdx.x >= 64u) {
-            // ---- the prefetch wave: lane group j follows block j
-            const bool live = j < BPW && b < a.n;
-            const uint32_t n = live ? a.in_len[b] : 0u;
-            const uint8_t* in = a.in_base + (live ? a.in_off[b] : 0ull);
-            uint32_t pf = 0u, acc = 0u;
-            for (;;) {
-                const uint32_t pos = live ? *reinterpret_cast<volatile uint32_t*>(&progress[j]) : 0xFFFFFFFFu;
-                const bool done = pos == 0xFFFFFFFFu;
-                if (!__any(!done)) break;
-                if (!done) {
-                    if (pf < pos) pf = pos & ~127u;
-                    if (pf < pos + LZ4_PF_AHEAD - 128u * G) {
-                        const uint32_t at = pf + 128u * grp.g;
-                        if (at + 4u <= n) acc += *reinterpret_cast<const volatile uint32_t*>(in + (at & ~3u));
-                        pf += 128u * G;
-                    }
-                }
-                __builtin_amdgcn_s_sleep(64);
-            }
-            if (acc == 0x9E3779B9u && live) progress[j] = acc;   // keeps the loads alive
+            emitter_wave<G>(a, b, live, EmitQ{(lds_u8*)(queues + (size_t)(live ? j : 0u) * LZ4_EQ_BYTES)}, grp);
             return;
         }
     }
     if (j >= BPW) return;
-    if (b >= a.n || dict_blk) {
-        if (MODE == 2 && grp.g == 0u) progress[j] = 0xFFFFFFFFu;
-        return;
-    }
+    if (b >= a.n || dict_blk) return;
     const uint32_t n = a.in_len[b];
     const uint32_t flags = a.flags ? a.flags[b] : 0u;
     uint32_t produced = 0u;
@@ -969,13 +832,11 @@ __global__ void __launch_bounds__(MODE == 0 ? 64 : 128) lz4_compress_blocks_kern
         const uint8_t* in = a.in_base + a.in_off[b];
         uint8_t* out = a.out_base + a.out_off[b];
         TblT* tbl = tables + (size_t)j * 4096u;
-        volatile uint32_t* pg = MODE == 2 ? &progress[j] : nullptr;
-        const EmitQ eq{(lds_u8*)(rings + (size_t)(EQ ? j : 0u) * EQB)};
-        if (__all(h5)) st = encode_block<G, TblT, 1, EQ, RG>(in, n, out, a.out_cap[b], flags, tbl, grp, &produced, pg, eq);
-        else if (__all(!h5)) st = encode_block<G, TblT, 0, EQ, RG>(in, n, out, a.out_cap[b], flags, tbl, grp, &produced, pg, eq);
-        else st = encode_block<G, TblT, 2, EQ, RG>(in, n, out, a.out_cap[b], flags, tbl, grp, &produced, pg, eq);
+        const EmitQ eq{(lds_u8*)(queues + (size_t)(EQ ? j : 0u) * LZ4_EQ_BYTES)};
+        if (__all(h5)) st = encode_block<G, TblT, 1, EQ>(in, n, out, a.out_cap[b], flags, tbl, grp, &produced, eq);
+        else if (__all(!h5)) st = encode_block<G, TblT, 0, EQ>(in, n, out, a.out_cap[b], flags, tbl, grp, &produced, eq);
+        else st = encode_block<G, TblT, 2, EQ>(in, n, out, a.out_cap[b], flags, tbl, grp, &produced, eq);
     }
-    if (MODE == 2 && grp.g == 0u) *reinterpret_cast<volatile uint32_t*>(&progress[j]) = 0xFFFFFFFFu;
     if (grp.g == 0u && st != LZ4FLEX_DEV_QUEUED) {   // a queued block's length and status come from the emitter wave
         a.status[b] = st;
         a.out_len[b] = st == 0 ? produced : 0u;
@@ -986,45 +847,32 @@ template <int G, typename TblT, int MODE, int BPW>
 static hipError_t launch_c(const CompressArgs& a, hipStream_t s) {
     static_assert(BPW * G <= 64 && BPW <= 8, "one encoder wave per workgroup");
     const uint32_t grid = (a.n + BPW - 1u) / BPW;
-    const size_t lds = (size_t)BPW * 4096u * sizeof(TblT) +
-                       (MODE == 2 ? 64u : (MODE == 3 ? (size_t)BPW * LZ4_EQ_BYTES : (MODE == 4 ? (size_t)BPW * LZ4_EQ_BYTES_RING : 0u)));
+    const size_t lds = (size_t)BPW * 4096u * sizeof(TblT) + (MODE == 3 ? (size_t)BPW * LZ4_EQ_BYTES : 0u);
     auto kern = lz4_compress_blocks_kernel<G, TblT, MODE, BPW>;
-    if (lds > 65536u) {   // the attribute is per device: remember which devices have it (per instantiation)
-        static unsigned long long have = 0ull;   // benign race: setting it twice is harmless
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(have & bit)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            have |= bit;
-        }
+    if (lds > 65536u) {
+        static LargeLds large;   // (per instantiation)
+        const hipError_t e = large.allow(lds, kern);
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(MODE == 0 ? 64 : 128), lds, s, a);
     return hipGetLastError();
 }
 
+// emitter: MODE 3 of lz4_compress_blocks_kernel.  Without it MODE 0, a cross-check that only variant builds hold
 template <int G, typename TblT, int BPW>
-static hipError_t launch_m(const CompressArgs& a, int mode, hipStream_t s) {
-    // MODE 2 (prefetch-only second wavefront) and MODE 4 (LDS input ring) were round-1 experiments that measured slower than
-    // MODE 3; they are no longer instantiated
-    if (mode == 3) return launch_c<G, TblT, 3, BPW>(a, s);
-#ifdef LZ4FLEX_ALL_VARIANTS   // MODE 0 (the group encoder without an emitter wavefront) is a cross-check: variant builds only
+static hipError_t launch_m(const CompressArgs& a, bool emitter, hipStream_t s) {
+    if (emitter) return launch_c<G, TblT, 3, BPW>(a, s);
+#ifdef LZ4FLEX_ALL_VARIANTS
     return launch_c<G, TblT, 0, BPW>(a, s);
 #else
     return hipErrorInvalidValue;
 #endif
 }
 
-// variant: bits 0..7 = lanes per block (8 or 16), bit 8 = blocks may exceed 64 KiB (u32 table),
-// bits 9..10 + bit 12 = MODE of lz4_compress_blocks_kernel (0, 2, 3; bit 12: 4)
-hipError_t launch_compress(const CompressArgs& a, int variant, hipStream_t s) {
+hipError_t launch_compress(const CompressArgs& a, int lanes, bool big, bool emitter, hipStream_t s) {
     if (a.n == 0u) return hipSuccess;
-    const int G = variant & 0xFF;
-    const bool big = (variant & 0x100) != 0;
-    const int mode = ((variant >> 9) & 3) | ((variant & 0x1000) ? 4 : 0);
-    if (G == 8) return big ? launch_m<8, uint32_t, 8>(a, mode, s) : launch_m<8, uint16_t, 8>(a, mode, s);
-    if (G == 16) return big ? launch_m<16, uint32_t, 4>(a, mode, s) : launch_m<16, uint16_t, 4>(a, mode, s);
+    if (lanes == 8) return big ? launch_m<8, uint32_t, 8>(a, emitter, s) : launch_m<8, uint16_t, 8>(a, emitter, s);
+    if (lanes == 16) return big ? launch_m<16, uint32_t, 4>(a, emitter, s) : launch_m<16, uint16_t, 4>(a, emitter, s);
     return hipErrorInvalidValue;
 }
 

@@ -38,17 +38,14 @@
 #include <stdint.h>
 
 #include "lz4_device.h"
+#include "lz4_wave_prims.h"
 
 namespace lz4flex_dev {
 namespace wave {
 
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) uint8_t g_u8;          // global memory, named: pointers that cross a call would be flat
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) u32x4 g_u32x4;         // global memory, named: pointers that cross a call would be flat
 typedef __attribute__((address_space(1))) u32x2 g_u32x2;
 typedef __attribute__((address_space(1))) uint32_t g_u32;
 typedef __attribute__((address_space(1))) int32_t g_i32;
@@ -164,31 +161,19 @@ __device__ __forceinline__ uint32_t dpp_wave_shr1(uint32_t v, uint32_t lane0) {
 __device__ __forceinline__ uint32_t dpp_wave_shl1(uint32_t v, uint32_t lane63) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)lane63, (int)v, 0x130, 0xf, 0xf, false);
 }
-#define LZ4W_DPP(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rmask), 0xf, false))
 __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v) {
     uint32_t t;
-    t = LZ4W_DPP(v, 0x111, 0xf); v = v > t ? v : t;     // row_shr:1
-    t = LZ4W_DPP(v, 0x112, 0xf); v = v > t ? v : t;     // row_shr:2
-    t = LZ4W_DPP(v, 0x114, 0xf); v = v > t ? v : t;     // row_shr:4
-    t = LZ4W_DPP(v, 0x118, 0xf); v = v > t ? v : t;     // row_shr:8
-    t = LZ4W_DPP(v, 0x142, 0xa); v = v > t ? v : t;     // row_bcast:15 -> rows 1, 3
-    t = LZ4W_DPP(v, 0x143, 0xc); v = v > t ? v : t;     // row_bcast:31 -> rows 2, 3
+    t = LZ4_DPP(v, 0x111, 0xf); v = v > t ? v : t;     // row_shr:1
+    t = LZ4_DPP(v, 0x112, 0xf); v = v > t ? v : t;     // row_shr:2
+    t = LZ4_DPP(v, 0x114, 0xf); v = v > t ? v : t;     // row_shr:4
+    t = LZ4_DPP(v, 0x118, 0xf); v = v > t ? v : t;     // row_shr:8
+    t = LZ4_DPP(v, 0x142, 0xa); v = v > t ? v : t;     // row_bcast:15 -> rows 1, 3
+    t = LZ4_DPP(v, 0x143, 0xc); v = v > t ? v : t;     // row_bcast:31 -> rows 2, 3
     return v;
 }
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    v += LZ4W_DPP(v, 0x111, 0xf);
-    v += LZ4W_DPP(v, 0x112, 0xf);
-    v += LZ4W_DPP(v, 0x114, 0xf);
-    v += LZ4W_DPP(v, 0x118, 0xf);
-    v += LZ4W_DPP(v, 0x142, 0xa);
-    v += LZ4W_DPP(v, 0x143, 0xc);
-    return v;
-}
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// (wave_incl_add, rdlane, uni, ctz64: lz4_wave_prims.h)
 __device__ __forceinline__ uint64_t ld64l(const lds_u8* p) { uint64_t v; __builtin_memcpy(&v, (const void*)p, 8); return v; }
 __device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { const uint32_t t = a < b ? a : b; return t < c ? t : c; }
-__device__ __forceinline__ uint32_t ctz64(uint64_t x) { return (uint32_t)__builtin_ctzll(x); }
 __device__ __forceinline__ uint32_t len_ext_bytes(uint32_t v) { return v >= 15u ? (v - 15u) / 255u + 1u : 0u; }   // compress.rs:237-247
 
 // v_ffbl_b32: index of the lowest set bit, 0xFFFFFFFF for 0.  As inline assembly: written as __ffs(x) - 1 hipcc guards the zero case
@@ -2034,23 +2019,11 @@ hipError_t launch_compress_wave(const CompressArgs& a, void* workspace, int n_wo
                                 const SharedDictArgs* shared_dict, const DictSetArgs* dict_set) {
     if (a.n == 0u) return hipSuccess;
     if (!workspace || n_workgroups <= 0) return hipErrorInvalidValue;
-    static unsigned long long have = 0ull;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(have & bit)) {
-        for (const void* k : {reinterpret_cast<const void*>(wave::lz4_compress_wave_kernel), reinterpret_cast<const void*>(wave::lz4_compress_wave_redo_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_compress_wave_dict_redo_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_compress_wave_shared_redo_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_wave_set_kernel),
-                              reinterpret_cast<const void*>(wave::lz4_wave_set_redo_kernel)}) {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-        have |= bit;
-    }
+    static LargeLds large;
+    const hipError_t le = large.allow(wave::LDS_BYTES, wave::lz4_compress_wave_kernel, wave::lz4_compress_wave_redo_kernel, wave::lz4_compress_wave_dict_kernel,
+                                      wave::lz4_compress_wave_dict_redo_kernel, wave::lz4_compress_wave_shared_kernel,
+                                      wave::lz4_compress_wave_shared_redo_kernel, wave::lz4_wave_set_kernel, wave::lz4_wave_set_redo_kernel);
+    if (le != hipSuccess) return le;
     // fewer blocks than workgroups: windows, not blocks, are dealt out (see item_seek); the carry slots and the item counter
     // behind the per-workgroup workspaces start at zero
     uint32_t* carry = nullptr;

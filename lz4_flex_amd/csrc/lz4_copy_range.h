@@ -4,9 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace lz4flex_dev {
+#include "lz4_wave_prims.h"
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+namespace lz4flex_dev {
 
 // thread t of nt copies its share of src[0, n) to dst: 16 bytes per lane where source and destination allow it
 __device__ __forceinline__ void copy_range(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint64_t n, uint32_t t, uint32_t nt) {

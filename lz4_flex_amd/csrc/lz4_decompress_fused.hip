@@ -333,15 +333,9 @@ hipError_t launch_decompress_fused(const DecompressArgs& a, int32_t redo_code, h
     const uint32_t grid = (a.n + fused::NB - 1u) / fused::NB;
     const size_t lds = (size_t)fused::NB * fused::Layout::BLK_LDS;
     auto kern = fused::lz4_decompress_fused_kernel;
-    static unsigned long long have = 0ull;   // the attribute is per device (benign race: setting it twice is harmless)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(have & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        have |= bit;
-    }
+    static LargeLds large;
+    const hipError_t e = large.allow(lds, kern);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, redo_code);
     return hipGetLastError();
 }

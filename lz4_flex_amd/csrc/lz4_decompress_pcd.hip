@@ -37,14 +37,13 @@
 
 #include "lz4_device.h"
 #include "lz4_pcd_common.h"
+#include "lz4_wave_prims.h"
 
 namespace lz4flex_dev {
 namespace pcd {
 
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t align_up(uint32_t v, uint32_t a) { return (v + a - 1u) / a * a; }
 constexpr uint32_t ceil_log2(uint32_t v) { uint32_t r = 0u; while ((1u << r) < v) ++r; return r; }
@@ -139,16 +138,7 @@ constexpr uint32_t PAIR_TOKB = (2u * MAXSEQ + 255u) / 256u * 256u;      // (the 
 enum : uint32_t { C_EXIT = 0, C_CUT = 1, C_TOTAL = 2, C_BAD = 3, C_G_SRC = 4, C_G_LIT = 5, C_G_ML = 6, C_G_OFF = 7, C_TIMEOUT = 8, C_BAD2 = 9,
                   C_NEEDPREV = 10, C_PREV = 11, C_G_IS = 12 };
 
-#define PCD_DPP(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rmask), 0xf, false))
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    v += PCD_DPP(v, 0x111, 0xf);     // row_shr:1
-    v += PCD_DPP(v, 0x112, 0xf);     // row_shr:2
-    v += PCD_DPP(v, 0x114, 0xf);     // row_shr:4
-    v += PCD_DPP(v, 0x118, 0xf);     // row_shr:8
-    v += PCD_DPP(v, 0x142, 0xa);     // row_bcast:15 -> rows 1, 3
-    v += PCD_DPP(v, 0x143, 0xc);     // row_bcast:31 -> rows 2, 3
-    return v;
-}
+// (wave_incl_add: lz4_wave_prims.h)
 __device__ __forceinline__ uint32_t bcast(uint32_t v, uint32_t l) { return (uint32_t)__shfl((int)v, (int)l, 64); }
 __device__ __forceinline__ u32x4 ld16l(const lds_u8* p) { u32x4 v; __builtin_memcpy(&v, (const void*)p, 16); return v; }
 __device__ __forceinline__ void st16l(lds_u8* p, const u32x4& v) { __builtin_memcpy((void*)p, &v, 16); }
@@ -1074,16 +1064,10 @@ __global__ void __launch_bounds__(G::T) lz4_decompress_pcd_kernel(DecompressArgs
 template <class G>
 static hipError_t launch_geo(const DecompressArgs& a, int32_t redo_code, hipStream_t s) {
     auto kern = lz4_decompress_pcd_kernel<G>;
-    if (G::LDS_BYTES > 65536u) {   // the attribute is per device: remember which devices have it (per instantiation)
-        static unsigned long long have = 0ull;   // benign race: setting it twice is harmless
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(have & bit)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            have |= bit;
-        }
+    if (G::LDS_BYTES > 65536u) {
+        static LargeLds large;   // (per instantiation)
+        const hipError_t e = large.allow(G::LDS_BYTES, kern);
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(a.pair_ws != nullptr ? 2u * a.n : a.n), dim3(G::T), G::LDS_BYTES, s, a, redo_code);
     return hipGetLastError();

@@ -30,14 +30,12 @@
 #include "lz4_device.h"
 #include "lz4_pcd_common.h"
 #include "lz4_plan_common.h"
+#include "lz4_wave_prims.h"
 
 namespace lz4flex_dev {
 namespace plan {
 
-typedef uint8_t __attribute__((address_space(3))) lds_u8;
 typedef uint32_t __attribute__((address_space(3))) lds_u32;
-typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-typedef uint32_t __attribute__((ext_vector_type(2))) u32x2;
 using pcd::X_END;
 using pcd::X_ERR;
 
@@ -65,18 +63,6 @@ __device__ __forceinline__ uint32_t tile_at(uint32_t r) { return r + 4u * (r / P
 // a sequence, 8 bytes: a = token position relative to the tile (13 bits) | literal length << 13 (16 bits); b = offset | match length << 16
 // (match length 0: the block's last sequence).  Literal and match lengths beyond 65 535 make a block irregular.
 typedef u32x2 Desc;      // .x = a, .y = b
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-#define LZ4P_DPP(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rmask), 0xf, false))
-    v += LZ4P_DPP(v, 0x111, 0xf);     // row_shr:1
-    v += LZ4P_DPP(v, 0x112, 0xf);     // row_shr:2
-    v += LZ4P_DPP(v, 0x114, 0xf);     // row_shr:4
-    v += LZ4P_DPP(v, 0x118, 0xf);     // row_shr:8
-    v += LZ4P_DPP(v, 0x142, 0xa);     // row_bcast:15 -> rows 1, 3
-    v += LZ4P_DPP(v, 0x143, 0xc);     // row_bcast:31 -> rows 2, 3
-#undef LZ4P_DPP
-    return v;
-}
 
 // the compressed bytes: the staged window from LDS, anything else from memory
 struct Reader {

@@ -19,12 +19,10 @@
 
 #include "lz4_device.h"
 #include "lz4_plan_common.h"
+#include "lz4_wave_prims.h"
 
 namespace lz4flex_dev {
 namespace plan {
-
-typedef uint32_t __attribute__((ext_vector_type(4))) u32x4;
-typedef uint8_t __attribute__((address_space(3))) lds_u8;
 
 // turns of K_END: what a lane group without a block (batch tail, irregular block) replays
 #define LZ4R_E4 END_REC, END_REC, END_REC, END_REC
@@ -277,15 +275,9 @@ hipError_t launch_replay(const ReplayArgs& a, hipStream_t s) {
     const uint32_t grid = (a.n + plan::NB - 1u) / plan::NB;
     const size_t lds = (size_t)plan::NB * plan::RING_STRIDE;
     auto kern = plan::lz4_replay_kernel;
-    static unsigned long long have = 0ull;   // the attribute is per device (benign race: setting it twice is harmless)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(have & bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        have |= bit;
-    }
+    static LargeLds large;
+    const hipError_t e = large.allow(lds, kern);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
 }

@@ -57,7 +57,6 @@ namespace lz4flex_dev {
 namespace sq {
 
 using namespace sw;      // the walk, its geometry and the lane / LDS helpers
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef LZ4S_R
 #define LZ4S_R 3584

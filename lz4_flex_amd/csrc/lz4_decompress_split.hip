@@ -634,16 +634,10 @@ static hipError_t launch_cfg(const DecompressArgs& a, hipStream_t s) {
     const uint32_t grid = (a.n + NB - 1u) / NB;
     const size_t lds = (size_t)NB * L::BLK_LDS;
     auto kern = lz4_decompress_split_kernel<L, NB, G, WB, NS>;
-    if (lds > 65536u) {   // the attribute is per device: remember which devices have it (per instantiation)
-        static unsigned long long have = 0ull;   // benign race: setting it twice is harmless
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(have & bit)) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            have |= bit;
-        }
+    if (lds > 65536u) {
+        static LargeLds large;   // (per instantiation)
+        const hipError_t e = large.allow(lds, kern);
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64u * split_waves<NB * G / 64u, G>()), lds, s, a);
     return hipGetLastError();

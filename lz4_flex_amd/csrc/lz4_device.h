@@ -224,7 +224,9 @@ hipError_t launch_decompress_fused(const DecompressArgs& a, int32_t redo_code, h
 // one WORKGROUP per block, token chain and copies parallel inside the block (lz4_decompress_pcd.hip: few, large blocks); irregular
 // blocks are left with status redo_code like behind launch_decompress_seq.  test_geometry: tiny tiles / batches (tests only)
 hipError_t launch_decompress_pcd(const DecompressArgs& a, int32_t redo_code, hipStream_t s, int geometry = 0);   // 0 production (1 024 lanes), 1 tests, 2 / 3 medium batches (256 / 512 lanes)
-hipError_t launch_compress(const CompressArgs& a, int variant, hipStream_t s);
+// the reference-exact block encoder (lz4_compress.hip): lanes per block (8 or 16), big: blocks may exceed 64 KiB (u32 table entries),
+// emitter: a second wavefront writes the output (the product; without it: -DLZ4FLEX_ALL_VARIANTS builds, else hipErrorInvalidValue)
+hipError_t launch_compress(const CompressArgs& a, int lanes, bool big, bool emitter, hipStream_t s);
 // throughput ("wave") encoder, lz4_compress_wave.hip: persistent workgroups, `workspace` holds
 // compress_wave_workspace_bytes(n_workgroups) bytes (cand[] slots + segment bodies, L2 / Infinity Cache resident)
 size_t compress_wave_workspace_bytes(int n_workgroups);
@@ -269,13 +271,13 @@ hipError_t launch_compress_chain(const uint8_t* in_base, const void* blocks, con
                                  const uint32_t* chain_count, uint32_t n_chains, uint8_t* out_base,
                                  const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
                                  uint32_t* tbl_state, hipStream_t s, const uint8_t* dict_base = nullptr);
-// compress_mode 1 (reference-exact), independent blocks: launch_compress(a, enc_bits) for the blocks without a dictionary and -- !big:
+// compress_mode 1 (reference-exact), independent blocks: launch_compress(a, lanes, big, emitter) for the blocks without a dictionary and -- !big:
 // the caller promised blocks of at most 64 KiB -- INVALID_ARG for those among them that are longer; then, where the batch has
 // dictionaries (a.dict_* or d), every block with one as a one-block chain of the chain kernel (dict_chain_record; refused: block_dict's
 // refusals and in_len > 0x7FFFFFFF).  The records are built on the device in ws (ws_bytes bytes, read with dictionaries only), in pieces
 // of as many blocks as it holds, at most max_piece of them (0: no limit; tests).
-hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int enc_bits, bool big, void* ws, size_t ws_bytes,
-                                 uint32_t max_piece, hipStream_t s);
+hipError_t launch_compress_exact(const CompressArgs& a, const DictSource& d, int lanes, bool big, bool emitter, void* ws,
+                                 size_t ws_bytes, uint32_t max_piece, hipStream_t s);
 
 hipError_t launch_xxh32_batch(const uint8_t* base, const uint64_t* off, const uint32_t* len, uint32_t n, uint32_t seed,
                               uint32_t* out, hipStream_t s);
@@ -471,5 +473,26 @@ hipError_t launch_frame_range_verdict(const FrameRangeVerdict& v, hipStream_t s)
 // DECODE_REDO: the status a first-pass decoder (sequence, workgroup, plan, fused) leaves on a block it does not decode: the host then runs a reference-order
 // kernel with only_status = DECODE_REDO over the batch (capi.cpp launch_redo; which routes have one: lz4_route.h Redo)
 constexpr int32_t DECODE_REDO = 0x7F000001;
+
+// A launcher's opt-in to more than 64 KiB of dynamic LDS.  The attribute is per kernel and per device: allow() sets it for every
+// kernel given on the current device the first time it runs there and remembers the device.  The first error is returned and the
+// device stays unmarked.  One object per set of kernels -- a function-local static of the launcher (of each instantiation of a
+// launcher template); two threads that race here both set the attribute, which is harmless.
+struct LargeLds {
+    unsigned long long have = 0ull;      // a bit per device
+    template <class... K>
+    hipError_t allow(size_t bytes, K... kernels) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (have & bit) return hipSuccess;
+        for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
+            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (e != hipSuccess) return e;
+        }
+        have |= bit;
+        return hipSuccess;
+    }
+};
 
 }  // namespace lz4flex_dev

@@ -96,12 +96,12 @@ __device__ __forceinline__ bool better(const Best& b, uint32_t used, uint32_t sl
 }
 
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-    v = max(v, LZ4SW_DPP(v, 0x111, 0xf));     // row_shr:1
-    v = max(v, LZ4SW_DPP(v, 0x112, 0xf));     // row_shr:2
-    v = max(v, LZ4SW_DPP(v, 0x114, 0xf));     // row_shr:4
-    v = max(v, LZ4SW_DPP(v, 0x118, 0xf));     // row_shr:8
-    v = max(v, LZ4SW_DPP(v, 0x142, 0xa));     // row_bcast:15 -> rows 1, 3
-    v = max(v, LZ4SW_DPP(v, 0x143, 0xc));     // row_bcast:31 -> rows 2, 3
+    v = max(v, LZ4_DPP(v, 0x111, 0xf));     // row_shr:1
+    v = max(v, LZ4_DPP(v, 0x112, 0xf));     // row_shr:2
+    v = max(v, LZ4_DPP(v, 0x114, 0xf));     // row_shr:4
+    v = max(v, LZ4_DPP(v, 0x118, 0xf));     // row_shr:8
+    v = max(v, LZ4_DPP(v, 0x142, 0xa));     // row_bcast:15 -> rows 1, 3
+    v = max(v, LZ4_DPP(v, 0x143, 0xc));     // row_bcast:31 -> rows 2, 3
     return rdlane(v, 63u);
 }
 
@@ -162,7 +162,7 @@ __device__ __forceinline__ uint32_t run_chunks(const g_u8* in, uint32_t ilen, ui
         const uint32_t p = op + incl - u;
         if ((ballot(off > p + lit) & ~lastm & am) != 0ull) return TILE_REDO;     // OffsetOutOfBounds (:399-401)
         // the match in front of this lane's sequence, the end rules' shortest final run behind it
-        const uint32_t left = LZ4SW_DPP(ml, 0x138, 0xf);                         // wave_shr:1
+        const uint32_t left = LZ4_DPP(ml, 0x138, 0xf);                         // wave_shr:1
         const uint32_t mp = lane == 0u ? mprev : left;
         const uint32_t lmin = mp == 0u ? 0u : (mp >= 7u ? 5u : 12u - mp);
         const Cand<uint32_t> cd = best_of_seq<uint32_t>(t0 + tpr, p, lit, ml, lmin, cap, n);

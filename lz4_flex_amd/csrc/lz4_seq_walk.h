@@ -17,15 +17,13 @@
 
 #include "lz4_device.h"
 #include "lz4_pcd_common.h"
+#include "lz4_wave_prims.h"
 
 namespace lz4flex_dev {
 namespace sw {
 
-typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint16_t lds_u16;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 using pcd::X_END;
 using pcd::X_ERR;
 
@@ -54,21 +52,9 @@ static_assert(PT - 1u + 4u + 15u + WALK_LITMAX + 4u < PT + TMARGIN, "a hop's len
 // function's result, the loop's state -- for divergent: masks and counters move to vector registers, uniform branches become
 // exec-mask loops (the first build of the decoder ran its whole main loop that way).
 #define SW_JOIN() asm volatile("; join")
-#define LZ4SW_DPP(v, ctrl, rmask) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rmask), 0xf, false))
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t v) {
-    v += LZ4SW_DPP(v, 0x111, 0xf);     // row_shr:1
-    v += LZ4SW_DPP(v, 0x112, 0xf);     // row_shr:2
-    v += LZ4SW_DPP(v, 0x114, 0xf);     // row_shr:4
-    v += LZ4SW_DPP(v, 0x118, 0xf);     // row_shr:8
-    v += LZ4SW_DPP(v, 0x142, 0xa);     // row_bcast:15 -> rows 1, 3
-    v += LZ4SW_DPP(v, 0x143, 0xc);     // row_bcast:31 -> rows 2, 3
-    return v;
-}
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// (wave_incl_add, rdlane, uni, ctz64: lz4_wave_prims.h)
 __device__ __forceinline__ uint64_t ballot(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 __device__ __forceinline__ bool lanes(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }      // this lane's bit of a wave-uniform mask
-__device__ __forceinline__ uint32_t ctz64(uint64_t x) { return (uint32_t)__builtin_ctzll(x); }
 __device__ __forceinline__ uint64_t low_mask(uint32_t n) { return n >= 64u ? ~0ull : (1ull << n) - 1ull; }
 __device__ __forceinline__ uint32_t bperm(uint32_t lane_src, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(lane_src * 4u), (int)v); }
 

@@ -304,8 +304,11 @@ def test_dictionary_entries_give_mode_0_bytes(high_default):
     in_off = (np.cumsum(in_len.astype(np.uint64)) - in_len).astype(np.uint64)
     cap = np.array([O.max_out(len(b)) for b in blocks], dtype=np.uint32)
     out_off = (np.cumsum(cap.astype(np.uint64)) - cap).astype(np.uint64)
-    dicts = np.frombuffer(j[:4096] + j[30000:30000 + 40000], dtype=np.uint8)
+    # (the fixture has 66 675 bytes: the second dictionary's 40 000 come from two copies of it -- j[30000:70000] was 36 675 bytes, and
+    # the 40 000 of d_len reached 3 325 bytes past the buffer, into whatever lay behind it: bytes that changed from call to call)
+    dicts = np.frombuffer(j[:4096] + (j * 2)[30000:30000 + 40000], dtype=np.uint8)
     d_off, d_len = np.array([0, 4096, 0], dtype=np.uint64), np.array([4096, 40000, 0], dtype=np.uint32)
+    assert len(dicts) == int(d_off[1] + d_len[1])
 
     def every_entry():
         res = []

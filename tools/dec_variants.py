@@ -128,7 +128,9 @@ def main():
                 b0 = int(neq[0]); d = (back.view(n, B)[b0] != src.view(n, B)[b0]).nonzero().flatten()
                 print("    block %d: %d wrong bytes, first at %s, last at %d; got %s want %s" % (b0, d.numel(), d[:8].tolist(), int(d[-1]),
                       bytes(back.view(n, B)[b0][int(d[0]) - 8:int(d[0]) + 24].tolist()), bytes(src.view(n, B)[b0][int(d[0]) - 8:int(d[0]) + 24].tolist())), flush=True)
-        if variant >= 5:      # how many blocks did the first pass leave to the reference-order kernel?
+        # a decoder with a second pass (the workgroup decoder's geometries 7 / 8 / 10 / 11, the sequence decoder 13; in tools builds plan /
+        # replay 9 and fused 12): how many blocks did the first pass leave to the reference-order kernel?
+        if variant in (7, 8, 9, 10, 11, 12, 13):
             assert lib.lz4flex_set_tuning(ctx, b"decompress_second_pass", 0) == 0
             dec_once(); torch.cuda.synchronize()
             print("    first pass left %d of %d bench blocks to the second pass" % (int((bst != 0).sum().item()), n), flush=True)
