@@ -105,7 +105,9 @@ const char *lz4flex_build_id(void);
  * lz4flex_compress_paged with lz4flex_compress_paged_work_size, lz4flex_paged_pages_bound and lz4flex_paged_rounds_bound (no setting, no
  * workspace in the context: the caller brings scratch and work; a caller detects them by the symbol), then their read side
  * lz4flex_paged_read_ranges with lz4flex_paged_read_work_size and lz4flex_paged_range_pages_bound (no setting, no workspace in the
- * context in MEM_DEVICE: the caller brings scratch and work; a caller detects them by the symbol). */
+ * context in MEM_DEVICE: the caller brings scratch and work; a caller detects them by the symbol), then the append
+ * lz4flex_paged_append with lz4flex_paged_append_work_size and lz4flex_paged_append_stage_bound (no setting, no workspace in the context
+ * in MEM_DEVICE: the caller brings stage, scratch and work; a caller detects them by the symbol). */
 int lz4flex_abi_version(void);
 /* last HIP error string seen by this thread (diagnostics) */
 const char *lz4flex_last_error(void);
@@ -914,6 +916,88 @@ int lz4flex_paged_read_ranges(lz4flex_ctx *ctx, const void *pages, uint32_t page
                               uint32_t n, const uint32_t *range_stream, const uint32_t *range_off, const uint32_t *range_len, uint32_t m,
                               void *out_base, const uint64_t *out_off, uint32_t *out_len, int32_t *status, uint32_t max_items,
                               void *scratch, uint64_t scratch_cap, void *work, int mem_kind, void *hip_stream);
+
+/* ---- paged streams, append: new bytes for any subset of the streams, the tail page reopened (lz4_paged_append.hip, paged_append.h) -----
+ * "Here are more bytes for some of my n paged streams."  One call, planned on the device in MEM_DEVICE: every stream that gets bytes has
+ * its last page decoded again, the new bytes put behind it, and the paged rule of lz4flex_compress_paged resumed over the two -- so the
+ * old last page is filled up before a new one is begun, the work follows the new bytes and not the stream's length, and the source of
+ * what is already paged is not needed.  The tables are those lz4flex_compress_paged wrote, with room behind n_pages[i] (entries up to
+ * page_off[i+1]) for the pages to come.
+ *
+ * THE RULE (tests/paged_append_model.py is the same rule as a program; paged_append.h holds its integer part for the host and the kernels).
+ * P = page_size.  On entry stream i has `first = page_off[i]`, `C = page_off[i+1] - first`, `k = n_pages[i]`, `S = in_done[i]` and
+ * `A = add_len[i]` new bytes at `add_base + add_off[i]`.  Whatever status[i] held on entry is ignored: a stream that ended
+ * LZ4FLEX_E_OUTPUT_TOO_SMALL earlier continues from its in_done.
+ *   1. `A == 0`: the stream takes no part, nothing of it is touched; `status[i] = 0`, `stage_off[i] = ~0`, `tail_src[i] = S`.
+ *   2. A table that contradicts itself: LZ4FLEX_E_INVALID_ARG, nothing of the stream is written (`stage_off[i] = ~0`, `tail_src[i] = S`).
+ *      That is: page_off counting down; `k > C`; `k == 0` with `S != 0`; with `k > 0` a last entry `e = first + k - 1` with
+ *      `page_len[e] == 0`, `page_len[e] > P`, `page_src[e] >= S` or `T = S - page_src[e] > window_max` (no page that
+ *      lz4flex_compress_paged wrote at that window_max holds more than a window); `S + A > 2^32 - 1`.
+ *   3. The tail: `base = page_src[e]`, `T = S - base`; with `k == 0`: `base = 0`, `T = 0`.  `tail_src[i] = base`.
+ *   4. Staging: stream i needs `roundup64(T + A)` bytes of `stage`; its slot starts at the sum of those sizes over the streams in front
+ *      of it that passed 2.  A stream whose slot ends behind stage_cap is not served: LZ4FLEX_E_OUTPUT_TOO_SMALL, `stage_off[i] = ~0`,
+ *      nothing of it is touched, the other streams are unaffected.  A served stream gets `stage_off[i]` = its slot.
+ *      lz4flex_paged_append_stage_bound(sum of add_len, n, window_max) = `sum_add_len + n * (window_max + 63)` is a stage_cap that always
+ *      suffices; window_max 0 stands for 65536, the default of every page size up to 16 KiB at the default window_min -- pass the resolved
+ *      window_max otherwise; 0 for a window_max below 64 or above 2^31.
+ *   5. Reopen: the last page is decoded into the slot (lz4flex_decompress_batch_partial at target T) and the new bytes are copied behind
+ *      it.  A tail page that fails gives the decoder's code; one that decodes to fewer than T bytes gives LZ4FLEX_E_EXPECTED_ANOTHER_BYTE.
+ *      In both cases the stream's tables and pages stay untouched.
+ *   6. Resume: the stream runs the rule of lz4flex_compress_paged unchanged, in the same rounds as the others, over the virtual stream
+ *      `V = tail ++ add` of T + A bytes: it starts at `W = window_min`, `pos = base` and page index `k - 1` (0 with `k == 0`), so entry
+ *      `first + k - 1` is overwritten and the entries behind it are taken up to C.  A stream that is not served, failed or has `A == 0` is
+ *      a dead stream in every round (an empty window at capacity 0), so n is the same in every round.  page_src values are stream
+ *      positions, `base + (position in V)`.  On return n_pages, in_done and status are the loop's results.  On a nonzero status from the
+ *      rounds the tables describe a valid prefix `[0, in_done)`: in_done may be smaller than S, never smaller than base, and the bytes
+ *      not yet paged are at `stage + stage_off[i] + (in_done[i] - tail_src[i])`, so nothing is lost.
+ * What it equals: for a served stream the entries from `first + k - 1` on, their pages' first page_len bytes, `n_pages - (k - 1)`,
+ *   `in_done - base` and status are those of ONE lz4flex_compress_paged call over n streams -- stream i is V_i, or empty for a dead
+ *   stream -- with the same n, windows, max_rounds and settings at capacity `C - (k - 1)` (C with `k == 0`); page_src there counts from 0.
+ * Invariants: every page but a stream's last still holds at least `Lfit(P, infinity)` bytes after any sequence of appends -- the reopened
+ *   page was the last one, and every page committed in front of a new last one is committed by the paged rule with more to come.  Hence
+ *   `n_pages <= lz4flex_paged_pages_bound(in_done, P)` however many appends there were, a capacity of the bound for the final length always
+ *   suffices, lz4flex_paged_range_pages_bound stays valid, and `lz4flex_paged_rounds_bound(window_max + the longest add_len, ...)` rounds
+ *   always suffice.
+ * What may be written: the pages and the table entries from the reopened entry up to the new n_pages (page bytes behind page_len and
+ *   pages at or behind n_pages are unspecified, as for lz4flex_compress_paged), the three per-stream results, stage_off, tail_src,
+ *   stage, scratch, work.  Nothing else: table entries at or behind the new n_pages and in front of the reopened entry stay as they are.
+ * Hostile tables (MEM_DEVICE: caller-supplied device memory): whatever they hold, no page is read outside `pages[e * P, e * P + P)` of
+ *   an entry inside the stream's `[first, first + C)`, nothing is written outside the stream's entries, pages and stage slot: 2 is
+ *   checked before an item exists.
+ * Call-level returns, in the order of lz4flex_compress_paged and before a context or a device is looked at: -LZ4FLEX_E_INVALID_ARG for
+ *   the page size and the windows (same limits and defaults), then for a mem_kind other than HOST / DEVICE (| BIG_BLOCKS;
+ *   LZ4FLEX_MEM_CHAINED is refused); then n == 0 returns 0; then -LZ4FLEX_E_INVALID_ARG for a missing array (add_off, add_len, the five
+ *   tables, status, stage_off, tail_src; DEVICE: a missing work, scratch or stage).  -LZ4FLEX_E_NO_DEVICE without a device.
+ * mem_kind: LZ4FLEX_MEM_DEVICE -- every pointer is device memory, asynchronous on hip_stream, nothing is allocated and nothing is
+ *   synchronised.  The launches are fixed and sized by n and max_rounds: locate, the offset scan (lz4_packed.hip's), emit, the partial
+ *   decode over n tail items, the copy batch over n add items, resume, then max_rounds x (lz4flex_compress_batch_fit + the paged step).
+ *   A slot nobody owns is a one-byte block with target 0, which the partial decoder answers without reading anything.  scratch:
+ *   `lz4flex_compress_packed_scratch_bound(sum of min(T_i + add_len[i], window_max), n, 0)` suffices (T_i = window_max where it is not
+ *   known on the host).  work: lz4flex_paged_append_work_size(n) bytes, 8-byte aligned.  LZ4FLEX_MEM_BIG_BLOCKS goes to the decoder and to
+ *   the encoder.  LZ4FLEX_MEM_HOST -- staged through the context and synchronous; stage, scratch, work and their capacities are ignored
+ *   and no stream is refused under 4.  Only the tables, each appended stream's last page and the new bytes go up; only the entries and
+ *   pages from the reopened one on -- as many as T + A bytes can take by the pages bound, whatever room the table keeps behind them --
+ *   and the results come down, copied to their places.  Rounds = min(max_rounds, the rounds bound of the
+ *   longest T + A).  There is no caller-visible stage: stage_off[i] is ~0 for every stream, tail_src[i] is reported; a caller that needs
+ *   the unpaged bytes back after a nonzero status uses the device form.
+ * Kernels (lz4_paged_append.hip; a lane per stream each, no LDS, no atomics, no scratch memory): locate 24, emit 26, resume 36 VGPRs.
+ * Measured on an MI355X (tools/paged_append_bench.py, one session with the legs alternating, profiles/r26_paged_append.txt; device-resident,
+ *   ms per call, host clock around a synchronised call, max_rounds = the rounds bound of what the leg encodes): 16 384 x 64 KiB JSON tiles
+ *   in 4 KiB pages appended by 256 B / 4 KiB / 16 KiB per stream 1.85 / 2.95 / 5.38, lz4flex_compress_paged over the same tail ++ add
+ *   streams 1.67 / 2.77 / 5.13 (the reopen -- locate, three scan launches, emit, the partial decode, the copy, resume -- costs 5 to 11 %),
+ *   re-paging the grown streams from byte 0 14.9 / 16.0 / 18.4; 65 536 x 4 KiB log records in 1 KiB pages appended by 256 B / 1 KiB /
+ *   16 KiB 8.89 / 11.5 / 56.3, over tail ++ add 8.34 / 10.9 / 55.5, re-paging 16.0 / 18.6 / 63.1.  Cheaper than re-paging at every size
+ *   measured; the gain shrinks as the add outweighs the stream.
+ * Not in scope: dictionaries, history, filters, frames; skipping the reopen when the tail page is known to be full; truncation or
+ *   in-place overwrite of stream bytes. */
+int lz4flex_paged_append(lz4flex_ctx *ctx, const void *add_base, const uint64_t *add_off, const uint32_t *add_len, uint32_t n,
+                         uint32_t page_size, uint32_t window_min, uint32_t window_max, uint32_t max_rounds, void *pages,
+                         const uint64_t *page_off /* n + 1, entries */, uint32_t *page_len, uint32_t *page_src,
+                         uint32_t *n_pages /* in/out */, uint32_t *in_done /* in/out */, int32_t *status, void *stage, uint64_t stage_cap,
+                         uint64_t *stage_off /* n, out */, uint32_t *tail_src /* n, out */, void *scratch, uint64_t scratch_cap, void *work,
+                         int mem_kind, void *hip_stream);
+size_t lz4flex_paged_append_work_size(uint32_t n);
+uint64_t lz4flex_paged_append_stage_bound(uint64_t sum_add_len, uint32_t n, uint32_t window_max);
 
 /* Settings (ctx NULL = the default context the scalar / frame entry points use):
  * "compress_mode": 0 = throughput encoder (default; lz4_compress_wave.hip: a valid LZ4 block with this library's own

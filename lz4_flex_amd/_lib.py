@@ -112,6 +112,10 @@ SIGNATURES = {
     "lz4flex_paged_read_work_size": (_SZ, [_U32, _U32]),
     "lz4flex_paged_read_ranges": (_I32, [_VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _U64,
                                           _VP, _I32, _VP]),
+    "lz4flex_paged_append": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP,
+                                     _VP, _U64, _VP, _I32, _VP]),
+    "lz4flex_paged_append_work_size": (_SZ, [_U32]),
+    "lz4flex_paged_append_stage_bound": (_U64, [_U64, _U32, _U32]),
     "lz4flex_set_tuning": (_I32, [_VP, C.c_char_p, _I32]),
     "lz4flex_get_tuning": (_I32, [_VP, C.c_char_p]),
     "lz4flex_frame_encoder_new": (_VP, [C.POINTER(FrameInfoC), WRITE_FN, _VP]),

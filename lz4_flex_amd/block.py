@@ -1335,6 +1335,167 @@ def read_paged_ranges_device(paged, sid, off, length, out=None, out_off=None, ma
     return out, out_off, out_len, status
 
 
+# ---- paged streams, append: new bytes for any subset of the streams (lz4flex_paged_append) ------------------------------------------------
+NO_STAGE = 0xFFFFFFFFFFFFFFFF     # stage_off[i] of a stream without a stage slot
+
+
+def paged_append_stage_bound(sum_add_len, n, page_size, window_min=0, window_max=0):
+    """lz4flex_paged_append_stage_bound: a stage_cap that always suffices for n streams that get sum_add_len new bytes in all.  The
+    windows are resolved here as lz4flex_paged_append resolves them for page_size (0: the defaults), so the bound and a call with the
+    same arguments agree; 0 for windows the entry refuses."""
+    return int(L.load().lz4flex_paged_append_stage_bound(int(sum_add_len), int(n), _paged_windows(page_size, window_min, window_max)[1]))
+
+
+def reserve_paged(paged, page_cap):
+    """The same streams in a table with room for page_cap[i] entries per stream (compress_paged sizes its table exactly by default, which
+    leaves no room to append): page_off becomes the exclusive sums of page_cap from 0, every committed page and its entry move to their
+    new places.  Host form (numpy arrays) or device form (torch tensors; one synchronisation for the sizes), as `paged` is.  A page_cap[i]
+    below n_pages[i] is a ValueError.  Plain indexing, not a kernel.  Returns a new PagedStreams; `paged` is not changed."""
+    P = int(paged.page_size)
+    n = len(paged.n_pages)
+    if isinstance(paged.pages, np.ndarray):
+        cap = _np(page_cap, np.int64)
+        k = paged.n_pages.astype(np.int64)
+        if len(cap) != n:
+            raise ValueError("the streams and page_cap differ in length")
+        if (cap < k).any():
+            raise ValueError("page_cap is below n_pages")
+        new_off = np.zeros(n + 1, dtype=np.uint64)
+        new_off[1:] = np.cumsum(cap)
+        entries, total = int(new_off[n]), int(k.sum())
+        owner = np.repeat(np.arange(n), k)
+        j = np.arange(total) - np.repeat(np.cumsum(k) - k, k)
+        old, new = paged.page_off[:n].astype(np.int64)[owner] + j, new_off[:n].astype(np.int64)[owner] + j
+        pages = np.zeros(max(entries * P, 1), dtype=np.uint8)[:entries * P]
+        page_len, page_src = np.zeros(entries, dtype=np.uint32), np.zeros(entries, dtype=np.uint32)
+        if total:
+            pages.reshape(entries, P)[new] = _host_u8(paged.pages)[:(int(old.max()) + 1) * P].reshape(-1, P)[old]
+            page_len[new], page_src[new] = paged.page_len[old], paged.page_src[old]
+        return PagedStreams(page_size=P, pages=pages, page_off=new_off, page_len=page_len, page_src=page_src, n_pages=paged.n_pages.copy(),
+                            in_done=paged.in_done.copy(), status=paged.status.copy())
+    import torch
+    dev = paged.pages.device
+    cap = torch.as_tensor(page_cap).to(device=dev, dtype=torch.int64)
+    k = paged.n_pages.to(torch.int64) & 0xFFFFFFFF
+    if int(cap.numel()) != n:
+        raise ValueError("the streams and page_cap differ in length")
+    new_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        new_off[1:] = torch.cumsum(cap, 0)
+    short, entries, total = (int(v) for v in torch.stack([(cap < k).sum(), new_off[n], k.sum()]).cpu()) if n else (0, 0, 0)
+    if short:
+        raise ValueError("page_cap is below n_pages")
+    pages = torch.zeros(max(entries * P, 1), dtype=torch.uint8, device=dev)[:entries * P]
+    page_len, page_src = (torch.zeros(entries, dtype=torch.int32, device=dev) for _ in range(2))
+    if total:
+        owner = torch.repeat_interleave(torch.arange(n, device=dev), k, output_size=total)
+        j = torch.arange(total, device=dev) - (torch.cumsum(k, 0) - k)[owner]
+        old, new = paged.page_off[:n].to(torch.int64)[owner] + j, new_off[:n][owner] + j
+        pages.view(entries, P)[new] = paged.pages[:(int(paged.pages.numel()) // P) * P].view(-1, P)[old]
+        page_len[new], page_src[new] = paged.page_len[old], paged.page_src[old]
+    return PagedStreams(page_size=P, pages=pages, page_off=new_off, page_len=page_len, page_src=page_src, n_pages=paged.n_pages.clone(),
+                        in_done=paged.in_done.clone(), status=paged.status.clone())
+
+
+def append_paged(paged, adds, window_min=0, window_max=0, max_rounds=None, ctx=None):
+    """lz4flex_paged_append over a PagedStreams of numpy arrays (MEM_HOST): adds[i] (bytes-like; empty: none) goes behind stream i, whose
+    last page is reopened and filled up before new pages are begun (the rule: include/lz4flex_amd.h).  The table needs room behind
+    n_pages[i] for the pages to come: reserve_paged.  max_rounds default: what always suffices.  `paged` is updated in place -- pages,
+    table, n_pages, in_done, status -- and returned; a stream that ran out of pages or rounds has status E_OUTPUT_TOO_SMALL and a valid
+    prefix of in_done[i] bytes (which may be fewer than before the call: the rest of the reopened page is lost to the host form)."""
+    P = int(paged.page_size)
+    n = len(paged.n_pages)
+    parts = [_host_u8(a) for a in adds]
+    if len(parts) != n:
+        raise ValueError("the streams and adds differ in length")
+    add_len = np.array([p.size for p in parts], dtype=np.uint32)
+    add_off = np.zeros(n, dtype=np.uint64)
+    if n:
+        add_off[1:] = np.cumsum(add_len[:-1], dtype=np.uint64)
+    src = np.concatenate(parts + [np.zeros(1, dtype=np.uint8)])
+    pages, page_off, page_len, page_src, n_pages, in_done = _paged_tables(paged)
+    for name, a, b in (("pages", pages, paged.pages), ("page_len", page_len, paged.page_len), ("page_src", page_src, paged.page_src),
+                       ("n_pages", n_pages, paged.n_pages), ("in_done", in_done, paged.in_done)):
+        if b.size and (a is not b or not b.flags.c_contiguous or (name == "pages" and b.dtype != np.uint8)):
+            raise ValueError("%s must be a contiguous array of the table's type: the call updates it in place" % name)
+    if max_rounds is None:
+        wmax = _paged_windows(P, window_min, window_max)[1]
+        max_rounds = paged_rounds_bound(min(wmax + (int(add_len.max()) if n else 0), 0xFFFFFFFF), P, window_min, window_max)
+    status = np.zeros(n, dtype=np.int32)
+    stage_off, tail_src = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+    args = [src, add_off, add_len, n, P, int(window_min), int(window_max), int(max_rounds), pages, page_off, page_len, page_src, n_pages, in_done,
+            status, None, 0, stage_off, tail_src, None, 0, None]
+    _check(L.load().lz4flex_paged_append(ctx, *map(_arg, args), L.MEM_HOST, None), "lz4flex_paged_append")
+    paged.status = status
+    return paged
+
+
+def _device_u32(a, dev):
+    """an integer tensor (or anything numpy converts) as the int32 bit pattern of u32 on `dev`: the low 32 bits count"""
+    import torch
+    a = torch.as_tensor(np.asarray(a, dtype=np.int64) if not hasattr(a, "data_ptr") else a)
+    return ((a.to(device=dev, dtype=torch.int64) + 0x80000000) % 0x100000000 - 0x80000000).to(torch.int32).contiguous()
+
+
+def append_paged_device(paged, src, add_off, add_len, window_min=0, window_max=0, max_rounds=None, stage_cap=None, scratch_cap=None, stream=None):
+    """lz4flex_paged_append over a PagedStreams of device tensors (MEM_DEVICE, asynchronous on `stream`, default the current one): stream i
+    gets the add_len[i] bytes src[add_off[i] : add_off[i] + add_len[i]] (src: a uint8 tensor on the pages' GPU; 0: none).  The table
+    needs room behind n_pages[i]: reserve_paged.  Nothing is read back unless a default needs it, and then in ONE synchronisation: the
+    defaults of max_rounds, stage_cap and scratch_cap are lz4flex_paged_rounds_bound, the stage slots and
+    lz4flex_compress_packed_scratch_bound for the tails the tables name (T_i = in_done - page_src of the last entry, clamped to window_max)
+    and the new bytes -- never more than lz4flex_paged_append_stage_bound and the header's scratch bound.  Stage, scratch and work come
+    from torch's allocator on the CURRENT stream, as in the other device forms.  `paged` is updated in place.  Returns (paged, stage,
+    stage_off, tail_src): after a nonzero status from the rounds the bytes of stream i that are not paged yet are
+    stage[stage_off[i] + in_done[i] - tail_src[i] : ...]; stage_off as int64 (-1: no slot), tail_src as the int32 bit pattern of u32."""
+    import torch
+    P = int(paged.page_size)
+    dev = paged.pages.device
+    dev_, n, d_off, d_len64, sp = _device_args(src, add_off, add_len, stream, wide_len=True)
+    if dev_ != dev:
+        raise ValueError("src must be on the GPU of the pages")
+    if int(paged.n_pages.numel()) != n:
+        raise ValueError("the streams and add_off differ in length")
+    for name in ("pages", "page_len", "page_src", "n_pages", "in_done"):
+        if not getattr(paged, name).is_contiguous():
+            raise ValueError("%s must be contiguous: the call updates it in place" % name)
+    d_len = _device_u32(d_len64, dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    stage_off = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    tail_src = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return paged, torch.empty(0, dtype=torch.uint8, device=dev), stage_off, tail_src
+    lib = L.load()
+    wmin, wmax = _paged_windows(P, window_min, window_max)
+    longest = None
+    if max_rounds is None or stage_cap is None or scratch_cap is None:
+        A = d_len.to(torch.int64) & 0xFFFFFFFF
+        k = paged.n_pages.to(torch.int64) & 0xFFFFFFFF
+        first = paged.page_off[:n].to(torch.int64)
+        entries = int(paged.page_src.numel())
+        last = torch.clamp(first + k - 1, 0, max(entries - 1, 0))
+        src_last = (paged.page_src.to(torch.int64) & 0xFFFFFFFF)[last] if entries else torch.zeros_like(k)
+        T = torch.where(k > 0, torch.clamp((paged.in_done.to(torch.int64) & 0xFFFFFFFF) - src_last, 0, wmax), torch.zeros_like(k))
+        V = torch.where(A > 0, T + A, torch.zeros_like(A))
+        longest, slots, offered = (int(v) for v in torch.stack([V.max(), ((V + 63) // 64 * 64).sum(), torch.clamp(V, max=wmax).sum()]).cpu())
+        if max_rounds is None:
+            max_rounds = paged_rounds_bound(min(longest, 0xFFFFFFFF), P, window_min, window_max)
+        if stage_cap is None:
+            stage_cap = slots
+        if scratch_cap is None:
+            scratch_cap = int(lib.lz4flex_compress_packed_scratch_bound(offered, n, 0))
+    stage_cap, scratch_cap = int(stage_cap), int(scratch_cap)
+    stage = torch.empty(max(stage_cap, 1), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(max(scratch_cap, 1), dtype=torch.uint8, device=dev)
+    work = torch.empty(int(lib.lz4flex_paged_append_work_size(n)), dtype=torch.uint8, device=dev)
+    keep = [t.new_zeros(1) if t.numel() == 0 else t for t in (paged.pages, paged.page_len, paged.page_src)]
+    big = wmax > 65536 if longest is None else min(longest, wmax) > 65536
+    _device_call("lz4flex_paged_append", [src, d_off, d_len], n,
+                 [P, int(window_min), int(window_max), int(max_rounds), keep[0], paged.page_off.to(torch.int64).contiguous(), keep[1], keep[2],
+                  paged.n_pages, paged.in_done, status, stage, stage_cap, stage_off, tail_src, scratch, scratch_cap, work], big, sp)
+    paged.status = status
+    return paged, stage[:stage_cap], stage_off, tail_src
+
+
 class CompressedTensor:
     """What compress_tensor returns and decompress_tensor takes: the compressed blocks back to back in `data` (a uint8 device tensor),
     block i at data[offsets[i] : offsets[i] + lengths[i]] (device tensors), and what the tensor was: shape, dtype, the block_bytes it was

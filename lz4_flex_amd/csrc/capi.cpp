@@ -1734,20 +1734,27 @@ uint32_t paged_doublings(uint32_t window_min, uint32_t window_max) {
     return d;
 }
 
+// max_rounds times the fit entry over the windows the step in front laid out in w, and the step behind it (lz4_paged.hip): the rounds of
+// lz4flex_compress_paged behind its PAGED_FIRST step, and of lz4flex_paged_append behind its resume step
+int paged_rounds(lz4flex_ctx* c, const PagedArgs& a, const PagedWork& w, const uint8_t* in_base, uint8_t* out_base, uint32_t max_rounds,
+                 uint8_t* scratch, uint64_t scratch_cap, bool big, hipStream_t s) {
+    const FitArgs round{nullptr, nullptr, nullptr, in_base, w.w_off, w.w_len, a.n, out_base, w.o_off, w.o_cap, w.r_len, w.r_used, w.r_st};
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        if (const int rc = compress_fit_on_device(c, round, scratch, scratch_cap, w.packed, big, s)) return rc;
+        const hipError_t e = launch_paged_step(a, w, r + 1u == max_rounds ? PAGED_LAST : PAGED_NEXT, s);
+        if (e != hipSuccess) return hip_fail(e, "paged step launch");
+    }
+    return 0;
+}
+
 // the rounds of a paged call on device memory: the step (lz4_paged.hip), then max_rounds times the fit entry over the windows the
 // step laid out and the step behind it.  a's arrays, in_base and out_base are device memory; nothing is allocated or synchronised.
 int paged_on_device(lz4flex_ctx* c, const PagedArgs& a, const uint8_t* in_base, uint8_t* out_base, uint32_t max_rounds, uint8_t* scratch,
                     uint64_t scratch_cap, void* work, bool big, hipStream_t s) {
     const PagedWork w = paged_work(work, a.n);
-    const FitArgs round{nullptr, nullptr, nullptr, in_base, w.w_off, w.w_len, a.n, out_base, w.o_off, w.o_cap, w.r_len, w.r_used, w.r_st};
-    hipError_t e = launch_paged_step(a, w, PAGED_FIRST | (max_rounds == 0u ? PAGED_LAST : 0), s);
+    const hipError_t e = launch_paged_step(a, w, PAGED_FIRST | (max_rounds == 0u ? PAGED_LAST : 0), s);
     if (e != hipSuccess) return hip_fail(e, "paged step launch");
-    for (uint32_t r = 0; r < max_rounds; r++) {
-        if (const int rc = compress_fit_on_device(c, round, scratch, scratch_cap, w.packed, big, s)) return rc;
-        e = launch_paged_step(a, w, r + 1u == max_rounds ? PAGED_LAST : PAGED_NEXT, s);
-        if (e != hipSuccess) return hip_fail(e, "paged step launch");
-    }
-    return 0;
+    return paged_rounds(c, a, w, in_base, out_base, max_rounds, scratch, scratch_cap, big, s);
 }
 
 struct PagedCall {
@@ -2011,6 +2018,189 @@ int lz4flex_paged_read_ranges(lz4flex_ctx* ctx, const void* pages, uint32_t page
     const PagedReadCall p{(const uint8_t*)pages, t, range_stream, range_off, range_len, m, (uint8_t*)out_base, out_off, out_len, status};
     try {
         return paged_read_on_host(ctx, p, k.big || page_size > 131072u);
+    } catch (...) { return -LZ4FLEX_E_NOMEM; }
+}
+
+// ---- paged streams, append: new bytes for any subset of the streams, the tail page reopened (lz4_paged_append.hip, paged_append.h) ----
+}  // extern "C"
+
+namespace {
+
+using lz4flex_paged::AppendRec;
+
+// a call on device memory: a fixed sequence of launches sized by n and max_rounds; nothing is allocated, read back or synchronised
+int paged_append_on_device(lz4flex_ctx* c, const PagedAppendArgs& a, const uint8_t* add_base, uint8_t* pages, uint8_t* stage, uint32_t max_rounds,
+                           uint8_t* scratch, uint64_t scratch_cap, void* work, bool big, bool big_pages, hipStream_t s) {
+    const PagedAppendWork w = paged_append_work(work, a.n);
+    hipError_t e = launch_paged_append_locate(a, w, s);
+    if (e == hipSuccess) e = launch_packed_scan(w.need, a.n, 1u, ~0ull, 0u, w.tiles, w.slot, nullptr, nullptr, nullptr, s);
+    if (e == hipSuccess) e = launch_paged_append_emit(a, w, s);
+    if (e != hipSuccess) return hip_fail(e, "paged append plan launch");
+    const int mem = LZ4FLEX_MEM_DEVICE | (big_pages ? LZ4FLEX_MEM_BIG_BLOCKS : 0);
+    if (const int rc = lz4flex_decompress_batch_partial(c, pages, w.t_in, w.t_len, a.n, stage, w.t_out, w.t_tgt, w.t_olen, w.t_st, mem, s)) return rc;
+    e = launch_copy_batch(add_base, w.c_src, w.c_len, stage, w.c_dst, a.n, s);
+    if (e == hipSuccess) e = launch_paged_append_resume(a, w, max_rounds == 0u, s);
+    if (e != hipSuccess) return hip_fail(e, "paged append resume launch");
+    const PagedArgs rounds{w.v_off, w.v_len, a.n, a.page_size, a.window_min, a.window_max, a.page_off, a.page_len, a.page_src, a.n_pages, a.in_done,
+                           a.status};
+    return paged_rounds(c, rounds, paged_work(w.paged, a.n), stage, pages, max_rounds, scratch, scratch_cap, big, s);
+}
+
+struct PagedAppendCall {
+    const uint8_t* add_base; const uint64_t* add_off; const uint32_t* add_len; uint32_t n;
+    uint32_t page_size, window_min, window_max, max_rounds;
+    uint8_t* pages; const uint64_t* page_off; uint32_t* page_len; uint32_t* page_src; uint32_t* n_pages; uint32_t* in_done; int32_t* status;
+    uint64_t* stage_off; uint32_t* tail_src;
+};
+
+// MEM_HOST: the host runs steps 1 to 3 itself (paged_append.h, the functions the kernels run) and answers the streams that take no part
+// or whose table contradicts itself; the others become the streams of a table of their own -- stream i holds its reopened entry and the
+// free entries behind it, a stream that does not go on holds none and has nothing to add, so n is the caller's in every round -- whose
+// tail pages and new bytes go up.  The device path runs with exactly the stage it needs, the entries and pages from the reopened one on
+// -- as many as T + A bytes can take, not the room the caller keeps behind them -- and the results come down with one synchronisation and
+// are copied to their places.
+int paged_append_on_host(lz4flex_ctx* c, const PagedAppendCall& p, bool big) {
+    const uint32_t n = p.n, P = p.page_size;
+    DeviceGuard guard(c->device);
+    HIP_TRY(guard.err);
+    const lz4flex_paged::AppendTables t{p.page_off, p.page_len, p.page_src, p.n_pages, p.in_done, n, P, p.window_max};
+    std::vector<AppendRec> recs(n);
+    std::vector<uint8_t> go(n);
+    Span add_span;
+    // the entries stream i gets in the device's table: the reopened one and the free ones behind it, and no more than T + A bytes can
+    // take (the pages bound) -- what goes up, is reserved and comes down follows the new bytes, not the room the caller keeps
+    const auto room_of = [&](const AppendRec& q) {
+        return std::min<uint64_t>(lz4flex_paged::append_room(q), lz4flex_paged_pages_bound(q.T + q.A, P));
+    };
+    uint64_t entries = 0, stage_bytes = 0, slots = 0;
+    uint32_t longest = 0, going = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        AppendRec& q = recs[i];
+        lz4flex_paged::append_locate(t, i, p.add_len[i], &q);
+        const int32_t pre = lz4flex_paged::append_pre(q, 0, ~0ull);
+        go[i] = pre == -1;
+        p.stage_off[i] = lz4flex_paged::NO_STAGE;
+        p.tail_src[i] = go[i] ? q.base : q.S;
+        if (!go[i]) {                                         // (a dead stream still has an empty window in every round: its scratch slot)
+            p.status[i] = pre;
+            slots += lz4flex_get_maximum_output_size(0);
+            continue;
+        }
+        const uint64_t room = room_of(q);
+        if (entries + room > 0xFFFFFFFFull) return -LZ4FLEX_E_UNSUPPORTED;
+        entries += room; going++;
+        stage_bytes += lz4flex_paged::append_slot_bytes(q);
+        const uint32_t v = q.T + q.A, w = std::min(v, p.window_max);
+        slots += lz4flex_get_maximum_output_size(w);
+        big = big || w > 65536u;
+        longest = std::max(longest, v);
+        add_span.add(p.add_off[i], q.A);
+    }
+    if (going == 0u) return 0;
+    add_span = add_span.closed();
+    const uint32_t rounds = std::min(p.max_rounds, lz4flex_paged_rounds_bound(longest, P, p.window_min, p.window_max));
+    const size_t out_bytes = (size_t)(entries * P);
+    HostStage st;
+    const auto add_off = st.up<uint64_t>(n), page_off = st.up<uint64_t>((size_t)n + 1u);
+    const auto add_len = st.up<uint32_t>(n);
+    const auto page_len = st.up<uint32_t>((size_t)entries), page_src = st.up<uint32_t>((size_t)entries);       // (these four go up and come down)
+    const auto n_pages = st.up<uint32_t>(n), in_done = st.up<uint32_t>(n);
+    const auto status = st.down<int32_t>(n);
+    const auto stage_off = st.down<uint64_t>(n);
+    const auto tail_src = st.down<uint32_t>(n);
+    const Region r_add = st.region(add_span.bytes(), 64), r_out = st.region(out_bytes, 64), r_stage = st.region((size_t)stage_bytes, 64);
+    st.columns();
+    const Region r_work = st.region(paged_append_work_bytes(n), 0);
+    int rc;
+    if ((rc = stage_open(c, st))) return rc;
+    if ((rc = ensure_buf(c->pay, out_bytes + 16))) return rc;
+    void* d_scratch = nullptr;
+    if ((rc = ctx_scratch(c, 0, (size_t)slots + 256, &d_scratch))) return rc;
+    hipStream_t s = st.s;
+    st.zero(page_len); st.zero(page_src);
+    uint64_t e_at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const AppendRec& q = recs[i];
+        st.host(page_off)[i] = e_at;
+        st.host(add_off)[i] = go[i] ? p.add_off[i] - add_span.lo : 0ull;
+        st.host(add_len)[i] = go[i] ? q.A : 0u;
+        st.host(n_pages)[i] = go[i] && q.k != 0u ? 1u : 0u;
+        st.host(in_done)[i] = go[i] ? q.S : 0u;
+        if (!go[i]) continue;
+        if (q.k != 0u) {
+            const uint64_t e = q.first + (q.k - 1u);
+            st.host(page_len)[e_at] = p.page_len[e]; st.host(page_src)[e_at] = p.page_src[e];
+            HIP_TRY(hipMemcpyAsync(st.dev(r_out) + e_at * P, p.pages + e * P, p.page_len[e], hipMemcpyHostToDevice, s));
+        }
+        e_at += room_of(q);
+    }
+    st.host(page_off)[n] = e_at;
+    HIP_TRY(st.send(r_add, p.add_base + add_span.lo));
+    HIP_TRY(st.send_columns());
+    const PagedAppendArgs dv{st.dev(add_off), st.dev(add_len), n, P, p.window_min, p.window_max, st.dev(page_off), st.dev_opt(page_len),
+                             st.dev_opt(page_src), st.dev(n_pages), st.dev(in_done), st.dev(status), stage_bytes, st.dev(stage_off), st.dev(tail_src)};
+    if ((rc = paged_append_on_device(c, dv, st.dev(r_add), st.dev(r_out), st.dev(r_stage), rounds, (uint8_t*)d_scratch, slots, st.dev(r_work),
+                                     big, big || P > 131072u, s)))
+        return rc;
+    std::vector<uint32_t> resumed(n);                         // (v_len: S + A where the rounds took the stream's tables over, else 0)
+    HIP_TRY(hipMemcpyAsync(resumed.data(), paged_append_work(st.dev(r_work), n).v_len, 4ull * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(st.fetch_columns(page_len));
+    if (out_bytes) HIP_TRY(hipMemcpyAsync(c->pay.p, st.dev(r_out), out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t* h_len = st.host(page_len);
+    const uint32_t* h_src = st.host(page_src);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!go[i]) continue;
+        const AppendRec& q = recs[i];
+        p.status[i] = st.host(status)[i];
+        p.tail_src[i] = st.host(tail_src)[i];
+        const uint32_t k0 = lz4flex_paged::append_k0(q), got = st.host(n_pages)[i];
+        if (resumed[i] == 0u) continue;                       // (the tail page did not deliver: the stream is untouched)
+        p.n_pages[i] = k0 + got; p.in_done[i] = st.host(in_done)[i];
+        for (uint32_t j = 0; j < got; j++) {
+            const uint64_t e = q.first + k0 + j, r = st.host(page_off)[i] + j;
+            p.page_len[e] = h_len[r]; p.page_src[e] = h_src[r];
+            memcpy(p.pages + e * P, c->pay.p + r * P, h_len[r]);
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lz4flex_paged_append_work_size(uint32_t n) { return paged_append_work_bytes(n); }
+
+uint64_t lz4flex_paged_append_stage_bound(uint64_t sum_add_len, uint32_t n, uint32_t window_max) {
+    if (window_max == 0u) window_max = 65536u;
+    if (window_max < lz4flex_paged::PAGE_MIN || window_max > 0x80000000u) return 0;
+    return lz4flex_paged::append_stage_bound(sum_add_len, n, window_max);
+}
+
+int lz4flex_paged_append(lz4flex_ctx* ctx, const void* add_base, const uint64_t* add_off, const uint32_t* add_len, uint32_t n, uint32_t page_size,
+                         uint32_t window_min, uint32_t window_max, uint32_t max_rounds, void* pages, const uint64_t* page_off, uint32_t* page_len,
+                         uint32_t* page_src, uint32_t* n_pages, uint32_t* in_done, int32_t* status, void* stage, uint64_t stage_cap,
+                         uint64_t* stage_off, uint32_t* tail_src, void* scratch, uint64_t scratch_cap, void* work, int mem_kind, void* hip_stream) {
+    if (!paged_params(page_size, window_min, window_max)) return -LZ4FLEX_E_INVALID_ARG;
+    const MemKind k = classify_mem(mem_kind, LZ4FLEX_MEM_BIG_BLOCKS, LZ4FLEX_MEM_BIG_BLOCKS);     // (no LZ4FLEX_MEM_CHAINED)
+    if (k.where == Mem::Invalid) return -LZ4FLEX_E_INVALID_ARG;
+    if (n == 0) return 0;
+    if (!add_off || !add_len || !page_off || !page_len || !page_src || !n_pages || !in_done || !status || !stage_off || !tail_src)
+        return -LZ4FLEX_E_INVALID_ARG;
+    if (k.where == Mem::Device && (!work || !scratch || !stage)) return -LZ4FLEX_E_INVALID_ARG;
+    int rc;
+    if ((rc = ctx_resolve(&ctx))) return rc;                  // (lz4flex_decompress_batch_partial has the "debug_fail_next_batch" hook)
+    if (k.where == Mem::Device) {
+        const PagedAppendArgs a{add_off, add_len, n, page_size, window_min, window_max, page_off, page_len, page_src, n_pages, in_done, status,
+                                stage_cap, stage_off, tail_src};
+        return paged_append_on_device(ctx, a, (const uint8_t*)add_base, (uint8_t*)pages, (uint8_t*)stage, max_rounds, (uint8_t*)scratch, scratch_cap,
+                                      work, k.big, k.big, (hipStream_t)hip_stream);
+    }
+    const PagedAppendCall p{(const uint8_t*)add_base, add_off, add_len, n, page_size, window_min, window_max, max_rounds, (uint8_t*)pages, page_off,
+                            page_len, page_src, n_pages, in_done, status, stage_off, tail_src};
+    try {
+        return paged_append_on_host(ctx, p, k.big);
     } catch (...) { return -LZ4FLEX_E_NOMEM; }
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "paged_range.h" // the records of lz4flex_paged_read_ranges (plain integers, host and device)
+#include "paged_append.h" // the record of lz4flex_paged_append (plain integers, host and device)
 #include "lz4_route.h"  // PCD_PAIR_MAX_BLOCKS, the DISPATCH_* batch sizes and decode_route / encode_route: which kernel a batch takes (host-only, plain integers)
 
 #define LZ4FLEX_DEV_E_OUTPUT_TOO_SMALL 1
@@ -377,8 +378,41 @@ PagedReadWork paged_read_work(void* work, uint32_t m, uint32_t max_items);
 hipError_t launch_paged_read_locate(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s);
 hipError_t launch_paged_read_plan(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s);
 hipError_t launch_paged_read_verdict(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s);
+// lz4_paged_append.hip (lz4flex_paged_append): new bytes for any subset of n paged streams, planned on the device.  Every pointer is
+// device memory.  The launches, in order: locate (a record per stream; w.need: the stage bytes the scan sums), launch_packed_scan (w.slot:
+// align 1, the sizes are multiples of 64), emit (who is served; stage_off, tail_src; the tail items t_* of one partial decode, sink: the
+// stage; the copy items c_* of the new bytes), the partial decode and the copy (capi.cpp), resume (the verdict of the tail decode, the
+// rounds' state, round 1 in the PagedWork arrays and v_off / v_len, the in_off / in_len of the PagedArgs the rounds run with).
+struct PagedAppendArgs {
+    const uint64_t* add_off; const uint32_t* add_len; uint32_t n;
+    uint32_t page_size, window_min, window_max;
+    const uint64_t* page_off;                                       // n + 1, in entries
+    uint32_t* page_len; uint32_t* page_src;                         // per entry
+    uint32_t* n_pages; uint32_t* in_done; int32_t* status;          // per stream
+    uint64_t stage_cap; uint64_t* stage_off; uint32_t* tail_src;    // per stream
+};
+// the arrays a call keeps in the caller's `work` (paged_append_work_bytes(n) bytes, any 8-byte aligned address)
+struct PagedAppendWork {
+    void* paged;                                                    // the rounds' own work area (paged_work(paged, n))
+    lz4flex_paged::AppendRec* rec;                                  // n
+    uint64_t* need;                                                 // n: stage bytes
+    uint64_t* slot;                                                 // n + 1: their exclusive sums
+    uint64_t* tiles;                                                // the scan's tile sums
+    uint64_t* t_in; uint64_t* t_out; uint64_t* c_src; uint64_t* c_dst; uint64_t* v_off;                    // n each
+    uint32_t* t_len; uint32_t* t_tgt; uint32_t* t_olen; int32_t* t_st; uint32_t* c_len; uint32_t* v_len;   // n each
+};
+size_t paged_append_work_bytes(uint32_t n);
+PagedAppendWork paged_append_work(void* work, uint32_t n);
+hipError_t launch_paged_append_locate(const PagedAppendArgs& a, const PagedAppendWork& w, hipStream_t s);
+hipError_t launch_paged_append_emit(const PagedAppendArgs& a, const PagedAppendWork& w, hipStream_t s);
+hipError_t launch_paged_append_resume(const PagedAppendArgs& a, const PagedAppendWork& w, bool no_rounds, hipStream_t s);
 // lz4_packed.hip (lz4flex_decompress_batch_packed / lz4flex_compress_batch_packed): the output layout of a batch, computed on the device.
 constexpr uint32_t PACKED_SCAN_TILE = 1024u;         // the sizes one workgroup scans ("packed_scan_tile")
+// host helpers of the files that lay arrays out in a caller's `work` and launch a lane or a workgroup per item: an array's bytes rounded
+// up to 256, the tile words launch_packed_scan needs for n sizes, the workgroups of a launch (the kernels stride over what is left)
+inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+inline size_t scan_tiles(uint32_t n) { return (size_t)(((uint64_t)n + PACKED_SCAN_TILE - 1u) / PACKED_SCAN_TILE) + 2u; }
+inline uint32_t grid_of(uint64_t groups) { return (uint32_t)(groups < (1u << 22) ? (groups ? groups : 1u) : (1u << 22)); }
 enum : int {
     PACKED_SIZES_PREPENDED = 0,   // the LE u32 in front of every block; sh_off / sh_len receive the block behind it (in_len < 4: EXPECTED_ANOTHER_BYTE)
     PACKED_SIZES_GIVEN = 1,       // given[i]

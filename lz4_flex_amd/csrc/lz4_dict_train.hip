@@ -65,8 +65,6 @@ struct TrainWork {
     uint64_t* tiles;      // the scan's tile sums
     uint8_t* staging;     // CAP_MAX bytes
 };
-inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-inline size_t scan_tiles(uint32_t n) { return (size_t)(((uint64_t)n + PACKED_SCAN_TILE - 1u) / PACKED_SCAN_TILE) + 2u; }
 TrainWork train_work(void* work, uint32_t n) {
     uint8_t* p = (uint8_t*)work;
     TrainWork w;

@@ -181,9 +181,7 @@ __global__ void __launch_bounds__(256) packed_gather_kernel(const uint8_t* __res
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 static inline uint32_t tiles_of(uint32_t n) { return (uint32_t)(((uint64_t)n + PACKED_SCAN_TILE - 1u) / PACKED_SCAN_TILE); }
-static inline uint32_t grid_of(uint64_t items) { return (uint32_t)(items < MAX_GRID ? (items ? items : 1u) : MAX_GRID); }
 
 size_t packed_work_bytes(uint32_t n) {
     const size_t m = n;

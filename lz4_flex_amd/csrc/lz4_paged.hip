@@ -23,10 +23,6 @@
 
 namespace lz4flex_dev {
 
-namespace {
-inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-}  // namespace
-
 size_t paged_work_bytes(uint32_t n) {
     const size_t m = n;
     return packed_work_bytes(n) + 2u * up256(8u * m) + 7u * up256(4u * m);

@@ -31,11 +31,6 @@ using lz4flex_paged::REC_HEAD;
 using lz4flex_paged::REC_NO_STREAM;
 using lz4flex_paged::REC_SERVED;
 
-namespace {
-inline size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-inline size_t scan_tiles(uint32_t m) { return ((size_t)m + PACKED_SCAN_TILE - 1u) / PACKED_SCAN_TILE + 2u; }
-}  // namespace
-
 size_t paged_read_work_bytes(uint32_t m, uint32_t max_items) {
     const size_t r = m, t = max_items;
     return up256(sizeof(RangeRec) * r) + 2u * up256(8u * r) + 2u * up256(8u * (r + 1u)) + up256(8u * scan_tiles(m)) +
@@ -176,10 +171,6 @@ __global__ void __launch_bounds__(256) paged_read_verdict_kernel(PagedReadArgs a
     }
     if (lane == 0u) { a.status[r] = st; a.out_len[r] = st == 0 ? q.len : 0u; }
 }
-
-namespace {
-inline uint32_t grid_of(uint64_t groups) { return (uint32_t)(groups < (1u << 22) ? (groups ? groups : 1u) : (1u << 22)); }
-}  // namespace
 
 hipError_t launch_paged_read_locate(const PagedReadArgs& a, const PagedReadWork& w, hipStream_t s) {
     if (a.m == 0u) return hipSuccess;
